@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Refign align-and-refine hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs) and prints the line;
+`roofline`, `cpu_baseline` and `config.data_parallel.small_all_reduce_us` are null / absent there.  `--full` adds those
+measurements after the timed region (`--no-cpu` / `--no-roofline` leave one of them out).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N ranks (it re-executes itself under
 torch.distributed.run on 127.0.0.1, one rank per GPU; it refuses when the node has fewer than N GPUs) -- the form the
@@ -14,7 +18,7 @@ One "step" = one pass of the hot path over one batch of b=2 synthetic (target, r
 collective ("scaling": "weak").  The timed region is bracketed by a barrier + torch.cuda.synchronize() on both sides, the
 MAX over ranks is taken, rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+Extra objects on the line (--full only):
   roofline      the dominant kernel (patch-9 local correlation at level 1: C=128, 270x480 per image), algorithmic bytes
                 4*B*H*W*(2C+81) per launch / average launch duration measured live with HIP events on the launch stream.
   cpu_baseline  the reference's CPU path for the same step on a bounded sample (1 pair), timed on this box's host
@@ -58,8 +62,14 @@ def parse():
                     help="adapt_to_ref: True as refign_hrda_star.yaml:92 writes it: a coin per step, on heads the teacher sees "
                          "the reference image alone (no align, no refine).  Default off = every step aligns and refines (the "
                          "more expensive side of the coin, every step)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline kernel (HIP events), the CPU baseline and, with a "
+                         "process group, one small all-reduce; a plain run measures the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, fixed seeded samples "
+                         "of large arrays, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--cpu-sample", default="full", choices=["full", "small"],
                     help="cpu_baseline leg: one step at the full image size (default, ~1 min) or two reduced sizes + extrapolation")
     ap.add_argument("--cpu-baseline-full", action="store_true",
@@ -116,6 +126,9 @@ class AlignRefineKernels:
         warped, mask, cert = align_tail(self.logits_ref, self.f1 * 4.0, self.logvar)
         probs = refine(self.logits_trg, warped, mask, cert, gamma=0.25)
         return corr4, corr3, corr2, corr1, probs
+
+    def outputs(self, result):
+        return dict(zip(("corr4", "corr3", "corr2", "corr1", "probs"), result))
 
     # ---- dominant kernel for the roofline: level-1 local correlation (patch 9, fused ReLU + L2 norm) ----
     def roofline_launch(self):
@@ -208,6 +221,9 @@ REF_CFG = {  # the `model:` / `optimizer:` / `lr_scheduler:` sections of refign_
 
 
 PIPELINE_NEXT_BATCH = True
+# synthetic label blocks: the stride of the HRDA context features at full resolution (the half-size image's 1/32 map),
+# a multiple of the plain MiT stride 32
+LABEL_BLOCK = 64
 
 
 class RefignStep:
@@ -239,8 +255,11 @@ class RefignStep:
         self.b, self.H, self.W = b, H, W
         self.name = type(self).name.replace("1080x1920", f"{H}x{W}")     # the label says the size that ran
         g = torch.Generator(device="cpu").manual_seed(seed)
-        lbl = torch.randint(0, 19, (b, (H + 31) // 32, (W + 31) // 32), generator=g)
-        lbl = lbl.repeat_interleave(32, 1).repeat_interleave(32, 2)[:, :H, :W].contiguous()
+        # class blocks of LABEL_BLOCK px: the feature-distance loss averages over the windows of the backbone's last feature map
+        # whose majority class (share >= 0.75) is a "thing" class; with blocks smaller than the window no window qualifies
+        # and the loss is 0 / 0
+        lbl = torch.randint(0, 19, (b, -(-H // LABEL_BLOCK), -(-W // LABEL_BLOCK)), generator=g)
+        lbl = lbl.repeat_interleave(LABEL_BLOCK, 1).repeat_interleave(LABEL_BLOCK, 2)[:, :H, :W].contiguous()
         lbl[torch.rand(b, H, W, generator=g) < 0.05] = 255
         trg = torch.randn(b, 3, H, W, generator=g)
         ref = 0.8 * torch.roll(trg, (3, -5), (2, 3)) + 0.2 * torch.randn(b, 3, H, W, generator=g)
@@ -253,6 +272,17 @@ class RefignStep:
         # ImageNet encoder's features of the next source images are then computed while this step's mixed pass runs
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.precision == "bf16"):
             self.trainer.step(self.batch, next_batch=self.batch if PIPELINE_NEXT_BATCH else None)
+
+    def outputs(self, result):
+        """What the caller of a training step holds after it: the logged losses, the trainable parameters as the optimiser
+        left them and the gradients it stepped with (flattened in optimiser order; dump_outputs samples both at the same
+        positions)."""
+        out = dict(self.model.logged)
+        params = [p for g in self.trainer.optimizer.param_groups for p in g["params"]]
+        out["params"] = torch.cat([p.detach().reshape(-1).float() for p in params])
+        out["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                  for p in params])
+        return out
 
     # roofline kernel + CPU baseline are those of the align/refine kernel workload at the same image size
     def _kernels(self):
@@ -306,6 +336,9 @@ class RefignAlignRefine(RefignStep):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.precision == "bf16"):
             return torch.max(m._teacher_align_refine(trg, ref), dim=1)
 
+    def outputs(self, result):
+        return {"confidence": result.values, "pseudo_label": result.indices}
+
 
 class UAWarpCAlign:
     """K2 (BASELINE.json config 2: "UAWarpC align-only, MegaDepth config, 512x512 pairs"): AlignmentModel.forward
@@ -336,6 +369,9 @@ class UAWarpCAlign:
     def step(self):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.precision == "bf16"):
             return self.model(self.img_i, self.img_j)
+
+    def outputs(self, result):
+        return dict(zip(("flow", "uncertainty"), result))
 
     def _level1_features(self):
         if self._l1 is None:
@@ -389,6 +425,38 @@ class LauncherSelfTest:
     def step(self):
         self.x = self.x * 1.0001
 
+    def outputs(self, result):
+        return {"x": self.x}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(named, out_dir):
+    """--dump-outputs: each tensor of `named` as out_dir/<name>.npy, float64 kept, anything else as float32.  An array of more
+    than DUMP_SAMPLE elements is written as DUMP_SAMPLE of its flattened elements at sorted positions drawn by a generator
+    seeded with its length: the same positions in every run and every build (and in two arrays of one length)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in named.items():
+        if t is None:
+            continue
+        t = torch.as_tensor(t).detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(pos).to(flat.device))
+            a = flat.to(dt).cpu().numpy()
+        else:
+            a = t.to(dt).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
 
 def pmc_traffic():
     """HBM-side bytes per launch of the roofline kernel from the committed rocprofv3 PMC passes (FETCH_SIZE doubled per
@@ -438,8 +506,11 @@ def cpu_baseline(wl, args):
     algorithm restated on torch-CPU ops (oracle/cpu_align.py + the same module trees on CPU)."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     # threads: all host cores up to 32 -- the step is thousands of small ops, and with 256 OpenMP threads per op the
-    # fork/join overhead dominates (measured: >7 min for one step on the 256-core box vs tens of seconds at 32)
-    cores = min(os.cpu_count() or 1, 32)
+    # fork/join overhead dominates (measured: >7 min for one step on the 256-core box vs tens of seconds at 32).  The cores this
+    # process may run on, and no more than an OMP_NUM_THREADS the environment sets.
+    cores = min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 32)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))
     torch.set_num_threads(cores)
     os.environ["OMP_NUM_THREADS"] = str(cores)
     import cpu_align
@@ -467,8 +538,8 @@ def cpu_baseline(wl, args):
 
     def one_step(h, w):
         g = torch.Generator().manual_seed(99)
-        lbl = torch.randint(0, 19, (1, (h + 31) // 32, (w + 31) // 32), generator=g)
-        lbl = lbl.repeat_interleave(32, 1).repeat_interleave(32, 2)[:, :h, :w].contiguous()
+        lbl = torch.randint(0, 19, (1, -(-h // LABEL_BLOCK), -(-w // LABEL_BLOCK)), generator=g)
+        lbl = lbl.repeat_interleave(LABEL_BLOCK, 1).repeat_interleave(LABEL_BLOCK, 2)[:, :h, :w].contiguous()
         trg = torch.randn(1, 3, h, w, generator=g)
         batch = {"image_src": torch.randn(1, 3, h, w, generator=g), "semantic_src": lbl, "image_trg": trg,
                  "image_ref": 0.8 * torch.roll(trg, (1, -1), (2, 3)) + 0.2 * torch.randn(1, 3, h, w, generator=g)}
@@ -638,8 +709,10 @@ def main():
     tick("timed region")
     a0 = getattr(getattr(wl, "model", None), "_adapted_to_ref_steps", 0)
     t0 = time.perf_counter()
+    result = None
     for _ in range(args.steps):
-        wl.step()
+        result = None                # (the previous step's outputs are released before the next step, as before)
+        result = wl.step()
     barrier()
     dt = time.perf_counter() - t0
     adapted_in_timed = getattr(getattr(wl, "model", None), "_adapted_to_ref_steps", 0) - a0
@@ -648,9 +721,12 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(result), args.dump_outputs)
+    result = None
 
     small_ar_us = None
-    if dist is not None and not selftest and dev.type == "cuda" and args.backend == "nccl":
+    if args.full and dist is not None and not selftest and dev.type == "cuda" and args.backend == "nccl":
         # EVERY rank: what one small exchange costs from the step's stream (reported in config.data_parallel)
         probe_t = torch.zeros(512, device=dev)
         for _ in range(5):
@@ -665,7 +741,7 @@ def main():
         small_ar_us = round(e0.elapsed_time(e1) * 1e3 / 50, 1)
 
     roof = None
-    if not args.no_roofline and rank == 0 and not selftest:
+    if args.full and not args.no_roofline and rank == 0 and not selftest:
         # HIP events around EACH launch of the dominant kernel, on the stream it is launched on.  Two series of 20:
         # "spaced" -- every launch behind ~1 ms of an idle device (one spinning wave), which also hides the host's launch
         # latency: the kernel as it runs in the step, between other work (the rocprofv3 kernel trace of the timed steps
@@ -698,7 +774,7 @@ def main():
                 "algorithmic_bytes_per_launch": wl.roofline_bytes(), "rocprofv3_in_step": rocprof_in_step_us() if (rh, rw, rb) == (270, 480, 2) else None}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not selftest:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not selftest:
         cpu = cpu_baseline(wl, args)
 
     ranks_in_group = world

@@ -46,3 +46,17 @@ def test_world_size_mismatch_is_refused():
     r = _run(["--gpus", "2", "--workload", "launcher_selftest", "--backend", "gloo"],
              {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29999"})
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after the timed steps, what the last one computed as DIR/<name>.npy in float32; --steps sets the number of
+    timed steps (the self-test's state is multiplied once per warm-up and timed step) and the line carries ms_per_step."""
+    import numpy as np
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "launcher_selftest", "--backend", "gloo",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 3 and out["ms_per_step"] >= 0
+    x = np.load(tmp_path / "out" / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (1024,)
+    np.testing.assert_allclose(x, np.float32(1.0001) ** 4, rtol=1e-6)

@@ -2,13 +2,12 @@
 models/backbones/mix_transformer.py:445-479): Lightning-format `.ckpt` files ({'state_dict': ...}) written by the
 reference load into refign_amd with strict=True and the other way round, with identical tensors; the sub-module loaders
 strip the prefixes the reference strips (`alignment_head.`, `backbone.`, drop `head.*`)."""
+import json
 import os
-import sys
 
 import pytest
 import torch
 
-HAVE_REF = os.path.isdir("/root/reference/models")
 DIMS = [32, 64, 160, 256]
 OPT = {"class_path": "torch.optim.AdamW", "init_args": {"lr": 6e-5, "weight_decay": 0.01}}
 SCH = {"class_path": "helpers.lr_scheduler.LinearWarmupPolynomialLR",
@@ -52,28 +51,39 @@ def test_lightning_checkpoint_round_trip(tmp_path):
         ours(pretrained=path)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference checkout not present (authoring container only)")
-def test_checkpoints_interchange_with_the_reference(tmp_path):
-    """A checkpoint written from the REFERENCE's module tree loads here with strict=True, one written here loads into
-    the reference with strict=True, tensor for tensor."""
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_golden_step as G          # builds the reference model through tests/golden/_ref_import.py
-    import _ref_import as R
+def _reference_state_dict():
+    """The state_dict of the REFERENCE's HRDA model with closed-form weights (make_golden_step.run_reference(True)), rebuilt
+    from tests/golden/ref_checkpoint_hrda_mit_b0.json (make_golden_refcheck.py): keys in the reference's order, shapes and
+    dtypes as it has them, closed_form_fill values for the floating entries and the recorded values for the others."""
+    import types
     from fill import closed_form_fill
-    R.setup()
-    ref = G.run_reference(True)           # HRDA variant, closed-form weights
+    with open(os.path.join(os.path.dirname(__file__), "golden", "ref_checkpoint_hrda_mit_b0.json")) as f:
+        entries = json.load(f)
+    sd = {e["key"]: (torch.tensor(e["value"], dtype=getattr(torch, e["dtype"])) if "value" in e else
+                     torch.empty(e["shape"], dtype=getattr(torch, e["dtype"]))) for e in entries}
+    closed_form_fill(types.SimpleNamespace(state_dict=lambda: sd))
+    return sd
+
+
+def test_checkpoints_interchange_with_the_reference(tmp_path):
+    """A checkpoint written from the REFERENCE's module tree loads here with strict=True, one written here has what the
+    reference's loader (segmentation_model.py:421-436: load_state_dict(strict=True)) takes: the same keys, shapes and
+    dtypes, tensor for tensor."""
+    sr = _reference_state_dict()          # HRDA variant, closed-form weights
     path = str(tmp_path / "ref.ckpt")
-    torch.save({"state_dict": ref.state_dict()}, path)
+    torch.save({"state_dict": sr}, path)
     mine = ours(pretrained=path)
-    sr, sm = ref.state_dict(), mine.state_dict()
+    sm = mine.state_dict()
     assert set(sr) == set(sm), sorted(set(sr) ^ set(sm))[:10]
     assert all(sr[k].shape == sm[k].shape and torch.equal(sr[k], sm[k]) for k in sr)
-    # and back: perturb ours, save, load into the reference with its own loader
+    # and back: perturb ours, save, and load the file the way the reference's strict loader does
     with torch.no_grad():
         for p in mine.parameters():
             p.mul_(1.5)
     back = str(tmp_path / "ours.ckpt")
     torch.save({"state_dict": mine.state_dict()}, back)
-    ref.load_weights(back)
-    sr = ref.state_dict()
-    assert all(torch.equal(sr[k], v) for k, v in mine.state_dict().items())
+    loaded = torch.load(back)["state_dict"]
+    assert list(loaded) == list(mine.state_dict())
+    assert set(loaded) == set(sr), sorted(set(loaded) ^ set(sr))[:10]
+    assert all(loaded[k].shape == sr[k].shape and loaded[k].dtype == sr[k].dtype for k in sr)
+    assert all(torch.equal(loaded[k], v) for k, v in mine.state_dict().items())

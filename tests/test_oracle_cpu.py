@@ -1,5 +1,5 @@
-"""CPU: the oracle (oracle/) against the golden vectors captured from the reference, and -- when the compiled reference
-oracle/_ref is present -- against the reference C++ itself on fresh random inputs."""
+"""CPU: the oracle (oracle/) against the golden vectors captured from the reference, among them the reference C++ itself on
+seeded random inputs."""
 import numpy as np
 import pytest
 from conftest import golden, golden_names
@@ -20,25 +20,17 @@ def test_corr_oracle_matches_reference_golden(oracle, name):
 
 
 def test_corr_oracle_matches_compiled_reference(oracle):
-    import build_ref
-    ref = build_ref.load_prebuilt()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    import torch
-    rng = np.random.default_rng(7)
-    for (B, C, H, W, args) in [(2, 7, 19, 23, (1, 1, 9, 9, 0, 0, 1, 1, 1, 1, 1, 1)),
-                               (1, 3, 14, 15, (3, 3, 7, 5, 2, 1, 1, 2, 2, 1, 2, 1))]:
-        a = rng.standard_normal((B, C, H, W)).astype(np.float32)
-        b = rng.standard_normal((B, C, H, W)).astype(np.float32)
-        want = ref.forward(torch.from_numpy(a), torch.from_numpy(b), *args).numpy()
+    """The compiled reference correlation's forward and backward on two seeded random cases (a general and a strided,
+    dilated, padded one), captured in tests/golden/refcorr_random.npz by make_golden_refcheck.py."""
+    g = golden("refcorr_random")
+    for i in range(2):
+        a, b, args = g[f"in1_{i}"], g[f"in2_{i}"], [int(v) for v in g[f"args_{i}"]]
         kw = dict(kernel_size=args[0:2], patch_size=args[2:4], padding=args[4:6], dilation=args[6:8],
                   dilation_patch=args[8:10], stride=args[10:12])
-        np.testing.assert_array_equal(oracle.corr_forward(a, b, **kw), want)
-        go = rng.standard_normal(want.shape).astype(np.float32)
-        w1, w2 = ref.backward(torch.from_numpy(a), torch.from_numpy(b), torch.from_numpy(go), *args)
-        g1, g2 = oracle.corr_backward(a, b, go, **kw)
-        np.testing.assert_array_equal(g1, w1.numpy())
-        np.testing.assert_array_equal(g2, w2.numpy())
+        np.testing.assert_array_equal(oracle.corr_forward(a, b, **kw), g[f"out_{i}"])
+        g1, g2 = oracle.corr_backward(a, b, g[f"grad_out_{i}"], **kw)
+        np.testing.assert_array_equal(g1, g[f"grad_in1_{i}"])
+        np.testing.assert_array_equal(g2, g[f"grad_in2_{i}"])
 
 
 @pytest.mark.parametrize("name", golden_names("localcorr_"))

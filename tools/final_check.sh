@@ -6,17 +6,17 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/${1:-final}; mkdir -p $O
 RFN_TEST_REPORT_DIR=$O timeout 1800 python -m pytest tests -x -q -m gpu --tb=short 2>&1 | tail -40 > $O/pytest_gpu.txt
-timeout 600 python bench.py 2>/dev/null | tail -1 > $O/bench_n1.json
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --no-cpu --no-roofline 2>/dev/null | grep '^{"metric"' > $O/bench_torchrun_n1.json
-timeout 900 python bench.py --precision fp32 --no-cpu --steps 10 2>/dev/null | tail -1 > $O/bench_fp32_n1.json
-timeout 600 python bench.py --precision k5 --no-cpu 2>/dev/null | tail -1 > $O/bench_k5_n1.json
-timeout 600 python bench.py --adapt-to-ref --no-cpu 2>/dev/null | tail -1 > $O/bench_adapt_to_ref_n1.json
-timeout 600 python bench.py --workload uawarpc_align_512x512 --steps 50 --warmup 5 2>/dev/null | tail -1 > $O/bench_k2.json
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $O/bench_n1.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --full --no-cpu --no-roofline 2>/dev/null | grep '^{"metric"' > $O/bench_torchrun_n1.json
+timeout 900 python bench.py --precision fp32 --full --no-cpu --steps 10 2>/dev/null | tail -1 > $O/bench_fp32_n1.json
+timeout 600 python bench.py --precision k5 --full --no-cpu 2>/dev/null | tail -1 > $O/bench_k5_n1.json
+timeout 600 python bench.py --adapt-to-ref --full --no-cpu 2>/dev/null | tail -1 > $O/bench_adapt_to_ref_n1.json
+timeout 600 python bench.py --workload uawarpc_align_512x512 --full --steps 50 --warmup 5 2>/dev/null | tail -1 > $O/bench_k2.json
 timeout 600 python bench.py --workload refign_daformer_step_1080x1920 --height 512 --width 1024 --no-cpu --no-roofline 2>/dev/null | tail -1 > $O/bench_k3_daformer_512x1024.json
 timeout 300 python tools/step_timeline.py 2>&1 | grep "^step\|^(" > $O/step_timeline.txt
 timeout 300 python tools/step_timeline.py --adapt-to-ref 2>&1 | grep "^step\|^(" > $O/step_timeline_adapt_to_ref.txt
 { timeout 300 python tools/step_timeline.py --alone 2>&1 | grep "^step"; timeout 300 python tools/step_timeline.py --alone --adapt-to-ref 2>&1 | grep "^step"; } > $O/phases_alone_final.txt
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o bench --output-format csv -- python $R/bench.py --no-cpu --steps 6 --warmup 3 > /tmp/prof_bench.log 2>&1
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -o bench --output-format csv -- python $R/bench.py --full --no-cpu --steps 6 --warmup 3 > /tmp/prof_bench.log 2>&1
 cd $R
 grep '^{"metric"' /tmp/prof_bench.log > $O/bench_under_rocprof.json
 find /tmp/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/rocprofv3_bench_kernel_stats.csv \;
