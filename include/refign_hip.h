@@ -186,7 +186,7 @@ int rfn_align_tail_f32(const float* logits_ref, const float* flow_q, const float
  * Depthwise 3x3 convolution on channels-last maps -- the DWConv of every Mix-FFN block
  * (models/backbones/mix_transformer.py:96-103,556-568: nn.Conv2d(dim, dim, 3, 1, 1, groups=dim) between two token
  * transposes) and the dilated depthwise branches of the DAFormer ASPP (models/heads/daformer.py:46-62).
- * x, y, grad_y: (B,H,W,C) contiguous == the (B, N, C) token layout; dtype 0 = float32, 1 = bfloat16.
+ * x, y, grad_y: (B,H,W,C) contiguous == the (B, N, C) token layout; dtype 0 = float32, 1 = bfloat16, 2 = float16.
  * weight / grad_weight: TAP-MAJOR (9, C) float32 (= conv.weight.view(C, 9).t()); bias / grad_bias: (C) float32,
  * nullable.  Zero padding = dilation (same-size output).  flip = 1 applies the taps mirrored (that IS the
  * backward-data pass: grad_x = fwd(grad_y, weight, NULL, flip = 1)).  bwd_weight needs
@@ -229,6 +229,13 @@ int rfn_dwconv3x3_tri_bn_act_fwd(const void* x, const float* weight3, const floa
                                  const float* const* beta3, const double* sums3, float* const* running_mean3,
                                  float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
                                  const float* momentum3, int relu, rfn_stream_t stream);
+/* The same two passes on an fp16 input, fp16 outputs. */
+int rfn_dwconv3x3_tri_stats_f16(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C,
+                                int g, rfn_stream_t stream);
+int rfn_dwconv3x3_tri_bn_act_fwd_f16(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
+                                     const float* const* beta3, const double* sums3, float* const* running_mean3,
+                                     float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
+                                     const float* momentum3, int relu, rfn_stream_t stream);
 /* The same convolution (dilation 1) followed by GELU (exact erf) -- the DWConv + act of the Mix-FFN
  * (mix_transformer.py:99-101) in one pass: y_act = gelu(conv(x) + bias); y_pre (may be NULL) = the pre-activation,
  * which the backward of GELU needs and a gradient-free pass does not. */
@@ -242,7 +249,7 @@ int rfn_dwconv3x3_nhwc_bwd_weight(const void* x, const void* grad_y, float* grad
 /* ------------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim of a (rows, C) matrix, C <= 1024 -- the 213 LayerNorms of a MiT-B5 forward
  * (models/backbones/mix_transformer.py:135,188-207,234,369-419; eps 1e-6 in blocks/stage norms, 1e-5 in
- * patch-embed and spatial-reduction norms).  Statistics in fp32; activations float32 (dtype code 0) or bfloat16 (1),
+ * patch-embed and spatial-reduction norms).  Statistics in fp32; activations float32 (dtype code 0), bfloat16 (1) or float16 (2),
  * independently for input and output, so the residual stream can stay in bf16 with no separate cast passes.
  * gamma, beta, grad_gamma, grad_beta: (C) float32; mean, rstd: (rows) float32 saved by fwd for bwd.
  * bwd: grad_x has x's dtype; needs rfn_layernorm_bwd_workspace_bytes(C) bytes of workspace (deterministic two-stage
@@ -290,7 +297,7 @@ int rfn_uncertainty9_frontend_f16mm(const float* corr, const float* weights, flo
  * 100-186 and models/heads/daformer.py, segformer.py.)  Two uses on the training step, both formerly a library reduction followed by a separate gradient-accumulation add:
  *   - bias gradient of every token-wise Linear: x = grad_y (tokens, features), S = tokens (8 160 ... 259 200)
  *   - reduction of the split-T weight-gradient partials (refign_amd/linear.py): x = (S <= 64, N*K)
- * x dtype 0 = float32, 1 = bfloat16; n must be a multiple of 8.  accumulate != 0: out += sum (out is the parameter's
+ * x dtype 0 = float32, 1 = bfloat16, 2 = float16; n must be a multiple of 8.  accumulate != 0: out += sum (out is the parameter's
  * .grad view).  Tall inputs (S > 64) go through per-stripe partial sums in `workspace`
  * (rfn_sum_rows_workspace_bytes(S, n) bytes; may be NULL when that is 0) reduced in a fixed order: deterministic.
  * ---------------------------------------------------------------------------------------------------------- */
@@ -319,6 +326,8 @@ int rfn_multi_cast_chunk_elems(void);
 int rfn_multi_permute_chunk_elems(void);
 int rfn_multi_permute_cast_f32(const void* table, int nchunks, rfn_stream_t stream);
 int rfn_multi_cast_f32_bf16(const void* table, int nchunks, rfn_stream_t stream);
+/* The same table, fp16 copies (the fp16 recipe): bit-equal to tensor.to(torch.float16). */
+int rfn_multi_cast_f32_f16(const void* table, int nchunks, rfn_stream_t stream);
 /* EMA-teacher update of a whole parameter set in ONE launch (models/segmentation_model.py:676-689):
  * ema <- momentum * ema + (1 - momentum) * live, fp32 in place; table = nchunks x {float* ema, const float* live,
  * bf16* copy_or_NULL, long n} in device memory (chunks of at most rfn_multi_cast_chunk_elems() elements); where a chunk
@@ -328,6 +337,7 @@ int rfn_multi_ema_f32(const void* table, int nchunks, float momentum, rfn_stream
  * contiguous; table = ntiles x {const float* src, bf16* dst, int N, int K, int n0, int k0} (one T x T tile each, T = rfn_multi_transpose_tile(): 64
  * since ABI 3, 32 before) in device memory.  (The cached W^T operands of the input-gradient GEMMs, refreshed after optimiser / EMA updates.) */
 int rfn_multi_transpose_cast_f32_bf16(const void* table, int ntiles, rfn_stream_t stream);
+int rfn_multi_transpose_cast_f32_f16(const void* table, int ntiles, rfn_stream_t stream);
 int rfn_multi_transpose_tile(void);
 /* AdamW step of a whole parameter set in ONE launch (what the reference's optimizer section instantiates --
  * configs/cityscapes_darkzurich/refign_hrda_star.yaml:176-180, stepped by models/segmentation_model.py:252 --
@@ -336,13 +346,25 @@ int rfn_multi_transpose_tile(void);
  * ngroups (<= 8) x {lr, beta1, beta2, eps, weight_decay, 1 - beta1^t, sqrt(1 - beta2^t), 1 - beta1, 1 - beta2} for this
  * step (the derived values computed in double by the host, as torch does). */
 int rfn_multi_adamw_f32(const void* table, int nchunks, const float* group_args, int ngroups, rfn_stream_t stream);
+/* Loss scaling of the fp16 recipe (torch.amp.GradScaler semantics), no host synchronisation: scale (1 float), found_inf (1 float, zeroed
+   by the caller before the unscale), growth_tracker (1 int) and step (the optimiser's step count, 1 float) are device memory.
+   rfn_amp_unscale_f32: grads (16-byte aligned fp32) *= 1 / scale in place, found_inf = 1 if any was inf / NaN.
+   rfn_multi_adamw_amp_f32: rfn_multi_adamw_f32's table; group_args HOST doubles, 7 per group {lr, beta1, beta2, eps, weight_decay,
+   1 - beta1, 1 - beta2}; does nothing when *found_inf != 0, else the AdamW update of step *step + 1.
+   rfn_amp_update_scale: torch._amp_update_scale_ (scale *= backoff on inf; *= growth after growth_interval clean steps) and, when the
+   step was taken, *step += 1 (step may be NULL). */
+int rfn_amp_unscale_f32(float* grads, long n, const float* scale, float* found_inf, rfn_stream_t stream);
+int rfn_multi_adamw_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
+                            const float* step, rfn_stream_t stream);
+int rfn_amp_update_scale(float* scale, int* growth_tracker, const float* found_inf, float* step, float growth_factor,
+                         float backoff_factor, int growth_interval, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Multi-resolution fusion front end of the decode heads (DAFormerHead.forward, models/heads/daformer.py:205-222;
  * SegFormerHead.forward, models/heads/segformer.py:86-104): bilinear up-sampling (align_corners=False) of up to four
  * embedded stage maps to (H, W) and their channel concatenation, one pass, channels-last output (n, H, W, sum C_l).
  * src_l: TOKEN maps (n, hs[l]*ws[l], cs[l]) contiguous (= channels-last), cs[l] % 8 == 0; a level that already has
- * (H, W) is copied.  hs / ws / cs: HOST arrays of nlev ints.  dtype 0 = float32, 1 = bfloat16 (fp32 blend).
+ * (H, W) is copied.  hs / ws / cs: HOST arrays of nlev ints.  dtype 0 = float32, 1 = bfloat16, 2 = float16 (fp32 blend).
  * ---------------------------------------------------------------------------------------------------------- */
 int rfn_upsample_concat_nhwc(const void* src0, const void* src1, const void* src2, const void* src3, const int* hs,
                              const int* ws, const int* cs, int nlev, void* out, int n, int H, int W, int dtype,
@@ -485,6 +507,9 @@ int rfn_split3_cat_bf16(const float* const* parts, const long* strides, const in
  * ---------------------------------------------------------------------------------------------------------- */
 int rfn_ffn_fc1_dw_gelu_bf16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
                              int views, int H, int W, int C, int HID, rfn_stream_t stream);
+/* The same with fp16 x, w1, b1 and a (fp16 MFMA). */
+int rfn_ffn_fc1_dw_gelu_f16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
+                            int views, int H, int W, int C, int HID, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Training-mode BatchNorm2d (+ ReLU) on channels-last 16-bit tensors viewed as (T = B*H*W, C): the norm + activation of

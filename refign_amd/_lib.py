@@ -47,7 +47,9 @@ SIGNATURES = {
     "rfn_dwconv3x3_nhwc_stats": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "rfn_dwconv3x3_tri_usable": (c_int, [c_int] * 5),
     "rfn_dwconv3x3_tri_stats": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
+    "rfn_dwconv3x3_tri_stats_f16": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
     "rfn_dwconv3x3_tri_bn_act_fwd": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p]),
+    "rfn_dwconv3x3_tri_bn_act_fwd_f16": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p]),
     "rfn_dwconv3x3_bn_act_nhwc_fwd": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
     "rfn_dwconv3x3_nhwc_fwd_stats": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "rfn_dwconv3x3_nhwc_fwd": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
@@ -76,6 +78,11 @@ SIGNATURES = {
     "rfn_multi_ema_f32": (c_int, [c_void_p, c_int, c_float, c_void_p]),
     "rfn_multi_transpose_cast_f32_bf16": (c_int, [c_void_p, c_int, c_void_p]),
     "rfn_multi_adamw_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "rfn_multi_cast_f32_f16": (c_int, [c_void_p, c_int, c_void_p]),
+    "rfn_multi_transpose_cast_f32_f16": (c_int, [c_void_p, c_int, c_void_p]),
+    "rfn_amp_unscale_f32": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p]),
+    "rfn_multi_adamw_amp_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "rfn_amp_update_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p]),
     "rfn_gemm_nt": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p] + [ctypes.c_long] * 6 + [c_int, c_void_p]),
     "rfn_conv2d_nhwc": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 10 + [ctypes.c_long, ctypes.c_long, c_int,
                                                                                        c_void_p]),
@@ -103,6 +110,7 @@ SIGNATURES = {
     "rfn_split3_bf16": (c_int, [c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_int, c_int,
                                 c_int, c_void_p]),
     "rfn_ffn_fc1_dw_gelu_bf16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "rfn_ffn_fc1_dw_gelu_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "rfn_split3_cat_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rfn_upsample_ce": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
     "rfn_bn_stats_fwd": (c_int, [c_void_p] * 2 + [ctypes.c_long, c_int, c_int, c_void_p]),

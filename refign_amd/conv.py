@@ -99,7 +99,7 @@ class Conv2d(nn.Conv2d):
 # accumulated into the flat buffer) + one scatter copy; the library's convolution backward for this shape is five
 # launches of its own plus per-call zero-fill / cast tensor ops (~85 us of GPU time per layer per pass, 240 per step).
 # ---------------------------------------------------------------------------------------------------------------------
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def _split32():

@@ -1,5 +1,6 @@
 // refign_amd/csrc/common.h -- shared helpers for the gfx950 kernels (error reporting, launch checks, math).
 #pragma once
+#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -40,6 +41,44 @@ __device__ __forceinline__ unsigned bf16x2_bits(float lo, float hi) {
   typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
   const bf16x2 v = {(__bf16)lo, (__bf16)hi};
   return __builtin_bit_cast(unsigned, v);
+}
+
+// fp32 -> fp16 bits, round to nearest even (torch's .to(torch.float16): overflow -> inf, NaN stays NaN), and back
+__device__ __forceinline__ unsigned f16_bits(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+__device__ __forceinline__ unsigned f16x2_bits(float lo, float hi) {
+  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+  const f16x2 v = {(_Float16)lo, (_Float16)hi};
+  return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+__device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+
+// Activation dtype codes of the C ABI: 0 = float32, 1 = bfloat16, 2 = float16.  dt_one / dt_pair call fn with a DT<T> tag
+// per code (dt_pair: the pairs that meet in one call -- equal codes, or one of them fp32; bf16 and fp16 never mix) and return
+// RFN_EINVAL with `what` in the message for anything else.
+template <typename T>
+struct DT {
+  using type = T;
+};
+template <typename Fn>
+inline int dt_one(int a, const char* what, Fn&& fn) {
+  switch (a) {
+    case 0: return fn(DT<float>{});
+    case 1: return fn(DT<__hip_bfloat16>{});
+    case 2: return fn(DT<_Float16>{});
+  }
+  return fail(RFN_EINVAL, "%s: dtype code must be 0 (f32), 1 (bf16) or 2 (f16) (got %d)", what, a);
+}
+template <typename Fn>
+inline int dt_pair(int a, int b, const char* what, Fn&& fn) {
+  if (a == 0 && b == 0) return fn(DT<float>{}, DT<float>{});
+  if (a == 0 && b == 1) return fn(DT<float>{}, DT<__hip_bfloat16>{});
+  if (a == 1 && b == 0) return fn(DT<__hip_bfloat16>{}, DT<float>{});
+  if (a == 1 && b == 1) return fn(DT<__hip_bfloat16>{}, DT<__hip_bfloat16>{});
+  if (a == 0 && b == 2) return fn(DT<float>{}, DT<_Float16>{});
+  if (a == 2 && b == 0) return fn(DT<_Float16>{}, DT<float>{});
+  if (a == 2 && b == 2) return fn(DT<_Float16>{}, DT<_Float16>{});
+  return fail(RFN_EINVAL, "%s: dtype codes (%d, %d): each 0 (f32), 1 (bf16) or 2 (f16), bf16 and f16 not mixed", what, a, b);
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

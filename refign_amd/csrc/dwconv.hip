@@ -13,7 +13,7 @@
 // all; lanes run along C (16-byte vectors: 8 bf16 or 4 fp32 channels per lane => a wave reads 1 KiB contiguous), each
 // thread produces 4 consecutive pixels along W and keeps its 9 x VEC weights in registers.  Halo re-reads between
 // neighbouring threads/blocks are served by L1/L2.  Accumulation is fp32; weights/bias/weight-gradients stay fp32
-// (master precision) while activations may be bf16.
+// (master precision) while activations may be bf16 or fp16.
 //   forward       y[b,h,w,c]  = bias[c] + sum_{ky,kx} wgt[c,ky,kx] * x[b, h+(ky-1)d, w+(kx-1)d, c]
 //   backward-data dx           = same stencil over gy with the taps flipped, no bias
 //   backward-wgt  dw[c,ky,kx]  = sum_{b,h,w} gy[b,h,w,c] * x[b, h+(ky-1)d, w+(kx-1)d, c];   db[c] = sum gy
@@ -46,6 +46,7 @@ struct VecIO<float> {
   __device__ static void store(float* p, const float (&v)[4]) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   }
+  __device__ static float rnd(float v) { return v; }                  // the value a store of v reads back as
 };
 
 template <>
@@ -82,6 +83,35 @@ struct VecIO<__hip_bfloat16> {
     t.x = pack(v[0], v[1]); t.y = pack(v[2], v[3]); t.z = pack(v[4], v[5]); t.w = pack(v[6], v[7]);
     *reinterpret_cast<uint4*>(p) = t;
   }
+  __device__ static float rnd(float v) { return __uint_as_float(bf16_bits(v) << 16); }
+};
+
+// fp16 (the reference's `precision: 16` recipe): the bf16 layout, IEEE half conversions
+template <>
+struct VecIO<_Float16> {
+  static constexpr int N = 8;
+  typedef uint4 Raw;
+  __device__ static Raw load_raw(const _Float16* p) { return *reinterpret_cast<const uint4*>(p); }
+  __device__ static void unpack(const Raw& t, float (&v)[8]) {
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[2 * i] = f16_lo(w[i]);
+      v[2 * i + 1] = f16_hi(w[i]);
+    }
+  }
+  typedef float Pair __attribute__((ext_vector_type(2)));
+  __device__ static void unpack2(const Raw& t, Pair (&v)[4]) {
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = Pair{f16_lo(w[i]), f16_hi(w[i])};
+  }
+  __device__ static void load(const _Float16* p, float (&v)[8]) { unpack(load_raw(p), v); }
+  __device__ static unsigned pack(float lo, float hi) { return f16x2_bits(lo, hi); }
+  __device__ static void store(_Float16* p, const float (&v)[8]) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7]));
+  }
+  __device__ static float rnd(float v) { return (float)(_Float16)v; }
 };
 
 // K5: e4m3 activations, 8 channels per lane (8-byte vectors); dequantisation / quantisation scales are kernel arguments
@@ -290,7 +320,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
           // the statistics were taken of the ROUNDED convolution result (what the unfused path stores and reads back)
 #pragma unroll
           for (int i = 0; i < V; ++i) {
-            const float r = sizeof(T) == 2 ? __uint_as_float(bf16_bits(o[i]) << 16) : o[i];
+            const float r = VecIO<T>::rnd(o[i]);
             const float z = fmaf(r, bsc[i], bsh[i]);
             o[i] = (bn.relu && z <= 0.f) ? 0.f : z;
           }
@@ -299,7 +329,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
         if constexpr (STATS != 0) {
 #pragma unroll
           for (int i = 0; i < V; ++i) {
-            const float r = sizeof(T) == 2 ? __uint_as_float(bf16_bits(o[i]) << 16) : o[i];
+            const float r = VecIO<T>::rnd(o[i]);
             st0[i] += r;
             st1[i] = fmaf(r, r, st1[i]);
           }
@@ -604,11 +634,11 @@ struct TriArgs {
   float* running_mean[3];    // may be null
   float* running_var[3];
   float eps[3], momentum[3];
-  __hip_bfloat16* y[3];
+  void* y[3];                // bf16 or fp16, the input's type
   int relu, ablate;
 };
 
-template <int M, int MODE>
+template <int M, int MODE, typename T>
 __device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img, float* __restrict__ scratch, const TriArgs& a,
                                            int b, int B, int H, int W, int C, int g, int py, int px, int Hs, int Ws, int c0, int cv,
                                            int pl, bool first_block, bool stat_block) {
@@ -665,7 +695,7 @@ __device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img
         uint4 raw = *reinterpret_cast<const uint4*>(rowp + min(max(xx, 0), Ws - 1) * kTriPitch);
         if (!(rowok && xx >= 0 && xx < Ws)) raw = make_uint4(0u, 0u, 0u, 0u);
         f2 v[4];
-        VecIO<__hip_bfloat16>::unpack2(raw, v);
+        VecIO<T>::unpack2(raw, v);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           const int d = o - p;                           // column offset of this load relative to output p, + M
@@ -682,9 +712,9 @@ __device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img
       float o[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        // the unfused path stores the convolution result in bf16 before the statistics / BatchNorm read it back
-        o[2 * i] = __uint_as_float(bf16_bits(acc[p][i].x) << 16);
-        o[2 * i + 1] = __uint_as_float(bf16_bits(acc[p][i].y) << 16);
+        // the unfused path stores the convolution result in 16 bits before the statistics / BatchNorm read it back
+        o[2 * i] = VecIO<T>::rnd(acc[p][i].x);
+        o[2 * i + 1] = VecIO<T>::rnd(acc[p][i].y);
       }
       if constexpr (MODE == 0) {
 #pragma unroll
@@ -698,7 +728,7 @@ __device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img
           const float z = fmaf(o[i], bsc[i], bsh[i]);
           o[i] = (a.relu && z <= 0.f) ? 0.f : z;
         }
-        VecIO<__hip_bfloat16>::store(a.y[k] + (((size_t)b * H + py + g * ys) * W + px + g * (x0 + p)) * C + c, o);
+        VecIO<T>::store(reinterpret_cast<T*>(a.y[k]) + (((size_t)b * H + py + g * ys) * W + px + g * (x0 + p)) * C + c, o);
       }
     }
   }
@@ -732,8 +762,8 @@ __device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img
   }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void dwconv3x3_tri_kernel(const __hip_bfloat16* __restrict__ x, TriArgs a, int B, int H, int W,
+template <int MODE, typename T>
+__global__ __launch_bounds__(256, 2) void dwconv3x3_tri_kernel(const T* __restrict__ x, TriArgs a, int B, int H, int W,
                                                                int C, int g, int nitems) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kTriMaxPix * kTriPitch + kTriScratch];
   // block L runs on XCD L % 8 (the dispatcher's round-robin; speed only): the two halves of item i are blocks 8 apart on one XCD
@@ -743,7 +773,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_tri_kernel(const __hip_bfloa
   const int py = phase / g, px = phase % g;
   const int Hs = (H - py + g - 1) / g, Ws = (W - px + g - 1) / g;
   const int cv = threadIdx.x & 3, pl = threadIdx.x >> 2;
-  const __hip_bfloat16* xb = x + (size_t)b * H * W * C + c0 + cv * 8;
+  const T* xb = x + (size_t)b * H * W * C + c0 + cv * 8;
   const int npix = Hs * Ws;
   // all of the thread's loads first (up to 15 in flight), then the LDS writes
   constexpr int NL = (kTriMaxPix + 63) / 64;
@@ -762,10 +792,10 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_tri_kernel(const __hip_bfloa
   float* scratch = reinterpret_cast<float*>(lds + kTriMaxPix * kTriPitch);
   const bool first_block = item == 0 && half == 0, stat_block = phase == 0 && b == 0;
   if (a.ablate & 2) return;
-  tri_branch<1, MODE>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
+  tri_branch<1, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
   if (a.ablate & 4) return;
-  tri_branch<2, MODE>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
-  tri_branch<3, MODE>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
+  tri_branch<2, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
+  tri_branch<3, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
 }
 
 static int tri_domain(int B, int H, int W, int C, int g) {
@@ -773,38 +803,25 @@ static int tri_domain(int B, int H, int W, int C, int g) {
          (long)g * g * (C / 64) * B < (1L << 26);
 }
 
-}  // namespace rfn
-
-using namespace rfn;
-
-extern "C" {
-// Three dilated depthwise 3x3 branches (dilations g, 2 g, 3 g; padding = dilation) of one bf16 NHWC input in ONE pass each:
-//   rfn_dwconv3x3_tri_stats        sums3 [3][2 C + 1] doubles <- (sum, sum of squares, rows) of the three rounded results;
-//   rfn_dwconv3x3_tri_bn_act_fwd   y[k] = act(bn_k(conv_k(x))) with the statistics in sums3 (a SyncBatchNorm all-reduces them in
-//                                  between).  weight3: [3][9][C] tap-major fp32, bias3: [3][C] or NULL; gamma / beta / running_mean /
-//                                  running_var / y / eps / momentum: HOST arrays of 3.  C % 64 == 0, ceil(H / g) ceil(W / g) <= 944.
-// rfn_dwconv3x3_tri_usable: 1 when a shape is inside that domain.
-int rfn_dwconv3x3_tri_usable(int B, int H, int W, int C, int g) { return tri_domain(B, H, W, C, g); }
-
-int rfn_dwconv3x3_tri_stats(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C, int g,
-                            rfn_stream_t stream) {
+template <typename T>
+static int tri_stats(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C, int g,
+                     hipStream_t st) {
   RFN_REQUIRE(x && weight3 && sums3, "rfn_dwconv3x3_tri_stats: null pointer");
   RFN_REQUIRE(tri_domain(B, H, W, C, g), "rfn_dwconv3x3_tri_stats: B=%d H=%d W=%d C=%d g=%d outside the kernel's domain", B, H, W, C, g);
-  hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums3, 3 * (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
   TriArgs a{};
   a.w = weight3, a.bias = bias3, a.sums = sums3;
   a.ablate = 0;
   const long nitems = (long)g * g * (C / 64) * B;
-  hipLaunchKernelGGL((dwconv3x3_tri_kernel<0>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, st, (const __hip_bfloat16*)x, a,
+  hipLaunchKernelGGL((dwconv3x3_tri_kernel<0, T>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, st, (const T*)x, a,
                      B, H, W, C, g, (int)nitems);
   return check_launch("dwconv3x3_tri_kernel<stats>");
 }
 
-int rfn_dwconv3x3_tri_bn_act_fwd(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
-                                 const float* const* beta3, const double* sums3, float* const* running_mean3,
-                                 float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
-                                 const float* momentum3, int relu, rfn_stream_t stream) {
+template <typename T>
+static int tri_apply(const void* x, const float* weight3, const float* bias3, const float* const* gamma3, const float* const* beta3,
+                     const double* sums3, float* const* running_mean3, float* const* running_var3, void* const* y3, int B, int H,
+                     int W, int C, int g, const float* eps3, const float* momentum3, int relu, hipStream_t st) {
   RFN_REQUIRE(x && weight3 && sums3 && y3 && gamma3 && beta3 && running_mean3 && running_var3 && eps3 && momentum3,
               "rfn_dwconv3x3_tri_bn_act_fwd: null pointer");
   RFN_REQUIRE(tri_domain(B, H, W, C, g), "rfn_dwconv3x3_tri_bn_act_fwd: B=%d H=%d W=%d C=%d g=%d outside the kernel's domain", B, H, W, C, g);
@@ -814,12 +831,52 @@ int rfn_dwconv3x3_tri_bn_act_fwd(const void* x, const float* weight3, const floa
   for (int k = 0; k < 3; ++k) {
     RFN_REQUIRE(y3[k], "rfn_dwconv3x3_tri_bn_act_fwd: null output %d", k);
     a.gamma[k] = gamma3[k], a.beta[k] = beta3[k], a.running_mean[k] = running_mean3[k], a.running_var[k] = running_var3[k];
-    a.eps[k] = eps3[k], a.momentum[k] = momentum3[k], a.y[k] = (__hip_bfloat16*)y3[k];
+    a.eps[k] = eps3[k], a.momentum[k] = momentum3[k], a.y[k] = y3[k];
   }
   const long nitems = (long)g * g * (C / 64) * B;
-  hipLaunchKernelGGL((dwconv3x3_tri_kernel<1>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, (hipStream_t)stream,
-                     (const __hip_bfloat16*)x, a, B, H, W, C, g, (int)nitems);
+  hipLaunchKernelGGL((dwconv3x3_tri_kernel<1, T>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, st, (const T*)x, a, B, H,
+                     W, C, g, (int)nitems);
   return check_launch("dwconv3x3_tri_kernel<apply>");
+}
+
+}  // namespace rfn
+
+using namespace rfn;
+
+extern "C" {
+// Three dilated depthwise 3x3 branches (dilations g, 2 g, 3 g; padding = dilation) of one bf16 NHWC input in ONE pass each
+// (the _f16 forms: an fp16 input, fp16 outputs):
+//   rfn_dwconv3x3_tri_stats        sums3 [3][2 C + 1] doubles <- (sum, sum of squares, rows) of the three rounded results;
+//   rfn_dwconv3x3_tri_bn_act_fwd   y[k] = act(bn_k(conv_k(x))) with the statistics in sums3 (a SyncBatchNorm all-reduces them in
+//                                  between).  weight3: [3][9][C] tap-major fp32, bias3: [3][C] or NULL; gamma / beta / running_mean /
+//                                  running_var / y / eps / momentum: HOST arrays of 3.  C % 64 == 0, ceil(H / g) ceil(W / g) <= 944.
+// rfn_dwconv3x3_tri_usable: 1 when a shape is inside that domain.
+int rfn_dwconv3x3_tri_usable(int B, int H, int W, int C, int g) { return tri_domain(B, H, W, C, g); }
+
+int rfn_dwconv3x3_tri_stats(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C, int g,
+                            rfn_stream_t stream) {
+  return tri_stats<__hip_bfloat16>(x, weight3, bias3, sums3, B, H, W, C, g, (hipStream_t)stream);
+}
+
+int rfn_dwconv3x3_tri_stats_f16(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C,
+                                int g, rfn_stream_t stream) {
+  return tri_stats<_Float16>(x, weight3, bias3, sums3, B, H, W, C, g, (hipStream_t)stream);
+}
+
+int rfn_dwconv3x3_tri_bn_act_fwd(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
+                                 const float* const* beta3, const double* sums3, float* const* running_mean3,
+                                 float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
+                                 const float* momentum3, int relu, rfn_stream_t stream) {
+  return tri_apply<__hip_bfloat16>(x, weight3, bias3, gamma3, beta3, sums3, running_mean3, running_var3, y3, B, H, W, C, g, eps3,
+                                   momentum3, relu, (hipStream_t)stream);
+}
+
+int rfn_dwconv3x3_tri_bn_act_fwd_f16(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
+                                     const float* const* beta3, const double* sums3, float* const* running_mean3,
+                                     float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
+                                     const float* momentum3, int relu, rfn_stream_t stream) {
+  return tri_apply<_Float16>(x, weight3, bias3, gamma3, beta3, sums3, running_mean3, running_var3, y3, B, H, W, C, g, eps3, momentum3,
+                             relu, (hipStream_t)stream);
 }
 
 
@@ -831,26 +888,26 @@ int rfn_dwconv3x3_nhwc_fwd(const void* x, const float* weight, const float* bias
     RFN_REQUIRE(C % 4 == 0, "rfn_dwconv3x3_nhwc_fwd: C must be a multiple of 4 for f32 (got %d)", C);
     return launch_fwd<float>(x, weight, bias, y, B, H, W, C, dilation, flip, (hipStream_t)stream);
   }
-  if (dtype == 1) {
-    RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd: C must be a multiple of 8 for bf16 (got %d)", C);
-    return launch_fwd<__hip_bfloat16>(x, weight, bias, y, B, H, W, C, dilation, flip, (hipStream_t)stream);
-  }
-  return fail(RFN_EINVAL, "rfn_dwconv3x3_nhwc_fwd: dtype must be 0 (f32) or 1 (bf16)");
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd: C must be a multiple of 8 for 16-bit activations (got %d)", C);
+  return dt_one(dtype, "rfn_dwconv3x3_nhwc_fwd", [&](auto t) {
+    return launch_fwd<typename decltype(t)::type>(x, weight, bias, y, B, H, W, C, dilation, flip, (hipStream_t)stream);
+  });
 }
 
-// rfn_dwconv3x3_nhwc_fwd (bf16) that also leaves the BatchNorm statistics of its result in `sums` (2 C + 1 doubles: sum,
+// rfn_dwconv3x3_nhwc_fwd (bf16 / f16) that also leaves the BatchNorm statistics of its result in `sums` (2 C + 1 doubles: sum,
 // sum of squares, rows -- the buffer of rfn_bn_stats_fwd, zeroed here): the statistics pass over the result is not needed
 int rfn_dwconv3x3_nhwc_fwd_stats(const void* x, const float* weight, const float* bias, void* y, double* sums, int B, int H,
                                  int W, int C, int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && y && sums, "rfn_dwconv3x3_nhwc_fwd_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats: bad size");
-  RFN_REQUIRE(dtype == 1 && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats: bf16 (dtype 1), C %% 8 == 0");
+  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st);
+  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st)
+                    : launch_fwd_stats<_Float16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st);
 }
 
-// Gradient-free depthwise 3x3 -> BatchNorm(batch statistics) -> ReLU in two passes over the INPUT (bf16):
+// Gradient-free depthwise 3x3 -> BatchNorm(batch statistics) -> ReLU in two passes over the INPUT (bf16 / f16):
 //   rfn_dwconv3x3_nhwc_stats        sums <- (sum, sum of squares, rows) of the rounded convolution result, nothing stored;
 //   rfn_dwconv3x3_bn_act_nhwc_fwd   y = act(bn(conv(x))) with the statistics in `sums` (between the two a SyncBatchNorm
 //                                   all-reduces `sums`); running_mean / running_var (may be NULL) updated as rfn_bn_apply_fwd.
@@ -858,10 +915,11 @@ int rfn_dwconv3x3_nhwc_stats(const void* x, const float* weight, const float* bi
                              int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && sums, "rfn_dwconv3x3_nhwc_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats: bad size");
-  RFN_REQUIRE(dtype == 1 && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: bf16 (dtype 1), C %% 8 == 0");
+  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st);
+  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st)
+                    : launch_fwd_stats<_Float16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st);
 }
 
 int rfn_dwconv3x3_bn_act_nhwc_fwd(const void* x, const float* weight, const float* bias, const float* gamma, const float* beta,
@@ -869,8 +927,12 @@ int rfn_dwconv3x3_bn_act_nhwc_fwd(const void* x, const float* weight, const floa
                                   int C, int dilation, float eps, float momentum, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && sums && y, "rfn_dwconv3x3_bn_act_nhwc_fwd: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_bn_act_nhwc_fwd: bad size");
-  RFN_REQUIRE(dtype == 1 && C % 8 == 0 && (relu == 0 || relu == 1), "rfn_dwconv3x3_bn_act_nhwc_fwd: bf16, C %% 8 == 0, relu 0 / 1");
+  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0 && (relu == 0 || relu == 1),
+              "rfn_dwconv3x3_bn_act_nhwc_fwd: bf16 / f16, C %% 8 == 0, relu 0 / 1");
   BnEpi bn{gamma, beta, running_mean, running_var, eps, momentum, relu};
+  if (dtype == 2)
+    return launch_fwd_stats<_Float16, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
+                                               (hipStream_t)stream, bn);
   return launch_fwd_stats<__hip_bfloat16, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
                                                    (hipStream_t)stream, bn);
 }
@@ -883,11 +945,10 @@ int rfn_dwconv3x3_gelu_nhwc_fwd(const void* x, const float* weight, const float*
     RFN_REQUIRE(C % 4 == 0, "rfn_dwconv3x3_gelu_nhwc_fwd: C must be a multiple of 4 for f32 (got %d)", C);
     return launch_fwd_gelu<float>(x, weight, bias, y_pre, y_act, B, H, W, C, (hipStream_t)stream);
   }
-  if (dtype == 1) {
-    RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_gelu_nhwc_fwd: C must be a multiple of 8 for bf16 (got %d)", C);
-    return launch_fwd_gelu<__hip_bfloat16>(x, weight, bias, y_pre, y_act, B, H, W, C, (hipStream_t)stream);
-  }
-  return fail(RFN_EINVAL, "rfn_dwconv3x3_gelu_nhwc_fwd: dtype must be 0 (f32) or 1 (bf16)");
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_gelu_nhwc_fwd: C must be a multiple of 8 for 16-bit activations (got %d)", C);
+  return dt_one(dtype, "rfn_dwconv3x3_gelu_nhwc_fwd", [&](auto t) {
+    return launch_fwd_gelu<typename decltype(t)::type>(x, weight, bias, y_pre, y_act, B, H, W, C, (hipStream_t)stream);
+  });
 }
 
 int rfn_dwconv3x3_gelu_nhwc_fwd_f8(const void* x8, const float* weight, const float* bias, void* y8, int B, int H, int W, int C,
@@ -911,12 +972,11 @@ int rfn_dwconv3x3_nhwc_bwd_weight(const void* x, const void* grad_y, float* grad
     return launch_bwd_weight<float>(x, grad_y, grad_weight, grad_bias, (float*)workspace, B, H, W, C, dilation,
                                     flags, (hipStream_t)stream);
   }
-  if (dtype == 1) {
-    RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_bwd_weight: C must be a multiple of 8 for bf16");
-    return launch_bwd_weight<__hip_bfloat16>(x, grad_y, grad_weight, grad_bias, (float*)workspace, B, H, W, C, dilation,
-                                             flags, (hipStream_t)stream);
-  }
-  return fail(RFN_EINVAL, "rfn_dwconv3x3_nhwc_bwd_weight: dtype must be 0 (f32) or 1 (bf16)");
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_bwd_weight: C must be a multiple of 8 for 16-bit activations");
+  return dt_one(dtype, "rfn_dwconv3x3_nhwc_bwd_weight", [&](auto t) {
+    return launch_bwd_weight<typename decltype(t)::type>(x, grad_y, grad_weight, grad_bias, (float*)workspace, B, H, W, C,
+                                                         dilation, flags, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

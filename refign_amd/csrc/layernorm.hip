@@ -5,7 +5,7 @@
 // LayerNorms per MiT-B5 forward.  Under bf16 autocast the library path runs them in fp32 and the surrounding linears in
 // bf16, so every LayerNorm is followed by a separate fp32->bf16 cast pass and the residual stream stays fp32
 // (14 bytes of traffic per element where 4-6 are needed; ~100 ms of a 600 ms step incl. the casts).  This kernel does
-// the statistics in fp32 registers and reads/writes the activation dtype directly (fp32 or bf16 in, fp32 or bf16 out),
+// the statistics in fp32 registers and reads/writes the activation dtype directly (fp32, bf16 or fp16 in and out),
 // so the residual stream can live in bf16.  Pure HBM-bound row reductions:
 //   * one wave per row, lanes strided over C (C <= 1024): the row lives in registers (<= 16 values per lane), mean and
 //     variance by two wave butterflies (two-pass variance, no E[x^2]-E[x]^2 cancellation);
@@ -30,8 +30,12 @@ template <>
 __device__ __forceinline__ float ld<__hip_bfloat16>(const __hip_bfloat16* p) {
   return __uint_as_float(((unsigned)*reinterpret_cast<const unsigned short*>(p)) << 16);
 }
+template <>
+__device__ __forceinline__ float ld<_Float16>(const _Float16* p) { return (float)*p; }
 template <typename T>
 __device__ __forceinline__ void st(T* p, float v);
+template <>
+__device__ __forceinline__ void st<_Float16>(_Float16* p, float v) { *p = (_Float16)v; }
 template <>
 __device__ __forceinline__ void st<float>(float* p, float v) { *p = v; }
 template <>
@@ -168,8 +172,23 @@ __device__ __forceinline__ void ld8<__hip_bfloat16>(const __hip_bfloat16* p, flo
     v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
   }
 }
+template <>
+__device__ __forceinline__ void ld8<_Float16>(const _Float16* p, float (&v)[8]) {
+  const uint4 t = *reinterpret_cast<const uint4*>(p);
+  const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = f16_lo(w[i]);
+    v[2 * i + 1] = f16_hi(w[i]);
+  }
+}
 template <typename T>
 __device__ __forceinline__ void st8(T* p, const float (&v)[8]);
+template <>
+__device__ __forceinline__ void st8<_Float16>(_Float16* p, const float (&v)[8]) {
+  *reinterpret_cast<uint4*>(p) = make_uint4(f16x2_bits(v[0], v[1]), f16x2_bits(v[2], v[3]), f16x2_bits(v[4], v[5]),
+                                            f16x2_bits(v[6], v[7]));
+}
 template <>
 __device__ __forceinline__ void st8<float>(float* p, const float (&v)[8]) {
   *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
@@ -460,20 +479,15 @@ unsigned long rfn_layernorm_bwd_workspace_bytes(int C) {
   return (unsigned long)kLnMaxBlocks * 2ul * (unsigned long)(C > 0 ? C : 0) * sizeof(float);
 }
 
-// dtype codes: 0 = float32, 1 = bfloat16
+// dtype codes: 0 = float32, 1 = bfloat16, 2 = float16 (common.h: dt_pair)
 int rfn_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                       long rows, int C, float eps, int in_dtype, int out_dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && gamma && beta && y && mean && rstd, "rfn_layernorm_fwd: null pointer");
   RFN_REQUIRE(rows > 0 && C > 0 && C <= 64 * kLnMaxPerLane, "rfn_layernorm_fwd: need 0 < C <= 1024 (got %d)", C);
   hipStream_t st = (hipStream_t)stream;
-  if (in_dtype == 0 && out_dtype == 0) return ln_fwd_dispatch<float, float>(x, gamma, beta, y, mean, rstd, rows, C, eps, st);
-  if (in_dtype == 0 && out_dtype == 1)
-    return ln_fwd_dispatch<float, __hip_bfloat16>(x, gamma, beta, y, mean, rstd, rows, C, eps, st);
-  if (in_dtype == 1 && out_dtype == 1)
-    return ln_fwd_dispatch<__hip_bfloat16, __hip_bfloat16>(x, gamma, beta, y, mean, rstd, rows, C, eps, st);
-  if (in_dtype == 1 && out_dtype == 0)
-    return ln_fwd_dispatch<__hip_bfloat16, float>(x, gamma, beta, y, mean, rstd, rows, C, eps, st);
-  return fail(RFN_EINVAL, "rfn_layernorm_fwd: dtype codes must be 0 (f32) or 1 (bf16)");
+  return dt_pair(in_dtype, out_dtype, "rfn_layernorm_fwd", [&](auto ti, auto to) {
+    return ln_fwd_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(x, gamma, beta, y, mean, rstd, rows, C, eps, st);
+  });
 }
 
 int rfn_layernorm_bwd_add(const void* x, const void* grad_y, const void* add, const float* gamma, const float* mean,
@@ -484,15 +498,10 @@ int rfn_layernorm_bwd_add(const void* x, const void* grad_y, const void* add, co
   RFN_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 64 * kLnMaxPerLane, "rfn_layernorm_bwd_add: need C %% 8 == 0, C <= 1024 (got %d)", C);
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  if (x_dtype == 0 && gy_dtype == 0)
-    return ln_bwd_dispatch<float, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add);
-  if (x_dtype == 0 && gy_dtype == 1)
-    return ln_bwd_dispatch<float, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add);
-  if (x_dtype == 1 && gy_dtype == 1)
-    return ln_bwd_dispatch<__hip_bfloat16, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add);
-  if (x_dtype == 1 && gy_dtype == 0)
-    return ln_bwd_dispatch<__hip_bfloat16, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add);
-  return fail(RFN_EINVAL, "rfn_layernorm_bwd_add: dtype codes must be 0 (f32) or 1 (bf16)");
+  return dt_pair(x_dtype, gy_dtype, "rfn_layernorm_bwd_add", [&](auto tx, auto tg) {
+    return ln_bwd_dispatch<typename decltype(tx)::type, typename decltype(tg)::type>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma,
+                                                                                      grad_beta, ws, rows, C, accumulate, st, add);
+  });
 }
 
 // grad_y2 / add: either may be null
@@ -504,15 +513,10 @@ int rfn_layernorm_bwd_add2(const void* x, const void* grad_y, const void* grad_y
   RFN_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 64 * kLnMaxPerLane, "rfn_layernorm_bwd_add2: need C %% 8 == 0, C <= 1024 (got %d)", C);
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  if (x_dtype == 0 && gy_dtype == 0)
-    return ln_bwd_dispatch<float, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add, grad_y2);
-  if (x_dtype == 0 && gy_dtype == 1)
-    return ln_bwd_dispatch<float, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add, grad_y2);
-  if (x_dtype == 1 && gy_dtype == 1)
-    return ln_bwd_dispatch<__hip_bfloat16, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add, grad_y2);
-  if (x_dtype == 1 && gy_dtype == 0)
-    return ln_bwd_dispatch<__hip_bfloat16, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st, add, grad_y2);
-  return fail(RFN_EINVAL, "rfn_layernorm_bwd_add2: dtype codes must be 0 (f32) or 1 (bf16)");
+  return dt_pair(x_dtype, gy_dtype, "rfn_layernorm_bwd_add2", [&](auto tx, auto tg) {
+    return ln_bwd_dispatch<typename decltype(tx)::type, typename decltype(tg)::type>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma,
+                                                                                      grad_beta, ws, rows, C, accumulate, st, add, grad_y2);
+  });
 }
 
 int rfn_layernorm_fwd_f8(const void* x_bf16, const float* gamma, const float* beta, void* y8, long rows, int C, float eps,
@@ -531,15 +535,10 @@ int rfn_layernorm_bwd(const void* x, const void* grad_y, const float* gamma, con
   RFN_REQUIRE(rows > 0 && C > 0 && C <= 64 * kLnMaxPerLane, "rfn_layernorm_bwd: need 0 < C <= 1024 (got %d)", C);
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
-  if (x_dtype == 0 && gy_dtype == 0)
-    return ln_bwd_dispatch<float, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st);
-  if (x_dtype == 0 && gy_dtype == 1)
-    return ln_bwd_dispatch<float, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st);
-  if (x_dtype == 1 && gy_dtype == 1)
-    return ln_bwd_dispatch<__hip_bfloat16, __hip_bfloat16>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st);
-  if (x_dtype == 1 && gy_dtype == 0)
-    return ln_bwd_dispatch<__hip_bfloat16, float>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma, grad_beta, ws, rows, C, accumulate, st);
-  return fail(RFN_EINVAL, "rfn_layernorm_bwd: dtype codes must be 0 (f32) or 1 (bf16)");
+  return dt_pair(x_dtype, gy_dtype, "rfn_layernorm_bwd", [&](auto tx, auto tg) {
+    return ln_bwd_dispatch<typename decltype(tx)::type, typename decltype(tg)::type>(x, grad_y, gamma, mean, rstd, grad_x, grad_gamma,
+                                                                                      grad_beta, ws, rows, C, accumulate, st);
+  });
 }
 
 }  // extern "C"

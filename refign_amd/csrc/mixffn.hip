@@ -1,5 +1,5 @@
 // refign_amd/csrc/mixffn.hip -- Mix-FFN front half of the gradient-free MiT passes (mix_transformer.py:79-103): fc1, the depthwise
-// 3x3 convolution and the exact GELU in ONE kernel,   a = gelu(dw3x3(x W1^T + b1) + bdw),   bf16 in / out, fp32 accumulation.
+// 3x3 convolution and the exact GELU in ONE kernel,   a = gelu(dw3x3(x W1^T + b1) + bdw),   bf16 or fp16 in / out, fp32 accumulation.
 // The EMA teacher's 40 views made the 4C-wide hidden tensor the step's largest HBM customer: fc1 wrote it (209 MB per block at
 // stage 3), the depthwise kernel read and re-wrote it (8.4 ms of the 73 ms the gradient-free half takes on its own:
 // profiles/r06_teacher_half_kernel_stats.csv), fc2 read it.  Here the pre-activation never leaves the CU.
@@ -69,6 +69,14 @@ struct FfnRows {
   u32x4 w[4];      // the same piece of four W1 rows
 };
 
+// DT: 1 = bf16, 2 = fp16 operands, hidden tile and output (mfma.h Elem<DT>: the 32x32x16 bf16 / f16 MFMA, same cycles on gfx950)
+template <int DT>
+__device__ __forceinline__ f32p widen2(unsigned w) {
+  if constexpr (DT == 2) return f32p{f16_lo(w), f16_hi(w)};
+  else return f32p{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+}
+
+template <int DT>
 __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W1,
                                                               const uint16_t* __restrict__ b1, const float* __restrict__ wdw,
                                                               const float* __restrict__ bdw, uint16_t* __restrict__ A, int H,
@@ -133,17 +141,17 @@ __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t*
     const unsigned char* ws = xs + kFfnXBytes;
 #pragma unroll
     for (int ks = 0; ks < kFfnKC / 16; ++ks) {
-      bf16x8 wf[2], xf[4];
+      typename Elem<DT>::vec8 wf[2], xf[4];
 #pragma unroll
       for (int a = 0; a < 2; ++a)
-        wf[a] = *(const bf16x8*)(ws + ((2 * wn + a) * 32 + j) * (kFfnPitch * 2) + (ks * 16 + 8 * g) * 2);
+        wf[a] = *(const typename Elem<DT>::vec8*)(ws + ((2 * wn + a) * 32 + j) * (kFfnPitch * 2) + (ks * 16 + 8 * g) * 2);
 #pragma unroll
       for (int b = 0; b < 4; ++b)
-        xf[b] = *(const bf16x8*)(xs + ((4 * wm + b) * 32 + j) * (kFfnPitch * 2) + (ks * 16 + 8 * g) * 2);
+        xf[b] = *(const typename Elem<DT>::vec8*)(xs + ((4 * wm + b) * 32 + j) * (kFfnPitch * 2) + (ks * 16 + 8 * g) * 2);
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = Elem<1>::mma(wf[a], xf[b], acc[a][b]);
+        for (int b = 0; b < 4; ++b) acc[a][b] = Elem<DT>::mma(wf[a], xf[b], acc[a][b]);
     }
   }
   __syncthreads();
@@ -163,9 +171,9 @@ __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t*
         const int hc = (2 * wn + a) * 32 + 8 * c + 4 * g;             // four consecutive hidden channels
         const u32x2 bb = *(const u32x2*)(b1 + n0 + hc);
         float bf[4];
-        unpack4<1>(bb, bf);
+        unpack4<DT>(bb, bf);
         u32x2 pk = {0u, 0u};
-        if (in) pk = pack4<1>(acc[a][b][4 * c] + bf[0], acc[a][b][4 * c + 1] + bf[1], acc[a][b][4 * c + 2] + bf[2],
+        if (in) pk = pack4<DT>(acc[a][b][4 * c] + bf[0], acc[a][b][4 * c + 1] + bf[1], acc[a][b][4 * c + 2] + bf[2],
                               acc[a][b][4 * c + 3] + bf[3]);
         *(u32x2*)(ht + tok * kFfnHPitch + hc) = pk;
       }
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t*
       for (int c = 0; c < kFfnStrip + 2; ++c) {
         const u32x4 raw = *(const u32x4*)(ht + ((iy + dy) * kFfnTX + sx + c) * kFfnHPitch + cg * 8);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) hv[c][e] = f32p{__uint_as_float(raw[e] << 16), __uint_as_float(raw[e] & 0xffff0000u)};
+        for (int e = 0; e < 4; ++e) hv[c][e] = widen2<DT>(raw[e]);
       }
 #pragma unroll
       for (int o = 0; o < kFfnStrip; ++o)
@@ -225,25 +233,38 @@ __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t*
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const f32p gz = gelu2(s[o][e]);
-        pk[e] = bf16x2_bits(gz[0], gz[1]);
+        pk[e] = DT == 2 ? f16x2_bits(gz[0], gz[1]) : bf16x2_bits(gz[0], gz[1]);
       }
       *(u32x4*)(arow + (long)o * HID) = pk;
     }
   }
 }
 
-}  // namespace rfn
-
-extern "C" int rfn_ffn_fc1_dw_gelu_bf16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
-                                        int views, int H, int W, int C, int HID, rfn_stream_t stream) {
-  using namespace rfn;
+static int ffn_launch(int dt, const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
+                      int views, int H, int W, int C, int HID, hipStream_t stream) {
   RFN_REQUIRE(x && w1 && b1 && wdw_tap && bdw && a, "ffn_fc1_dw_gelu: null pointer");
   RFN_REQUIRE(views > 0 && H > 0 && W > 0 && C > 0 && C % kFfnKC == 0 && HID > 0 && HID % kFfnNH == 0,
               "ffn_fc1_dw_gelu: views=%d H=%d W=%d C=%d (%% 64) HID=%d (%% 128)", views, H, W, C, HID);
   const int tiles_y = cdiv(H, kFfnIY), tiles_x = cdiv(W, kFfnIX);
   const long blocks = (long)views * tiles_y * tiles_x * (HID / kFfnNH);
   RFN_REQUIRE(blocks < (1L << 31), "ffn_fc1_dw_gelu: %ld workgroups", blocks);
-  hipLaunchKernelGGL(ffn_fc1_dw_gelu_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
-                     (const uint16_t*)w1, (const uint16_t*)b1, wdw_tap, bdw, (uint16_t*)a, H, W, C, HID, tiles_y, tiles_x);
+  if (dt == 2)
+    hipLaunchKernelGGL(ffn_fc1_dw_gelu_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint16_t*)x, (const uint16_t*)w1,
+                       (const uint16_t*)b1, wdw_tap, bdw, (uint16_t*)a, H, W, C, HID, tiles_y, tiles_x);
+  else
+    hipLaunchKernelGGL(ffn_fc1_dw_gelu_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint16_t*)x, (const uint16_t*)w1,
+                       (const uint16_t*)b1, wdw_tap, bdw, (uint16_t*)a, H, W, C, HID, tiles_y, tiles_x);
   return check_launch("ffn_fc1_dw_gelu");
+}
+
+}  // namespace rfn
+
+extern "C" int rfn_ffn_fc1_dw_gelu_bf16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
+                                        int views, int H, int W, int C, int HID, rfn_stream_t stream) {
+  return rfn::ffn_launch(1, x, w1, b1, wdw_tap, bdw, a, views, H, W, C, HID, (hipStream_t)stream);
+}
+
+extern "C" int rfn_ffn_fc1_dw_gelu_f16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
+                                       int views, int H, int W, int C, int HID, rfn_stream_t stream) {
+  return rfn::ffn_launch(2, x, w1, b1, wdw_tap, bdw, a, views, H, W, C, HID, (hipStream_t)stream);
 }

@@ -14,6 +14,7 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -34,6 +35,17 @@ __device__ __forceinline__ void load8<__hip_bfloat16>(const __hip_bfloat16* p, f
   for (int i = 0; i < 4; ++i) {
     v[2 * i] = __uint_as_float(w[i] << 16);
     v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+}
+
+template <>
+__device__ __forceinline__ void load8<_Float16>(const _Float16* p, float (&v)[8]) {
+  const uint4 t = *reinterpret_cast<const uint4*>(p);
+  const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = f16_lo(w[i]);
+    v[2 * i + 1] = f16_hi(w[i]);
   }
 }
 
@@ -104,8 +116,12 @@ __device__ __forceinline__ void sum_rows_flat_body(const T* __restrict__ x, floa
 #pragma unroll 4
     for (int s = 0; s < S; ++s) {
       const uint2 v = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(x) + (long)s * n + i);
-      s0 += __uint_as_float(v.x << 16); s1 += __uint_as_float(v.x & 0xffff0000u);
-      s2 += __uint_as_float(v.y << 16); s3 += __uint_as_float(v.y & 0xffff0000u);
+      if constexpr (std::is_same<T, _Float16>::value) {
+        s0 += f16_lo(v.x); s1 += f16_hi(v.x); s2 += f16_lo(v.y); s3 += f16_hi(v.y);
+      } else {
+        s0 += __uint_as_float(v.x << 16); s1 += __uint_as_float(v.x & 0xffff0000u);
+        s2 += __uint_as_float(v.y << 16); s3 += __uint_as_float(v.y & 0xffff0000u);
+      }
     }
   }
   float4* o = reinterpret_cast<float4*>(out + i);
@@ -216,24 +232,17 @@ int rfn_linear_param_grads(const void* grad_y, float* grad_bias, void* workspace
   RFN_REQUIRE(grad_y && grad_bias && workspace && w_partials && grad_weight, "rfn_linear_param_grads: null pointer");
   RFN_REQUIRE(T > kFlatMaxS && N > 0 && N % 8 == 0 && S > 0 && S <= kFlatMaxS && NK > 0 && NK % 8 == 0,
               "rfn_linear_param_grads: need T > 64, 0 < S <= 64, N and N*K multiples of 8");
-  RFN_REQUIRE(dtype == 0 || dtype == 1, "rfn_linear_param_grads: dtype must be 0 (f32) or 1 (bf16)");
   hipStream_t st = (hipStream_t)stream;
   const TallPlan p = plan_tall(T, N);
   const int nb_bias = cdiv(N, 32), nb_w = cdiv(cdiv(NK, 4), 256);
-  if (dtype == 0) {
-    hipLaunchKernelGGL((sum_rows_tall_kernel<float>), dim3(p.stripes, p.gy), dim3(p.cvb * p.ty), 0, st,
-                       (const float*)grad_y, (float*)workspace, T, N, p.cvb, p.ty, p.rows_per_stripe);
-    hipLaunchKernelGGL((linear_param_grads_kernel<float>), dim3(nb_bias + nb_w), dim3(256), 0, st,
-                       (const float*)workspace, grad_bias, p.stripes, N, acc_bias, nb_bias, (const float*)w_partials,
-                       grad_weight, S, NK, acc_weight);
-  } else {
-    hipLaunchKernelGGL((sum_rows_tall_kernel<__hip_bfloat16>), dim3(p.stripes, p.gy), dim3(p.cvb * p.ty), 0, st,
-                       (const __hip_bfloat16*)grad_y, (float*)workspace, T, N, p.cvb, p.ty, p.rows_per_stripe);
-    hipLaunchKernelGGL((linear_param_grads_kernel<__hip_bfloat16>), dim3(nb_bias + nb_w), dim3(256), 0, st,
-                       (const float*)workspace, grad_bias, p.stripes, N, acc_bias, nb_bias,
-                       (const __hip_bfloat16*)w_partials, grad_weight, S, NK, acc_weight);
-  }
-  return check_launch("linear_param_grads_kernel");
+  return dt_one(dtype, "rfn_linear_param_grads", [&](auto t) {
+    using E = typename decltype(t)::type;
+    hipLaunchKernelGGL((sum_rows_tall_kernel<E>), dim3(p.stripes, p.gy), dim3(p.cvb * p.ty), 0, st, (const E*)grad_y,
+                       (float*)workspace, T, N, p.cvb, p.ty, p.rows_per_stripe);
+    hipLaunchKernelGGL((linear_param_grads_kernel<E>), dim3(nb_bias + nb_w), dim3(256), 0, st, (const float*)workspace, grad_bias,
+                       p.stripes, N, acc_bias, nb_bias, (const E*)w_partials, grad_weight, S, NK, acc_weight);
+    return check_launch("linear_param_grads_kernel");
+  });
 }
 
 int rfn_sum_rows(const void* x, float* out, void* workspace, long S, long n, int x_dtype, int accumulate,
@@ -241,10 +250,9 @@ int rfn_sum_rows(const void* x, float* out, void* workspace, long S, long n, int
   RFN_REQUIRE(x && out, "rfn_sum_rows: null pointer");
   RFN_REQUIRE(S > 0 && n > 0 && n % 8 == 0, "rfn_sum_rows: need S > 0 and n a positive multiple of 8 (got %ld, %ld)", S, n);
   RFN_REQUIRE(S <= kFlatMaxS || workspace, "rfn_sum_rows: workspace required for S > %d", kFlatMaxS);
-  if (x_dtype == 0) return launch_sum_rows<float>(x, out, (float*)workspace, S, n, accumulate, (hipStream_t)stream);
-  if (x_dtype == 1)
-    return launch_sum_rows<__hip_bfloat16>(x, out, (float*)workspace, S, n, accumulate, (hipStream_t)stream);
-  return fail(RFN_EINVAL, "rfn_sum_rows: x_dtype must be 0 (f32) or 1 (bf16)");
+  return dt_one(x_dtype, "rfn_sum_rows", [&](auto t) {
+    return launch_sum_rows<typename decltype(t)::type>(x, out, (float*)workspace, S, n, accumulate, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"
@@ -265,7 +273,14 @@ struct CastChunk {
 
 __device__ __forceinline__ unsigned f32_to_bf16_bits(float f) { return bf16_bits(f); }   // common.h
 
-__global__ __launch_bounds__(256) void multi_cast_f32_bf16_kernel(const CastChunk* __restrict__ table) {
+// F16: fp16 copies instead (the fp16 recipe, Trainer(precision=16)): bit-equal to tensor.to(torch.float16)
+__device__ __forceinline__ unsigned f32_to_16_bits(float f, bool f16) { return f16 ? f16_bits(f) : bf16_bits(f); }
+__device__ __forceinline__ unsigned f32x2_to_16_bits(float lo, float hi, bool f16) {
+  return f16 ? f16x2_bits(lo, hi) : bf16x2_bits(lo, hi);
+}
+
+template <bool F16>
+__global__ __launch_bounds__(256) void multi_cast_f32_16_kernel(const CastChunk* __restrict__ table) {
   const CastChunk c = table[blockIdx.x];
   const bool aligned = (((size_t)c.src & 15) == 0) && (((size_t)c.dst & 7) == 0);
   long i = (long)threadIdx.x * 4;
@@ -273,14 +288,14 @@ __global__ __launch_bounds__(256) void multi_cast_f32_bf16_kernel(const CastChun
     for (; i + 3 < c.n; i += 256 * 4) {
       const float4 v = *reinterpret_cast<const float4*>(c.src + i);
       uint2 o;
-      o.x = bf16x2_bits(v.x, v.y);
-      o.y = bf16x2_bits(v.z, v.w);
+      o.x = f32x2_to_16_bits(v.x, v.y, F16);
+      o.y = f32x2_to_16_bits(v.z, v.w, F16);
       *reinterpret_cast<uint2*>(c.dst + i) = o;
     }
   }
   // tail (and unaligned tensors): scalar
   for (long j = aligned ? (c.n & ~3L) + threadIdx.x : threadIdx.x; j < c.n; j += 256)
-    c.dst[j] = (unsigned short)f32_to_bf16_bits(c.src[j]);
+    c.dst[j] = (unsigned short)f32_to_16_bits(c.src[j], F16);
 }
 
 // Layout-changing copies of a parameter set in one launch: dst (contiguous, up to 4-D, fp32 / bf16 / f16) <- a strided fp32 view
@@ -358,6 +373,7 @@ struct TransposeTile {
 
 constexpr int kTransposeTile = 64;     // rfn_multi_transpose_tile()
 
+template <bool F16>
 __global__ __launch_bounds__(256) void multi_transpose_cast_kernel(const TransposeTile* __restrict__ table) {
   // 64 x 64 tile: rows of 64 floats read as 16-byte pieces (256 B per row), columns written as 16-byte pieces of 8 bf16 (128 B per
   // destination row).  (Round 5; 32 x 32 tiles with 2-byte stores: 0.94 ms for MiT-B5's 82 M weights, 64-byte write segments.)
@@ -391,14 +407,14 @@ __global__ __launch_bounds__(256) void multi_transpose_cast_kernel(const Transpo
     if (k >= t.K || n >= t.N) continue;
     if (vec_out && n + 7 < t.N) {
       uint4 o;
-      o.x = bf16x2_bits(tile[8 * c8][r], tile[8 * c8 + 1][r]);
-      o.y = bf16x2_bits(tile[8 * c8 + 2][r], tile[8 * c8 + 3][r]);
-      o.z = bf16x2_bits(tile[8 * c8 + 4][r], tile[8 * c8 + 5][r]);
-      o.w = bf16x2_bits(tile[8 * c8 + 6][r], tile[8 * c8 + 7][r]);
+      o.x = f32x2_to_16_bits(tile[8 * c8][r], tile[8 * c8 + 1][r], F16);
+      o.y = f32x2_to_16_bits(tile[8 * c8 + 2][r], tile[8 * c8 + 3][r], F16);
+      o.z = f32x2_to_16_bits(tile[8 * c8 + 4][r], tile[8 * c8 + 5][r], F16);
+      o.w = f32x2_to_16_bits(tile[8 * c8 + 6][r], tile[8 * c8 + 7][r], F16);
       *reinterpret_cast<uint4*>(t.dst + (size_t)k * t.N + n) = o;
     } else {
       for (int e = 0; e < 8 && n + e < t.N; ++e)
-        t.dst[(size_t)k * t.N + n + e] = (unsigned short)f32_to_bf16_bits(tile[8 * c8 + e][r]);
+        t.dst[(size_t)k * t.N + n + e] = (unsigned short)f32_to_16_bits(tile[8 * c8 + e][r], F16);
     }
   }
 }
@@ -449,15 +465,145 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(const AdamChunk* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Loss scaling of the fp16 recipe (the reference trains with `precision: 16`: Lightning's native AMP, torch.amp.GradScaler
+// around a non-fused torch.optim.AdamW), with no host synchronisation: the scale, the found-inf flag, the growth tracker and
+// the optimiser's step count live in device memory and every decision is taken on the device.
+//   amp_unscale_kernel     g *= 1 / scale over the flat gradient buffer, found_inf = 1 if any g is inf or NaN
+//                          (torch._amp_foreach_non_finite_check_and_unscale_; inv_scale = float(1 / double(scale)) as GradScaler);
+//   multi_adamw_amp_kernel multi_adamw_kernel's arithmetic, but a no-op when found_inf is set, with the bias corrections of
+//                          step t = *step + 1 computed on the device (in double, as torch computes them on the host);
+//   amp_update_scale_kernel torch._amp_update_scale_ (backoff on inf, growth after `interval` clean steps) and *step += 1
+//                          when the step was taken.  Runs last: it is the only writer of scale, tracker and step.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void amp_unscale_kernel(float* __restrict__ g, long n, const float* __restrict__ scale,
+                                                          float* __restrict__ found_inf) {
+  const float inv = (float)(1.0 / (double)*scale);
+  bool bad = false;
+  const long n4 = n >> 2, stride = (long)gridDim.x * 256;
+  float4* g4 = reinterpret_cast<float4*>(g);              // the flat buffer is 256-byte aligned (FlatGradBuffer.ALIGN)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 v = g4[i];
+    bad |= !(isfinite(v.x) && isfinite(v.y) && isfinite(v.z) && isfinite(v.w));
+    v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
+    g4[i] = v;
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    bad |= !isfinite(g[i]);
+    g[i] *= inv;
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.f;   // every writer writes the same value
+}
+
+struct AdamAmpGroups {
+  float lr[8], beta2[8], eps[8], wd[8], omb1[8], omb2[8];
+  double beta1d[8], beta2d[8];                            // the bias corrections are taken in double, as torch's host code does
+};
+
+__global__ __launch_bounds__(256) void multi_adamw_amp_kernel(const AdamChunk* __restrict__ table, AdamAmpGroups gr,
+                                                              const float* __restrict__ found_inf, const float* __restrict__ step) {
+  if (*found_inf != 0.f) return;                          // skipped step: parameters and both moments stay as they are
+  const AdamChunk c = table[blockIdx.x];
+  const int gi = (int)((unsigned long)c.n >> 56);
+  const long n = c.n & ((1L << 56) - 1);
+  const double t = (double)*step + 1.0;
+  const float bc1 = (float)(1.0 - pow(gr.beta1d[gi], t)), bc2s = (float)sqrt(1.0 - pow(gr.beta2d[gi], t));
+  const float lr = gr.lr[gi], b2 = gr.beta2[gi], eps = gr.eps[gi], wd = gr.wd[gi];
+  const float step_size = lr / bc1, omb1 = gr.omb1[gi], omb2 = gr.omb2[gi];
+  auto upd = [&](float& p, float g, float& m, float& v) {
+    p -= lr * wd * p;
+    m = m + omb1 * (g - m);
+    v = b2 * v + omb2 * g * g;
+    p -= step_size * m / (sqrtf(v) / bc2s + eps);
+  };
+  const bool aligned = ((((size_t)c.p | (size_t)c.g | (size_t)c.m | (size_t)c.v) & 15) == 0);
+  long i = (long)threadIdx.x * 4;
+  if (aligned) {
+    for (; i + 3 < n; i += 256 * 4) {
+      float4 p = *reinterpret_cast<const float4*>(c.p + i), m = *reinterpret_cast<const float4*>(c.m + i);
+      float4 v = *reinterpret_cast<const float4*>(c.v + i);
+      const float4 g = *reinterpret_cast<const float4*>(c.g + i);
+      upd(p.x, g.x, m.x, v.x); upd(p.y, g.y, m.y, v.y); upd(p.z, g.z, m.z, v.z); upd(p.w, g.w, m.w, v.w);
+      *reinterpret_cast<float4*>(c.p + i) = p;
+      *reinterpret_cast<float4*>(c.m + i) = m;
+      *reinterpret_cast<float4*>(c.v + i) = v;
+    }
+  }
+  for (long j = aligned ? (n & ~3L) + threadIdx.x : threadIdx.x; j < n; j += 256) {
+    float p = c.p[j], m = c.m[j], v = c.v[j];
+    upd(p, c.g[j], m, v);
+    c.p[j] = p; c.m[j] = m; c.v[j] = v;
+  }
+}
+
+__global__ void amp_update_scale_kernel(float* scale, int* tracker, const float* found_inf, float* step, float growth,
+                                        float backoff, int interval) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (*found_inf != 0.f) {
+    *scale = *scale * backoff;
+    *tracker = 0;
+    return;
+  }
+  const int ok = *tracker + 1;
+  if (ok == interval) {
+    const float grown = *scale * growth;
+    if (isfinite(grown)) *scale = grown;
+    *tracker = 0;
+  } else {
+    *tracker = ok;
+  }
+  if (step != nullptr) *step = *step + 1.f;
+}
+
 }  // namespace rfn
 
 extern "C" {
 
+int rfn_amp_unscale_f32(float* grads, long n, const float* scale, float* found_inf, rfn_stream_t stream) {
+  RFN_REQUIRE(grads && scale && found_inf && n > 0 && ((size_t)grads & 15) == 0,
+              "rfn_amp_unscale_f32: null pointer, empty or unaligned buffer");
+  const int grid = (int)std::min<long>(std::max<long>(1, cdiv(n, 4 * 256)), 256L * 8);
+  hipLaunchKernelGGL(rfn::amp_unscale_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, grads, n, scale, found_inf);
+  return rfn::check_launch("amp_unscale_kernel");
+}
+
+// group_args: 7 doubles per group {lr, beta1, beta2, eps, weight_decay, 1 - beta1, 1 - beta2}; step: the optimiser's
+// device step count (steps taken so far), advanced by rfn_amp_update_scale
+int rfn_multi_adamw_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
+                            const float* step, rfn_stream_t stream) {
+  RFN_REQUIRE(table && nchunks > 0 && group_args && ngroups > 0 && ngroups <= 8 && found_inf && step,
+              "rfn_multi_adamw_amp_f32: bad arguments");
+  rfn::AdamAmpGroups gr{};
+  for (int g = 0; g < ngroups; ++g) {
+    const double* a = group_args + 7 * g;
+    gr.lr[g] = (float)a[0]; gr.beta1d[g] = a[1]; gr.beta2d[g] = a[2]; gr.beta2[g] = (float)a[2]; gr.eps[g] = (float)a[3];
+    gr.wd[g] = (float)a[4]; gr.omb1[g] = (float)a[5]; gr.omb2[g] = (float)a[6];
+  }
+  hipLaunchKernelGGL(rfn::multi_adamw_amp_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
+                     (const rfn::AdamChunk*)table, gr, found_inf, step);
+  return rfn::check_launch("multi_adamw_amp_kernel");
+}
+
+int rfn_amp_update_scale(float* scale, int* growth_tracker, const float* found_inf, float* step, float growth_factor,
+                         float backoff_factor, int growth_interval, rfn_stream_t stream) {
+  RFN_REQUIRE(scale && growth_tracker && found_inf && growth_interval > 0, "rfn_amp_update_scale: bad arguments");
+  hipLaunchKernelGGL(rfn::amp_update_scale_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scale, growth_tracker,
+                     found_inf, step, growth_factor, backoff_factor, growth_interval);
+  return rfn::check_launch("amp_update_scale_kernel");
+}
+
 int rfn_multi_transpose_cast_f32_bf16(const void* table, int ntiles, rfn_stream_t stream) {
   RFN_REQUIRE(table && ntiles > 0, "rfn_multi_transpose_cast_f32_bf16: empty table");
-  hipLaunchKernelGGL(rfn::multi_transpose_cast_kernel, dim3(ntiles), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rfn::multi_transpose_cast_kernel<false>, dim3(ntiles), dim3(256), 0, (hipStream_t)stream,
                      (const rfn::TransposeTile*)table);
   return rfn::check_launch("multi_transpose_cast_kernel");
+}
+
+int rfn_multi_transpose_cast_f32_f16(const void* table, int ntiles, rfn_stream_t stream) {
+  RFN_REQUIRE(table && ntiles > 0, "rfn_multi_transpose_cast_f32_f16: empty table");
+  hipLaunchKernelGGL(rfn::multi_transpose_cast_kernel<true>, dim3(ntiles), dim3(256), 0, (hipStream_t)stream,
+                     (const rfn::TransposeTile*)table);
+  return rfn::check_launch("multi_transpose_cast_kernel<f16>");
 }
 
 int rfn_multi_adamw_f32(const void* table, int nchunks, const float* group_args, int ngroups, rfn_stream_t stream) {
@@ -496,9 +642,16 @@ int rfn_multi_permute_cast_f32(const void* table, int nchunks, rfn_stream_t stre
 
 int rfn_multi_cast_f32_bf16(const void* table, int nchunks, rfn_stream_t stream) {
   RFN_REQUIRE(table && nchunks > 0, "rfn_multi_cast_f32_bf16: empty table");
-  hipLaunchKernelGGL(rfn::multi_cast_f32_bf16_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(rfn::multi_cast_f32_16_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
                      (const rfn::CastChunk*)table);
   return rfn::check_launch("multi_cast_f32_bf16_kernel");
+}
+
+int rfn_multi_cast_f32_f16(const void* table, int nchunks, rfn_stream_t stream) {
+  RFN_REQUIRE(table && nchunks > 0, "rfn_multi_cast_f32_f16: empty table");
+  hipLaunchKernelGGL(rfn::multi_cast_f32_16_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
+                     (const rfn::CastChunk*)table);
+  return rfn::check_launch("multi_cast_f32_f16_kernel");
 }
 
 }  // extern "C"

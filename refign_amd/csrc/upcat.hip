@@ -39,6 +39,25 @@ __device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
 // (index arithmetic -> 4 loads -> blend -> store) at 2.6 TB/s of a 6.7 TB/s write rate
 constexpr int kUpPX = 4;
 
+// 8 channels of a 16-bit type (bf16 or fp16) as one 16-byte vector <-> 8 floats
+template <typename T>
+__device__ __forceinline__ void widen8(const uint4& t, float (&f)[8]) {
+  if constexpr (std::is_same<T, _Float16>::value) {
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[2 * i] = f16_lo(w[i]), f[2 * i + 1] = f16_hi(w[i]);
+  } else {
+    unpack8(t, f);
+  }
+}
+template <typename T>
+__device__ __forceinline__ uint4 narrow8(const float (&r)[8]) {
+  if constexpr (std::is_same<T, _Float16>::value)
+    return make_uint4(f16x2_bits(r[0], r[1]), f16x2_bits(r[2], r[3]), f16x2_bits(r[4], r[5]), f16x2_bits(r[6], r[7]));
+  else
+    return make_uint4(bf16x2_bits(r[0], r[1]), bf16x2_bits(r[2], r[3]), bf16x2_bits(r[4], r[5]), bf16x2_bits(r[6], r[7]));
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restrict__ out, int H, int W, long total) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -87,7 +106,7 @@ __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restr
     }
   }
   auto widen = [](const V16 (&t)[NV], float (&f)[8]) {
-    if constexpr (sizeof(T) == 2) unpack8(t[0], f);
+    if constexpr (sizeof(T) == 2) widen8<T>(t[0], f);
     else {
       f[0] = t[0].x; f[1] = t[0].y; f[2] = t[0].z; f[3] = t[0].w;
       f[4] = t[1].x; f[5] = t[1].y; f[6] = t[1].z; f[7] = t[1].w;
@@ -112,12 +131,7 @@ __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restr
     }
     T* o = out + (((size_t)n * H + y) * W + x) * (size_t)CV * 8 + (size_t)cv * 8;
     if constexpr (sizeof(T) == 2) {
-      uint4 t;
-      t.x = bf16x2_bits(r[0], r[1]);
-      t.y = bf16x2_bits(r[2], r[3]);
-      t.z = bf16x2_bits(r[4], r[5]);
-      t.w = bf16x2_bits(r[6], r[7]);
-      *reinterpret_cast<uint4*>(o) = t;
+      *reinterpret_cast<uint4*>(o) = narrow8<T>(r);
     } else {
       *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
       *reinterpret_cast<float4*>(o + 4) = make_float4(r[4], r[5], r[6], r[7]);
@@ -160,7 +174,7 @@ __global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, con
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   auto add = [&](const T* p, float wgt) {
     float v[8];
-    if constexpr (sizeof(T) == 2) unpack8(*reinterpret_cast<const uint4*>(p), v);
+    if constexpr (sizeof(T) == 2) widen8<T>(*reinterpret_cast<const uint4*>(p), v);
     else {
       const float4 u = *reinterpret_cast<const float4*>(p), t = *reinterpret_cast<const float4*>(p + 4);
       v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; v[4] = t.x; v[5] = t.y; v[6] = t.z; v[7] = t.w;
@@ -194,12 +208,7 @@ __global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, con
   }
   T* o = reinterpret_cast<T*>(a.dst[l]) + (((size_t)n * hl + ys) * wl + xs) * (size_t)CVl * 8 + (size_t)cl * 8;
   if constexpr (sizeof(T) == 2) {
-    uint4 t;
-    t.x = bf16x2_bits(acc[0], acc[1]);
-    t.y = bf16x2_bits(acc[2], acc[3]);
-    t.z = bf16x2_bits(acc[4], acc[5]);
-    t.w = bf16x2_bits(acc[6], acc[7]);
-    *reinterpret_cast<uint4*>(o) = t;
+    *reinterpret_cast<uint4*>(o) = narrow8<T>(acc);
   } else {
     *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     *reinterpret_cast<float4*>(o + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
@@ -236,15 +245,11 @@ int rfn_upsample_concat_nhwc(const void* src0, const void* src1, const void* src
   const long total = (long)n * H * ((W + kUpPX - 1) / kUpPX) * a.cv0[nlev];      // threads: kUpPX pixels of a row each
   RFN_REQUIRE(total / 256 < 0x7fffffffL, "rfn_upsample_concat_nhwc: too large");
   const int grid = cdiv(total, 256);
-  if (dtype == 1)
-    hipLaunchKernelGGL((upcat_nhwc_kernel<__hip_bfloat16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a,
-                       (__hip_bfloat16*)out, H, W, total);
-  else if (dtype == 0)
-    hipLaunchKernelGGL((upcat_nhwc_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (float*)out, H, W,
-                       total);
-  else
-    return fail(RFN_EINVAL, "rfn_upsample_concat_nhwc: dtype must be 0 (f32) or 1 (bf16)");
-  return check_launch("upcat_nhwc_kernel");
+  return dt_one(dtype, "rfn_upsample_concat_nhwc", [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((upcat_nhwc_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (T*)out, H, W, total);
+    return check_launch("upcat_nhwc_kernel");
+  });
 }
 
 int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs,
@@ -275,15 +280,12 @@ int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1,
   const long total = a.vec0[nlev];
   RFN_REQUIRE(total / 256 < 0x7fffffffL, "rfn_upsample_concat_nhwc_bwd: too large");
   const int grid = cdiv(total, 256);
-  if (dtype == 1)
-    hipLaunchKernelGGL((upcat_bwd_nhwc_kernel<__hip_bfloat16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a,
-                       (const __hip_bfloat16*)grad_out, H, W, total);
-  else if (dtype == 0)
-    hipLaunchKernelGGL((upcat_bwd_nhwc_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a,
-                       (const float*)grad_out, H, W, total);
-  else
-    return fail(RFN_EINVAL, "rfn_upsample_concat_nhwc_bwd: dtype must be 0 (f32) or 1 (bf16)");
-  return check_launch("upcat_bwd_nhwc_kernel");
+  return dt_one(dtype, "rfn_upsample_concat_nhwc_bwd", [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((upcat_bwd_nhwc_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (const T*)grad_out, H, W,
+                       total);
+    return check_launch("upcat_bwd_nhwc_kernel");
+  });
 }
 
 }  // extern "C"
@@ -427,8 +429,8 @@ int rfn_patchify_tokens_cmajor(const void* src, void* dst, int B, int H, int W, 
                                rfn_stream_t stream) {
   RFN_REQUIRE(src && dst && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && (r == 2 || r == 4 || r == 8) && r <= H && r <= W,
               "rfn_patchify_tokens_cmajor: bad arguments (C %% 8 == 0, r in {2, 4, 8})");
-  RFN_REQUIRE(dtype == 0 || dtype == 1, "rfn_patchify_tokens_cmajor: dtype must be 0 (f32) or 1 (bf16 / f16)");
-  if (dtype == 1) return rfn::launch_patchify_cmajor<unsigned short>(src, dst, B, H, W, C, r, inverse, (hipStream_t)stream);
+  RFN_REQUIRE(dtype >= 0 && dtype <= 2, "rfn_patchify_tokens_cmajor: dtype must be 0 (f32), 1 (bf16) or 2 (f16)");
+  if (dtype != 0) return rfn::launch_patchify_cmajor<unsigned short>(src, dst, B, H, W, C, r, inverse, (hipStream_t)stream);
   return rfn::launch_patchify_cmajor<unsigned int>(src, dst, B, H, W, C, r, inverse, (hipStream_t)stream);
 }
 
@@ -436,11 +438,11 @@ int rfn_patchify_tokens(const void* src, void* dst, int B, int H, int W, int C, 
                         rfn_stream_t stream) {
   RFN_REQUIRE(src && dst && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && r > 0 && r <= H && r <= W,
               "rfn_patchify_tokens: bad arguments (C must be a multiple of 8)");
-  RFN_REQUIRE(dtype == 0 || dtype == 1, "rfn_patchify_tokens: dtype must be 0 (f32) or 1 (bf16)");
+  RFN_REQUIRE(dtype >= 0 && dtype <= 2, "rfn_patchify_tokens: dtype must be 0 (f32), 1 (bf16) or 2 (f16)");
   const int Hr = H / r, Wr = W / r, CV = C / 8;
   const long total = (long)B * Hr * Wr * r * r * CV;
   const int grid = rfn::cdiv(total, 256);
-  if (dtype == 1)
+  if (dtype != 0)                                      // a pure move: bf16 and f16 alike
     hipLaunchKernelGGL((rfn::patchify_kernel<16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)src,
                        (char*)dst, H, W, CV, r, Hr, Wr, total, inverse);
   else

@@ -3,7 +3,7 @@
 `dwconv3x3_tokens(x, weight, bias, H, W)` is the DWConv of the Mix-FFN (mix_transformer.py:556-568) WITHOUT the two
 NCHW transposes of the reference: x is (B, N=H*W, C) and stays that way.  `dwconv3x3_nhwc(x, weight, bias, dilation)`
 is the same on (B, H, W, C) maps with dilation (DAFormer ASPP branches, daformer.py:46-62).  `weight` is the reference
-parameter itself, shape (C, 1, 3, 3); activations float32 or bfloat16, accumulation fp32, weight grads fp32.
+parameter itself, shape (C, 1, 3, 3); activations float32, bfloat16 or float16, accumulation fp32, weight grads fp32.
 """
 import os
 
@@ -13,7 +13,7 @@ from . import _lib
 from ._tensor import current_stream, on_device, ptr, require_device_tensor, workspace
 from .params import as_dtype, derived, grad_sink
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _DW_WS_STRIPES = 128       # kMaxStripes in csrc/dwconv.hip (checked against the ABI in the GPU tests)
 
 
@@ -151,21 +151,22 @@ FUSED_FFN = os.environ.get("RFN_FUSED_FFN", "1") != "0"      # (tests flip the a
 
 @torch.no_grad()
 def ffn_fc1_dw_gelu(x, fc1, dw, H, W):
-    """gelu(dw(fc1(x))) of a Mix-FFN (mix_transformer.py:99-101) on gradient-free bf16 tokens (views, H*W, C) in ONE kernel
+    """gelu(dw(fc1(x))) of a Mix-FFN (mix_transformer.py:99-101) on gradient-free bf16 / fp16 tokens (views, H*W, C) in ONE kernel
     (csrc/mixffn.hip): the 4C-wide pre-activation never reaches HBM.  `fc1`: the Linear, `dw`: the depthwise nn.Conv2d.  None
     outside the kernel's domain (the caller runs fc1, then dwconv3x3_gelu_tokens)."""
     B, N, C = x.shape
     HID = fc1.weight.shape[0]
-    if not (FUSED_FFN and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and N == H * W and C % 64 == 0
+    if not (FUSED_FFN and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and N == H * W and C % 64 == 0
             and HID % 128 == 0 and fc1.bias is not None and dw.bias is not None and dw.weight.shape == (HID, 1, 3, 3)
             and dw.padding == (1, 1) and dw.stride == (1, 1) and dw.dilation == (1, 1)):
         return None
-    w1, b1 = as_dtype(fc1.weight, torch.bfloat16), as_dtype(fc1.bias, torch.bfloat16)
+    w1, b1 = as_dtype(fc1.weight, x.dtype), as_dtype(fc1.bias, x.dtype)
     w_tap = derived(dw.weight, "tap_major_f32", lambda t: t.float().reshape(HID, 9).t().contiguous(), lambda t: t.reshape(HID, 9).t())
     bdw = as_dtype(dw.bias, torch.float32).detach().contiguous()
-    a = torch.empty((B, N, HID), dtype=torch.bfloat16, device=x.device)
+    a = torch.empty((B, N, HID), dtype=x.dtype, device=x.device)
+    fn = _lib.load_library().rfn_ffn_fc1_dw_gelu_f16 if x.dtype == torch.float16 else _lib.load_library().rfn_ffn_fc1_dw_gelu_bf16
     with on_device(x.device):
-        rc = _lib.load_library().rfn_ffn_fc1_dw_gelu_bf16(ptr(x), ptr(w1), ptr(b1), ptr(w_tap), ptr(bdw), ptr(a), B, H, W, C, HID,
+        rc = fn(ptr(x), ptr(w1), ptr(b1), ptr(w_tap), ptr(bdw), ptr(a), B, H, W, C, HID,
                                                           current_stream(x.device))
     _lib.check(rc, "ffn_fc1_dw_gelu")
     return a
@@ -173,13 +174,13 @@ def ffn_fc1_dw_gelu(x, fc1, dw, H, W):
 
 def dwconv3x3_nhwc(x, weight, bias=None, dilation=1, stats=None):
     """x: (B,H,W,C) fp32/bf16; weight: (C,1,3,3); bias: (C) or None; same-size output (padding = dilation).
-    `stats` (bf16 x, C % 8 == 0): a float64 tensor of 2 C + 1 elements that receives the BatchNorm statistics of the result
+    `stats` (bf16 / fp16 x, C % 8 == 0): a float64 tensor of 2 C + 1 elements that receives the BatchNorm statistics of the result
     (sum, sum of squares, rows: the buffer of bn._stats_fwd)."""
     if x.dim() != 4 or weight.shape[0] != x.shape[-1]:
         raise RuntimeError("dwconv3x3_nhwc: x must be (B,H,W,C) and weight (C,1,3,3)")
-    if stats is not None and not (x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and stats.dtype == torch.float64
+    if stats is not None and not (x.dtype in (torch.bfloat16, torch.float16) and x.shape[-1] % 8 == 0 and stats.dtype == torch.float64
                                   and stats.is_contiguous() and stats.numel() == 2 * x.shape[-1] + 1):
-        raise RuntimeError("dwconv3x3_nhwc(stats=...): bf16 input with C % 8 == 0 and a float64 buffer of 2 C + 1 elements")
+        raise RuntimeError("dwconv3x3_nhwc(stats=...): bf16 / fp16 input with C % 8 == 0 and a float64 buffer of 2 C + 1 elements")
     return _DWConv3x3.apply(x, weight, bias, int(dilation), stats)
 
 
@@ -188,7 +189,7 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     """act(bn(dwconv3x3(x))) with BATCH statistics, gradient-free (the EMA teacher's ASPP branches run their BatchNorms in
     training mode; daformer.py:10-62): two passes over x -- statistics of the convolution result without storing
     it, then convolution + normalisation + ReLU -- instead of convolution, statistics pass and BatchNorm pass over the
-    result.  x: (B, H, W, C) bf16 contiguous; bn: the (Sync)BatchNorm2d module (running buffers updated as in training)."""
+    result.  x: (B, H, W, C) bf16 / fp16 contiguous; bn: the (Sync)BatchNorm2d module (running buffers updated as in training)."""
     from . import bn as bnk
     B, H, W, C = x.shape
     w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
@@ -218,7 +219,7 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
 def tri_usable(x, convs, bns):
     """the three (conv, bn) pairs are depthwise 3x3 with dilations g, 2 g, 3 g and padding = dilation on a shape the one-pass
     kernel takes (csrc/dwconv.hip dwconv3x3_tri_kernel)"""
-    if len(convs) != 3 or not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()):
+    if len(convs) != 3 or not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 4 and x.is_contiguous()):
         return False
     B, H, W, C = x.shape
     d = [c.dilation[0] for c in convs]
@@ -242,9 +243,9 @@ def dwconv3x3_bn_act_nhwc_tri(x, convs, bns, relu):
                               lambda t: t.reshape(C, 9).t()) for c in convs]).contiguous()
     b3 = None if convs[0].bias is None else torch.stack([as_dtype(c.bias, torch.float32).detach() for c in convs]).contiguous()
     sums = torch.empty((3, 2 * C + 1), dtype=torch.float64, device=x.device)
-    lib = _lib.load_library()
+    lib, f16 = _lib.load_library(), x.dtype == torch.float16
     with on_device(x.device):
-        rc = lib.rfn_dwconv3x3_tri_stats(ptr(x), ptr(w3), ptr(b3), ptr(sums), B, H, W, C, int(g), current_stream(x.device))
+        rc = (lib.rfn_dwconv3x3_tri_stats_f16 if f16 else lib.rfn_dwconv3x3_tri_stats)(ptr(x), ptr(w3), ptr(b3), ptr(sums), B, H, W, C, int(g), current_stream(x.device))
     _lib.check(rc, "dwconv3x3_tri_stats")
     for k, bn in enumerate(bns):
         group = bnk.sync_group(bn)
@@ -266,7 +267,7 @@ def dwconv3x3_bn_act_nhwc_tri(x, convs, bns, relu):
     eps = (ctypes.c_float * 3)(*[float(b.eps) for b in bns])
     mom = (ctypes.c_float * 3)(*[float(b.momentum) for b in bns])
     with on_device(x.device):
-        rc = lib.rfn_dwconv3x3_tri_bn_act_fwd(ptr(x), ptr(w3), ptr(b3), ga, be, ptr(sums), rm, rv, yp, B, H, W, C, int(g), eps, mom,
+        rc = (lib.rfn_dwconv3x3_tri_bn_act_fwd_f16 if f16 else lib.rfn_dwconv3x3_tri_bn_act_fwd)(ptr(x), ptr(w3), ptr(b3), ga, be, ptr(sums), rm, rv, yp, B, H, W, C, int(g), eps, mom,
                                               1 if relu else 0, current_stream(x.device))
     _lib.check(rc, "dwconv3x3_tri_bn_act_fwd")
     for b in bns:

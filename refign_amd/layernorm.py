@@ -13,7 +13,7 @@ from . import _lib
 from ._tensor import current_stream, on_device, ptr, workspace
 from .params import as_dtype, grad_sink
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _LN_WS_ROWS = 256          # kLnMaxBlocks in csrc/layernorm.hip (checked against the ABI in the GPU tests)
 
 

@@ -173,7 +173,7 @@ class ConvBNReLU(nn.Module):
         """depthwise 3x3 -> BatchNorm(train): the convolution kernel leaves the batch statistics of its result behind
         (csrc/dwconv.hip STATS), the BatchNorm skips its statistics pass.  (_DW_BN_STATS = False: two passes.)"""
         c = self.conv
-        return (_DW_BN_STATS and x.is_cuda and x.dtype == torch.bfloat16 and cd == torch.bfloat16
+        return (_DW_BN_STATS and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and cd == x.dtype
                 and c.groups == c.in_channels == c.out_channels and c.kernel_size == (3, 3) and c.stride == (1, 1)
                 and c.padding == c.dilation and c.dilation[0] == c.dilation[1] and c.in_channels % 8 == 0)
 

@@ -26,6 +26,7 @@ class MultiTensorAdamW:
         self._t = 0
         self._synced_t = 0
         self._params = None
+        self._dev_step = None                              # step count on the device (step_amp: the host does not know it)
         self.launches = 0                                  # diagnostics / tests
         # state['step'] of the 1 000 parameters is brought up to date when somebody looks (checkpoint, torch's own step)
         optimizer.register_state_dict_pre_hook(lambda opt: self._sync_steps())
@@ -35,10 +36,16 @@ class MultiTensorAdamW:
         optimizer.register_load_state_dict_post_hook(lambda opt: self._reset())
 
     def _reset(self):
-        self._table = self._sig = self._steps = self._params = None
+        self._table = self._sig = self._steps = self._params = self._dev_step = None
         self._t = self._synced_t = 0
 
     def _sync_steps(self):
+        if self._dev_step is not None:
+            if self._steps is not None:
+                with torch.no_grad():
+                    for s in self._steps:
+                        s.copy_(self._dev_step[0])
+            return
         if self._steps is not None and self._synced_t != self._t:
             with torch.no_grad():
                 torch._foreach_add_(self._steps, float(self._t - self._synced_t))
@@ -118,3 +125,36 @@ class MultiTensorAdamW:
         self.launches += 1
         self.opt._opt_called = True                        # what Optimizer.step's wrapper tells the LR scheduler
         refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
+
+    def step_amp(self, found_inf):
+        """The step under loss scaling (amp.LossScaler): the same update, skipped on the device when `found_inf` is set.
+        The step count lives on the device (`device_step`, advanced by LossScaler.update when the step was taken); the
+        torch state's `step` tensors are brought up to date from it when somebody looks.  Returns False where it declines
+        (first step, configuration outside plain AdamW): the caller then steps torch's optimizer itself."""
+        sig = self._signature()
+        if self._table is None or sig != self._sig:
+            self._sync_steps()
+            self._table = self._dev_step = None
+            if not (self._plain() and self._build()):
+                return False
+        if self._dev_step is None:
+            self._dev_step = torch.full((1,), float(self._t), dtype=torch.float32, device=self._table[2])
+        args = []
+        for g in self.opt.param_groups:
+            b1, b2 = g["betas"]
+            args += [float(g["lr"]), b1, b2, float(g["eps"]), float(g["weight_decay"]), 1.0 - b1, 1.0 - b2]
+        host = np.asarray(args, dtype=np.float64)
+        table, n, dev = self._table
+        with torch.no_grad():
+            with on_device(dev):
+                rc = _lib.load_library().rfn_multi_adamw_amp_f32(ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
+                                                                 ptr(found_inf), ptr(self._dev_step), current_stream(dev))
+            _lib.check(rc, "multi_adamw_amp_f32")
+        self.launches += 1
+        self.opt._opt_called = True
+        refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
+        return True
+
+    @property
+    def device_step(self):
+        return self._dev_step

@@ -16,7 +16,7 @@ from torch.optim.optimizer import register_optimizer_step_post_hook
 from . import _lib
 from ._tensor import current_stream, on_device, ptr, workspace
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def derived(p, key, fn, refill=None):
@@ -62,30 +62,31 @@ def _build_plan(params):
                     continue
             del cache[key]
             _GENERATION[0] += 1
-    # plain fp32 -> bf16 casts of contiguous tensors: ONE launch of the multi-tensor cast kernel (csrc/reduce.hip);
-    # torch._foreach_copy_ with a dtype change is one tiny kernel per tensor.  Layout-changing copies stay per tensor.
+    # plain fp32 -> bf16 / fp16 casts of contiguous tensors: ONE launch of the multi-tensor cast kernel per device and dtype
+    # (csrc/reduce.hip); torch._foreach_copy_ with a dtype change is one tiny kernel per tensor.  Layout-changing copies stay
+    # per tensor.
     fast = [i for i, (d, s_) in enumerate(zip(dst, src))
-            if d.is_cuda and d.dtype == torch.bfloat16 and s_.dtype == torch.float32 and d.is_contiguous()
+            if d.is_cuda and d.dtype in _CAST16 and s_.dtype == torch.float32 and d.is_contiguous()
             and s_.is_contiguous() and d.numel() == s_.numel() and d.numel() > 0]
     casts = {}
     if len(fast) >= 4:
         for i in fast:
-            casts.setdefault(dst[i].device, []).append(i)
+            casts.setdefault((dst[i].device, dst[i].dtype), []).append(i)
         skip = set(fast)
     else:
         skip = set()
     # transposed bf16 copies (W^T of the Linear weights): one launch of the tile-transpose kernel instead of one strided
     # copy per tensor
     rest = [i for i in range(len(dst)) if i not in skip]
-    tr = [i for i in rest if dst[i].is_cuda and dst[i].dtype == torch.bfloat16 and src[i].dtype == torch.float32
+    tr = [i for i in rest if dst[i].is_cuda and dst[i].dtype in _CAST16 and src[i].dtype == torch.float32
           and dst[i].dim() == 2 and dst[i].is_contiguous() and src[i].dim() == 2 and src[i].t().is_contiguous()
           and src[i].numel() > 0]
     transposes = []
     if len(tr) >= 4:
         by_dev = {}
         for i in tr:
-            by_dev.setdefault(dst[i].device, []).append(i)
-        for dev, idx in by_dev.items():
+            by_dev.setdefault((dst[i].device, dst[i].dtype), []).append(i)
+        for (dev, _), idx in by_dev.items():
             transposes.append(_transpose_table([dst[i] for i in idx], [src[i] for i in idx], dev) +
                               (dev, [dst[i] for i in idx], [src[i] for i in idx]))
         skip = skip | set(tr)
@@ -108,12 +109,15 @@ def _build_plan(params):
             # (the tensors are kept next to the table: they own the memory the table points into)
             "casts": [_cast_table([dst[i] for i in idx], [src[i] for i in idx], dev) + (dev, [dst[i] for i in idx],
                                                                                          [src[i] for i in idx])
-                      for dev, idx in casts.items()],
+                      for (dev, _), idx in casts.items()],
             "rest": ([d for i, d in enumerate(dst) if i not in skip], [s_ for i, s_ in enumerate(src) if i not in skip]),
             "gen": _GENERATION[0]}
 
 
 _PERM_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+# 16-bit copy dtype -> (multi-tensor cast, multi-tensor transpose + cast) entry points of csrc/reduce.hip
+_CAST16 = {torch.bfloat16: ("rfn_multi_cast_f32_bf16", "rfn_multi_transpose_cast_f32_bf16"),
+           torch.float16: ("rfn_multi_cast_f32_f16", "rfn_multi_transpose_cast_f32_f16")}
 
 
 def _permute_table(dst, src, dev):
@@ -132,7 +136,7 @@ def _permute_table(dst, src, dev):
 
 
 def _cast_table(dst, src, dev):
-    """Chunk table of the multi-tensor fp32 -> bf16 cast kernel: {src*, dst*, n}, 24 bytes per chunk, built once."""
+    """Chunk table of the multi-tensor fp32 -> bf16 / fp16 cast kernel (one dst dtype per table): {src*, dst*, n}, 24 bytes per chunk, built once."""
     import numpy as np
     chunk = _lib.load_library().rfn_multi_cast_chunk_elems()
     rows = []
@@ -144,7 +148,7 @@ def _cast_table(dst, src, dev):
 
 def _transpose_table(dst, src, dev):
     """Tile table of the multi-tensor transpose + cast kernel: src views are (K, N) transposes of contiguous (N, K)
-    fp32 parameters, dst the contiguous (K, N) bf16 copies."""
+    fp32 parameters, dst the contiguous (K, N) bf16 or fp16 copies (one dtype per table)."""
     import numpy as np
     rows = []
     T = _lib.load_library().rfn_multi_transpose_tile()
@@ -157,10 +161,11 @@ def _transpose_table(dst, src, dev):
     return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
 
 
-def _multi_cast(table, nrows, dev):
+def _multi_cast(table, nrows, dev, dtype=torch.bfloat16):
+    name = _CAST16[dtype][0]
     with on_device(dev):
-        rc = _lib.load_library().rfn_multi_cast_f32_bf16(ptr(table), nrows, current_stream(dev))
-    _lib.check(rc, "multi_cast_f32_bf16")
+        rc = getattr(_lib.load_library(), name)(ptr(table), nrows, current_stream(dev))
+    _lib.check(rc, name)
 
 
 def _optimizer_step_post_hook(optimizer, args, kwargs):
@@ -200,11 +205,11 @@ def refresh(params, plan_key=None):
                 _PLANS.clear()
             _PLANS[plan_key] = plan
     with torch.no_grad():
-        for table, nrows, dev, _, _ in plan["casts"]:
-            _multi_cast(table, nrows, dev)
-        for table, ntiles, dev, _, _ in plan["transposes"]:
+        for table, nrows, dev, dsts, _ in plan["casts"]:
+            _multi_cast(table, nrows, dev, dsts[0].dtype)
+        for table, ntiles, dev, dsts, _ in plan["transposes"]:
             with on_device(dev):
-                rc = _lib.load_library().rfn_multi_transpose_cast_f32_bf16(ptr(table), ntiles, current_stream(dev))
+                rc = getattr(_lib.load_library(), _CAST16[dsts[0].dtype][1])(ptr(table), ntiles, current_stream(dev))
             _lib.check(rc, "multi_transpose_cast")
         for table, nrows, dev, _, _ in plan["permutes"]:
             with on_device(dev):
@@ -289,7 +294,7 @@ def grad_sink(p):
 
 
 def sum_rows(x, out=None, accumulate=False):
-    """out[n] (+)= sum over the leading dim of a contiguous (S, n) fp32/bf16 matrix, fp32 result (csrc/reduce.hip)."""
+    """out[n] (+)= sum over the leading dim of a contiguous (S, n) fp32 / bf16 / fp16 matrix, fp32 result (csrc/reduce.hip)."""
     S, n = x.shape
     if not x.is_cuda or n % 8 != 0 or x.dtype not in _DT or not x.is_contiguous():
         r = x.sum(0, dtype=torch.float32)

@@ -112,7 +112,7 @@ class Mlp(nn.Module):
         self.drop = nn.Dropout(drop)
 
     def forward(self, x, H, W, res=None, rowscale=None):
-        if x.is_cuda and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and type(self.act) is nn.GELU \
+        if x.is_cuda and not torch.is_grad_enabled() and x.dtype in (torch.bfloat16, torch.float16) and type(self.act) is nn.GELU \
                 and self.act.approximate == 'none' and self.drop.p == 0. and type(self.fc1) is Linear and not _f8.active():
             # gradient-free passes (EMA teacher's 40 views, ImageNet encoder): fc1 + depthwise 3x3 + GELU in ONE kernel, the 4C-wide
             # pre-activation never reaches HBM (csrc/mixffn.hip); fc2 (+ residual) follows as before
@@ -232,7 +232,7 @@ def _norm_pass(norm, x, fan=1):
     fan=2: ((n, n'), x') -- two handles on norm(x) for the two consumers inside the attention module (q projection, key / value
     path), whose gradients meet in the same kernel (layernorm.layer_norm_pass2)."""
     if _LN_PASS and x.is_cuda and torch.is_grad_enabled() and x.requires_grad and type(norm) is LayerNorm and x.shape[-1] % 8 == 0 \
-            and x.shape[-1] <= 1024 and x.dtype in (torch.float32, torch.bfloat16) and len(norm.normalized_shape) == 1:
+            and x.shape[-1] <= 1024 and x.dtype in (torch.float32, torch.bfloat16, torch.float16) and len(norm.normalized_shape) == 1:
         from .layernorm import layer_norm_pass, layer_norm_pass2
         if fan == 2 and _LN_FAN2:
             n, nb, xa = layer_norm_pass2(x, norm.weight, norm.bias, norm.eps)
@@ -523,11 +523,11 @@ class ASPPWrapper(nn.Module):
                 # three of each
                 dw_out = {}
                 sep = [m for m in mods if m.depthwise_separable]
-                if _ASPP_TRI and len(sep) == 3 and compute_dtype(x) == torch.bfloat16:
+                if _ASPP_TRI and len(sep) == 3 and compute_dtype(x) in (torch.bfloat16, torch.float16):
                     from .dwconv import dwconv3x3_bn_act_nhwc_tri, tri_usable
                     dws = [m.depthwise_conv for m in sep]
                     xh = x.permute(0, 2, 3, 1)
-                    if xh.dtype == torch.bfloat16 and xh.is_contiguous() and all(d.use_norm and d.training and d.act in (None, 'relu')
+                    if xh.dtype == compute_dtype(x) and xh.is_contiguous() and all(d.use_norm and d.training and d.act in (None, 'relu')
                                                                                  and d.act == dws[0].act for d in dws) \
                             and tri_usable(xh, [d.conv for d in dws], [d.bn for d in dws]):
                         ys = dwconv3x3_bn_act_nhwc_tri(xh, [d.conv for d in dws], [d.bn for d in dws], dws[0].act == 'relu')

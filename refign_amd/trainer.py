@@ -291,7 +291,16 @@ class Trainer:
     """fit-loop subset: `step(batch)` = one reference training_step including EMA, three backward passes, the single
     gradient all-reduce and the optimiser/scheduler step."""
 
-    def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None):
+    def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
+                 scaler_args=None):
+        """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
+        entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
+        scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
+        growth_interval); 'bf16' / 'bf16-mixed' -- bf16 autocast; 32 -- no autocast.  Anything else: ValueError."""
+        from .amp import parse_precision
+        self.precision = parse_precision(precision)
+        if scaler_args and self.precision != "16":
+            raise ValueError("Trainer: scaler_args needs precision=16")
         self.model = model
         if gc_interval is None:
             gc_interval = int(os.environ.get("RFN_GC_INTERVAL", "100"))
@@ -379,6 +388,10 @@ class Trainer:
         model._grad_buffer = self.grads                      # uda: second buffer for the concurrently running mixed pass
         model._scheduler = sch
         model._backward = self._backward
+        self.scaler = None
+        if self.precision == "16":
+            from .amp import LossScaler
+            self.scaler = LossScaler(self.grads.flat.device, **(scaler_args or {}))
         self.guard = None
         if dist.is_available() and dist.is_initialized():
             self.broadcast_parameters()
@@ -394,6 +407,8 @@ class Trainer:
         capturing = loss.is_cuda and torch.cuda.is_current_stream_capturing()
         overlap = last and self.data_parallel and os.environ.get("RFN_DDP_OVERLAP", "1") != "0"
         seg._GRAD_READY_CB = self.grads.on_ready if overlap else None
+        if self.scaler is not None:
+            loss = self.scaler.scale(loss)
         from . import mfma
         try:
             with mfma.deferred_wgrads():                 # Linear weight gradients: queued, launched per block in groups
@@ -430,7 +445,12 @@ class Trainer:
         try:
             # (the step's main-stream work on a stream of its own / of another priority: neutral, profiles/r05_main_priority_ab.txt --
             # HIP offers two priority levels here, (0, -1), and the teacher's stream already has the high one)
-            self.model.training_step(batch, batch_idx)
+            if self.precision is None:
+                self.model.training_step(batch, batch_idx)
+            else:
+                dtype = {"16": torch.float16, "bf16": torch.bfloat16, "32": None}[self.precision]
+                with torch.autocast("cuda", dtype=dtype or torch.float32, enabled=dtype is not None):
+                    self.model.training_step(batch, batch_idx)
             if self.guard is not None:
                 self.guard.note(f"step {self._steps_done} queued")
         finally:
@@ -468,6 +488,21 @@ class _OptimizerProxy:
 
     def step(self):
         self.t.grads.all_reduce_mean(self.t.bucket_mb)        # (and what a concurrently run pass accumulated on the side)
+        sc = self.t.scaler
+        if sc is not None:
+            # GradScaler.step + update: the reduced (scaled) gradients are unscaled in place -- an inf on any rank reached every
+            # rank through the sum, so all ranks skip together -- then AdamW, skipped on the device when found_inf is set, then
+            # the new scale.  torch's own step (first step, non-plain configurations) needs the flag on the host.
+            sc.unscale_(self.t.grads.flat)
+            if self.t.fast_step is not None and self.t.fast_step.step_amp(sc.found_inf):
+                sc.update(self.t.fast_step.device_step)
+                return
+            if not bool(sc.found_inf.item()):
+                self.t.optimizer.step()
+            else:
+                self.t.optimizer._opt_called = True       # a skipped step still lets the LR scheduler advance
+            sc.update(None)
+            return
         if self.t.fast_step is not None:
             self.t.fast_step.step()
         else:

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._tensor import current_stream, on_device, ptr
 
-_DT = {torch.float32: 0, torch.bfloat16: 1}
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 class _UpCat(torch.autograd.Function):
