@@ -20,6 +20,67 @@ import torch.nn as nn
 
 from .params import mark_grad_sink
 
+LIGHTNING_VERSION = "1.5.10"        # the checkpoint layout of Trainer.save_checkpoint (the reference's requirements.txt)
+_OWN_KEY = "refign_amd"             # what that layout has no slot for
+_IMPL_FLAGS = ("fused", "foreach", "capturable", "differentiable")   # AdamW flags that pick an implementation
+
+
+def _rng_state(dev):
+    """This process's host RNG states and its device generator's (numpy's key as a list: the file stays plain data)."""
+    import random
+
+    import numpy as np
+    kind, key, pos, has_gauss, gauss = np.random.get_state()
+    return {"python": random.getstate(), "numpy": (kind, key.tolist(), int(pos), int(has_gauss), float(gauss)),
+            "torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None}
+
+
+def _set_rng_state(st, dev):
+    import random
+
+    import numpy as np
+    random.setstate(st["python"])
+    kind, key, pos, has_gauss, gauss = st["numpy"]
+    np.random.set_state((kind, np.asarray(key, dtype=np.uint32), pos, has_gauss, gauss))
+    torch.set_rng_state(st["torch"])
+    if dev.type == "cuda" and st.get("cuda") is not None:
+        torch.cuda.set_rng_state(st["cuda"], dev)
+
+
+def _seed_rank(global_step, rank):
+    """Resume without saved RNG states: python, numpy, torch CPU and device generators seeded from (global_step, rank)."""
+    import random
+
+    import numpy as np
+    seed = (int(global_step) * 1000003 + int(rank)) % 2 ** 32
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+def _write_file(obj, f):
+    """The serialiser of save_checkpoint (a name of its own: the tests slow it down and make it fail part-way)."""
+    torch.save(obj, f)
+
+
+def _atomic_save(obj, filepath):
+    """`obj` to a temporary file next to `filepath`, flushed to the disk, then renamed over it: a reader sees the old file
+    or the complete new one, never a part."""
+    os.makedirs(os.path.dirname(os.path.abspath(filepath)), exist_ok=True)
+    tmp = f"{filepath}.tmp{os.getpid()}"
+    try:
+        with open(tmp, "wb") as f:
+            _write_file(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, filepath)
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
 
 class LinearWarmupPolynomialLR(torch.optim.lr_scheduler.LRScheduler):
     """helpers/lr_scheduler.py:10-57: linear warm-up from warmup_ratio*lr over warmup_iters, then polynomial decay to
@@ -261,7 +322,9 @@ class FlatGradBuffer:
 class StallGuard:
     """A multi-rank run that makes no progress for `limit` seconds (RFN_STALL_S, default 600; RFN_BENCH_STALL_S is still read) says
     where it stopped on stderr and exits with code 17 instead of hanging the node in a collective.  `note(what)` is the heartbeat:
-    Trainer.step calls it around every step; bench.py adds its own phases.  One daemon thread per process."""
+    Trainer.step calls it around every step; bench.py adds its own phases.  One daemon thread per process.
+    `paused(what)`: a context in which the guard does not fire (checkpoint I/O, whose length depends on the disk, not on the
+    other ranks); the clock restarts when it ends.  `stop()` ends the thread."""
 
     def __init__(self, rank, world, limit=None):
         import threading
@@ -269,19 +332,43 @@ class StallGuard:
         self.rank, self.world = rank, world
         self.limit = float(os.environ.get("RFN_STALL_S", os.environ.get("RFN_BENCH_STALL_S", "600"))) if limit is None else float(limit)
         self.progress = [time.monotonic(), "start"]
-        threading.Thread(target=self._watch, daemon=True, name="refign-stall-guard").start()
+        self._paused, self._stop = 0, threading.Event()
+        self._thread = threading.Thread(target=self._watch, daemon=True, name="refign-stall-guard")
+        self._thread.start()
 
     def note(self, what):
         import time
         self.progress[0], self.progress[1] = time.monotonic(), what
 
+    def pause(self, what):
+        self._paused += 1
+        self.note(what)
+
+    def resume(self, what):
+        self.note(what)                              # before the count drops: the guard never sees the time spent paused
+        self._paused = max(0, self._paused - 1)
+
+    def paused(self, what):
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            self.pause(what)
+            try:
+                yield
+            finally:
+                self.resume(f"{what} done")
+        return ctx()
+
+    def stop(self):
+        self._stop.set()
+
     def _watch(self):
         import sys
         import time
-        while True:
-            time.sleep(min(5.0, max(0.2, self.limit / 4)))
+        while not self._stop.wait(min(5.0, max(0.2, self.limit / 4))):
             idle = time.monotonic() - self.progress[0]
-            if idle > self.limit:
+            if idle > self.limit and not self._paused:
                 print(f"refign_amd rank {self.rank}/{self.world}: no progress for {idle:.0f} s after '{self.progress[1]}'; giving up",
                       file=sys.stderr, flush=True)
                 os._exit(17)
@@ -292,11 +379,12 @@ class Trainer:
     gradient all-reduce and the optimiser/scheduler step."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
-                 scaler_args=None):
+                 scaler_args=None, ckpt_path=None):
         """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
         entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
         scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
-        growth_interval); 'bf16' / 'bf16-mixed' -- bf16 autocast; 32 -- no autocast.  Anything else: ValueError."""
+        growth_interval); 'bf16' / 'bf16-mixed' -- bf16 autocast; 32 -- no autocast.  Anything else: ValueError.
+        `ckpt_path` (Lightning's `fit(ckpt_path=...)`): a file of save_checkpoint to continue from (load_checkpoint)."""
         from .amp import parse_precision
         self.precision = parse_precision(precision)
         if scaler_args and self.precision != "16":
@@ -397,6 +485,8 @@ class Trainer:
             self.broadcast_parameters()
             if dist.get_world_size() > 1:                    # a rank that never arrives must not hang the others for ever
                 self.guard = StallGuard(dist.get_rank(), dist.get_world_size())
+        if ckpt_path is not None:
+            self.load_checkpoint(ckpt_path)
 
     def _backward(self, loss, retain_graph=False, last=False):
         """What Lightning's manual_backward does, plus: during the LAST backward pass of a step under data parallelism
@@ -462,9 +552,141 @@ class Trainer:
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.model.logged.items()} \
             if os.environ.get("RFN_LOG_LOSSES") else None
 
+    # -- checkpoints ---------------------------------------------------------------------------------------------------
+    def _io(self, what):
+        """Checkpoint I/O runs outside step(): the stall guard must not take a slow disk for a lost rank."""
+        import contextlib
+        return self.guard.paused(what) if self.guard is not None else contextlib.nullcontext()
+
+    def save_checkpoint(self, filepath, weights_only=False):
+        """Write the run's state to `filepath` in the dict layout of PyTorch-Lightning 1.5.10 (the reference's version):
+        `epoch` (0: this trainer counts steps only), `global_step` (model.global_step, the steps done),
+        `pytorch-lightning_version`, `state_dict` (model.state_dict(): the reference's key names), `loops` (the step count,
+        for the layout's sake; not read back), `callbacks` ({}), `optimizer_states` ([the torch AdamW's state_dict()], step
+        counts brought up from the device first), `lr_schedulers` ([scheduler.state_dict()]) and, under precision=16,
+        `native_amp_scaling_state` (LossScaler.state_dict(), GradScaler's format).  What that layout has no slot for goes
+        under `refign_amd`: every rank's RNG states (python `random`, numpy, torch CPU, the rank's device generator),
+        the world size, the precision and the scaler's skipped-step count.  Whether Lightning itself resumes from this
+        file is not tested (it is not a dependency); what is tested is the layout and that `state_dict` is what the
+        reference's strict loader takes.
+        `weights_only=True`: only epoch / global_step / version / state_dict (loads through `pretrained=` / load_weights).
+        Call between steps, on every rank: the ranks' RNG states are gathered to rank 0, which alone writes -- to a
+        temporary file in the same directory, moved into place when complete, so a save that fails part-way leaves the
+        previous file as it was -- and every rank returns once the file is in place (an error on rank 0 raises on all).
+        Not exact under precision=32 (parity mode): see DESIGN.md, Checkpoints."""
+        dist_on = dist.is_available() and dist.is_initialized()
+        rank = dist.get_rank() if dist_on else 0
+        dev = self.grads.flat.device
+        with self._io(f"save_checkpoint {filepath}"):
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)           # everything the last step queued is in the tensors written below
+            ckpt = {"epoch": 0, "global_step": int(self.model.global_step), "pytorch-lightning_version": LIGHTNING_VERSION,
+                    "state_dict": self.model.state_dict()}
+            if not weights_only:
+                rng = [_rng_state(dev)]
+                if dist_on:
+                    rng = [None] * dist.get_world_size()
+                    dist.all_gather_object(rng, _rng_state(dev))
+                gs = ckpt["global_step"]
+                progress = {"ready": gs, "started": gs, "processed": gs, "completed": gs}
+                ckpt["loops"] = {"fit_loop": {"epoch_loop.batch_progress": {"total": dict(progress), "current": dict(progress)}}}
+                ckpt["callbacks"] = {}
+                ckpt["optimizer_states"] = [self.optimizer.state_dict()]   # (MultiTensorAdamW's pre-hook syncs `step`)
+                ckpt["lr_schedulers"] = [self.scheduler.state_dict()]
+                if self.scaler is not None:
+                    ckpt["native_amp_scaling_state"] = self.scaler.state_dict()
+                ckpt[_OWN_KEY] = {"world_size": len(rng), "precision": self.precision, "rng": rng,
+                                  "scaler_skipped": self.scaler.skipped_steps() if self.scaler is not None else 0}
+            err = None
+            if rank == 0:
+                try:
+                    _atomic_save(ckpt, filepath)
+                except Exception as e:
+                    if not dist_on:
+                        raise
+                    err = e
+            if dist_on:
+                box = [None if err is None else f"{type(err).__name__}: {err}"]
+                dist.broadcast_object_list(box, src=0)        # the others wait here until the file is in place
+                if err is not None:
+                    raise err
+                if box[0] is not None:
+                    raise RuntimeError(f"Trainer.save_checkpoint: rank 0 could not write {filepath}: {box[0]}")
+
+    def load_checkpoint(self, filepath):
+        """Continue the run saved in `filepath` (save_checkpoint, or a Lightning file of the reference): the next step()
+        is the one the saved run would have taken next.  Model: state_dict loaded strictly, global_step restored, every
+        cached copy of a parameter (16-bit / transposed copies, fp8 teacher weights) re-made from the loaded values, captured
+        graphs, folded BatchNorm weights and packed frozen weights dropped (they are re-made on use).  Optimizer: the torch
+        AdamW's state (the running trainer keeps its own implementation flags: fused / foreach / capturable); the fused step
+        rebuilds its chunk table from it.  Scheduler, and the loss scaler under precision=16 (a file without a scaler state:
+        fresh scaler, warning; a scaler state into a trainer without loss scaling: ignored, warning).  RNG: this rank's
+        saved states; a file without them or written by another world size (a reference Lightning file) seeds rank r from
+        (global_step, r) instead, with a warning -- the random draws then differ from the uninterrupted run's.
+        Every rank calls it; each reads the file itself."""
+        import warnings
+        dist_on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
+        dev = self.grads.flat.device
+        model = self.model
+        with self._io(f"load_checkpoint {filepath}"):
+            # (full pickle, as Lightning 1.5 loads: a reference file carries its hyper-parameters as python objects)
+            ckpt = torch.load(filepath, map_location="cpu", weights_only=False)
+            if "optimizer_states" not in ckpt or "lr_schedulers" not in ckpt:
+                raise KeyError(f"Trainer.load_checkpoint: {filepath} holds the model only (save_checkpoint(weights_only=True)); "
+                               f"load it through the model's `pretrained=` / load_weights to start a new run from it")
+            model.load_state_dict(ckpt["state_dict"], strict=True)      # (uda: drops the captured graphs)
+            model.global_step = int(ckpt.get("global_step", 0))
+            for k in ("_imnet_prefetch", "_class_prefetch", "_align_prefetch"):   # made for a batch of the run before
+                if k in model.__dict__:
+                    model.__dict__[k] = None
+            from .params import refresh
+            refresh(model.parameters())               # cached 16-bit copies re-filled from the loaded values, others dropped
+            if getattr(model, "teacher_f8", False):
+                from . import f8
+                f8.requantize()                       # K5: e4m3 teacher weights from the re-filled bf16 copies
+            self._load_optimizer_state(ckpt["optimizer_states"][0])
+            self.scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+            own = ckpt.get(_OWN_KEY) or {}
+            amp = ckpt.get("native_amp_scaling_state")
+            if self.scaler is not None:
+                if amp:
+                    self.scaler.load_state_dict(amp)
+                    self.scaler._skipped.fill_(float(own.get("scaler_skipped", 0)))
+                else:
+                    warnings.warn(f"Trainer.load_checkpoint: {filepath} holds no loss-scaler state; the fp16 loss scaler "
+                                  f"starts fresh")
+            elif amp:
+                warnings.warn(f"Trainer.load_checkpoint: {filepath} holds a loss-scaler state, this trainer does not scale "
+                              f"(precision={self.precision}); ignored")
+            rng = own.get("rng")
+            if rng and int(own.get("world_size", -1)) == world and len(rng) == world:
+                _set_rng_state(rng[rank], dev)
+            else:
+                why = "no RNG states" if not rng else f"RNG states of {own.get('world_size')} ranks, this run has {world}"
+                warnings.warn(f"Trainer.load_checkpoint: {filepath} has {why}; rank {rank} is seeded from (global_step, rank) "
+                              f"-- the resumed run's random draws differ from the uninterrupted run's")
+                _seed_rank(model.global_step, rank)
+
+    def _load_optimizer_state(self, state):
+        """torch's Optimizer.load_state_dict with the param groups checked by name and the running optimizer's
+        implementation flags kept (a file from a fused_optimizer=False trainer loads into a fused one and back; the `step`
+        tensors then sit where these flags want them)."""
+        mine = self.optimizer.param_groups
+        names = [g.get("name") for g in state["param_groups"]]
+        if names != [g.get("name") for g in mine]:
+            raise ValueError(f"Trainer.load_checkpoint: optimizer param groups {names} != this model's "
+                             f"{[g.get('name') for g in mine]}")
+        state = dict(state, param_groups=[{**g, **{k: cur[k] for k in _IMPL_FLAGS if k in cur}}
+                                          for g, cur in zip(state["param_groups"], mine)])
+        self.optimizer.load_state_dict(state)         # (MultiTensorAdamW's post-hook drops its chunk table and device step)
 
     def close(self):
-        """Give the process its cyclic garbage collector back (step() runs with it disabled between its own collections)."""
+        """Give the process its cyclic garbage collector back (step() runs with it disabled between its own collections)
+        and stop the stall guard."""
+        if self.guard is not None:
+            self.guard.stop()
+            self.guard = None
         if self.gc_interval and self._steps_done:
             import gc
             gc.enable()
