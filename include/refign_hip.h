@@ -559,6 +559,24 @@ int rfn_bn_train_bwd(const void* x, const void* grad_y, const double* fwd_sums, 
 int rfn_upsample_ce(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum, int B,
                     int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16, rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Tail of the evaluation forward in one kernel (csrc/evaltail.hip): from the head's low-resolution crop logits to arg-max
+ * labels and confusion counts -- models/segmentation_model.py:304-382 (whole_inference / slide_inference) + the arg-max and
+ * bincount of helpers/metrics.py IoU.update, without the up-sampled logits ever existing.
+ * crop_logits (nbox * B, C, h, w) contiguous, crop k of image b at row k * B + b; dtype 0 fp32, 1 bf16, 2 f16.  boxes: HOST
+ * array nbox x (y1, y2, x1, x2) in image pixels, read at call time (it travels in the kernel arguments: the call can be
+ * captured into a graph).  Per image pixel (y, x): for every box that contains it the bilinear sample (align_corners = False,
+ * ATen's source-index rule with scale h / (y2 - y1), w / (x2 - x1)) of that crop's logits at (y - y1, x - x1); the mean over
+ * those boxes in fp32; label = the smallest class index with the largest mean.  labels (B, H, W) uint8 <- label (or NULL).
+ * With target (B, H, W) int64: where target != ignore_index and 0 <= target < C, confmat[target][label] += 1; confmat (C, C)
+ * int64 is ADDED to (or NULL).  Whole-image inference: nbox = 1, box = (0, H, 0, W).
+ * Errors (nothing is launched): C > 32, nbox > 64, a box outside the image, boxes of different sizes, boxes that leave a
+ * pixel uncovered (checked here on the host), labels and confmat both NULL, confmat without target.  B * H * W < 2^31.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_slide_argmax_confmat(const void* crop_logits, int dtype, int B, int C, int h, int w, const int* boxes, int nbox, int H,
+                             int W, const long* target, int ignore_index, unsigned char* labels, long* confmat,
+                             rfn_stream_t stream);
+
 /* fp32-RESULT variants (split-bf16 parity mode, refign_amd/split32.py): bf16 operands whose reduction index carries the
  * three split products side by side, fp32 accumulate, fp32 bias / residual / result (leading dimension ldy in floats).
  * rfn_conv2d_nhwc_o32: (B, H, W, C) = the convolution's input side, N output channels; transposed = 0: Y (B, OH, OW, N) from

@@ -113,6 +113,8 @@ SIGNATURES = {
     "rfn_ffn_fc1_dw_gelu_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "rfn_split3_cat_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rfn_upsample_ce": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
+    "rfn_slide_argmax_confmat": (c_int, [c_void_p] + [c_int] * 5 + [ctypes.POINTER(c_int)] + [c_int] * 3 + [c_void_p, c_int,
+                                                                                                       c_void_p, c_void_p, c_void_p]),
     "rfn_bn_stats_fwd": (c_int, [c_void_p] * 2 + [ctypes.c_long, c_int, c_int, c_void_p]),
     "rfn_bn_apply_fwd": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "rfn_bn_apply_fwd_ld": (c_int, [c_void_p] * 4 + [ctypes.c_long] + [c_void_p] * 3 + [ctypes.c_long, c_int, c_float, c_float, c_int, c_int, c_void_p]),

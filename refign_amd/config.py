@@ -98,3 +98,24 @@ def build_model(cfg, overrides=None):
     metrics = init.pop("metrics", {})
     kwargs = {k: (v if k in ("optimizer_init", "lr_scheduler_init") else build(v)) for k, v in init.items()}
     return resolve(model["class_path"])(metrics=metrics, **kwargs)
+
+
+def trainer_kwargs(cfg):
+    """What the loops of refign_amd.trainer.Trainer take from a loaded YAML's `trainer:` section (LightningCLI's Trainer
+    arguments): `max_steps`, `sync_batchnorm`, `precision` as they stand, `val_every_n_steps` from the ValEveryNSteps
+    callback's `every_n_steps` and `save_last` from ModelCheckpoint, found in the `callbacks` list by class_path.  Missing
+    entries: None (False for the two flags).  Loggers, LearningRateMonitor and every other Lightning argument stay ignored.
+    -> Trainer(model, sync_batchnorm=, precision=) and Trainer.fit(max_steps=, val_every_n_steps=, save_last=)."""
+    tr = (cfg or {}).get("trainer") or {}
+    out = {"max_steps": tr.get("max_steps"), "val_every_n_steps": None, "save_last": False,
+           "sync_batchnorm": bool(tr.get("sync_batchnorm", False)), "precision": tr.get("precision")}
+    callbacks = tr.get("callbacks") or []
+    for cb in ([callbacks] if is_spec(callbacks) else callbacks):
+        if not is_spec(cb):
+            continue
+        name, args = cb["class_path"].rsplit(".", 1)[-1], cb.get("init_args") or {}
+        if name == "ValEveryNSteps":
+            out["val_every_n_steps"] = args.get("every_n_steps")
+        elif name == "ModelCheckpoint":
+            out["save_last"] = bool(args.get("save_last", False))
+    return out

@@ -1,0 +1,133 @@
+"""The tail of the evaluation forward as one HIP kernel (csrc/evaltail.hip, rfn_slide_argmax_confmat): from the head's
+low-resolution crop logits (DomainAdaptationSegmentationModel.crop_logits) straight to arg-max labels and confusion counts.
+
+Semantics, per image pixel: for every crop box that contains it the bilinear sample (align_corners=False, ATen's rule) of
+that crop's logits; the mean over those boxes in fp32; the first largest class.  With a target, pixels whose target is
+`ignore_index` or outside [0, C) are skipped, the others counted in a (C, C) int64 matrix (rows = target).  That is what
+forward() -> arg-max -> IoU.update computes when the label size equals the image size, without the up-sampled logits, the
+image-sized sum and count tensors and the host synchronisation of slide_inference's cover assert (the cover is checked on
+the host from the box list).  One difference: under 16-bit autocast forward() rounds every up-sampled crop to 16 bits before
+averaging; the kernel averages the fp32 samples.
+
+`RFN_EVAL_FUSED=0` keeps Trainer.validate / test / predict on validation_step / test_step / predict_step."""
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+from ._tensor import current_stream, on_device, ptr
+
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+MAX_CLASSES = 32
+_BOXES = {}
+
+
+def enabled():
+    return os.environ.get("RFN_EVAL_FUSED", "1") != "0"
+
+
+def _c_boxes(boxes):
+    key = tuple(int(v) for b in boxes for v in b)
+    arr = _BOXES.get(key)
+    if arr is None:
+        if len(_BOXES) > 256:
+            _BOXES.clear()
+        arr = _BOXES[key] = (ctypes.c_int * len(key))(*key)
+    return arr
+
+
+def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255, want_labels=True, confmat=None):
+    """The kernel call.  crop_logits (nbox * B, C, h, w) on the device, crop k of image b at row k * B + b; boxes: nbox x
+    (y1, y2, x1, x2); size = (H, W).  -> labels (B, H, W) uint8 or None; with `confmat` (C, C) int64 the counts against
+    `target` (B, H, W) int64 are ADDED to it.  Nothing here waits for the device."""
+    if not crop_logits.is_cuda:
+        raise RuntimeError("evaltail: crop_logits must be a HIP (cuda:N) tensor: refign_amd has no CPU path")
+    if crop_logits.dtype not in _DT or crop_logits.dim() != 4:
+        raise RuntimeError(f"evaltail: crop_logits (N, C, h, w) in fp32 / bf16 / fp16 expected, got "
+                           f"{tuple(crop_logits.shape)} {crop_logits.dtype}")
+    nbox = len(boxes)
+    N, C, h, w = crop_logits.shape
+    if nbox == 0 or N % nbox:
+        raise RuntimeError(f"evaltail: {N} crop logits for {nbox} boxes")
+    B, (H, W) = N // nbox, size
+    lg = crop_logits.contiguous()
+    dev = lg.device
+    if target is not None:
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W) or target.device != dev:
+            raise RuntimeError(f"evaltail: target ({B}, {H}, {W}) int64 on {dev} expected, got {tuple(target.shape)} "
+                               f"{target.dtype} on {target.device}")
+        target = target.contiguous()
+    if confmat is not None and (confmat.dtype != torch.int64 or tuple(confmat.shape) != (C, C) or confmat.device != dev
+                                or not confmat.is_contiguous()):
+        raise RuntimeError(f"evaltail: confmat ({C}, {C}) int64 contiguous on {dev} expected")
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_labels else None
+    with on_device(dev):
+        rc = _lib.load_library().rfn_slide_argmax_confmat(ptr(lg), _DT[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
+                                                          ptr(target), int(ignore_index), ptr(labels), ptr(confmat),
+                                                          current_stream(dev))
+    _lib.check(rc, "slide_argmax_confmat")
+    return labels
+
+
+def _size(x, out_size):
+    H, W = x.shape[-2:]
+    if out_size is not None and tuple(int(v) for v in out_size) != (H, W):
+        raise ValueError(f"evaltail: output size {tuple(out_size)} != image size {(H, W)}: the second interpolation of "
+                         f"forward(x, out_size) is not the identity; use forward()")
+    return H, W
+
+
+@torch.no_grad()
+def labels(model, x, out_size=None):
+    """-> (B, H, W) uint8: arg-max of model.forward(x) without the full-resolution logits.  `out_size`: None or the image size."""
+    size = _size(x, out_size)
+    logits, boxes = model.crop_logits(x)
+    return slide_argmax_confmat(logits, boxes, size)
+
+
+@torch.no_grad()
+def confusion(model, x, target, ignore_index=255):
+    """-> (C, C) int64 on the device: counts of (target, arg-max of model.forward(x, target.shape[-2:]))."""
+    size = _size(x, target.shape[-2:])
+    logits, boxes = model.crop_logits(x)
+    out = torch.zeros((logits.shape[1],) * 2, dtype=torch.int64, device=logits.device)
+    slide_argmax_confmat(logits, boxes, size, target, ignore_index, want_labels=False, confmat=out)
+    return out
+
+
+def _model_ok(model, x):
+    return enabled() and hasattr(model, "crop_logits") and torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and \
+        getattr(getattr(model, "head", None), "num_classes", MAX_CLASSES + 1) <= MAX_CLASSES
+
+
+def eval_step(model, metrics, batch, src_name):
+    """The fused validation / test step: one kernel call, its count matrix added to every metric of this dataset.  -> True when
+    it ran; False when a condition does not hold (RFN_EVAL_FUSED=0; not a segmentation model with crop_logits; tensors not on
+    the device; more than 32 classes; label size != image size; a selected metric that is not an IoU over the head's classes
+    with one common ignore_index; no metric selected) -- the caller then runs the model's own step."""
+    from .metrics import IoU
+    x, y = batch.get('image'), batch.get('semantic')
+    if not _model_ok(model, x) or not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.int64 or \
+            tuple(y.shape) != (x.shape[0], *x.shape[-2:]):
+        return False
+    chosen = [m for k, m in metrics.items() if src_name in k]
+    C = model.head.num_classes
+    if not chosen or any(not isinstance(m, IoU) or m.num_classes != C or m.ignore_index is None for m in chosen) or \
+            len({int(m.ignore_index) for m in chosen}) != 1:
+        return False
+    delta = confusion(model, x, y, chosen[0].ignore_index)
+    for m in chosen:
+        m.add_confusion(delta)
+    return True
+
+
+def predict_step(model, batch, save_dir, orig_size=None, dataset_name=None):
+    """The fused predict step -> the (B, H, W) uint8 label maps written (numpy), or None when a condition does not hold."""
+    x = batch.get('image')
+    if not _model_ok(model, x) or (orig_size is not None and tuple(int(v) for v in orig_size) != tuple(x.shape[-2:])):
+        return None
+    preds = labels(model, x).cpu().numpy()
+    if save_dir is not None:
+        model.write_label_pngs(preds, batch['filename'], save_dir, dataset_name)
+    return preds

@@ -42,6 +42,17 @@ class IoU(nn.Module):
 
     __call__ = update                                     # compute_on_step=False: a call only accumulates
 
+    @torch.no_grad()
+    def add_confusion(self, delta):
+        """Add a (C, C) count matrix (rows = target, columns = prediction) made elsewhere -- the fused evaluation tail
+        (refign_amd/evaltail.py) counts on the device in one kernel -- to the state; equals update() on the labels behind it."""
+        if tuple(delta.shape) != (self.num_classes, self.num_classes) or delta.is_floating_point():
+            raise ValueError(f"IoU.add_confusion: an integer ({self.num_classes}, {self.num_classes}) matrix expected, got "
+                             f"{tuple(delta.shape)} {delta.dtype}")
+        if self.confmat.device != delta.device:
+            self.confmat = self.confmat.to(delta.device)
+        self.confmat += delta.to(torch.long)
+
     def _scores(self, confmat):
         inter = torch.diag(confmat)
         union = confmat.sum(0) + confmat.sum(1) - inter

@@ -102,10 +102,15 @@ class LinearWarmupPolynomialLR(torch.optim.lr_scheduler.LRScheduler):
 
 
 class ValEveryNSteps:
-    """helpers/callbacks.py: validation every N steps (evaluation is out of scope here; kept so configs parse)."""
+    """helpers/callbacks.py: validation every N steps.  Built from a config's callback list as in the reference; the rule
+    itself (`should_validate`, helpers/callbacks.py:19) is what Trainer.fit(val_every_n_steps=) applies, and
+    config.trainer_kwargs reads `every_n_steps` out of the YAML for it."""
 
     def __init__(self, every_n_steps):
         self.every_n_steps = every_n_steps
+
+    def should_validate(self, global_step):
+        return bool(self.every_n_steps) and global_step != 0 and global_step % self.every_n_steps == 0
 
 
 class FlatGradBuffer:
@@ -375,8 +380,9 @@ class StallGuard:
 
 
 class Trainer:
-    """fit-loop subset: `step(batch)` = one reference training_step including EMA, three backward passes, the single
-    gradient all-reduce and the optimiser/scheduler step."""
+    """`step(batch)` = one reference training_step including EMA, three backward passes, the single gradient all-reduce and
+    the optimiser/scheduler step; `fit` / `validate` / `test` / `predict` = the loops of the Lightning entry points the
+    reference is driven through (run.py fit | validate | test | predict); `save_checkpoint` / `load_checkpoint`."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
                  scaler_args=None, ckpt_path=None):
@@ -535,12 +541,8 @@ class Trainer:
         try:
             # (the step's main-stream work on a stream of its own / of another priority: neutral, profiles/r05_main_priority_ab.txt --
             # HIP offers two priority levels here, (0, -1), and the teacher's stream already has the high one)
-            if self.precision is None:
+            with self._autocast():
                 self.model.training_step(batch, batch_idx)
-            else:
-                dtype = {"16": torch.float16, "bf16": torch.bfloat16, "32": None}[self.precision]
-                with torch.autocast("cuda", dtype=dtype or torch.float32, enabled=dtype is not None):
-                    self.model.training_step(batch, batch_idx)
             if self.guard is not None:
                 self.guard.note(f"step {self._steps_done} queued")
         finally:
@@ -551,6 +553,156 @@ class Trainer:
             seg._DEVICE_CROPS.clear()
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.model.logged.items()} \
             if os.environ.get("RFN_LOG_LOSSES") else None
+
+    # -- loops ---------------------------------------------------------------------------------------------------------
+    def _autocast(self):
+        """The autocast of this trainer's `precision` for step() and the evaluation loops (None: whatever the caller entered)."""
+        import contextlib
+        if self.precision is None:
+            return contextlib.nullcontext()
+        dtype = {"16": torch.float16, "bf16": torch.bfloat16, "32": None}[self.precision]
+        return torch.autocast("cuda", dtype=dtype or torch.float32, enabled=dtype is not None)
+
+    @staticmethod
+    def _named(loaders):
+        """{dataset name: iterable} in the order of the reference's datamodule.idx_to_name[split], or one bare iterable ("")."""
+        from collections.abc import Mapping
+        return list(loaders.items()) if isinstance(loaders, Mapping) else [("", loaders)]
+
+    def _to_device(self, batch):
+        dev = self.grads.flat.device
+        moved = {k: v.to(dev, non_blocking=True) for k, v in batch.items() if torch.is_tensor(v) and v.device != dev}
+        return dict(batch, **moved) if moved else batch
+
+    def _evaluation(self, what, loaders, per_batch, at_end=None, metrics=None):
+        """The frame of validate / test / predict: model in eval(), no_grad, this trainer's autocast, `per_batch(batch,
+        batch_idx, dataloader_idx, name)` over every loader, `at_end()` once; then every module back in the mode it was in
+        (through model.train(), which drops captured graphs and mode-dependent caches: the student passes are captured again
+        on the next steps) and what the last step prefetched for its successor dropped (made under the graphs of before; the
+        next step computes it itself, the numbers are the same).  If a batch raises, the metrics are reset."""
+        model = self.model
+        modes = [(m, m.training) for m in model.modules()]
+        model.eval()
+        try:
+            with torch.no_grad():
+                with self._autocast():
+                    for idx, (name, loader) in enumerate(self._named(loaders)):
+                        for i, batch in enumerate(loader):
+                            if self.guard is not None:
+                                self.guard.note(f"{what}: dataset {idx} '{name}' batch {i}")
+                            per_batch(self._to_device(batch), i, idx, name)
+                out = at_end() if at_end is not None else None
+            return out
+        except BaseException:
+            if metrics is not None:
+                metrics.reset()
+            raise
+        finally:
+            model.train(modes[0][1])
+            for m, mode in modes:
+                m.training = mode
+            for k in ("_imnet_prefetch", "_class_prefetch", "_align_prefetch"):
+                if k in model.__dict__:
+                    model.__dict__[k] = None
+            if self.guard is not None:
+                self.guard.note(f"{what} done")
+
+    def _metric_loop(self, split, loaders):
+        from . import evaltail
+        model = self.model
+        metrics = getattr(model, "valid_metrics" if split == "validation" else "test_metrics", None)
+        step, end = getattr(model, f"{split}_step"), getattr(model, f"{split}_epoch_end")
+
+        def per_batch(batch, i, idx, name):
+            if metrics is None or not evaltail.eval_step(model, metrics, batch, name):
+                step(batch, i, idx, src_name=name)
+
+        out = self._evaluation(split, loaders, per_batch, end, metrics)
+        return {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in (out or {}).items()}
+
+    def validate(self, loaders):
+        """Lightning's `validate`: every batch of every loader through the model's validation step, then
+        validation_epoch_end once -> {metric name: float, or list for per-class metrics}.  `loaders`: {dataset name: iterable
+        of batches} in the order of the reference's datamodule.idx_to_name['val'] (the name is validation_step's `src_name`,
+        the position its `dataloader_idx`), or one bare iterable (name "").  A batch is the reference's dict (`image`,
+        `semantic`, ...); host tensors are moved to the model's device.  Runs in eval mode under no_grad and the autocast of
+        this trainer's `precision`, and leaves every module in the mode it was in: nothing a later step() reads changes
+        (parameters, EMA, BatchNorm statistics, optimizer, RNG streams).  A segmentation batch goes through the fused
+        evaluation tail (refign_amd/evaltail.py: one kernel from the crop logits to the confusion counts) when its conditions
+        hold -- evaltail.eval_step lists them; RFN_EVAL_FUSED=0 turns it off -- and through model.validation_step otherwise
+        (any model with validation_step / validation_epoch_end works, AlignmentModel included).
+        Multi-rank: each rank iterates its own loaders, of any length; the only collectives are the ones the metrics'
+        compute() issues at the end, once per metric, so every rank must call validate() the same number of times."""
+        return self._metric_loop("validation", loaders)
+
+    def test(self, loaders):
+        """Lightning's `test`: as validate(), through test_step / test_epoch_end and the model's test metrics."""
+        return self._metric_loop("test", loaders)
+
+    def predict(self, loaders, save_dir, orig_size=None):
+        """Lightning's `predict`: arg-max label maps of every batch (`image`, `filename`) as PNGs under
+        `<save_dir>/preds/<dataset>/<filename>` and `<save_dir>/color_preds/<dataset>/<filename>` (segmentation_model.py:
+        283-302; no sub-directory for a bare iterable).  `orig_size`: the size the predictions are interpolated to (the
+        reference's datamodule.predict_ds[i].orig_dims); None: the image size.  -> the number of files written."""
+        from . import evaltail
+        model, written = self.model, [0]
+
+        def per_batch(batch, i, idx, name):
+            preds = evaltail.predict_step(model, batch, save_dir, orig_size, name or None)
+            if preds is None:
+                preds = model.predict_step(batch, i, idx, save_dir=save_dir, orig_size=orig_size, dataset_name=name or None)
+            written[0] += 2 * len(preds) if save_dir is not None else 0
+
+        self._evaluation("predict", loaders, per_batch)
+        return written[0]
+
+    def fit(self, train_batches, val_loaders=None, max_steps=None, val_every_n_steps=None, ckpt_dir=None, save_last=True):
+        """Lightning's `fit`: step() until model.global_step == max_steps -- after `ckpt_path=` / load_checkpoint the run
+        continues from the restored step count, it does not start over.  `train_batches` is iterated again when it is
+        exhausted; WHERE in it a resumed run continues is the caller's to restore (hand in an iterable that starts at the
+        batch the saved run would have taken next): the checkpoint holds no loader state.  The loop looks one batch ahead and
+        hands it to step(..., next_batch=), which prefetches what depends on the next inputs only; the last step gets None.
+        After every step whose new global_step is a non-zero multiple of `val_every_n_steps` (helpers/callbacks.py:19) it
+        runs validate(val_loaders); with `ckpt_dir` and `save_last` it writes `<ckpt_dir>/last.ckpt` (save_checkpoint) after
+        each validation and at the end (ModelCheckpoint(save_last=True)).  max_steps=None: the scheduler's max_steps.
+        -> [(global_step, metrics dict)], one entry per validation run."""
+        model = self.model
+        if max_steps is None:
+            max_steps = getattr(self.scheduler, "max_updates", None)
+        if max_steps is None:
+            raise ValueError("Trainer.fit: max_steps is not given and the scheduler has none")
+        rule = ValEveryNSteps(val_every_n_steps if val_loaders is not None else None)
+        last = os.path.join(ckpt_dir, "last.ckpt") if ckpt_dir is not None and save_last else None
+        history, saved_at = [], None
+        if int(model.global_step) >= max_steps:
+            return history
+
+        def batches():
+            while True:
+                n = 0
+                for b in train_batches:
+                    n += 1
+                    yield b
+                if n == 0:
+                    raise ValueError("Trainer.fit: train_batches is empty")
+
+        it = batches()
+        batch = self._to_device(next(it))
+        while int(model.global_step) < max_steps:
+            start = int(model.global_step)
+            nxt = self._to_device(next(it)) if start + 1 < max_steps else None
+            self.step(batch, start, next_batch=nxt)
+            if int(model.global_step) <= start:
+                raise RuntimeError("Trainer.fit: the model's training_step did not advance global_step")
+            batch = nxt
+            if rule.should_validate(int(model.global_step)):
+                history.append((int(model.global_step), self.validate(val_loaders)))
+                if last is not None:
+                    self.save_checkpoint(last)
+                    saved_at = int(model.global_step)
+        if last is not None and saved_at != int(model.global_step):
+            self.save_checkpoint(last)
+        return history
 
     # -- checkpoints ---------------------------------------------------------------------------------------------------
     def _io(self, what):

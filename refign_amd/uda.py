@@ -1026,24 +1026,31 @@ class DomainAdaptationSegmentationModel(nn.Module):
         ("truck", (0, 0, 70)), ("bus", (0, 60, 100)), ("train", (0, 80, 100)), ("motorcycle", (0, 0, 230)),
         ("bicycle", (119, 11, 32)))
 
-    @torch.no_grad()
-    def predict_step(self, batch, batch_idx=0, dataloader_idx=0, save_dir=None, orig_size=None):
-        """segmentation_model.py:283-302: arg-max label maps of a batch as PNGs -- `<save_dir>/preds/<filename>` holds the
-        train ids (8-bit), `<save_dir>/color_preds/<filename>` the same image with the Cityscapes palette.  The reference
-        takes `save_dir` from the Lightning checkpoint directory and `orig_size` from the data module."""
+    def write_label_pngs(self, preds, filenames, save_dir, dataset_name=None):
+        """`preds` (B, H, W) uint8 train ids as PNGs: `<save_dir>/preds/[<dataset_name>/]<filename>` (8-bit) and
+        `<save_dir>/color_preds/[<dataset_name>/]<filename>` (the same image with the Cityscapes palette), the layout of
+        segmentation_model.py:283-302.  Shared by predict_step and the fused evaluation tail (refign_amd/evaltail.py)."""
         from PIL import Image
+        pal = [v for _, rgb in self.CITYSCAPES_COLOURS for v in rgb]
+        pal += [0] * (768 - len(pal))
+        dirs = [os.path.join(save_dir, sub, dataset_name or "") for sub in ('preds', 'color_preds')]
+        for arr, name in zip(preds, filenames):
+            image = Image.fromarray(arr)
+            col = image.convert('P')
+            col.putpalette(pal)
+            for d, im in zip(dirs, (image, col)):
+                os.makedirs(os.path.dirname(os.path.join(d, name)), exist_ok=True)
+                im.save(os.path.join(d, name))
+
+    @torch.no_grad()
+    def predict_step(self, batch, batch_idx=0, dataloader_idx=0, save_dir=None, orig_size=None, dataset_name=None):
+        """segmentation_model.py:283-302: arg-max label maps of a batch as PNGs -- `<save_dir>/preds/<filename>` holds the
+        train ids (8-bit), `<save_dir>/color_preds/<filename>` the same image with the Cityscapes palette; with
+        `dataset_name` both get that sub-directory (`preds/<dataset_name>/<filename>`), as the reference lays them out.  The
+        reference takes `save_dir` from the Lightning checkpoint directory and `orig_size` from the data module."""
         preds = torch.argmax(self.forward(batch['image'], orig_size), dim=1).to(torch.uint8).cpu().numpy()
         if save_dir is not None:
-            pal = [v for _, rgb in self.CITYSCAPES_COLOURS for v in rgb]
-            pal += [0] * (768 - len(pal))
-            for sub in ('preds', 'color_preds'):
-                os.makedirs(os.path.join(save_dir, sub), exist_ok=True)
-            for arr, name in zip(preds, batch['filename']):
-                image = Image.fromarray(arr)
-                image.save(os.path.join(save_dir, 'preds', name))
-                col = image.convert('P')
-                col.putpalette(pal)
-                col.save(os.path.join(save_dir, 'color_preds', name))
+            self.write_label_pngs(preds, batch['filename'], save_dir, dataset_name)
         return preds
 
     # -- inference (:304-382) ------------------------------------------------------------------------------------
@@ -1057,15 +1064,35 @@ class DomainAdaptationSegmentationModel(nn.Module):
         logits = self.head(self.backbone(x))
         return F.interpolate(logits, x.shape[-2:], mode='bilinear', align_corners=False)
 
-    def slide_inference(self, img):
+    def slide_boxes(self, H, W):
+        """The sliding crops of an H x W image, (y1, y2, x1, x2) each: stride `inference_stride`, the last ones of a row /
+        column moved back inside the border (:338-352)."""
         hs, ws = self.inference_stride
         hc, wc = self.inference_crop_size
-        b, _, H, W = img.shape
         boxes = []
         for iy in range(max(H - hc + hs - 1, 0) // hs + 1):
             for ix in range(max(W - wc + ws - 1, 0) // ws + 1):
                 y2, x2 = min(iy * hs + hc, H), min(ix * ws + wc, W)
                 boxes.append((max(y2 - hc, 0), y2, max(x2 - wc, 0), x2))
+        return boxes
+
+    def crop_logits(self, x):
+        """-> (logits, boxes): the head's output BEFORE any up-sampling, for the sliding crops of `x` (batched or crop by
+        crop, per `inference_batched_slide`) or for the whole image -- (nbox * B, C, h, w), crop k of image b at row
+        k * B + b, and the crops' boxes (y1, y2, x1, x2) in image pixels.  What forward() makes of them (each crop up-sampled
+        to its box, summed, divided by the cover count) the fused evaluation tail does without the up-sampled tensors
+        (refign_amd/evaltail.py)."""
+        H, W = x.shape[-2:]
+        if not self.use_slide_inference:
+            return self.head(self.backbone(x)), [(0, H, 0, W)]
+        boxes = self.slide_boxes(H, W)
+        if self.inference_batched_slide:
+            return self.head(self.backbone(torch.cat([x[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in boxes], dim=0))), boxes
+        return torch.cat([self.head(self.backbone(x[:, :, y1:y2, x1:x2])) for y1, y2, x1, x2 in boxes], dim=0), boxes
+
+    def slide_inference(self, img):
+        b, _, H, W = img.shape
+        boxes = self.slide_boxes(H, W)
         preds = img.new_zeros((b, self.head.num_classes, H, W))
         count = img.new_zeros((b, 1, H, W))
         if self.inference_batched_slide:
