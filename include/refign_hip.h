@@ -26,6 +26,8 @@ extern "C" {
 #define RFN_EINVAL (-1)    /* bad argument (null pointer, non-positive size, unsupported parameterisation) */
 #define RFN_ELAUNCH (-2)   /* hipLaunchKernel / runtime error, see rfn_last_error() */
 #define RFN_ENOTSUP (-3)   /* valid in the reference but not built here (documented per function) */
+#define RFN_ENONDET (-4)   /* refused: the result would depend on the arrival order of floating-point atomics while
+                              rfn_set_deterministic(1) is in force (see "Deterministic mode" below) */
 
 /* 2: rfn_global_corr_layer_f32 takes a workspace; rfn_dacs_mix_jitter accepts one half of the mix.
  * 3: rfn_local_corr_layer_split_f32's workspace carries tickets (rfn_local_corr_layer_split_workspace_bytes; zero before first use);
@@ -38,6 +40,23 @@ typedef void* rfn_stream_t; /* hipStream_t */
 
 int rfn_abi_version(void);
 const char* rfn_last_error(void);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic mode (additions to ABI 4; nothing existing changed).  The flag is process-wide.  While it is set,
+ * every entry point whose result depends on the arrival order of floating-point atomics returns RFN_ENONDET
+ * instead of launching: rfn_gemm_tn (accumulate == 1, or a bias sum with accumulate == 0), rfn_gemm_tn_grouped,
+ * rfn_conv2d_nhwc_wgrad (a bias sum with accumulate != 2), rfn_attn_bwd_dkv, rfn_attn32_bwd (more than one query
+ * chunk), rfn_bn_stats_fwd / _bwd (and rfn_bn_train_fwd / _bwd), the depthwise statistics entry points
+ * (rfn_dwconv3x3_nhwc_stats, _nhwc_fwd_stats, _tri_stats, _tri_stats_f16), rfn_dacs_mix_jitter (when a jitter needs
+ * the image mean), rfn_upsample_ce, rfn_warp_bwd_f32 and the generic (atomic) form of rfn_corr_bwd_f32 / _f64.
+ * The entry points named *_det below, rfn_upsample_bilinear2d_bwd and `accumulate == 2` of the weight-gradient
+ * GEMMs give bit-identical results from launch to launch with or without the flag: partial sums are written
+ * with plain stores and added in a fixed order.
+ * One tightening of an existing argument comes with `accumulate == 2`: rfn_gemm_tn and rfn_conv2d_nhwc_wgrad used to read
+ * `accumulate` as a boolean (any non-zero value = atomics, as the documented 1); values outside 0, 1, 2 are RFN_EINVAL now.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_set_deterministic(int on);   /* returns RFN_OK */
+int rfn_get_deterministic(void);     /* 0 / 1 */
 
 /* ------------------------------------------------------------------------------------------------------------
  * Spatial correlation sampler -- replaces the pybind module `models.correlation_ops.correlation`
@@ -406,6 +425,8 @@ int rfn_patchify_tokens_cmajor(const void* src, void* dst, int B, int H, int W, 
  *     accumulate = 0: P[s][N,K] = fp32 partial of slab s (deterministic; caller reduces);
  *     accumulate = 1: P[N,K] += every slab, fp32 atomics (the parameter's view of the flat gradient buffer);
  *     grad_bias (may be NULL): [N] fp32, += column sums of G (the bias gradient), fp32 atomics.
+ *     accumulate = 2 (deterministic form): P as for 0, and grad_bias (may be NULL) is [S][N] fp32: row s receives the column
+ *       sums of slab s with plain stores (every element is written); the caller adds the slabs in slab order (rfn_sum_rows).
  *   N % 64 == 0, K % 64 == 0, rows_per_slab % 32 == 0.
  * ---------------------------------------------------------------------------------------------------------- */
 int rfn_gemm_nt(const void* X, const void* W, const void* bias, const void* res, const float* rowscale,
@@ -595,7 +616,8 @@ int rfn_conv2d_nhwc_o32(const void* X, const void* W, const float* bias, int act
  *   rfn_conv2d_nhwc_wgrad  P = weight gradient in the PACKED layout [n][(ky, kx, c)], row length Kpad (% 64, >= KH*KW*C), fp32:
  *                          the split-T kernel of rfn_gemm_tn with the im2col rows gathered on the fly.  accumulate = 0: one
  *                          (N, Kpad) partial per slab of rows_per_slab output pixels; 1: atomics into one.  grad_bias (may be
- *                          NULL) += column sums of GY.  N % 64 == 0, C % 2 == 0, ldg = row stride of GY in elements. */
+ *                          NULL) += column sums of GY.  accumulate = 2: P as for 0 and grad_bias [S][N] per-slab column sums,
+ *                          plain stores (see rfn_gemm_tn).  N % 64 == 0, C % 2 == 0, ldg = row stride of GY in elements. */
 int rfn_conv2d_nhwc_dgrad(const void* GY, const void* Wt, void* DX, int B, int H, int W, int C, int N, int KH, int KW,
                           int stride, int pad, int dil, long ldw, long ldy, int dtype, rfn_stream_t stream);
 int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_bias, int B, int H, int W, int C, int N, int KH,
@@ -678,6 +700,52 @@ int rfn_attn_pack_f8(const void* kv8, long batch_stride, long row_stride, int B,
 int rfn_attn_fwd_f8(const void* q8, long q_batch_stride, long q_row_stride, const void* pack, void* o8, long o_batch_stride,
                     long o_row_stride, int B, int heads, int Nq, int Nkv, int nst, float scale, float q_scale, float k_scale,
                     float v_scale, float out_q, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic forms (see "Deterministic mode" at the top).  Each takes the arguments of the entry point it
+ * stands in for plus a workspace for the partial sums; results agree with the atomic form to rounding and are
+ * bit-identical from launch to launch.
+ *   rfn_bn_stats_fwd_det / _bwd_det        BatchNorm statistics; workspace rfn_bn_stats_det_workspace_bytes(T, C)
+ *   rfn_dwconv3x3_nhwc_fwd_stats_det,
+ *   rfn_dwconv3x3_nhwc_stats_det           depthwise 3x3 (+ statistics of its result); workspace
+ *                                          rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation)
+ *   rfn_attn_bwd_dkv_det                   accT holds ceil(nqblk / blocks_per_chunk) images of
+ *                                          B * heads * 2 * 64 * nkpad floats (one per query chunk)
+ *   rfn_dacs_mix_jitter_det                mean_ws holds rfn_dacs_mix_jitter_det_workspace_bytes(H, W) bytes
+ *   rfn_upsample_ce_det                    workspace rfn_upsample_ce_det_workspace_bytes(B, C, H, W); the loss is
+ *                                          in loss_sum[0] (slots 1 .. 63 are zero)
+ *   rfn_upsample_bilinear2d_bwd            gather-form backward of F.interpolate(mode='bilinear',
+ *                                          align_corners=False): grad_in (planes, h, w) from grad_out (planes, H, W),
+ *                                          H >= h, W >= w; dtype 0 fp32 / 1 bf16 / 2 f16; scale_y / scale_x: ATen's
+ *                                          source-index scales (1 / scale_factor when the caller gave one), <= 0: h / H.
+ * No workspace has to be zeroed.  Workspaces of the statistics / loss forms are read by the launches the call
+ * itself enqueues and are free again when those have run.
+ * ------------------------------------------------------------------------------------------------------------ */
+unsigned long rfn_bn_stats_det_workspace_bytes(long T, int C);
+int rfn_bn_stats_fwd_det(const void* x, double* sums, void* workspace, long T, int C, int dtype, rfn_stream_t stream);
+int rfn_bn_stats_bwd_det(const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
+                         float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream);
+unsigned long rfn_dwconv3x3_stats_det_workspace_bytes(int B, int H, int W, int C, int dilation);
+int rfn_dwconv3x3_nhwc_fwd_stats_det(const void* x, const float* weight, const float* bias, void* y, double* sums, void* workspace,
+                                     int B, int H, int W, int C, int dilation, int dtype, rfn_stream_t stream);
+int rfn_dwconv3x3_nhwc_stats_det(const void* x, const float* weight, const float* bias, double* sums, void* workspace, int B, int H,
+                                 int W, int C, int dilation, int dtype, rfn_stream_t stream);
+int rfn_attn_bwd_dkv_det(const void* K, const void* V, long kv_batch_stride, long kv_row_stride, const void* q_rpack,
+                         const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
+                         const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
+                         int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream);
+unsigned long rfn_dacs_mix_jitter_det_workspace_bytes(int H, int W);
+int rfn_dacs_mix_jitter_det(const float* src, const float* trg, const long* gt_src, const long* pseudo_label,
+                            const float* pseudo_weight, float* mixed_img, long* mixed_lbl, float* mixed_weight, double* mean_ws,
+                            int B, int H, int W, const long* class_bits, const int* jitter_on, const int* order,
+                            const float* factor, const float* hue, const float* mean3, const float* std3,
+                            rfn_stream_t stream);
+unsigned long rfn_upsample_ce_det_workspace_bytes(int B, int C, int H, int W);
+int rfn_upsample_ce_det(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum,
+                        void* workspace, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16,
+                        rfn_stream_t stream);
+int rfn_upsample_bilinear2d_bwd(const void* grad_out, void* grad_in, long planes, int h, int w, int H, int W, float scale_y,
+                                float scale_x, int dtype, rfn_stream_t stream);
 
 #ifdef __cplusplus
 }

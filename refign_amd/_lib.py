@@ -23,6 +23,8 @@ _CORR12 = [c_int] * 12
 SIGNATURES = {
     "rfn_abi_version": (c_int, []),
     "rfn_last_error": (ctypes.c_char_p, []),
+    "rfn_set_deterministic": (c_int, [c_int]),
+    "rfn_get_deterministic": (c_int, []),
     "rfn_corr_fwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + _CORR12 + [c_void_p]),
     "rfn_corr_fwd_f64": (c_int, [c_void_p] * 3 + [c_int] * 4 + _CORR12 + [c_void_p]),
     "rfn_corr_bwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + _CORR12 + [c_void_p]),
@@ -138,6 +140,20 @@ SIGNATURES = {
     "rfn_uncertainty9_weights_len": (c_int, []),
     "rfn_uncertainty9_frontend_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "rfn_uncertainty9_frontend_f16mm": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
+    # deterministic forms (refign_amd/determinism.py; additions to ABI 4)
+    "rfn_bn_stats_det_workspace_bytes": (ctypes.c_ulong, [ctypes.c_long, c_int]),
+    "rfn_bn_stats_fwd_det": (c_int, [c_void_p] * 3 + [ctypes.c_long, c_int, c_int, c_void_p]),
+    "rfn_bn_stats_bwd_det": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
+    "rfn_dwconv3x3_stats_det_workspace_bytes": (ctypes.c_ulong, [c_int] * 5),
+    "rfn_dwconv3x3_nhwc_fwd_stats_det": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
+    "rfn_dwconv3x3_nhwc_stats_det": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
+    "rfn_attn_bwd_dkv_det": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long] + [c_void_p] * 8 + [c_int] * 8
+                             + [c_float, c_int, c_void_p]),
+    "rfn_dacs_mix_jitter_det_workspace_bytes": (ctypes.c_ulong, [c_int, c_int]),
+    "rfn_dacs_mix_jitter_det": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 7 + [c_void_p]),
+    "rfn_upsample_ce_det_workspace_bytes": (ctypes.c_ulong, [c_int] * 4),
+    "rfn_upsample_ce_det": (c_int, [c_void_p] * 6 + [c_int] * 9 + [c_void_p]),
+    "rfn_upsample_bilinear2d_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_long] + [c_int] * 4 + [c_float, c_float, c_int, c_void_p]),
 }
 
 

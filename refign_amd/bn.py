@@ -15,8 +15,8 @@ stay replayable from hipGraphs (tools/micro/rccl_capture.py).
 import torch
 import torch.distributed as dist
 
-from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from . import _lib, determinism
+from ._tensor import current_stream, on_device, ptr, workspace
 from .params import grad_sink
 
 _DT16 = {torch.bfloat16: 1, torch.float16: 2}
@@ -120,6 +120,13 @@ def usable(x, bn, dtype, channels=None, count=None):
 # CPU restatements in their place and drive the exchange logic below over gloo.
 def _stats_fwd(xh, sums):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
+    if determinism.enabled():                              # per-workgroup partial rows + an ordered column sum (csrc/bn.hip)
+        lib = _lib.load_library()
+        ws = workspace(lib.rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
+        with on_device(xh.device):
+            _lib.check(lib.rfn_bn_stats_fwd_det(ptr(xh), ptr(sums), ptr(ws), T, C, _DT16[xh.dtype], current_stream(xh.device)),
+                       "bn_stats_fwd_det")
+        return
     with on_device(xh.device):
         _lib.check(_lib.load_library().rfn_bn_stats_fwd(ptr(xh), ptr(sums), T, C, _DT16[xh.dtype], current_stream(xh.device)),
                    "bn_stats_fwd")
@@ -143,6 +150,13 @@ def _apply_fwd(xh, weight, bias, y, sums, bn, relu):
 
 def _stats_bwd(xh, gy, sums, weight, bias, bsums, eps, relu):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
+    if determinism.enabled():
+        lib = _lib.load_library()
+        ws = workspace(lib.rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
+        with on_device(xh.device):
+            _lib.check(lib.rfn_bn_stats_bwd_det(ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), ptr(ws), T, C,
+                                                eps, int(relu), _DT16[xh.dtype], current_stream(xh.device)), "bn_stats_bwd_det")
+        return
     with on_device(xh.device):
         _lib.check(_lib.load_library().rfn_bn_stats_bwd(ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), T, C,
                                                         eps, int(relu), _DT16[xh.dtype], current_stream(xh.device)),

@@ -119,3 +119,13 @@ def trainer_kwargs(cfg):
         elif name == "ModelCheckpoint":
             out["save_last"] = bool(args.get("save_last", False))
     return out
+
+
+def trainer_deterministic(cfg):
+    """`trainer.deterministic` of a loaded YAML (Lightning's `--trainer.deterministic true`; `warn` counts as on); False when
+    absent.  Kept out of trainer_kwargs, whose five keys are what Trainer / Trainer.fit took before the mode existed:
+    Trainer(model, ..., deterministic=trainer_deterministic(cfg))."""
+    v = ((cfg or {}).get("trainer") or {}).get("deterministic", False)
+    if isinstance(v, str):
+        return v.strip().lower() in ("true", "1", "yes", "warn")
+    return bool(v)

@@ -435,7 +435,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const uint16_t* __res
                                                            const unsigned char* __restrict__ Gt,
                                                            const float* __restrict__ lse2, const float* __restrict__ delta,
                                                            float* __restrict__ accT, int heads, int Nq, int Nkv, int nqblk,
-                                                           int nqpad, int nkpad, int blocks_per_chunk, float scale) {
+                                                           int nqpad, int nkpad, int blocks_per_chunk, float scale,
+                                                           long chunk_stride = 0) {
   using E = Elem<DT>;
   using vec8 = typename E::vec8;
   constexpr int STATS = 4 * kPackBlock;                 // offset of the statistics: 32 lse2, 32 delta
@@ -552,15 +553,22 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const uint16_t* __res
     }
   }
   if (kok) {
-    float* ak = accT + (long)bh * 2 * 64 * nkpad + key;
+    // chunk_stride != 0 (deterministic form): query chunk blockIdx.y owns image blockIdx.y of accT and writes every (d, key < Nkv)
+    // of it with plain stores; attn_dkv_finish_kernel adds the images in chunk order
+    float* ak = accT + (long)blockIdx.y * chunk_stride + (long)bh * 2 * 64 * nkpad + key;
     float* av = ak + (long)64 * nkpad;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int d = db * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        atomicAdd(ak + (long)d * nkpad, dk[db][r] * scale);
-        atomicAdd(av + (long)d * nkpad, dv[db][r]);
+        if (chunk_stride != 0) {
+          ak[(long)d * nkpad] = dk[db][r] * scale;
+          av[(long)d * nkpad] = dv[db][r];
+        } else {
+          atomicAdd(ak + (long)d * nkpad, dk[db][r] * scale);
+          atomicAdd(av + (long)d * nkpad, dv[db][r]);
+        }
       }
   }
 }
@@ -568,7 +576,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const uint16_t* __res
 // accT[bh][2][64][nkpad] fp32 -> dKV[b][key][2][heads][64] 16-bit
 template <int DT>
 __global__ __launch_bounds__(256) void attn_dkv_finish_kernel(const float* __restrict__ accT, uint16_t* __restrict__ dkv,
-                                                              int heads, int Nkv, int nkpad, long total) {
+                                                              int heads, int Nkv, int nkpad, long total, int chunks = 1,
+                                                              long chunk_stride = 0) {
   using S = typename Elem<DT>::scalar;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -580,7 +589,9 @@ __global__ __launch_bounds__(256) void attn_dkv_finish_kernel(const float* __res
   r >>= 1;
   const int key = (int)(r % Nkv);
   const int b = (int)(r / Nkv);
-  const float v = accT[(((long)(b * heads + hd) * 2 + which) * 64 + d) * nkpad + key];
+  const float* p = accT + (((long)(b * heads + hd) * 2 + which) * 64 + d) * nkpad + key;
+  float v = p[0];
+  for (int c = 1; c < chunks; ++c) v += p[(long)c * chunk_stride];        // deterministic form: chunk order
   const S o = (S)v;
   dkv[i] = __builtin_bit_cast(uint16_t, o);
 }
@@ -651,10 +662,10 @@ int rfn_attn_bwd_dq(const void* Q, long q_batch_stride, long q_row_stride, const
   return check_launch("attn_bwd_dq");
 }
 
-int rfn_attn_bwd_dkv(const void* K, const void* V, long kv_batch_stride, long kv_row_stride, const void* q_rpack,
-                     const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
-                     const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
-                     int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream) {
+static int attn_bwd_dkv_impl(bool det, const void* K, const void* V, long kv_batch_stride, long kv_row_stride, const void* q_rpack,
+                             const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
+                             const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
+                             int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream) {
   ATTN_DT_OK(dtype);
   RFN_REQUIRE(K && V && q_rpack && q_tpack && do_rpack && do_tpack && lse2 && delta && accT && dKV,
               "attn_bwd_dkv: null pointer");
@@ -664,14 +675,17 @@ int rfn_attn_bwd_dkv(const void* K, const void* V, long kv_batch_stride, long kv
               nqpad, nkpad, blocks_per_chunk);
   hipStream_t s = (hipStream_t)stream;
   // (a kernel, not a memset node, when the pass is captured into a hipGraph: capi.hip zero_async)
-  if (int rc = zero_async(accT, (size_t)B * heads * 2 * 64 * nkpad * sizeof(float), s)) return rc;
+  const long image = (long)B * heads * 2 * 64 * nkpad, chunk_stride = det ? image : 0;
+  if (!det)
+    if (int rc = zero_async(accT, (size_t)image * sizeof(float), s)) return rc;
   dim3 grid(cdiv(Nkv, 256), cdiv(nqblk, blocks_per_chunk), B * heads);
+  const int chunks = det ? (int)grid.y : 1;
   static const int ring = 2;     // 2 or 4: no difference measured (round 3)
 #define RFN_DKV_LAUNCH_(D, R)                                                                                           \
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<D, R>), grid, dim3(512), 0, s, (const uint16_t*)K, (const uint16_t*)V,            \
                      kv_batch_stride, kv_row_stride, (const unsigned char*)q_rpack, (const unsigned char*)q_tpack,      \
                      (const unsigned char*)do_rpack, (const unsigned char*)do_tpack, lse2, delta, accT, heads, Nq, Nkv,  \
-                     nqblk, nqpad, nkpad, blocks_per_chunk, scale)
+                     nqblk, nqpad, nkpad, blocks_per_chunk, scale, chunk_stride)
 #define RFN_DKV_LAUNCH(D)                                                                                               \
   switch (ring) {                                                                                                       \
     case 4: RFN_DKV_LAUNCH_(D, 4); break;                                                                               \
@@ -685,11 +699,30 @@ int rfn_attn_bwd_dkv(const void* K, const void* V, long kv_batch_stride, long kv
   const long total = (long)B * Nkv * 2 * heads * 64;
   if (dtype == 1)
     hipLaunchKernelGGL(attn_dkv_finish_kernel<1>, dim3(cdiv(total, 256)), dim3(256), 0, s, accT, (uint16_t*)dKV, heads,
-                       Nkv, nkpad, total);
+                       Nkv, nkpad, total, chunks, chunk_stride);
   else
     hipLaunchKernelGGL(attn_dkv_finish_kernel<2>, dim3(cdiv(total, 256)), dim3(256), 0, s, accT, (uint16_t*)dKV, heads,
-                       Nkv, nkpad, total);
+                       Nkv, nkpad, total, chunks, chunk_stride);
   return check_launch("attn_dkv_finish");
+}
+
+int rfn_attn_bwd_dkv(const void* K, const void* V, long kv_batch_stride, long kv_row_stride, const void* q_rpack,
+                     const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
+                     const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
+                     int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream) {
+  RFN_REFUSE_NONDET(true, "rfn_attn_bwd_dkv", "attn_bwd_dkv_kernel, fp32 atomics (use rfn_attn_bwd_dkv_det)");
+  return attn_bwd_dkv_impl(false, K, V, kv_batch_stride, kv_row_stride, q_rpack, q_tpack, do_rpack, do_tpack, lse2, delta, accT,
+                           dKV, B, heads, Nq, Nkv, nqblk, nqpad, nkpad, blocks_per_chunk, scale, dtype, stream);
+}
+
+// Deterministic form: accT holds ceil(nqblk / blocks_per_chunk) images of B * heads * 2 * 64 * nkpad floats (no need to zero
+// them): every query chunk stores its partial dK / dV image, the finishing kernel adds the images in chunk order.
+int rfn_attn_bwd_dkv_det(const void* K, const void* V, long kv_batch_stride, long kv_row_stride, const void* q_rpack,
+                         const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
+                         const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
+                         int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream) {
+  return attn_bwd_dkv_impl(true, K, V, kv_batch_stride, kv_row_stride, q_rpack, q_tpack, do_rpack, do_tpack, lse2, delta, accT,
+                           dKV, B, heads, Nq, Nkv, nqblk, nqpad, nkpad, blocks_per_chunk, scale, dtype, stream);
 }
 
 }  // extern "C"

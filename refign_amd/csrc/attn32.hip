@@ -395,6 +395,9 @@ int rfn_attn32_bwd(const float* Q, long q_batch_stride, long q_row_stride, const
               query_chunks);
   ATTN32_STRIDES_OK(q_row_stride, q_batch_stride, kv_row_stride, kv_batch_stride, o_row_stride, o_batch_stride, dq_row_stride,
                     dq_batch_stride, dkv_row_stride, dkv_batch_stride);
+  // (attn32_bwd_launch: more than one query chunk adds the chunks' dK / dV with fp32 atomics)
+  RFN_REFUSE_NONDET(std::min(query_chunks, cdiv(Nq, 32)) > 1, "rfn_attn32_bwd",
+                    "attn32_bwd_dkv_kernel<atomic>, fp32 atomics (query_chunks = 1 is deterministic)");
   hipStream_t st = (hipStream_t)stream;
   if (head_dim == 64)
     return attn32_bwd_launch<64>(Q, q_batch_stride, q_row_stride, KV, kv_batch_stride, kv_row_stride, dO, O, o_batch_stride,

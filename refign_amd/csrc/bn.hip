@@ -63,9 +63,13 @@ template <int DT, bool BWD>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
                                                        const double* __restrict__ fwd_sums, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, void* __restrict__ sums_, long T,
-                                                       int C, int cvb, float eps, int relu, float slope) {
+                                                       int C, int cvb, float eps, int relu, float slope,
+                                                       void* __restrict__ part_ = nullptr) {
   using ST = typename std::conditional<BWD, float, double>::type;      // forward sums: doubles (header)
   ST* __restrict__ sums = (ST*)sums_;
+  // deterministic form: part[gridDim.y][2 C], one row per workgroup row with plain stores (every element is written);
+  // ordered_colsum adds the rows in row order afterwards
+  ST* __restrict__ part = (ST*)part_;
   __shared__ ST red[2][256][8];
   const int CV = C / 8, pl = 256 / cvb;
   const int cv = blockIdx.x * cvb + threadIdx.x % cvb, rl = threadIdx.x / cvb;
@@ -137,9 +141,13 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restric
     if (cvg >= CV) continue;
     ST sum = 0;
     for (int r = 0; r < pl; ++r) sum += red[which][r * cvb + v][e];
-    atomicAdd(sums + which * C + cvg * 8 + e, sum);
+    if (part != nullptr) part[((long)blockIdx.y * 2 + which) * C + cvg * 8 + e] = sum;
+    else atomicAdd(sums + which * C + cvg * 8 + e, sum);
   }
-  if (!BWD && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(sums + 2 * C, (ST)T);
+  if (!BWD && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    if (part != nullptr) sums[2 * C] = (ST)T;
+    else atomicAdd(sums + 2 * C, (ST)T);
+  }
 }
 
 template <int DT, bool BWD>
@@ -205,10 +213,16 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
 
 static inline int bn_cvb(int CV) { return CV >= 64 ? 64 : (CV >= 32 ? 32 : (CV >= 16 ? 16 : 8)); }
 
+// workgroup rows of a statistics launch (= rows of the deterministic form's partial image)
+static inline int bn_stats_rows(long T, int C) {
+  const int CV = C / 8, cvb = bn_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
+  return (int)std::max<long>(1, std::min<long>(cdiv(T, (long)pl * 4), std::max<long>(1, 512 / gx)));
+}
+
 template <int DT>
 static int bn_launch(bool bwd, bool apply, const void* x, const void* g, const double* fwd_sums, void* sums_or_bwd,
                      const float* gamma, const float* beta, void* out, float* rmean, float* rvar, long T, int C, float eps,
-                     float momentum, int relu, float slope, hipStream_t s, long ldo = 0) {
+                     float momentum, int relu, float slope, hipStream_t s, long ldo = 0, void* part = nullptr) {
   if (ldo == 0) ldo = C;
   const int CV = C / 8, cvb = bn_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
   // workgroups per launch.  A statistics workgroup ends with 2 x (its channels) atomics on the SAME 2C sums: 512 of them
@@ -218,15 +232,16 @@ static int bn_launch(bool bwd, bool apply, const void* x, const void* g, const d
   static const long wgs_apply = 1024;
   static const long wgs_stats = 512;
   const long wgs = apply ? wgs_apply : wgs_stats;
-  const int gy = (int)std::max<long>(1, std::min<long>(cdiv(T, (long)pl * 4), std::max<long>(1, wgs / gx)));
+  const int gy = apply ? (int)std::max<long>(1, std::min<long>(cdiv(T, (long)pl * 4), std::max<long>(1, wgs / gx)))
+                       : bn_stats_rows(T, C);
   dim3 grid(gx, gy), block(256);
   if (!apply) {
     if (bwd)
       hipLaunchKernelGGL((bn_stats_kernel<DT, true>), grid, block, 0, s, (const uint16_t*)x, (const uint16_t*)g, fwd_sums,
-                         gamma, beta, sums_or_bwd, T, C, cvb, eps, relu, slope);
+                         gamma, beta, sums_or_bwd, T, C, cvb, eps, relu, slope, part);
     else
       hipLaunchKernelGGL((bn_stats_kernel<DT, false>), grid, block, 0, s, (const uint16_t*)x, nullptr, nullptr, nullptr,
-                         nullptr, sums_or_bwd, T, C, cvb, eps, relu, slope);
+                         nullptr, sums_or_bwd, T, C, cvb, eps, relu, slope, part);
   } else {
     if (bwd)
       hipLaunchKernelGGL((bn_apply_kernel<DT, true>), grid, block, 0, s, (const uint16_t*)x, (const uint16_t*)g, fwd_sums,
@@ -257,6 +272,7 @@ static int bn_check(const char* what, long T, int C, int dtype) {
 int rfn_bn_stats_fwd(const void* x, double* sums, long T, int C, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && sums, "bn_stats_fwd: null pointer");
   if (int rc = bn_check("bn_stats_fwd", T, C, dtype)) return rc;
+  RFN_REFUSE_NONDET(true, "rfn_bn_stats_fwd", "bn_stats_kernel, fp64 atomics (use rfn_bn_stats_fwd_det)");
   hipStream_t s = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), s)) return rc;   // kernel, not a memset node (capi.hip)
   return RFN_BN_DISPATCH(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C, 0.f, 0.f, 0, 0.f, s);
@@ -286,9 +302,38 @@ int rfn_bn_stats_bwd(const void* x, const void* grad_y, const double* fwd_sums, 
                      float* bwd_sums, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums, "bn_stats_bwd: null pointer");
   if (int rc = bn_check("bn_stats_bwd", T, C, dtype)) return rc;
+  RFN_REFUSE_NONDET(true, "rfn_bn_stats_bwd", "bn_stats_kernel, fp32 atomics (use rfn_bn_stats_bwd_det)");
   hipStream_t s = (hipStream_t)stream;
   if (int rc = zero_async(bwd_sums, 2 * (size_t)C * sizeof(float), s)) return rc;
   return RFN_BN_DISPATCH(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps, 0.f, relu != 0, bn_slope(relu), s);
+}
+
+// Deterministic forms of the two statistics passes: every workgroup row stores its 2 C partial sums into `workspace`
+// (rfn_bn_stats_det_workspace_bytes(T, C) bytes, no need to zero it), a second launch adds the rows in row order.
+unsigned long rfn_bn_stats_det_workspace_bytes(long T, int C) {
+  if (T < 1 || C <= 0 || C % 8 != 0) return 0;
+  return (unsigned long)bn_stats_rows(T, C) * 2 * C * sizeof(double);
+}
+
+int rfn_bn_stats_fwd_det(const void* x, double* sums, void* workspace, long T, int C, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && sums && workspace, "bn_stats_fwd_det: null pointer");
+  if (int rc = bn_check("bn_stats_fwd_det", T, C, dtype)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = RFN_BN_DISPATCH(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C, 0.f,
+                               0.f, 0, 0.f, s, 0, workspace))
+    return rc;
+  return ordered_colsum_f64((const double*)workspace, sums, bn_stats_rows(T, C), 2 * C, s);
+}
+
+int rfn_bn_stats_bwd_det(const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
+                         float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums && workspace, "bn_stats_bwd_det: null pointer");
+  if (int rc = bn_check("bn_stats_bwd_det", T, C, dtype)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = RFN_BN_DISPATCH(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps,
+                               0.f, relu != 0, bn_slope(relu), s, 0, workspace))
+    return rc;
+  return ordered_colsum_f32((const float*)workspace, bwd_sums, bn_stats_rows(T, C), 2 * C, s);
 }
 
 int rfn_bn_apply_bwd(const void* x, const void* grad_y, const double* fwd_sums, const float* bwd_sums, const float* gamma,

@@ -1,4 +1,5 @@
 // refign_amd/csrc/capi.hip -- error plumbing + version of the C ABI (include/refign_hip.h).
+#include <atomic>
 #include <cstdint>
 
 #include "common.h"
@@ -9,6 +10,9 @@ char* err_buf() {
   static thread_local char buf[512] = {0};
   return buf;
 }
+
+static std::atomic<int> g_deterministic{0};
+int deterministic() { return g_deterministic.load(std::memory_order_relaxed); }
 
 int fail(int code, const char* fmt, ...) {
   va_list ap;
@@ -53,4 +57,9 @@ int zero_async(void* p, size_t bytes, hipStream_t st) {
 extern "C" {
 int rfn_abi_version(void) { return RFN_ABI_VERSION; }
 const char* rfn_last_error(void) { return rfn::err_buf(); }
+int rfn_set_deterministic(int on) {
+  rfn::g_deterministic.store(on != 0 ? 1 : 0, std::memory_order_relaxed);
+  return RFN_OK;
+}
+int rfn_get_deterministic(void) { return rfn::deterministic(); }
 }

@@ -81,12 +81,27 @@ inline int dt_pair(int a, int b, const char* what, Fn&& fn) {
   return fail(RFN_EINVAL, "%s: dtype codes (%d, %d): each 0 (f32), 1 (bf16) or 2 (f16), bf16 and f16 not mixed", what, a, b);
 }
 
+// rfn_set_deterministic() / rfn_get_deterministic(): process-wide (capi.hip)
+int deterministic();
+
+// out[c] = sum over r of part[r * cols + c], added in an order that depends on (rows, cols) only (det.hip): the second launch
+// of the store-and-sum forms that replace floating-point atomics in deterministic mode
+int ordered_colsum_f32(const float* part, float* out, long rows, int cols, hipStream_t st);
+int ordered_colsum_f64(const double* part, double* out, long rows, int cols, hipStream_t st);
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // zero-fill as a kernel on `st` (capi.hip: why not hipMemsetAsync)
 int zero_async(void* p, size_t bytes, hipStream_t st);
 
 }  // namespace rfn
+
+// Entry points whose result depends on the arrival order of floating-point atomics refuse while the deterministic flag is set.
+#define RFN_REFUSE_NONDET(cond, entry, why)                                                                              \
+  do {                                                                                                                   \
+    if (rfn::deterministic() && (cond))                                                                                  \
+      return rfn::fail(RFN_ENONDET, "%s refused in deterministic mode: %s", entry, why);                                 \
+  } while (0)
 
 #define RFN_REQUIRE(cond, ...) \
   do {                         \

@@ -1423,6 +1423,7 @@ static int corr_bwd_any(const T* in1, const T* in2, const T* gout, T* g1, T* g2,
     hipLaunchKernelGGL((corr_k1_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, in1, in2, gout, g1, g2, p, total);
     return check_launch("corr_k1_bwd_kernel");
   }
+  RFN_REFUSE_NONDET(true, "rfn_corr_bwd", "corr_generic_bwd_kernel, floating-point atomics (no deterministic form)");
   const size_t bytes = sizeof(T) * (size_t)p.B * p.C * p.iH * p.iW;
   if (hipMemsetAsync(g1, 0, bytes, st) != hipSuccess || hipMemsetAsync(g2, 0, bytes, st) != hipSuccess)
     return fail(RFN_ELAUNCH, "corr bwd: hipMemsetAsync failed");

@@ -69,7 +69,8 @@ __global__ __launch_bounds__(256) void dacs_mix_jitter_kernel(const float* __res
                                                               const float* __restrict__ pweight, float* __restrict__ img,
                                                               long* __restrict__ lbl, float* __restrict__ wgt,
                                                               double* __restrict__ msum, long plane,
-                                                              const long* __restrict__ class_bits, DacsArgs a) {
+                                                              const long* __restrict__ class_bits, DacsArgs a,
+                                                              double* __restrict__ mpart = nullptr) {
   // class_bits[n] (device data: the class set comes from torch.unique on the device, no host round trip): bit c = class c
   // is taken from the source image, bit 31 = the ignore label 255 is
   const int n = blockIdx.y;
@@ -139,7 +140,12 @@ __global__ __launch_bounds__(256) void dacs_mix_jitter_kernel(const float* __res
     part = wave_sum(part);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(msum + n, (double)((red[0] + red[1]) + (red[2] + red[3])));
+    // mpart (deterministic form): one slot per workgroup, [blockIdx.x][kDacsMaxBatch], added in block order afterwards
+    if (threadIdx.x == 0) {
+      const double v = (double)((red[0] + red[1]) + (red[2] + red[3]));
+      if (mpart != nullptr) mpart[(long)blockIdx.x * kDacsMaxBatch + n] = v;
+      else atomicAdd(msum + n, v);
+    }
   }
 }
 
@@ -181,11 +187,11 @@ __global__ __launch_bounds__(256) void dacs_blur_kernel(const float* __restrict_
 
 extern "C" {
 
-int rfn_dacs_mix_jitter(const float* src, const float* trg, const long* gt_src, const long* pseudo_label,
-                        const float* pseudo_weight, float* mixed_img, long* mixed_lbl, float* mixed_weight, double* mean_ws,
-                        int B, int H, int W, const long* class_bits, const int* jitter_on, const int* order,
-                        const float* factor, const float* hue, const float* mean3, const float* std3,
-                        rfn_stream_t stream) {
+static int dacs_mix_jitter_impl(bool det, const float* src, const float* trg, const long* gt_src, const long* pseudo_label,
+                                const float* pseudo_weight, float* mixed_img, long* mixed_lbl, float* mixed_weight, double* mean_ws,
+                                int B, int H, int W, const long* class_bits, const int* jitter_on, const int* order,
+                                const float* factor, const float* hue, const float* mean3, const float* std3,
+                                rfn_stream_t stream) {
   using namespace rfn;
   // either half may be left out: mixed_img == NULL -> labels / weights only (src / trg unused), mixed_lbl == NULL -> image only
   // (pseudo_label / pseudo_weight / mixed_weight unused); the masks of the two halves agree when gt_src / class_bits do
@@ -214,7 +220,15 @@ int rfn_dacs_mix_jitter(const float* src, const float* trg, const long* gt_src, 
   const long plane = (long)H * W;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(plane / 4, 256), (unsigned)B), block(256);
-  if (need_mean) {
+  RFN_REFUSE_NONDET(need_mean && !det, "rfn_dacs_mix_jitter", "dacs_mix_jitter_kernel<0>, fp64 atomics (use rfn_dacs_mix_jitter_det)");
+  if (need_mean && det) {
+    // partial sums of every workgroup behind the kDacsMaxBatch means.  The columns of samples >= B are never written; the column
+    // sum adds whatever they hold into means that nobody reads (pass 1 reads msum[n] for n < B only).
+    double* mpart = mean_ws + kDacsMaxBatch;
+    hipLaunchKernelGGL((dacs_mix_jitter_kernel<0>), grid, block, 0, st, src, trg, gt_src, pseudo_label, pseudo_weight,
+                       mixed_img, mixed_lbl, mixed_weight, mean_ws, plane, class_bits, a, mpart);
+    if (int rc = ordered_colsum_f64(mpart, mean_ws, grid.x, kDacsMaxBatch, st)) return rc;
+  } else if (need_mean) {
     if (int rc = zero_async(mean_ws, sizeof(double) * kDacsMaxBatch, st)) return rc;
     hipLaunchKernelGGL((dacs_mix_jitter_kernel<0>), grid, block, 0, st, src, trg, gt_src, pseudo_label, pseudo_weight,
                        mixed_img, mixed_lbl, mixed_weight, mean_ws, plane, class_bits, a);
@@ -222,6 +236,31 @@ int rfn_dacs_mix_jitter(const float* src, const float* trg, const long* gt_src, 
   hipLaunchKernelGGL((dacs_mix_jitter_kernel<1>), grid, block, 0, st, src, trg, gt_src, pseudo_label, pseudo_weight, mixed_img,
                      mixed_lbl, mixed_weight, mean_ws, plane, class_bits, a);
   return check_launch("dacs_mix_jitter_kernel");
+}
+
+int rfn_dacs_mix_jitter(const float* src, const float* trg, const long* gt_src, const long* pseudo_label,
+                        const float* pseudo_weight, float* mixed_img, long* mixed_lbl, float* mixed_weight, double* mean_ws,
+                        int B, int H, int W, const long* class_bits, const int* jitter_on, const int* order,
+                        const float* factor, const float* hue, const float* mean3, const float* std3,
+                        rfn_stream_t stream) {
+  return dacs_mix_jitter_impl(false, src, trg, gt_src, pseudo_label, pseudo_weight, mixed_img, mixed_lbl, mixed_weight, mean_ws, B,
+                              H, W, class_bits, jitter_on, order, factor, hue, mean3, std3, stream);
+}
+
+// Deterministic form: mean_ws holds rfn_dacs_mix_jitter_det_workspace_bytes(H, W) bytes; the image means are per-workgroup
+// partial sums added in workgroup order instead of fp64 atomics.  Everything else as rfn_dacs_mix_jitter.
+unsigned long rfn_dacs_mix_jitter_det_workspace_bytes(int H, int W) {
+  if (H <= 0 || W <= 0) return 0;
+  return sizeof(double) * rfn::kDacsMaxBatch * (1 + (unsigned long)rfn::cdiv((long)H * W / 4, 256));
+}
+
+int rfn_dacs_mix_jitter_det(const float* src, const float* trg, const long* gt_src, const long* pseudo_label,
+                            const float* pseudo_weight, float* mixed_img, long* mixed_lbl, float* mixed_weight, double* mean_ws,
+                            int B, int H, int W, const long* class_bits, const int* jitter_on, const int* order,
+                            const float* factor, const float* hue, const float* mean3, const float* std3,
+                            rfn_stream_t stream) {
+  return dacs_mix_jitter_impl(true, src, trg, gt_src, pseudo_label, pseudo_weight, mixed_img, mixed_lbl, mixed_weight, mean_ws, B,
+                              H, W, class_bits, jitter_on, order, factor, hue, mean3, std3, stream);
 }
 
 int rfn_dacs_blur(const float* x, float* tmp, float* y, int B, int C, int H, int W, int ksize_y, int ksize_x, const int* blur_on,

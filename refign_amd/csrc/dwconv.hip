@@ -188,7 +188,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
                                                             int H, int W, int C, int dil, int cvb,
                                                             T* __restrict__ ya = nullptr, float xs = 1.f,
                                                             float oq = 1.f, int sliced = 0,
-                                                            double* __restrict__ sums = nullptr, BnEpi bn = BnEpi{}) {
+                                                            double* __restrict__ sums = nullptr, BnEpi bn = BnEpi{},
+                                                            double* __restrict__ spart = nullptr) {
   // xs / oq (e4m3 activations only): stored input bytes mean xs * value -- folded into the weights; outputs are stored as
   // value * oq
   constexpr bool F8 = std::is_same<T, f8e4m3>::value;
@@ -360,9 +361,14 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
       if (cvbase + v >= CV) continue;
       float sum = 0.f;
       for (int r = 0; r < pl; ++r) sum += sred[which][r * cvb + v][e];
-      atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
+      // spart (deterministic form): one row of 2 C partial sums per block row, plain stores; added in row order afterwards
+      if (spart != nullptr) spart[((size_t)(sliced ? blockIdx.x >> 3 : blockIdx.y) * 2 + which) * C + (cvbase + v) * V + e] = (double)sum;
+      else atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(sums + 2 * C, (double)B * H * W);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+      if (spart != nullptr) sums[2 * C] = (double)B * H * W;
+      else atomicAdd(sums + 2 * C, (double)B * H * W);
+    }
   }
 }
 
@@ -539,21 +545,36 @@ static int launch_fwd_gelu(const void* x, const float* w, const float* bias, voi
 // STATS 1: convolution + statistics; 2: statistics only; BNE: convolution + BatchNorm + activation from complete statistics
 template <typename T, int STATS, bool BNE>
 static int launch_fwd_stats(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
-                            int dil, hipStream_t st, BnEpi bn = BnEpi{}) {
+                            int dil, hipStream_t st, BnEpi bn = BnEpi{}, double* spart = nullptr) {
   constexpr int V = VecIO<T>::N;
   const int CV = C / V;
   const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
+  int rows;                                              // block rows = rows of the deterministic form's partial image
   if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) {
     hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS, BNE>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias,
-                       (T*)y, B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1, sums, bn);
-    return check_launch("dwconv3x3_fwd_kernel<sliced, stats / bn>");
+                       (T*)y, B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1, sums, bn, spart);
+    if (int rc = check_launch("dwconv3x3_fwd_kernel<sliced, stats / bn>")) return rc;
+    rows = sg.grid / 8;
+  } else {
+    const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
+    const long nquads = (long)B * H * WQ;
+    const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
+    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS, BNE>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
+                       (T*)y, B, H, W, C, dil, cvb, (T*)nullptr, 1.f, 1.f, 0, sums, bn, spart);
+    if (int rc = check_launch("dwconv3x3_fwd_kernel<stats / bn>")) return rc;
+    rows = gy;
   }
+  if (spart != nullptr) return ordered_colsum_f64(spart, sums, rows, 2 * C, st);
+  return RFN_OK;
+}
+
+// block rows of launch_fwd_stats for 16-bit activations (V = 8), either geometry
+static int dw_stats_rows(int B, int H, int W, int C, int dil) {
+  const int CV = C / 8;
+  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
+  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) return sg.grid / 8;
   const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-  const long nquads = (long)B * H * WQ;
-  const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
-  hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS, BNE>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
-                     (T*)y, B, H, W, C, dil, cvb, (T*)nullptr, 1.f, 1.f, 0, sums, bn);
-  return check_launch("dwconv3x3_fwd_kernel<stats / bn>");
+  return (int)std::max<long>(1, std::min<long>(cdiv((long)B * H * WQ, pl), (256L * 16) / gx));
 }
 
 template <typename T>
@@ -808,6 +829,7 @@ static int tri_stats(const void* x, const float* weight3, const float* bias3, do
                      hipStream_t st) {
   RFN_REQUIRE(x && weight3 && sums3, "rfn_dwconv3x3_tri_stats: null pointer");
   RFN_REQUIRE(tri_domain(B, H, W, C, g), "rfn_dwconv3x3_tri_stats: B=%d H=%d W=%d C=%d g=%d outside the kernel's domain", B, H, W, C, g);
+  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_tri_stats", "dwconv3x3_tri_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det per branch)");
   if (int rc = zero_async(sums3, 3 * (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
   TriArgs a{};
   a.w = weight3, a.bias = bias3, a.sums = sums3;
@@ -901,10 +923,39 @@ int rfn_dwconv3x3_nhwc_fwd_stats(const void* x, const float* weight, const float
   RFN_REQUIRE(x && weight && y && sums, "rfn_dwconv3x3_nhwc_fwd_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats: bad size");
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
+  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_fwd_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_fwd_stats_det)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
   return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st)
                     : launch_fwd_stats<_Float16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st);
+}
+
+// Deterministic forms of rfn_dwconv3x3_nhwc_fwd_stats / rfn_dwconv3x3_nhwc_stats: every block row stores its 2 C partial sums
+// into `workspace` (rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation) bytes, no need to zero it) and a second launch
+// adds the rows in row order.  Same convolution, same `sums` layout.
+unsigned long rfn_dwconv3x3_stats_det_workspace_bytes(int B, int H, int W, int C, int dilation) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || dilation <= 0) return 0;
+  return (unsigned long)dw_stats_rows(B, H, W, C, dilation) * 2 * C * sizeof(double);
+}
+
+int rfn_dwconv3x3_nhwc_fwd_stats_det(const void* x, const float* weight, const float* bias, void* y, double* sums, void* workspace,
+                                     int B, int H, int W, int C, int dilation, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && weight && y && sums && workspace, "rfn_dwconv3x3_nhwc_fwd_stats_det: null pointer");
+  RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bad size");
+  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace)
+                    : launch_fwd_stats<_Float16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace);
+}
+
+int rfn_dwconv3x3_nhwc_stats_det(const void* x, const float* weight, const float* bias, double* sums, void* workspace, int B, int H,
+                                 int W, int C, int dilation, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && weight && sums && workspace, "rfn_dwconv3x3_nhwc_stats_det: null pointer");
+  RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats_det: bad size");
+  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace)
+                    : launch_fwd_stats<_Float16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace);
 }
 
 // Gradient-free depthwise 3x3 -> BatchNorm(batch statistics) -> ReLU in two passes over the INPUT (bf16 / f16):
@@ -916,6 +967,7 @@ int rfn_dwconv3x3_nhwc_stats(const void* x, const float* weight, const float* bi
   RFN_REQUIRE(x && weight && sums, "rfn_dwconv3x3_nhwc_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats: bad size");
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
+  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
   return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st)

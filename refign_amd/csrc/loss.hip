@@ -58,7 +58,9 @@ template <int DT, bool FULLC>
 __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict__ logits, const long* __restrict__ target,
                                                           const float* __restrict__ weight, float* __restrict__ grad_lo,
                                                           double* __restrict__ loss_sum, int C, int h, int w, int H, int W,
-                                                          float sy, float sx, int ignore_index, int round16) {
+                                                          float sy, float sx, int ignore_index, int round16,
+                                                          float* __restrict__ tile_part = nullptr,
+                                                          double* __restrict__ loss_part = nullptr) {
   using E = LossElem<DT>;
   // the footprint logits (steps 1-2) and the x-reduced gradient (step 3) share their LDS
   __shared__ float tmp[kLossMaxC * kLossTH * kLossFX];         // [c][ty][fx]
@@ -146,9 +148,14 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
   __syncthreads();
   // kLossSlots partial sums (the host adds them): 8 160 tiles adding to ONE address were serialised in the L2 -- 435 us of
   // same-address atomics around 70 us of work
-  if (tid == 0)
-    atomicAdd(loss_sum + (blockIdx.x + 7 * blockIdx.y + 13 * blockIdx.z) % kLossSlots,
-              (double)((red[0] + red[1]) + (red[2] + red[3])));
+  // tile_part / loss_part (deterministic form): this tile's loss and footprint gradient go to slots of their own with plain
+  // stores; upsample_ce_gather_kernel / ordered_colsum add them in tile order
+  const long tile_id = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (tid == 0) {
+    const double v = (double)((red[0] + red[1]) + (red[2] + red[3]));
+    if (loss_part != nullptr) loss_part[tile_id] = v;
+    else atomicAdd(loss_sum + (blockIdx.x + 7 * blockIdx.y + 13 * blockIdx.z) % kLossSlots, v);
+  }
   // the tile columns / rows whose footprint contains a cell are a contiguous run (the source index is monotone): its ends,
   // so that the sums below walk ~2 x scale pixels instead of the whole tile edge
   if (tid < nfx) {
@@ -193,9 +200,52 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
       const float wgt = (ry0[ty] == cell ? 1.f - l : 0.f) + (ry1[ty] == cell ? l : 0.f);
       acc = fmaf(wgt, tmp[(c * kLossTH + ty) * kLossFX + fx], acc);
     }
-    if (acc != 0.f) atomicAdd(grad_lo + ((long)b * C + c) * plane + (long)cell * w + fx0 + fx, acc);
+    if (tile_part != nullptr) tile_part[((tile_id * C + c) * kLossFY + fy) * kLossFX + fx] = acc;
+    else if (acc != 0.f) atomicAdd(grad_lo + ((long)b * C + c) * plane + (long)cell * w + fx0 + fx, acc);
   }
 }
+
+// first output index whose source cells can include `cell`, and one past the last: a conservative window from the inverse of
+// src_index (membership is tested exactly per tile)
+__device__ __forceinline__ void cell_window(int cell, float scale, int out_size, int& lo, int& hi) {
+  const float inv = 1.f / scale;
+  lo = cell <= 1 ? 0 : max(0, (int)floorf(((float)cell - 0.5f) * inv - 0.5f) - 1);
+  hi = min(out_size, (int)ceilf(((float)cell + 1.5f) * inv - 0.5f) + 2);
+}
+
+// Deterministic form, second launch: grad_lo[b][c][y][x] = sum, over the tiles whose footprint holds the cell (tile rows outer,
+// tile columns inner, ascending), of that tile's partial.  One thread per low-resolution cell.
+__global__ __launch_bounds__(256) void upsample_ce_gather_kernel(const float* __restrict__ tile_part, float* __restrict__ grad_lo,
+                                                                 long total, int C, int h, int w, int H, int W, float sy, float sx,
+                                                                 int tiles_x, int tiles_y) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int x = (int)(i % w), y = (int)((i / w) % h), c = (int)((i / ((long)w * h)) % C), b = (int)(i / ((long)w * h * C));
+  int Ylo, Yhi, Xlo, Xhi;
+  cell_window(y, sy, H, Ylo, Yhi);
+  cell_window(x, sx, W, Xlo, Xhi);
+  float acc = 0.f;
+  for (int TY = Ylo / kLossTH; TY <= (Yhi - 1) / kLossTH; ++TY) {
+    const int Y0 = TY * kLossTH, YN = min(kLossTH, H - Y0);
+    int f0, f1, t0, t1;
+    float l;
+    src_index(Y0, sy, h, f0, t1, l);
+    src_index(Y0 + YN - 1, sy, h, t0, f1, l);
+    if (y < f0 || y > f1) continue;
+    for (int TX = Xlo / kLossTW; TX <= (Xhi - 1) / kLossTW; ++TX) {
+      const int X0 = TX * kLossTW, XN = min(kLossTW, W - X0);
+      int g0, g1;
+      src_index(X0, sx, w, g0, t1, l);
+      src_index(X0 + XN - 1, sx, w, t0, g1, l);
+      if (x < g0 || x > g1) continue;
+      const long tile = ((long)b * tiles_y + TY) * tiles_x + TX;
+      acc += tile_part[((tile * C + c) * kLossFY + (y - f0)) * kLossFX + (x - g0)];
+    }
+  }
+  grad_lo[i] = acc;
+}
+
+static inline unsigned long ce_loss_part_bytes(long tiles) { return ((unsigned long)tiles * sizeof(double) + 15) & ~15ul; }
 
 }  // namespace rfn
 
@@ -206,29 +256,64 @@ using namespace rfn;
 // gradient of that sum with respect to the low-resolution logits; both are zeroed here.  logits: (B, C, h, w) contiguous,
 // dtype 0 fp32 / 1 bf16 / 2 f16; target: (B, H, W) int64; weight: (B, H, W) fp32 or NULL.  round16: round the interpolated
 // logits to `dtype` first (what an unfused 16-bit up-sampling stores).
-int rfn_upsample_ce(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum, int B,
-                    int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16, rfn_stream_t stream) {
+static int upsample_ce_impl(void* workspace, const void* logits, const long* target, const float* weight, float* grad_lo,
+                           double* loss_sum, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16,
+                           rfn_stream_t stream) {
   RFN_REQUIRE(logits && target && grad_lo && loss_sum, "upsample_ce: null pointer");
   RFN_REQUIRE(B > 0 && C > 0 && C <= kLossMaxC && h > 0 && w > 0, "upsample_ce: B=%d C=%d (<= %d) h=%d w=%d", B, C, kLossMaxC, h, w);
   RFN_REQUIRE(H >= 2 * h && W >= 2 * w, "upsample_ce: %dx%d -> %dx%d (scale factors >= 2 only)", h, w, H, W);
   RFN_REQUIRE(dtype >= 0 && dtype <= 2, "upsample_ce: dtype %d (0 = f32, 1 = bf16, 2 = f16)", dtype);
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = zero_async(grad_lo, (size_t)B * C * h * w * sizeof(float), s)) return rc;
+  const bool det = workspace != nullptr;
+  if (!det)
+    if (int rc = zero_async(grad_lo, (size_t)B * C * h * w * sizeof(float), s)) return rc;
   if (int rc = zero_async(loss_sum, kLossSlots * sizeof(double), s)) return rc;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;      // ATen: area_pixel_compute_scale with size=
   dim3 grid(cdiv(W, kLossTW), cdiv(H, kLossTH), B);
+  // deterministic form: workspace = [tiles doubles: loss][tiles x C x kLossFY x kLossFX floats: footprint gradients]
+  const long tiles = (long)grid.x * grid.y * grid.z;
+  double* loss_part = det ? (double*)workspace : nullptr;
+  float* tile_part = det ? (float*)((char*)workspace + ce_loss_part_bytes(tiles)) : nullptr;
 #define RFN_UCE(D)                                                                                                     \
   if (C == kLossMaxC)                                                                                                  \
     hipLaunchKernelGGL((upsample_ce_kernel<D, true>), grid, dim3(256), 0, s, logits, target, weight, grad_lo, loss_sum, \
-                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0);                                         \
+                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0, tile_part, loss_part);                   \
   else                                                                                                                  \
     hipLaunchKernelGGL((upsample_ce_kernel<D, false>), grid, dim3(256), 0, s, logits, target, weight, grad_lo, loss_sum, \
-                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0)
+                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0, tile_part, loss_part)
   if (dtype == 0) RFN_UCE(0);
   else if (dtype == 1) RFN_UCE(1);
   else RFN_UCE(2);
 #undef RFN_UCE
-  return check_launch("upsample_ce");
+  if (int rc = check_launch("upsample_ce")) return rc;
+  if (!det) return RFN_OK;
+  const long total = (long)B * C * h * w;
+  hipLaunchKernelGGL(upsample_ce_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, (const float*)tile_part, grad_lo, total, C,
+                     h, w, H, W, sy, sx, (int)grid.x, (int)grid.y);
+  if (int rc = check_launch("upsample_ce_gather_kernel")) return rc;
+  return ordered_colsum_f64(loss_part, loss_sum, tiles, 1, s);          // slot 0 <- every tile's loss in tile order
+}
+
+int rfn_upsample_ce(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum, int B,
+                    int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16, rfn_stream_t stream) {
+  RFN_REFUSE_NONDET(true, "rfn_upsample_ce", "upsample_ce_kernel, fp32 / fp64 atomics (use rfn_upsample_ce_det)");
+  return upsample_ce_impl(nullptr, logits, target, weight, grad_lo, loss_sum, B, C, h, w, H, W, ignore_index, dtype, round16, stream);
+}
+
+// Deterministic form of rfn_upsample_ce: every 16 x 16 tile stores its loss and its footprint of the low-resolution gradient
+// into `workspace` (rfn_upsample_ce_det_workspace_bytes(B, C, H, W) bytes, no need to zero it); a second launch adds, per
+// low-resolution cell, the tiles that touch it in tile order, a third the tiles' losses (loss_sum[0]; slots 1 .. 63 are zero).
+unsigned long rfn_upsample_ce_det_workspace_bytes(int B, int C, int H, int W) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  const long tiles = (long)cdiv(W, kLossTW) * cdiv(H, kLossTH) * B;
+  return ce_loss_part_bytes(tiles) + (unsigned long)tiles * C * kLossFY * kLossFX * sizeof(float);
+}
+
+int rfn_upsample_ce_det(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum,
+                        void* workspace, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, int round16,
+                        rfn_stream_t stream) {
+  RFN_REQUIRE(workspace, "upsample_ce_det: null workspace");
+  return upsample_ce_impl(workspace, logits, target, weight, grad_lo, loss_sum, B, C, h, w, H, W, ignore_index, dtype, round16, stream);
 }
 
 }  // extern "C"

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
   }
 
   // D[i = n][j = k]: lane holds column k = .. + col, rows n = (r & 3) + 8 (r >> 2) + 4 g
-  float* out = accumulate ? P : P + (long)slab * N * K;
+  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
 #pragma unroll
   for (int i = 0; i < IB; ++i)
 #pragma unroll
@@ -636,7 +636,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);     // 128-byte coalesced fp32 atomics
+        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);     // 128-byte coalesced fp32 atomics
         else out[(long)n * K + kk] = acc[i][j][r];
       }
     }
@@ -649,7 +649,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
       const int cp = threadIdx.x >> 1, e = threadIdx.x & 1;
       float sum = 0.f;
       for (int t = cp; t < 256; t += GP) sum += red[t * 2 + e];
-      atomicAdd(gbias + n0 + threadIdx.x, sum);
+      if (accumulate == 2) gbias[(long)slab * N + n0 + threadIdx.x] = sum;      // per-slab bias partials (deterministic form)
+      else atomicAdd(gbias + n0 + threadIdx.x, sum);
     }
   }
 }
@@ -838,7 +839,7 @@ __global__ __launch_bounds__(256) void gemm_tn2_kernel(const uint16_t* __restric
     __syncthreads();
   }
 
-  float* out = accumulate ? P : P + (long)slab * N * K;
+  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
 #pragma unroll
   for (int i = 0; i < IB; ++i)
 #pragma unroll
@@ -847,7 +848,7 @@ __global__ __launch_bounds__(256) void gemm_tn2_kernel(const uint16_t* __restric
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
+        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
         else out[(long)n * K + kk] = acc[i][j][r];
       }
     }
@@ -862,7 +863,8 @@ __global__ __launch_bounds__(256) void gemm_tn2_kernel(const uint16_t* __restric
       const int c8 = threadIdx.x >> 3, e = threadIdx.x & 7;
       float sum = 0.f;
       for (int qq = 0; qq < NQ; ++qq) sum += red[(qq * (BN / 8) + c8) * 8 + e];
-      atomicAdd(gbias + n0 + threadIdx.x, sum);
+      if (accumulate == 2) gbias[(long)slab * N + n0 + threadIdx.x] = sum;      // per-slab bias partials (deterministic form)
+      else atomicAdd(gbias + n0 + threadIdx.x, sum);
     }
   }
 }
@@ -1143,7 +1145,7 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
     }
   }
 
-  float* out = accumulate ? P : P + (long)slab * N * K;
+  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
 #pragma unroll
   for (int i = 0; i < IB; ++i)
 #pragma unroll
@@ -1152,7 +1154,7 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
+        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
         else out[(long)n * K + kk] = acc[i][j][r];
       }
     }
@@ -1160,7 +1162,10 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
 #pragma unroll
     for (int i = 0; i < IB; ++i) {
       const float sum = half_sum(bsum[i]);
-      if (g == 0) atomicAdd(gbias + n0 + wn * (BN / 2) + i * 32 + col, sum);
+      if (g == 0) {
+        if (accumulate == 2) gbias[(long)slab * N + n0 + wn * (BN / 2) + i * 32 + col] = sum;
+        else atomicAdd(gbias + n0 + wn * (BN / 2) + i * 32 + col, sum);
+      }
     }
   }
 }
@@ -1516,6 +1521,9 @@ int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_b
               "conv2d_nhwc_wgrad: extent / rows_per_slab");
   auto magic = [](long d) { return (unsigned)((0x100000000ULL + d - 1) / d); };
   RFN_REQUIRE(Kpad < 65536, "conv2d_nhwc_wgrad: Kpad=%ld", Kpad);
+  RFN_REQUIRE(accumulate >= 0 && accumulate <= 2, "conv2d_nhwc_wgrad: accumulate %d (0, 1 or 2)", accumulate);
+  RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_conv2d_nhwc_wgrad",
+                    "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
   WgradGeom wg{H, Wd, C, OH, OW, KH, KW, stride, pad, dil, magic(C), magic(KW)};
   hipStream_t s = (hipStream_t)stream;
   return dtype == 1 ? launch_tn<1, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg)
@@ -1532,6 +1540,9 @@ int rfn_gemm_tn(const void* G, const void* X, float* P, long T, long N, long K, 
   RFN_REQUIRE(T > 0 && T < (1L << 31) && rows_per_slab > 0 && rows_per_slab % 32 == 0,
               "gemm_tn: T=%ld rows_per_slab=%d (%% 32)", T, rows_per_slab);
   RFN_REQUIRE(N % 64 == 0 && K % 64 == 0 && ldg % 2 == 0 && ldx % 2 == 0, "gemm_tn: N=%ld K=%ld (%% 64)", N, K);
+  RFN_REQUIRE(accumulate >= 0 && accumulate <= 2, "gemm_tn: accumulate %d (0, 1 or 2)", accumulate);
+  RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_gemm_tn",
+                    "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
   hipStream_t s = (hipStream_t)stream;
   return dtype == 1 ? launch_tn<1>(G, X, P, T, N, K, ldg, ldx, rows_per_slab, accumulate, grad_bias, rowscale, rows_per_sample, s)
                     : launch_tn<2>(G, X, P, T, N, K, ldg, ldx, rows_per_slab, accumulate, grad_bias, rowscale, rows_per_sample, s);
@@ -1545,6 +1556,7 @@ int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, f
   RFN_REQUIRE(G && X && P && grad_bias && rowscale && T && N && K && ldg && ldx && rows_per_slab && rows_per_sample,
               "gemm_tn_grouped: null array");
   RFN_REQUIRE(dtype == 1 || dtype == 2, "gemm_tn_grouped: dtype %d", dtype);
+  RFN_REFUSE_NONDET(true, "rfn_gemm_tn_grouped", "gemm_tn3_group_kernel, fp32 atomics (use rfn_gemm_tn with accumulate = 2)");
   TnGroup grp{};
   grp.count = count;
   long blocks = 0;

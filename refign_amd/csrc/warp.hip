@@ -413,6 +413,7 @@ int rfn_warp_bwd_f32(const float* x, const float* flow, const float* grad_out, f
   RFN_REQUIRE(x && flow && grad_out && (grad_x || grad_flow), "rfn_warp_bwd_f32: null pointer");
   RFN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "rfn_warp_bwd_f32: non-positive size");
   RFN_REQUIRE((long)H * W < 0x7fffffffL && B <= 65535, "rfn_warp_bwd_f32: tensor too large");
+  RFN_REFUSE_NONDET(true, "rfn_warp_bwd_f32", "warp_bwd_kernel, fp32 atomics (no deterministic form)");
   hipStream_t s = (hipStream_t)stream;
   const size_t HW = (size_t)H * W;
   if (grad_x && hipMemsetAsync(grad_x, 0, (size_t)B * C * HW * sizeof(float), s) != hipSuccess)

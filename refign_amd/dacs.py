@@ -15,7 +15,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, determinism
 from ._tensor import current_stream, on_device, ptr, upload_async
 
 IMNET_MEAN = (0.485, 0.456, 0.406)
@@ -84,20 +84,22 @@ def mix(images_src, images_trg, gt_src, pseudo_label, pseudo_weight, class_bits,
         pw = pseudo_weight.to(torch.float32).contiguous()
         lbl = torch.empty_like(gt)
         wgt = torch.empty_like(pw)
-    ws = torch.empty(MAX_BATCH, dtype=torch.float64, device=dev)
+    lib = _lib.load_library()
+    det = determinism.enabled()            # image means from per-workgroup partial sums added in order (csrc/dacs.hip)
+    ws = torch.empty(lib.rfn_dacs_mix_jitter_det_workspace_bytes(H, W) // 8 if det else MAX_BATCH, dtype=torch.float64, device=dev)
     on = (ctypes.c_int * B)(*[0 if j is None else 1 for j in jitter])
     order = (ctypes.c_int * (4 * B))(*[v for j in jitter for v in ([0, 1, 2, 3] if j is None else j[0])])
     factor = (ctypes.c_float * (4 * B))(*[v for j in jitter for v in ([1.0] * 4 if j is None else j[1])])
     hue = (ctypes.c_float * (9 * B))(*[float(v) for j in jitter
                                        for v in (np.eye(3) if j is None else np.asarray(j[2])).reshape(-1)])
     mean3, std3 = (ctypes.c_float * 3)(*IMNET_MEAN), (ctypes.c_float * 3)(*IMNET_STD)
-    lib = _lib.load_library()
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     optr = lambda t: None if t is None else ptr(t)  # noqa: E731
+    mix_jitter = lib.rfn_dacs_mix_jitter_det if det else lib.rfn_dacs_mix_jitter
     with on_device(dev):
-        rc = lib.rfn_dacs_mix_jitter(optr(src), optr(trg), ptr(gt), optr(ps), optr(pw), optr(img), optr(lbl), optr(wgt), ptr(ws),
-                                     B, H, W, ptr(class_bits.contiguous()), cast(on), cast(order), cast(factor), cast(hue),
-                                     cast(mean3), cast(std3), current_stream(dev))
+        rc = mix_jitter(optr(src), optr(trg), ptr(gt), optr(ps), optr(pw), optr(img), optr(lbl), optr(wgt), ptr(ws), B, H, W,
+                        ptr(class_bits.contiguous()), cast(on), cast(order), cast(factor), cast(hue), cast(mean3), cast(std3),
+                        current_stream(dev))
         _lib.check(rc, "dacs_mix_jitter")
         if img is not None and any(s is not None for s in blur_sigma):
             bon = (ctypes.c_int * B)(*[0 if s is None else 1 for s in blur_sigma])

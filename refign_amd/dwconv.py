@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, determinism
 from ._tensor import current_stream, on_device, ptr, require_device_tensor, workspace
 from .params import as_dtype, derived, grad_sink
 
@@ -21,6 +21,13 @@ def _fwd(x, w_tap, bias, dilation, flip, stats=None):
     B, H, W, C = x.shape
     y = torch.empty_like(x)
     lib = _lib.load_library()
+    if stats is not None and determinism.enabled():         # ... as per-block partial rows + an ordered column sum
+        ws = workspace(lib.rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation), x.device)
+        with on_device(x.device):
+            rc = lib.rfn_dwconv3x3_nhwc_fwd_stats_det(ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), ptr(ws), B, H, W, C,
+                                                      dilation, _DT[x.dtype], current_stream(x.device))
+        _lib.check(rc, "dwconv3x3_nhwc_fwd_stats_det")
+        return y
     if stats is not None:                                   # + the BatchNorm statistics of the result (csrc/dwconv.hip STATS)
         with on_device(x.device):
             rc = lib.rfn_dwconv3x3_nhwc_fwd_stats(ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), B, H, W, C, dilation,
@@ -200,9 +207,15 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
     y = torch.empty_like(x)
     lib = _lib.load_library()
-    with on_device(x.device):
-        rc = lib.rfn_dwconv3x3_nhwc_stats(ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, int(dilation), _DT[x.dtype],
-                                          current_stream(x.device))
+    if determinism.enabled():
+        ws = workspace(lib.rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, int(dilation)), x.device)
+        with on_device(x.device):
+            rc = lib.rfn_dwconv3x3_nhwc_stats_det(ptr(x), ptr(w_tap), ptr(b32), ptr(sums), ptr(ws), B, H, W, C, int(dilation),
+                                                  _DT[x.dtype], current_stream(x.device))
+    else:
+        with on_device(x.device):
+            rc = lib.rfn_dwconv3x3_nhwc_stats(ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, int(dilation), _DT[x.dtype],
+                                              current_stream(x.device))
     _lib.check(rc, "dwconv3x3_nhwc_stats")
     group = bnk.sync_group(bn)
     if group is not None:
@@ -219,6 +232,8 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
 def tri_usable(x, convs, bns):
     """the three (conv, bn) pairs are depthwise 3x3 with dilations g, 2 g, 3 g and padding = dilation on a shape the one-pass
     kernel takes (csrc/dwconv.hip dwconv3x3_tri_kernel)"""
+    if determinism.enabled():          # the one-pass statistics kernel adds with fp64 atomics: one branch at a time instead
+        return False
     if len(convs) != 3 or not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 4 and x.is_contiguous()):
         return False
     B, H, W, C = x.shape

@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, determinism
 from ._tensor import current_stream, on_device, ptr
 
 _DT16 = {torch.bfloat16: 1, torch.float16: 2}
@@ -162,10 +162,16 @@ def conv2d_nhwc_wgrad(gy, x, KH, KW, Kpad, stride=1, pad=0, dil=1, bias_out=None
     rows = slab_rows(T, (N // tile) * (Kpad // tile))
     S = -(-T // rows)
     part = torch.empty((S, N, Kpad), dtype=torch.float32, device=gy.device)
+    det = determinism.enabled() and bias_out is not None      # per-slab bias sums, added in slab order (else: fp32 atomics)
+    bpart = torch.empty((S, N), dtype=torch.float32, device=gy.device) if det else bias_out
     with on_device(gy.device):
-        rc = _lib.load_library().rfn_conv2d_nhwc_wgrad(ptr(gy), ptr(x), ptr(part), ptr(bias_out), B, H, W, C, N, KH, KW, stride,
-                                                       pad, dil, N, Kpad, rows, 0, _DT16[gy.dtype], current_stream(gy.device))
+        rc = _lib.load_library().rfn_conv2d_nhwc_wgrad(ptr(gy), ptr(x), ptr(part), ptr(bpart), B, H, W, C, N, KH, KW, stride,
+                                                       pad, dil, N, Kpad, rows, 2 if det else 0, _DT16[gy.dtype],
+                                                       current_stream(gy.device))
     _lib.check(rc, "conv2d_nhwc_wgrad")
+    if det:
+        from .params import sum_rows
+        sum_rows(bpart, out=bias_out.view(-1), accumulate=True)
     return part
 
 
@@ -194,7 +200,8 @@ def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, ro
     """(diag(rowscale) g[T,N])^T @ x[T,K] with the token dimension split into slabs (`rowscale`: fp32, one value per
     `rows_per_sample` consecutive rows -- the stochastic-depth scale of the branch the gradient g belongs to).  `out` None: returns the fp32 partials (S, N, K)
     (deterministic; sum over S is the result).  `out` (N, K) fp32: every slab is ADDED into it with fp32 atomics (the
-    parameter's view of the flat gradient buffer) and `bias_out` (N,) fp32, if given, += the column sums of g.
+    parameter's view of the flat gradient buffer) and `bias_out` (N,) fp32, if given, += the column sums of g -- in
+    deterministic mode (refign_amd/determinism.py) the slabs are stored and added in slab order instead (_gemm_tn_det).
     None if outside the kernel's domain."""
     if not (ENABLED and g.is_cuda and g.dtype in _DT16 and x.dtype == g.dtype and g.dim() == 2 and x.dim() == 2
             and g.stride(1) == 1 and x.stride(1) == 1 and g.stride(0) % 2 == 0 and x.stride(0) % 2 == 0
@@ -216,6 +223,8 @@ def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, ro
                 (bias_out is None or (bias_out.dtype == torch.float32 and bias_out.is_contiguous()
                                       and bias_out.numel() == N))):
             return None
+        if determinism.enabled():
+            return _gemm_tn_det(g, x, int(rows_per_slab), S, out, bias_out, rowscale, rows_per_sample)
         part = out
     else:
         part = torch.empty((S, N, K), dtype=torch.float32, device=g.device)
@@ -226,6 +235,27 @@ def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, ro
                              int(rows_per_sample), _DT16[g.dtype], current_stream(g.device))
     _lib.check(rc, "gemm_tn")
     return part
+
+
+def _gemm_tn_det(g, x, rows_per_slab, S, out, bias_out, rowscale, rows_per_sample):
+    """The accumulate form of gemm_tn in deterministic mode: the slabs' partials (weights AND bias column sums) are stored
+    (rfn_gemm_tn, accumulate = 2) and added into `out` / `bias_out` in slab order by sum_rows -- two or three launches back to
+    back on one stream.  The partial image, S x N x (K + 1) floats, is an allocation of its own (the step's weight gradients run
+    on several streams and inside captured passes), freed to the caching allocator when the call returns."""
+    from .params import sum_rows
+    T, N = g.shape
+    K = x.shape[1]
+    part = torch.empty((S, N * K), dtype=torch.float32, device=g.device)
+    bpart = torch.empty((S, N), dtype=torch.float32, device=g.device) if bias_out is not None else None
+    with on_device(g.device):
+        rc = _lib.load_library().rfn_gemm_tn(ptr(g), ptr(x), ptr(part), T, N, K, g.stride(0), x.stride(0), rows_per_slab, 2,
+                                             ptr(bpart), ptr(rowscale), int(rows_per_sample), _DT16[g.dtype],
+                                             current_stream(g.device))
+    _lib.check(rc, "gemm_tn (deterministic form)")
+    sum_rows(part, out=out.view(-1), accumulate=True)
+    if bpart is not None:
+        sum_rows(bpart, out=bias_out.view(-1), accumulate=True)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -260,7 +290,9 @@ def defer_gemm_tn(g, x, out, bias_out=None, rowscale=None, rows_per_sample=0):
     """Queue `out += (diag(rowscale) g)^T x` (+ `bias_out += column sums of g`) for the next flush.  False when nothing is being
     deferred or the problem is outside the grouped kernel's domain (the caller then launches it where it stands)."""
     q = _WGRAD_QUEUE
-    if q is None or not _tn_domain(g, x, rowscale, rows_per_sample):
+    # (deterministic mode: the grouped kernel adds with atomics; the caller launches the store-and-sum form where it stands, so the
+    # launch order is the order of the autograd graph)
+    if q is None or determinism.enabled() or not _tn_domain(g, x, rowscale, rows_per_sample):
         return False
     T, N = g.shape
     K = x.shape[1]
@@ -456,14 +488,18 @@ class _AttnFn(torch.autograd.Function):
         _lib.check(rc, "attn_bwd_dq")
         (qr, qt), (gr, gt) = _pack(q, q.stride(0), q.stride(1), B, heads, N, nqblk, src2=do)
         nkpad = -(-Nkv // 32) * 32
-        accT = torch.empty(B * heads * 2 * 64 * nkpad, dtype=torch.float32, device=dev)
+        chunk = _chunk_blocks(nqblk, Nkv, B * heads)
+        det = determinism.enabled()
+        # (deterministic form: one dK / dV image per query chunk, added in chunk order by the finishing kernel)
+        images = -(-nqblk // chunk) if det else 1
+        accT = torch.empty(images * B * heads * 2 * 64 * nkpad, dtype=torch.float32, device=dev)
         dkv = torch.empty_like(kv)
         k_view, v_view = kv[:, :, :C], kv[:, :, C:]
+        bwd_dkv = lib.rfn_attn_bwd_dkv_det if det else lib.rfn_attn_bwd_dkv
         with on_device(dev):
-            rc = lib.rfn_attn_bwd_dkv(ptr(k_view), ptr(v_view), kv.stride(0), kv.stride(1), ptr(qr), ptr(qt), ptr(gr),
-                                      ptr(gt), ptr(lse2), ptr(delta), ptr(accT), ptr(dkv), B, heads, N, Nkv, nqblk,
-                                      nqpad, nkpad, _chunk_blocks(nqblk, Nkv, B * heads), float(scale), dt,
-                                      current_stream(dev))
+            rc = bwd_dkv(ptr(k_view), ptr(v_view), kv.stride(0), kv.stride(1), ptr(qr), ptr(qt), ptr(gr), ptr(gt), ptr(lse2),
+                         ptr(delta), ptr(accT), ptr(dkv), B, heads, N, Nkv, nqblk, nqpad, nkpad, chunk, float(scale), dt,
+                         current_stream(dev))
         _lib.check(rc, "attn_bwd_dkv")
         return dq, dkv, None, None
 

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from . import f8 as _f8
 from . import linear as _linear
-from . import mfma
+from . import determinism, mfma
 from ._tensor import const_tensor
 from .align import BaseHead
 from .conv import Conv2d, patch_conv_tokens
@@ -37,6 +37,7 @@ from .layernorm import LayerNorm
 from .layers import MLP, ConvBNReLU, DropPath
 from .linear import Linear
 from .upcat import upsample_concat
+from .upsample import interpolate_bilinear
 
 # ---------------------------------------------------------------------------------------------------------------------
 # MiT (SegFormer encoder)
@@ -429,7 +430,7 @@ def _mmseg_init(module):
 
 
 def _up(x, size):
-    return F.interpolate(x, size=size, mode='bilinear', align_corners=False)
+    return interpolate_bilinear(x, size=size)
 
 
 def _up_logits(x, size):
@@ -796,8 +797,8 @@ def hrda_head(self, hrda_scale_attention: nn.Module, head_os: int, is_teacher: b
             if self.training and not is_teacher and isinstance(boxes[0], DeviceBox):
                 box = boxes[0]
                 att = att * box.mask(lr_seg.shape[2], lr_seg.shape[3], 2.0 * head_os, lr_seg)
-                up_lr = F.interpolate((1 - att) * lr_seg, scale_factor=2, mode='bilinear', align_corners=False)
-                up_att = F.interpolate(att, scale_factor=2, mode='bilinear', align_corners=False)
+                up_lr = interpolate_bilinear((1 - att) * lr_seg, scale_factor=2)
+                up_att = interpolate_bilinear(att, scale_factor=2)
                 inserted = box.insert(hr_seg, up_lr.shape[2:], head_os)
                 return up_att * inserted + up_lr, defer_logits(hr_seg, (box.h, box.w), fused_ce_consumer(self)), box
             if self.training and not is_teacher:
@@ -807,8 +808,8 @@ def hrda_head(self, hrda_scale_attention: nn.Module, head_os: int, is_teacher: b
                 sy, sx = hr_crop_slice(box, 2.0 * head_os)
                 mask[:, :, sy, sx] = 1
                 att = att * mask
-                up_lr = F.interpolate((1 - att) * lr_seg, scale_factor=2, mode='bilinear', align_corners=False)
-                up_att = F.interpolate(att, scale_factor=2, mode='bilinear', align_corners=False)
+                up_lr = interpolate_bilinear((1 - att) * lr_seg, scale_factor=2)
+                up_att = interpolate_bilinear(att, scale_factor=2)
                 inserted = torch.zeros_like(up_lr)
                 sy, sx = hr_crop_slice(box, head_os)
                 inserted[:, :, sy, sx] = hr_seg
@@ -904,9 +905,21 @@ class _UpsampleCEFn(torch.autograd.Function):
         total = torch.empty(64, dtype=torch.float64, device=lg.device)          # kLossSlots partial sums
         # 16-bit logits: the unfused path stores the up-sampled logits in that dtype before the fp32 softmax
         rc = None
+        lib = _lib.load_library()
+        if determinism.enabled():
+            # per-tile partials + ordered sums (csrc/loss.hip): the loss arrives in slot 0, the other slots are zero
+            from ._tensor import workspace
+            ws = workspace(lib.rfn_upsample_ce_det_workspace_bytes(B, C, H, W), lg.device)
+            with on_device(lg.device):
+                rc = lib.rfn_upsample_ce_det(ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), ptr(ws), B, C, h, w, H, W,
+                                             int(ignore_index), _CE_DT[lg.dtype], 1, current_stream(lg.device))
+            _lib.check(rc, "upsample_ce_det")
+            ctx.save_for_backward(grad)
+            ctx.npix, ctx.dtype = float(B * H * W), logits.dtype
+            return (total[0] / ctx.npix).to(torch.float32)
         with on_device(lg.device):
-            rc = _lib.load_library().rfn_upsample_ce(ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), B, C, h, w, H, W,
-                                                     int(ignore_index), _CE_DT[lg.dtype], 1, current_stream(lg.device))
+            rc = lib.rfn_upsample_ce(ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), B, C, h, w, H, W,
+                                     int(ignore_index), _CE_DT[lg.dtype], 1, current_stream(lg.device))
         _lib.check(rc, "upsample_ce")
         ctx.save_for_backward(grad)
         ctx.npix, ctx.dtype = float(B * H * W), logits.dtype

@@ -385,16 +385,25 @@ class Trainer:
     reference is driven through (run.py fit | validate | test | predict); `save_checkpoint` / `load_checkpoint`."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
-                 scaler_args=None, ckpt_path=None):
+                 scaler_args=None, ckpt_path=None, deterministic=False):
         """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
         entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
         scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
         growth_interval); 'bf16' / 'bf16-mixed' -- bf16 autocast; 32 -- no autocast.  Anything else: ValueError.
-        `ckpt_path` (Lightning's `fit(ckpt_path=...)`): a file of save_checkpoint to continue from (load_checkpoint)."""
+        `ckpt_path` (Lightning's `fit(ckpt_path=...)`): a file of save_checkpoint to continue from (load_checkpoint).
+        `deterministic` (Lightning's `--trainer.deterministic true`): bit-reproducible steps -- same build, machine type, seeds
+        and batches give the same bits in every loss, parameter, buffer and optimiser state.  Fixed for the life of the trainer
+        (refign_amd/determinism.py: on here, off in close(); the kernels that add with floating-point atomics are replaced by
+        their store-and-sum forms or refuse) and not available with precision=32.  One process, one GPU."""
         from .amp import parse_precision
         self.precision = parse_precision(precision)
         if scaler_args and self.precision != "16":
             raise ValueError("Trainer: scaler_args needs precision=16")
+        self.deterministic = bool(deterministic)
+        if self.deterministic and self.precision == "32":
+            raise ValueError("Trainer: deterministic=True is not available with precision=32 (the fp32 parity attention adds its "
+                             "dK / dV chunks with atomics)")
+        self._det_held = False
         self.model = model
         if gc_interval is None:
             gc_interval = int(os.environ.get("RFN_GC_INTERVAL", "100"))
@@ -491,6 +500,11 @@ class Trainer:
             self.broadcast_parameters()
             if dist.get_world_size() > 1:                    # a rank that never arrives must not hang the others for ever
                 self.guard = StallGuard(dist.get_rank(), dist.get_world_size())
+        # the last act before anything launches a kernel that has two forms: a constructor that raised further up holds nothing
+        if self.deterministic:
+            from . import determinism
+            determinism.acquire()
+            self._det_held = True
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
 
@@ -541,7 +555,8 @@ class Trainer:
         try:
             # (the step's main-stream work on a stream of its own / of another priority: neutral, profiles/r05_main_priority_ab.txt --
             # HIP offers two priority levels here, (0, -1), and the teacher's stream already has the high one)
-            with self._autocast():
+            from . import determinism
+            with determinism.torch_deterministic(self.deterministic), self._autocast():
                 self.model.training_step(batch, batch_idx)
             if self.guard is not None:
                 self.guard.note(f"step {self._steps_done} queued")
@@ -836,12 +851,16 @@ class Trainer:
     def close(self):
         """Give the process its cyclic garbage collector back (step() runs with it disabled between its own collections)
         and stop the stall guard."""
-        if self.guard is not None:
+        if getattr(self, "guard", None) is not None:
             self.guard.stop()
             self.guard = None
-        if self.gc_interval and self._steps_done:
+        if getattr(self, "gc_interval", 0) and getattr(self, "_steps_done", 0):
             import gc
             gc.enable()
+        if getattr(self, "_det_held", False):
+            from . import determinism
+            self._det_held = False
+            determinism.release()
 
     def __del__(self):
         try:

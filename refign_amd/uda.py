@@ -36,6 +36,7 @@ from . import dacs as _dacs
 from . import f8 as _f8
 from .graphs import GraphedNoGrad, GraphedSegment, GraphedSplitStep, GraphedStep
 from .params import ema_update
+from .upsample import interpolate_bilinear
 from .config import instantiate_class
 from . import seg as _seg
 from .seg import DeviceBox, defer_logits, draw_crop_offsets, hrda_backbone, hrda_head, predraw_crop, push_device_crop
@@ -160,7 +161,7 @@ def _upsample_logits(logits, size):
     (20 MB) makes the up-sampled tensor NCHW-contiguous from the start: same arithmetic, no copy."""
     if logits.is_cuda:
         logits = logits.contiguous()
-    return F.interpolate(logits, size, mode='bilinear', align_corners=False)
+    return interpolate_bilinear(logits, size=size)
 
 
 def _logits_for_loss(model, logits, size):
@@ -556,7 +557,13 @@ class DomainAdaptationSegmentationModel(nn.Module):
         # labels are 0 .. 18 and 255; histc drops values outside [0, 255] (another ignore convention, -1 ...): the bin total
         # then falls short of the pixel count and _take_class_prefetch declines (torch.unique keeps such labels, and the host's
         # random stream depends on the size of the class set)
-        hist = torch.histc(g.to(torch.float32), bins=256, min=0, max=255)
+        # (torch's deterministic switch refuses histc on floats wholesale: its bins are float atomics.  Here every add is + 1.0 onto a
+        # count below 2^24, exact in fp32 in any order; a label map too large for that takes torch.unique in the next step)
+        from . import determinism
+        if g.numel() >= 1 << 24 and torch.are_deterministic_algorithms_enabled():
+            return
+        with determinism.torch_switch_suspended():
+            hist = torch.histc(g.to(torch.float32), bins=256, min=0, max=255)
         host = getattr(self, "_class_hist_host", None)
         if host is None:
             host = self._class_hist_host = torch.empty(256, dtype=torch.float32).pin_memory()
