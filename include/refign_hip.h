@@ -747,6 +747,26 @@ int rfn_upsample_ce_det(const void* logits, const long* target, const float* wei
 int rfn_upsample_bilinear2d_bwd(const void* grad_out, void* grad_in, long planes, int h, int w, int H, int W, float scale_y,
                                 float scale_x, int dtype, rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Step log (csrc/steplog.hip, refign_amd/steplog.py; additions to ABI 4): a training step's scalars into one row of
+ * fp64 values on the device, with no host synchronisation.  Both only read what they log and use no floating-point
+ * atomics: legal under rfn_set_deterministic(1), bit-identical from launch to launch.
+ *   rfn_steplog_gather      row[i] = (double)*ptrs[i] for i < n, one launch.  ptrs / dtypes: HOST arrays of n DEVICE
+ *                           pointers and dtype codes (0 f32, 1 bf16, 2 f16, 3 f64, 4 i32), read at call time (they travel
+ *                           in the kernel arguments).  Every conversion is exact.  Errors (nothing is launched): n < 1 or
+ *                           n > 32, a null pointer, a pointer not aligned to its dtype, an unknown dtype code.
+ *   rfn_grad_sqnorm_groups  out[g] = sum of flat[i]^2 over the chunks of group g, g < ngroups <= 32, accumulated in fp64;
+ *                           out[ngroups] = the number of chunks whose partial sum is not finite.  flat: n fp32, 16-byte
+ *                           aligned.  chunks: DEVICE table of nchunks x 3 int64 (offset, length, group); a chunk is summed
+ *                           by one workgroup, so the caller cuts long runs (refign_amd/steplog.py: 32 768 elements); a
+ *                           chunk outside [0, n) or with a group outside [0, ngroups) is not read and counts as a
+ *                           non-finite partial.  partials: nchunks doubles of device scratch, written by the first launch
+ *                           and read by the second.  Partials are added per group in chunk order.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_steplog_gather(const void* const* ptrs, const int* dtypes, int n, double* row, rfn_stream_t stream);
+int rfn_grad_sqnorm_groups(const float* flat, long n, const long* chunks, int nchunks, int ngroups, double* partials,
+                           double* out, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

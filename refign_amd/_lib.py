@@ -154,6 +154,9 @@ SIGNATURES = {
     "rfn_upsample_ce_det_workspace_bytes": (ctypes.c_ulong, [c_int] * 4),
     "rfn_upsample_ce_det": (c_int, [c_void_p] * 6 + [c_int] * 9 + [c_void_p]),
     "rfn_upsample_bilinear2d_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_long] + [c_int] * 4 + [c_float, c_float, c_int, c_void_p]),
+    # step log (refign_amd/steplog.py; additions to ABI 4)
+    "rfn_steplog_gather": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
+    "rfn_grad_sqnorm_groups": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

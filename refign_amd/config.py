@@ -104,7 +104,8 @@ def trainer_kwargs(cfg):
     """What the loops of refign_amd.trainer.Trainer take from a loaded YAML's `trainer:` section (LightningCLI's Trainer
     arguments): `max_steps`, `sync_batchnorm`, `precision` as they stand, `val_every_n_steps` from the ValEveryNSteps
     callback's `every_n_steps` and `save_last` from ModelCheckpoint, found in the `callbacks` list by class_path.  Missing
-    entries: None (False for the two flags).  Loggers, LearningRateMonitor and every other Lightning argument stay ignored.
+    entries: None (False for the two flags).  Loggers and LearningRateMonitor are read by trainer_logging; every other
+    Lightning argument stays ignored.
     -> Trainer(model, sync_batchnorm=, precision=) and Trainer.fit(max_steps=, val_every_n_steps=, save_last=)."""
     tr = (cfg or {}).get("trainer") or {}
     out = {"max_steps": tr.get("max_steps"), "val_every_n_steps": None, "save_last": False,
@@ -129,3 +130,26 @@ def trainer_deterministic(cfg):
     if isinstance(v, str):
         return v.strip().lower() in ("true", "1", "yes", "warn")
     return bool(v)
+
+
+def trainer_logging(cfg):
+    """The record of the run as a loaded YAML asks for it: `trainer.logger` (one spec or a list; the first
+    pytorch_lightning.loggers.TensorBoardLogger with its `save_dir` / `name` / `version` becomes a
+    refign_amd.steplog.TensorBoardLogger, anything else is passed over), `trainer.log_every_n_steps` (Lightning's default 50
+    when absent) and whether LearningRateMonitor is among the callbacks.  Kept out of trainer_kwargs like trainer_deterministic.
+    -> {"logger": TensorBoardLogger or None, "log_every_n_steps": n, "log_lr": bool}, the keywords of Trainer(model, ...).
+    The logger touches the disk on its first write only."""
+    tr = (cfg or {}).get("trainer") or {}
+    out = {"logger": None, "log_every_n_steps": int(tr.get("log_every_n_steps") or 50), "log_lr": False}
+    loggers = tr.get("logger")
+    for spec in ([loggers] if is_spec(loggers) else loggers if isinstance(loggers, list) else []):
+        if is_spec(spec) and spec["class_path"].rsplit(".", 1)[-1] == "TensorBoardLogger" and out["logger"] is None:
+            from .steplog import TensorBoardLogger
+            args = spec.get("init_args") or {}
+            out["logger"] = TensorBoardLogger(args.get("save_dir", "lightning_logs"), name=args.get("name", "default"),
+                                              version=args.get("version"))
+    callbacks = tr.get("callbacks") or []
+    for cb in ([callbacks] if is_spec(callbacks) else callbacks):
+        if is_spec(cb) and cb["class_path"].rsplit(".", 1)[-1] == "LearningRateMonitor":
+            out["log_lr"] = True
+    return out

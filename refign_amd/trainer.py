@@ -385,7 +385,7 @@ class Trainer:
     reference is driven through (run.py fit | validate | test | predict); `save_checkpoint` / `load_checkpoint`."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
-                 scaler_args=None, ckpt_path=None, deterministic=False):
+                 scaler_args=None, ckpt_path=None, deterministic=False, logger=None, log_every_n_steps=50, log_lr=True):
         """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
         entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
         scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
@@ -394,8 +394,29 @@ class Trainer:
         `deterministic` (Lightning's `--trainer.deterministic true`): bit-reproducible steps -- same build, machine type, seeds
         and batches give the same bits in every loss, parameter, buffer and optimiser state.  Fixed for the life of the trainer
         (refign_amd/determinism.py: on here, off in close(); the kernels that add with floating-point atomics are replaced by
-        their store-and-sum forms or refuse) and not available with precision=32.  One process, one GPU."""
+        their store-and-sum forms or refuse) and not available with precision=32.  One process, one GPU.
+        `logger` (a steplog.TensorBoardLogger, or anything with log_metrics(dict, step) / flush() / close(); None: nothing is
+        recorded and nothing new runs), `log_every_n_steps`, `log_lr`: the record of the run.  The step that takes
+        model.global_step from s to s + 1 is recorded when (s + 1) % log_every_n_steps == 0 and its row is labelled s (rows
+        49, 99, ... at the default: this project's definition).  A row holds every entry of model.logged under its own
+        name, `grad_norm/<optimizer group>` and `grad_norm/total` of the gradient the optimizer consumed (after the
+        all-reduce and, under precision=16, the unscale; a skipped fp16 step shows its infinite or NaN norm),
+        `grad_norm/nonfinite_chunks`, under precision=16 `amp/scale`, `amp/found_inf` (both this step's) and
+        `amp/skipped_steps` (before this step), and with `log_lr` `lr-AdamW/<optimizer group>`, the rate this step used.
+        The row is put together on the device between the unscale and AdamW (refign_amd/steplog.py) and reaches the host
+        through a pinned mirror: the step does not wait for it.  step() hands finished rows to the logger and to
+        `log_history`, a list of (step, {name: float}); validate() / test() log their results at the current global_step;
+        fit() flushes before each validation, before each checkpoint and at its end, close() flushes and closes the file.
+        Several ranks: rank 0 records and writes.  Nothing of the logger goes into a checkpoint."""
         from .amp import parse_precision
+        self.log_every_n_steps, self.log_lr = int(log_every_n_steps), bool(log_lr)
+        if logger is not None and self.log_every_n_steps < 1:
+            raise ValueError("Trainer: log_every_n_steps must be positive")
+        if logger is not None and dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+            logger = None                                    # rank 0 records and writes; no collective is involved
+        self.logger, self.log_history = logger, []
+        self._steplog = self._norm_plan = None
+        self.log_stalls, self._eval_logged = 0, set()
         self.precision = parse_precision(precision)
         if scaler_args and self.precision != "16":
             raise ValueError("Trainer: scaler_args needs precision=16")
@@ -536,6 +557,8 @@ class Trainer:
         """`next_batch` (optional): the batch of the following step, already on the device -- lets the model compute
         what depends on its inputs only (the frozen ImageNet encoder's features of the next source images) while this
         step's mixed pass runs (uda.prefetch_imnet_features)."""
+        if self._steplog is not None:
+            self._hand_over(self._steplog.poll())            # rows whose events have completed: no waiting
         if next_batch is not None:
             batch = dict(batch, image_src_next=next_batch["image_src"], semantic_src_next=next_batch.get("semantic_src"),
                          image_trg_next=next_batch.get("image_trg"), image_ref_next=next_batch.get("image_ref"))
@@ -568,6 +591,78 @@ class Trainer:
             seg._DEVICE_CROPS.clear()
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.model.logged.items()} \
             if os.environ.get("RFN_LOG_LOSSES") else None
+
+    # -- the record of the run -----------------------------------------------------------------------------------------
+    def _record_row(self):
+        """Called by _OptimizerProxy.step between the unscale and AdamW: the losses are in model.logged and the current stream
+        has joined the streams that made them, the gradients are final, the scaler has not been updated, and
+        model.global_step is still the label of this step."""
+        if self.logger is None:
+            return
+        label = int(self.model.global_step)
+        if (label + 1) % self.log_every_n_steps != 0:
+            return
+        from . import steplog
+        flat = self.grads.flat
+        if flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Trainer: the optimizer step is being captured into a graph; a logged row (copy to the host mirror, "
+                               "event record) cannot be part of a capture")
+        groups = self.optimizer.param_groups
+        gnames = [str(g.get("name", i)) for i, g in enumerate(groups)]
+        scalars, host = {}, {}
+        for k, v in self.model.logged.items():
+            if k in self._eval_logged:                       # left there by validate() / test(), which log their own rows
+                continue
+            if torch.is_tensor(v):
+                if v.numel() != 1:
+                    continue                                 # (a row holds scalars)
+                if v.device != flat.device:
+                    raise TypeError(f"Trainer: model.logged[{k!r}] is on {v.device}, the step runs on {flat.device}")
+                scalars[k] = v if v.dtype in steplog.DTYPE_CODES else v.double()
+            else:
+                host[k] = float(v)
+        if self.scaler is not None:
+            scalars.update({"amp/scale": self.scaler._scale, "amp/found_inf": self.scaler.found_inf,
+                            "amp/skipped_steps": self.scaler._skipped})
+        if self.log_lr:
+            host.update({f"lr-AdamW/{n}": float(g["lr"]) for n, g in zip(gnames, groups)})
+        if self._norm_plan is None:
+            self._norm_plan = steplog.GradNormPlan.for_buffer(self.grads, groups)
+        log = self._steplog
+        if log is None or log.names != list(scalars):
+            if log is not None:                              # another set of logged names (a model stepped by hand): a new ring
+                self._hand_over(log.flush())
+                self.log_stalls += log.stalls
+            log = self._steplog = steplog.StepLog(flat.device, list(scalars), group_names=gnames)
+        log.record(label, scalars, grads=(flat, self._norm_plan), host=host)
+
+    def _hand_over(self, rows):
+        for step, row in rows:
+            self.log_history.append((step, row))
+            self.logger.log_metrics(row, step)
+
+    def _log_results(self, results):
+        """validate / test results as scalars at the current global_step; a per-class list becomes <name>/<class index>."""
+        if self.logger is None or not results:
+            return
+        row = {}
+        for k, v in results.items():
+            if isinstance(v, (list, tuple)):
+                row.update({f"{k}/{i}": float(x) for i, x in enumerate(v)})
+            else:
+                row[k] = float(v)
+        self.flush_log()
+        self._hand_over([(int(self.model.global_step), row)])
+
+    def flush_log(self):
+        """Every recorded row to the logger and to log_history (waits for the rows' events, not for the device), and the
+        logger's file flushed.  Returns the number of times record() had to wait for a free row so far."""
+        if self.logger is None:
+            return 0
+        if self._steplog is not None:
+            self._hand_over(self._steplog.flush())
+        self.logger.flush()
+        return self.log_stalls + (self._steplog.stalls if self._steplog is not None else 0)
 
     # -- loops ---------------------------------------------------------------------------------------------------------
     def _autocast(self):
@@ -632,8 +727,13 @@ class Trainer:
             if metrics is None or not evaltail.eval_step(model, metrics, batch, name):
                 step(batch, i, idx, src_name=name)
 
+        before = dict(model.logged) if self.logger is not None and hasattr(model, "logged") else None
         out = self._evaluation(split, loaders, per_batch, end, metrics)
-        return {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in (out or {}).items()}
+        if before is not None:                               # what the epoch end logged is no part of a training step's row
+            self._eval_logged |= {k for k, v in model.logged.items() if k not in before or before[k] is not v}
+        out = {k: (v.tolist() if torch.is_tensor(v) else v) for k, v in (out or {}).items()}
+        self._log_results(out)
+        return out
 
     def validate(self, loaders):
         """Lightning's `validate`: every batch of every loader through the model's validation step, then
@@ -711,12 +811,16 @@ class Trainer:
                 raise RuntimeError("Trainer.fit: the model's training_step did not advance global_step")
             batch = nxt
             if rule.should_validate(int(model.global_step)):
+                self.flush_log()
                 history.append((int(model.global_step), self.validate(val_loaders)))
                 if last is not None:
+                    self.flush_log()
                     self.save_checkpoint(last)
                     saved_at = int(model.global_step)
         if last is not None and saved_at != int(model.global_step):
+            self.flush_log()
             self.save_checkpoint(last)
+        self.flush_log()
         return history
 
     # -- checkpoints ---------------------------------------------------------------------------------------------------
@@ -850,7 +954,13 @@ class Trainer:
 
     def close(self):
         """Give the process its cyclic garbage collector back (step() runs with it disabled between its own collections)
-        and stop the stall guard."""
+        and stop the stall guard; with a logger: hand over every recorded row and close its file."""
+        if getattr(self, "logger", None) is not None:
+            try:
+                self.flush_log()
+            finally:
+                self.logger.close()
+                self.logger = None
         if getattr(self, "guard", None) is not None:
             self.guard.stop()
             self.guard = None
@@ -879,6 +989,13 @@ class _OptimizerProxy:
     def zero_grad(self):
         self.t.grads.zero()
 
+    def _record_row(self):
+        """Trainer._record_row, looked up at call time (tests wrap it); whoever drives the proxy with a stand-in for the trainer
+        that has no logging (no `_record_row`) records nothing."""
+        record = getattr(self.t, "_record_row", None)
+        if record is not None:
+            record()
+
     def step(self):
         self.t.grads.all_reduce_mean(self.t.bucket_mb)        # (and what a concurrently run pass accumulated on the side)
         sc = self.t.scaler
@@ -887,6 +1004,7 @@ class _OptimizerProxy:
             # rank through the sum, so all ranks skip together -- then AdamW, skipped on the device when found_inf is set, then
             # the new scale.  torch's own step (first step, non-plain configurations) needs the flag on the host.
             sc.unscale_(self.t.grads.flat)
+            self._record_row()                                # this step's scale and found_inf: the scaler is updated below
             if self.t.fast_step is not None and self.t.fast_step.step_amp(sc.found_inf):
                 sc.update(self.t.fast_step.device_step)
                 return
@@ -896,6 +1014,7 @@ class _OptimizerProxy:
                 self.t.optimizer._opt_called = True       # a skipped step still lets the LR scheduler advance
             sc.update(None)
             return
+        self._record_row()
         if self.t.fast_step is not None:
             self.t.fast_step.step()
         else:
