@@ -666,6 +666,31 @@ int rfn_crop_flip_norm_u8(const void* image, const void* label, int C, int H, in
                           const float* mean3, const float* std3, float* out_image, long* out_label, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * N4, third part -- the LOAD-TIME resize on the device, bit-equal to Pillow (csrc/resample.hip; additions to ABI 4): what the
+ * reference's data set readers do per sample on the host (data_modules/datasets/cityscapes.py:119-127: Image.resize(dims,
+ * BILINEAR) for images, NEAREST for labels) and data_modules.transforms.Resize (transforms.py:57-74,120-203).  The image is the
+ * DECODED one, uint8 (H, W, 3) channels last.  Tables are DEVICE arrays made by refign_amd/resample.py exactly as Pillow makes
+ * them (Resample.c precompute_coeffs + normalize_coeffs_8bpc; Geometry.c ImagingScaleAffine), per axis:
+ *   bounds  int32 [out][2] = (first source pixel, number of taps) of every output pixel
+ *   coef    int32 [out][kmax] = the taps in 22-bit fixed point; kmax = ceil(max(in / out, 1)) * 2 + 1
+ * A pass is (sum_k in[first + k] * coef[k] + 2^21) >> 22 clipped to a byte; horizontal first, bytes in between.
+ *   rfn_resize_crop_flip_norm_u8  out_image (3, h, w) fp32 = rfn_crop_flip_norm_u8 of the crop (top, left, h, w) of the image
+ *                                 resized to (Hd, Wd), without that image ever being stored: a workgroup per tile of the
+ *                                 crop (16 x 64 pixels; fewer rows when H / Hd is large), the horizontal pass of the tile's source rows in LDS.  mean3 / std3: HOST arrays.
+ *   rfn_resize_u8                 the resized image itself, uint8 (3, Hd, Wd).
+ *   rfn_resize_nearest_u8         label map (H, W) -> (Hd, Wd) through ytab[Hd] / xtab[Wd] (source row / column per output one).
+ * Errors (nothing is launched): a null pointer, a crop outside the resized image, h or Hd > 65535, kmax not the value above,
+ * kmax > 129 (down-scaling by more than 64).  Table entries are clamped to the source before they index it.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_resize_crop_flip_norm_u8(const void* image_hwc, int H, int W, int Hd, int Wd, const int* bounds_x, const int* coef_x, int kmax_x,
+                                 const int* bounds_y, const int* coef_y, int kmax_y, int top, int left, int h, int w, int flip,
+                                 const float* mean3, const float* std3, float* out_image, rfn_stream_t stream);
+int rfn_resize_u8(const void* image_hwc, int H, int W, int Hd, int Wd, const int* bounds_x, const int* coef_x, int kmax_x,
+                  const int* bounds_y, const int* coef_y, int kmax_y, void* out_chw, rfn_stream_t stream);
+int rfn_resize_nearest_u8(const void* label, int H, int W, int Hd, int Wd, const int* ytab, const int* xtab, void* out,
+                          rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K5 (BASELINE.json config 5, "bf16 HRDA + fp8 MFMA attention"): fp8 (OCP e4m3, fp32 accumulate) matrix-core path of
  * the gradient-free EMA teacher (segmentation_model.py:204-209 runs MiT-B5, mix_transformer.py:96-103,137-164, on 40
  * HRDA views per GPU).  No reference analogue (the reference's recipe is 16-bit AMP, README.md:262); csrc/f8.hip.

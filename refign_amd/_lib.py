@@ -127,6 +127,11 @@ SIGNATURES = {
     "rfn_dacs_mix_jitter": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 7 + [c_void_p]),
     "rfn_crop_label_hist_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "rfn_crop_flip_norm_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4 + [c_void_p]),
+    # load-time resize (refign_amd/resample.py; additions to ABI 4)
+    "rfn_resize_crop_flip_norm_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int] * 2 + [c_int] * 5
+                                     + [c_void_p] * 3 + [c_void_p]),
+    "rfn_resize_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int] * 2 + [c_void_p, c_void_p]),
+    "rfn_resize_nearest_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_void_p]),
     "rfn_dacs_blur": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [c_void_p]),
     "rfn_gemm_nt_f8": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_void_p, c_int, c_float]
                        + [ctypes.c_long] * 6 + [c_void_p]),

@@ -153,3 +153,59 @@ def trainer_logging(cfg):
         if is_spec(cb) and cb["class_path"].rsplit(".", 1)[-1] == "LearningRateMonitor":
             out["log_lr"] = True
     return out
+
+
+# transforms of a data set's pipeline that the device data step covers, in the order the reference's configs apply them
+_INGEST_ORDER = ("Resize", "ToTensor", "RandomCrop", "RandomHorizontalFlip", "ConvertImageDtype", "Normalize")
+_INGEST_ARGS = {"Resize": {"size", "img_only", "only_if_larger"}, "ToTensor": set(), "RandomCrop": {"size", "cat_max_ratio"},
+                "RandomHorizontalFlip": {"p"}, "ConvertImageDtype": set(), "Normalize": {"mean", "std"}}
+
+
+def ingest_plan(cfg, split, dataset):
+    """What `data.init_args.load_config[split][dataset]` of a loaded YAML asks of the path from a decoded file to the batch
+    tensors, as the keywords of the device data step (refign_amd/resample.py, refign_amd/datastep.py):
+      dims           load-time size (h, w) of the data set reader, or None
+      resize         transforms.Resize's `size` (int or (h, w)), or None; img_only: its flag (the label keeps its size);
+                     only_if_larger: its flag
+      crop_size      RandomCrop's size (h, w), or None; cat_max_ratio: its ratio (1.0 when absent)
+      flip           RandomHorizontalFlip's probability (0.0 when absent)
+      mean / std     Normalize's statistics (ImageNet's by default)
+      load_keys      the reader's keys, as given
+    train: RareClassSourceSampler / PairSampler(..., dims=, crop_size=, cat_max_ratio=); val / test / predict:
+    resample.EvalIngest(dims=, resize=, img_only=).  The pipeline must be made of ToTensor / Resize / RandomCrop /
+    RandomHorizontalFlip / ConvertImageDtype / Normalize in the reference's order with their defaults for everything the plan
+    does not carry; anything else (ColorJitter, the MegaDepth flow synthesis, ...) raises OutOfScopeError naming the transform.
+    `build` and IGNORED_PREFIXES are untouched: data_modules.* specs still come back as specs from there."""
+    from .datastep import IMNET_MEAN, IMNET_STD
+    try:
+        sec = cfg["data"]["init_args"]["load_config"][split][dataset]
+    except (KeyError, TypeError) as e:
+        raise KeyError(f"ingest_plan: no data.init_args.load_config.{split}.{dataset} in this config") from e
+    pair = lambda v: v if isinstance(v, int) else tuple(int(a) for a in v)  # noqa: E731
+    plan = {"dims": pair(sec["dims"]) if sec.get("dims") is not None else None, "resize": None, "img_only": False,
+            "only_if_larger": False, "crop_size": None, "cat_max_ratio": 1.0, "flip": 0.0, "mean": tuple(IMNET_MEAN),
+            "std": tuple(IMNET_STD), "load_keys": list(sec.get("load_keys") or [])}
+    stage = -1
+    for spec in sec.get("transforms") or []:
+        path = spec["class_path"] if is_spec(spec) else str(spec)
+        name, args = path.rsplit(".", 1)[-1], (spec.get("init_args") or {}) if is_spec(spec) else {}
+        if not path.startswith("data_modules.transforms.") or name not in _INGEST_ORDER:
+            raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) is outside the device data step "
+                                  f"({' / '.join(_INGEST_ORDER)})")
+        if _INGEST_ORDER.index(name) <= stage and name != "Resize":
+            raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) comes out of the order {' -> '.join(_INGEST_ORDER)}")
+        extra = set(args) - _INGEST_ARGS[name]
+        if extra or (name == "Resize" and plan["resize"] is not None):
+            raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) with {sorted(extra) or 'a second Resize'} is outside the "
+                                  f"device data step")
+        stage = _INGEST_ORDER.index(name)
+        if name == "Resize":
+            plan["resize"], plan["img_only"] = pair(args["size"]), bool(args.get("img_only", False))
+            plan["only_if_larger"] = bool(args.get("only_if_larger", False))
+        elif name == "RandomCrop":
+            plan["crop_size"], plan["cat_max_ratio"] = pair(args["size"]), float(args.get("cat_max_ratio", 1.0))
+        elif name == "RandomHorizontalFlip":
+            plan["flip"] = float(args.get("p", 0.5))
+        elif name == "Normalize":
+            plan["mean"], plan["std"] = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
+    return plan

@@ -14,7 +14,9 @@ counted by ONE kernel launch (csrc/datastep.hip: the draws of a call do not depe
 does -- the host draws the whole chain, asks once and rewinds python's `random` stream to the stop, so the stream is consumed
 exactly as the reference consumes it), and crop + flip + conversion + normalisation write straight into the sample's slot of
 the batch tensors.  Same `random` calls in the same order: seeded alike, it yields the reference's batches
-(tests/test_datastep_*.py against goldens captured from the reference's own code, tests/golden/make_golden_data.py)."""
+(tests/test_datastep_*.py against goldens captured from the reference's own code, tests/golden/make_golden_data.py).
+With `dims=(Hd, Wd)` the samplers start one stage earlier, at the DECODED file: the data set readers' load-time resize
+(datasets/cityscapes.py:119-127) runs on the device too, bit-equal to Pillow and fused into the crop (refign_amd/resample.py)."""
 import random
 
 import numpy as np
@@ -114,10 +116,14 @@ class RareClassSourceSampler:
     """Cityscapes.__getitem__ with rcs_enabled (datasets/cityscapes.py:100-158) over ToTensor / RandomCrop / RandomHorizontalFlip /
     ConvertImageDtype / Normalize.  `load(index)` -> (image uint8 (3, H, W), label uint8 (H, W)) host tensors (what ToTensor leaves,
     transforms.py:250-279) -- pinned ones are uploaded asynchronously.  rcs_classes / rcs_classprob / indices_with_class: as
-    Cityscapes.__init__ builds them (:82-98,160-190)."""
+    Cityscapes.__init__ builds them (:82-98,160-190).
+    dims=(Hd, Wd): `load(index)` -> (decoded image uint8 (H, W, 3) channels last, label uint8 (H, W)) of any size; the label is
+    resized (NEAREST) on the device once per sample and every box is drawn and counted on the resized map as before; the image
+    is resized (BILINEAR), cropped, mirrored and normalised by one kernel.  The `random` calls and their order do not change."""
 
     def __init__(self, load, rcs_classes, rcs_classprob, indices_with_class, crop_size, device, cat_max_ratio=0.75,
-                 rcs_min_pixels=3000, rcs_min_crop_ratio=0.5, ignore_index=255, mean=IMNET_MEAN, std=IMNET_STD, hists=None):
+                 rcs_min_pixels=3000, rcs_min_crop_ratio=0.5, ignore_index=255, mean=IMNET_MEAN, std=IMNET_STD, hists=None,
+                 dims=None):
         self.load, self.device = load, torch.device(device)
         self.rcs_classes, self.rcs_classprob = list(rcs_classes), rcs_classprob
         self.indices_with_class = indices_with_class
@@ -125,6 +131,7 @@ class RareClassSourceSampler:
         self.rcs_min_pixels, self.rcs_min_crop_ratio = rcs_min_pixels, rcs_min_crop_ratio
         self.mean, self.std = mean, std
         self._hists = hists                               # tests inject a host counter; None: the device kernel
+        self.dims = None if dims is None else (int(dims[0]), int(dims[1]))
 
     def _augment_params(self, lbl_dev, h, w):
         """one `load_and_augment_sample`: the crop box (with its histogram) and the flip draw"""
@@ -141,10 +148,15 @@ class RareClassSourceSampler:
         c = random.choices(self.rcs_classes, weights=self.rcs_classprob, k=1)[0]
         index = random.choice(self.indices_with_class[c])
         img, lbl = self.load(index)
+        if self.dims is not None:                          # np.asarray(PIL image) as it comes
+            img, lbl = torch.as_tensor(img), torch.as_tensor(lbl)
         img_d = img.to(self.device, non_blocking=True)
         lbl_d = lbl.to(self.device, non_blocking=True)
         self._host_label = lbl                             # (for an injected host counter)
-        h, w = lbl.shape
+        if self.dims is not None and tuple(lbl_d.shape) != self.dims:
+            from .resample import resize_nearest_u8
+            lbl_d = resize_nearest_u8(lbl_d, self.dims)
+        h, w = lbl_d.shape
         box, flip, hist = self._augment_params(lbl_d, h, w)
         if self.rcs_min_crop_ratio > 0:
             for _ in range(10):
@@ -155,22 +167,36 @@ class RareClassSourceSampler:
 
     def sample(self, out_image=None, out_label=None):
         _, img_d, lbl_d, (top, left, hh, ww), flip = self.draw()
+        if self.dims is not None:
+            from .resample import resize_crop_flip_normalize
+            out_image = resize_crop_flip_normalize(img_d, self.dims, top, left, hh, ww, flip, out_image, self.mean, self.std)
+            _, out_label = crop_flip_normalize(None, lbl_d, top, left, hh, ww, flip, None, out_label)
+            return out_image, out_label
         return crop_flip_normalize(img_d, lbl_d, top, left, hh, ww, flip, out_image, out_label, self.mean, self.std)
 
 
 class PairSampler:
     """the target set's pipeline (refign_hrda_star.yaml:25-40): RandomCrop(size) + RandomHorizontalFlip with ONE set of parameters
-    for image and image_ref, then conversion + normalisation.  `load(index)` -> (image uint8, image_ref uint8) host tensors."""
+    for image and image_ref, then conversion + normalisation.  `load(index)` -> (image uint8, image_ref uint8) host tensors.
+    dims=(Hd, Wd): `load` returns the two DECODED images, (H, W, 3) channels last, each of any size; both are resized to dims
+    inside the crop kernel."""
 
-    def __init__(self, load, crop_size, device, mean=IMNET_MEAN, std=IMNET_STD):
+    def __init__(self, load, crop_size, device, mean=IMNET_MEAN, std=IMNET_STD, dims=None):
         self.load, self.size, self.device, self.mean, self.std = load, tuple(crop_size), torch.device(device), mean, std
+        self.dims = None if dims is None else (int(dims[0]), int(dims[1]))
 
     def sample(self, index, out_image=None, out_ref=None):
         img, ref = self.load(index)
+        if self.dims is not None:
+            img, ref = torch.as_tensor(img), torch.as_tensor(ref)
         img_d, ref_d = img.to(self.device, non_blocking=True), ref.to(self.device, non_blocking=True)
-        h, w = img.shape[-2:]
+        h, w = img.shape[-2:] if self.dims is None else self.dims
         (top, left, hh, ww), _ = draw_crop(h, w, self.size)
         flip = random.random() < 0.5
+        if self.dims is not None:
+            from .resample import resize_crop_flip_normalize
+            return (resize_crop_flip_normalize(img_d, self.dims, top, left, hh, ww, flip, out_image, self.mean, self.std),
+                    resize_crop_flip_normalize(ref_d, self.dims, top, left, hh, ww, flip, out_ref, self.mean, self.std))
         a, _ = crop_flip_normalize(img_d, None, top, left, hh, ww, flip, out_image, None, self.mean, self.std)
         b, _ = crop_flip_normalize(ref_d, None, top, left, hh, ww, flip, out_ref, None, self.mean, self.std)
         return a, b
