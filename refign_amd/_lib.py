@@ -6,7 +6,10 @@ never falls back to a CPU or PyTorch implementation.
 """
 import ctypes
 import os
+import re
 import threading
+
+from ._tensor import current_stream, on_device
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (RFN_LIB: another build of the same library, for A/B runs of kernel variants -- tools/ab_build.sh)
@@ -14,161 +17,37 @@ _LIB_PATH = os.environ.get("RFN_LIB") or os.path.join(_HERE, "lib", "librefign_h
 _lock = threading.Lock()
 _lib = None
 
-c_int = ctypes.c_int
-c_float = ctypes.c_float
 c_void_p = ctypes.c_void_p
-
-_CORR12 = [c_int] * 12
-# name -> (restype, argtypes); must list every entry point declared in include/refign_hip.h
-SIGNATURES = {
-    "rfn_abi_version": (c_int, []),
-    "rfn_last_error": (ctypes.c_char_p, []),
-    "rfn_set_deterministic": (c_int, [c_int]),
-    "rfn_get_deterministic": (c_int, []),
-    "rfn_corr_fwd_f32": (c_int, [c_void_p] * 3 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_corr_fwd_f64": (c_int, [c_void_p] * 3 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_corr_bwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_corr_bwd_f64": (c_int, [c_void_p] * 5 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_corr_fwd_f16": (c_int, [c_void_p] * 3 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_corr_bwd_f16": (c_int, [c_void_p] * 5 + [c_int] * 4 + _CORR12 + [c_void_p]),
-    "rfn_local_corr_layer_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
-    "rfn_local_corr_layer_split_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "rfn_local_corr_layer_split_workspace_bytes": (ctypes.c_long, [c_int] * 4),
-    "rfn_global_corr_layer_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
-    "rfn_warp_f32": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
-    "rfn_warp_bwd_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
-    "rfn_l2norm_channels_f32": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),
-    "rfn_l2norm_channels_nhwc16_f32": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p]),
-    "rfn_maxpool2x2_nhwc16": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
-    "rfn_retile_copy": (c_int, [c_void_p] * 2 + [c_int] * 7 + [c_void_p]),
-    "rfn_area_resize_f32": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p]),
-    "rfn_refine_workspace_bytes": (ctypes.c_ulong, [c_int]),
-    "rfn_label_majority": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_float, c_void_p]),
-    "rfn_refine_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_int, c_void_p]),
-    "rfn_align_tail_f32": (c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p]),
-    "rfn_dwconv3x3_nhwc_stats": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
-    "rfn_dwconv3x3_tri_usable": (c_int, [c_int] * 5),
-    "rfn_dwconv3x3_tri_stats": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "rfn_dwconv3x3_tri_stats_f16": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "rfn_dwconv3x3_tri_bn_act_fwd": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p]),
-    "rfn_dwconv3x3_tri_bn_act_fwd_f16": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p]),
-    "rfn_dwconv3x3_bn_act_nhwc_fwd": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_float, c_float, c_int, c_int, c_void_p]),
-    "rfn_dwconv3x3_nhwc_fwd_stats": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
-    "rfn_dwconv3x3_nhwc_fwd": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
-    "rfn_dwconv3x3_gelu_nhwc_fwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
-    "rfn_layernorm_fwd": (c_int, [c_void_p] * 6 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
-    "rfn_layernorm_bwd_workspace_bytes": (ctypes.c_ulong, [c_int]),
-    "rfn_layernorm_bwd": (c_int, [c_void_p] * 9 + [ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "rfn_layernorm_bwd_add": (c_int, [c_void_p] * 10 + [ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "rfn_layernorm_bwd_add2": (c_int, [c_void_p] * 11 + [ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "rfn_dwconv3x3_bwd_weight_workspace_bytes": (ctypes.c_ulong, [c_int]),
-    "rfn_dwconv3x3_nhwc_bwd_weight": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
-    "rfn_sum_rows_workspace_bytes": (ctypes.c_ulong, [ctypes.c_long, ctypes.c_long]),
-    "rfn_sum_rows": (c_int, [c_void_p] * 3 + [ctypes.c_long, ctypes.c_long, c_int, c_int, c_void_p]),
-    "rfn_linear_param_grads": (c_int, [c_void_p] * 3 + [ctypes.c_long, ctypes.c_long, c_int, c_void_p, c_void_p, c_int,
-                                       ctypes.c_long, c_int, c_int, c_void_p]),
-    "rfn_upsample_concat_nhwc": (c_int, [c_void_p] * 4 + [ctypes.POINTER(c_int)] * 3 + [c_int, c_void_p] + [c_int] * 4
-                                 + [c_void_p]),
-    "rfn_upsample_concat_nhwc_bwd": (c_int, [c_void_p] * 5 + [ctypes.POINTER(c_int)] * 3 + [c_int] * 5 + [c_void_p]),
-    "rfn_patchify_tokens": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
-    "rfn_patchify_tokens_cmajor": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
-    "rfn_multi_cast_chunk_elems": (c_int, []),
-    "rfn_multi_transpose_tile": (c_int, []),
-    "rfn_multi_permute_chunk_elems": (c_int, []),
-    "rfn_multi_permute_cast_f32": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_multi_cast_f32_bf16": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_multi_ema_f32": (c_int, [c_void_p, c_int, c_float, c_void_p]),
-    "rfn_multi_transpose_cast_f32_bf16": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_multi_adamw_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "rfn_multi_cast_f32_f16": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_multi_transpose_cast_f32_f16": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_amp_unscale_f32": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p]),
-    "rfn_multi_adamw_amp_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "rfn_amp_update_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p]),
-    "rfn_gemm_nt": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p] + [ctypes.c_long] * 6 + [c_int, c_void_p]),
-    "rfn_conv2d_nhwc": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 10 + [ctypes.c_long, ctypes.c_long, c_int,
-                                                                                       c_void_p]),
-    "rfn_gemm_nt_o32": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p] + [ctypes.c_long] * 6 + [c_void_p]),
-    "rfn_conv2d_nhwc_o32": (c_int, [c_void_p] * 3 + [c_int, c_void_p] + [c_int] * 10 + [ctypes.c_long, ctypes.c_long, c_int,
-                                                                                           c_void_p]),
-    "rfn_conv2d_nhwc_dgrad": (c_int, [c_void_p] * 3 + [c_int] * 10 + [ctypes.c_long, ctypes.c_long, c_int, c_void_p]),
-    "rfn_conv2d_nhwc_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 10 + [ctypes.c_long, ctypes.c_long, c_int, c_int, c_int,
-                                      c_void_p]),
-    "rfn_gemm_tn": (c_int, [c_void_p] * 3 + [ctypes.c_long] * 5 + [c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                            c_void_p]),
-    "rfn_gemm_tn_grouped": (c_int, [c_int] + [c_void_p] * 12 + [c_int, c_void_p]),
-    "rfn_attn_pack": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long] + [c_int] * 4 + [c_void_p] * 6),
-    "rfn_attn_fwd": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, c_void_p, ctypes.c_long,
-                             ctypes.c_long, c_void_p] + [c_int] * 6 + [c_float, c_int, c_int, c_void_p]),
-    "rfn_attn_bwd_dq": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, ctypes.c_long, ctypes.c_long]
-                        + [c_void_p] * 6 + [ctypes.c_long, ctypes.c_long] + [c_int] * 6 + [c_float, c_int, c_int,
-                                                                                         c_void_p]),
-    "rfn_attn_bwd_dkv": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long] + [c_void_p] * 8 + [c_int] * 8
-                         + [c_float, c_int, c_void_p]),
-    "rfn_attn32_fwd": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long] * 3 + [c_void_p] + [c_int] * 6 + [c_float, c_void_p]),
-    "rfn_attn32_bwd": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long] * 2 + [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long,
-                                                                                c_void_p, c_void_p]
-                       + [c_void_p, ctypes.c_long, ctypes.c_long] * 2 + [c_int] * 7 + [c_float, c_void_p]),
-    "rfn_split3_bf16": (c_int, [c_void_p, ctypes.c_long, c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_long, c_int, c_int,
-                                c_int, c_void_p]),
-    "rfn_ffn_fc1_dw_gelu_bf16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "rfn_ffn_fc1_dw_gelu_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "rfn_split3_cat_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "rfn_upsample_ce": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
-    "rfn_slide_argmax_confmat": (c_int, [c_void_p] + [c_int] * 5 + [ctypes.POINTER(c_int)] + [c_int] * 3 + [c_void_p, c_int,
-                                                                                                       c_void_p, c_void_p, c_void_p]),
-    "rfn_bn_stats_fwd": (c_int, [c_void_p] * 2 + [ctypes.c_long, c_int, c_int, c_void_p]),
-    "rfn_bn_apply_fwd": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_float, c_int, c_int, c_void_p]),
-    "rfn_bn_apply_fwd_ld": (c_int, [c_void_p] * 4 + [ctypes.c_long] + [c_void_p] * 3 + [ctypes.c_long, c_int, c_float, c_float, c_int, c_int, c_void_p]),
-    "rfn_bn_stats_bwd": (c_int, [c_void_p] * 6 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
-    "rfn_bn_apply_bwd": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
-    "rfn_bn_train_fwd": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_float, c_int, c_int, c_void_p]),
-    "rfn_bn_train_bwd": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
-    "rfn_dacs_mix_jitter": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 7 + [c_void_p]),
-    "rfn_crop_label_hist_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "rfn_crop_flip_norm_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4 + [c_void_p]),
-    # load-time resize (refign_amd/resample.py; additions to ABI 4)
-    "rfn_resize_crop_flip_norm_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int] * 2 + [c_int] * 5
-                                     + [c_void_p] * 3 + [c_void_p]),
-    "rfn_resize_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_int] * 2 + [c_void_p, c_void_p]),
-    "rfn_resize_nearest_u8": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 3 + [c_void_p]),
-    "rfn_dacs_blur": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [c_void_p]),
-    "rfn_gemm_nt_f8": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 3 + [c_int, c_int, c_void_p, c_int, c_float]
-                       + [ctypes.c_long] * 6 + [c_void_p]),
-    "rfn_quant_rows_f8": (c_int, [c_void_p, c_int, c_void_p]),
-    "rfn_quant_f8": (c_int, [c_void_p, c_void_p, ctypes.c_long, c_float, c_void_p]),
-    "rfn_layernorm_fwd_f8": (c_int, [c_void_p] * 4 + [ctypes.c_long, c_int, c_float, c_float, c_void_p]),
-    "rfn_dwconv3x3_gelu_nhwc_fwd_f8": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float, c_float, c_void_p]),
-    "rfn_attn_pack_f8": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long] + [c_int] * 4 + [c_void_p, c_void_p]),
-    "rfn_attn_fwd_f8": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_void_p, ctypes.c_long, ctypes.c_long]
-                        + [c_int] * 5 + [c_float] * 5 + [c_void_p]),
-    "rfn_uncertainty9_weights_len": (c_int, []),
-    "rfn_uncertainty9_frontend_f32": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
-    "rfn_uncertainty9_frontend_f16mm": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
-    # deterministic forms (refign_amd/determinism.py; additions to ABI 4)
-    "rfn_bn_stats_det_workspace_bytes": (ctypes.c_ulong, [ctypes.c_long, c_int]),
-    "rfn_bn_stats_fwd_det": (c_int, [c_void_p] * 3 + [ctypes.c_long, c_int, c_int, c_void_p]),
-    "rfn_bn_stats_bwd_det": (c_int, [c_void_p] * 7 + [ctypes.c_long, c_int, c_float, c_int, c_int, c_void_p]),
-    "rfn_dwconv3x3_stats_det_workspace_bytes": (ctypes.c_ulong, [c_int] * 5),
-    "rfn_dwconv3x3_nhwc_fwd_stats_det": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
-    "rfn_dwconv3x3_nhwc_stats_det": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
-    "rfn_attn_bwd_dkv_det": (c_int, [c_void_p, c_void_p, ctypes.c_long, ctypes.c_long] + [c_void_p] * 8 + [c_int] * 8
-                             + [c_float, c_int, c_void_p]),
-    "rfn_dacs_mix_jitter_det_workspace_bytes": (ctypes.c_ulong, [c_int, c_int]),
-    "rfn_dacs_mix_jitter_det": (c_int, [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 7 + [c_void_p]),
-    "rfn_upsample_ce_det_workspace_bytes": (ctypes.c_ulong, [c_int] * 4),
-    "rfn_upsample_ce_det": (c_int, [c_void_p] * 6 + [c_int] * 9 + [c_void_p]),
-    "rfn_upsample_bilinear2d_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_long] + [c_int] * 4 + [c_float, c_float, c_int, c_void_p]),
-    # step log (refign_amd/steplog.py; additions to ABI 4)
-    "rfn_steplog_gather": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
-    "rfn_grad_sqnorm_groups": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-}
+_HEADER = os.path.join(_HERE, os.pardir, "include", "refign_hip.h")
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "unsigned long": ctypes.c_ulong, "float": ctypes.c_float,
+            "double": ctypes.c_double, "rfn_stream_t": c_void_p}
 
 
-# RFN_ABI_VERSION of include/refign_hip.h this table was written against (4: round 6 added rfn_attn32_fwd / _bwd, rfn_split3_bf16,
-# rfn_split3_cat_bf16, rfn_ffn_fc1_dw_gelu_bf16; 2: rfn_global_corr_layer_f32 takes a workspace,
-# rfn_dacs_mix_jitter accepts one half of the mix; 3: the transpose-cast table holds 64 x 64 tiles, rfn_multi_transpose_tile)
-ABI_VERSION = 4
+def parse_header(text):
+    """(RFN_ABI_VERSION, {name: (restype, argtypes)}) of a C-ABI header: every `ret rfn_name(args);` it declares.  Any
+    pointer and rfn_stream_t become c_void_p (a `const char*` RETURN: c_char_p), scalars map through _SCALARS; a type
+    that is in neither raises and names the declaration -- never guessed."""
+    version = int(re.search(r"^\s*#\s*define\s+RFN_ABI_VERSION\s+(\d+)", text, re.M).group(1))
+    text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", " ", text, flags=re.S | re.M)
+
+    def ctype(decl, what, is_return=False):
+        words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            return ctypes.c_char_p if is_return and words == ["char", "*"] else c_void_p
+        key = " ".join(words if is_return else words[:-1])      # a by-value parameter carries its name
+        if key not in _SCALARS or (not is_return and words[-1] in _SCALARS):
+            raise ValueError(f"refign_hip.h: unknown C type in `{decl.strip()}` of {what}")
+        return _SCALARS[key]
+
+    signatures = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(rfn_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        signatures[name] = (ctype(ret, name, True), [ctype(a, name) for a in args])
+    return version, signatures
+
+
+with open(_HEADER) as _f:
+    ABI_VERSION, SIGNATURES = parse_header(_f.read())
 
 
 def library_path():
@@ -215,3 +94,12 @@ def check(rc, what):
     if rc != 0:
         msg = load_library().rfn_last_error()
         raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+def call(name, device, *args):
+    """Launch entry point `name` on `device`: on torch's current stream there (every launching entry point takes the
+    stream LAST), RuntimeError on a non-zero code.  The one place the launch protocol lives: ~3 000 calls per eager step."""
+    with on_device(device):
+        rc = getattr(_lib or load_library(), name)(*args, current_stream(device))
+    if rc != 0:
+        check(rc, name)

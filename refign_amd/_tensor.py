@@ -1,6 +1,10 @@
 """Tensor plumbing between torch (device memory + streams) and the C ABI.  torch is plumbing only."""
 import torch
 
+# dtype codes of the C ABI (include/refign_hip.h); DTYPE_CODE16: kernels that take 16-bit elements only
+DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+DTYPE_CODE16 = {t: c for t, c in DTYPE_CODE.items() if t.itemsize == 2}
+
 
 def require_device_tensor(t, name, dtype=None):
     """Mirror of the reference's CHECK_CUDA / CHECK_CONTIGUOUS (correlation_sampler.cpp:13-16): RuntimeError."""

@@ -233,13 +233,10 @@ def _maxpool2x2(x, m):
     if not xh.is_contiguous():
         return None
     from . import _lib
-    from ._tensor import current_stream, on_device, ptr
+    from ._tensor import ptr
     B, H, W, C = xh.shape
     y = torch.empty((B, H // 2, W // 2, C), dtype=x.dtype, device=x.device)
-    with on_device(x.device):
-        rc = _lib.load_library().rfn_maxpool2x2_nhwc16(ptr(xh), ptr(y), B, H, W, C, 1 if x.dtype == torch.bfloat16 else 2,
-                                                       current_stream(x.device))
-    _lib.check(rc, "maxpool2x2_nhwc16")
+    _lib.call("rfn_maxpool2x2_nhwc16", x.device, ptr(xh), ptr(y), B, H, W, C, 1 if x.dtype == torch.bfloat16 else 2)
     return y.permute(0, 3, 1, 2)
 
 

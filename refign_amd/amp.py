@@ -12,7 +12,7 @@ round-trips."""
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 
 
 class LossScaler:
@@ -36,21 +36,15 @@ class LossScaler:
         if not (grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous() and grads.data_ptr() % 16 == 0):
             raise RuntimeError("LossScaler.unscale_: a contiguous, 16-byte aligned fp32 CUDA buffer is required")
         self.found_inf.zero_()
-        with on_device(grads.device):
-            rc = _lib.load_library().rfn_amp_unscale_f32(ptr(grads), grads.numel(), ptr(self._scale), ptr(self.found_inf),
-                                                         current_stream(grads.device))
-        _lib.check(rc, "amp_unscale_f32")
+        _lib.call("rfn_amp_unscale_f32", grads.device, ptr(grads), grads.numel(), ptr(self._scale), ptr(self.found_inf))
 
     def update(self, optimizer_step=None):
         """After the optimizer: new scale from found_inf; `optimizer_step` (a device float tensor of the optimizer's step
         count, or None) is advanced by one when the step was taken."""
         with torch.no_grad():
             self._skipped.add_(self.found_inf)
-        with on_device(self.device):
-            rc = _lib.load_library().rfn_amp_update_scale(ptr(self._scale), ptr(self._growth_tracker), ptr(self.found_inf),
-                                                          ptr(optimizer_step), self.growth_factor, self.backoff_factor,
-                                                          self.growth_interval, current_stream(self.device))
-        _lib.check(rc, "amp_update_scale")
+        _lib.call("rfn_amp_update_scale", self.device, ptr(self._scale), ptr(self._growth_tracker), ptr(self.found_inf),
+                  ptr(optimizer_step), self.growth_factor, self.backoff_factor, self.growth_interval)
 
     # --- host-side reads (each synchronises) ---------------------------------------------------------------------------
     def get_scale(self):

@@ -16,10 +16,9 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, determinism
-from ._tensor import current_stream, on_device, ptr, workspace
+from ._tensor import ptr, workspace
+from ._tensor import DTYPE_CODE16 as _DT16          # (the name the GPU tests read the codes under)
 from .params import grad_sink
-
-_DT16 = {torch.bfloat16: 1, torch.float16: 2}
 
 
 def data_parallel():
@@ -121,54 +120,38 @@ def usable(x, bn, dtype, channels=None, count=None):
 def _stats_fwd(xh, sums):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
     if determinism.enabled():                              # per-workgroup partial rows + an ordered column sum (csrc/bn.hip)
-        lib = _lib.load_library()
-        ws = workspace(lib.rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
-        with on_device(xh.device):
-            _lib.check(lib.rfn_bn_stats_fwd_det(ptr(xh), ptr(sums), ptr(ws), T, C, _DT16[xh.dtype], current_stream(xh.device)),
-                       "bn_stats_fwd_det")
+        ws = workspace(_lib.load_library().rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
+        _lib.call("rfn_bn_stats_fwd_det", xh.device, ptr(xh), ptr(sums), ptr(ws), T, C, _DT16[xh.dtype])
         return
-    with on_device(xh.device):
-        _lib.check(_lib.load_library().rfn_bn_stats_fwd(ptr(xh), ptr(sums), T, C, _DT16[xh.dtype], current_stream(xh.device)),
-                   "bn_stats_fwd")
+    _lib.call("rfn_bn_stats_fwd", xh.device, ptr(xh), ptr(sums), T, C, _DT16[xh.dtype])
 
 
 def _apply_fwd(xh, weight, bias, y, sums, bn, relu):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
     if y.stride(-2) != C:                                  # a channel slice of a wider channels-last tensor
-        with on_device(xh.device):
-            _lib.check(_lib.load_library().rfn_bn_apply_fwd_ld(ptr(xh), ptr(weight), ptr(bias), ptr(y), y.stride(-2), ptr(sums),
-                                                               ptr(bn.running_mean), ptr(bn.running_var), T, C,
-                                                               float(bn.eps), float(bn.momentum), int(relu),
-                                                               _DT16[xh.dtype], current_stream(xh.device)), "bn_apply_fwd_ld")
+        _lib.call("rfn_bn_apply_fwd_ld", xh.device, ptr(xh), ptr(weight), ptr(bias), ptr(y), y.stride(-2), ptr(sums),
+                  ptr(bn.running_mean), ptr(bn.running_var), T, C, float(bn.eps), float(bn.momentum), int(relu),
+                  _DT16[xh.dtype])
         return
-    with on_device(xh.device):
-        _lib.check(_lib.load_library().rfn_bn_apply_fwd(ptr(xh), ptr(weight), ptr(bias), ptr(y), ptr(sums),
-                                                        ptr(bn.running_mean), ptr(bn.running_var), T, C, float(bn.eps),
-                                                        float(bn.momentum), int(relu), _DT16[xh.dtype],
-                                                        current_stream(xh.device)), "bn_apply_fwd")
+    _lib.call("rfn_bn_apply_fwd", xh.device, ptr(xh), ptr(weight), ptr(bias), ptr(y), ptr(sums), ptr(bn.running_mean),
+              ptr(bn.running_var), T, C, float(bn.eps), float(bn.momentum), int(relu), _DT16[xh.dtype])
 
 
 def _stats_bwd(xh, gy, sums, weight, bias, bsums, eps, relu):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
     if determinism.enabled():
-        lib = _lib.load_library()
-        ws = workspace(lib.rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
-        with on_device(xh.device):
-            _lib.check(lib.rfn_bn_stats_bwd_det(ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), ptr(ws), T, C,
-                                                eps, int(relu), _DT16[xh.dtype], current_stream(xh.device)), "bn_stats_bwd_det")
+        ws = workspace(_lib.load_library().rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
+        _lib.call("rfn_bn_stats_bwd_det", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), ptr(ws),
+                  T, C, eps, int(relu), _DT16[xh.dtype])
         return
-    with on_device(xh.device):
-        _lib.check(_lib.load_library().rfn_bn_stats_bwd(ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), T, C,
-                                                        eps, int(relu), _DT16[xh.dtype], current_stream(xh.device)),
-                   "bn_stats_bwd")
+    _lib.call("rfn_bn_stats_bwd", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), T, C, eps,
+              int(relu), _DT16[xh.dtype])
 
 
 def _apply_bwd(xh, gy, sums, bsums, weight, bias, gx, eps, relu):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
-    with on_device(xh.device):
-        _lib.check(_lib.load_library().rfn_bn_apply_bwd(ptr(xh), ptr(gy), ptr(sums), ptr(bsums), ptr(weight), ptr(bias),
-                                                        ptr(gx), T, C, eps, int(relu), _DT16[xh.dtype],
-                                                        current_stream(xh.device)), "bn_apply_bwd")
+    _lib.call("rfn_bn_apply_bwd", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(bsums), ptr(weight), ptr(bias), ptr(gx), T, C,
+              eps, int(relu), _DT16[xh.dtype])
 
 
 class _BNActTrain(torch.autograd.Function):

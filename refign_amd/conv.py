@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import mfma as _mfma
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import DTYPE_CODE, ptr
 from .params import _identity, as_dtype, compute_dtype, derived, grad_sink
 
 
@@ -99,7 +99,6 @@ class Conv2d(nn.Conv2d):
 # accumulated into the flat buffer) + one scatter copy; the library's convolution backward for this shape is five
 # launches of its own plus per-call zero-fill / cast tensor ops (~85 us of GPU time per layer per pass, 240 per step).
 # ---------------------------------------------------------------------------------------------------------------------
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
 def _split32():
@@ -119,22 +118,19 @@ _PATCH_CMAJOR = True
 
 
 def _cmajor_ok(x, C, r):
-    return _PATCH_CMAJOR and r in (2, 4, 8) and x.is_cuda and x.dtype in _DT and C % 8 == 0 and C >= 16 and \
+    return _PATCH_CMAJOR and r in (2, 4, 8) and x.is_cuda and x.dtype in DTYPE_CODE and C % 8 == 0 and C >= 16 and \
         r * r * C * x.element_size() <= 65528
 
 
 def _patchify(src, dst, B, H, W, C, r, inverse, cmajor=False):
-    lib = _lib.load_library()
-    with on_device(src.device):
-        fn = lib.rfn_patchify_tokens_cmajor if cmajor else lib.rfn_patchify_tokens
-        rc = fn(ptr(src), ptr(dst), B, H, W, C, r, _DT[src.dtype], 1 if inverse else 0, current_stream(src.device))
-    _lib.check(rc, "patchify_tokens")
+    _lib.call("rfn_patchify_tokens_cmajor" if cmajor else "rfn_patchify_tokens", src.device, ptr(src), ptr(dst), B, H, W, C, r,
+              DTYPE_CODE[src.dtype], 1 if inverse else 0)
 
 
 def _to_patches(x, H, W, r, cmajor=False):
     B, N, C = x.shape
     Hr, Wr = H // r, W // r
-    if x.is_cuda and x.dtype in _DT and C % 8 == 0 and x.is_contiguous():
+    if x.is_cuda and x.dtype in DTYPE_CODE and C % 8 == 0 and x.is_contiguous():
         out = torch.empty((B * Hr * Wr, r * r * C), dtype=x.dtype, device=x.device)
         _patchify(x, out, B, H, W, C, r, False, cmajor)              # one vectorised gather (csrc/upcat.hip)
         return out, Hr, Wr
@@ -146,7 +142,7 @@ def _to_patches(x, H, W, r, cmajor=False):
 
 
 def _from_patches(gp, B, H, W, C, r, Hr, Wr, cmajor=False):
-    if gp.is_cuda and gp.dtype in _DT and C % 8 == 0 and gp.is_contiguous():
+    if gp.is_cuda and gp.dtype in DTYPE_CODE and C % 8 == 0 and gp.is_contiguous():
         ragged = Hr * r != H or Wr * r != W
         out = (torch.zeros if ragged else torch.empty)((B, H * W, C), dtype=gp.dtype, device=gp.device)
         _patchify(gp, out, B, H, W, C, r, True, cmajor)
@@ -253,7 +249,7 @@ def patch_conv_tokens(x, H, W, conv):
     # channel-major patches where the weight gradient is wanted (the student); the gradient-free networks keep the (ry, rx, c)
     # rows, whose gather needs no transposition (teacher, 40 views: 16 vs 22 us per call)
     needs_grad = torch.is_grad_enabled() and conv.weight.requires_grad
-    cmajor = needs_grad and _cmajor_ok(x, C, r) and cd in _DT
+    cmajor = needs_grad and _cmajor_ok(x, C, r) and cd in DTYPE_CODE
     if cmajor:
         w2 = as_dtype(conv.weight, cd).detach().view(Co, C * r * r)
     else:

@@ -17,7 +17,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from . import _lib
-from ._tensor import current_stream, ptr, require_device_tensor, same_device, on_device
+from ._tensor import ptr, require_device_tensor, same_device
 
 # (half: the pybind module of the reference dispatches it on the device, correlation_cuda_kernel.cu:267; `forward` / `backward`
 # below take it, `spatial_correlation_sample` casts to float32 like the reference's wrapper and never passes it)
@@ -50,12 +50,8 @@ def forward(input1, input2, kH, kW, patchH, patchW, padH, padW, dilationH, dilat
     if oH <= 0 or oW <= 0:
         raise RuntimeError(f"correlation.forward: empty output {oH}x{oW}")
     out = torch.empty((B, patchH, patchW, oH, oW), dtype=input1.dtype, device=dev)
-    lib = _lib.load_library()
-    fn = getattr(lib, "rfn_corr_fwd_" + _suffix(input1))
-    with on_device(dev):
-        rc = fn(ptr(input1), ptr(input2), ptr(out), B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilationH,
-                dilationW, dilation_patchH, dilation_patchW, dH, dW, current_stream(dev))
-    _lib.check(rc, "correlation.forward")
+    _lib.call("rfn_corr_fwd_" + _suffix(input1), dev, ptr(input1), ptr(input2), ptr(out), B, C, iH, iW, kH, kW, patchH, patchW,
+              padH, padW, dilationH, dilationW, dilation_patchH, dilation_patchW, dH, dW)
     return out
 
 
@@ -73,12 +69,8 @@ def backward(input1, input2, grad_output, kH, kW, patchH, patchW, padH, padW, di
                            f"{(B, patchH, patchW, oH, oW)}")
     g1 = torch.empty_like(input1)
     g2 = torch.empty_like(input2)
-    lib = _lib.load_library()
-    fn = getattr(lib, "rfn_corr_bwd_" + _suffix(input1))
-    with on_device(dev):
-        rc = fn(ptr(input1), ptr(input2), ptr(grad_output), ptr(g1), ptr(g2), B, C, iH, iW, kH, kW, patchH, patchW,
-                padH, padW, dilationH, dilationW, dilation_patchH, dilation_patchW, dH, dW, current_stream(dev))
-    _lib.check(rc, "correlation.backward")
+    _lib.call("rfn_corr_bwd_" + _suffix(input1), dev, ptr(input1), ptr(input2), ptr(grad_output), ptr(g1), ptr(g2), B, C, iH,
+              iW, kH, kW, patchH, patchW, padH, padW, dilationH, dilationW, dilation_patchH, dilation_patchW, dH, dW)
     return [g1, g2]
 
 
@@ -139,17 +131,13 @@ def local_correlation_layer(feature_source, feature_target, flow=None, single_ke
         from .matching import warp_nocheck
         feature_source, flow = warp_nocheck(feature_source, flow), None
     out = torch.empty((B, 81, H, W), dtype=torch.float32, device=dev)
-    lib = _lib.load_library()
     splits = _channel_splits(B, C, H, W) if flow is None else 1
-    with on_device(dev):
-        if splits > 1:
-            ws = _split_workspace(lib.rfn_local_corr_layer_split_workspace_bytes(B, H, W, splits), dev)
-            rc = lib.rfn_local_corr_layer_split_f32(ptr(feature_target), ptr(feature_source), ptr(out), ptr(ws), B, C, H, W,
-                                                    splits, current_stream(dev))
-        else:
-            rc = lib.rfn_local_corr_layer_f32(ptr(feature_target), ptr(feature_source), ptr(flow), ptr(out), B, C, H, W,
-                                              current_stream(dev))
-    _lib.check(rc, "local_correlation_layer")
+    if splits > 1:
+        ws = _split_workspace(_lib.load_library().rfn_local_corr_layer_split_workspace_bytes(B, H, W, splits), dev)
+        _lib.call("rfn_local_corr_layer_split_f32", dev, ptr(feature_target), ptr(feature_source), ptr(out), ptr(ws), B, C, H,
+                  W, splits)
+    else:
+        _lib.call("rfn_local_corr_layer_f32", dev, ptr(feature_target), ptr(feature_source), ptr(flow), ptr(out), B, C, H, W)
     return out
 
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, determinism
-from ._tensor import current_stream, on_device, ptr, upload_async
+from ._tensor import ptr, upload_async
 
 IMNET_MEAN = (0.485, 0.456, 0.406)
 IMNET_STD = (0.229, 0.224, 0.225)
@@ -95,20 +95,15 @@ def mix(images_src, images_trg, gt_src, pseudo_label, pseudo_weight, class_bits,
     mean3, std3 = (ctypes.c_float * 3)(*IMNET_MEAN), (ctypes.c_float * 3)(*IMNET_STD)
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
     optr = lambda t: None if t is None else ptr(t)  # noqa: E731
-    mix_jitter = lib.rfn_dacs_mix_jitter_det if det else lib.rfn_dacs_mix_jitter
-    with on_device(dev):
-        rc = mix_jitter(optr(src), optr(trg), ptr(gt), optr(ps), optr(pw), optr(img), optr(lbl), optr(wgt), ptr(ws), B, H, W,
-                        ptr(class_bits.contiguous()), cast(on), cast(order), cast(factor), cast(hue), cast(mean3), cast(std3),
-                        current_stream(dev))
-        _lib.check(rc, "dacs_mix_jitter")
-        if img is not None and any(s is not None for s in blur_sigma):
-            bon = (ctypes.c_int * B)(*[0 if s is None else 1 for s in blur_sigma])
-            sig = (ctypes.c_double * B)(*[1.0 if s is None else float(s) for s in blur_sigma])
-            tmp, out = torch.empty_like(img), torch.empty_like(img)
-            # kornia's window (dacs_transforms.py:68-72): ~0.1 x the extent, odd
-            ks = [int(np.floor(np.ceil(0.1 * d) - 0.5 + np.ceil(0.1 * d) % 2)) for d in (H, W)]
-            rc = lib.rfn_dacs_blur(ptr(img), ptr(tmp), ptr(out), B, 3, H, W, ks[0], ks[1], cast(bon), cast(sig), cast(sig),
-                                   current_stream(dev))
-            _lib.check(rc, "dacs_blur")
-            img = out
+    _lib.call("rfn_dacs_mix_jitter_det" if det else "rfn_dacs_mix_jitter", dev, optr(src), optr(trg), ptr(gt), optr(ps), optr(pw),
+              optr(img), optr(lbl), optr(wgt), ptr(ws), B, H, W, ptr(class_bits.contiguous()), cast(on), cast(order),
+              cast(factor), cast(hue), cast(mean3), cast(std3))
+    if img is not None and any(s is not None for s in blur_sigma):
+        bon = (ctypes.c_int * B)(*[0 if s is None else 1 for s in blur_sigma])
+        sig = (ctypes.c_double * B)(*[1.0 if s is None else float(s) for s in blur_sigma])
+        tmp, out = torch.empty_like(img), torch.empty_like(img)
+        # kornia's window (dacs_transforms.py:68-72): ~0.1 x the extent, odd
+        ks = [int(np.floor(np.ceil(0.1 * d) - 0.5 + np.ceil(0.1 * d) % 2)) for d in (H, W)]
+        _lib.call("rfn_dacs_blur", dev, ptr(img), ptr(tmp), ptr(out), B, 3, H, W, ks[0], ks[1], cast(bon), cast(sig), cast(sig))
+        img = out
     return img, lbl, wgt

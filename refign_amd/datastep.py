@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 
 IMNET_MEAN = (0.485, 0.456, 0.406)
 IMNET_STD = (0.229, 0.224, 0.225)
@@ -38,9 +38,7 @@ def device_label_hists(label_u8, boxes):
     H, W = label_u8.shape
     hist = torch.empty((K, 256), dtype=torch.int32, device=label_u8.device)
     arr = (np.asarray(boxes, dtype=np.int32).reshape(K, 4)).copy()
-    with on_device(label_u8.device):
-        rc = _lib.load_library().rfn_crop_label_hist_u8(ptr(label_u8), H, W, arr.ctypes.data, K, ptr(hist), current_stream(label_u8.device))
-    _lib.check(rc, "crop_label_hist_u8")
+    _lib.call("rfn_crop_label_hist_u8", label_u8.device, ptr(label_u8), H, W, arr.ctypes.data, K, ptr(hist))
     return hist.cpu().numpy().astype(np.int64)
 
 
@@ -69,11 +67,8 @@ def crop_flip_normalize(image_u8, label_u8, top, left, h, w, flip, out_image=Non
             raise RuntimeError("crop_flip_normalize: out_label must be a contiguous (h, w) int64 tensor")
     m = np.asarray(mean, dtype=np.float32).copy()
     s = np.asarray(std, dtype=np.float32).copy()
-    with on_device(ref.device):
-        rc = _lib.load_library().rfn_crop_flip_norm_u8(ptr(image_u8), ptr(label_u8), C, H, W, int(top), int(left), int(h), int(w),
-                                                       1 if flip else 0, m.ctypes.data, s.ctypes.data, ptr(out_image), ptr(out_label),
-                                                       current_stream(ref.device))
-    _lib.check(rc, "crop_flip_norm_u8")
+    _lib.call("rfn_crop_flip_norm_u8", ref.device, ptr(image_u8), ptr(label_u8), C, H, W, int(top), int(left), int(h), int(w),
+              1 if flip else 0, m.ctypes.data, s.ctypes.data, ptr(out_image), ptr(out_label))
     return out_image, out_label
 
 

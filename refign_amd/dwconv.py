@@ -10,10 +10,9 @@ import os
 import torch
 
 from . import _lib, determinism
-from ._tensor import current_stream, on_device, ptr, require_device_tensor, workspace
+from ._tensor import DTYPE_CODE, ptr, require_device_tensor, workspace
 from .params import as_dtype, derived, grad_sink
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _DW_WS_STRIPES = 128       # kMaxStripes in csrc/dwconv.hip (checked against the ABI in the GPU tests)
 
 
@@ -23,28 +22,22 @@ def _fwd(x, w_tap, bias, dilation, flip, stats=None):
     lib = _lib.load_library()
     if stats is not None and determinism.enabled():         # ... as per-block partial rows + an ordered column sum
         ws = workspace(lib.rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation), x.device)
-        with on_device(x.device):
-            rc = lib.rfn_dwconv3x3_nhwc_fwd_stats_det(ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), ptr(ws), B, H, W, C,
-                                                      dilation, _DT[x.dtype], current_stream(x.device))
-        _lib.check(rc, "dwconv3x3_nhwc_fwd_stats_det")
+        _lib.call("rfn_dwconv3x3_nhwc_fwd_stats_det", x.device, ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), ptr(ws), B,
+                  H, W, C, dilation, DTYPE_CODE[x.dtype])
         return y
     if stats is not None:                                   # + the BatchNorm statistics of the result (csrc/dwconv.hip STATS)
-        with on_device(x.device):
-            rc = lib.rfn_dwconv3x3_nhwc_fwd_stats(ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), B, H, W, C, dilation,
-                                                  _DT[x.dtype], current_stream(x.device))
-        _lib.check(rc, "dwconv3x3_nhwc_fwd_stats")
+        _lib.call("rfn_dwconv3x3_nhwc_fwd_stats", x.device, ptr(x), ptr(w_tap), ptr(bias), ptr(y), ptr(stats), B, H, W, C,
+                  dilation, DTYPE_CODE[x.dtype])
         return y
-    with on_device(x.device):
-        rc = lib.rfn_dwconv3x3_nhwc_fwd(ptr(x), ptr(w_tap), ptr(bias), ptr(y), B, H, W, C, dilation, _DT[x.dtype],
-                                        1 if flip else 0, current_stream(x.device))
-    _lib.check(rc, "dwconv3x3_nhwc_fwd")
+    _lib.call("rfn_dwconv3x3_nhwc_fwd", x.device, ptr(x), ptr(w_tap), ptr(bias), ptr(y), B, H, W, C, dilation, DTYPE_CODE[x.dtype],
+              1 if flip else 0)
     return y
 
 
 class _DWConv3x3(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, dilation, stats=None):
-        if x.dtype not in _DT:
+        if x.dtype not in DTYPE_CODE:
             x = x.float()
         x = require_device_tensor(x.contiguous(), "x")
         C = x.shape[-1]
@@ -70,7 +63,7 @@ class _DWConv3x3Gelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, with_z=False):
-        if x.dtype not in _DT:
+        if x.dtype not in DTYPE_CODE:
             x = x.float()
         x = require_device_tensor(x.contiguous(), "x")
         B, H, W, C = x.shape
@@ -82,11 +75,8 @@ class _DWConv3x3Gelu(torch.autograd.Function):
         ctx.set_materialize_grads(False)          # the non-differentiable output's "gradient" must not become a zero tensor
         z = torch.empty_like(x) if need else None
         a = torch.empty_like(x)
-        lib = _lib.load_library()
-        with on_device(x.device):
-            rc = lib.rfn_dwconv3x3_gelu_nhwc_fwd(ptr(x), ptr(w_tap), ptr(b32), ptr(z), ptr(a), B, H, W, C, _DT[x.dtype],
-                                                 current_stream(x.device))
-        _lib.check(rc, "dwconv3x3_gelu_nhwc_fwd")
+        _lib.call("rfn_dwconv3x3_gelu_nhwc_fwd", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(z), ptr(a), B, H, W, C,
+                  DTYPE_CODE[x.dtype])
         if need:
             ctx.save_for_backward(x, w_tap, z)
             ctx.has_bias, ctx.wshape, ctx.wdtype = bias is not None, weight.shape, weight.dtype
@@ -126,15 +116,11 @@ def _dwconv_backward(ctx, x, w_tap, gy):
         else:
             dw = torch.empty((9, C), dtype=torch.float32, device=x.device)
             db = torch.empty((C,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
-        lib = _lib.load_library()
 
         def run():
             ws = workspace(_DW_WS_STRIPES * 10 * C * 4, x.device)        # per stream: looked up on the stream it runs on
-            with on_device(x.device):
-                rc = lib.rfn_dwconv3x3_nhwc_bwd_weight(ptr(x), ptr(gy), ptr(dw), ptr(db), ptr(ws), B, H, W, C,
-                                                       ctx.dilation, _DT[x.dtype], 3 if direct else 0,
-                                                       current_stream(x.device))
-            _lib.check(rc, "dwconv3x3_nhwc_bwd_weight")
+            _lib.call("rfn_dwconv3x3_nhwc_bwd_weight", x.device, ptr(x), ptr(gy), ptr(dw), ptr(db), ptr(ws), B, H, W, C,
+                      ctx.dilation, DTYPE_CODE[x.dtype], 3 if direct else 0)
 
         run()
         if not direct:
@@ -171,11 +157,8 @@ def ffn_fc1_dw_gelu(x, fc1, dw, H, W):
     w_tap = derived(dw.weight, "tap_major_f32", lambda t: t.float().reshape(HID, 9).t().contiguous(), lambda t: t.reshape(HID, 9).t())
     bdw = as_dtype(dw.bias, torch.float32).detach().contiguous()
     a = torch.empty((B, N, HID), dtype=x.dtype, device=x.device)
-    fn = _lib.load_library().rfn_ffn_fc1_dw_gelu_f16 if x.dtype == torch.float16 else _lib.load_library().rfn_ffn_fc1_dw_gelu_bf16
-    with on_device(x.device):
-        rc = fn(ptr(x), ptr(w1), ptr(b1), ptr(w_tap), ptr(bdw), ptr(a), B, H, W, C, HID,
-                                                          current_stream(x.device))
-    _lib.check(rc, "ffn_fc1_dw_gelu")
+    _lib.call("rfn_ffn_fc1_dw_gelu_f16" if x.dtype == torch.float16 else "rfn_ffn_fc1_dw_gelu_bf16", x.device, ptr(x), ptr(w1),
+              ptr(b1), ptr(w_tap), ptr(bdw), ptr(a), B, H, W, C, HID)
     return a
 
 
@@ -206,25 +189,19 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     be = None if bn.bias is None else as_dtype(bn.bias, torch.float32).detach().contiguous()
     sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
     y = torch.empty_like(x)
-    lib = _lib.load_library()
     if determinism.enabled():
-        ws = workspace(lib.rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, int(dilation)), x.device)
-        with on_device(x.device):
-            rc = lib.rfn_dwconv3x3_nhwc_stats_det(ptr(x), ptr(w_tap), ptr(b32), ptr(sums), ptr(ws), B, H, W, C, int(dilation),
-                                                  _DT[x.dtype], current_stream(x.device))
+        ws = workspace(_lib.load_library().rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, int(dilation)), x.device)
+        _lib.call("rfn_dwconv3x3_nhwc_stats_det", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), ptr(ws), B, H, W, C,
+                  int(dilation), DTYPE_CODE[x.dtype])
     else:
-        with on_device(x.device):
-            rc = lib.rfn_dwconv3x3_nhwc_stats(ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, int(dilation), _DT[x.dtype],
-                                              current_stream(x.device))
-    _lib.check(rc, "dwconv3x3_nhwc_stats")
+        _lib.call("rfn_dwconv3x3_nhwc_stats", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, int(dilation),
+                  DTYPE_CODE[x.dtype])
     group = bnk.sync_group(bn)
     if group is not None:
         bnk._all_reduce(sums, group, bnk._exchange_comm(bn))
-    with on_device(x.device):
-        rc = lib.rfn_dwconv3x3_bn_act_nhwc_fwd(ptr(x), ptr(w_tap), ptr(b32), ptr(g), ptr(be), ptr(sums), ptr(bn.running_mean),
-                                               ptr(bn.running_var), ptr(y), B, H, W, C, int(dilation), float(bn.eps),
-                                               float(bn.momentum), 1 if relu else 0, _DT[x.dtype], current_stream(x.device))
-    _lib.check(rc, "dwconv3x3_bn_act_nhwc_fwd")
+    _lib.call("rfn_dwconv3x3_bn_act_nhwc_fwd", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(g), ptr(be), ptr(sums),
+              ptr(bn.running_mean), ptr(bn.running_var), ptr(y), B, H, W, C, int(dilation), float(bn.eps), float(bn.momentum),
+              1 if relu else 0, DTYPE_CODE[x.dtype])
     bn.num_batches_tracked.add_(1)
     return y
 
@@ -258,10 +235,8 @@ def dwconv3x3_bn_act_nhwc_tri(x, convs, bns, relu):
                               lambda t: t.reshape(C, 9).t()) for c in convs]).contiguous()
     b3 = None if convs[0].bias is None else torch.stack([as_dtype(c.bias, torch.float32).detach() for c in convs]).contiguous()
     sums = torch.empty((3, 2 * C + 1), dtype=torch.float64, device=x.device)
-    lib, f16 = _lib.load_library(), x.dtype == torch.float16
-    with on_device(x.device):
-        rc = (lib.rfn_dwconv3x3_tri_stats_f16 if f16 else lib.rfn_dwconv3x3_tri_stats)(ptr(x), ptr(w3), ptr(b3), ptr(sums), B, H, W, C, int(g), current_stream(x.device))
-    _lib.check(rc, "dwconv3x3_tri_stats")
+    f16 = "_f16" if x.dtype == torch.float16 else ""
+    _lib.call("rfn_dwconv3x3_tri_stats" + f16, x.device, ptr(x), ptr(w3), ptr(b3), ptr(sums), B, H, W, C, int(g))
     for k, bn in enumerate(bns):
         group = bnk.sync_group(bn)
         if group is not None:
@@ -281,10 +256,8 @@ def dwconv3x3_bn_act_nhwc_tri(x, convs, bns, relu):
     yp = arr(ys)
     eps = (ctypes.c_float * 3)(*[float(b.eps) for b in bns])
     mom = (ctypes.c_float * 3)(*[float(b.momentum) for b in bns])
-    with on_device(x.device):
-        rc = (lib.rfn_dwconv3x3_tri_bn_act_fwd_f16 if f16 else lib.rfn_dwconv3x3_tri_bn_act_fwd)(ptr(x), ptr(w3), ptr(b3), ga, be, ptr(sums), rm, rv, yp, B, H, W, C, int(g), eps, mom,
-                                              1 if relu else 0, current_stream(x.device))
-    _lib.check(rc, "dwconv3x3_tri_bn_act_fwd")
+    _lib.call("rfn_dwconv3x3_tri_bn_act_fwd" + f16, x.device, ptr(x), ptr(w3), ptr(b3), ga, be, ptr(sums), rm, rv, yp, B, H, W, C,
+              int(g), eps, mom, 1 if relu else 0)
     for b in bns:
         b.num_batches_tracked.add_(1)
     return ys

@@ -16,9 +16,8 @@ import os
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import DTYPE_CODE, ptr
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 MAX_CLASSES = 32
 _BOXES = {}
 
@@ -43,7 +42,7 @@ def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255
     `target` (B, H, W) int64 are ADDED to it.  Nothing here waits for the device."""
     if not crop_logits.is_cuda:
         raise RuntimeError("evaltail: crop_logits must be a HIP (cuda:N) tensor: refign_amd has no CPU path")
-    if crop_logits.dtype not in _DT or crop_logits.dim() != 4:
+    if crop_logits.dtype not in DTYPE_CODE or crop_logits.dim() != 4:
         raise RuntimeError(f"evaltail: crop_logits (N, C, h, w) in fp32 / bf16 / fp16 expected, got "
                            f"{tuple(crop_logits.shape)} {crop_logits.dtype}")
     nbox = len(boxes)
@@ -62,11 +61,8 @@ def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255
                                 or not confmat.is_contiguous()):
         raise RuntimeError(f"evaltail: confmat ({C}, {C}) int64 contiguous on {dev} expected")
     labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_labels else None
-    with on_device(dev):
-        rc = _lib.load_library().rfn_slide_argmax_confmat(ptr(lg), _DT[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
-                                                          ptr(target), int(ignore_index), ptr(labels), ptr(confmat),
-                                                          current_stream(dev))
-    _lib.check(rc, "slide_argmax_confmat")
+    _lib.call("rfn_slide_argmax_confmat", dev, ptr(lg), DTYPE_CODE[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
+              ptr(target), int(ignore_index), ptr(labels), ptr(confmat))
     return labels
 
 

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, params
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 
 ACT_Q = 8.0                 # stored byte = e4m3(value * ACT_Q): |value| < 56 in range, subnormal below 2e-3
 _ACTIVE = [False]
@@ -49,9 +49,7 @@ def quantize(x, q=ACT_Q):
     """bf16 tensor -> e4m3 bytes of x * q (saturating, round to nearest even)."""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() % 4 == 0
     y = _u8(x.shape, x.device)
-    with on_device(x.device):
-        rc = _lib.load_library().rfn_quant_f8(ptr(x), ptr(y), x.numel(), float(q), current_stream(x.device))
-    _lib.check(rc, "quant_f8")
+    _lib.call("rfn_quant_f8", x.device, ptr(x), ptr(y), x.numel(), float(q))
     return y
 
 
@@ -96,9 +94,7 @@ def _rows(ent):
 
 
 def _launch(table, n, dev):
-    with on_device(dev):
-        rc = _lib.load_library().rfn_quant_rows_f8(ptr(table), n, current_stream(dev))
-    _lib.check(rc, "quant_rows_f8")
+    _lib.call("rfn_quant_rows_f8", dev, ptr(table), n)
 
 
 def _quantize_entries(ents):
@@ -153,11 +149,9 @@ def gemm_nt(x8, w8, ws, bias=None, res=None, rowscale=None, rows_per_sample=0, a
         assert not out_f8 and res.dtype == torch.bfloat16 and res.shape == y.shape and res.is_contiguous()
     if bias is not None:
         assert bias.dtype == torch.bfloat16 and bias.is_contiguous() and bias.numel() == N
-    with on_device(dev):
-        rc = _lib.load_library().rfn_gemm_nt_f8(ptr(x8), ptr(w8), ptr(ws), float(x_scale), ptr(bias), ptr(res), ptr(rowscale),
-                                                int(rows_per_sample), int(act), ptr(y), 1 if out_f8 else 0, float(out_q),
-                                                M, N, K, x8.stride(0), w8.stride(0), y.stride(0), current_stream(dev))
-    _lib.check(rc, "gemm_nt_f8")
+    _lib.call("rfn_gemm_nt_f8", dev, ptr(x8), ptr(w8), ptr(ws), float(x_scale), ptr(bias), ptr(res), ptr(rowscale),
+              int(rows_per_sample), int(act), ptr(y), 1 if out_f8 else 0, float(out_q), M, N, K, x8.stride(0), w8.stride(0),
+              y.stride(0))
     return y
 
 
@@ -168,10 +162,8 @@ def layernorm(x, ln, out_q=ACT_Q):
     y = _u8(x.shape, x.device)
     w32 = params.as_dtype(ln.weight, torch.float32).detach()
     b32 = params.as_dtype(ln.bias, torch.float32).detach()
-    with on_device(x.device):
-        rc = _lib.load_library().rfn_layernorm_fwd_f8(ptr(x), ptr(w32), ptr(b32), ptr(y), x.numel() // C, C, float(ln.eps),
-                                                      float(out_q), current_stream(x.device))
-    _lib.check(rc, "layernorm_fwd_f8")
+    _lib.call("rfn_layernorm_fwd_f8", x.device, ptr(x), ptr(w32), ptr(b32), ptr(y), x.numel() // C, C, float(ln.eps),
+              float(out_q))
     return y
 
 
@@ -182,10 +174,8 @@ def dwconv_gelu(h8, dw, B, H, W, x_scale=1.0 / ACT_Q, out_q=ACT_Q):
                            lambda t: t.reshape(C, 9).t())
     b32 = None if dw.bias is None else params.as_dtype(dw.bias, torch.float32).detach()
     y = _u8(h8.shape, h8.device)
-    with on_device(h8.device):
-        rc = _lib.load_library().rfn_dwconv3x3_gelu_nhwc_fwd_f8(ptr(h8), ptr(w_tap), ptr(b32), ptr(y), B, H, W, C,
-                                                                float(x_scale), float(out_q), current_stream(h8.device))
-    _lib.check(rc, "dwconv3x3_gelu_nhwc_fwd_f8")
+    _lib.call("rfn_dwconv3x3_gelu_nhwc_fwd_f8", h8.device, ptr(h8), ptr(w_tap), ptr(b32), ptr(y), B, H, W, C, float(x_scale),
+              float(out_q))
     return y
 
 
@@ -198,14 +188,9 @@ def attention(q8, kv8, heads, scale, q_scale=1.0 / ACT_Q, kv_scale=1.0 / ACT_Q, 
     nst = -(-Nkv // 64)
     pack = _u8(B * heads * nst * 8192, dev)
     o8 = _u8(q8.shape, dev)
-    lib = _lib.load_library()
-    with on_device(dev):
-        rc = lib.rfn_attn_pack_f8(ptr(kv8), kv8.stride(0), kv8.stride(1), B, heads, Nkv, nst, ptr(pack), current_stream(dev))
-        _lib.check(rc, "attn_pack_f8")
-        rc = lib.rfn_attn_fwd_f8(ptr(q8), q8.stride(0), q8.stride(1), ptr(pack), ptr(o8), o8.stride(0), o8.stride(1), B,
-                                 heads, N, Nkv, nst, float(scale), float(q_scale), float(kv_scale), float(kv_scale),
-                                 float(out_q), current_stream(dev))
-    _lib.check(rc, "attn_fwd_f8")
+    _lib.call("rfn_attn_pack_f8", dev, ptr(kv8), kv8.stride(0), kv8.stride(1), B, heads, Nkv, nst, ptr(pack))
+    _lib.call("rfn_attn_fwd_f8", dev, ptr(q8), q8.stride(0), q8.stride(1), ptr(pack), ptr(o8), o8.stride(0), o8.stride(1), B, heads,
+              N, Nkv, nst, float(scale), float(q_scale), float(kv_scale), float(kv_scale), float(out_q))
     return o8
 
 
@@ -213,9 +198,7 @@ def _patchify8(x8, B, H, W, C, r):
     """(B, H*W, C) e4m3 tokens -> (B*(H/r)*(W/r), r*r*C) patches: the byte mover of the 16-bit path on C/2 "elements"."""
     Hr, Wr = H // r, W // r
     out = _u8((B * Hr * Wr, r * r * C), x8.device)
-    with on_device(x8.device):
-        rc = _lib.load_library().rfn_patchify_tokens(ptr(x8), ptr(out), B, H, W, C // 2, r, 1, 0, current_stream(x8.device))
-    _lib.check(rc, "patchify_tokens")
+    _lib.call("rfn_patchify_tokens", x8.device, ptr(x8), ptr(out), B, H, W, C // 2, r, 1, 0)
     return out, Hr, Wr
 
 

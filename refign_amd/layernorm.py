@@ -10,10 +10,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr, workspace
+from ._tensor import DTYPE_CODE, ptr, workspace
 from .params import as_dtype, grad_sink
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 _LN_WS_ROWS = 256          # kLnMaxBlocks in csrc/layernorm.hip (checked against the ABI in the GPU tests)
 
 
@@ -28,11 +27,8 @@ class _LayerNormFn(torch.autograd.Function):
         y = torch.empty((rows, C), dtype=out_dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-        lib = _lib.load_library()
-        with on_device(x.device):
-            rc = lib.rfn_layernorm_fwd(ptr(x2), ptr(w32), ptr(b32), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps),
-                                       _DT[x2.dtype], _DT[out_dtype], current_stream(x.device))
-        _lib.check(rc, "layernorm_fwd")
+        _lib.call("rfn_layernorm_fwd", x.device, ptr(x2), ptr(w32), ptr(b32), ptr(y), ptr(mean), ptr(rstd), rows, C, float(eps),
+                  DTYPE_CODE[x2.dtype], DTYPE_CODE[out_dtype])
         ctx.save_for_backward(x2, w32, mean, rstd)
         ctx.shape, ctx.wdtype = x.shape, weight.dtype
         ctx.weight, ctx.bias = weight, bias
@@ -50,7 +46,7 @@ def _ln_backward(ctx, gy, add, gy_b=None):
             gy, gy_b = gy_b, None
         if gy is None:                                     # only the pass-through output was used
             return (add, None, None, None, None)
-        if gy.dtype not in _DT:
+        if gy.dtype not in DTYPE_CODE:
             gy = gy.float()
         gy2 = gy.contiguous().view(rows, C)
         if gy_b is not None:                               # a second consumer of the LayerNorm output (layer_norm_pass2)
@@ -66,24 +62,17 @@ def _ln_backward(ctx, gy, add, gy_b=None):
         direct = sg is not None and sb is not None
         dg = sg if direct else torch.empty(C, dtype=torch.float32, device=x2.device)
         db = sb if direct else torch.empty(C, dtype=torch.float32, device=x2.device)
-        lib = _lib.load_library()
         ws = workspace(_LN_WS_ROWS * 2 * C * 4, x2.device)     # == rfn_layernorm_bwd_workspace_bytes(C)
-        with on_device(x2.device):
-            if gy_b is not None:
-                rc = lib.rfn_layernorm_bwd_add2(ptr(x2), ptr(gy2), ptr(gy_b), ptr(add) if add is not None else None, ptr(w32),
-                                                ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db), ptr(ws), rows, C, _DT[x2.dtype],
-                                                _DT[gy2.dtype], 1 if direct else 0, current_stream(x2.device))
-                add = None
-            elif add is not None and C % 8 == 0:
-                rc = lib.rfn_layernorm_bwd_add(ptr(x2), ptr(gy2), ptr(add), ptr(w32), ptr(mean), ptr(rstd), ptr(dx), ptr(dg),
-                                               ptr(db), ptr(ws), rows, C, _DT[x2.dtype], _DT[gy2.dtype], 1 if direct else 0,
-                                               current_stream(x2.device))
-                add = None
-            else:
-                rc = lib.rfn_layernorm_bwd(ptr(x2), ptr(gy2), ptr(w32), ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db),
-                                           ptr(ws), rows, C, _DT[x2.dtype], _DT[gy2.dtype], 1 if direct else 0,
-                                           current_stream(x2.device))
-        _lib.check(rc, "layernorm_bwd")
+        tail = (ptr(w32), ptr(mean), ptr(rstd), ptr(dx), ptr(dg), ptr(db), ptr(ws), rows, C, DTYPE_CODE[x2.dtype],
+                DTYPE_CODE[gy2.dtype], 1 if direct else 0)
+        if gy_b is not None:
+            _lib.call("rfn_layernorm_bwd_add2", x2.device, ptr(x2), ptr(gy2), ptr(gy_b), ptr(add), *tail)
+            add = None
+        elif add is not None and C % 8 == 0:
+            _lib.call("rfn_layernorm_bwd_add", x2.device, ptr(x2), ptr(gy2), ptr(add), *tail)
+            add = None
+        else:
+            _lib.call("rfn_layernorm_bwd", x2.device, ptr(x2), ptr(gy2), *tail)
         if add is not None:
             dx = dx + add
         if direct:
@@ -124,7 +113,7 @@ class _LayerNormPass2Fn(torch.autograd.Function):
 def layer_norm_pass2(x, weight, bias, eps=1e-5):
     """-> (LayerNorm(x), LayerNorm(x), x): two handles on the output for two consumers, and the residual pass-through."""
     out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-    if out_dtype not in _DT:
+    if out_dtype not in DTYPE_CODE:
         out_dtype = x.dtype
     return _LayerNormPass2Fn.apply(x, weight, bias, eps, out_dtype)
 
@@ -132,17 +121,17 @@ def layer_norm_pass2(x, weight, bias, eps=1e-5):
 def layer_norm_pass(x, weight, bias, eps=1e-5):
     """-> (LayerNorm(x), x) with the residual gradient folded into the LayerNorm backward (HIP tensors, C % 8 == 0)."""
     out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-    if out_dtype not in _DT:
+    if out_dtype not in DTYPE_CODE:
         out_dtype = x.dtype
     return _LayerNormPassFn.apply(x, weight, bias, eps, out_dtype)
 
 
 def layer_norm(x, weight, bias, eps=1e-5, out_dtype=None):
-    if x.dtype not in _DT:
+    if x.dtype not in DTYPE_CODE:
         x = x.float()
     if out_dtype is None:
         out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
-        if out_dtype not in _DT:
+        if out_dtype not in DTYPE_CODE:
             out_dtype = x.dtype
     return _LayerNormFn.apply(x, weight, bias, eps, out_dtype)
 

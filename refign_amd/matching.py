@@ -5,7 +5,7 @@ import os
 import torch
 
 from . import _lib
-from ._tensor import current_stream, ptr, require_device_tensor, same_device, on_device
+from ._tensor import DTYPE_CODE16, ptr, require_device_tensor, same_device
 
 
 def warp(x, flo, padding_mode='zeros', return_mask=False):
@@ -49,10 +49,7 @@ class _WarpFn(torch.autograd.Function):
         B, C, H, W = x.shape
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gf = torch.empty_like(flo) if ctx.needs_input_grad[1] else None
-        lib = _lib.load_library()
-        with on_device(x.device):
-            rc = lib.rfn_warp_bwd_f32(ptr(x), ptr(flo), ptr(g), ptr(gx), ptr(gf), B, C, H, W, current_stream(x.device))
-        _lib.check(rc, "warp backward")
+        _lib.call("rfn_warp_bwd_f32", x.device, ptr(x), ptr(flo), ptr(g), ptr(gx), ptr(gf), B, C, H, W)
         return gx, gf
 
 
@@ -62,38 +59,27 @@ def warp_nocheck(x, flo, return_mask=False):
     B, C, H, W = x.shape
     out = torch.empty_like(x)
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_mask else None
-    lib = _lib.load_library()
-    with on_device(dev):
-        rc = lib.rfn_warp_f32(ptr(x), ptr(flo), ptr(out), ptr(mask), B, C, H, W, current_stream(dev))
-    _lib.check(rc, "warp")
+    _lib.call("rfn_warp_f32", dev, ptr(x), ptr(flo), ptr(out), ptr(mask), B, C, H, W)
     if return_mask:
         return out, mask.view(torch.bool)
     return out
-
-
-_DT16 = {torch.bfloat16: 1, torch.float16: 2}
 
 
 def l2_normalize_channels(x):
     """F.normalize(x.float(), p=2, dim=1) for (B, C, H, W) features (uawarpc.py:101-108) -> NCHW float32.  Channels-last
     16-bit features (what the matcher's convolutions deliver under the AMP recipe) are widened, re-laid out and
     normalised in one kernel; anything else is made NCHW float32 first."""
-    lib = _lib.load_library()
-    if x.is_cuda and x.dim() == 4 and x.dtype in _DT16 and x.shape[1] % 8 == 0 and x.shape[1] <= 2048 and \
+    if x.is_cuda and x.dim() == 4 and x.dtype in DTYPE_CODE16 and x.shape[1] % 8 == 0 and x.shape[1] <= 2048 and \
             x.is_contiguous(memory_format=torch.channels_last):
         B, C, H, W = x.shape
         out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
-        with on_device(x.device):
-            rc = lib.rfn_l2norm_channels_nhwc16_f32(ptr(x), ptr(out), B, C, H * W, _DT16[x.dtype], current_stream(x.device))
-        _lib.check(rc, "l2_normalize_channels (channels-last 16-bit)")
+        _lib.call("rfn_l2norm_channels_nhwc16_f32", x.device, ptr(x), ptr(out), B, C, H * W, DTYPE_CODE16[x.dtype])
         return out
     x = require_device_tensor(x.float().contiguous(), "x", torch.float32)
     B, C = x.shape[:2]
     hw = x[0, 0].numel()
     out = torch.empty_like(x)
-    with on_device(x.device):
-        rc = lib.rfn_l2norm_channels_f32(ptr(x), ptr(out), B, C, hw, current_stream(x.device))
-    _lib.check(rc, "l2_normalize_channels")
+    _lib.call("rfn_l2norm_channels_f32", x.device, ptr(x), ptr(out), B, C, hw)
     return out
 
 
@@ -110,11 +96,9 @@ def uncertainty9_frontend(corr, packed_weights, half_matrix=False):
                            % lib.rfn_uncertainty9_weights_len())
     same_device(corr, w)
     out = torch.empty((B, 6, H, W), dtype=torch.float32, device=corr.device)
-    with on_device(corr.device):
-        # half_matrix: the 32 -> 32 and 32 -> 16 layers on the f16 matrix pipe (the reference's AMP precision for these convolutions)
-        fn = lib.rfn_uncertainty9_frontend_f16mm if half_matrix else lib.rfn_uncertainty9_frontend_f32
-        rc = fn(ptr(corr), ptr(w), ptr(out), B, H, W, current_stream(corr.device))
-    _lib.check(rc, "uncertainty9_frontend")
+    # half_matrix: the 32 -> 32 and 32 -> 16 layers on the f16 matrix pipe (the reference's AMP precision for these convolutions)
+    _lib.call("rfn_uncertainty9_frontend_f16mm" if half_matrix else "rfn_uncertainty9_frontend_f32", corr.device, ptr(corr),
+              ptr(w), ptr(out), B, H, W)
     return out
 
 
@@ -128,10 +112,7 @@ class _RetileFn(torch.autograd.Function):
         ctx.geom = (B, h, w, k, C)
         es = y.element_size()
         out = torch.empty((B, k * h, k * w, C), dtype=y.dtype, device=y.device)
-        with on_device(y.device):
-            rc = _lib.load_library().rfn_retile_copy(ptr(y), ptr(out), B, h, w, k, C * es // 16, y.stride(3) * es // 16, 0,
-                                                     current_stream(y.device))
-        _lib.check(rc, "retile_copy")
+        _lib.call("rfn_retile_copy", y.device, ptr(y), ptr(out), B, h, w, k, C * es // 16, y.stride(3) * es // 16, 0)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -141,9 +122,7 @@ class _RetileFn(torch.autograd.Function):
         gh = go.permute(0, 2, 3, 1).contiguous()
         u = C * gh.element_size() // 16
         gy = torch.empty((B, (k + 2) * h - 2, (k + 2) * w - 2, C), dtype=gh.dtype, device=gh.device)
-        with on_device(gh.device):
-            rc = _lib.load_library().rfn_retile_copy(ptr(gh), ptr(gy), B, h, w, k, u, u, 1, current_stream(gh.device))
-        _lib.check(rc, "retile_copy (backward)")
+        _lib.call("rfn_retile_copy", gh.device, ptr(gh), ptr(gy), B, h, w, k, u, u, 1)
         return gy.permute(0, 3, 1, 2), None, None, None
 
 
@@ -167,10 +146,7 @@ def area_resize(x, size):
     x = require_device_tensor(x.float().contiguous(), "x", torch.float32)
     B, C, H, W = x.shape
     out = torch.empty((B, C, size[0], size[1]), dtype=torch.float32, device=x.device)
-    lib = _lib.load_library()
-    with on_device(x.device):
-        rc = lib.rfn_area_resize_f32(ptr(x), ptr(out), B * C, H, W, size[0], size[1], current_stream(x.device))
-    _lib.check(rc, "area_resize")
+    _lib.call("rfn_area_resize_f32", x.device, ptr(x), ptr(out), B * C, H, W, size[0], size[1])
     return out
 
 
@@ -234,11 +210,8 @@ def align_tail(logits_ref, flow_q, logvar_q, return_flow=False):
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     cert = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
     flow_up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_flow else None
-    lib = _lib.load_library()
-    with on_device(dev):
-        rc = lib.rfn_align_tail_f32(ptr(logits_ref), ptr(flow_q), ptr(logvar_q), ptr(warped), ptr(mask), ptr(cert),
-                                    ptr(flow_up), B, C, H, W, h, w, current_stream(dev))
-    _lib.check(rc, "align_tail")
+    _lib.call("rfn_align_tail_f32", dev, ptr(logits_ref), ptr(flow_q), ptr(logvar_q), ptr(warped), ptr(mask), ptr(cert),
+              ptr(flow_up), B, C, H, W, h, w)
     if return_flow:
         return warped, mask.view(torch.bool), cert, flow_up
     return warped, mask.view(torch.bool), cert

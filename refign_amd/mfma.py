@@ -13,9 +13,9 @@ import os
 import torch
 
 from . import _lib, determinism
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
+from ._tensor import DTYPE_CODE16 as _DT16          # (the name the GPU tests read the codes under)
 
-_DT16 = {torch.bfloat16: 1, torch.float16: 2}
 ENABLED = True            # (module switch for tests: False = library GEMM / SDPA everywhere)
 
 # Every dense op of a HIP tensor that ends up in a ROCm LIBRARY (hipBLASLt / MIOpen / fused SDPA behind F.linear, torch.mm,
@@ -72,12 +72,8 @@ def gemm_nt(x, w, bias=None, res=None, rowscale=None, rows_per_sample=0, act=0, 
         return None
     if rowscale is not None and (rows_per_sample <= 0 or rowscale.dtype != torch.float32 or not rowscale.is_contiguous()):
         return None
-    lib = _lib.load_library()
-    with on_device(x.device):
-        rc = lib.rfn_gemm_nt(ptr(x), ptr(w), ptr(bias), ptr(res), ptr(rowscale), int(rows_per_sample), int(act),
-                             ptr(out), M, N, K, x.stride(0), w.stride(0), out.stride(0), _DT16[x.dtype],
-                             current_stream(x.device))
-    _lib.check(rc, "gemm_nt")
+    _lib.call("rfn_gemm_nt", x.device, ptr(x), ptr(w), ptr(bias), ptr(res), ptr(rowscale), int(rows_per_sample), int(act),
+              ptr(out), M, N, K, x.stride(0), w.stride(0), out.stride(0), _DT16[x.dtype])
     return out
 
 
@@ -117,11 +113,8 @@ def conv2d_nhwc(x, wp, bias, KH, KW, stride=1, pad=0, dil=1, act=0, res=None, ou
         return None
     if bias is not None and not (bias.dtype == x.dtype and bias.is_contiguous() and bias.numel() == N):
         return None
-    lib = _lib.load_library()
-    with on_device(x.device):
-        rc = lib.rfn_conv2d_nhwc(ptr(x), ptr(wp), ptr(bias), ptr(res), int(act), ptr(out), B, H, W, C, N, KH, KW, stride,
-                                 pad, dil, wp.stride(0), out.stride(2), _DT16[x.dtype], current_stream(x.device))
-    _lib.check(rc, "conv2d_nhwc")
+    _lib.call("rfn_conv2d_nhwc", x.device, ptr(x), ptr(wp), ptr(bias), ptr(res), int(act), ptr(out), B, H, W, C, N, KH, KW,
+              stride, pad, dil, wp.stride(0), out.stride(2), _DT16[x.dtype])
     return out
 
 
@@ -137,10 +130,8 @@ def conv2d_nhwc_dgrad(gy, wt, H, W, C, KH, KW, stride=1, pad=0, dil=1):
     if (OH, OW) != ((H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1):
         return None
     dx = torch.empty((B, H, W, C), dtype=gy.dtype, device=gy.device)
-    with on_device(gy.device):
-        rc = _lib.load_library().rfn_conv2d_nhwc_dgrad(ptr(gy), ptr(wt), ptr(dx), B, H, W, C, N, KH, KW, stride, pad, dil,
-                                                       wt.stride(0), C, _DT16[gy.dtype], current_stream(gy.device))
-    _lib.check(rc, "conv2d_nhwc_dgrad")
+    _lib.call("rfn_conv2d_nhwc_dgrad", gy.device, ptr(gy), ptr(wt), ptr(dx), B, H, W, C, N, KH, KW, stride, pad, dil,
+              wt.stride(0), C, _DT16[gy.dtype])
     return dx
 
 
@@ -164,11 +155,8 @@ def conv2d_nhwc_wgrad(gy, x, KH, KW, Kpad, stride=1, pad=0, dil=1, bias_out=None
     part = torch.empty((S, N, Kpad), dtype=torch.float32, device=gy.device)
     det = determinism.enabled() and bias_out is not None      # per-slab bias sums, added in slab order (else: fp32 atomics)
     bpart = torch.empty((S, N), dtype=torch.float32, device=gy.device) if det else bias_out
-    with on_device(gy.device):
-        rc = _lib.load_library().rfn_conv2d_nhwc_wgrad(ptr(gy), ptr(x), ptr(part), ptr(bpart), B, H, W, C, N, KH, KW, stride,
-                                                       pad, dil, N, Kpad, rows, 2 if det else 0, _DT16[gy.dtype],
-                                                       current_stream(gy.device))
-    _lib.check(rc, "conv2d_nhwc_wgrad")
+    _lib.call("rfn_conv2d_nhwc_wgrad", gy.device, ptr(gy), ptr(x), ptr(part), ptr(bpart), B, H, W, C, N, KH, KW, stride, pad,
+              dil, N, Kpad, rows, 2 if det else 0, _DT16[gy.dtype])
     if det:
         from .params import sum_rows
         sum_rows(bpart, out=bias_out.view(-1), accumulate=True)
@@ -196,6 +184,21 @@ def slab_rows(T, tiles, nk=0):
     return rows
 
 
+def _tn_domain(g, x, rowscale, rows_per_sample):
+    if not (ENABLED and g.is_cuda and g.dtype in _DT16 and x.dtype == g.dtype and g.dim() == 2 and x.dim() == 2
+            and g.stride(1) == 1 and x.stride(1) == 1 and g.stride(0) % 2 == 0 and x.stride(0) % 2 == 0
+            and g.data_ptr() % 4 == 0 and x.data_ptr() % 4 == 0):
+        return False
+    T, N = g.shape
+    K = x.shape[1]
+    if x.shape[0] != T or N % 64 != 0 or K % 64 != 0 or T == 0:
+        return False
+    if rowscale is not None and not (rowscale.dtype == torch.float32 and rowscale.is_contiguous() and rows_per_sample > 0
+                                     and rowscale.numel() * rows_per_sample >= T):
+        return False
+    return True
+
+
 def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, rows_per_sample=0):
     """(diag(rowscale) g[T,N])^T @ x[T,K] with the token dimension split into slabs (`rowscale`: fp32, one value per
     `rows_per_sample` consecutive rows -- the stochastic-depth scale of the branch the gradient g belongs to).  `out` None: returns the fp32 partials (S, N, K)
@@ -203,17 +206,10 @@ def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, ro
     parameter's view of the flat gradient buffer) and `bias_out` (N,) fp32, if given, += the column sums of g -- in
     deterministic mode (refign_amd/determinism.py) the slabs are stored and added in slab order instead (_gemm_tn_det).
     None if outside the kernel's domain."""
-    if not (ENABLED and g.is_cuda and g.dtype in _DT16 and x.dtype == g.dtype and g.dim() == 2 and x.dim() == 2
-            and g.stride(1) == 1 and x.stride(1) == 1 and g.stride(0) % 2 == 0 and x.stride(0) % 2 == 0
-            and g.data_ptr() % 4 == 0 and x.data_ptr() % 4 == 0):
+    if not _tn_domain(g, x, rowscale, rows_per_sample):
         return None
     T, N = g.shape
     K = x.shape[1]
-    if x.shape[0] != T or N % 64 != 0 or K % 64 != 0 or T == 0:
-        return None
-    if rowscale is not None and not (rowscale.dtype == torch.float32 and rowscale.is_contiguous() and rows_per_sample > 0
-                                     and rowscale.numel() * rows_per_sample >= T):
-        return None
     if rows_per_slab is None:
         tile = 128 if (N % 128 == 0 and K % 128 == 0) else 64
         rows_per_slab = slab_rows(T, (N // tile) * (K // tile), N * K)
@@ -228,12 +224,9 @@ def gemm_tn(g, x, rows_per_slab=None, out=None, bias_out=None, rowscale=None, ro
         part = out
     else:
         part = torch.empty((S, N, K), dtype=torch.float32, device=g.device)
-    lib = _lib.load_library()
-    with on_device(g.device):
-        rc = lib.rfn_gemm_tn(ptr(g), ptr(x), ptr(part), T, N, K, g.stride(0), x.stride(0), int(rows_per_slab),
-                             0 if out is None else 1, ptr(bias_out) if out is not None else None, ptr(rowscale),
-                             int(rows_per_sample), _DT16[g.dtype], current_stream(g.device))
-    _lib.check(rc, "gemm_tn")
+    _lib.call("rfn_gemm_tn", g.device, ptr(g), ptr(x), ptr(part), T, N, K, g.stride(0), x.stride(0), int(rows_per_slab),
+              0 if out is None else 1, ptr(bias_out) if out is not None else None, ptr(rowscale), int(rows_per_sample),
+              _DT16[g.dtype])
     return part
 
 
@@ -247,11 +240,8 @@ def _gemm_tn_det(g, x, rows_per_slab, S, out, bias_out, rowscale, rows_per_sampl
     K = x.shape[1]
     part = torch.empty((S, N * K), dtype=torch.float32, device=g.device)
     bpart = torch.empty((S, N), dtype=torch.float32, device=g.device) if bias_out is not None else None
-    with on_device(g.device):
-        rc = _lib.load_library().rfn_gemm_tn(ptr(g), ptr(x), ptr(part), T, N, K, g.stride(0), x.stride(0), rows_per_slab, 2,
-                                             ptr(bpart), ptr(rowscale), int(rows_per_sample), _DT16[g.dtype],
-                                             current_stream(g.device))
-    _lib.check(rc, "gemm_tn (deterministic form)")
+    _lib.call("rfn_gemm_tn", g.device, ptr(g), ptr(x), ptr(part), T, N, K, g.stride(0), x.stride(0), rows_per_slab, 2,
+              ptr(bpart), ptr(rowscale), int(rows_per_sample), _DT16[g.dtype])
     sum_rows(part, out=out.view(-1), accumulate=True)
     if bpart is not None:
         sum_rows(bpart, out=bias_out.view(-1), accumulate=True)
@@ -269,21 +259,6 @@ def _gemm_tn_det(g, x, rows_per_slab, S, out, bias_out, rowscale, rows_per_sampl
 GROUP_WGRADS = True           # (module switch: tests compare the grouped step with the one-launch-per-gradient step)
 _TN_GROUP_MAX = 8
 _WGRAD_QUEUE = None          # None: not deferring; else a list of (g, x, out, bias_out, rowscale, rows_per_sample, rows_per_slab)
-
-
-def _tn_domain(g, x, rowscale, rows_per_sample):
-    if not (ENABLED and g.is_cuda and g.dtype in _DT16 and x.dtype == g.dtype and g.dim() == 2 and x.dim() == 2
-            and g.stride(1) == 1 and x.stride(1) == 1 and g.stride(0) % 2 == 0 and x.stride(0) % 2 == 0
-            and g.data_ptr() % 4 == 0 and x.data_ptr() % 4 == 0):
-        return False
-    T, N = g.shape
-    K = x.shape[1]
-    if x.shape[0] != T or N % 64 != 0 or K % 64 != 0 or T == 0:
-        return False
-    if rowscale is not None and not (rowscale.dtype == torch.float32 and rowscale.is_contiguous() and rows_per_sample > 0
-                                     and rowscale.numel() * rows_per_sample >= T):
-        return False
-    return True
 
 
 def defer_gemm_tn(g, x, out, bias_out=None, rowscale=None, rows_per_sample=0):
@@ -317,7 +292,6 @@ def flush_wgrads():
     classes = {}
     for it in items:
         classes.setdefault((it[4] is not None, it[0].dtype, it[0].device), []).append(it)
-    lib = _lib.load_library()
     vp, lg, it_ = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
     for (seg, dt, dev), lst in classes.items():
         for a in range(0, len(lst), _TN_GROUP_MAX):
@@ -337,10 +311,8 @@ def flush_wgrads():
             rps = arr(it_, [t[6] for t in grp])
             rsa = arr(it_, [t[5] for t in grp])
             cast = lambda a_: ctypes.cast(a_, vp)  # noqa: E731
-            with on_device(dev):
-                rc = lib.rfn_gemm_tn_grouped(n, cast(G), cast(X), cast(P), cast(Bv), cast(R), cast(T), cast(N), cast(K),
-                                             cast(ldg), cast(ldx), cast(rps), cast(rsa), _DT16[dt], current_stream(dev))
-            _lib.check(rc, "gemm_tn_grouped")
+            _lib.call("rfn_gemm_tn_grouped", dev, n, cast(G), cast(X), cast(P), cast(Bv), cast(R), cast(T), cast(N), cast(K),
+                      cast(ldg), cast(ldx), cast(rps), cast(rsa), _DT16[dt])
 
 
 class deferred_wgrads:
@@ -398,11 +370,8 @@ def _pack(src, batch_stride, row_stride, B, heads, nrows, nblk, want_r=True, wan
     new = lambda want: torch.empty(nbytes, dtype=torch.uint8, device=dev) if want else None  # noqa: E731
     r, t = new(want_r), new(want_t)
     r2, t2 = (new(want_r), new(want_t)) if src2 is not None else (None, None)
-    lib = _lib.load_library()
-    with on_device(dev):
-        rc = lib.rfn_attn_pack(ptr(src), batch_stride, row_stride, B, heads, nrows, nblk, ptr(r), ptr(t), ptr(src2),
-                               ptr(r2), ptr(t2), current_stream(dev))
-    _lib.check(rc, "attn_pack")
+    _lib.call("rfn_attn_pack", dev, ptr(src), batch_stride, row_stride, B, heads, nrows, nblk, ptr(r), ptr(t), ptr(src2),
+              ptr(r2), ptr(t2))
     return (r, t), (r2, t2)
 
 
@@ -432,12 +401,8 @@ def _fwd(q, kv, heads, scale, need_bwd):
     voff = heads * nkblk * _PACK_BLOCK
     o = torch.empty_like(q)
     lse2 = torch.empty((B * heads, nqpad), dtype=torch.float32, device=dev)
-    lib = _lib.load_library()
-    with on_device(dev):
-        rc = lib.rfn_attn_fwd(ptr(q), q.stride(0), q.stride(1), kvr.data_ptr(), kvt.data_ptr() + voff, ptr(o),
-                              o.stride(0), o.stride(1), ptr(lse2), B, heads, N, Nkv, nkblk, nqpad, float(scale),
-                              2 * heads, _DT16[q.dtype], current_stream(dev))
-    _lib.check(rc, "attn_fwd")
+    _lib.call("rfn_attn_fwd", dev, ptr(q), q.stride(0), q.stride(1), kvr.data_ptr(), kvt.data_ptr() + voff, ptr(o), o.stride(0),
+              o.stride(1), ptr(lse2), B, heads, N, Nkv, nkblk, nqpad, float(scale), 2 * heads, _DT16[q.dtype])
     return o, lse2, (kvr, kvt)
 
 
@@ -476,16 +441,12 @@ class _AttnFn(torch.autograd.Function):
         if not do.is_contiguous():
             do = do.contiguous()
         dt = _DT16[q.dtype]
-        lib = _lib.load_library()
         dq = torch.empty_like(q)
         delta = torch.empty_like(lse2)
         voff = heads * nkblk * _PACK_BLOCK
-        with on_device(dev):
-            rc = lib.rfn_attn_bwd_dq(ptr(q), q.stride(0), q.stride(1), ptr(do), ptr(o), o.stride(0), o.stride(1),
-                                     kvr.data_ptr(), kvr.data_ptr() + voff, kvt.data_ptr(), ptr(lse2), ptr(delta),
-                                     ptr(dq), dq.stride(0), dq.stride(1), B, heads, N, Nkv, nkblk, nqpad, float(scale),
-                                     2 * heads, dt, current_stream(dev))
-        _lib.check(rc, "attn_bwd_dq")
+        _lib.call("rfn_attn_bwd_dq", dev, ptr(q), q.stride(0), q.stride(1), ptr(do), ptr(o), o.stride(0), o.stride(1),
+                  kvr.data_ptr(), kvr.data_ptr() + voff, kvt.data_ptr(), ptr(lse2), ptr(delta), ptr(dq), dq.stride(0),
+                  dq.stride(1), B, heads, N, Nkv, nkblk, nqpad, float(scale), 2 * heads, dt)
         (qr, qt), (gr, gt) = _pack(q, q.stride(0), q.stride(1), B, heads, N, nqblk, src2=do)
         nkpad = -(-Nkv // 32) * 32
         chunk = _chunk_blocks(nqblk, Nkv, B * heads)
@@ -495,12 +456,9 @@ class _AttnFn(torch.autograd.Function):
         accT = torch.empty(images * B * heads * 2 * 64 * nkpad, dtype=torch.float32, device=dev)
         dkv = torch.empty_like(kv)
         k_view, v_view = kv[:, :, :C], kv[:, :, C:]
-        bwd_dkv = lib.rfn_attn_bwd_dkv_det if det else lib.rfn_attn_bwd_dkv
-        with on_device(dev):
-            rc = bwd_dkv(ptr(k_view), ptr(v_view), kv.stride(0), kv.stride(1), ptr(qr), ptr(qt), ptr(gr), ptr(gt), ptr(lse2),
-                         ptr(delta), ptr(accT), ptr(dkv), B, heads, N, Nkv, nqblk, nqpad, nkpad, chunk, float(scale), dt,
-                         current_stream(dev))
-        _lib.check(rc, "attn_bwd_dkv")
+        _lib.call("rfn_attn_bwd_dkv_det" if det else "rfn_attn_bwd_dkv", dev, ptr(k_view), ptr(v_view), kv.stride(0), kv.stride(1),
+                  ptr(qr), ptr(qt), ptr(gr), ptr(gt), ptr(lse2), ptr(delta), ptr(accT), ptr(dkv), B, heads, N, Nkv, nqblk, nqpad,
+                  nkpad, chunk, float(scale), dt)
         return dq, dkv, None, None
 
 

@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._tensor import current_stream, ptr, require_device_tensor, same_device, on_device
+from ._tensor import ptr, require_device_tensor, same_device
 from .correlation import local_correlation_layer, spatial_correlation_sample
 
 
@@ -51,9 +51,6 @@ class GlobalFeatureCorrelationLayer(nn.Module):
             raise RuntimeError("GlobalFeatureCorrelationLayer: batch/channel mismatch")
         out = torch.empty((B, hs * ws, ht, wt), dtype=torch.float32, device=dev)
         ws_ = torch.empty((B, hs * ws), dtype=torch.float32, device=dev) if self.cyclic_consistency else None
-        lib = _lib.load_library()
-        with on_device(dev):
-            rc = lib.rfn_global_corr_layer_f32(ptr(fs), ptr(ft), ptr(out), None if ws_ is None else ptr(ws_), B, C, hs, ws, ht, wt,
-                                               1 if self.cyclic_consistency else 0, current_stream(dev))
-        _lib.check(rc, "GlobalFeatureCorrelationLayer")
+        _lib.call("rfn_global_corr_layer_f32", dev, ptr(fs), ptr(ft), ptr(out), None if ws_ is None else ptr(ws_), B, C, hs, ws,
+                  ht, wt, 1 if self.cyclic_consistency else 0)
         return out

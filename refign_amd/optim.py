@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 from .params import refresh
 
 
@@ -118,10 +118,7 @@ class MultiTensorAdamW:
         host = np.asarray(args, dtype=np.float32)
         table, n, dev = self._table
         with torch.no_grad():
-            with on_device(dev):
-                rc = _lib.load_library().rfn_multi_adamw_f32(ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
-                                                             current_stream(dev))
-            _lib.check(rc, "multi_adamw_f32")
+            _lib.call("rfn_multi_adamw_f32", dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups))
         self.launches += 1
         self.opt._opt_called = True                        # what Optimizer.step's wrapper tells the LR scheduler
         refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
@@ -146,10 +143,8 @@ class MultiTensorAdamW:
         host = np.asarray(args, dtype=np.float64)
         table, n, dev = self._table
         with torch.no_grad():
-            with on_device(dev):
-                rc = _lib.load_library().rfn_multi_adamw_amp_f32(ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
-                                                                 ptr(found_inf), ptr(self._dev_step), current_stream(dev))
-            _lib.check(rc, "multi_adamw_amp_f32")
+            _lib.call("rfn_multi_adamw_amp_f32", dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
+                      ptr(found_inf), ptr(self._dev_step))
         self.launches += 1
         self.opt._opt_called = True
         refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))

@@ -14,9 +14,7 @@ import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr, workspace
-
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+from ._tensor import DTYPE_CODE, ptr, workspace
 
 
 def derived(p, key, fn, refill=None):
@@ -93,7 +91,7 @@ def _build_plan(params):
     # every other layout-changing copy of an fp32 parameter view into a contiguous <= 4-D tensor: one launch
     # (csrc/reduce.hip multi_permute_cast_kernel) instead of one strided-copy kernel per tensor
     rest = [i for i in range(len(dst)) if i not in skip]
-    pm = [i for i in rest if dst[i].is_cuda and dst[i].is_contiguous() and dst[i].dtype in _PERM_DT
+    pm = [i for i in rest if dst[i].is_cuda and dst[i].is_contiguous() and dst[i].dtype in DTYPE_CODE
           and src[i].dtype == torch.float32 and 1 <= dst[i].dim() <= 4 and dst[i].numel() > 0
           and src[i].shape == dst[i].shape]
     permutes = []
@@ -114,7 +112,6 @@ def _build_plan(params):
             "gen": _GENERATION[0]}
 
 
-_PERM_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 # 16-bit copy dtype -> (multi-tensor cast, multi-tensor transpose + cast) entry points of csrc/reduce.hip
 _CAST16 = {torch.bfloat16: ("rfn_multi_cast_f32_bf16", "rfn_multi_transpose_cast_f32_bf16"),
            torch.float16: ("rfn_multi_cast_f32_f16", "rfn_multi_transpose_cast_f32_f16")}
@@ -131,7 +128,7 @@ def _permute_table(dst, src, dev):
         n = d.numel()
         assert n < 2 ** 31, "the permute kernel indexes one tensor with 32 bits"
         rows += [(s_.data_ptr(), d.data_ptr(), shape[1], shape[2], shape[3], strides[0], strides[1], strides[2], strides[3],
-                  off, min(chunk, n - off), _PERM_DT[d.dtype]) for off in range(0, n, chunk)]
+                  off, min(chunk, n - off), DTYPE_CODE[d.dtype]) for off in range(0, n, chunk)]
     return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
 
 
@@ -162,10 +159,7 @@ def _transpose_table(dst, src, dev):
 
 
 def _multi_cast(table, nrows, dev, dtype=torch.bfloat16):
-    name = _CAST16[dtype][0]
-    with on_device(dev):
-        rc = getattr(_lib.load_library(), name)(ptr(table), nrows, current_stream(dev))
-    _lib.check(rc, name)
+    _lib.call(_CAST16[dtype][0], dev, ptr(table), nrows)
 
 
 def _optimizer_step_post_hook(optimizer, args, kwargs):
@@ -208,13 +202,9 @@ def refresh(params, plan_key=None):
         for table, nrows, dev, dsts, _ in plan["casts"]:
             _multi_cast(table, nrows, dev, dsts[0].dtype)
         for table, ntiles, dev, dsts, _ in plan["transposes"]:
-            with on_device(dev):
-                rc = getattr(_lib.load_library(), _CAST16[dsts[0].dtype][1])(ptr(table), ntiles, current_stream(dev))
-            _lib.check(rc, "multi_transpose_cast")
+            _lib.call(_CAST16[dsts[0].dtype][1], dev, ptr(table), ntiles)
         for table, nrows, dev, _, _ in plan["permutes"]:
-            with on_device(dev):
-                rc = _lib.load_library().rfn_multi_permute_cast_f32(ptr(table), nrows, current_stream(dev))
-            _lib.check(rc, "multi_permute_cast")
+            _lib.call("rfn_multi_permute_cast_f32", dev, ptr(table), nrows)
         if plan["rest"][0]:
             torch._foreach_copy_(*plan["rest"])
 
@@ -244,9 +234,7 @@ def ema_update(ema_params, live_params, momentum, plan_key):
                 rows += [(ep + 4 * off, lp + 4 * off, 0, min(chunk, n - off)) for off in range(0, n, chunk)]
             table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
             ent = _EMA_TABLES[plan_key] = (sig, table, len(rows))
-        with on_device(dev):
-            rc = lib.rfn_multi_ema_f32(ptr(ent[1]), ent[2], float(momentum), current_stream(dev))
-        _lib.check(rc, "multi_ema_f32")
+        _lib.call("rfn_multi_ema_f32", dev, ptr(ent[1]), ent[2], float(momentum))
     else:
         ema, live = [p.data for p in ema_params], [p.data for p in live_params]
         torch._foreach_mul_(ema, momentum)
@@ -296,7 +284,7 @@ def grad_sink(p):
 def sum_rows(x, out=None, accumulate=False):
     """out[n] (+)= sum over the leading dim of a contiguous (S, n) fp32 / bf16 / fp16 matrix, fp32 result (csrc/reduce.hip)."""
     S, n = x.shape
-    if not x.is_cuda or n % 8 != 0 or x.dtype not in _DT or not x.is_contiguous():
+    if not x.is_cuda or n % 8 != 0 or x.dtype not in DTYPE_CODE or not x.is_contiguous():
         r = x.sum(0, dtype=torch.float32)
         if out is None:
             return r
@@ -306,10 +294,7 @@ def sum_rows(x, out=None, accumulate=False):
     lib = _lib.load_library()
     nb = lib.rfn_sum_rows_workspace_bytes(S, n)
     ws = workspace(nb, x.device)
-    with on_device(x.device):
-        rc = lib.rfn_sum_rows(ptr(x), ptr(out), ptr(ws), S, n, _DT[x.dtype], 1 if accumulate else 0,
-                              current_stream(x.device))
-    _lib.check(rc, "sum_rows")
+    _lib.call("rfn_sum_rows", x.device, ptr(x), ptr(out), ptr(ws), S, n, DTYPE_CODE[x.dtype], 1 if accumulate else 0)
     return out
 
 
@@ -319,13 +304,11 @@ def linear_param_grads(g2, part, gb_out, gw_out):
     the shapes are outside the fused kernel's domain (caller falls back to two sum_rows calls)."""
     T, N = g2.shape
     S, NK = part.shape
-    if not (g2.is_cuda and g2.dtype == part.dtype and g2.dtype in _DT and T > 64 and S <= 64 and N % 8 == 0
+    if not (g2.is_cuda and g2.dtype == part.dtype and g2.dtype in DTYPE_CODE and T > 64 and S <= 64 and N % 8 == 0
             and NK % 8 == 0 and g2.is_contiguous() and part.is_contiguous()):
         return False
     lib = _lib.load_library()
     ws = workspace(lib.rfn_sum_rows_workspace_bytes(T, N), g2.device)
-    with on_device(g2.device):
-        rc = lib.rfn_linear_param_grads(ptr(g2), ptr(gb_out), ptr(ws), T, N, 1, ptr(part), ptr(gw_out), S, NK, 1,
-                                        _DT[g2.dtype], current_stream(g2.device))
-    _lib.check(rc, "linear_param_grads")
+    _lib.call("rfn_linear_param_grads", g2.device, ptr(g2), ptr(gb_out), ptr(ws), T, N, 1, ptr(part), ptr(gw_out), S, NK, 1,
+              DTYPE_CODE[g2.dtype])
     return True

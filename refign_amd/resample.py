@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 from .datastep import IMNET_MEAN, IMNET_STD
 
 PRECISION_BITS = 32 - 8 - 2      # Resample.c: 8 bits of pixel, 2 spare bits for the accumulation
@@ -168,10 +168,7 @@ def resize_u8(image_hwc_u8, size):
     bx, cx, kx = _device_tables("bilinear", W, Wd, dev)
     by, cy, ky = _device_tables("bilinear", H, Hd, dev)
     out = torch.empty((3, Hd, Wd), dtype=torch.uint8, device=dev)
-    with on_device(dev):
-        rc = _lib.load_library().rfn_resize_u8(ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky, ptr(out),
-                                               current_stream(dev))
-    _lib.check(rc, "resize_u8")
+    _lib.call("rfn_resize_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky, ptr(out))
     return out
 
 
@@ -186,9 +183,7 @@ def resize_nearest_u8(label_u8, size):
     dev = label_u8.device
     ty, tx = _device_tables("nearest", H, Hd, dev), _device_tables("nearest", W, Wd, dev)
     out = torch.empty((Hd, Wd), dtype=torch.uint8, device=dev)
-    with on_device(dev):
-        rc = _lib.load_library().rfn_resize_nearest_u8(ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(out), current_stream(dev))
-    _lib.check(rc, "resize_nearest_u8")
+    _lib.call("rfn_resize_nearest_u8", dev, ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(out))
     return out
 
 
@@ -208,11 +203,8 @@ def resize_crop_flip_normalize(image_hwc_u8, dims, top, left, h, w, flip, out_im
     by, cy, ky = _device_tables("bilinear", H, Hd, dev)
     m = np.asarray(mean, dtype=np.float32).copy()
     s = np.asarray(std, dtype=np.float32).copy()
-    with on_device(dev):
-        rc = _lib.load_library().rfn_resize_crop_flip_norm_u8(ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy),
-                                                              ky, int(top), int(left), int(h), int(w), 1 if flip else 0,
-                                                              m.ctypes.data, s.ctypes.data, ptr(out_image), current_stream(dev))
-    _lib.check(rc, "resize_crop_flip_norm_u8")
+    _lib.call("rfn_resize_crop_flip_norm_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky,
+              int(top), int(left), int(h), int(w), 1 if flip else 0, m.ctypes.data, s.ctypes.data, ptr(out_image))
     return out_image
 
 

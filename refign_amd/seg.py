@@ -31,6 +31,7 @@ from . import f8 as _f8
 from . import linear as _linear
 from . import determinism, mfma
 from ._tensor import const_tensor
+from ._tensor import DTYPE_CODE as _CE_DT          # (the name the GPU tests read the codes under)
 from .align import BaseHead
 from .conv import Conv2d, patch_conv_tokens
 from .layernorm import LayerNorm
@@ -850,9 +851,6 @@ def fused_ce_consumer(module):
     return bool(getattr(module, "_rfn_fused_ce_consumer", False))
 
 
-_CE_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
-
-
 class DeferredUpsample:
     """Class logits that are still to be up-sampled (bilinear, align_corners=False) to `size` -- what the decode head /
     the training step hand to the loss instead of the up-sampled tensor, so that PixelWeightedCrossEntropyLoss can do
@@ -893,7 +891,7 @@ class _UpsampleCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, size, ignore_index):
         from . import _lib
-        from ._tensor import current_stream, on_device, ptr
+        from ._tensor import ptr
         B, C, h, w = logits.shape
         H, W = size
         lg = logits.contiguous()
@@ -910,17 +908,13 @@ class _UpsampleCEFn(torch.autograd.Function):
             # per-tile partials + ordered sums (csrc/loss.hip): the loss arrives in slot 0, the other slots are zero
             from ._tensor import workspace
             ws = workspace(lib.rfn_upsample_ce_det_workspace_bytes(B, C, H, W), lg.device)
-            with on_device(lg.device):
-                rc = lib.rfn_upsample_ce_det(ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), ptr(ws), B, C, h, w, H, W,
-                                             int(ignore_index), _CE_DT[lg.dtype], 1, current_stream(lg.device))
-            _lib.check(rc, "upsample_ce_det")
+            _lib.call("rfn_upsample_ce_det", lg.device, ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), ptr(ws), B, C, h, w,
+                      H, W, int(ignore_index), _CE_DT[lg.dtype], 1)
             ctx.save_for_backward(grad)
             ctx.npix, ctx.dtype = float(B * H * W), logits.dtype
             return (total[0] / ctx.npix).to(torch.float32)
-        with on_device(lg.device):
-            rc = lib.rfn_upsample_ce(ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), B, C, h, w, H, W,
-                                     int(ignore_index), _CE_DT[lg.dtype], 1, current_stream(lg.device))
-        _lib.check(rc, "upsample_ce")
+        _lib.call("rfn_upsample_ce", lg.device, ptr(lg), ptr(tg), ptr(wt), ptr(grad), ptr(total), B, C, h, w, H, W,
+                  int(ignore_index), _CE_DT[lg.dtype], 1)
         ctx.save_for_backward(grad)
         ctx.npix, ctx.dtype = float(B * H * W), logits.dtype
         return (total.sum() / ctx.npix).to(torch.float32)

@@ -18,7 +18,7 @@ import os
 import torch
 
 from . import _lib, mfma
-from ._tensor import current_stream, on_device, ptr
+from ._tensor import ptr
 
 ENABLED = True
 BF = torch.bfloat16
@@ -43,10 +43,8 @@ def split3(x2, order, Kp, stack=False):
     if x2.stride(1) != 1 or x2.stride(0) < K:
         x2 = x2.contiguous()
     out = torch.empty((3 * rows, Kp) if stack else (rows, 3 * Kp), dtype=BF, device=x2.device)
-    with on_device(x2.device):
-        rc = _lib.load_library().rfn_split3_bf16(ptr(x2), x2.stride(0), ptr(out), out.stride(0), rows * Kp if stack else Kp,
-                                                 rows, K, Kp, _ORDER[order], current_stream(x2.device))
-    _lib.check(rc, "split3_bf16")
+    _lib.call("rfn_split3_bf16", x2.device, ptr(x2), x2.stride(0), ptr(out), out.stride(0), rows * Kp if stack else Kp, rows, K,
+              Kp, _ORDER[order])
     return out
 
 
@@ -69,12 +67,9 @@ def gemm_nt(x, w, bias=None, res=None, act=0):
     y = torch.empty((M, Np), dtype=torch.float32, device=x.device)
     if res is not None and Np != N:
         res = torch.nn.functional.pad(res, (0, Np - N))
-    with on_device(x.device):
-        rc = _lib.load_library().rfn_gemm_nt_o32(ptr(x3), ptr(w3), ptr(None if bias is None else bias.contiguous()),
-                                                 ptr(None if res is None else res.contiguous()), None, 0, int(act), ptr(y),
-                                                 M, Np, x3.shape[1], x3.stride(0), w3.stride(0), y.stride(0),
-                                                 current_stream(x.device))
-    _lib.check(rc, "gemm_nt_o32")
+    _lib.call("rfn_gemm_nt_o32", x.device, ptr(x3), ptr(w3), ptr(None if bias is None else bias.contiguous()),
+              ptr(None if res is None else res.contiguous()), None, 0, int(act), ptr(y), M, Np, x3.shape[1], x3.stride(0),
+              w3.stride(0), y.stride(0))
     return y if Np == N else y[:, :N]
 
 
@@ -132,12 +127,8 @@ class _Attn32Fn(torch.autograd.Function):
         nqpad = -(-N // 128) * 128
         o = torch.empty_like(q)
         lse2 = torch.empty((B * heads, nqpad), dtype=torch.float32, device=q.device)
-        with on_device(q.device):
-            rc = _lib.load_library().rfn_attn32_fwd(ptr(q), q.stride(0), q.stride(1), ptr(kv), kv.stride(0), kv.stride(1), ptr(o),
-                                                    o.stride(0), o.stride(1), ptr(lse2), B, heads, C // heads, N, Nkv, nqpad,
-                                                    float(scale),
-                                                    current_stream(q.device))
-        _lib.check(rc, "attn32_fwd")
+        _lib.call("rfn_attn32_fwd", q.device, ptr(q), q.stride(0), q.stride(1), ptr(kv), kv.stride(0), kv.stride(1), ptr(o),
+                  o.stride(0), o.stride(1), ptr(lse2), B, heads, C // heads, N, Nkv, nqpad, float(scale))
         if q.requires_grad or kv.requires_grad:
             ctx.save_for_backward(q, kv, o, lse2)
             ctx.heads, ctx.scale = heads, scale
@@ -158,12 +149,9 @@ class _Attn32Fn(torch.autograd.Function):
         tiles = -(-Nkv // 128) * B * heads
         chunks = max(1, min(-(-N // 32), -(-1024 // tiles)))
         dkv = (torch.zeros_like if chunks > 1 else torch.empty_like)(kv)
-        with on_device(q.device):
-            rc = _lib.load_library().rfn_attn32_bwd(ptr(q), q.stride(0), q.stride(1), ptr(kv), kv.stride(0), kv.stride(1), ptr(do),
-                                                    ptr(o), o.stride(0), o.stride(1), ptr(lse2), ptr(delta), ptr(dq), dq.stride(0),
-                                                    dq.stride(1), ptr(dkv), dkv.stride(0), dkv.stride(1), B, heads, C // heads, N,
-                                                    Nkv, lse2.shape[1], chunks, float(scale), current_stream(q.device))
-        _lib.check(rc, "attn32_bwd")
+        _lib.call("rfn_attn32_bwd", q.device, ptr(q), q.stride(0), q.stride(1), ptr(kv), kv.stride(0), kv.stride(1), ptr(do),
+                  ptr(o), o.stride(0), o.stride(1), ptr(lse2), ptr(delta), ptr(dq), dq.stride(0), dq.stride(1), ptr(dkv),
+                  dkv.stride(0), dkv.stride(1), B, heads, C // heads, N, Nkv, lse2.shape[1], chunks, float(scale))
         return dq, dkv, None, None
 
 
@@ -267,10 +255,7 @@ def cat_split(parts):
     strides = (ctypes.c_long * (4 * n))(*[v for p in parts for v in p.stride()])
     chans = (ctypes.c_int * n)(*[p.shape[1] for p in parts])
     cast = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
-    with on_device(out.device):
-        rc = _lib.load_library().rfn_split3_cat_bf16(cast(ptrs), cast(strides), cast(chans), n, ptr(out), B, H, W, Cp,
-                                                     current_stream(out.device))
-    _lib.check(rc, "split3_cat_bf16")
+    _lib.call("rfn_split3_cat_bf16", out.device, cast(ptrs), cast(strides), cast(chans), n, ptr(out), B, H, W, Cp)
     return out, Cp, C
 
 
@@ -300,11 +285,8 @@ def _conv_o32(x3, wp, bias, B, H, W, C, N, KH, KW, s, p, d, act, transposed, out
     channels (forward) or C channels (transposed = data gradient)."""
     oc = C if transposed else N
     y = torch.empty((B,) + tuple(out_hw) + (oc,), dtype=torch.float32, device=x3.device)
-    with on_device(x3.device):
-        rc = _lib.load_library().rfn_conv2d_nhwc_o32(ptr(x3), ptr(wp), ptr(bias), int(act), ptr(y), B, H, W, C, N, KH, KW,
-                                                     s, p, d, wp.stride(0), oc, 1 if transposed else 0,
-                                                     current_stream(x3.device))
-    _lib.check(rc, "conv2d_nhwc_o32")
+    _lib.call("rfn_conv2d_nhwc_o32", x3.device, ptr(x3), ptr(wp), ptr(bias), int(act), ptr(y), B, H, W, C, N, KH, KW, s, p, d,
+              wp.stride(0), oc, 1 if transposed else 0)
     return y
 
 

@@ -16,10 +16,10 @@ import time
 import torch
 
 from . import _lib
-from ._tensor import current_stream, on_device
+from ._tensor import DTYPE_CODE
 
 # dtype codes of rfn_steplog_gather
-DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.float64: 3, torch.int32: 4}
+DTYPE_CODES = {**DTYPE_CODE, torch.float64: 3, torch.int32: 4}      # the record format's two additions
 MAX_GATHER = 32                 # values per launch of rfn_steplog_gather
 MAX_GROUPS = 32
 CHUNK = 32768                   # elements per workgroup of the norm kernel's first stage (128 KB of fp32)
@@ -101,10 +101,8 @@ def grad_sqnorm_groups(flat, plan, out):
     if not plan.chunks:
         out.zero_()
         return out
-    with on_device(flat.device):
-        rc = _lib.load_library().rfn_grad_sqnorm_groups(flat.data_ptr(), flat.numel(), plan.table.data_ptr(), len(plan.chunks), G,
-                                                        plan.partials.data_ptr(), out.data_ptr(), current_stream(flat.device))
-    _lib.check(rc, "grad_sqnorm_groups")
+    _lib.call("rfn_grad_sqnorm_groups", flat.device, flat.data_ptr(), flat.numel(), plan.table.data_ptr(), len(plan.chunks), G,
+              plan.partials.data_ptr(), out.data_ptr())
     return out
 
 
@@ -123,15 +121,11 @@ def gather_scalars(tensors, row):
     if not row.is_cuda:
         row[:len(tensors)] = torch.stack([t.detach().reshape(()).double() for t in tensors])
         return row
-    lib = _lib.load_library()
-    with on_device(row.device):
-        st = current_stream(row.device)
-        for a in range(0, len(tensors), MAX_GATHER):
-            part = tensors[a:a + MAX_GATHER]
-            ptrs = (ctypes.c_void_p * len(part))(*[t.data_ptr() for t in part])
-            codes = (ctypes.c_int * len(part))(*[DTYPE_CODES[t.dtype] for t in part])
-            rc = lib.rfn_steplog_gather(ptrs, codes, len(part), row.data_ptr() + 8 * a, st)
-            _lib.check(rc, "steplog_gather")
+    for a in range(0, len(tensors), MAX_GATHER):
+        part = tensors[a:a + MAX_GATHER]
+        ptrs = (ctypes.c_void_p * len(part))(*[t.data_ptr() for t in part])
+        codes = (ctypes.c_int * len(part))(*[DTYPE_CODES[t.dtype] for t in part])
+        _lib.call("rfn_steplog_gather", row.device, ptrs, codes, len(part), row.data_ptr() + 8 * a)
     return row
 
 

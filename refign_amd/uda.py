@@ -1282,12 +1282,10 @@ class DomainAdaptationSegmentationModel(nn.Module):
                 (out_size is not None or (H % scale_factor == 0 and W % scale_factor == 0)):
             # one kernel instead of a 330 MB one-hot tensor, a pooling pass and a max (csrc/refine.hip)
             from . import _lib
-            from ._tensor import current_stream, on_device, ptr
+            from ._tensor import ptr
             out = torch.empty((b, 1, oh, ow), dtype=torch.long, device=gt.device)
-            with on_device(gt.device):
-                rc = _lib.load_library().rfn_label_majority(ptr(gt), ptr(out), b, H, W, int(scale_factor), int(n_classes),
-                                                            int(ignore_index), float(min_ratio), current_stream(gt.device))
-            _lib.check(rc, "label_majority")
+            _lib.call("rfn_label_majority", gt.device, ptr(gt), ptr(out), b, H, W, int(scale_factor), int(n_classes),
+                      int(ignore_index), float(min_ratio))
             return out
         out = gt.clone()
         out[out == ignore_index] = n_classes

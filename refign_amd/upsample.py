@@ -13,25 +13,21 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, determinism
-from ._tensor import current_stream, on_device, ptr
-
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+from ._tensor import DTYPE_CODE, ptr
 
 
 def bilinear2d_backward(grad_out, in_size, scales=(0.0, 0.0)):
     """Gradient of the (N, C, h, w) input of a bilinear up-sampling (align_corners=False) for the gradient `grad_out`
     (N, C, H, W) of its result.  `scales`: ATen's source-index scales (1 / scale_factor) when the forward was given a scale
     factor, 0 for h / H, w / W."""
-    if not (grad_out.is_cuda and grad_out.dim() == 4 and grad_out.dtype in _DT):
+    if not (grad_out.is_cuda and grad_out.dim() == 4 and grad_out.dtype in DTYPE_CODE):
         raise RuntimeError("bilinear2d_backward: a 4-d fp32 / bf16 / fp16 HIP tensor expected")
     g = grad_out.contiguous()
     N, C, H, W = g.shape
     h, w = int(in_size[0]), int(in_size[1])
     gin = torch.empty((N, C, h, w), dtype=g.dtype, device=g.device)
-    with on_device(g.device):
-        rc = _lib.load_library().rfn_upsample_bilinear2d_bwd(ptr(g), ptr(gin), N * C, h, w, H, W, float(scales[0]),
-                                                             float(scales[1]), _DT[g.dtype], current_stream(g.device))
-    _lib.check(rc, "upsample_bilinear2d_bwd")
+    _lib.call("rfn_upsample_bilinear2d_bwd", g.device, ptr(g), ptr(gin), N * C, h, w, H, W, float(scales[0]), float(scales[1]),
+              DTYPE_CODE[g.dtype])
     return gin
 
 
@@ -54,7 +50,7 @@ class _UpBilinearFn(torch.autograd.Function):
 
 
 def interpolate_bilinear(x, size=None, scale_factor=None):
-    if determinism.enabled() and x.is_cuda and x.dim() == 4 and x.dtype in _DT and torch.is_grad_enabled() and x.requires_grad:
+    if determinism.enabled() and x.is_cuda and x.dim() == 4 and x.dtype in DTYPE_CODE and torch.is_grad_enabled() and x.requires_grad:
         up = (scale_factor is not None and float(scale_factor) >= 1.0) or \
             (size is not None and size[0] >= x.shape[2] and size[1] >= x.shape[3])
         if up:

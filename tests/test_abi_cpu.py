@@ -71,3 +71,60 @@ def test_plugin_package_importable_by_name():
     assert list(sig.parameters) == ["input1", "input2", "kernel_size", "patch_size", "stride", "padding", "dilation",
                                     "dilation_patch"]                       # correlation_function.py:14-16
     assert [p.default for p in list(sig.parameters.values())[2:]] == [1, 1, 1, 0, 1, 1]
+
+
+def _header_text():
+    with open(os.path.join(ROOT, "include", "refign_hip.h")) as f:
+        return f.read()
+
+
+def test_signatures_parsed_from_header_pinned():
+    """The (restype, argtypes) `_lib` derives from the header, spelled out for entry points that together cover every C type
+    the header uses: pointers to void / float / double / int / long / unsigned char, void**, int / long / float by value,
+    rfn_stream_t, and the int / long / unsigned long / const char* returns."""
+    from ctypes import c_char_p, c_float, c_int, c_long, c_ulong, c_void_p
+    from refign_amd import _lib
+    p, i, l_, f = c_void_p, c_int, c_long, c_float
+    expected = {
+        "rfn_corr_fwd_f32": (i, [p] * 3 + [i] * 4 + [i] * 12 + [p]),
+        "rfn_corr_bwd_f64": (i, [p] * 5 + [i] * 4 + [i] * 12 + [p]),
+        "rfn_last_error": (c_char_p, []),
+        "rfn_local_corr_layer_split_workspace_bytes": (l_, [i] * 4),
+        "rfn_refine_workspace_bytes": (c_ulong, [i]),
+        "rfn_layernorm_fwd": (i, [p] * 6 + [l_, i, f, i, i, p]),
+        "rfn_gemm_nt": (i, [p] * 5 + [i, i, p] + [l_] * 6 + [i, p]),
+        "rfn_steplog_gather": (i, [p, p, i, p, p]),
+        "rfn_crop_flip_norm_u8": (i, [p, p] + [i] * 8 + [p] * 4 + [p]),
+    }
+    for name, sig in expected.items():
+        assert _lib.SIGNATURES[name] == sig, name
+
+
+def test_header_parser_rejects_unknown_type():
+    from ctypes import c_int, c_long, c_void_p
+    from refign_amd import _lib
+    ok = "#define RFN_ABI_VERSION 9\nint rfn_fine(const float* x, long n, rfn_stream_t stream);\n"
+    assert _lib.parse_header(ok) == (9, {"rfn_fine": (c_int, [c_void_p, c_long, c_void_p])})
+    for bad in ("int rfn_bad(short n, rfn_stream_t stream);", "size_t rfn_bad(int n);", "int rfn_bad(long long n);"):
+        with pytest.raises(ValueError, match="rfn_bad"):
+            _lib.parse_header("#define RFN_ABI_VERSION 9\n" + bad + "\n")
+
+
+def test_stream_is_the_last_argument():
+    """What `_lib.call` rests on: a declaration that takes an rfn_stream_t takes exactly one, as its last parameter."""
+    text = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    decls = re.findall(r"\b(rfn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    assert len(decls) == len(_declared_symbols())
+    launching = 0
+    for name, args in decls:
+        params = [a.strip() for a in args.split(",")]
+        n = sum(1 for a in params if re.match(r"rfn_stream_t\b", a))
+        assert n == 0 or (n == 1 and params[-1].startswith("rfn_stream_t")), name
+        launching += n
+    assert launching >= 100
+
+
+def test_abi_version_comes_from_the_header():
+    from refign_amd import _lib
+    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == int(re.search(r"#define\s+RFN_ABI_VERSION\s+(\d+)", _header_text()).group(1))
