@@ -691,6 +691,43 @@ int rfn_resize_nearest_u8(const void* label, int H, int W, int Hd, int Wd, const
                           rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The same two passes with the filter as an argument (additions to ABI 4; the three entry points above keep their signatures and
+ * still insist on bilinear tap counts).  filter: 0 = bilinear (support 1), 1 = lanczos (Pillow's LANCZOS, sinc(x) sinc(x / 3) on
+ * [-3, 3): what the matcher's data sets -- datasets/megadepth.py, robotcarmatching.py -- and its `test:` sections resize with).
+ * Tables as above (refign_amd/resample.py: filter_tables) with kmax = ceil(support * max(in / out, 1)) * 2 + 1; Lanczos taps are
+ * negative in places, the table builder checks 255 * sum |coef| + 2^21 < 2^31 per row (int32 accumulation), and the clip to a
+ * byte after each pass is where the overshoot goes.
+ *   rfn_resize_filter_u8                     the resized image, uint8 (3, Hd, Wd).
+ *   rfn_resize_filter_crop_flip_norm_pad_u8  as rfn_resize_crop_flip_norm_u8, into out_image (3, Hf, Wf) fp32 with Hf >= h, Wf >= w:
+ *                                            the crop at the top left, 0.0f everywhere else (transforms.PadBottomRight after
+ *                                            Normalize: the fill is 0 in normalised space), written by the same launch.
+ * Errors (nothing is launched): those above, a filter other than 0 / 1, kmax not the filter's value, kmax > 129 (lanczos:
+ * down-scaling by more than 64 / 3; the message names the filter and the cap), Hf < h or Wf < w, Hf > 65535.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_resize_filter_u8(const void* image_hwc, int H, int W, int Hd, int Wd, int filter, const int* bounds_x, const int* coef_x,
+                         int kmax_x, const int* bounds_y, const int* coef_y, int kmax_y, void* out_chw, rfn_stream_t stream);
+int rfn_resize_filter_crop_flip_norm_pad_u8(const void* image_hwc, int H, int W, int Hd, int Wd, int filter, const int* bounds_x,
+                                            const int* coef_x, int kmax_x, const int* bounds_y, const int* coef_y, int kmax_y, int top,
+                                            int left, int h, int w, int flip, const float* mean3, const float* std3, float* out_image,
+                                            int Hf, int Wf, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * helpers/metrics.py:68-201 (SparseEPE.update with compute_aucs) in one launch, a workgroup per sample (csrc/sparseepe.hip;
+ * addition to ABI 4).  flow (B, 2, h, w) fp32: the flow target -> reference at full resolution; conf (B, 1, h, w) fp32 or NULL
+ * (no AUSE); pts_src / pts_trg (N, 2) fp32 (x, y): the batch's correspondences one sample after the other, sample b owning rows
+ * [offsets[b], offsets[b + 1]); offsets: HOST array of B + 1 ints (they come from tensor shapes).  Per sample: a point is valid
+ * when its four coordinates, rounded half to even, lie inside [0, w) x [0, h); flow and confidence are read at the rounded
+ * target point; EPE = |(src - trg) - flow| in fp32; with conf the area between the sparsification curves of the confidence and
+ * of the oracle (50 intervals; thresholds by torch.quantile's fp32 rank / lerp recipe on the points sorted in LDS, every kept set
+ * a suffix of the sorted order, its mean from an fp64 scan).
+ * rows (B, 8) fp64: mean EPE, #EPE <= 1, <= 3, <= 5, <= 10, AUSE, n_valid, 1 (sample counted) -- all 0 for a sample without a
+ * valid point.  Every row is written (no memset needed), sums are fp64, there are no atomics: legal in deterministic mode.
+ * Errors (nothing is launched): a null pointer, B > 64, offsets not ascending from 0, more than 8192 points in a sample.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_sparse_epe_f32(const float* flow, const float* conf, const float* pts_src, const float* pts_trg, const int* offsets, int B,
+                       int h, int w, double* rows, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * K5 (BASELINE.json config 5, "bf16 HRDA + fp8 MFMA attention"): fp8 (OCP e4m3, fp32 accumulate) matrix-core path of
  * the gradient-free EMA teacher (segmentation_model.py:204-209 runs MiT-B5, mix_transformer.py:96-103,137-164, on 40
  * HRDA views per GPU).  No reference analogue (the reference's recipe is 16-bit AMP, README.md:262); csrc/f8.hip.

@@ -156,25 +156,33 @@ def trainer_logging(cfg):
 
 
 # transforms of a data set's pipeline that the device data step covers, in the order the reference's configs apply them
-_INGEST_ORDER = ("Resize", "ToTensor", "RandomCrop", "RandomHorizontalFlip", "ConvertImageDtype", "Normalize")
-_INGEST_ARGS = {"Resize": {"size", "img_only", "only_if_larger"}, "ToTensor": set(), "RandomCrop": {"size", "cat_max_ratio"},
-                "RandomHorizontalFlip": {"p"}, "ConvertImageDtype": set(), "Normalize": {"mean", "std"}}
+_INGEST_ORDER = ("Resize", "ToTensor", "RandomCrop", "RandomHorizontalFlip", "ConvertImageDtype", "Normalize", "PadBottomRight")
+_INGEST_ARGS = {"Resize": {"size", "img_only", "only_if_larger", "img_interpolation"}, "ToTensor": set(),
+                "RandomCrop": {"size", "cat_max_ratio"}, "RandomHorizontalFlip": {"p"}, "ConvertImageDtype": set(),
+                "Normalize": {"mean", "std"}, "PadBottomRight": {"size", "same_shape_keys"}}
+_INGEST_FILTERS = ("bilinear", "lanczos")                 # Pillow filters the device resize restates (refign_amd/resample.py)
 
 
 def ingest_plan(cfg, split, dataset):
     """What `data.init_args.load_config[split][dataset]` of a loaded YAML asks of the path from a decoded file to the batch
     tensors, as the keywords of the device data step (refign_amd/resample.py, refign_amd/datastep.py):
-      dims           load-time size (h, w) of the data set reader, or None
+      dims           load-time size (h, w) of the data set reader as the section gives it, or None (a reader's own default --
+                     RobotCarMatching's (1024, 1024) -- is the reader's business: readers are outside this package)
       resize         transforms.Resize's `size` (int or (h, w)), or None; img_only: its flag (the label keeps its size);
-                     only_if_larger: its flag
+                     only_if_larger: its flag; interpolation: its `img_interpolation` ("bilinear" when absent)
+      dims_interpolation  the filter of the reader's load-time resize: "lanczos" for MegaDepth, RobotCarMatching's
+                     `resize_filter` ("lanczos" when absent), "bilinear" for every other data set
+      pad            transforms.PadBottomRight after Normalize: None, "same" (`same_shape_keys`: both images at the larger
+                     height and width) or its `size` (h, w)
       crop_size      RandomCrop's size (h, w), or None; cat_max_ratio: its ratio (1.0 when absent)
       flip           RandomHorizontalFlip's probability (0.0 when absent)
       mean / std     Normalize's statistics (ImageNet's by default)
       load_keys      the reader's keys, as given
     train: RareClassSourceSampler / PairSampler(..., dims=, crop_size=, cat_max_ratio=); val / test / predict:
-    resample.EvalIngest(dims=, resize=, img_only=).  The pipeline must be made of ToTensor / Resize / RandomCrop /
-    RandomHorizontalFlip / ConvertImageDtype / Normalize in the reference's order with their defaults for everything the plan
-    does not carry; anything else (ColorJitter, the MegaDepth flow synthesis, ...) raises OutOfScopeError naming the transform.
+    resample.EvalIngest(dims=, resize=, img_only=, only_if_larger=, interpolation=, dims_interpolation=, pad=).  The pipeline
+    must be made of ToTensor / Resize / RandomCrop / RandomHorizontalFlip / ConvertImageDtype / Normalize / PadBottomRight in
+    the reference's order with their defaults for everything the plan does not carry; anything else (ColorJitter, the MegaDepth
+    flow synthesis, a filter other than bilinear / lanczos, ...) raises OutOfScopeError naming the transform or the value.
     `build` and IGNORED_PREFIXES are untouched: data_modules.* specs still come back as specs from there."""
     from .datastep import IMNET_MEAN, IMNET_STD
     try:
@@ -184,7 +192,12 @@ def ingest_plan(cfg, split, dataset):
     pair = lambda v: v if isinstance(v, int) else tuple(int(a) for a in v)  # noqa: E731
     plan = {"dims": pair(sec["dims"]) if sec.get("dims") is not None else None, "resize": None, "img_only": False,
             "only_if_larger": False, "crop_size": None, "cat_max_ratio": 1.0, "flip": 0.0, "mean": tuple(IMNET_MEAN),
-            "std": tuple(IMNET_STD), "load_keys": list(sec.get("load_keys") or [])}
+            "std": tuple(IMNET_STD), "load_keys": list(sec.get("load_keys") or []), "interpolation": "bilinear",
+            "dims_interpolation": {"MegaDepth": "lanczos", "RobotCarMatching": sec.get("resize_filter", "lanczos")}.get(
+                dataset, "bilinear"), "pad": None}
+    if plan["dims_interpolation"] not in _INGEST_FILTERS:
+        raise OutOfScopeError(f"ingest_plan: resize_filter {plan['dims_interpolation']!r} ({split}.{dataset}) is outside the "
+                              f"device resize ({' / '.join(_INGEST_FILTERS)})")
     stage = -1
     for spec in sec.get("transforms") or []:
         path = spec["class_path"] if is_spec(spec) else str(spec)
@@ -202,10 +215,19 @@ def ingest_plan(cfg, split, dataset):
         if name == "Resize":
             plan["resize"], plan["img_only"] = pair(args["size"]), bool(args.get("img_only", False))
             plan["only_if_larger"] = bool(args.get("only_if_larger", False))
+            plan["interpolation"] = args.get("img_interpolation", "bilinear")
+            if plan["interpolation"] not in _INGEST_FILTERS:
+                raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) with img_interpolation "
+                                      f"{plan['interpolation']!r} is outside the device resize ({' / '.join(_INGEST_FILTERS)})")
         elif name == "RandomCrop":
             plan["crop_size"], plan["cat_max_ratio"] = pair(args["size"]), float(args.get("cat_max_ratio", 1.0))
         elif name == "RandomHorizontalFlip":
             plan["flip"] = float(args.get("p", 0.5))
         elif name == "Normalize":
             plan["mean"], plan["std"] = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
+        elif name == "PadBottomRight":
+            keys, size = args.get("same_shape_keys"), args.get("size")
+            if (keys is None) == (size is None) or (keys is not None and len(keys) != 2):
+                raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) takes `same_shape_keys` (two keys) or `size`")
+            plan["pad"] = "same" if keys is not None else pair(size)
     return plan

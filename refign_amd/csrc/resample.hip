@@ -11,14 +11,20 @@
 //                     the crop's footprint of the source is read.  int32 accumulation: 255 * 2^22 + 2^21 fits.
 //   resize_kernel<1>  the same two passes, bytes out: Pillow's pixels as a (3, Hd, Wd) image.
 //   resize_nearest_kernel  label map through the two index tables (nearest_table: Pillow ACCUMULATES the source coordinate).
+// The kernel knows nothing of the filter: Pillow's LANCZOS (sinc(x) sinc(x / 3) on [-3, 3), the matcher's data sets and `test:`
+// sections) is the same two passes over longer tables with negative taps (refign_amd/resample.py: filter_tables checks
+// 255 * sum |coef| + 2^21 < 2^31 per row, so the int32 accumulation holds), and the clip to a byte between the passes is where its
+// overshoot goes.  In the fp32 mode the output may be larger than the crop, (3, Hf, Wf) with Hf >= h, Wf >= w: the pixels outside
+// the crop are written 0.0f by the tile that covers them -- transforms.PadBottomRight after Normalize, in the same launch.
 // Byte work, no MFMA, no scratch.  Every table entry is clamped to the image before it is used as an index.
 #include "common.h"
 
 namespace rfn {
 
 constexpr int kResTH = 16, kResTW = 64;      // output tile of a workgroup (4 waves: a wave per row, a lane per column)
-constexpr int kResKmax = 129;                // taps per output pixel the entry points accept: ceil(scale) * 2 + 1, scale <= 64 (the
-                                             // vertical footprint of a ONE-row tile, 2 * 64 + 3 rows of 256 bytes, still fits LDS)
+constexpr int kResKmax = 129;                // taps per output pixel the entry points accept: ceil(support * scale) * 2 + 1 with
+                                             // support * scale <= 64 (the vertical footprint of a ONE-row tile, 2 * 64 + 3 rows of
+                                             // 256 bytes, still fits LDS): scale <= 64 for bilinear, <= 64 / 3 for Lanczos
 constexpr size_t kResLds = 64 * 1024;        // LDS a workgroup may ask for without an opt-in
 constexpr int kResBits = 22;                 // Pillow's PRECISION_BITS for 8-bit pixels
 
@@ -28,12 +34,22 @@ template <int MODE>
 __global__ __launch_bounds__(256) void resize_kernel(const unsigned char* __restrict__ img, int H, int W,
                                                      const int2* __restrict__ bx, const int* __restrict__ cx, int kx,
                                                      const int2* __restrict__ by, const int* __restrict__ cy, int ky, int top, int left,
-                                                     int h, int w, int flip, int tile_h, int lds_rows, float m0, float m1, float m2, float s0,
-                                                     float s1, float s2, float* __restrict__ out_f, unsigned char* __restrict__ out_b) {
+                                                     int h, int w, int Hf, int Wf, int flip, int tile_h, int lds_rows, float m0, float m1,
+                                                     float m2, float s0, float s1, float s2, float* __restrict__ out_f,
+                                                     unsigned char* __restrict__ out_b) {
   extern __shared__ __attribute__((aligned(16))) unsigned int tile[];   // [lds_rows][kResTW]: byte c of a dword = channel c
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int x0 = blockIdx.x * kResTW, y0 = blockIdx.y * tile_h;
-  const int tw = min(kResTW, w - x0), th = min(tile_h, h - y0);
+  const int tw = min(kResTW, w - x0), th = min(tile_h, h - y0);       // the tile's part of the crop (<= 0: padding alone)
+  const int pw = min(kResTW, Wf - x0), ph = min(tile_h, Hf - y0);     // the tile's part of the output (MODE 1: the same)
+  const size_t plane = (size_t)Hf * Wf;
+  if (MODE == 0 && (tw <= 0 || th <= 0)) {             // (uniform over the workgroup: nobody waits at the barrier below)
+    if (lane < pw)
+      for (int y = wave; y < ph; y += 4)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out_f[c * plane + (size_t)(y0 + y) * Wf + x0 + lane] = 0.0f;
+    return;
+  }
   const int rc0 = left + (flip ? w - x0 - tw : x0);   // first RESIZED column of the tile (mirrored or not, the columns are contiguous)
   const int2 bfirst = by[top + y0], blast = by[top + y0 + th - 1];
   const int r0 = bfirst.x;                             // the tables are monotonic: rows [r0, last first tap + its count)
@@ -56,10 +72,15 @@ __global__ __launch_bounds__(256) void resize_kernel(const unsigned char* __rest
   }
   __syncthreads();
 
-  if (lane >= tw) return;
+  if (lane >= pw) return;
   const int x = x0 + lane;
   const int j = flip ? tw - 1 - lane : lane;           // column of the tile that output column x shows
-  for (int y = wave; y < th; y += 4) {                 // vertical pass: (first tap, count, coefficients) are wave-uniform
+  for (int y = wave; y < ph; y += 4) {                 // vertical pass: (first tap, count, coefficients) are wave-uniform
+    const size_t o = (size_t)(y0 + y) * Wf + x;
+    if (y >= th || lane >= tw) {                       // right of / below the crop (MODE 0 with Hf > h or Wf > w only)
+      if (MODE == 0) out_f[o] = out_f[plane + o] = out_f[2 * plane + o] = 0.0f;
+      continue;
+    }
     const int ry = top + y0 + y;
     const int2 b = by[ry];
     const int* __restrict__ k = cy + (size_t)ry * ky;
@@ -71,7 +92,6 @@ __global__ __launch_bounds__(256) void resize_kernel(const unsigned char* __rest
       a0 += (int)(p & 255u) * c, a1 += (int)((p >> 8) & 255u) * c, a2 += (int)((p >> 16) & 255u) * c;
     }
     const unsigned u[3] = {clip8(a0), clip8(a1), clip8(a2)};
-    const size_t o = (size_t)(y0 + y) * w + x, plane = (size_t)h * w;
     if (MODE == 0) {
       const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
 #pragma unroll
@@ -96,21 +116,41 @@ __global__ __launch_bounds__(256) void resize_nearest_kernel(const unsigned char
 // taps per output pixel of Pillow's bilinear filter from `in` to `out` pixels: ceil(max(in / out, 1)) * 2 + 1
 static inline int taps(int in, int out) { return (in > out ? cdiv(in, out) : 1) * 2 + 1; }
 
-static int launch_resize(int mode, const char* who, const void* image, int H, int W, int Hd, int Wd, const int* bounds_x,
+constexpr int kResBilinear = 0, kResLanczos = 1;     // the `filter` argument of the entry points that take one
+static inline double filter_support(int filter) { return filter == kResLanczos ? 3.0 : 1.0; }
+// ... of filter `filter`: ceil(support * max(in / out, 1)) * 2 + 1, in double as precompute_coeffs forms it
+static inline int taps(int in, int out, int filter) {
+  if (filter == kResBilinear) return taps(in, out);
+  const double scale = (double)in / out;
+  return (int)ceil(filter_support(filter) * (scale > 1.0 ? scale : 1.0)) * 2 + 1;
+}
+
+static int launch_resize(int mode, int filter, const char* who, const void* image, int H, int W, int Hd, int Wd, const int* bounds_x,
                          const int* coef_x, int kmax_x, const int* bounds_y, const int* coef_y, int kmax_y, int top, int left, int h,
-                         int w, int flip, const float* m, const float* s, float* out_f, unsigned char* out_b, hipStream_t st) {
+                         int w, int Hf, int Wf, int flip, const float* m, const float* s, float* out_f, unsigned char* out_b,
+                         hipStream_t st) {
   RFN_REQUIRE(image && bounds_x && coef_x && bounds_y && coef_y && (out_f || out_b), "%s: null pointer", who);
   RFN_REQUIRE(H > 0 && W > 0 && Hd > 0 && Wd > 0, "%s: sizes must be positive (%d x %d -> %d x %d)", who, H, W, Hd, Wd);
-  RFN_REQUIRE(taps(W, Wd) <= kResKmax && taps(H, Hd) <= kResKmax,
-              "%s: %d x %d -> %d x %d needs %d x %d taps per pixel, the kernel is built for %d (down-scaling by 64 at the most)", who,
-              H, W, Hd, Wd, taps(H, Hd), taps(W, Wd), kResKmax);
-  RFN_REQUIRE(kmax_x == taps(W, Wd) && kmax_y == taps(H, Hd), "%s: tables of %d x %d taps, %d -> %d and %d -> %d pixels take %d x %d",
-              who, kmax_y, kmax_x, H, Hd, W, Wd, taps(H, Hd), taps(W, Wd));
+  RFN_REQUIRE(filter == kResBilinear || filter == kResLanczos, "%s: filter %d (0 = bilinear, 1 = lanczos)", who, filter);
+  const int tx = taps(W, Wd, filter), ty = taps(H, Hd, filter);
+  const char* fname = filter == kResLanczos ? "lanczos" : "bilinear";
+  if (filter == kResBilinear)
+    RFN_REQUIRE(tx <= kResKmax && ty <= kResKmax,
+                "%s: %d x %d -> %d x %d needs %d x %d taps per pixel, the kernel is built for %d (down-scaling by 64 at the most)", who,
+                H, W, Hd, Wd, ty, tx, kResKmax);
+  else
+    RFN_REQUIRE(tx <= kResKmax && ty <= kResKmax,
+                "%s: %d x %d -> %d x %d with the %s filter needs %d x %d taps per pixel, the kernel is built for %d (%s: down-scaling "
+                "by 64 / 3 at the most)", who, H, W, Hd, Wd, fname, ty, tx, kResKmax, fname);
+  RFN_REQUIRE(kmax_x == tx && kmax_y == ty, "%s: tables of %d x %d taps, %d -> %d and %d -> %d pixels take %d x %d (%s)", who, kmax_y,
+              kmax_x, H, Hd, W, Wd, ty, tx, fname);
   RFN_REQUIRE(top >= 0 && left >= 0 && h > 0 && w > 0 && top + h <= Hd && left + w <= Wd && h <= 65535,
               "%s: crop (%d, %d, %d, %d) outside the %d x %d resized image", who, top, left, h, w, Hd, Wd);
+  RFN_REQUIRE(Hf >= h && Wf >= w && Hf <= 65535 && (mode == 0 || (Hf == h && Wf == w)),
+              "%s: output %d x %d smaller than the %d x %d crop (or larger than 65535 rows)", who, Hf, Wf, h, w);
   // source rows under tile_h output rows: (tile_h - 1) * scale between the first and the last centre, the support on either side;
-  // the tile loses rows until they fit (scale <= 64: a one-row tile does)
-  const double scale = (double)H / Hd, support = scale > 1.0 ? scale : 1.0;
+  // the tile loses rows until they fit (support <= 64: a one-row tile does)
+  const double scale = (double)H / Hd, support = filter_support(filter) * (scale > 1.0 ? scale : 1.0);
   int tile_h = kResTH, lds_rows = 0;
   size_t lds = 0;
   for (;; tile_h /= 2) {
@@ -119,14 +159,14 @@ static int launch_resize(int mode, const char* who, const void* image, int H, in
     if (lds <= kResLds || tile_h == 1) break;
   }
   RFN_REQUIRE(lds <= kResLds, "%s: %zu bytes of LDS", who, lds);
-  const dim3 grid((unsigned)cdiv(w, kResTW), (unsigned)cdiv(h, tile_h)), block(256);
+  const dim3 grid((unsigned)cdiv(Wf, kResTW), (unsigned)cdiv(Hf, tile_h)), block(256);
   if (mode == 0)
     hipLaunchKernelGGL(resize_kernel<0>, grid, block, lds, st, (const unsigned char*)image, H, W, (const int2*)bounds_x, coef_x, kmax_x,
-                       (const int2*)bounds_y, coef_y, kmax_y, top, left, h, w, flip, tile_h, lds_rows, m[0], m[1], m[2], s[0], s[1], s[2], out_f,
+                       (const int2*)bounds_y, coef_y, kmax_y, top, left, h, w, Hf, Wf, flip, tile_h, lds_rows, m[0], m[1], m[2], s[0], s[1], s[2], out_f,
                        out_b);
   else
     hipLaunchKernelGGL(resize_kernel<1>, grid, block, lds, st, (const unsigned char*)image, H, W, (const int2*)bounds_x, coef_x, kmax_x,
-                       (const int2*)bounds_y, coef_y, kmax_y, top, left, h, w, flip, tile_h, lds_rows, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, out_f, out_b);
+                       (const int2*)bounds_y, coef_y, kmax_y, top, left, h, w, Hf, Wf, flip, tile_h, lds_rows, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, out_f, out_b);
   return check_launch("resize_kernel");
 }
 
@@ -139,16 +179,35 @@ int rfn_resize_crop_flip_norm_u8(const void* image_hwc, int H, int W, int Hd, in
                                  const float* mean3, const float* std3, float* out_image, rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(mean3 && std3 && out_image, "rfn_resize_crop_flip_norm_u8: null pointer");
-  return launch_resize(0, "rfn_resize_crop_flip_norm_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x, bounds_y, coef_y, kmax_y,
-                       top, left, h, w, flip ? 1 : 0, mean3, std3, out_image, nullptr, (hipStream_t)stream);
+  return launch_resize(0, kResBilinear, "rfn_resize_crop_flip_norm_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x, bounds_y,
+                       coef_y, kmax_y, top, left, h, w, h, w, flip ? 1 : 0, mean3, std3, out_image, nullptr, (hipStream_t)stream);
+}
+
+int rfn_resize_filter_crop_flip_norm_pad_u8(const void* image_hwc, int H, int W, int Hd, int Wd, int filter, const int* bounds_x,
+                                            const int* coef_x, int kmax_x, const int* bounds_y, const int* coef_y, int kmax_y, int top,
+                                            int left, int h, int w, int flip, const float* mean3, const float* std3, float* out_image,
+                                            int Hf, int Wf, rfn_stream_t stream) {
+  using namespace rfn;
+  RFN_REQUIRE(mean3 && std3 && out_image, "rfn_resize_filter_crop_flip_norm_pad_u8: null pointer");
+  return launch_resize(0, filter, "rfn_resize_filter_crop_flip_norm_pad_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x,
+                       bounds_y, coef_y, kmax_y, top, left, h, w, Hf, Wf, flip ? 1 : 0, mean3, std3, out_image, nullptr,
+                       (hipStream_t)stream);
+}
+
+int rfn_resize_filter_u8(const void* image_hwc, int H, int W, int Hd, int Wd, int filter, const int* bounds_x, const int* coef_x,
+                         int kmax_x, const int* bounds_y, const int* coef_y, int kmax_y, void* out_chw, rfn_stream_t stream) {
+  using namespace rfn;
+  RFN_REQUIRE(out_chw, "rfn_resize_filter_u8: null pointer");
+  return launch_resize(1, filter, "rfn_resize_filter_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x, bounds_y, coef_y, kmax_y,
+                       0, 0, Hd, Wd, Hd, Wd, 0, nullptr, nullptr, nullptr, (unsigned char*)out_chw, (hipStream_t)stream);
 }
 
 int rfn_resize_u8(const void* image_hwc, int H, int W, int Hd, int Wd, const int* bounds_x, const int* coef_x, int kmax_x,
                   const int* bounds_y, const int* coef_y, int kmax_y, void* out_chw, rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(out_chw, "rfn_resize_u8: null pointer");
-  return launch_resize(1, "rfn_resize_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x, bounds_y, coef_y, kmax_y, 0, 0, Hd, Wd, 0,
-                       nullptr, nullptr, nullptr, (unsigned char*)out_chw, (hipStream_t)stream);
+  return launch_resize(1, kResBilinear, "rfn_resize_u8", image_hwc, H, W, Hd, Wd, bounds_x, coef_x, kmax_x, bounds_y, coef_y, kmax_y, 0,
+                       0, Hd, Wd, Hd, Wd, 0, nullptr, nullptr, nullptr, (unsigned char*)out_chw, (hipStream_t)stream);
 }
 
 int rfn_resize_nearest_u8(const void* label, int H, int W, int Hd, int Wd, const int* ytab, const int* xtab, void* out,

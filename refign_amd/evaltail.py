@@ -9,7 +9,11 @@ image-sized sum and count tensors and the host synchronisation of slide_inferenc
 the host from the box list).  One difference: under 16-bit autocast forward() rounds every up-sampled crop to 16 bits before
 averaging; the kernel averages the fp32 samples.
 
-`RFN_EVAL_FUSED=0` keeps Trainer.validate / test / predict on validation_step / test_step / predict_step."""
+The matcher (AlignmentModel) has a fused step of its own: after its forward, SparseEPE.update is one kernel per batch
+(csrc/sparseepe.hip through refign_amd/sparse_epe.py) instead of a hundred-odd small launches and a host synchronisation per
+sample; _matcher_eval_step lists its conditions.
+
+`RFN_EVAL_FUSED=0` keeps Trainer.validate / test / predict on validation_step / test_step / predict_step, for both models."""
 import ctypes
 import os
 
@@ -97,12 +101,45 @@ def _model_ok(model, x):
         getattr(getattr(model, "head", None), "num_classes", MAX_CLASSES + 1) <= MAX_CLASSES
 
 
+def _matcher_eval_step(model, metrics, batch, src_name):
+    """eval_step for an AlignmentModel: its forward as alignment_model._eval_step runs it, then SparseEPE.update as ONE kernel
+    (refign_amd/sparse_epe.py) whose rows every selected metric adds.  -> False when a condition does not hold: RFN_EVAL_FUSED=0;
+    images or points not on the device; the points not `batch size` (n, 2) fp32 tensors with n <= 8192 (and a batch of at most
+    64); a selected metric that is not exactly a SparseEPE; no metric selected."""
+    from . import sparse_epe
+    from .metrics import SparseEPE
+    img, ref = batch.get('image'), batch.get('image_ref')
+    if not enabled() or not all(torch.is_tensor(t) and t.is_cuda and t.dim() == 4 for t in (img, ref)) or ref.device != img.device:
+        return False
+    B, dev = img.shape[0], img.device
+    pts_ref, pts = batch.get('corr_pts_ref'), batch.get('corr_pts')
+    if B > sparse_epe.MAX_BATCH or not (sparse_epe.points_ok(pts_ref, B, dev) and sparse_epe.points_ok(pts, B, dev)) or \
+            any(a.shape[0] != b.shape[0] for a, b in zip(pts_ref, pts)):
+        return False
+    chosen = [m for k, m in metrics.items() if src_name in k]
+    if not chosen or any(type(m) is not SparseEPE for m in chosen):
+        return False
+    flow, uncert = model.forward(img, ref)                 # (the same call, hence the same bits, as _eval_step's)
+    if tuple(flow.shape[-2:]) != tuple(ref.shape[-2:]):
+        raise AssertionError("AlignmentModel.forward: the flow is not at the reference image's resolution")
+    if uncert is None and any(m.uncertainty_estimation for m in chosen):
+        raise RuntimeError("SparseEPE(uncertainty_estimation=True) on a matcher whose head estimates no uncertainty")
+    rows = sparse_epe.sparse_epe_rows(flow.float(), pts_ref, pts, None if uncert is None else uncert.float())
+    for m in chosen:
+        m.add_rows(rows)
+    return True
+
+
 def eval_step(model, metrics, batch, src_name):
     """The fused validation / test step: one kernel call, its count matrix added to every metric of this dataset.  -> True when
     it ran; False when a condition does not hold (RFN_EVAL_FUSED=0; not a segmentation model with crop_logits; tensors not on
     the device; more than 32 classes; label size != image size; a selected metric that is not an IoU over the head's classes
-    with one common ignore_index; no metric selected) -- the caller then runs the model's own step."""
+    with one common ignore_index; no metric selected) -- the caller then runs the model's own step.  An AlignmentModel takes
+    the matcher's fused step (_matcher_eval_step: one sparse-EPE kernel per batch) under its own conditions."""
+    from .alignment_model import AlignmentModel
     from .metrics import IoU
+    if isinstance(model, AlignmentModel):
+        return _matcher_eval_step(model, metrics, batch, src_name)
     x, y = batch.get('image'), batch.get('semantic')
     if not _model_ok(model, x) or not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.int64 or \
             tuple(y.shape) != (x.shape[0], *x.shape[-2:]):

@@ -165,6 +165,27 @@ class SparseEPE(nn.Module):
 
     __call__ = update
 
+    @torch.no_grad()
+    def add_rows(self, rows):
+        """Add per-sample rows made elsewhere -- refign_amd/sparse_epe.py computes them on the device in one kernel -- to the
+        state: (B, 8) fp64, columns (mean EPE, PCK_1, PCK_3, PCK_5, PCK_10 counts, AUSE, n_valid, sample counted 0 / 1), a zero
+        row for a sample without a valid correspondence.  Equals update() on the tensors behind them; one fixed-order column sum,
+        no host synchronisation.  The counterpart of IoU.add_confusion."""
+        if rows.dim() != 2 or rows.shape[1] != 8 or rows.dtype != torch.float64:
+            raise ValueError(f"SparseEPE.add_rows: a (B, 8) float64 tensor expected, got {tuple(rows.shape)} {rows.dtype}")
+        if self.AEPE.device != rows.device:
+            self.to(rows.device)
+        total = rows.sum(0)
+        self.AEPE += total[0]
+        self.PCK_1 += total[1]
+        self.PCK_3 += total[2]
+        self.PCK_5 += total[3]
+        self.PCK_10 += total[4]
+        if self.uncertainty_estimation:
+            self.AUSE_AEPE += total[5]
+        self.nbr_valid_corr += total[6].to(torch.long)
+        self.nbr_samples += total[7].to(torch.long)
+
     @staticmethod
     def compute_aucs(gt, pred, uncert, intervals=50):
         epe = torch.linalg.norm(gt - pred, ord=2, dim=1)

@@ -11,7 +11,13 @@ restated exactly: the tables are made HERE on the host, in double as Pillow make
                                datastep.crop_flip_normalize would give, in one kernel that reads only the crop's footprint;
   resize_u8 / resize_nearest_u8  Pillow's pixels themselves (image -> (3, Hd, Wd) uint8, label map -> (Hd, Wd) uint8).
 `resize_reference` / `resize_nearest_reference` are numpy restatements: the documentation of the arithmetic and the tests' operand
-(tests/test_resample_*.py against tests/golden/resample_pillow.npz, made with Pillow alone)."""
+(tests/test_resample_*.py against tests/golden/resample_pillow.npz, made with Pillow alone).
+
+The matcher's side (datasets/megadepth.py, robotcarmatching.py; the `test:` sections of megadepth/uawarpc_*.yaml) resizes with
+Pillow's LANCZOS filter and ends in transforms.PadBottomRight: `filter_tables(in, out, "lanczos")` are the same tables for that
+filter (negative taps: every row is checked against the int32 accumulator), `filter="lanczos"` / `pad_to=` select them in the
+device functions, `lanczos_reference` restates the pixels (tests/test_lanczos_*.py against tests/golden/lanczos_pillow.npz), and
+EvalIngest scales the sparse correspondences the way the reference does (`scale_points`)."""
 import math
 
 import numpy as np
@@ -25,16 +31,42 @@ PRECISION_BITS = 32 - 8 - 2      # Resample.c: 8 bits of pixel, 2 spare bits for
 
 
 # ------------------------------------------------------------------ host tables
-def bilinear_tables(in_size, out_size):
-    """Pillow's `precompute_coeffs` (bilinear: support 1) + `normalize_coeffs_8bpc` for one axis ->
-    (xmin[out] int32, n[out] int32, coef[out, kmax] int32): output pixel xx = (sum_k in[xmin[xx] + k] * coef[xx, k] + 2^21) >> 22
-    over k < n[xx]; coef beyond n is 0.  kmax = ceil(support) * 2 + 1 with support = max(in / out, 1)."""
+def _bilinear_filter(x):
+    return max(1.0 - abs(x), 0.0)
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos_filter(x):
+    """Resample.c `lanczos_filter`: the truncated sinc, a = 3, on the HALF-OPEN interval [-3, 3)"""
+    return _sinc(x) * _sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
+
+
+FILTERS = {"bilinear": (_bilinear_filter, 1.0), "lanczos": (_lanczos_filter, 3.0)}     # name -> (kernel, support)
+FILTER_CODE = {"bilinear": 0, "lanczos": 1}                                            # the C ABI's `filter` argument
+
+
+def check_accumulator(coef):
+    """every row of a coefficient table must keep a pass inside int32: 255 * sum |coef| + 2^21 < 2^31.  Automatic for a
+    non-negative filter (the row sums to 2^22); with Lanczos' negative lobes it is a condition, checked when a table is built."""
+    worst = int(np.abs(np.asarray(coef, dtype=np.int64)).sum(-1).max()) if np.size(coef) else 0
+    if 255 * worst + (1 << (PRECISION_BITS - 1)) >= 1 << 31:
+        raise ValueError(f"resample tables: a row with sum |coef| = {worst} overflows the int32 accumulator "
+                         f"(255 * sum |coef| + 2^{PRECISION_BITS - 1} must stay below 2^31)")
+
+
+def _tables(in_size, out_size, kernel, filter_support, who):
     in_size, out_size = int(in_size), int(out_size)
     if in_size < 1 or out_size < 1:
-        raise ValueError("bilinear_tables: sizes must be positive")
+        raise ValueError(f"{who}: sizes must be positive")
     scale = float(in_size) / out_size
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
+    support = filter_support * filterscale
     kmax = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / filterscale
     xmin = np.zeros(out_size, np.int32)
@@ -46,7 +78,7 @@ def bilinear_tables(in_size, out_size):
         lo = max(int(center - support + 0.5), 0)                       # C's (int): truncation (the operands are >= 0 after max)
         hi = min(int(center + support + 0.5), in_size)
         cnt = hi - lo
-        w = [max(1.0 - abs((x + lo - center + 0.5) * ss), 0.0) for x in range(cnt)]
+        w = [kernel((x + lo - center + 0.5) * ss) for x in range(cnt)]
         ww = 0.0
         for v in w:                                                    # left to right, in double
             ww += v
@@ -54,7 +86,25 @@ def bilinear_tables(in_size, out_size):
             k = w[x] / ww if ww != 0.0 else w[x]
             coef[xx, x] = int(-0.5 + k * one) if k < 0 else int(0.5 + k * one)   # half away from zero
         xmin[xx], n[xx] = lo, cnt
+    check_accumulator(coef)
     return xmin, n, coef
+
+
+def bilinear_tables(in_size, out_size):
+    """Pillow's `precompute_coeffs` (bilinear: support 1) + `normalize_coeffs_8bpc` for one axis ->
+    (xmin[out] int32, n[out] int32, coef[out, kmax] int32): output pixel xx = (sum_k in[xmin[xx] + k] * coef[xx, k] + 2^21) >> 22
+    over k < n[xx]; coef beyond n is 0.  kmax = ceil(support) * 2 + 1 with support = max(in / out, 1)."""
+    return _tables(in_size, out_size, _bilinear_filter, 1.0, "bilinear_tables")
+
+
+def filter_tables(in_size, out_size, filter="bilinear"):
+    """bilinear_tables for any filter of FILTERS: "bilinear" (exactly bilinear_tables) or "lanczos" (Pillow's LANCZOS:
+    sinc(x) sinc(x / 3) on [-3, 3), support 3, negative taps).  kmax = ceil(support * max(in / out, 1)) * 2 + 1.  Raises
+    ValueError when a row could overflow the int32 accumulation of a pass (check_accumulator)."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter_tables: filter {filter!r} (one of {sorted(FILTERS)})")
+    kernel, support = FILTERS[filter]
+    return _tables(in_size, out_size, kernel, support, "filter_tables")
 
 
 def nearest_table(in_size, out_size):
@@ -95,9 +145,9 @@ def target_size(h, w, size, only_if_larger=False):
 
 
 # ------------------------------------------------------------------ numpy restatements (tests, documentation)
-def _pass_reference(img, axis, out_size):
+def _pass_reference(img, axis, out_size, filter="bilinear"):
     """one 8-bit pass along `axis` of an (H, W, C) uint8 array: uint8 out, rounded and clipped as Pillow does between the passes"""
-    xmin, n, coef = bilinear_tables(img.shape[axis], out_size)
+    xmin, n, coef = filter_tables(img.shape[axis], out_size, filter)
     src = np.moveaxis(img, axis, 0).astype(np.int64)
     out = np.empty((out_size,) + src.shape[1:], np.int64)
     for xx in range(out_size):
@@ -106,18 +156,42 @@ def _pass_reference(img, axis, out_size):
     return np.moveaxis(np.clip(out, 0, 255).astype(np.uint8), 0, axis)
 
 
-def resize_reference(img_hwc_u8, size):
-    """`Image.fromarray(img).resize((w, h), BILINEAR)` of an (H, W, C) uint8 array -> (h, w, C) uint8: the horizontal pass to a
-    uint8 intermediate, then the vertical one; a pass is skipped when its axis keeps its size."""
+def resize_reference(img_hwc_u8, size, filter="bilinear"):
+    """`Image.fromarray(img).resize((w, h), BILINEAR)` (or LANCZOS: filter="lanczos") of an (H, W, C) uint8 array -> (h, w, C)
+    uint8: the horizontal pass to a uint8 intermediate, then the vertical one; a pass is skipped when its axis keeps its size.
+    With Lanczos the sums overshoot [0, 255] near edges of the image content: the clip of each pass is part of the result."""
     img = np.ascontiguousarray(img_hwc_u8)
     if img.dtype != np.uint8 or img.ndim != 3:
         raise ValueError("resize_reference: an (H, W, C) uint8 array is required")
     h, w = int(size[0]), int(size[1])
     if img.shape[1] != w:
-        img = _pass_reference(img, 1, w)
+        img = _pass_reference(img, 1, w, filter)
     if img.shape[0] != h:
-        img = _pass_reference(img, 0, h)
+        img = _pass_reference(img, 0, h, filter)
     return np.ascontiguousarray(img)
+
+
+def lanczos_reference(img_hwc_u8, size):
+    """`Image.fromarray(img).resize((w, h), LANCZOS)` -> (h, w, C) uint8"""
+    return resize_reference(img_hwc_u8, size, "lanczos")
+
+
+def pad_bottom_right_reference(chw, size, fill=0.0):
+    """transforms.PadBottomRight.pad of a (C, h, w) array to (C, size[0], size[1])"""
+    out = np.full((chw.shape[0], int(size[0]), int(size[1])), fill, dtype=chw.dtype)
+    out[:, :chw.shape[1], :chw.shape[2]] = chw
+    return out
+
+
+def scale_points(pts, h, w, new_h, new_w):
+    """what a resize of an (h, w) image to (new_h, new_w) does to its (n, 2) fp32 (x, y) points, as the readers
+    (datasets/megadepth.py:378-395) and transforms.Resize (transforms.py:163-198) do it: the factor is formed in double and
+    multiplies the fp32 coordinates as an fp32 number.  -> a new host tensor"""
+    pts = torch.as_tensor(pts).detach().cpu().to(torch.float32).clone()
+    x_scale, y_scale = new_w / float(w), new_h / float(h)
+    pts[:, 0] = x_scale * pts[:, 0]
+    pts[:, 1] = y_scale * pts[:, 1]
+    return pts
 
 
 def resize_nearest_reference(lbl_u8, size):
@@ -136,13 +210,13 @@ _TABLES = {}
 
 
 def _device_tables(kind, in_size, out_size, device):
-    """cached per (kind, in, out, device).  bilinear: (bounds int32 [out, 2] = (xmin, n), coef int32 [out, kmax], kmax);
+    """cached per (kind, in, out, device).  bilinear / lanczos: (bounds int32 [out, 2] = (xmin, n), coef int32 [out, kmax], kmax);
     nearest: int32 [out]"""
     key = (kind, int(in_size), int(out_size), device)
     t = _TABLES.get(key)
     if t is None:
-        if kind == "bilinear":
-            xmin, n, coef = bilinear_tables(in_size, out_size)
+        if kind in FILTERS:
+            xmin, n, coef = filter_tables(in_size, out_size, kind)
             t = (torch.from_numpy(np.stack([xmin, n], 1).copy()).to(device), torch.from_numpy(coef).to(device), coef.shape[1])
         else:
             t = torch.from_numpy(nearest_table(in_size, out_size)).to(device)
@@ -159,16 +233,28 @@ def _check_image(image, who):
 
 
 # ------------------------------------------------------------------ device functions
-def resize_u8(image_hwc_u8, size):
-    """Pillow's bilinear resize of a decoded (H, W, 3) uint8 DEVICE image -> (3, h, w) uint8 (what ToTensor would leave)"""
+def _filter(filter, who):
+    if filter not in FILTERS:
+        raise ValueError(f"{who}: filter {filter!r} (one of {sorted(FILTERS)})")
+    return filter
+
+
+def resize_u8(image_hwc_u8, size, filter="bilinear"):
+    """Pillow's bilinear (or, filter="lanczos", LANCZOS) resize of a decoded (H, W, 3) uint8 DEVICE image -> (3, h, w) uint8
+    (what ToTensor would leave)"""
     _check_image(image_hwc_u8, "resize_u8")
+    _filter(filter, "resize_u8")
     H, W, _ = image_hwc_u8.shape
     Hd, Wd = int(size[0]), int(size[1])
     dev = image_hwc_u8.device
-    bx, cx, kx = _device_tables("bilinear", W, Wd, dev)
-    by, cy, ky = _device_tables("bilinear", H, Hd, dev)
+    bx, cx, kx = _device_tables(filter, W, Wd, dev)
+    by, cy, ky = _device_tables(filter, H, Hd, dev)
     out = torch.empty((3, Hd, Wd), dtype=torch.uint8, device=dev)
-    _lib.call("rfn_resize_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky, ptr(out))
+    if filter == "bilinear":
+        _lib.call("rfn_resize_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky, ptr(out))
+    else:
+        _lib.call("rfn_resize_filter_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, FILTER_CODE[filter], ptr(bx), ptr(cx), kx, ptr(by),
+                  ptr(cy), ky, ptr(out))
     return out
 
 
@@ -187,53 +273,81 @@ def resize_nearest_u8(label_u8, size):
     return out
 
 
-def resize_crop_flip_normalize(image_hwc_u8, dims, top, left, h, w, flip, out_image=None, mean=IMNET_MEAN, std=IMNET_STD):
+def resize_crop_flip_normalize(image_hwc_u8, dims, top, left, h, w, flip, out_image=None, mean=IMNET_MEAN, std=IMNET_STD,
+                               filter="bilinear", pad_to=None):
     """load-time resize to `dims` = (Hd, Wd) + crop (top, left, h, w) of the RESIZED image + RandomHorizontalFlip +
     ConvertImageDtype + Normalize of a decoded (H, W, 3) uint8 DEVICE image in one kernel, written into `out_image` (3, h, w)
-    fp32 (a slot of a batch tensor) or a fresh tensor: bit for bit datastep.crop_flip_normalize of Pillow's resized image."""
+    fp32 (a slot of a batch tensor) or a fresh tensor: bit for bit datastep.crop_flip_normalize of Pillow's resized image.
+    filter: "bilinear" or "lanczos".  pad_to = (Hf, Wf) >= (h, w): the output is (3, Hf, Wf), the crop at its top left and 0.0
+    everywhere else -- transforms.PadBottomRight after Normalize -- written by the same launch."""
     _check_image(image_hwc_u8, "resize_crop_flip_normalize")
+    _filter(filter, "resize_crop_flip_normalize")
     H, W, _ = image_hwc_u8.shape
     Hd, Wd = int(dims[0]), int(dims[1])
     dev = image_hwc_u8.device
+    Hf, Wf = (int(h), int(w)) if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
     if out_image is None:
-        out_image = torch.empty((3, h, w), dtype=torch.float32, device=dev)
-    if not (out_image.dtype == torch.float32 and tuple(out_image.shape) == (3, h, w) and out_image.is_contiguous()):
-        raise RuntimeError("resize_crop_flip_normalize: out_image must be a contiguous (3, h, w) float32 tensor")
-    bx, cx, kx = _device_tables("bilinear", W, Wd, dev)
-    by, cy, ky = _device_tables("bilinear", H, Hd, dev)
+        out_image = torch.empty((3, Hf, Wf), dtype=torch.float32, device=dev)
+    if not (out_image.dtype == torch.float32 and tuple(out_image.shape) == (3, Hf, Wf) and out_image.is_contiguous()):
+        raise RuntimeError("resize_crop_flip_normalize: out_image must be a contiguous (3, h, w) float32 tensor (h, w: pad_to "
+                           "when given)")
+    bx, cx, kx = _device_tables(filter, W, Wd, dev)
+    by, cy, ky = _device_tables(filter, H, Hd, dev)
     m = np.asarray(mean, dtype=np.float32).copy()
     s = np.asarray(std, dtype=np.float32).copy()
-    _lib.call("rfn_resize_crop_flip_norm_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky,
-              int(top), int(left), int(h), int(w), 1 if flip else 0, m.ctypes.data, s.ctypes.data, ptr(out_image))
+    if filter == "bilinear" and pad_to is None:
+        _lib.call("rfn_resize_crop_flip_norm_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, ptr(bx), ptr(cx), kx, ptr(by), ptr(cy), ky,
+                  int(top), int(left), int(h), int(w), 1 if flip else 0, m.ctypes.data, s.ctypes.data, ptr(out_image))
+    else:
+        _lib.call("rfn_resize_filter_crop_flip_norm_pad_u8", dev, ptr(image_hwc_u8), H, W, Hd, Wd, FILTER_CODE[filter], ptr(bx),
+                  ptr(cx), kx, ptr(by), ptr(cy), ky, int(top), int(left), int(h), int(w), 1 if flip else 0, m.ctypes.data,
+                  s.ctypes.data, ptr(out_image), Hf, Wf)
     return out_image
 
 
 class EvalIngest:
     """The val / test / predict pipelines of the reference's configs from decoded files to the tensors Trainer.validate / test /
-    predict take: load-time `dims` (image bilinear, label nearest), an optional transforms.Resize (`resize`: int or (h, w);
-    `img_only`: the label keeps its size, as in refign_*.yaml `test:`), ConvertImageDtype, Normalize.  Two successive resizes are
-    two Pillow resizes with a uint8 image in between (they are NOT merged: the intermediate rounding is part of the result); the
-    last one is fused with the conversion (a whole-image crop, no flip).
-    __call__(image, semantic=None, image_ref=None) -> {"image" (1, 3, h, w) fp32[, "image_ref"][, "semantic" (1, h', w') int64]};
-    images are (H, W, 3) uint8, the label (H, W) uint8, host arrays / tensors (uploaded) or device tensors."""
+    predict take: load-time `dims` (image `dims_interpolation`, label nearest), an optional transforms.Resize (`resize`: int or
+    (h, w) with `interpolation`; `img_only`: the label and the points keep their size, as in refign_*.yaml `test:`),
+    ConvertImageDtype, Normalize, an optional transforms.PadBottomRight (`pad`: "same" = `image` and `image_ref` both at
+    (max h, max w), or a fixed (h, w); the fill is 0 AFTER the normalisation).  Two successive resizes are two Pillow resizes with
+    a uint8 image in between (they are NOT merged: the intermediate rounding is part of the result); the last one is fused with
+    the conversion and the padding (a whole-image crop, no flip).  The filters are "bilinear" (the segmentation data sets) or
+    "lanczos" (the matcher's: MegaDepth / RobotCarMatching readers and `test:` sections).
+    __call__(image, semantic=None, image_ref=None, corr_pts=None, corr_pts_ref=None) -> {"image" (1, 3, h, w) fp32
+    [, "image_ref"][, "semantic" (1, h', w') int64][, "corr_pts" / "corr_pts_ref": [(n, 2) fp32]]}; images are (H, W, 3) uint8,
+    the label (H, W) uint8, host arrays / tensors (uploaded) or device tensors.  The points are (n, 2) fp32 (x, y) of `image`
+    (corr_pts) and of `image_ref` (corr_pts_ref): every resize step scales them by its own image's size change, on the host in
+    fp32 as the reference does (scale_points); padding and normalisation leave them alone; they are uploaded afterwards and come
+    back as one-element lists, the way the reference's my_collate batches them."""
 
-    def __init__(self, dims=None, resize=None, img_only=False, mean=IMNET_MEAN, std=IMNET_STD, only_if_larger=False, device=None):
+    def __init__(self, dims=None, resize=None, img_only=False, mean=IMNET_MEAN, std=IMNET_STD, only_if_larger=False, device=None,
+                 interpolation="bilinear", dims_interpolation="bilinear", pad=None):
         self.device = torch.device(device) if device is not None else None      # None: the input's device, else the current one
         self.dims = None if dims is None else (int(dims[0]), int(dims[1]))
         self.resize, self.img_only, self.only_if_larger = resize, bool(img_only), bool(only_if_larger)
         self.mean, self.std = mean, std
+        self.interpolation = _filter(interpolation, "EvalIngest(interpolation=)")
+        self.dims_interpolation = _filter(dims_interpolation, "EvalIngest(dims_interpolation=)")
+        if not (pad is None or pad == "same" or (isinstance(pad, (tuple, list)) and len(pad) == 2)):
+            raise ValueError(f"EvalIngest: pad must be None, 'same' or (h, w), got {pad!r}")
+        self.pad = pad if pad is None or pad == "same" else (int(pad[0]), int(pad[1]))
 
-    def _sizes(self, h, w):
-        """the chain of sizes an (h, w) input runs through (identity steps dropped)"""
+    def _steps(self, h, w):
+        """the chain of (size, filter, is the Resize) an (h, w) input runs through (identity steps dropped)"""
         chain = []
-        for step in (self.dims, self.resize):
+        for step, filt in ((self.dims, self.dims_interpolation), (self.resize, self.interpolation)):
             if step is None:
                 continue
             nh, nw = target_size(h, w, step, self.only_if_larger) if step is self.resize else step
             if (nh, nw) != (h, w):
-                chain.append((nh, nw))
+                chain.append(((nh, nw), filt, step is self.resize))
                 h, w = nh, nw
         return chain
+
+    def _sizes(self, h, w):
+        """the chain of sizes an (h, w) input runs through (identity steps dropped)"""
+        return [size for size, _, _ in self._steps(h, w)]
 
     def _upload(self, x):
         if isinstance(x, np.ndarray):
@@ -245,14 +359,14 @@ class EvalIngest:
             raise RuntimeError("EvalIngest: a HIP device is required (the product path has no CPU fallback)")
         return x.to(dev, non_blocking=True)
 
-    def image(self, image_hwc_u8):
+    def image(self, image_hwc_u8, pad_to=None):
         x = self._upload(image_hwc_u8)
         _check_image(x, "EvalIngest")
-        chain = self._sizes(x.shape[0], x.shape[1])
-        for size in chain[:-1]:                                         # Pillow's uint8 image in between, channels last again
-            x = resize_u8(x, size).permute(1, 2, 0).contiguous()
-        h, w = chain[-1] if chain else (x.shape[0], x.shape[1])
-        return resize_crop_flip_normalize(x, (h, w), 0, 0, h, w, False, None, self.mean, self.std).unsqueeze(0)
+        chain = self._steps(x.shape[0], x.shape[1])
+        for size, filt, _ in chain[:-1]:                                # Pillow's uint8 image in between, channels last again
+            x = resize_u8(x, size, filt).permute(1, 2, 0).contiguous()
+        (h, w), filt = chain[-1][:2] if chain else ((x.shape[0], x.shape[1]), "bilinear")
+        return resize_crop_flip_normalize(x, (h, w), 0, 0, h, w, False, None, self.mean, self.std, filt, pad_to).unsqueeze(0)
 
     def label(self, label_u8):
         y = self._upload(label_u8)
@@ -265,10 +379,36 @@ class EvalIngest:
                 y = resize_nearest_u8(y, size)
         return y.to(torch.int64).unsqueeze(0)
 
-    def __call__(self, image, semantic=None, image_ref=None):
-        out = {"image": self.image(image)}
+    def points(self, pts, h, w):
+        """(n, 2) fp32 (x, y) points of a decoded (h, w) image through that image's resize steps -> a HOST fp32 tensor"""
+        pts = torch.as_tensor(pts).detach().cpu().to(torch.float32).clone()
+        if pts.dim() != 2 or pts.shape[1] != 2:
+            raise ValueError(f"EvalIngest: points must be (n, 2) (x, y), got {tuple(pts.shape)}")
+        for (nh, nw), _, is_resize in self._steps(h, w):
+            if not (is_resize and self.img_only):
+                pts = scale_points(pts, h, w, nh, nw)
+            h, w = nh, nw
+        return pts
+
+    def final_size(self, h, w):
+        chain = self._sizes(h, w)
+        return chain[-1] if chain else (int(h), int(w))
+
+    def __call__(self, image, semantic=None, image_ref=None, corr_pts=None, corr_pts_ref=None):
+        if corr_pts_ref is not None and image_ref is None:
+            raise ValueError("EvalIngest: corr_pts_ref are points of image_ref, which is missing")
+        pad_to = self.pad
+        if pad_to == "same":
+            sizes = [self.final_size(*x.shape[:2]) for x in (image, image_ref) if x is not None]
+            pad_to = (max(s[0] for s in sizes), max(s[1] for s in sizes))
+        out = {"image": self.image(image, pad_to)}
         if image_ref is not None:
-            out["image_ref"] = self.image(image_ref)
+            out["image_ref"] = self.image(image_ref, pad_to)
         if semantic is not None:
+            if pad_to is not None:
+                raise NotImplementedError("EvalIngest: PadBottomRight of a label map is not built (no config of the reference pads one)")
             out["semantic"] = self.label(semantic)
+        for key, pts, img in (("corr_pts", corr_pts, image), ("corr_pts_ref", corr_pts_ref, image_ref)):
+            if pts is not None:
+                out[key] = [self._upload(self.points(pts, img.shape[0], img.shape[1]))]
         return out
