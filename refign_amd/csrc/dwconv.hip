@@ -168,11 +168,11 @@ __device__ __forceinline__ uint2 mask_raw(const uint2& t, bool ok) { return ok ?
 // result: a thread owns one channel vector for its whole life, so it adds up what it stores (the ROUNDED values: what the
 // statistics pass of csrc/bn.hip would have read back -- 2.65 GB for the teacher's 42 maps, 0.5 ms, per branch), the block
 // folds its pixel lanes in LDS and adds to the fp64 buffer of csrc/bn.hip (sum x, sum x^2, rows).
-// STATS = 2: statistics only, nothing is stored; BNE: the result is BatchNorm(batch statistics from `sums`) + ReLU of the
-// convolution -- the two passes of the gradient-free form (the EMA teacher's decode head): statistics pass, then convolution
-// + normalisation + activation in one pass; 3 tensor passes (read, read, write) instead of the 5 of convolution (read,
-// write), statistics (read), BatchNorm (read, write).  BnEpi: gamma / beta (may be null), eps, relu, and the running buffers
-// the blocks of the first row of the grid update (momentum), as csrc/bn.hip's apply pass does.
+// The gradient-free form (the EMA teacher's decode head) runs as two passes over the INPUT in dwconv3x3_roll_kernel below:
+// statistics only (nothing stored), then convolution + BatchNorm(batch statistics from `sums`) + ReLU; 3 tensor passes (read,
+// read, write) instead of the 5 of convolution (read, write), statistics (read), BatchNorm (read, write).  BnEpi: gamma / beta
+// (may be null), eps, relu, and the running buffers the blocks of the first row of the grid update (momentum), as
+// csrc/bn.hip's apply pass does.
 struct BnEpi {
   const float* gamma;
   const float* beta;
@@ -182,14 +182,15 @@ struct BnEpi {
   int relu;
 };
 
-template <typename T, bool FLIP, bool ACT = false, int STATS = 0, bool BNE = false>
+template <typename T, bool FLIP, bool ACT = false, int STATS = 0>
 __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wgt,
                                                             const float* __restrict__ bias, T* __restrict__ y, int B,
                                                             int H, int W, int C, int dil, int cvb,
                                                             T* __restrict__ ya = nullptr, float xs = 1.f,
                                                             float oq = 1.f, int sliced = 0,
-                                                            double* __restrict__ sums = nullptr, BnEpi bn = BnEpi{},
+                                                            double* __restrict__ sums = nullptr,
                                                             double* __restrict__ spart = nullptr) {
+  static_assert(STATS == 0 || STATS == 1, "the gradient-free forms (statistics only, BatchNorm) are dwconv3x3_roll_kernel's");
   // xs / oq (e4m3 activations only): stored input bytes mean xs * value -- folded into the weights; outputs are stored as
   // value * oq
   constexpr bool F8 = std::is_same<T, f8e4m3>::value;
@@ -227,25 +228,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
   if constexpr (STATS != 0) {
 #pragma unroll
     for (int i = 0; i < V; ++i) st0[i] = st1[i] = 0.f;
-  }
-  float bsc[BNE ? V : 1], bsh[BNE ? V : 1];              // y = relu(conv * bsc + bsh)
-  if constexpr (BNE) {
-    const double cnt = sums[2 * C], inv = 1.0 / cnt;
-    const bool first = sliced ? (blockIdx.x >> 3) == 0 : blockIdx.y == 0;
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const int c = c0 + i;
-      const double m = sums[c] * inv;
-      const float var = (float)fmax(sums[C + c] * inv - m * m, 0.0), mean = (float)m;
-      const float g = bn.gamma != nullptr ? bn.gamma[c] : 1.f, be = bn.beta != nullptr ? bn.beta[c] : 0.f;
-      bsc[i] = rsqrtf(var + bn.eps) * g;
-      bsh[i] = be - mean * bsc[i];
-      if (first && active && threadIdx.x / cvb == 0 && bn.running_mean != nullptr) {
-        const float n = (float)cnt;
-        bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * mean;
-        bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * var * (n / fmaxf(n - 1.f, 1.f));
-      }
-    }
   }
   // weights, bias and accumulators live as adjacent-channel PAIRS: every multiply-add below is one v_pk_fma_f32
   f32x2 wr[9][V2];   // tap-major weights (9, C): one contiguous fp32 vector per tap
@@ -317,16 +299,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
         float o[V];
 #pragma unroll
         for (int i = 0; i < V2; ++i) { o[2 * i] = acc[p][i].x; o[2 * i + 1] = acc[p][i].y; }
-        if constexpr (BNE) {
-          // the statistics were taken of the ROUNDED convolution result (what the unfused path stores and reads back)
-#pragma unroll
-          for (int i = 0; i < V; ++i) {
-            const float r = VecIO<T>::rnd(o[i]);
-            const float z = fmaf(r, bsc[i], bsh[i]);
-            o[i] = (bn.relu && z <= 0.f) ? 0.f : z;
-          }
-        }
-        if (STATS != 2 && (!ACT || y != nullptr)) VecIO<T>::store(y + obase + (size_t)(w0 + p * dil) * C, o);
+        if (!ACT || y != nullptr) VecIO<T>::store(y + obase + (size_t)(w0 + p * dil) * C, o);
         if constexpr (STATS != 0) {
 #pragma unroll
           for (int i = 0; i < V; ++i) {
@@ -361,6 +334,265 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
       if (cvbase + v >= CV) continue;
       float sum = 0.f;
       for (int r = 0; r < pl; ++r) sum += sred[which][r * cvb + v][e];
+      // spart (deterministic form): one row of 2 C partial sums per block row, plain stores; added in row order afterwards
+      if (spart != nullptr) spart[((size_t)(sliced ? blockIdx.x >> 3 : blockIdx.y) * 2 + which) * C + (cvbase + v) * V + e] = (double)sum;
+      else atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+      if (spart != nullptr) sums[2 * C] = (double)B * H * W;
+      else atomicAdd(sums + 2 * C, (double)B * H * W);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Rolling row walk: the body of the gradient-free forms (STATS == 2: statistics only; BNE: convolution + BatchNorm +
+// activation), 16-bit activations.  dwconv3x3_fwd_kernel fetches and converts 3 rows x 6 columns for every quad, so every
+// input row is fetched, converted and edge-masked three times (for the output rows h - d, h, h + d).  Here a thread owns a
+// channel vector and a strip of 4 outputs spaced by the dilation, as there, but walks a SEGMENT of consecutive rows of one
+// residue class of one image (h, h + d, h + 2 d, ...): every row of 6 columns is loaded and converted ONCE and added into
+// the three output rows it belongs to, whose fp32 accumulators stay in registers (the rolling window, kept as three rows of
+// partial sums instead of three rows of inputs: 48 registers instead of 72 + 16); the three roles rotate by renaming (the
+// walk is unrolled by 3, or by 6 with two load buffers), no register moves.  Loads run DEPTH rows ahead of their use.
+//  * 4 channels per thread (8-byte loads; the lanes of a pixel still cover the 128-byte-or-longer run of their slice): with
+//    8 channels the accumulators, 72 weights and the rows in flight do not fit in the 256 registers of 2 waves per SIMD.
+//  * zero padding by ADDRESS: a column outside the image reads the zeroed line `zero` (its row step is 0), a row outside the
+//    image is a row of zeros without loads; the zeros enter the same FMAs the masked loads of the first body entered, and an
+//    output row meets its taps in the same order (bias, then ky = 0, 1, 2, within a row kx = 0, 1, 2), so the convolution
+//    values are bit-equal.
+//  * a segment starts from nothing: its first two rows (k0 - 1, k0) are loaded again, no sum is carried over an image, a
+//    residue class or a segment.
+// Items (image, residue class, segment, strip), strip fastest, are dealt to the pixel lanes of either launch geometry of
+// dwconv3x3_fwd_kernel (grid of channel blocks x lane blocks, or XCD-sliced); `seg` rows per segment: roll_geom().
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ uint4 g_zero_line_dw[1];          // zero-initialised: what a tap left or right of the image reads
+
+constexpr int kRV = 4;                       // channels per thread of the rolling body
+// rows in flight per thread: 2 for bf16 (measured against 1, profiles/dwconv_roll_kbench.txt); fp16, whose conversions need
+// more temporaries, spills with 2
+template <typename T>
+constexpr int kRollDepth = std::is_same<T, _Float16>::value ? 1 : 2;
+
+template <typename T>
+__device__ __forceinline__ f32x2 pair_f32(unsigned w);
+template <>
+__device__ __forceinline__ f32x2 pair_f32<__hip_bfloat16>(unsigned w) {
+  return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+}
+template <>
+__device__ __forceinline__ f32x2 pair_f32<_Float16>(unsigned w) { return f32x2{f16_lo(w), f16_hi(w)}; }
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+template <typename T, int STATS, bool BNE, int DEPTH>
+__global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restrict__ x, const float* __restrict__ wgt,
+                                                             const float* __restrict__ bias, T* __restrict__ y, int B,
+                                                             int H, int W, int C, int dil, int cvb, int seg, int sliced,
+                                                             double* __restrict__ sums, BnEpi bn,
+                                                             double* __restrict__ spart, const void* __restrict__ zero) {
+  static_assert(sizeof(T) == 2 && (STATS == 2) != BNE, "statistics-only or BatchNorm form, 16-bit activations");
+  static_assert(DEPTH == 1 || DEPTH == 2, "the walk is written for one or two rows in flight");
+  constexpr int V = kRV, V2 = V / 2, NC = kPX + 2;
+  const int CV = C / V, WQ = quads_per_row(W, dil);
+  int pl, cv, qfirst, qstride;
+  bool active;
+  if (sliced) {                                          // (the two geometries: dwconv3x3_fwd_kernel)
+    pl = blockDim.x / cvb;
+    active = (int)threadIdx.x < cvb * pl;
+    cv = (blockIdx.x & 7) * cvb + threadIdx.x % cvb;
+    qfirst = (blockIdx.x >> 3) * pl + threadIdx.x / cvb;
+    qstride = (gridDim.x >> 3) * pl;
+  } else {
+    pl = 256 / cvb;
+    cv = blockIdx.x * cvb + threadIdx.x % cvb;
+    active = cv < CV;
+    qfirst = blockIdx.y * pl + threadIdx.x / cvb;
+    qstride = gridDim.y * pl;
+  }
+  if (STATS == 0 && !active) return;
+  if (!active) cv = 0;                                   // (STATS: idle threads stay for the block reduction)
+  const int c0 = cv * V;
+  f32x2 st0[STATS ? V2 : 1], st1[STATS ? V2 : 1];
+  if constexpr (STATS != 0) {
+#pragma unroll
+    for (int i = 0; i < V2; ++i) st0[i] = st1[i] = f32x2{0.f, 0.f};
+  }
+  f32x2 bsc[BNE ? V2 : 1], bsh[BNE ? V2 : 1];            // y = relu(conv * bsc + bsh)
+  if constexpr (BNE) {
+    const double cnt = sums[2 * C], inv = 1.0 / cnt;
+    const bool first = sliced ? (blockIdx.x >> 3) == 0 : blockIdx.y == 0;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const int c = c0 + i;
+      const double m = sums[c] * inv;
+      const float var = (float)fmax(sums[C + c] * inv - m * m, 0.0), mean = (float)m;
+      const float g = bn.gamma != nullptr ? bn.gamma[c] : 1.f, be = bn.beta != nullptr ? bn.beta[c] : 0.f;
+      const float sc = rsqrtf(var + bn.eps) * g, sh = be - mean * sc;
+      if (i & 1) bsc[i / 2].y = sc, bsh[i / 2].y = sh;
+      else bsc[i / 2].x = sc, bsh[i / 2].x = sh;
+      if (first && active && threadIdx.x / cvb == 0 && bn.running_mean != nullptr) {
+        const float n = (float)cnt;
+        bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * mean;
+        bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * var * (n / fmaxf(n - 1.f, 1.f));
+      }
+    }
+  }
+  f32x2 wr[9][V2], bs[V2];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float4 t4 = *reinterpret_cast<const float4*>(wgt + (size_t)k * C + c0);
+    wr[k][0] = f32x2{t4.x, t4.y};
+    wr[k][1] = f32x2{t4.z, t4.w};
+  }
+#pragma unroll
+  for (int i = 0; i < V2; ++i)
+    bs[i] = (bias != nullptr) ? f32x2{bias[c0 + 2 * i], bias[c0 + 2 * i + 1]} : f32x2{0.0f, 0.0f};
+
+  const int Hd = (H + dil - 1) / dil, nseg = (Hd + seg - 1) / seg;
+  const int nitems = active ? B * dil * nseg * WQ : 0;   // (fits: checked at launch)
+  const unsigned rs = (unsigned)((size_t)dil * W * C * sizeof(T));   // one row of a residue class down, in bytes
+  const size_t dc = (size_t)dil * C;                                  // one output of the strip to the right
+  for (int it = qfirst; it < nitems; it += qstride) {
+    const int wq = it % WQ;
+    int t = it / WQ;
+    const int sg = t % nseg;
+    t /= nseg;
+    const int r = t % dil, b = t / dil;
+    const int nr = (H - r + dil - 1) / dil;              // rows of residue class r (0 when r >= H)
+    const int k0 = sg * seg, k1 = min(k0 + seg, nr);     // this segment: rows r + k dil, k0 <= k < k1
+    const int w0 = (wq % dil) + (wq / dil) * kPX * dil;
+    if (k0 >= nr || w0 >= W) continue;
+    // column addresses at row k0 - 1 (never dereferenced while that is outside the image) and their row steps
+    typedef const __attribute__((address_space(1))) char* gptr;   // (global: the loads stay global_load through the asm below)
+    gptr ap[NC];
+    unsigned astep[NC];
+    const long row0 = ((long)b * H + r + (long)(k0 - 1) * dil) * W;
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const int xx = w0 + (j - 1) * dil;
+      const bool ok = xx >= 0 && xx < W;
+      ap[j] = ok ? (gptr)x + ((row0 + xx) * C + c0) * (long)sizeof(T) : (gptr)zero;
+      astep[j] = ok ? rs : 0u;
+    }
+    typedef __attribute__((address_space(1))) T* optr;
+    optr yo = BNE ? (optr)y + (((size_t)b * H + r + (size_t)k0 * dil) * W + w0) * C + c0 : nullptr;
+    // row q of the class into a load buffer (zeros unless it is in the image and this segment needs it); one row step down
+    auto fetch = [&](u32x2 (&raw)[NC], int q) __attribute__((always_inline)) {
+      if (q >= 0 && q < nr && q <= k1) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) raw[j] = *(const __attribute__((address_space(1))) u32x2*)ap[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) raw[j] = u32x2{0u, 0u};
+      }
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        ap[j] += astep[j];
+        // opaque to the optimiser: it would otherwise keep ap[j] + n astep[j] for every step n of the unrolled walk (spills)
+        asm("" : "+v"(ap[j]));
+      }
+    };
+    // One arriving row q of the class, converted out of `raw` (which then takes row q + DEPTH), feeds three output rows: it
+    // completes row q - 1 (its ky = 2 taps; A), is the middle row of row q (ky = 1; B) and opens row q + 1 (bias + its
+    // ky = 0 taps; C) -- each output row meets its input rows in the order ky = 0, 1, 2.  Row q - 1 then goes out.
+    auto step = [&](f32x2 (&aa)[kPX][V2], f32x2 (&ab)[kPX][V2], f32x2 (&ac)[kPX][V2], u32x2 (&raw)[NC], int q, auto parts)
+                    __attribute__((always_inline)) {
+      constexpr int PARTS = decltype(parts)::value;      // bit 0: A and the output, bit 1: B, bit 2: C
+      f32x2 row[NC][V2];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        row[j][0] = pair_f32<T>(raw[j].x);
+        row[j][1] = pair_f32<T>(raw[j].y);
+      }
+      fetch(raw, q + DEPTH);
+#pragma unroll
+      for (int j = 0; j < NC; ++j)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int p = j - kx;                          // output pixel fed by column j through tap kx
+          if (p < 0 || p >= kPX) continue;
+#pragma unroll
+          for (int i = 0; i < V2; ++i) {
+            if constexpr ((PARTS & 1) != 0) aa[p][i] = __builtin_elementwise_fma(wr[6 + kx][i], row[j][i], aa[p][i]);
+            if constexpr ((PARTS & 2) != 0) ab[p][i] = __builtin_elementwise_fma(wr[3 + kx][i], row[j][i], ab[p][i]);
+            if constexpr ((PARTS & 4) != 0) ac[p][i] = __builtin_elementwise_fma(wr[kx][i], row[j][i], kx == 0 ? bs[i] : ac[p][i]);
+          }
+        }
+      if constexpr ((PARTS & 1) != 0) {
+#pragma unroll
+        for (int p = 0; p < kPX; ++p)
+          if (w0 + p * dil < W) {
+            // the ROUNDED convolution result (what the unfused path stores and reads back) enters the sums / the BatchNorm
+            unsigned o[V2];
+#pragma unroll
+            for (int i = 0; i < V2; ++i) {
+              const f32x2 rv = pair_f32<T>(VecIO<T>::pack(aa[p][i].x, aa[p][i].y));
+              if constexpr (BNE) {
+                const f32x2 z = __builtin_elementwise_fma(rv, bsc[i], bsh[i]);
+                o[i] = VecIO<T>::pack((bn.relu && z.x <= 0.f) ? 0.f : z.x, (bn.relu && z.y <= 0.f) ? 0.f : z.y);
+              } else {
+                st0[i] += rv;
+                st1[i] = __builtin_elementwise_fma(rv, rv, st1[i]);
+              }
+            }
+            if constexpr (BNE) *(__attribute__((address_space(1))) u32x2*)(yo + p * dc) = u32x2{o[0], o[1]};
+          }
+        if constexpr (BNE) {
+          yo += (size_t)dil * W * C;
+          asm("" : "+v"(yo));
+        }
+      }
+    };
+    f32x2 a0[kPX][V2], a1[kPX][V2], a2[kPX][V2];
+    u32x2 r0[NC], r1[NC];
+    constexpr std::integral_constant<int, 4> open_only{};
+    constexpr std::integral_constant<int, 6> no_output{};
+    constexpr std::integral_constant<int, 7> full{};
+    // (pinned per item: left to itself the optimiser keeps a copy of the weights per unrolled step and spills)
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+      for (int i = 0; i < V2; ++i) asm("" : "+v"(wr[k][i]));
+    // rows k0 - 1 and k0 complete nothing of this segment; then rows k0 + 1 .. k1, the roles rotating by renaming
+    fetch(r0, k0 - 1);
+    if constexpr (DEPTH == 2) {
+      fetch(r1, k0);
+      step(a2, a2, a0, r0, k0 - 1, open_only);
+      step(a2, a0, a1, r1, k0, no_output);
+      for (int q = k0 + 1;;) {
+        step(a0, a1, a2, r0, q, full); if (++q > k1) break;
+        step(a1, a2, a0, r1, q, full); if (++q > k1) break;
+        step(a2, a0, a1, r0, q, full); if (++q > k1) break;
+        step(a0, a1, a2, r1, q, full); if (++q > k1) break;
+        step(a1, a2, a0, r0, q, full); if (++q > k1) break;
+        step(a2, a0, a1, r1, q, full); if (++q > k1) break;
+      }
+    } else {
+      step(a2, a2, a0, r0, k0 - 1, open_only);
+      step(a2, a0, a1, r0, k0, no_output);
+      for (int q = k0 + 1;;) {
+        step(a0, a1, a2, r0, q, full); if (++q > k1) break;
+        step(a1, a2, a0, r0, q, full); if (++q > k1) break;
+        step(a2, a0, a1, r0, q, full); if (++q > k1) break;
+      }
+    }
+  }
+  if constexpr (STATS != 0) {
+    __shared__ float sred[2][256][V + 1];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const f32x2 a0 = st0[i / 2], a1 = st1[i / 2];
+      sred[0][threadIdx.x][i] = active ? ((i & 1) ? a0.y : a0.x) : 0.f;
+      sred[1][threadIdx.x][i] = active ? ((i & 1) ? a1.y : a1.x) : 0.f;
+    }
+    __syncthreads();
+    // thread (which, channel vector of the block, element): fold the pixel lanes, one fp64 atomic per channel and block
+    const int cvbase = sliced ? (blockIdx.x & 7) * cvb : blockIdx.x * cvb;
+    for (int idx = threadIdx.x; idx < 2 * cvb * V; idx += blockDim.x) {
+      const int which = idx / (cvb * V), rem = idx % (cvb * V), v = rem / V, e = rem % V;
+      if (cvbase + v >= CV) continue;
+      float sum = 0.f;
+      for (int q = 0; q < pl; ++q) sum += sred[which][q * cvb + v][e];
       // spart (deterministic form): one row of 2 C partial sums per block row, plain stores; added in row order afterwards
       if (spart != nullptr) spart[((size_t)(sliced ? blockIdx.x >> 3 : blockIdx.y) * 2 + which) * C + (cvbase + v) * V + e] = (double)sum;
       else atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
@@ -542,39 +774,101 @@ static int launch_fwd_gelu(const void* x, const float* w, const float* bias, voi
   return check_launch("dwconv3x3_fwd_kernel<gelu>");
 }
 
-// STATS 1: convolution + statistics; 2: statistics only; BNE: convolution + BatchNorm + activation from complete statistics
-template <typename T, int STATS, bool BNE>
-static int launch_fwd_stats(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
-                            int dil, hipStream_t st, BnEpi bn = BnEpi{}, double* spart = nullptr) {
-  constexpr int V = VecIO<T>::N;
-  const int CV = C / V;
-  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-  int rows;                                              // block rows = rows of the deterministic form's partial image
-  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) {
-    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS, BNE>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias,
-                       (T*)y, B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1, sums, bn, spart);
-    if (int rc = check_launch("dwconv3x3_fwd_kernel<sliced, stats / bn>")) return rc;
-    rows = sg.grid / 8;
+// Launch geometry of dwconv3x3_roll_kernel (16-bit activations, 4 channels per thread): the XCD-sliced grid where
+// sliced_geom() has it (slices of C / 8 channels, 64 resident blocks per XCD), else channel blocks x lane blocks.
+// `seg`, the rows of a segment: a whole residue class (ceil(H / d) rows: no refill rows at all, the rows above and below a
+// class are outside the image) whenever that still leaves every pixel lane of the grid 4 items -- the teacher's ASPP
+// (40 x 135 x 240 x 1024: 14 400 / 28 800 / 51 840 items of 23 / 12 / 8 rows on the 512 lanes of a channel slice) is there for every dilation;
+// smaller maps are cut down to segments of 8 rows at the least, where the two refill rows are a quarter more loads.
+struct RollGeom {
+  bool sliced;
+  int cvb, gx, gy, seg, rows;      // grid (gx, gy); sliced: gy == 1; rows: block rows = rows of the deterministic partial image
+  long nitems;
+};
+static RollGeom roll_geom(int B, int H, int W, int C, int dil) {
+  RollGeom g{};
+  const int CV = C / kRV, Hd = cdiv(H, dil);
+  const int WQ = dil * cdiv(cdiv(W, dil), kPX);
+  const SlicedGeom sg = sliced_geom(C / 8, 1L << 30);
+  int pl;
+  long lanes;
+  if (sg.on) {
+    g.sliced = true, g.cvb = 2 * sg.cvb, pl = 256 / g.cvb;
+    lanes = (long)(sg.grid / 8) * pl;
   } else {
-    const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-    const long nquads = (long)B * H * WQ;
-    const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
-    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS, BNE>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
-                       (T*)y, B, H, W, C, dil, cvb, (T*)nullptr, 1.f, 1.f, 0, sums, bn, spart);
-    if (int rc = check_launch("dwconv3x3_fwd_kernel<stats / bn>")) return rc;
-    rows = gy;
+    g.cvb = pick_cvb(CV), g.gx = cdiv(CV, g.cvb), pl = 256 / g.cvb;
+    lanes = (256L * 16) / g.gx * pl;
   }
-  if (spart != nullptr) return ordered_colsum_f64(spart, sums, rows, 2 * C, st);
+  const long per_seg = (long)B * dil * WQ;
+  const long want = std::max<long>(1, cdiv(4 * lanes, per_seg));              // segments per class for 4 items per lane
+  g.seg = (int)std::min<long>(Hd, std::max<long>(8, cdiv(Hd, want)));
+  g.nitems = per_seg * cdiv(Hd, g.seg);
+  if (sg.on) {
+    g.rows = (int)std::max<long>(1, std::min<long>(cdiv(g.nitems, pl), sg.grid / 8));
+    g.gx = 8 * g.rows, g.gy = 1;
+  } else {
+    g.rows = g.gy = (int)std::max<long>(1, std::min<long>(cdiv(g.nitems, pl), (256L * 16) / g.gx));
+  }
+  return g;
+}
+
+template <typename T, int STATS, bool BNE>
+static int launch_roll(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
+                       int dil, hipStream_t st, BnEpi bn, double* spart) {
+  static void* zero_line = nullptr;          // looked up once (first call is an eager warm-up, never inside a capture)
+  if (zero_line == nullptr && hipGetSymbolAddress(&zero_line, HIP_SYMBOL(g_zero_line_dw)) != hipSuccess)
+    return fail(RFN_ELAUNCH, "dwconv3x3_roll_kernel: zero line symbol");
+  const RollGeom g = roll_geom(B, H, W, C, dil);
+  RFN_REQUIRE(g.nitems < (1L << 30) && (long)dil * W * C * (long)sizeof(T) < (1L << 32),
+              "dwconv3x3_roll_kernel: B=%d H=%d W=%d C=%d dilation=%d too large", B, H, W, C, dil);
+  hipLaunchKernelGGL((dwconv3x3_roll_kernel<T, STATS, BNE, kRollDepth<T>>), dim3(g.gx, g.gy), dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B, H,
+                     W, C, dil, g.cvb, g.seg, g.sliced ? 1 : 0, sums, bn, spart, (const void*)zero_line);
+  if (int rc = check_launch("dwconv3x3_roll_kernel")) return rc;
+  if (spart != nullptr) return ordered_colsum_f64(spart, sums, g.rows, 2 * C, st);
   return RFN_OK;
 }
 
-// block rows of launch_fwd_stats for 16-bit activations (V = 8), either geometry
+// STATS 1: convolution + statistics; 2: statistics only; BNE: convolution + BatchNorm + activation from complete statistics.
+// The two gradient-free forms (2, BNE) run the rolling-window body, STATS 1 (it stores the convolution for a backward pass)
+// the first one.
+template <typename T, int STATS, bool BNE>
+static int launch_fwd_stats(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
+                            int dil, hipStream_t st, BnEpi bn = BnEpi{}, double* spart = nullptr) {
+  if constexpr (STATS == 2 || BNE) {
+    return launch_roll<T, STATS, BNE>(x, w, bias, y, sums, B, H, W, C, dil, st, bn, spart);
+  } else {
+    constexpr int V = VecIO<T>::N;
+    const int CV = C / V;
+    const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
+    int rows;                                              // block rows = rows of the deterministic form's partial image
+    if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) {
+      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias,
+                         (T*)y, B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1, sums, spart);
+      if (int rc = check_launch("dwconv3x3_fwd_kernel<sliced, stats>")) return rc;
+      rows = sg.grid / 8;
+    } else {
+      const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
+      const long nquads = (long)B * H * WQ;
+      const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
+      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
+                         (T*)y, B, H, W, C, dil, cvb, (T*)nullptr, 1.f, 1.f, 0, sums, spart);
+      if (int rc = check_launch("dwconv3x3_fwd_kernel<stats>")) return rc;
+      rows = gy;
+    }
+    if (spart != nullptr) return ordered_colsum_f64(spart, sums, rows, 2 * C, st);
+    return RFN_OK;
+  }
+}
+
+// block rows of launch_fwd_stats for 16-bit activations: the larger of the two bodies' (one workspace size serves
+// rfn_dwconv3x3_nhwc_fwd_stats_det and rfn_dwconv3x3_nhwc_stats_det)
 static int dw_stats_rows(int B, int H, int W, int C, int dil) {
   const int CV = C / 8;
   const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) return sg.grid / 8;
+  const int roll = roll_geom(B, H, W, C, dil).rows;
+  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) return std::max(roll, sg.grid / 8);
   const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-  return (int)std::max<long>(1, std::min<long>(cdiv((long)B * H * WQ, pl), (256L * 16) / gx));
+  return std::max(roll, (int)std::max<long>(1, std::min<long>(cdiv((long)B * H * WQ, pl), (256L * 16) / gx)));
 }
 
 template <typename T>
@@ -967,7 +1261,7 @@ int rfn_dwconv3x3_nhwc_stats(const void* x, const float* weight, const float* bi
   RFN_REQUIRE(x && weight && sums, "rfn_dwconv3x3_nhwc_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats: bad size");
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
+  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_roll_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
   return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st)

@@ -174,6 +174,31 @@ def dwconv3x3_nhwc(x, weight, bias=None, dilation=1, stats=None):
     return _DWConv3x3.apply(x, weight, bias, int(dilation), stats)
 
 
+def _stats_only(x, w_tap, b32, dilation):
+    """(sum, sum of squares, rows) of the rounded convolution result, nothing stored: 2 C + 1 doubles"""
+    B, H, W, C = x.shape
+    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+    if determinism.enabled():
+        ws = workspace(_lib.load_library().rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation), x.device)
+        _lib.call("rfn_dwconv3x3_nhwc_stats_det", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), ptr(ws), B, H, W, C,
+                  dilation, DTYPE_CODE[x.dtype])
+    else:
+        _lib.call("rfn_dwconv3x3_nhwc_stats", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, dilation,
+                  DTYPE_CODE[x.dtype])
+    return sums
+
+
+@torch.no_grad()
+def dwconv3x3_stats_nhwc(x, weight, bias, dilation):
+    """The first pass of dwconv3x3_bn_act_nhwc alone: the BatchNorm statistics of dwconv3x3_nhwc(x, weight, bias, dilation)
+    (a float64 tensor of 2 C + 1: sum, sum of squares, rows) without storing the convolution.  x: (B, H, W, C) bf16 / fp16."""
+    C = x.shape[-1]
+    w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
+                    lambda t: t.reshape(C, 9).t())
+    b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
+    return _stats_only(x, w_tap, b32, int(dilation))
+
+
 @torch.no_grad()
 def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     """act(bn(dwconv3x3(x))) with BATCH statistics, gradient-free (the EMA teacher's ASPP branches run their BatchNorms in
@@ -187,15 +212,8 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
     g = None if bn.weight is None else as_dtype(bn.weight, torch.float32).detach().contiguous()
     be = None if bn.bias is None else as_dtype(bn.bias, torch.float32).detach().contiguous()
-    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
     y = torch.empty_like(x)
-    if determinism.enabled():
-        ws = workspace(_lib.load_library().rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, int(dilation)), x.device)
-        _lib.call("rfn_dwconv3x3_nhwc_stats_det", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), ptr(ws), B, H, W, C,
-                  int(dilation), DTYPE_CODE[x.dtype])
-    else:
-        _lib.call("rfn_dwconv3x3_nhwc_stats", x.device, ptr(x), ptr(w_tap), ptr(b32), ptr(sums), B, H, W, C, int(dilation),
-                  DTYPE_CODE[x.dtype])
+    sums = _stats_only(x, w_tap, b32, int(dilation))
     group = bnk.sync_group(bn)
     if group is not None:
         bnk._all_reduce(sums, group, bnk._exchange_comm(bn))

@@ -488,8 +488,9 @@ class DepthwiseSeparableASPPModule(nn.ModuleList):
 _ASPP_NOCAT = True
 # the three dilated branches from ONE LDS-resident copy of the input (csrc/dwconv.hip: dwconv3x3_tri_kernel): correct, every
 # input byte fetched once at HBM speed (0.53 ms for the teacher's 2.65 GB), but the passes are VALU-bound (bf16 -> fp32
-# conversions + packed FMAs + zero-padding selects: 2.9 ms of 3.3), so it measures 8.6 ms against 8.1 ms for six single-branch
-# passes (profiles/r04_aspp_try.txt): kept, tested, OFF by default
+# conversions + packed FMAs + zero-padding selects: 2.9 ms of 3.3), so it measured 8.6 ms against 8.1 ms for six single-branch
+# passes of the first body (profiles/r04_aspp_try.txt) -- and the six passes of the rolling row walk (dwconv3x3_roll_kernel)
+# take 5.7 ms (profiles/dwconv_roll_kbench.txt; the tri kernel has not been given that walk): kept, tested, OFF by default
 _ASPP_TRI = False
 
 

@@ -115,6 +115,24 @@ def main():
             gy = torch.randn_like(y)
             add(f"dwconv fwd+bwd {B_}x{H}x{W}x{C} d{dil} {str(dt)[6:]}", timeit(lambda: torch.autograd.grad(dwconv3x3_nhwc(xg, wg, bb, dil), (xg, wg), gy), reps=5), 7 * x.numel() * es)
     if not args.only or "dw" in args.only:
+        # the EMA teacher's ASPP branches (gradient-free: statistics pass, then convolution + BatchNorm + ReLU), one launch each
+        from refign_amd import _lib
+        from refign_amd._tensor import ptr
+        B_, H, W, C = 40, 135, 240, 1024
+        x = torch.randn(B_, H, W, C, device=dev).to(torch.bfloat16)
+        y = torch.empty_like(x)
+        w_tap = torch.randn(9, C, device=dev)
+        bb, ga, be = torch.randn(C, device=dev), torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev)
+        sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+        for dil in (6, 12, 18):
+            add(f"dwconv statistics only {B_}x{H}x{W}x{C} d{dil} bfloat16",
+                timeit(lambda: _lib.call("rfn_dwconv3x3_nhwc_stats", dev, ptr(x), ptr(w_tap), ptr(bb), ptr(sums), B_, H, W, C, dil, 1)),
+                x.numel() * 2)
+            add(f"dwconv + bn + relu {B_}x{H}x{W}x{C} d{dil} bfloat16",
+                timeit(lambda: _lib.call("rfn_dwconv3x3_bn_act_nhwc_fwd", dev, ptr(x), ptr(w_tap), ptr(bb), ptr(ga), ptr(be), ptr(sums),
+                                         None, None, ptr(y), B_, H, W, C, dil, 1e-5, 0.1, 1, 1)), 2 * x.numel() * 2)
+        del x, y
+    if not args.only or "dw" in args.only:
         from refign_amd.dwconv import dwconv3x3_gelu_tokens
         for (B_, H, W, C) in [(40, 34, 60, 1280), (40, 68, 120, 512), (40, 135, 240, 256), (4, 34, 60, 1280)]:
             x = torch.randn(B_, H * W, C, device=dev).to(torch.bfloat16)
