@@ -103,13 +103,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
   using E = Elem<DT>;
   using vec8 = typename E::vec8;
   static_assert(BK == 32 || BK == 64, "K-step of 32 or 64");
-  // profiling builds only (make FLAGS+=-DRFN_GEMM_PROFILE; tools/gemm_ablate.py): RFN_GEMM_ABLATE bit 1 no DMA, 2 no MFMA,
-  // 4 no stores -- which phases of a launch overlap (round 3: none do, profiles/r03_gemm_ablation.txt)
-#ifdef RFN_GEMM_PROFILE
-  const int ablate = epi.act >> 8;
-#else
-  constexpr int ablate = 0;
-#endif
   // NW waves as 2 (m) x NW / 2 (n); 8 waves (a 256 x 256 tile, wave tile 128 x 64) halve the LDS-DMA instructions a wave
   // issues per MFMA -- their issue cost, not the data volume, is what paces the 4-wave 128 x 128 tile (2 MFMAs per DMA)
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
@@ -192,7 +185,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
   auto issue = [&](int kt, int buf) {
     unsigned char* xs = smem + buf * STAGE;
     unsigned char* ws = xs + XBYTES;
-    if (ablate & 1) return;
     if constexpr (GATHER) {
       if (fastc) {
         if (kt == 0) {
@@ -301,12 +293,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
     for (int ks = 0; ks < BK / 16; ++ks) {
       if (ks + FD - 1 < BK / 16) read_frags(ks + FD - 1, (ks + FD - 1) % FD);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(ablate & 2)) {
 #pragma unroll
-        for (int i = 0; i < IB; ++i)
+      for (int i = 0; i < IB; ++i)
 #pragma unroll
-          for (int j = 0; j < JB; ++j) acc[i][j] = E::mma(wf[ks % FD][i], xf[ks % FD][j], acc[i][j]);
-      }
+        for (int j = 0; j < JB; ++j) acc[i][j] = E::mma(wf[ks % FD][i], xf[ks % FD][j], acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (++c_kt == nk) {
@@ -377,9 +367,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] += b[e];
             }
-            if ((epi.act & 255) != 0) {
+            if (epi.act != 0) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act & 255);
+              for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act);
             }
             *(u32x2*)(stg + frow * PITCH + cl * 2) = pack4<DT>(v[0], v[1], v[2], v[3]);
           }
@@ -416,7 +406,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
               }
               o = u32x4{lo[0], lo[1], hi[0], hi[1]};
             }
-            if (!(ablate & 4)) *(u32x4*)(Y + (long)m * ldy + n) = o;
+            *(u32x4*)(Y + (long)m * ldy + n) = o;
           }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // staging reads done before the next j block overwrites
@@ -429,27 +419,111 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// TN kernel (weight gradient): P_s[N,K] = sum over the rows t of slab s of G[t, n] * X[t, k], fp32 partials per slab.
-// Both operands are needed "transposed" (the reduction index is their ROW index), so the tiles are staged through LDS
-// in the k-slot-major image [t / 4][column][4 t] by a register pass (8-byte ds_write per lane holding 4 rows of one
-// column pair would need a transpose; instead each lane loads ONE column pair of 4 consecutive rows: 4 dword loads),
-// and both MFMA operands are then plain 8-byte LDS reads: A[i = n][slots] = G^T, B[slots][j = k] = X.
-// Slot order inside a 16-row k-step follows mfma.h: slot (g, e) = row {0-3, 8-11}[e] + 4 g.
-// ---------------------------------------------------------------------------------------------------------------------
+// TN kernels (weight gradient): P_s[N,K] = sum over the rows t of slab s of G[t, n] * X[t, k], fp32 partials per slab
+// (accumulate 0 / 2: stored as P[slab]; 1: added into ONE [N, K] image with fp32 atomics), and in the same launch the bias
+// gradient = the column sums of G.  Both operands are needed "transposed": the reduction index is their ROW index.
+// Two kernels (launch_tn picks):
+//   gemm_tn_dma_kernel, gemm_tn_group_kernel -- LDS-DMA staging + hardware transpose reads.  Runs whenever both operands
+//     are 16-byte aligned with row pitches (a convolution: channel counts) that are multiples of 8 and, with a row scale, the
+//     scales of a slab fit in 64 LDS floats: every weight gradient of the training step.
+//   gemm_tn_fallback_kernel -- dword loads + register transpose.  Everything else the ABI admits: operands that are only
+//     4-byte aligned (views at an odd column offset, row pitches % 2), convolutions with C % 8 != 0, a row scale with more
+//     than 63 samples touching one slab.
+// Shared, below: the slab / tile mapping, the im2col tap and row cursor of the GATHER forms, the accumulator epilogue.
+// Slot order inside a 16-row k-step follows mfma.h in both: slot (g, e) = row {0-3, 8-11}[e] + 4 g.
 // GATHER: the weight gradient of a convolution (rfn_conv2d_nhwc_wgrad): row t of the X operand is the im2col row of output
 // pixel t = (b, oy, ox), column k = (tap, c) reads x[b, oy s - p + ky d, ox s - p + kx d, c] (zero outside the image / past
-// the last tap) -- no im2col buffer; a thread's column pair is fixed, so its (tap, c) is decomposed once.
+// the last tap) -- no im2col buffer.
 struct WgradGeom {
   int H, W, C, OH, OW, KH, KW, stride, pad, dil;
   unsigned c_magic, kw_magic;                          // ceil(2^32 / d) for C, KW (dividends < 2^16)
 };
 
+// A workgroup's slab and output tile.  Logical order is slab-major and XCD-aware (mfma.h xcd_remap: consecutive logical ids on
+// ONE XCD): the tiles of a slab share its rows of G and X (a slab of both operands fits the XCD's 4 MB L2), so each operand
+// byte crosses the fabric once instead of once per XCD.  `bid` of `nblocks` = the workgroup's place in ITS problem's grid.
+struct TnTile {
+  int slab, n0, k0;
+  long t0, tend;                                       // the slab's rows: R of them (R % 32 == 0), the last slab ends at T
+};
+template <int BN, int BK>
+__device__ __forceinline__ TnTile tn_tile(int bid, int nblocks, int N, int tiles_k, int R, int T) {
+  const int tiles = (N / BN) * tiles_k;
+  const int lid = xcd_remap(bid, nblocks);
+  const int slab = lid / tiles, tile = lid % tiles;
+  const long t0 = (long)slab * R;
+  return {slab, (tile / tiles_k) * BN, (tile % tiles_k) * BK, t0, min((long)T, t0 + R)};
+}
+
+// GATHER: im2col column k = (tap, channel c); (dy, dx) = the tap's offset from the window origin (oy s, ox s) of an output
+// pixel, ok = a real tap (the columns past the last tap are padding and read zeros).  c1: C == 1, whose magic is 2^32.
+struct TnTap { bool ok; int dy, dx, c; };
+__device__ __forceinline__ TnTap tn_tap(const WgradGeom& wg, unsigned k, bool c1 = false) {
+  const unsigned tap = c1 ? k : __umulhi(k, wg.c_magic);
+  const unsigned ky = wg.KW == 1 ? tap : __umulhi(tap, wg.kw_magic), kx = tap - ky * wg.KW;
+  return {(int)ky < wg.KH, (int)ky * wg.dil - wg.pad, (int)kx * wg.dil - wg.pad, (int)(k - tap * wg.C)};
+}
+
+// GATHER: (image, oy, ox) of an im2col row, set from its index once and then advanced by the rows of a stage (no division in
+// the loop)
+struct TnRow {
+  int b, oy, ox;
+  __device__ __forceinline__ void seek(const WgradGeom& wg, long t) {
+    const long ohw = (long)wg.OH * wg.OW;
+    b = (int)(t / ohw);
+    const int rem = (int)(t - b * ohw);
+    oy = rem / wg.OW;
+    ox = rem - oy * wg.OW;
+  }
+  __device__ __forceinline__ void advance(const WgradGeom& wg, int rows) {
+    ox += rows;
+    while (ox >= wg.OW) {
+      ox -= wg.OW;
+      if (++oy == wg.OH) {
+        oy = 0;
+        ++b;
+      }
+    }
+  }
+};
+
+// Accumulator epilogue of wave (wn, wk), which owns the 32 x 32 blocks (wn IB + i, wk JB + j) of the tile.  D[i = n][j = k]
+// (mfma.h): a lane holds column k = col = lane & 31 and rows n = (r & 3) + 8 (r >> 2) + 4 g, g = lane >> 5, of a block (both
+// passed in: recomputed here, the DMA kernel's register allocation comes out different).  accumulate 1: added into P[N, K]
+// (128-byte coalesced fp32 atomics), 0 / 2: stored to the slab's own image.
+template <int IB, int JB>
+__device__ __forceinline__ void tn_store(const f32x16 (&acc)[IB][JB], float* __restrict__ P, int accumulate, const TnTile& tt,
+                                         int N, int K, int wn, int wk, int g, int col) {
+  float* out = accumulate == 1 ? P : P + (long)tt.slab * N * K;
+#pragma unroll
+  for (int i = 0; i < IB; ++i)
+#pragma unroll
+    for (int j = 0; j < JB; ++j) {
+      const int kk = tt.k0 + (wk * JB + j) * 32 + col;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = tt.n0 + (wn * IB + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
+        else out[(long)n * K + kk] = acc[i][j][r];
+      }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fallback kernel.  The tiles are staged through LDS in the k-slot-major image [t / 4][column][4 t] by a register pass: each
+// lane loads ONE column pair (a dword) of 4 consecutive rows -- the only load width that 4-byte aligned operands and C % 2
+// channel counts allow -- and transposes them into two 8-byte columns, so both MFMA operands are plain 8-byte LDS reads:
+// A[i = n][slots] = G^T, B[slots][j = k] = X.  Load issue and the transpose pace it (see the measurements at the DMA kernel).
+// GATHER: a thread's column pair is fixed, so its tap is decomposed once.
+// rowscale: G <- diag(rowscale[row / rows_per_sample]) G, scaled in fp32 and rounded back to the 16-bit type like the eager
+// g * mask; the bias column sums are those of the rounded values.
+// ---------------------------------------------------------------------------------------------------------------------
 template <int DT, int BN, int BK, bool GATHER = false>
-__global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
-                                                      float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
-                                                      int R, int tiles_k, int accumulate, float* __restrict__ gbias,
-                                                      const float* __restrict__ rowscale, int rows_per_sample,
-                                                      WgradGeom wg, int xcd) {
+__global__ __launch_bounds__(256) void gemm_tn_fallback_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
+                                                               float* __restrict__ P, int T, int N, int K, long ldg,
+                                                               long ldx, int R, int tiles_k, int accumulate,
+                                                               float* __restrict__ gbias, const float* __restrict__ rowscale,
+                                                               int rows_per_sample, WgradGeom wg) {
   using E = Elem<DT>;
   constexpr int BT = 32;                   // rows of the reduction per stage (two 16-slot k-steps)
   constexpr int IB = BN / 64, JB = BK / 64;
@@ -459,14 +533,9 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave >> 1, wk = wave & 1;
-  const int tiles = (N / BN) * tiles_k;
-  // slab-major logical order, XCD-aware (mfma.h xcd_remap: consecutive logical ids on ONE XCD): the tiles of a slab share
-  // its rows of G and X (a slab of both operands fits the XCD's 4 MB L2), so each operand byte crosses the fabric once instead
-  // of once per XCD.  xcd = 0 (RFN_GEMM_TN_XCD=0): dispatch order, as in the first two rounds.
-  const int lid = xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int slab = lid / tiles, tile = lid % tiles;
-  const int n0 = (tile / tiles_k) * BN, k0 = (tile % tiles_k) * BK;
-  const long t0 = (long)slab * R;          // slab = R rows (R % 32 == 0), the last one may run past T: masked loads
+  const TnTile tt = tn_tile<BN, BK>((int)blockIdx.x, (int)gridDim.x, N, tiles_k, R, T);
+  const int n0 = tt.n0, k0 = tt.k0;
+  const long t0 = tt.t0, tend = tt.tend;   // R % BT == 0: only the last stage of the last slab is ragged
 
   // register staging: thread handles column pair cp (2 columns = one dword per row) of quad q: 4 dword loads (rows
   // 4q .. 4q+3), transposed in registers into two 8-byte LDS writes (one per column)
@@ -479,32 +548,16 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
   // keeps the running sums of its two columns; only the k-tile-0 workgroups of each (n tile, slab) contribute
   const bool do_bias = (gbias != nullptr) && (k0 == 0);
   float bsum[2] = {0.f, 0.f};
-  // GATHER: (tap, channel) of this thread's X column pair (the same in every stage and for all its items)
-  int gdy = 0, gdx = 0, gc = 0;
-  bool gtap_ok = true;
+  // GATHER: the tap of this thread's X column pair (the same in every stage and for all its items) and the im2col rows it
+  // stages, advanced by BT per stage
+  TnTap tap{true, 0, 0, 0};
+  TnRow row[GATHER ? XPT : 1][4];
   if constexpr (GATHER) {
-    const unsigned k = (unsigned)(k0 + 2 * (threadIdx.x % XP));
-    const unsigned tap = wg.C == 1 ? k : __umulhi(k, wg.c_magic);
-    gc = (int)(k - tap * wg.C);
-    const unsigned ky = wg.KW == 1 ? tap : __umulhi(tap, wg.kw_magic), kx = tap - ky * wg.KW;
-    gtap_ok = (int)ky < wg.KH;
-    gdy = (int)ky * wg.dil - wg.pad;
-    gdx = (int)kx * wg.dil - wg.pad;
-  }
-  // (image, oy, ox) of the rows this thread stages, advanced by BT per stage (no division in the loop)
-  int gb[GATHER ? XPT : 1][4], goy[GATHER ? XPT : 1][4], gox[GATHER ? XPT : 1][4];
-  if constexpr (GATHER) {
+    tap = tn_tap(wg, (unsigned)(k0 + 2 * (threadIdx.x % XP)), wg.C == 1);
 #pragma unroll
     for (int u = 0; u < XPT; ++u)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long t = t0 + 4 * ((u * 256 + (int)threadIdx.x) / XP) + r;
-        const long ohw = (long)wg.OH * wg.OW;
-        gb[u][r] = (int)(t / ohw);
-        const int rem = (int)(t - gb[u][r] * ohw);
-        goy[u][r] = rem / wg.OW;
-        gox[u][r] = rem - goy[u][r] * wg.OW;
-      }
+      for (int r = 0; r < 4; ++r) row[u][r].seek(wg, t0 + 4 * ((u * 256 + (int)threadIdx.x) / XP) + r);
   }
   auto load_stage = [&](int it) {
     const long tb = t0 + (long)it * BT;
@@ -512,15 +565,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
     for (int u = 0; u < GPT; ++u) {
       const int item = u * 256 + threadIdx.x, q = item / GP, cp = item % GP;
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        greg[u][r] = (tb + 4 * q + r < T) ? *(const unsigned*)(G + (tb + 4 * q + r) * ldg + n0 + 2 * cp) : 0u;
-      if (rowscale != nullptr) {
-        // G <- diag(rowscale[row / rows_per_sample]) G (the stochastic-depth scale of the branch this gradient belongs
-        // to): the two 16-bit values of each row dword, scaled in fp32 and rounded back like the eager g * mask
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const long row = tb + 4 * q + r;
-          const float sc = row < T ? rowscale[row / rows_per_sample] : 0.f;
+      for (int r = 0; r < 4; ++r) {
+        const long t = tb + 4 * q + r;
+        greg[u][r] = t < tend ? *(const unsigned*)(G + t * ldg + n0 + 2 * cp) : 0u;
+        if (rowscale != nullptr) {                       // the two 16-bit values of the row dword
+          const float sc = t < tend ? rowscale[t / rows_per_sample] : 0.f;
           float f[4];
           unpack4<DT>(u32x2{greg[u][r], 0u}, f);
           greg[u][r] = pack4<DT>(f[0] * sc, f[1] * sc, 0.f, 0.f)[0];
@@ -532,24 +581,23 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
       const int item = u * 256 + threadIdx.x, q = item / XP, cp = item % XP;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        const long t = tb + 4 * q + r;
         if constexpr (GATHER) {
-          const long t = tb + 4 * q + r;
-          const int iy = goy[u][r] * wg.stride + gdy, ix = gox[u][r] * wg.stride + gdx;
-          const bool ok = t < T && gtap_ok && (unsigned)iy < (unsigned)wg.H && (unsigned)ix < (unsigned)wg.W;
-          xreg[u][r] = ok ? *(const unsigned*)(X + (((long)gb[u][r] * wg.H + iy) * wg.W + ix) * wg.C + gc) : 0u;
-          gox[u][r] += BT;                              // the same row of the NEXT stage
-          while (gox[u][r] >= wg.OW) {
-            gox[u][r] -= wg.OW;
-            if (++goy[u][r] == wg.OH) {
-              goy[u][r] = 0;
-              ++gb[u][r];
-            }
-          }
+          TnRow& px = row[u][r];
+          const int iy = px.oy * wg.stride + tap.dy, ix = px.ox * wg.stride + tap.dx;
+          const bool ok = t < tend && tap.ok && (unsigned)iy < (unsigned)wg.H && (unsigned)ix < (unsigned)wg.W;
+          xreg[u][r] = ok ? *(const unsigned*)(X + (((long)px.b * wg.H + iy) * wg.W + ix) * wg.C + tap.c) : 0u;
+          px.advance(wg, BT);                           // the same row of the NEXT stage
         } else {
-          xreg[u][r] = (tb + 4 * q + r < T) ? *(const unsigned*)(X + (tb + 4 * q + r) * ldx + k0 + 2 * cp) : 0u;
+          xreg[u][r] = t < tend ? *(const unsigned*)(X + t * ldx + k0 + 2 * cp) : 0u;
         }
       }
     }
+  };
+  // even column: low halves of the 4 row dwords; odd column: high halves
+  auto transpose4 = [](const unsigned (&v)[4]) {
+    return u32x4{(v[0] & 0xffffu) | (v[1] << 16), (v[2] & 0xffffu) | (v[3] << 16), (v[0] >> 16) | (v[1] & 0xffff0000u),
+                 (v[2] >> 16) | (v[3] & 0xffff0000u)};
   };
   auto write_stage = [&](int buf) {
     unsigned char* gs = smem + buf * STAGE;
@@ -557,12 +605,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
     for (int u = 0; u < GPT; ++u) {
       const int item = u * 256 + threadIdx.x, q = item / GP, cp = item % GP;
-      // even column: low halves of the 4 row dwords; odd column: high halves
-      u32x4 o;
-      o[0] = (greg[u][0] & 0xffffu) | (greg[u][1] << 16);
-      o[1] = (greg[u][2] & 0xffffu) | (greg[u][3] << 16);
-      o[2] = (greg[u][0] >> 16) | (greg[u][1] & 0xffff0000u);
-      o[3] = (greg[u][2] >> 16) | (greg[u][3] & 0xffff0000u);
+      const u32x4 o = transpose4(greg[u]);
       *(u32x4*)(gs + (q * BN + 2 * cp) * 8) = o;
       if (do_bias) {
         float f[4];
@@ -575,12 +618,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
 #pragma unroll
     for (int u = 0; u < XPT; ++u) {
       const int item = u * 256 + threadIdx.x, q = item / XP, cp = item % XP;
-      u32x4 o;
-      o[0] = (xreg[u][0] & 0xffffu) | (xreg[u][1] << 16);
-      o[1] = (xreg[u][2] & 0xffffu) | (xreg[u][3] << 16);
-      o[2] = (xreg[u][0] >> 16) | (xreg[u][1] & 0xffff0000u);
-      o[3] = (xreg[u][2] >> 16) | (xreg[u][3] & 0xffff0000u);
-      *(u32x4*)(xs + (q * BK + 2 * cp) * 8) = o;
+      *(u32x4*)(xs + (q * BK + 2 * cp) * 8) = transpose4(xreg[u]);
     }
   };
 
@@ -593,7 +631,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int g = lane >> 5, col = lane & 31;
-  const int nit = (int)((min((long)R, (long)T - t0) + BT - 1) / BT);
+  const int nit = (int)((tend - t0 + BT - 1) / BT);
   load_stage(0);
   write_stage(0);
   __syncthreads();
@@ -626,20 +664,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
     __syncthreads();
   }
 
-  // D[i = n][j = k]: lane holds column k = .. + col, rows n = (r & 3) + 8 (r >> 2) + 4 g
-  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int j = 0; j < JB; ++j) {
-      const int kk = k0 + wk * (BK / 2) + j * 32 + col;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);     // 128-byte coalesced fp32 atomics
-        else out[(long)n * K + kk] = acc[i][j][r];
-      }
-    }
+  tn_store<IB, JB>(acc, P, accumulate, tt, N, K, wn, wk, g, col);
   if (do_bias) {                                   // reduce the per-thread column sums over the row quads, one atomic per column
     float* red = (float*)smem;                     // the staging ring is free now (last __syncthreads above)
     red[threadIdx.x * 2] = bsum[0];
@@ -649,234 +674,19 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const uint16_t* __restrict
       const int cp = threadIdx.x >> 1, e = threadIdx.x & 1;
       float sum = 0.f;
       for (int t = cp; t < 256; t += GP) sum += red[t * 2 + e];
-      if (accumulate == 2) gbias[(long)slab * N + n0 + threadIdx.x] = sum;      // per-slab bias partials (deterministic form)
+      if (accumulate == 2) gbias[(long)tt.slab * N + n0 + threadIdx.x] = sum;   // per-slab bias partials (deterministic form)
       else atomicAdd(gbias + n0 + threadIdx.x, sum);
     }
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------
-// TN kernel, second generation (round 3): the same product and the same LDS image / MFMA operand order as above, but the
-// operand tiles are fetched with 16-BYTE loads and transposed in registers.  128 threads stage the G tile, 128 the X tile;
-// a thread owns ONE 4-row x 8-column block per stage: 4 x global_load_dwordx4 (a 16-lane group reads 256 contiguous bytes
-// of a row), 16 v_perm_b32, 4 x ds_write_b128 -- a quarter of the load instructions per element of the first generation
-// (4-byte loads), which was paced by load issue.  The 16-byte piece j (column pair j of the block) of block cv is stored at
-// piece slot j ^ ((cv >> 1) & 3): the 8 lanes of a ds_write_b128 group then cover the eight 16-byte slots of a 128-byte
-// bank row, and a fragment read stays a permutation inside its 256-byte span (conflict-free both ways).
-// BT = rows of the reduction per stage: 32 for the 128 x 128 tile, 64 for the 64 x 64 tile (128 blocks per operand either
-// way).  GATHER: im2col rows of a convolution (see WgradGeom); a thread's block is 8 channels of ONE tap of 4 consecutive
-// output pixels.
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned perm_lo(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }  // {a.lo, b.lo}
-__device__ __forceinline__ unsigned perm_hi(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }  // {a.hi, b.hi}
-
-template <int DT, int BN, int BK, int BT, bool GATHER>
-__global__ __launch_bounds__(256) void gemm_tn2_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
-                                                       float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
-                                                       int R, int tiles_k, int accumulate, float* __restrict__ gbias,
-                                                       const float* __restrict__ rowscale, int rows_per_sample,
-                                                       WgradGeom wg, int xcd) {
-  using E = Elem<DT>;
-  constexpr int IB = BN / 64, JB = BK / 64;
-  constexpr int NQ = BT / 4;                                     // row quads per stage
-  constexpr int GBYTES = NQ * BN * 8, XBYTES = NQ * BK * 8, STAGE = GBYTES + XBYTES;
-  static_assert(NQ * (BN / 8) == 128 && NQ * (BK / 8) == 128, "128 blocks per operand and stage");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wn = wave >> 1, wk = wave & 1;
-  const int tiles = (N / BN) * tiles_k;
-  // slab-major logical order, XCD-aware (mfma.h xcd_remap: consecutive logical ids on ONE XCD): the tiles of a slab share
-  // its rows of G and X (a slab of both operands fits the XCD's 4 MB L2), so each operand byte crosses the fabric once instead
-  // of once per XCD.  xcd = 0 (RFN_GEMM_TN_XCD=0): dispatch order, as in the first two rounds.
-  const int lid = xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int slab = lid / tiles, tile = lid % tiles;
-  const int n0 = (tile / tiles_k) * BN, k0 = (tile % tiles_k) * BK;
-  const long t0 = (long)slab * R;
-
-  // staging role: threads 0..127 the G tile, 128..255 the X tile; block (q, cv) = 4 rows x 8 columns
-  const bool isx = threadIdx.x >= 128;
-  const int bid = threadIdx.x & 127;
-  const int cols8 = (isx ? BK : BN) / 8;
-  const int cv = bid % cols8, q = bid / cols8;
-  const int sw = (cv >> 1) & 3;
-  const bool do_bias = (gbias != nullptr) && (k0 == 0) && !isx;
-  float bsum[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) bsum[e] = 0.f;
-
-  // GATHER (X threads): (tap, channel) of the block's 8 columns, and the (image, oy, ox) of its 4 rows, advanced per stage
-  int gdy = 0, gdx = 0, gc = 0;
-  bool gtap_ok = true;
-  int gb[4], goy[4], gox[4];
-  if constexpr (GATHER) {
-    const unsigned k = (unsigned)(k0 + 8 * cv);
-    const unsigned tap = __umulhi(k, wg.c_magic);
-    gc = (int)(k - tap * wg.C);
-    const unsigned ky = wg.KW == 1 ? tap : __umulhi(tap, wg.kw_magic), kx = tap - ky * wg.KW;
-    gtap_ok = (int)ky < wg.KH;
-    gdy = (int)ky * wg.dil - wg.pad;
-    gdx = (int)kx * wg.dil - wg.pad;
-    const long ohw = (long)wg.OH * wg.OW;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long t = t0 + 4 * q + r;
-      gb[r] = (int)(t / ohw);
-      const int rem = (int)(t - gb[r] * ohw);
-      goy[r] = rem / wg.OW;
-      gox[r] = rem - goy[r] * wg.OW;
-    }
-  }
-  const uint16_t* base = isx ? X + k0 + 8 * cv : G + n0 + 8 * cv;
-  const long ld = isx ? ldx : ldg;
-  const long tend = min((long)T, t0 + R);             // a slab need not be a multiple of BT rows: mask at its end
-  u32x4 reg[4];
-  auto load_stage = [&](int it) {
-    const long tb = t0 + (long)it * BT + 4 * q;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long t = tb + r;
-      bool ok = t < tend;
-      const uint16_t* src;
-      if (GATHER && isx) {
-        const int iy = goy[r] * wg.stride + gdy, ix = gox[r] * wg.stride + gdx;
-        ok = ok && gtap_ok && (unsigned)iy < (unsigned)wg.H && (unsigned)ix < (unsigned)wg.W;
-        src = X + (((long)gb[r] * wg.H + iy) * wg.W + ix) * wg.C + gc;
-        gox[r] += BT;
-        while (gox[r] >= wg.OW) {
-          gox[r] -= wg.OW;
-          if (++goy[r] == wg.OH) {
-            goy[r] = 0;
-            ++gb[r];
-          }
-        }
-      } else {
-        src = base + t * ld;
-      }
-      reg[r] = ok ? *(const u32x4*)src : u32x4{0u, 0u, 0u, 0u};
-    }
-    if (rowscale != nullptr && !isx) {
-      // G <- diag(rowscale[row / rows_per_sample]) G, scaled in fp32 and rounded back like the eager g * mask
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = tb + r;
-        const float sc = row < tend ? rowscale[row / rows_per_sample] : 0.f;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          float f[4];
-          unpack4<DT>(u32x2{reg[r][2 * h], reg[r][2 * h + 1]}, f);
-          const u32x2 o = pack4<DT>(f[0] * sc, f[1] * sc, f[2] * sc, f[3] * sc);
-          reg[r][2 * h] = o[0];
-          reg[r][2 * h + 1] = o[1];
-        }
-      }
-    }
-  };
-  auto write_stage = [&](int buf) {
-    unsigned char* dst = smem + buf * STAGE + (isx ? GBYTES : 0) + (q * (isx ? BK : BN) + 8 * cv) * 8;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // column pair j: dword j of the four rows -> {even column: 4 rows, odd column: 4 rows}
-      u32x4 o;
-      o[0] = perm_lo(reg[0][j], reg[1][j]);
-      o[1] = perm_lo(reg[2][j], reg[3][j]);
-      o[2] = perm_hi(reg[0][j], reg[1][j]);
-      o[3] = perm_hi(reg[2][j], reg[3][j]);
-      *(u32x4*)(dst + 16 * (j ^ sw)) = o;
-      if (do_bias) {
-        float f[4];
-        unpack4<DT>(u32x2{o[0], o[1]}, f);
-        bsum[2 * j] += (f[0] + f[1]) + (f[2] + f[3]);
-        unpack4<DT>(u32x2{o[2], o[3]}, f);
-        bsum[2 * j + 1] += (f[0] + f[1]) + (f[2] + f[3]);
-      }
-    }
-  };
-
-  f32x16 acc[IB][JB];
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int j = 0; j < JB; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int g = lane >> 5, col = lane & 31;
-  // byte offset of column c inside a quad's row of the image (swizzled 16-byte pieces inside 64-byte blocks)
-  auto coff = [](int c) { return (c & ~7) * 8 + 16 * (((c >> 1) & 3) ^ ((c >> 4) & 3)) + 8 * (c & 1); };
-  int aoff[IB], boff[JB];
-#pragma unroll
-  for (int i = 0; i < IB; ++i) aoff[i] = coff(wn * (BN / 2) + i * 32 + col);
-#pragma unroll
-  for (int j = 0; j < JB; ++j) boff[j] = coff(wk * (BK / 2) + j * 32 + col);
-
-  const int nit = (int)((min((long)R, (long)T - t0) + BT - 1) / BT);
-  load_stage(0);
-  write_stage(0);
-  __syncthreads();
-  for (int it = 0; it < nit; ++it) {
-    const int buf = it & 1;
-    if (it + 1 < nit) load_stage(it + 1);
-    const unsigned char* gs = smem + buf * STAGE;
-    const unsigned char* xs = gs + GBYTES;
-#pragma unroll
-    for (int ks = 0; ks < BT / 16; ++ks) {
-      const int qa = 4 * ks + g, qb = 4 * ks + 2 + g;
-      typename E::vec8 af[IB], bf[JB];
-#pragma unroll
-      for (int i = 0; i < IB; ++i)
-        af[i] = join8<DT>(*(const u32x2*)(gs + qa * BN * 8 + aoff[i]), *(const u32x2*)(gs + qb * BN * 8 + aoff[i]));
-#pragma unroll
-      for (int j = 0; j < JB; ++j)
-        bf[j] = join8<DT>(*(const u32x2*)(xs + qa * BK * 8 + boff[j]), *(const u32x2*)(xs + qb * BK * 8 + boff[j]));
-#pragma unroll
-      for (int i = 0; i < IB; ++i)
-#pragma unroll
-        for (int j = 0; j < JB; ++j) acc[i][j] = E::mma(af[i], bf[j], acc[i][j]);
-    }
-    if (it + 1 < nit) write_stage(buf ^ 1);
-    __syncthreads();
-  }
-
-  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int j = 0; j < JB; ++j) {
-      const int kk = k0 + wk * (BK / 2) + j * 32 + col;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
-        else out[(long)n * K + kk] = acc[i][j][r];
-      }
-    }
-  if (gbias != nullptr && k0 == 0) {             // the G threads' column sums over their row quads, one atomic per column
-    float* red = (float*)smem;                   // [128 blocks][8]
-    if (!isx) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[bid * 8 + e] = bsum[e];
-    }
-    __syncthreads();
-    if (threadIdx.x < BN) {
-      const int c8 = threadIdx.x >> 3, e = threadIdx.x & 7;
-      float sum = 0.f;
-      for (int qq = 0; qq < NQ; ++qq) sum += red[(qq * (BN / 8) + c8) * 8 + e];
-      if (accumulate == 2) gbias[(long)slab * N + n0 + threadIdx.x] = sum;      // per-slab bias partials (deterministic form)
-      else atomicAdd(gbias + n0 + threadIdx.x, sum);
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// TN kernel, third generation (round 3): LDS-DMA staging + hardware transpose reads.
+// DMA kernel: LDS-DMA staging + hardware transpose reads.
 // The weight gradient needs both operands with the reduction index t as the slot index of the MFMA operands, i.e.
-// "transposed" against their row-major storage; generations 1 and 2 transposed in registers on the way to LDS (16 v_perm,
-// 4 ds_write_b128 per thread and stage) and were bound by exactly that -- per CU one workgroup-step per ~0.45 us whatever
-// the number of slabs, the prefetch depth or the occupancy (PMC: 9 % MFMA, 53 % waiting; VALU and LDS pipe each about half
-// of the step).  gfx950's `ds_read_b64_tr_b16` does the transpose in the LDS read: within a 16-lane group lane p supplies
+// "transposed" against their row-major storage; kernels that transpose in registers on the way to LDS (the fallback above; with
+// 16-byte loads: 16 v_perm, 4 ds_write_b128 per thread and stage) are bound by exactly that -- per CU one workgroup-step per
+// ~0.45 us whatever the number of slabs, the prefetch depth or the occupancy (PMC: 9 % MFMA, 53 % waiting; VALU and LDS pipe
+// each about half of the step).  gfx950's `ds_read_b64_tr_b16` does the transpose in the LDS read: within a 16-lane group lane p supplies
 // the address of 4 contiguous 16-bit elements and lane i receives element i % 4 of lanes i / 4 + 4 j, j = 0..3 (probed:
 // tools/micro/tr_probe.hip).  With lane p pointing at row p / 4, columns 4 (p % 4) .. + 3 of a [4 rows][16 columns] block
 // lane i gets rows 0..3 of column i: 4 consecutive t of ONE column -- half an MFMA operand.  So the tiles go to LDS ROW-MAJOR,
@@ -903,13 +713,13 @@ __device__ __forceinline__ u32x2 lds_read_tr16(unsigned addr) {
 // version scaled the G FRAGMENTS -- unpack, multiply, round, repack, 40 VALU instructions per 16-row step in every one of
 // the K / 64 tiles that share a G panel: 8 160 x 320 x 1 280 took 42 us against 25 us without a scale.)
 // (the kernel's body as a device function: `bid` of `nblocks` = this workgroup's place in ITS problem's grid -- the whole
-// launch for gemm_tn3_kernel, a sub-range of it for gemm_tn3_group_kernel)
+// launch for gemm_tn_dma_kernel, a sub-range of it for gemm_tn_group_kernel)
 template <int DT, int BN, int BK, int BT, bool GATHER = false, bool SEG = false>
-__device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
-                                              float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
-                                              int R, int tiles_k, int accumulate, float* __restrict__ gbias,
-                                              const float* __restrict__ rowscale, int rows_per_sample,
-                                              const void* zero, int xcd, const WgradGeom& wg, int bid, int nblocks) {
+__device__ __forceinline__ void gemm_tn_dma_body(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
+                                                 float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
+                                                 int R, int tiles_k, int accumulate, float* __restrict__ gbias,
+                                                 const float* __restrict__ rowscale, int rows_per_sample,
+                                                 const void* zero, const WgradGeom& wg, int bid, int nblocks) {
   using E = Elem<DT>;
   constexpr int IB = BN / 64, JB = BK / 64;
   constexpr int GROW = BN * 2, XROW = BK * 2;                      // bytes per LDS row
@@ -923,12 +733,9 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wn = wave >> 1, wk = wave & 1;
-  const int tiles = (N / BN) * tiles_k;
-  const int lid = xcd ? xcd_remap(bid, nblocks) : bid;
-  const int slab = lid / tiles, tile = lid % tiles;
-  const int n0 = (tile / tiles_k) * BN, k0 = (tile % tiles_k) * BK;
-  const long t0 = (long)slab * R;
-  const long tend = min((long)T, t0 + R);
+  const TnTile tt = tn_tile<BN, BK>(bid, nblocks, N, tiles_k, R, T);
+  const int slab = tt.slab, n0 = tt.n0, k0 = tt.k0;
+  const long t0 = tt.t0, tend = tt.tend;
   static_assert(!(SEG && GATHER), "sample segments: plain operands only");
   auto gswz = [](int r) { return BN == 64 ? ((r >> 1) & 1) << 2 : (r & 3) << 2; };
   auto xswz = [](int r) { return BK == 64 ? ((r >> 1) & 1) << 2 : (r & 3) << 2; };
@@ -949,27 +756,15 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
   } else {
     nit = (int)((tend - t0 + BT - 1) / BT);
   }
-  // GATHER: per X instruction u of this lane: (dy, dx, channel) of its piece, (image, oy, ox) of its row in stage 0
-  int gdy[GATHER ? XI : 1], gdx[GATHER ? XI : 1], gch[GATHER ? XI : 1], gb[GATHER ? XI : 1], goy[GATHER ? XI : 1],
-      gox[GATHER ? XI : 1];
-  bool gok[GATHER ? XI : 1];
+  // GATHER: per X instruction u of this lane: the tap of its piece, the im2col row it fetches in stage 0
+  TnTap tap[GATHER ? XI : 1];
+  TnRow px[GATHER ? XI : 1];
   if constexpr (GATHER) {
-    const long ohw = (long)wg.OH * wg.OW;
 #pragma unroll
     for (int u = 0; u < XI; ++u) {
       const int q = XI * wave + u, r = q * (64 / XPPR) + lane / XPPR, c = lane % XPPR;
-      const unsigned k = (unsigned)(k0 + 8 * (c ^ xswz(r)));
-      const unsigned tap = __umulhi(k, wg.c_magic);
-      gch[u] = (int)(k - tap * wg.C);
-      const unsigned ky = wg.KW == 1 ? tap : __umulhi(tap, wg.kw_magic), kx = tap - ky * wg.KW;
-      gok[u] = (int)ky < wg.KH;
-      gdy[u] = (int)ky * wg.dil - wg.pad;
-      gdx[u] = (int)kx * wg.dil - wg.pad;
-      const long t = t0 + r;
-      gb[u] = (int)(t / ohw);
-      const int rem = (int)(t - gb[u] * ohw);
-      goy[u] = rem / wg.OW;
-      gox[u] = rem - goy[u] * wg.OW;
+      tap[u] = tn_tap(wg, (unsigned)(k0 + 8 * (c ^ xswz(r))));
+      px[u].seek(wg, t0 + r);
     }
   }
   // ---- DMA: instruction u of this wave moves 64 pieces = 64 / PPR rows of the tile; lane = (row, LDS piece slot), it fetches
@@ -1000,17 +795,10 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
       const long t = tb + r;
       const void* src;
       if constexpr (GATHER) {
-        const int iy = goy[u] * wg.stride + gdy[u], ix = gox[u] * wg.stride + gdx[u];
-        const bool ok = t < tend && gok[u] && (unsigned)iy < (unsigned)wg.H && (unsigned)ix < (unsigned)wg.W;
-        src = ok ? (const void*)(X + (((long)gb[u] * wg.H + iy) * wg.W + ix) * wg.C + gch[u]) : zero;
-        gox[u] += BT;                                  // the stage after this one (stages are issued in order)
-        while (gox[u] >= wg.OW) {
-          gox[u] -= wg.OW;
-          if (++goy[u] == wg.OH) {
-            goy[u] = 0;
-            ++gb[u];
-          }
-        }
+        const int iy = px[u].oy * wg.stride + tap[u].dy, ix = px[u].ox * wg.stride + tap[u].dx;
+        const bool ok = t < tend && tap[u].ok && (unsigned)iy < (unsigned)wg.H && (unsigned)ix < (unsigned)wg.W;
+        src = ok ? (const void*)(X + (((long)px[u].b * wg.H + iy) * wg.W + ix) * wg.C + tap[u].c) : zero;
+        px[u].advance(wg, BT);                         // the stage after this one (stages are issued in order)
       } else {
         src = t < tlim ? (const void*)(X + t * ldx + k0 + 8 * (c ^ xswz(r))) : zero;
       }
@@ -1145,19 +933,7 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
     }
   }
 
-  float* out = accumulate == 1 ? P : P + (long)slab * N * K;
-#pragma unroll
-  for (int i = 0; i < IB; ++i)
-#pragma unroll
-    for (int j = 0; j < JB; ++j) {
-      const int kk = k0 + wk * (BK / 2) + j * 32 + col;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * (BN / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (accumulate == 1) atomicAdd(out + (long)n * K + kk, acc[i][j][r]);
-        else out[(long)n * K + kk] = acc[i][j][r];
-      }
-    }
+  tn_store<IB, JB>(acc, P, accumulate, tt, N, K, wn, wk, g, col);
   if (do_bias) {                                  // lanes (col, g = 0 / 1) hold the two k-slot halves of column col
 #pragma unroll
     for (int i = 0; i < IB; ++i) {
@@ -1171,13 +947,13 @@ __device__ __forceinline__ void gemm_tn3_body(const uint16_t* __restrict__ G, co
 }
 
 template <int DT, int BN, int BK, int BT, bool GATHER = false, bool SEG = false>
-__global__ __launch_bounds__(256) void gemm_tn3_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
-                                                       float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
-                                                       int R, int tiles_k, int accumulate, float* __restrict__ gbias,
-                                                       const float* __restrict__ rowscale, int rows_per_sample,
-                                                       const void* zero, int xcd, WgradGeom wg = WgradGeom{}) {
-  gemm_tn3_body<DT, BN, BK, BT, GATHER, SEG>(G, X, P, T, N, K, ldg, ldx, R, tiles_k, accumulate, gbias, rowscale,
-                                             rows_per_sample, zero, xcd, wg, (int)blockIdx.x, (int)gridDim.x);
+__global__ __launch_bounds__(256) void gemm_tn_dma_kernel(const uint16_t* __restrict__ G, const uint16_t* __restrict__ X,
+                                                          float* __restrict__ P, int T, int N, int K, long ldg, long ldx,
+                                                          int R, int tiles_k, int accumulate, float* __restrict__ gbias,
+                                                          const float* __restrict__ rowscale, int rows_per_sample,
+                                                          const void* zero, WgradGeom wg = WgradGeom{}) {
+  gemm_tn_dma_body<DT, BN, BK, BT, GATHER, SEG>(G, X, P, T, N, K, ldg, ldx, R, tiles_k, accumulate, gbias, rowscale,
+                                                rows_per_sample, zero, wg, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Several weight gradients in ONE launch (round 5): the weight gradients of a MiT block's Linear layers are off the backward
@@ -1202,17 +978,23 @@ struct TnGroup {
 };
 
 template <int DT, bool SEG>
-__global__ __launch_bounds__(256) void gemm_tn3_group_kernel(TnGroup grp, const void* zero, int xcd) {
+__global__ __launch_bounds__(256) void gemm_tn_group_kernel(TnGroup grp, const void* zero) {
   int i = 0;
 #pragma unroll
   for (int k = 1; k < kTnGroupMax; ++k)
     if (k < grp.count && (int)blockIdx.x >= grp.p[k].first) i = k;
   const TnProblem& q = grp.p[i];
-  gemm_tn3_body<DT, 64, 64, 64, false, SEG>(q.G, q.X, q.P, q.T, q.N, q.K, q.ldg, q.ldx, q.R, q.tiles_k, 1, q.gbias, q.rowscale,
-                                            q.rows_per_sample, zero, xcd, WgradGeom{}, (int)blockIdx.x - q.first, q.nblk);
+  gemm_tn_dma_body<DT, 64, 64, 64, false, SEG>(q.G, q.X, q.P, q.T, q.N, q.K, q.ldg, q.ldx, q.R, q.tiles_k, 1, q.gbias, q.rowscale,
+                                               q.rows_per_sample, zero, WgradGeom{}, (int)blockIdx.x - q.first, q.nblk);
 }
 
 __device__ uint4 g_zero_page[4];          // zero-initialised: DMA source of out-of-image / padding pieces
+// its device address, looked up once (a library's first call is an eager warm-up, never inside a capture); null: lookup failed
+static const void* zero_page() {
+  static void* page = nullptr;
+  if (page == nullptr && hipGetSymbolAddress(&page, HIP_SYMBOL(g_zero_page)) != hipSuccess) page = nullptr;
+  return page;
+}
 
 // gemm2.hip (its own translation unit: this file is built with MFMA results in VGPRs, gemm2.h pins its accumulators to AGPRs)
 int launch_nt2(const void* X, const void* W, void* Y, long M, long N, long K, long ldx, long ldw, long ldy, const void* bias,
@@ -1222,10 +1004,8 @@ template <int DT, bool GATHER>
 static int launch_nt(const void* X, const void* W, void* Y, long M, long N, long K, long ldx, long ldw, long ldy,
                      const GemmEpi& epi, ConvGeom cg, hipStream_t s, bool out32 = false) {
   if (GATHER) {
-    static void* zero_page = nullptr;        // looked up once (first call is an eager warm-up, never inside a capture)
-    if (zero_page == nullptr && hipGetSymbolAddress(&zero_page, HIP_SYMBOL(g_zero_page)) != hipSuccess)
-      return fail(RFN_ELAUNCH, "conv2d_nhwc: zero page symbol");
-    cg.zero = zero_page;
+    cg.zero = zero_page();
+    if (cg.zero == nullptr) return fail(RFN_ELAUNCH, "conv2d_nhwc: zero page symbol");
   }
   // second-generation kernel (gemm2.h: software-pipelined K loop, stores dripped under the next tile's MFMAs) for the big
   // Linear layers whose column count is a multiple of 320 -- every GEMM of MiT-B5's stage 3 on the teacher's 40 views:
@@ -1233,13 +1013,12 @@ static int launch_nt(const void* X, const void* W, void* Y, long M, long N, long
   // other big problems with N % 256 == 0 (stages 2 / 4, the decode heads' 1 x 1 convolutions), which the 8-wave 256 x 256
   // tile of the first generation served.  
   if constexpr (!GATHER && DT == 1) {
-    constexpr int g2 = 2;
     constexpr long g2_min = 200;
     // (192 x 256 from K = 256 on: at K = 128 the 8-wave tile is 3-7 % faster, at K >= 512 the new one 1.1-1.45 x --
     // profiles/r04_gemm2_256_ab.txt)
-    const int bn2 = N % 320 == 0 ? 320 : (g2 >= 2 && N % 256 == 0 && K >= 256 ? 256 : 0);
+    const int bn2 = N % 320 == 0 ? 320 : (N % 256 == 0 && K >= 256 ? 256 : 0);
     const long t2 = bn2 ? (long)cdiv(M, 192) * (N / bn2) : 0;
-    if (g2 && bn2 && !out32 && K >= 192 && K % 64 == 0 && (epi.act & 255) == 0 && t2 >= g2_min &&
+    if (bn2 && !out32 && K >= 192 && K % 64 == 0 && epi.act == 0 && t2 >= g2_min &&
         (M + 192) * ldy * 2 < (1L << 32) && ldx < (1L << 22) && ldw < (1L << 22) && (((size_t)X | (size_t)W | (size_t)Y) & 15) == 0 &&
         (epi.res == nullptr || ((size_t)epi.res & 15) == 0)) {
       return launch_nt2(X, W, Y, M, N, K, ldx, ldw, ldy, epi.bias, epi.res, epi.rowscale, epi.rows_per_sample, bn2, t2, s);
@@ -1256,52 +1035,44 @@ static int launch_nt(const void* X, const void* W, void* Y, long M, long N, long
     bn = 64;
     if ((long)cdiv(M, 128) * cdiv(N, 64) < min_tiles) bm = 64;
   }
-  int ns = 2;
   // big problems whose n extent fills 256-wide tiles: 8 waves on a 256 x 256 tile (1 workgroup per CU); with a long
   // reduction (K >= 1024) already from 128 tiles on (20400 x 2048 -> 512: 74.8 -> 59.7 us)
   if (N % 256 == 0 && (long)cdiv(M, 256) * (N / 256) >= (K >= 1024 ? 128 : 256)) bm = bn = 256;
   const int tiles_m = cdiv(M, bm), tiles_n = cdiv(N, bn);
   const long total = (long)tiles_m * tiles_n;
-  // workgroups per CU by LDS (ns-deep ring of (bm + bn) * 128 bytes; 160 KB per CU), at most 4
-  const int ring = ns * (bm + bn) * 128;
+  // workgroups per CU by LDS (2-deep ring of (bm + bn) * 128 bytes; 160 KB per CU), at most 4
+  const int ring = 2 * (bm + bn) * 128;
   const int per_cu = std::max(1, std::min(160 * 1024 / ring, 4));
   // persistent (one pipeline across tiles) pays when a tile has only a few K-steps: the next tile's loads hide under the
   // epilogue.  With many K-steps per tile the plain one-tile-per-workgroup launch measured faster (dispatcher refills a CU
   // the moment a workgroup retires; its stores drain behind it).
   const bool persistent = K <= 256;
   const int slots = persistent ? 256 * per_cu : 0x7fffffff;
-  dim3 grid((unsigned)std::min<long>(total, slots)), block(256);
-#define RFN_NT(BM_, BN_, NS_)                                                                                            \
-  hipLaunchKernelGGL((gemm_nt_kernel<DT, BM_, BN_, 64, NS_, GATHER>), grid, block, 0, s, (const uint16_t*)X,             \
-                     (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total, epi,  \
-                     cg)
+  dim3 grid((unsigned)std::min<long>(total, slots));
+#define RFN_NT(BM_, BN_, NW_, OUT32_, GRID_, TILES_N_, TOTAL_)                                                            \
+  hipLaunchKernelGGL((gemm_nt_kernel<DT, BM_, BN_, 64, 2, GATHER, NW_, OUT32_>), GRID_, dim3(64 * NW_), 0, s,              \
+                     (const uint16_t*)X, (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, TILES_N_, \
+                     (int)(TOTAL_), epi, cg)
   if (out32) {                                  // fp32 result (split-bf16 parity mode): two tile shapes, no persistence
     bn = (N % 128 == 0) ? 128 : 64;
     bm = bn;
     const int tn = cdiv(N, bn);
     const long tot = (long)cdiv(M, bm) * tn;
     dim3 g32((unsigned)tot);
-    if (bn == 128)
-      hipLaunchKernelGGL((gemm_nt_kernel<DT, 128, 128, 64, 2, GATHER, 4, true>), g32, block, 0, s, (const uint16_t*)X,
-                         (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tn, (int)tot, epi, cg);
-    else
-      hipLaunchKernelGGL((gemm_nt_kernel<DT, 64, 64, 64, 2, GATHER, 4, true>), g32, block, 0, s, (const uint16_t*)X,
-                         (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tn, (int)tot, epi, cg);
+    if (bn == 128) RFN_NT(128, 128, 4, true, g32, tn, tot);
+    else RFN_NT(64, 64, 4, true, g32, tn, tot);
     return check_launch("gemm_nt (fp32 result)");
   }
-  const int key = bm * 10000 + bn * 10 + ns;
-  switch (key) {
-    case 1281282: RFN_NT(128, 128, 2); break;
-    case 1280642: RFN_NT(128, 64, 2); break;
-    case 641282: RFN_NT(64, 128, 2); break;
-    case 640642: RFN_NT(64, 64, 2); break;
-    case 2562562:
-      grid = dim3((unsigned)std::min<long>(total, persistent ? 256 : 0x7fffffff));
-      hipLaunchKernelGGL((gemm_nt_kernel<DT, 256, 256, 64, 2, GATHER, 8>), grid, dim3(512), 0, s, (const uint16_t*)X,
-                         (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total,
-                         epi, cg);
-      break;
-    default: return fail(RFN_EINVAL, "gemm_nt: no kernel for tile %dx%d ring %d", bm, bn, ns);
+  // (bm, bn) is one of 256 x 256, 128 x 128, 128 x 64, 64 x 64: bm drops to 64 only after bn has
+  if (bm == 256) {
+    grid = dim3((unsigned)std::min<long>(total, persistent ? 256 : 0x7fffffff));
+    RFN_NT(256, 256, 8, false, grid, tiles_n, total);
+  } else if (bn == 128) {
+    RFN_NT(128, 128, 4, false, grid, tiles_n, total);
+  } else if (bm == 128) {
+    RFN_NT(128, 64, 4, false, grid, tiles_n, total);
+  } else {
+    RFN_NT(64, 64, 4, false, grid, tiles_n, total);
   }
 #undef RFN_NT
   return check_launch("gemm_nt");
@@ -1312,59 +1083,56 @@ static int launch_tn(const void* G, const void* X, float* P, long T, long N, lon
                      int accumulate, float* gbias, const float* rowscale, int rps, hipStream_t s,
                      WgradGeom wg = WgradGeom{}) {
   const int S = cdiv(T, R);
-  dim3 block(256);
-  static const int tn_xcd = 1;
-  // (first-generation kernel = the fall-back for operands that are not 16-byte aligned; measured on the step: 189.2 ms with
-  // it everywhere, 185.8 ms with the second generation)
+  const bool big = N % 128 == 0 && K % 128 == 0;        // 128 x 128 tiles, else 64 x 64
+  dim3 grid((unsigned)(big ? (N / 128) * (K / 128) * S : (N / 64) * (K / 64) * S)), block(256);
+  // the DMA kernel moves 16-byte pieces: aligned operands, 8 columns (a convolution: channels of ONE tap) per piece; its
+  // stochastic-depth scale needs the slab's scales in 64 LDS floats (and is not combined with the gather)
   const bool vec = (GATHER ? wg.C % 8 == 0 : ldx % 8 == 0) && ((size_t)X & 15) == 0 && ldg % 8 == 0 && ((size_t)G & 15) == 0;
-  static const int tn3 = 1;
-  if (vec && tn3) {
-    // third generation (LDS-DMA + transpose reads); the stochastic-depth scale needs whole samples per 8-row fragment and the
-    // slab's scales in 64 LDS floats
-    const long span = rowscale != nullptr ? ((long)R + rps - 1) / rps + 1 : 0;
-    if (rowscale == nullptr || (!GATHER && span <= 64)) {
-      static void* zero_page = nullptr;
-      if (zero_page == nullptr && hipGetSymbolAddress(&zero_page, HIP_SYMBOL(g_zero_page)) != hipSuccess)
-        return fail(RFN_ELAUNCH, "gemm_tn: zero page symbol");
-      const bool big = N % 128 == 0 && K % 128 == 0;
-      dim3 grid((unsigned)(big ? (N / 128) * (K / 128) * S : (N / 64) * (K / 64) * S));
-#define RFN_TN3(BN_, BK_, BT_, SEG_)                                                                                      \
-  hipLaunchKernelGGL((gemm_tn3_kernel<DT, BN_, BK_, BT_, GATHER && !SEG_, SEG_>), grid, block, 0, s, (const uint16_t*)G, \
-                     (const uint16_t*)X, P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / BK_), accumulate, gbias,      \
-                     rowscale, rps, zero_page, tn_xcd, wg)
-      if (rowscale != nullptr) {
-        if (big) RFN_TN3(128, 128, 32, true);
-        else RFN_TN3(64, 64, 64, true);
-      } else {
-        if (big) RFN_TN3(128, 128, 32, false);
-        else RFN_TN3(64, 64, 64, false);
-      }
-#undef RFN_TN3
-      return check_launch("gemm_tn3");
-    }
+  const long span = rowscale != nullptr ? ((long)R + rps - 1) / rps + 1 : 0;
+  if (vec && (rowscale == nullptr || (!GATHER && span <= 64))) {
+    const void* zero = zero_page();
+    if (zero == nullptr) return fail(RFN_ELAUNCH, "gemm_tn: zero page symbol");
+#define RFN_TN_DMA(BN_, BK_, BT_, SEG_)                                                                                      \
+  hipLaunchKernelGGL((gemm_tn_dma_kernel<DT, BN_, BK_, BT_, GATHER && !SEG_, SEG_>), grid, block, 0, s, (const uint16_t*)G, \
+                     (const uint16_t*)X, P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / BK_), accumulate, gbias,         \
+                     rowscale, rps, zero, wg)
+    if (rowscale != nullptr && big) RFN_TN_DMA(128, 128, 32, true);
+    else if (rowscale != nullptr) RFN_TN_DMA(64, 64, 64, true);
+    else if (big) RFN_TN_DMA(128, 128, 32, false);
+    else RFN_TN_DMA(64, 64, 64, false);
+#undef RFN_TN_DMA
+    return check_launch("gemm_tn_dma_kernel");
   }
-  if (vec) {
-    if (N % 128 == 0 && K % 128 == 0) {
-      dim3 grid((unsigned)((N / 128) * (K / 128) * S));
-      hipLaunchKernelGGL((gemm_tn2_kernel<DT, 128, 128, 32, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X,
-                         P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 128), accumulate, gbias, rowscale, rps, wg, tn_xcd);
-    } else {
-      dim3 grid((unsigned)((N / 64) * (K / 64) * S));
-      hipLaunchKernelGGL((gemm_tn2_kernel<DT, 64, 64, 64, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X,
-                         P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 64), accumulate, gbias, rowscale, rps, wg, tn_xcd);
-    }
-    return check_launch("gemm_tn2");
-  }
-  if (N % 128 == 0 && K % 128 == 0) {
-    dim3 grid((unsigned)((N / 128) * (K / 128) * S));
-    hipLaunchKernelGGL((gemm_tn_kernel<DT, 128, 128, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X, P,
-                       (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 128), accumulate, gbias, rowscale, rps, wg, tn_xcd);
-  } else {
-    dim3 grid((unsigned)((N / 64) * (K / 64) * S));
-    hipLaunchKernelGGL((gemm_tn_kernel<DT, 64, 64, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X, P,
-                       (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 64), accumulate, gbias, rowscale, rps, wg, tn_xcd);
-  }
-  return check_launch("gemm_tn");
+  // everything else the ABI admits (the step with this kernel for every weight gradient: 189.2 ms, with 16-byte loads: 185.8 ms)
+  if (big)
+    hipLaunchKernelGGL((gemm_tn_fallback_kernel<DT, 128, 128, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X,
+                       P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 128), accumulate, gbias, rowscale, rps, wg);
+  else
+    hipLaunchKernelGGL((gemm_tn_fallback_kernel<DT, 64, 64, GATHER>), grid, block, 0, s, (const uint16_t*)G, (const uint16_t*)X,
+                       P, (int)T, (int)N, (int)K, ldg, ldx, R, (int)(K / 64), accumulate, gbias, rowscale, rps, wg);
+  return check_launch("gemm_tn_fallback_kernel");
+}
+
+// ---- geometry of the convolution entry points (callers have checked kernel, stride, dilation > 0, pad >= 0)
+static int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
+static unsigned magic(long d) { return (unsigned)((0x100000000ULL + d - 1) / d); }       // ceil(2^32 / d)
+static long conv_kpad(int KH, int KW, int C) { return ((long)KH * KW * C + 63) / 64 * 64; }   // (tap, c) padded to whole K-steps
+// forward gather: X (B, H, W, C) -> rows (b, oy, ox); OH / OW <= 0: empty output
+static ConvGeom conv_geom(int H, int Wd, int C, int KH, int KW, int stride, int pad, int dil) {
+  return {H, Wd, C, conv_out(H, KH, stride, pad, dil), conv_out(Wd, KW, stride, pad, dil), KH, KW, stride, pad, dil, C / 8,
+          magic(C / 8), magic(KW), nullptr, 0, 0};
+}
+// transposed gather (the data gradient of the convolution above with N output channels): the gathered tensor is grad_y
+// (B, OH, OW, N) -- so the geometry's H / W / C are the convolution's OH / OW / N -- and the rows are the input pixels (b, iy, ix)
+static ConvGeom conv_geom_dgrad(int H, int Wd, int N, int KH, int KW, int stride, int pad, int dil) {
+  int sshift = 0;
+  while ((1 << sshift) < stride) ++sshift;
+  return {conv_out(H, KH, stride, pad, dil), conv_out(Wd, KW, stride, pad, dil), N, H, Wd, KH, KW, stride, pad, dil, N / 8,
+          magic(N / 8), magic(KW), nullptr, 1, sshift};
+}
+static WgradGeom wgrad_geom(int H, int Wd, int C, int KH, int KW, int stride, int pad, int dil) {
+  return {H, Wd, C, conv_out(H, KH, stride, pad, dil), conv_out(Wd, KW, stride, pad, dil), KH, KW, stride, pad, dil, magic(C),
+          magic(KW)};
 }
 
 }  // namespace rfn
@@ -1375,10 +1143,6 @@ int rfn_gemm_nt(const void* X, const void* W, const void* bias, const void* res,
                 int rows_per_sample, int act, void* Y, long M, long N, long K, long ldx, long ldw, long ldy, int dtype,
                 rfn_stream_t stream) {
   using namespace rfn;
-#ifdef RFN_GEMM_PROFILE
-  static const int prof = 0;
-  const int act_arg = act;
-#endif
   RFN_REQUIRE(X && W && Y, "gemm_nt: null operand");
   RFN_REQUIRE(dtype == 1 || dtype == 2, "gemm_nt: dtype %d (1 = bf16, 2 = f16)", dtype);
   RFN_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0, "gemm_nt: M=%ld N=%ld K=%ld (K %% 64, N %% 8)", M, N, K);
@@ -1389,13 +1153,9 @@ int rfn_gemm_nt(const void* X, const void* W, const void* bias, const void* res,
   RFN_REQUIRE(act == 0 || act == 1 || act == 3 || (act == 4 && res != nullptr),
               "gemm_nt: act (0 none, 1 ReLU, 3 LeakyReLU 0.1, 4 = times gelu'(res), needs res)");
   GemmEpi epi{(const uint16_t*)bias, (const uint16_t*)res, rowscale, rows_per_sample > 0 ? rows_per_sample : 1, act};
-#ifdef RFN_GEMM_PROFILE
-  epi.act = act_arg | (prof << 8);
-#endif
   hipStream_t s = (hipStream_t)stream;
-  ConvGeom cg{};
-  return dtype == 1 ? launch_nt<1, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, cg, s)
-                    : launch_nt<2, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, cg, s);
+  return dtype == 1 ? launch_nt<1, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, s)
+                    : launch_nt<2, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, s);
 }
 
 int rfn_conv2d_nhwc(const void* X, const void* W, const void* bias, const void* res, int act, void* Y, int B, int H,
@@ -1408,16 +1168,14 @@ int rfn_conv2d_nhwc(const void* X, const void* W, const void* bias, const void* 
               "(C %% 8, N %% 8)", B, H, Wd, C, N);
   RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_nhwc: kernel %dx%d stride %d pad %d dil %d",
               KH, KW, stride, pad, dil);
-  const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, OW = (Wd + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  RFN_REQUIRE(OH > 0 && OW > 0, "conv2d_nhwc: empty output");
-  const long K = ((long)KH * KW * C + 63) / 64 * 64, M = (long)B * OH * OW;
+  const ConvGeom cg = conv_geom(H, Wd, C, KH, KW, stride, pad, dil);
+  RFN_REQUIRE(cg.OH > 0 && cg.OW > 0, "conv2d_nhwc: empty output");
+  const long K = conv_kpad(KH, KW, C), M = (long)B * cg.OH * cg.OW;
   RFN_REQUIRE(ldw % 8 == 0 && ldw >= K && ldy % 8 == 0 && ldy >= N, "conv2d_nhwc: ldw=%ld (>= %ld, padded k) ldy=%ld", ldw,
               K, ldy);
   RFN_REQUIRE(M < (1L << 31) && K / 8 < 65536 && (long)H * Wd * C < (1L << 31), "conv2d_nhwc: extent");
   RFN_REQUIRE(act == 0 || act == 1 || act == 3, "conv2d_nhwc: act (0 none, 1 ReLU, 3 LeakyReLU 0.1)");
   GemmEpi epi{(const uint16_t*)bias, (const uint16_t*)res, nullptr, 1, act};
-  ConvGeom cg{H, Wd, C, OH, OW, KH, KW, stride, pad, dil, C / 8, (unsigned)((0x100000000ULL + C / 8 - 1) / (C / 8)),
-              (unsigned)((0x100000000ULL + KW - 1) / KW), nullptr, 0, 0};
   hipStream_t s = (hipStream_t)stream;
   if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && res == nullptr) {
     // halo-tiled form (conv3x3.hip): the input tile staged once per 64 channels instead of once per tap
@@ -1439,8 +1197,7 @@ int rfn_gemm_nt_o32(const void* X, const void* W, const float* bias, const float
   RFN_REQUIRE(rowscale == nullptr || rows_per_sample > 0, "gemm_nt_o32: rowscale needs rows_per_sample");
   RFN_REQUIRE(act == 0 || act == 1 || act == 3, "gemm_nt_o32: act");
   GemmEpi epi{(const uint16_t*)bias, (const uint16_t*)res, rowscale, rows_per_sample > 0 ? rows_per_sample : 1, act};
-  ConvGeom cg{};
-  return launch_nt<1, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, cg, (hipStream_t)stream, true);
+  return launch_nt<1, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, (hipStream_t)stream, true);
 }
 
 int rfn_conv2d_nhwc_o32(const void* X, const void* W, const float* bias, int act, float* Y, int B, int H, int Wd, int C, int N,
@@ -1452,29 +1209,19 @@ int rfn_conv2d_nhwc_o32(const void* X, const void* W, const float* bias, int act
   RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0 && (!transposed || (stride & (stride - 1)) == 0),
               "conv2d_nhwc_o32: geometry");
   RFN_REQUIRE(act == 0 || act == 1 || act == 3, "conv2d_nhwc_o32: act");
-  const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, OW = (Wd + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  RFN_REQUIRE(OH > 0 && OW > 0, "conv2d_nhwc_o32: empty output");
+  // forward: X (B, H, W, C) -> Y (B, OH, OW, N), W[n][(tap, c)];  data gradient: X = grad_y (B, OH, OW, N), Y = dx (B, H, W, C),
+  // W = Wt[c][(tap, n)].  Either way the GEMM's rows are Y's pixels, its reduction X's (tap, channel), its columns Y's channels
+  const ConvGeom cg = transposed ? conv_geom_dgrad(H, Wd, N, KH, KW, stride, pad, dil) : conv_geom(H, Wd, C, KH, KW, stride, pad, dil);
+  RFN_REQUIRE(cg.H > 0 && cg.W > 0 && cg.OH > 0 && cg.OW > 0, "conv2d_nhwc_o32: empty output");
+  const long K = conv_kpad(KH, KW, cg.C), M = (long)B * cg.OH * cg.OW, cols = transposed ? C : N;
+  RFN_REQUIRE(ldw % 8 == 0 && ldw >= K && ldy % 4 == 0 && ldy >= cols && M < (1L << 31) && K / 8 < 65536, "conv2d_nhwc_o32: ld");
   GemmEpi epi{(const uint16_t*)bias, nullptr, nullptr, 1, act};
   hipStream_t s = (hipStream_t)stream;
-  if (!transposed) {           // forward: X (B, H, W, C) -> Y (B, OH, OW, N), W[n][(tap, c)]
-    const long K = ((long)KH * KW * C + 63) / 64 * 64, M = (long)B * OH * OW;
-    RFN_REQUIRE(ldw % 8 == 0 && ldw >= K && ldy % 4 == 0 && ldy >= N && M < (1L << 31) && K / 8 < 65536, "conv2d_nhwc_o32: ld");
-    ConvGeom cg{H, Wd, C, OH, OW, KH, KW, stride, pad, dil, C / 8, (unsigned)((0x100000000ULL + C / 8 - 1) / (C / 8)),
-                (unsigned)((0x100000000ULL + KW - 1) / KW), nullptr, 0, 0};
-    if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1) {       // halo-tiled form (conv3x3.hip)
-      const int rc = launch_conv3x3_halo(X, W, bias, Y, B, H, Wd, C, N, ldw, ldy, act, 1, 1, s);
-      if (rc != 1) return rc;
-    }
-    return launch_nt<1, true>(X, W, Y, M, N, K, 0, ldw, ldy, epi, cg, s, true);
+  if (!transposed && KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1) {       // halo-tiled form (conv3x3.hip)
+    const int rc = launch_conv3x3_halo(X, W, bias, Y, B, H, Wd, C, N, ldw, ldy, act, 1, 1, s);
+    if (rc != 1) return rc;
   }
-  // data gradient: X = grad_y (B, OH, OW, N), Y = dx (B, H, W, C), W = Wt[c][(tap, n)]
-  const long K = ((long)KH * KW * N + 63) / 64 * 64, M = (long)B * H * Wd;
-  RFN_REQUIRE(ldw % 8 == 0 && ldw >= K && ldy % 4 == 0 && ldy >= C && M < (1L << 31) && K / 8 < 65536, "conv2d_nhwc_o32: ld");
-  int sshift = 0;
-  while ((1 << sshift) < stride) ++sshift;
-  ConvGeom cg{OH, OW, N, H, Wd, KH, KW, stride, pad, dil, N / 8, (unsigned)((0x100000000ULL + N / 8 - 1) / (N / 8)),
-              (unsigned)((0x100000000ULL + KW - 1) / KW), nullptr, 1, sshift};
-  return launch_nt<1, true>(X, W, Y, M, C, K, 0, ldw, ldy, epi, cg, s, true);
+  return launch_nt<1, true>(X, W, Y, M, cols, K, 0, ldw, ldy, epi, cg, s, true);
 }
 
 int rfn_conv2d_nhwc_dgrad(const void* GY, const void* Wt, void* DX, int B, int H, int Wd, int C, int N, int KH, int KW,
@@ -1486,18 +1233,15 @@ int rfn_conv2d_nhwc_dgrad(const void* GY, const void* Wt, void* DX, int B, int H
               "N=%d (C %% 8, N %% 8)", B, H, Wd, C, N);
   RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && (stride & (stride - 1)) == 0 && dil > 0 && pad >= 0,
               "conv2d_nhwc_dgrad: kernel %dx%d stride %d (power of two) pad %d dil %d", KH, KW, stride, pad, dil);
-  const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, OW = (Wd + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const ConvGeom cg = conv_geom_dgrad(H, Wd, N, KH, KW, stride, pad, dil);
+  const int OH = cg.H, OW = cg.W;                    // grad_y's extent
   RFN_REQUIRE(OH > 0 && OW > 0, "conv2d_nhwc_dgrad: empty output");
   // GEMM view: rows = input pixels (B, H, W), reduction = (tap, n) over grad_y's channels, result columns = C
-  const long K = ((long)KH * KW * N + 63) / 64 * 64, M = (long)B * H * Wd;
+  const long K = conv_kpad(KH, KW, N), M = (long)B * H * Wd;
   RFN_REQUIRE(ldw % 8 == 0 && ldw >= K && ldy % 8 == 0 && ldy >= C, "conv2d_nhwc_dgrad: ldw=%ld (>= %ld, padded k) ldy=%ld", ldw,
               K, ldy);
   RFN_REQUIRE(M < (1L << 31) && K / 8 < 65536 && (long)OH * OW * N < (1L << 31), "conv2d_nhwc_dgrad: extent");
-  int sshift = 0;
-  while ((1 << sshift) < stride) ++sshift;
   GemmEpi epi{nullptr, nullptr, nullptr, 1, 0};
-  ConvGeom cg{OH, OW, N, H, Wd, KH, KW, stride, pad, dil, N / 8, (unsigned)((0x100000000ULL + N / 8 - 1) / (N / 8)),
-              (unsigned)((0x100000000ULL + KW - 1) / KW), nullptr, 1, sshift};
   hipStream_t s = (hipStream_t)stream;
   return dtype == 1 ? launch_nt<1, true>(GY, Wt, DX, M, C, K, 0, ldw, ldy, epi, cg, s)
                     : launch_nt<2, true>(GY, Wt, DX, M, C, K, 0, ldw, ldy, epi, cg, s);
@@ -1513,18 +1257,16 @@ int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_b
               "(C %% 2, N %% 64)", B, H, Wd, C, N);
   RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_nhwc_wgrad: kernel %dx%d stride %d pad %d dil %d", KH,
               KW, stride, pad, dil);
-  const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1, OW = (Wd + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  RFN_REQUIRE(OH > 0 && OW > 0, "conv2d_nhwc_wgrad: empty output");
-  const long T = (long)B * OH * OW;
+  const WgradGeom wg = wgrad_geom(H, Wd, C, KH, KW, stride, pad, dil);
+  RFN_REQUIRE(wg.OH > 0 && wg.OW > 0, "conv2d_nhwc_wgrad: empty output");
+  const long T = (long)B * wg.OH * wg.OW;
   RFN_REQUIRE(Kpad % 64 == 0 && Kpad >= (long)KH * KW * C && ldg % 2 == 0 && ldg >= N, "conv2d_nhwc_wgrad: Kpad=%ld ldg=%ld", Kpad, ldg);
   RFN_REQUIRE(T < (1L << 31) && (long)B * H * Wd * C < (1L << 31) && rows_per_slab > 0 && rows_per_slab % 32 == 0,
               "conv2d_nhwc_wgrad: extent / rows_per_slab");
-  auto magic = [](long d) { return (unsigned)((0x100000000ULL + d - 1) / d); };
   RFN_REQUIRE(Kpad < 65536, "conv2d_nhwc_wgrad: Kpad=%ld", Kpad);
   RFN_REQUIRE(accumulate >= 0 && accumulate <= 2, "conv2d_nhwc_wgrad: accumulate %d (0, 1 or 2)", accumulate);
   RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_conv2d_nhwc_wgrad",
                     "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
-  WgradGeom wg{H, Wd, C, OH, OW, KH, KW, stride, pad, dil, magic(C), magic(KW)};
   hipStream_t s = (hipStream_t)stream;
   return dtype == 1 ? launch_tn<1, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg)
                     : launch_tn<2, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg);
@@ -1556,7 +1298,7 @@ int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, f
   RFN_REQUIRE(G && X && P && grad_bias && rowscale && T && N && K && ldg && ldx && rows_per_slab && rows_per_sample,
               "gemm_tn_grouped: null array");
   RFN_REQUIRE(dtype == 1 || dtype == 2, "gemm_tn_grouped: dtype %d", dtype);
-  RFN_REFUSE_NONDET(true, "rfn_gemm_tn_grouped", "gemm_tn3_group_kernel, fp32 atomics (use rfn_gemm_tn with accumulate = 2)");
+  RFN_REFUSE_NONDET(true, "rfn_gemm_tn_grouped", "gemm_tn_group_kernel, fp32 atomics (use rfn_gemm_tn with accumulate = 2)");
   TnGroup grp{};
   grp.count = count;
   long blocks = 0;
@@ -1575,38 +1317,24 @@ int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, f
       const long span = ((long)rows_per_slab[i] + rows_per_sample[i] - 1) / rows_per_sample[i] + 1;
       RFN_REQUIRE(span <= 64, "gemm_tn_grouped: more than 64 samples per slab");
     }
-    TnProblem& q = grp.p[i];
-    q.G = (const uint16_t*)G[i];
-    q.X = (const uint16_t*)X[i];
-    q.P = P[i];
-    q.gbias = grad_bias[i];
-    q.rowscale = rowscale[i];
-    q.ldg = ldg[i];
-    q.ldx = ldx[i];
-    q.T = (int)T[i];
-    q.N = (int)N[i];
-    q.K = (int)K[i];
-    q.R = rows_per_slab[i];
-    q.tiles_k = (int)(K[i] / 64);
-    q.rows_per_sample = rows_per_sample[i];
-    q.first = (int)blocks;
-    q.nblk = (int)((N[i] / 64) * (K[i] / 64) * S);
-    blocks += q.nblk;
+    const int nblk = (int)((N[i] / 64) * (K[i] / 64) * S);
+    grp.p[i] = TnProblem{(const uint16_t*)G[i], (const uint16_t*)X[i], P[i], grad_bias[i], rowscale[i], ldg[i], ldx[i], (int)T[i],
+                         (int)N[i], (int)K[i], rows_per_slab[i], (int)(K[i] / 64), rows_per_sample[i], (int)blocks, nblk};
+    blocks += nblk;
     RFN_REQUIRE(blocks < (1L << 31), "gemm_tn_grouped: grid too large");
   }
-  static void* zero_page = nullptr;
-  if (zero_page == nullptr && hipGetSymbolAddress(&zero_page, HIP_SYMBOL(g_zero_page)) != hipSuccess)
-    return fail(RFN_ELAUNCH, "gemm_tn_grouped: zero page symbol");
+  const void* zero = zero_page();
+  if (zero == nullptr) return fail(RFN_ELAUNCH, "gemm_tn_grouped: zero page symbol");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)blocks), block(256);
   if (dtype == 1) {
-    if (seg) hipLaunchKernelGGL((gemm_tn3_group_kernel<1, true>), grid, block, 0, s, grp, (const void*)zero_page, 1);
-    else hipLaunchKernelGGL((gemm_tn3_group_kernel<1, false>), grid, block, 0, s, grp, (const void*)zero_page, 1);
+    if (seg) hipLaunchKernelGGL((gemm_tn_group_kernel<1, true>), grid, block, 0, s, grp, zero);
+    else hipLaunchKernelGGL((gemm_tn_group_kernel<1, false>), grid, block, 0, s, grp, zero);
   } else {
-    if (seg) hipLaunchKernelGGL((gemm_tn3_group_kernel<2, true>), grid, block, 0, s, grp, (const void*)zero_page, 1);
-    else hipLaunchKernelGGL((gemm_tn3_group_kernel<2, false>), grid, block, 0, s, grp, (const void*)zero_page, 1);
+    if (seg) hipLaunchKernelGGL((gemm_tn_group_kernel<2, true>), grid, block, 0, s, grp, zero);
+    else hipLaunchKernelGGL((gemm_tn_group_kernel<2, false>), grid, block, 0, s, grp, zero);
   }
-  return check_launch("gemm_tn3_group_kernel");
+  return check_launch("gemm_tn_group_kernel");
 }
 
 }  // extern "C"

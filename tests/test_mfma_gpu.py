@@ -232,6 +232,104 @@ def test_gemm_tn_accumulates_into_gradient_views(dev, T, N, K):
     assert float((gb.double() - want_b).abs().max()) <= 2e-5 * float(want_b.abs().max()) * math.sqrt(T / 1000 + 1) + 1e-3
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("T,N,K,rows", [(1000, 64, 64, 96), (300, 128, 128, None)])
+def test_gemm_tn_fallback_on_four_byte_aligned_views(dev, dtype, T, N, K, rows):
+    """Operands that are column slices [:, 2:] of buffers two columns wider: the data pointers sit 4 bytes past a 16-byte
+    boundary and the row pitches (66, 130) are no multiples of 8, so launch_tn's `vec` condition fails and the launch goes to
+    gemm_tn_fallback_kernel (dword loads, register transpose) -- mfma._tn_domain admits such views (pitch % 2, pointer % 4).
+    (1000, 64, 64) in slabs of 96 rows: 64 x 64 tiles, eleven slabs, the last one 40 rows = a full and a ragged stage of 32.
+    (300, 128, 128): 128 x 128 tiles, slabs of 256 rows (slab_rows' minimum), the second one 44 rows.
+    Three forms each: slab partials, fp32 atomics on top of what `out` / `bias_out` hold, and the deterministic form of the
+    latter (accumulate = 2: stored slab partials and per-slab bias rows, added by sum_rows).  Against fp64 products of the
+    same 16-bit operands, with the bounds of the tests above."""
+    from refign_amd import determinism
+    from refign_amd.mfma import gemm_tn
+    g = _rand((T, N + 2), dev, dtype, 50)[:, 2:2 + N]
+    x = _rand((T, K + 2), dev, dtype, 51)[:, 2:2 + K]
+    for t in (g, x):
+        assert t.data_ptr() % 16 == 4 and t.stride(0) % 8 != 0 and t.stride(0) % 2 == 0
+    want = g.double().t() @ x.double()
+    want_b = g.double().sum(0)
+    root = math.sqrt(T / 1000 + 1)
+    part = gemm_tn(g, x, rows)
+    assert part is not None and part.dtype == torch.float32 and part.shape[1:] == (N, K)
+    assert float((part.double().sum(0) - want).abs().max()) <= 1e-5 * float(want.abs().max()) * root + 1e-3
+    gw0 = torch.randn(N, K, device=dev)
+    gb0 = torch.randn(N, device=dev)
+    want_w, want_b = gw0.double() + want, gb0.double() + want_b
+    for det in (False, True):
+        gw, gb = gw0.clone(), gb0.clone()
+        if det:
+            with determinism.deterministic():
+                assert gemm_tn(g, x, rows, out=gw, bias_out=gb) is gw
+        else:
+            assert gemm_tn(g, x, rows, out=gw, bias_out=gb) is gw
+        assert float((gw.double() - want_w).abs().max()) <= 2e-5 * float(want_w.abs().max()) * root + 1e-3, det
+        assert float((gb.double() - want_b).abs().max()) <= 2e-5 * float(want_b.abs().max()) * root + 1e-3, det
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("rows_per_sample", [4, 5])
+def test_gemm_tn_row_scale_beyond_64_samples_per_slab(dev, dtype, rows_per_sample, T=520, N=64, K=64, rows=256):
+    """Both sides of launch_tn's `span <= 64` boundary (span = the samples a slab of 256 rows can touch, ceil(256 / rps) + 1),
+    aligned operands, accumulate form with a bias, scales from {0, 1 / 0.9} (stochastic depth, p = 0.1):
+    rows_per_sample = 4: span 65 -> gemm_tn_fallback_kernel.  It scales G in fp32 and rounds it back to the 16-bit type like
+      the eager `g * mask`, so the reference is the fp64 product of that ROUNDED tensor with x (bias: its column sums).
+    rows_per_sample = 5: span 53 -> gemm_tn_dma_kernel<SEG>, which scales the fp32 products of each sample: the reference is
+      the fp64 product of the unrounded scaled g, as in test_grouped_weight_gradients_match_fp64."""
+    from refign_amd.mfma import gemm_tn
+    g = _rand((T, N), dev, dtype, 52)
+    x = _rand((T, K), dev, dtype, 53)
+    nsamples = -(-T // rows_per_sample)
+    gen = torch.Generator(device="cpu").manual_seed(54)
+    rs = ((torch.rand(nsamples, generator=gen) < 0.7).float() / 0.9).to(dev)
+    assert 0 < int((rs == 0).sum()) < nsamples
+    per_row = rs.repeat_interleave(rows_per_sample)[:T, None]
+    gd = (g.float() * per_row).to(dtype).double() if rows_per_sample == 4 else g.double() * per_row.double()
+    gw0 = torch.randn(N, K, device=dev)
+    gb0 = torch.randn(N, device=dev)
+    gw, gb = gw0.clone(), gb0.clone()
+    assert gemm_tn(g, x, rows, out=gw, bias_out=gb, rowscale=rs, rows_per_sample=rows_per_sample) is gw
+    want_w = gw0.double() + gd.t() @ x.double()
+    want_b = gb0.double() + gd.sum(0)
+    tol = 2e-5 * math.sqrt(T / 1000 + 1)
+    assert float((gw.double() - want_w).abs().max()) <= tol * float(want_w.abs().max()) + 1e-3
+    assert float((gb.double() - want_b).abs().max()) <= tol * float(want_b.abs().max()) + 1e-3
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,H,W,C,N,k,stride,pad,dil", [(2, 9, 11, 4, 64, 3, 1, 1, 1), (2, 9, 11, 12, 128, 3, 1, 2, 2)])
+def test_conv_wgrad_fallback_channels_not_a_multiple_of_8(dev, dtype, B, H, W, C, N, k, stride, pad, dil):
+    """mfma.conv2d_nhwc_wgrad with C % 8 != 0 (the ABI admits C % 2): a 16-byte piece would span two taps, launch_tn's `vec`
+    condition fails and the gathered form of gemm_tn_fallback_kernel runs (a dword = a channel pair of one tap).
+    C = 4: Kpad = 64 for 36 real columns, 64 x 64 tile, sixteen taps' worth of columns in one k-step, 28 padding columns.
+    C = 12, dilation 2: Kpad = 128 for 108 real columns, 128 x 128 tile.
+    Against fp64 autograd of F.conv2d on the same 16-bit operands, rearranged to [n][(ky, kx, c)]; the padding columns must be
+    exactly zero; the bias gradient is added on top of what `bias_out` holds."""
+    import torch.nn.functional as F
+    from refign_amd import mfma
+    x = _rand((B, C, H, W), dev, dtype, 55)
+    w = torch.zeros((N, C, k, k), dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(x.cpu().double(), w, None, stride, pad, dil)
+    gy = _rand(tuple(y.shape), dev, dtype, 56)
+    y.backward(gy.cpu().double())
+    want = w.grad.permute(0, 2, 3, 1).reshape(N, k * k * C).to(dev)
+    Kpad = -(-k * k * C // 64) * 64
+    gb0 = torch.randn(N, device=dev)
+    gb = gb0.clone()
+    part = mfma.conv2d_nhwc_wgrad(gy.permute(0, 2, 3, 1).contiguous(), x.permute(0, 2, 3, 1).contiguous(), k, k, Kpad, stride, pad,
+                                  dil, bias_out=gb)
+    assert part is not None and part.shape[1:] == (N, Kpad)
+    T = gy.numel() // N
+    root = math.sqrt(T / 1000 + 1)
+    got = part.double().sum(0)
+    assert float((got[:, :k * k * C] - want).abs().max()) <= 1e-5 * float(want.abs().max()) * root + 1e-3
+    assert float(part[:, :, k * k * C:].abs().max()) == 0.0
+    want_b = gb0.double() + gy.double().sum((0, 2, 3))
+    assert float((gb.double() - want_b).abs().max()) <= 2e-5 * float(want_b.abs().max()) * root + 1e-3
+
+
 @pytest.mark.parametrize("scaled", [False, True])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_grouped_weight_gradients_match_fp64(dev, dtype, scaled):

@@ -113,7 +113,7 @@ def test_implicit_gemm_convolution_is_repeatable_under_memory_load():
 
 @pytest.mark.parametrize("T,N,K", [(8160, 1280, 320), (8160, 320, 320), (129600, 256, 1024)])
 def test_weight_gradient_partials_are_repeatable_under_memory_load(T, N, K):
-    """gemm_tn3_kernel, deterministic form (fp32 partials per slab): 40 launches."""
+    """gemm_tn_dma_kernel, deterministic form (fp32 partials per slab): 40 launches."""
     from refign_amd import mfma
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(4)
