@@ -264,6 +264,12 @@ unsigned long rfn_dwconv3x3_bwd_weight_workspace_bytes(int C);
 int rfn_dwconv3x3_nhwc_bwd_weight(const void* x, const void* grad_y, float* grad_weight, float* grad_bias,
                                   void* workspace, int B, int H, int W, int C, int dilation, int dtype, int flags,
                                   rfn_stream_t stream);
+/* The whole backward in one pass over grad_y: grad_x (what rfn_dwconv3x3_nhwc_fwd(grad_y, weight, NULL, flip = 1) gives) AND
+ * grad_weight / grad_bias (what rfn_dwconv3x3_nhwc_bwd_weight gives, same workspace, same `flags`, same sums in the same
+ * order: deterministic) -- grad_y, x and grad_x cross memory once each.  weight_tap_major: the forward's (9, C) weight. */
+int rfn_dwconv3x3_nhwc_bwd(const void* x, const void* grad_y, const float* weight_tap_major, void* grad_x, float* grad_weight,
+                           float* grad_bias, void* workspace, int B, int H, int W, int C, int dilation, int dtype, int flags,
+                           rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim of a (rows, C) matrix, C <= 1024 -- the 213 LayerNorms of a MiT-B5 forward

@@ -18,7 +18,8 @@
 //   backward-data dx           = same stencil over gy with the taps flipped, no bias
 //   backward-wgt  dw[c,ky,kx]  = sum_{b,h,w} gy[b,h,w,c] * x[b, h+(ky-1)d, w+(kx-1)d, c];   db[c] = sum gy
 //                 (per-thread register partials over its pixel quads -> LDS tree over the block's pixel lanes ->
-//                  one workspace row per stripe -> fixed-order reduction kernel: deterministic, no atomics)
+//                  one workspace row per block row -> fixed-order reduction kernel: deterministic, no atomics)
+//   backward      both of them from ONE pass over gy (dwconv3x3_bwd_kernel): gy, x and dx cross HBM once each
 #include <hip/hip_bf16.h>
 
 #include <type_traits>
@@ -604,95 +605,173 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
   }
 }
 
-// backward-weight, stage 1: register partials over the thread's quads, LDS tree over the block's pixel lanes, one
-// partial row per (stripe = blockIdx.y) in the workspace: ws[stripe][k][C], k = 0..8 taps, 9 = bias.  No atomics.
+// Vector I/O of dwconv3x3_bwd_kernel: 4 channels per lane for every activation type (fp32: VecIO; 16-bit: 8-byte vectors, as
+// dwconv3x3_roll_kernel) -- with 8 channels the 72 weights, 72 weight partials, 32 accumulators and 32 values of x do not fit in
+// the 256 registers of 2 waves per SIMD (the 8-channel build spilled 356 bytes per lane).
 template <typename T>
-__global__ __launch_bounds__(256) void dwconv3x3_bwd_weight_kernel(const T* __restrict__ x, const T* __restrict__ gy,
-                                                                   float* __restrict__ ws, int B, int H, int W, int C,
-                                                                   int dil, int cvb) {
-  constexpr int V = VecIO<T>::N;
+struct BwdIO {
+  static constexpr int N = kRV;
+  typedef uint2 Raw;
+  __device__ static Raw load_raw(const T* p) { return *reinterpret_cast<const uint2*>(p); }
+  __device__ static void unpack2(const Raw& t, f32x2 (&v)[2]) { v[0] = pair_f32<T>(t.x); v[1] = pair_f32<T>(t.y); }
+  __device__ static void store(T* p, const float (&v)[4]) {
+    *reinterpret_cast<uint2*>(p) = make_uint2(VecIO<T>::pack(v[0], v[1]), VecIO<T>::pack(v[2], v[3]));
+  }
+};
+template <>
+struct BwdIO<float> : VecIO<float> {};
+
+// Backward, both gradients from ONE pass over gy.  With y[p] = sum_d w[d] x[p + d dil]:
+//   gx[q] = sum_d w[d] gy[q - d dil]        gw[d] = sum_q x[q] gy[q - d dil]        gb = sum_q gy[q]
+// so a thread that holds the 3 x 6 window of gy around its quad q (the window of dwconv3x3_fwd_kernel<FLIP>) needs only the
+// 4 vectors of x AT q on top: the window value v at offset ((ky - 1) dil, (kx - 1) dil), k = 3 ky + kx, enters
+// gx[q] += w[8 - k] v and gw[8 - k] += x[q] v; the centre row of the window is gb's.  gy, x and gx cross HBM once each (the
+// two-kernel form read gy twice and an 18-vector window of x).  Out-of-image window values are zero (select on the packed
+// data) and x is zero for the pixels of a quad past the row end, whose gx is not stored.
+//  * either launch geometry of dwconv3x3_fwd_kernel; idle threads stay for the block's fold.
+//  * weight / bias partials: registers over the thread's quads -> LDS fold over the block's pixel lanes -> ONE workspace row
+//    per block row, ws[row][k][C] (k = 0..8 taps, 9 = bias) -> dwconv3x3_bwd_weight_reduce_kernel in fixed order.  No atomics:
+//    bit-reproducible.
+//  * GX = false (no input gradient wanted): no weights, no gx accumulators, no store -- the weight-gradient pass alone, the same
+//    sums in the same order.
+//  * the window is loaded row by row (6 packed vectors in flight), not all 18 at once: the registers go to the 9 x V weights,
+//    the 9 x V weight partials and the 4 x V accumulators.
+template <typename T, bool GX>
+__global__ __launch_bounds__(256, 2) void dwconv3x3_bwd_kernel(const T* __restrict__ x, const T* __restrict__ gy,
+                                                               const float* __restrict__ wgt, T* __restrict__ gx,
+                                                               float* __restrict__ ws, int B, int H, int W, int C, int dil,
+                                                               int cvb, int sliced) {
+  typedef BwdIO<T> IO;
+  constexpr int V = IO::N, V2 = V / 2;
   const int CV = C / V, WQ = quads_per_row(W, dil);
-  const int pl = 256 / cvb;
-  const int cvi = threadIdx.x % cvb, pli = threadIdx.x / cvb;
-  const int cv = blockIdx.x * cvb + cvi;
-  const bool active = cv < CV;
-  const int c0 = cv * V;
-  constexpr int V2 = V / 2;
-  f32x2 aw[9][V2], ab[V2];          // adjacent-channel pairs: every multiply-add is one v_pk_fma_f32
+  int pl, qfirst, qstride, cvbase, wsrow;
+  bool active;
+  if (sliced) {                                          // (the two geometries: dwconv3x3_fwd_kernel)
+    pl = blockDim.x / cvb;
+    active = (int)threadIdx.x < cvb * pl;
+    cvbase = (blockIdx.x & 7) * cvb;
+    wsrow = blockIdx.x >> 3;
+    qfirst = wsrow * pl + threadIdx.x / cvb;
+    qstride = (gridDim.x >> 3) * pl;
+  } else {
+    pl = 256 / cvb;
+    cvbase = blockIdx.x * cvb;
+    active = cvbase + (int)(threadIdx.x % cvb) < CV;
+    wsrow = blockIdx.y;
+    qfirst = blockIdx.y * pl + threadIdx.x / cvb;
+    qstride = gridDim.y * pl;
+  }
+  const int c0 = active ? (cvbase + threadIdx.x % cvb) * V : 0;
+  const int Hd = (H + dil - 1) / dil, h_slots = sliced ? dil * Hd : H;
+  f32x2 wr[GX ? 9 : 1][V2];         // wr[k] = w[8 - k]: the weight of window position k in gx
+  if constexpr (GX) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const float* wp = wgt + (size_t)(8 - k) * C + c0;
+#pragma unroll
+      for (int i = 0; i < V; i += 4) {
+        const float4 t4 = *reinterpret_cast<const float4*>(wp + i);
+        wr[k][i / 2] = f32x2{t4.x, t4.y};
+        wr[k][i / 2 + 1] = f32x2{t4.z, t4.w};
+      }
+    }
+  }
+  f32x2 aw[9][V2], ab[V2];          // aw[k]: the partial of gw[8 - k]; adjacent-channel pairs: every multiply-add is one v_pk_fma_f32
 #pragma unroll
   for (int i = 0; i < V2; ++i) {
     ab[i] = f32x2{0.0f, 0.0f};
 #pragma unroll
     for (int k = 0; k < 9; ++k) aw[k][i] = f32x2{0.0f, 0.0f};
   }
-  if (active) {
-    const long nquads = (long)B * H * WQ;
-    for (long quad = (long)blockIdx.y * pl + pli; quad < nquads; quad += (long)gridDim.y * pl) {
-      int b, h, w0;
-      quad_coords(quad, WQ, H, dil, b, h, w0);
-      f32x2 g[kPX][V2];
-      const T* gp = gy + (((size_t)b * H + h) * W) * C + c0;
-      {
-        typename VecIO<T>::Raw graw[kPX];
+  const long nquads = active ? (long)B * h_slots * WQ : 0;
+  for (long quad = qfirst; quad < nquads; quad += qstride) {
+    int b, h, w0;
+    quad_coords(quad, WQ, h_slots, dil, b, h, w0);
+    if (sliced && dil > 1) h = h / Hd + (h % Hd) * dil;  // slot -> row of residue class slot / Hd
+    if (h >= H || w0 >= W) continue;
+    const size_t img = (size_t)b * H * W * C + c0;
+    f32x2 xv[kPX][V2];
+    {
+      const T* xp = x + img + (size_t)h * W * C;
+      typename IO::Raw xraw[kPX];
 #pragma unroll
-        for (int p = 0; p < kPX; ++p)     // pixels past the row end contribute zero (select on the packed data)
-          graw[p] = mask_raw(VecIO<T>::load_raw(gp + (size_t)min(w0 + p * dil, W - 1) * C), w0 + p * dil < W);
+      for (int p = 0; p < kPX; ++p)
+        xraw[p] = mask_raw(IO::load_raw(xp + (size_t)min(w0 + p * dil, W - 1) * C), w0 + p * dil < W);
 #pragma unroll
-        for (int p = 0; p < kPX; ++p) {
-          VecIO<T>::unpack2(graw[p], g[p]);
+      for (int p = 0; p < kPX; ++p) IO::unpack2(xraw[p], xv[p]);
+    }
+    f32x2 acc[GX ? kPX : 1][V2];
+    if constexpr (GX) {
 #pragma unroll
-          for (int i = 0; i < V2; ++i) ab[i] += g[p][i];
-        }
+      for (int p = 0; p < kPX; ++p)
+#pragma unroll
+        for (int i = 0; i < V2; ++i) acc[p][i] = f32x2{0.0f, 0.0f};
+    }
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int yy = h + (ky - 1) * dil;
+      const bool rowok = yy >= 0 && yy < H;
+      const T* gr = gy + img + (size_t)min(max(yy, 0), H - 1) * W * C;
+      typename IO::Raw raw[kPX + 2];
+#pragma unroll
+      for (int j = 0; j < kPX + 2; ++j) {
+        const int xx = w0 + (j - 1) * dil;
+        raw[j] = mask_raw(IO::load_raw(gr + (size_t)min(max(xx, 0), W - 1) * C), rowok && xx >= 0 && xx < W);
       }
-      const T* xb = x + (size_t)b * H * W * C + c0;
 #pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        const int yy = h + (ky - 1) * dil;
-        const bool rowok = yy >= 0 && yy < H;
-        const T* xr = xb + (size_t)min(max(yy, 0), H - 1) * W * C;
-        typename VecIO<T>::Raw raw[kPX + 2];
+      for (int j = 0; j < kPX + 2; ++j) {
+        f32x2 v[V2];
+        IO::unpack2(raw[j], v);
+        if (ky == 1 && j >= 1 && j <= kPX) {             // gy at the quad's own pixels (zero past the row end)
 #pragma unroll
-        for (int j = 0; j < kPX + 2; ++j) {
-          const int xx = w0 + (j - 1) * dil;
-          raw[j] = mask_raw(VecIO<T>::load_raw(xr + (size_t)min(max(xx, 0), W - 1) * C), rowok && xx >= 0 && xx < W);
+          for (int i = 0; i < V2; ++i) ab[i] += v[i];
         }
 #pragma unroll
-        for (int j = 0; j < kPX + 2; ++j) {
-          f32x2 v[V2];
-          VecIO<T>::unpack2(raw[j], v);
+        for (int kx = 0; kx < 3; ++kx) {
+          const int p = j - kx;                          // pixel of the quad that sees column j at window position kx
+          if (p < 0 || p >= kPX) continue;
 #pragma unroll
-          for (int kx = 0; kx < 3; ++kx) {
-            const int p = j - kx;
-            if (p < 0 || p >= kPX) continue;
-#pragma unroll
-            for (int i = 0; i < V2; ++i) aw[ky * 3 + kx][i] = __builtin_elementwise_fma(g[p][i], v[i], aw[ky * 3 + kx][i]);
+          for (int i = 0; i < V2; ++i) {
+            if constexpr (GX) acc[p][i] = __builtin_elementwise_fma(wr[ky * 3 + kx][i], v[i], acc[p][i]);
+            aw[ky * 3 + kx][i] = __builtin_elementwise_fma(xv[p][i], v[i], aw[ky * 3 + kx][i]);
           }
         }
       }
     }
+    if constexpr (GX) {
+      T* gp = gx + img + (size_t)h * W * C;
+#pragma unroll
+      for (int p = 0; p < kPX; ++p)
+        if (w0 + p * dil < W) {
+          float o[V];
+#pragma unroll
+          for (int i = 0; i < V2; ++i) { o[2 * i] = acc[p][i].x; o[2 * i + 1] = acc[p][i].y; }
+          IO::store(gp + (size_t)(w0 + p * dil) * C, o);
+        }
+    }
   }
-  // fold the block's pixel lanes: two passes of 5 of the 10 rows (9 taps + bias) through 40 KB of LDS, every thread sums
+  // fold the block's pixel lanes: two passes of 5 of the 10 rows (9 taps + bias) through LDS, every thread sums
   // (10 one-row passes with two barriers each and only the first pixel lane summing were a 3-5 us tail)
   __shared__ float red[5][256][V];
-  float* wrow = ws + (size_t)blockIdx.y * 10 * C;
+  float* wrow = ws + (size_t)wsrow * 10 * C;
   for (int pass = 0; pass < 2; ++pass) {
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 5; ++kk) {
-      const int k = pass * 5 + kk;
+      const int k = pass * 5 + kk;                       // workspace row k: tap k = window position 8 - k
 #pragma unroll
       for (int i = 0; i < V; ++i) {
-        const f32x2 t = (k < 9) ? aw[k < 9 ? k : 0][i / 2] : ab[i / 2];
+        const f32x2 t = (k < 9) ? aw[k < 9 ? 8 - k : 0][i / 2] : ab[i / 2];
         red[kk][threadIdx.x][i] = (i & 1) ? t.y : t.x;
       }
     }
     __syncthreads();
     for (int o = threadIdx.x; o < 5 * cvb * V; o += 256) {
       const int kk = o / (cvb * V), rem = o - kk * cvb * V, cvj = rem / V, i = rem - cvj * V;
-      if (blockIdx.x * cvb + cvj >= CV) continue;
+      if (cvbase + cvj >= CV) continue;
       float sum = 0.0f;
       for (int p = 0; p < pl; ++p) sum += red[kk][p * cvb + cvj][i];
-      wrow[(size_t)(pass * 5 + kk) * C + (blockIdx.x * cvb + cvj) * V + i] = sum;
+      wrow[(size_t)(pass * 5 + kk) * C + (cvbase + cvj) * V + i] = sum;
     }
   }
 }
@@ -898,28 +977,45 @@ static int launch_fwd(const void* x, const float* w, const float* bias, void* y,
   return check_launch("dwconv3x3_fwd_kernel");
 }
 
+// Launch geometry of dwconv3x3_bwd_kernel (gx == nullptr: the weight / bias gradient alone) + the ordered reduction.
+//  * the XCD-sliced residue-class grid where sliced_geom() has it for 16-byte vectors, as roll_geom() (a gy row's three uses
+//    stay in one XCD's L2): at most 64 block rows = workspace rows.
+//  * else channel blocks x block rows.  The workspace holds kMaxStripes rows, so the block rows cannot supply the parallelism
+//    on their own: the channel blocks are made as narrow as it takes (down to 8 vectors = 128-byte runs per pixel) for 4 of
+//    them -- 512 workgroups, two per CU, at the row cap -- and a narrow block has more pixel lanes to fold in LDS, so the same
+//    workgroups write FEWER workspace rows (a row is 10 C floats however the channels are split).  Stage 3 of the student
+//    (4 x 34 x 60 x 1280 bf16): 64 rows = 3.3 MB of partials where the two-kernel form wrote 128 rows = 6.5 MB.
 template <typename T>
-static int launch_bwd_weight(const void* x, const void* gy, float* dw, float* db, float* ws, int B, int H, int W, int C,
-                             int dil, int flags, hipStream_t st) {
-  constexpr int V = VecIO<T>::N;
-  // narrow channel blocks on LARGE maps: with 16 vectors (256 contiguous bytes per pixel) a block has 16 pixel lanes instead
-  // of 4 -- four times the workgroups for the same partial-sum volume (the workspace row of a stripe is 10 C floats however
-  // the channels are split).  Measured (tools/kbench.py --only dw, forward + backward): 40 x 135 x 240 x 256: 1 393 -> 1 070 us;
-  // per-call census of the step (tools/abi_census.py): 4 x 68 x 120 x 512: 47 -> 24 us, 4 x 135 x 240 x 256: 78 -> 48 us; the
-  // student's stage 3 / 4 maps (4 x 34 x 60 x 1280: 27 vs 26 us) keep the wide blocks.  RFN_DWCONV_WGRAD_CVB forces a width.
-  static const int force_cvb = 0;
+static int launch_bwd(const void* x, const void* gy, const float* w, void* gx, float* dw, float* db, float* ws, int B, int H,
+                      int W, int C, int dil, int flags, hipStream_t st) {
+  constexpr int V = BwdIO<T>::N, V16 = 16 / (int)sizeof(T);   // channels per lane; per 16-byte vector, sliced_geom()'s unit
   const int CV = C / V;
-  const long nquads = (long)B * H * (dil * (((W + dil - 1) / dil + kPX - 1) / kPX));
-  const int want_cvb = force_cvb ? force_cvb : (nquads >= 8000 ? 16 : 0);
-  const int cvb = (want_cvb >= 8 && want_cvb <= 64 && (want_cvb & (want_cvb - 1)) == 0 && CV >= want_cvb) ? want_cvb : pick_cvb(CV);
-  const int gx = cdiv(CV, cvb), pl = 256 / cvb;
-  const int stripes = (int)std::max<long>(1, std::min<long>(std::min<long>(kMaxStripes, cdiv(nquads, pl)),
-                                                            std::max<long>(1, (256L * 8) / gx)));
-  hipLaunchKernelGGL((dwconv3x3_bwd_weight_kernel<T>), dim3(gx, stripes), dim3(256), 0, st, (const T*)x, (const T*)gy,
-                     ws, B, H, W, C, dil, cvb);
-  if (int rc = check_launch("dwconv3x3_bwd_weight_kernel")) return rc;
-  hipLaunchKernelGGL(dwconv3x3_bwd_weight_reduce_kernel, dim3(cdiv(10L * C, 32)), dim3(256), 0, st, ws, dw, db, C,
-                     stripes, flags);
+  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
+  int rows;
+  if (SlicedGeom sg = sliced_geom(C / V16, 1L << 30); sg.on) {
+    const int cvb = sg.cvb * (V16 / V), pl = 256 / cvb;
+    rows = (int)std::max<long>(1, std::min<long>(cdiv((long)B * dil * ((H + dil - 1) / dil) * WQ, pl), sg.grid / 8));
+    if (gx != nullptr)
+      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, true>), dim3(8 * rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w, (T*)gx,
+                         ws, B, H, W, C, dil, cvb, 1);
+    else
+      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, false>), dim3(8 * rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
+                         (T*)nullptr, ws, B, H, W, C, dil, cvb, 1);
+  } else {
+    int cvb = pick_cvb(CV);
+    while (cvb > 8 && cdiv(CV, cvb) < 4) cvb >>= 1;
+    const int gxb = cdiv(CV, cvb), pl = 256 / cvb;
+    const long nquads = (long)B * H * WQ;
+    rows = (int)std::max<long>(1, std::min<long>(std::min<long>(kMaxStripes, cdiv(nquads, pl)), std::max<long>(1, (256L * 8) / gxb)));
+    if (gx != nullptr)
+      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, true>), dim3(gxb, rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
+                         (T*)gx, ws, B, H, W, C, dil, cvb, 0);
+    else
+      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, false>), dim3(gxb, rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
+                         (T*)nullptr, ws, B, H, W, C, dil, cvb, 0);
+  }
+  if (int rc = check_launch("dwconv3x3_bwd_kernel")) return rc;
+  hipLaunchKernelGGL(dwconv3x3_bwd_weight_reduce_kernel, dim3(cdiv(10L * C, 32)), dim3(256), 0, st, ws, dw, db, C, rows, flags);
   return check_launch("dwconv3x3_bwd_weight_reduce_kernel");
 }
 
@@ -1308,21 +1404,37 @@ unsigned long rfn_dwconv3x3_bwd_weight_workspace_bytes(int C) {
   return (unsigned long)kMaxStripes * 10ul * (unsigned long)(C > 0 ? C : 0) * sizeof(float);
 }
 
+// Backward of rfn_dwconv3x3_nhwc_fwd: grad_x and grad_weight / grad_bias from one pass over grad_y (dwconv3x3_bwd_kernel);
+// grad_x == NULL (rfn_dwconv3x3_nhwc_bwd_weight): the parameter gradients alone.
+static int dw_bwd(const char* who, const void* x, const void* grad_y, const float* weight, void* grad_x, float* grad_weight,
+                  float* grad_bias, void* workspace, int B, int H, int W, int C, int dilation, int dtype, int flags,
+                  hipStream_t st) {
+  RFN_REQUIRE(x && grad_y && grad_weight && workspace, "%s: null pointer", who);
+  RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "%s: bad size", who);
+  if (dtype == 0) {
+    RFN_REQUIRE(C % 4 == 0, "%s: C must be a multiple of 4 for f32", who);
+    return launch_bwd<float>(x, grad_y, weight, grad_x, grad_weight, grad_bias, (float*)workspace, B, H, W, C, dilation, flags, st);
+  }
+  RFN_REQUIRE(C % 8 == 0, "%s: C must be a multiple of 8 for 16-bit activations", who);
+  return dt_one(dtype, who, [&](auto t) {
+    return launch_bwd<typename decltype(t)::type>(x, grad_y, weight, grad_x, grad_weight, grad_bias, (float*)workspace, B, H, W, C,
+                                                  dilation, flags, st);
+  });
+}
+
 int rfn_dwconv3x3_nhwc_bwd_weight(const void* x, const void* grad_y, float* grad_weight, float* grad_bias,
                                   void* workspace, int B, int H, int W, int C, int dilation, int dtype, int flags,
                                   rfn_stream_t stream) {
-  RFN_REQUIRE(x && grad_y && grad_weight && workspace, "rfn_dwconv3x3_nhwc_bwd_weight: null pointer");
-  RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_bwd_weight: bad size");
-  if (dtype == 0) {
-    RFN_REQUIRE(C % 4 == 0, "rfn_dwconv3x3_nhwc_bwd_weight: C must be a multiple of 4 for f32");
-    return launch_bwd_weight<float>(x, grad_y, grad_weight, grad_bias, (float*)workspace, B, H, W, C, dilation,
-                                    flags, (hipStream_t)stream);
-  }
-  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_bwd_weight: C must be a multiple of 8 for 16-bit activations");
-  return dt_one(dtype, "rfn_dwconv3x3_nhwc_bwd_weight", [&](auto t) {
-    return launch_bwd_weight<typename decltype(t)::type>(x, grad_y, grad_weight, grad_bias, (float*)workspace, B, H, W, C,
-                                                         dilation, flags, (hipStream_t)stream);
-  });
+  return dw_bwd("rfn_dwconv3x3_nhwc_bwd_weight", x, grad_y, nullptr, nullptr, grad_weight, grad_bias, workspace, B, H, W, C,
+                dilation, dtype, flags, (hipStream_t)stream);
+}
+
+int rfn_dwconv3x3_nhwc_bwd(const void* x, const void* grad_y, const float* weight_tap_major, void* grad_x, float* grad_weight,
+                           float* grad_bias, void* workspace, int B, int H, int W, int C, int dilation, int dtype, int flags,
+                           rfn_stream_t stream) {
+  RFN_REQUIRE(weight_tap_major && grad_x, "rfn_dwconv3x3_nhwc_bwd: null pointer");
+  return dw_bwd("rfn_dwconv3x3_nhwc_bwd", x, grad_y, weight_tap_major, grad_x, grad_weight, grad_bias, workspace, B, H, W, C,
+                dilation, dtype, flags, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -106,9 +106,10 @@ class _DWConv3x3Gelu(torch.autograd.Function):
 def _dwconv_backward(ctx, x, w_tap, gy):
     B, H, W, C = x.shape
     gx = gw = gb = None
-    if ctx.needs_input_grad[0]:
+    need_params = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+    if ctx.needs_input_grad[0] and not need_params:
         gx = _fwd(gy, w_tap, None, ctx.dilation, True)
-    if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+    if need_params:
         sw, sb = grad_sink(ctx.weight), grad_sink(ctx.bias) if ctx.has_bias else None
         direct = sw is not None and (sb is not None or not ctx.has_bias)
         if direct:
@@ -116,13 +117,13 @@ def _dwconv_backward(ctx, x, w_tap, gy):
         else:
             dw = torch.empty((9, C), dtype=torch.float32, device=x.device)
             db = torch.empty((C,), dtype=torch.float32, device=x.device) if ctx.has_bias else None
-
-        def run():
-            ws = workspace(_DW_WS_STRIPES * 10 * C * 4, x.device)        # per stream: looked up on the stream it runs on
-            _lib.call("rfn_dwconv3x3_nhwc_bwd_weight", x.device, ptr(x), ptr(gy), ptr(dw), ptr(db), ptr(ws), B, H, W, C,
-                      ctx.dilation, DTYPE_CODE[x.dtype], 3 if direct else 0)
-
-        run()
+        ws = workspace(_DW_WS_STRIPES * 10 * C * 4, x.device)            # per stream: looked up on the stream it runs on
+        tail = (ptr(dw), ptr(db), ptr(ws), B, H, W, C, ctx.dilation, DTYPE_CODE[x.dtype], 3 if direct else 0)
+        if ctx.needs_input_grad[0]:                                      # both gradients from one pass over gy
+            gx = torch.empty_like(x)
+            _lib.call("rfn_dwconv3x3_nhwc_bwd", x.device, ptr(x), ptr(gy), ptr(w_tap), ptr(gx), *tail)
+        else:
+            _lib.call("rfn_dwconv3x3_nhwc_bwd_weight", x.device, ptr(x), ptr(gy), *tail)
         if not direct:
             gw = dw.t().reshape(ctx.wshape).to(ctx.wdtype)
             gb = db

@@ -115,6 +115,30 @@ def main():
             gy = torch.randn_like(y)
             add(f"dwconv fwd+bwd {B_}x{H}x{W}x{C} d{dil} {str(dt)[6:]}", timeit(lambda: torch.autograd.grad(dwconv3x3_nhwc(xg, wg, bb, dil), (xg, wg), gy), reps=5), 7 * x.numel() * es)
     if not args.only or "dw" in args.only:
+        # the backward alone at the student's Mix-FFN and ASPP shapes: both gradients from one pass over grad_y (fused launch +
+        # reduce: x, grad_y, grad_x = 3 tensors) next to the separate entries (data gradient, then weight gradient + reduce:
+        # grad_y -> grad_x and x, grad_y -> partials = 4 tensors), which is all a library without the fused entry has
+        from refign_amd import _lib
+        from refign_amd._tensor import ptr
+        lib = _lib.load_library()
+        for (B_, H, W, C, dil) in [(4, 34, 60, 1280, 1), (4, 68, 120, 512, 1), (4, 135, 240, 256, 1), (4, 17, 30, 2048, 1),
+                                   (4, 135, 240, 1024, 6), (4, 135, 240, 1024, 12), (4, 135, 240, 1024, 18)]:
+            x = torch.randn(B_, H, W, C, device=dev).to(torch.bfloat16)
+            gy, gx = torch.randn_like(x), torch.empty_like(x)
+            w_tap, dw, db = torch.randn(9, C, device=dev), torch.empty(9, C, device=dev), torch.empty(C, device=dev)
+            ws = torch.empty(lib.rfn_dwconv3x3_bwd_weight_workspace_bytes(C), dtype=torch.uint8, device=dev)
+            tail = (ptr(dw), ptr(db), ptr(ws), B_, H, W, C, dil, 1, 0)
+
+            def separate():
+                _lib.call("rfn_dwconv3x3_nhwc_fwd", dev, ptr(gy), ptr(w_tap), None, ptr(gx), B_, H, W, C, dil, 1, 1)
+                _lib.call("rfn_dwconv3x3_nhwc_bwd_weight", dev, ptr(x), ptr(gy), *tail)
+
+            add(f"dwconv bwd data, weight + reduce (3 launches) {B_}x{H}x{W}x{C} d{dil} bf16", timeit(separate), 4 * x.numel() * 2)
+            if "rfn_dwconv3x3_nhwc_bwd" in _lib.SIGNATURES:
+                add(f"dwconv bwd fused + reduce (2 launches) {B_}x{H}x{W}x{C} d{dil} bf16",
+                    timeit(lambda: _lib.call("rfn_dwconv3x3_nhwc_bwd", dev, ptr(x), ptr(gy), ptr(w_tap), ptr(gx), *tail)), 3 * x.numel() * 2)
+        del x, gy, gx
+    if not args.only or "dw" in args.only:
         # the EMA teacher's ASPP branches (gradient-free: statistics pass, then convolution + BatchNorm + ReLU), one launch each
         from refign_amd import _lib
         from refign_amd._tensor import ptr
