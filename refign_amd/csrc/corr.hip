@@ -5,31 +5,28 @@
 //   out[n,ph,pw,h,w] = sum_c sum_{i<kH} sum_{j<kW} in1[n,c,u+i*dil,v+j*dil] * in2[n,c,u+i*dil+sU,v+j*dil+sV]
 //   u = -pad + h*stride, v = -pad + w*stride, sU = (ph - (patchH-1)/2)*dil_patch, zero outside the image.
 //
-// Two forward kernels:
-//   * corr9_tile_kernel -- the ONE parameterisation the hot path uses (kernel 1, patch 9, stride 1, pad 0;
-//     models/modules.py:268-270).  HBM-bound by design: algorithmic traffic 4*(2C+81) bytes per pixel against
-//     162*C flops per pixel (15 flop/B at C=128), so the only way to approach the HBM roofline on fp32 VALU is
-//     register tiling.  Layout:
-//       - a workgroup owns a TH x 64 pixel tile and walks the channels in chunks of CC; per chunk the
-//         target tile (TH x 64) and the source tile with its 4-pixel halo ((TH+8) x 72) are staged in LDS with
-//         16-byte coalesced global loads (NCHW rows are contiguous along w);
-//       - a thread owns a strip of 4 consecutive pixels x 9 horizontal shifts x 3 vertical shifts
-//         = 108 fp32 accumulators; per channel it issues 1 + 9 ds_read_b128 (40 dwords) for 108 FMAs;
-//         the three vertical-shift groups of a tile are three sets of waves (wave-uniform, no divergence);
-//       - lanes 16-31 / 48-63 of a wave take their strips rotated by 14 so that, with the 72-dword row pitch,
-//         every ds_read_b128 lane group {0-3,12-15,20-27}/{4-11,16-19,28-31} hits 64 distinct banks
-//         (MI355X LDS: b128 reads are serviced in those non-contiguous 16-lane groups);
-//       - the 81 output planes are written once, 16 bytes per lane, contiguous along w.
-//     Optional fusions selected by template flags:
-//       FUSE  : ReLU + L2-normalisation over the 81 shifts (LocalFeatureCorrelationLayer, modules.py:272-273)
-//               in the epilogue -- saves three full passes over the 81xHxW volume;
-//       WARP  : the source tile is produced by bilinear-warping the un-warped source features with the flow
-//               while staging (helpers/matching_utils.py:11-49) -- the warped feature map never exists in HBM.
-//   * corr_generic_fwd_kernel -- any parameterisation, one thread per output element, float or double.
+// Forward.  The hot path uses ONE parameterisation (kernel 1, patch 9, stride 1, pad 0; models/modules.py:268-270), fp32.  It
+// is HBM-bound by design -- 4*(2C+81) bytes per pixel against 162*C flops per pixel (15 flop/B at C=128) -- so both of its
+// kernels tile in registers: a thread owns a strip of 4 consecutive pixels x 9 horizontal x 3 vertical shifts = 108 fp32
+// accumulators, the three vertical-shift groups of a tile are three sets of waves, and per channel a thread reads 1 + 9
+// 16-byte vectors from LDS for 108 FMAs.  Optional ReLU + L2 norm over the 81 shifts in the epilogue (FUSE:
+// LocalFeatureCorrelationLayer, modules.py:272-273 -- saves three passes over the 81 x H x W volume).
+//   * corr9_pipe2_kernel -- every map with W % 4 == 0, C % 8 == 0, C >= 16 and samples below 4 GB (launch_corr9): tiles of
+//     16 x 32 or 8 x 32 pixels, brought in by global -> LDS DMA through a four-stage ring; the tiny maps' cross-workgroup
+//     channel split (launch_corr9_split, with corr9_split_reduce_kernel for the two-launch form) runs the same kernel.
+//   * corr9_tile_kernel -- everything else of the hot parameterisation: odd widths, few channels, samples of 4 GB and more,
+//     and the fused-warp form (WARP: the source tile is bilinear-warped with the flow while it is staged,
+//     helpers/matching_utils.py:11-49 -- the warped feature map never exists in HBM).  8 x 64 tiles staged through registers.
+//   * corr_generic_fwd_kernel -- any parameterisation, one thread per output element; float, double or half.
 //
 // Backward (reference: correlation.cpp:44-78,131-183; CUDA gather form correlation_cuda_kernel.cu:91-238):
-//   * corr_k1_bwd_kernel     -- gather form for kernel 1 / stride 1 / pad 0 (deterministic, no atomics);
-//   * corr_generic_bwd_kernel -- scatter with hardware float/double atomics for everything else.
+//   * corr9_bwd_strip_kernel  -- the hot parameterisation, f32, W % 4 == 0, C % 8 == 0: both gradients in one launch;
+//   * corr9_bwd_tile_kernel   -- the hot parameterisation otherwise: one pixel per thread, one launch per gradient;
+//   * corr_k1_bwd_kernel      -- gather form for kernel 1 / stride 1 / pad 0 (deterministic, no atomics);
+//   * corr_generic_bwd_gather_kernel -- half, any parameterisation (deterministic);
+//   * corr_generic_bwd_kernel -- scatter with hardware float / double atomics for everything else.
+// History of the forward (three earlier kernel generations, what was tried and dropped): docs/history/DESIGN_r01-r04.md
+// section 10; their measurements are profiles/r01-r06_*corr*.
 #include <cstdlib>
 #include <type_traits>
 
@@ -39,12 +36,38 @@
 
 namespace rfn {
 
+constexpr int kHalo = 4;           // (9-1)/2
+
+// XCD-local block order.  Workgroup b of a launch runs on XCD b % 8 (round-robin dispatch); this returns b's place in an order
+// that gives every XCD a contiguous band of tiles, so that the halo rows two neighbouring tiles both fetch meet in ONE L2
+// (the launches that use it are a single round: neighbours run side by side; the forward's DMA alone 65 -> 46 us).
+__device__ __forceinline__ int xcd_local_order(int wg, int nwg) {
+  const int qq = nwg / 8, rr = nwg % 8, xcd = wg % 8, loc = wg / 8;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
+}
+
+// tile id -> (tile column, tile row, image): columns run fastest
+struct TileId {
+  int tx, ty, n;
+};
+__device__ __forceinline__ TileId decode_tile(int bid, int tilesX, int tilesY) {
+  TileId t;
+  t.tx = bid % tilesX; bid /= tilesX;
+  t.ty = bid % tilesY;
+  t.n = bid / tilesY;
+  return t;
+}
+
 // --------------------------------------------------------------------------------------------------------
-// Tiled patch-9 forward
+// Tiled patch-9 forward, register-staged: a workgroup owns an 8 x 64 pixel tile and walks the channels in chunks of 8; per
+// chunk the target tile (8 x 64) and the source tile with its 4-pixel halo (16 x 72) are staged in LDS with 16-byte coalesced
+// global loads (NCHW rows are contiguous along w).  Lanes 16-31 / 48-63 of a wave take their strips rotated by 14: with the
+// 72-dword row pitch every 16-lane group of a 16-byte LDS read then covers 64 distinct banks.  Any width, any channel count.
 // --------------------------------------------------------------------------------------------------------
 constexpr int kTW = 64;            // tile width in pixels
+constexpr int kTH = 8;             // tile height
+constexpr int kCC = 8;             // channels per chunk
 constexpr int kStrips = 16;        // 4-pixel strips per tile row
-constexpr int kHalo = 4;           // (9-1)/2
 constexpr int kPitch = kTW + 2 * kHalo;  // 72 dwords: LDS row pitch of BOTH tiles (same bank geometry)
 
 // bilinear tap of the warp (matching_utils.py:35-43): returns the 4 clamped offsets and weights (0 for taps
@@ -83,10 +106,11 @@ __device__ __forceinline__ WarpTap make_tap(float gx, float gy, float fx, float 
   return t;
 }
 
-template <int TH, int CC, bool FUSE, bool WARP>
-__global__ __launch_bounds__(TH * kStrips * 3) void corr9_tile_kernel(
+template <bool FUSE, bool WARP>
+__global__ __launch_bounds__(kTH * kStrips * 3) void corr9_tile_kernel(
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ flow,
     float* __restrict__ out, int C, int H, int W, int tilesX, int tilesY) {
+  constexpr int TH = kTH, CC = kCC;
   constexpr int NT = TH * kStrips * 3;
   constexpr int R2 = TH + 2 * kHalo;
   __shared__ __attribute__((aligned(16))) float smem[CC * (R2 + TH) * kPitch];
@@ -94,18 +118,15 @@ __global__ __launch_bounds__(TH * kStrips * 3) void corr9_tile_kernel(
   float* s1 = smem + CC * R2 * kPitch;   // [CC][TH][kPitch]  target tile
 
   const int tid = threadIdx.x;
-  int bid = blockIdx.x;
-  const int tx = bid % tilesX; bid /= tilesX;
-  const int ty = bid % tilesY;
-  const int n = bid / tilesY;
-  const int h0 = ty * TH, w0 = tx * kTW;
+  const TileId id = decode_tile(blockIdx.x, tilesX, tilesY);
+  const int n = id.n, h0 = id.ty * TH, w0 = id.tx * kTW;
 
   const int lane = tid & 63, wave = tid >> 6;
   constexpr int WPG = TH / 4;            // waves per vertical-shift group
   const int dyg = wave / WPG;            // 0..2 : vertical shifts dyg*3 .. dyg*3+2   (wave-uniform)
   const int q = lane >> 4, j = lane & 15;
   const int row = (wave % WPG) * 4 + q;
-  const int strip = (q & 1) ? ((j + 14) & 15) : j;   // bank-conflict-free b128 lane groups, see header
+  const int strip = (q & 1) ? ((j + 14) & 15) : j;   // bank-conflict-free 16-byte reads, see the banner
 
   const size_t plane = (size_t)H * W;
   const float* p1 = in1 + (size_t)n * C * plane;
@@ -256,15 +277,70 @@ __global__ __launch_bounds__(TH * kStrips * 3) void corr9_tile_kernel(
 
 
 // --------------------------------------------------------------------------------------------------------
-// Tiled patch-9 forward, LDS-DMA pipeline (the fast path when W % 4 == 0 and C % CC == 0)
-//   Same tile/thread decomposition as corr9_tile_kernel, but the two tiles of a channel chunk are brought in by
-//   `global_load_lds_dwordx4` (global -> LDS DMA, no VGPR round trip, no ds_write) into a 2-deep LDS ring, so the
-//   HBM/L2 latency of chunk k+1 is hidden behind the 108 x CC FMAs per thread of chunk k and there is exactly one
-//   barrier per chunk.  The DMA writes wave-uniform-base + lane*16, so the LDS image of a chunk is the linear
-//   sequence of float4 "slots" (channel, row, 18 slots per 72-float row); rows 0..R2-1 are the source tile with
-//   halo, rows R2..R2+TH-1 the target tile (slots 16,17 of those rows are never written).  Slots that fall outside
-//   the image are never written either: the ring is zeroed once at kernel start and the out-of-image pattern is
-//   the same for every chunk, which gives the zero padding of the reference for free.
+// Tiled patch-9 forward, pipelined: corr9_pipe2_kernel (W % 4 == 0, C % 8 == 0; launch_corr9 has the selection rule)
+//
+// Tile and threads.  A WAVE GROUP of TH / 8 x 3 waves owns a TH x 32 pixel tile (TH = 16 or 8): a wave's lanes are 8 rows x 8
+// strips of 4 pixels, and the group's three thirds take vertical shifts 0-2, 3-5, 6-8.  The channels go by in CHUNKS of two.
+//
+// LDS image of a chunk.  `global_load_lds_dwordx4` (global -> LDS DMA: no VGPR round trip, no ds_write) writes 64 lanes x 16
+// bytes at a wave-uniform LDS address, so the image is a linear sequence of 16-byte SLOTS, 64 per instruction, in rows of 12
+// (48 floats): [target c0 | target c1 | source c0 | source c1], TH rows per target channel (slots 0-7 of a row in use),
+// TH + 8 rows per source channel (the tile with its 4-pixel halo: slots 0-9).  The target rows come first so that the border
+// between the two tensors falls on an instruction border (2 x TH x 12 slots = a multiple of 64): every instruction then has
+// ONE tensor as its source, a scalar 64-bit base + a 32-bit byte offset per lane -- half the address registers, and the loop
+// has none to spare (a spilled pointer is reloaded through `s_waitcnt vmcnt(0)`, which waits for every DMA in flight).  A slot
+// without a source (outside the image, or the unused end of a row) is masked out of its instruction and is the same slot in
+// every chunk: each lane zeroes its own such slots once, and that is the reference's zero padding.
+//
+// Why the row pitch is 48 floats, and the strip permutation.  A wave's `ds_read_b128` is served in four groups of 16 lanes --
+// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- one LDS cycle each when the group's lanes touch 16 DISTINCT
+// slots of the 256-byte bank row (64 banks x 4 bytes; bank = (address / 4) % 64).  With 8 strips per row a group holds one HALF
+// row (4 strips) of each of four consecutive rows.  A row needs 10 slots (32 + 2 x 4 pixels); at a pitch of 12 slots four
+// consecutive rows start at slots 0, 12, 8, 4 of the bank row, so four half rows tile it exactly -- if they are the SAME half of
+// every row.  The hardware's groups take lanes 0-3 of rows 0 and 3 but lanes 4-7 of rows 1 and 2 (and the other way round), so
+// rows 1 and 2 of every four swap their halves: strip = j ^ 4 there.  Group one then reads strips 0-3 of the four rows at slots
+// 0-3, 12-15, 8-11, 4-7, group two strips 4-7 at 4-7, 0-3, 12-15, 8-11: conflict-free, and so is every other read of the loop
+// (the next 16 bytes of a source row, another channel or vertical shift: a constant added to the whole group).  An unpadded
+// pitch of 10 slots starts the rows at 0, 10, 4, 14 and no permutation of half rows avoids the overlap.  The pitch also makes
+// the target rows fill whole instructions (above) and gives the paired edge tiles (PAIR) their 2 x 24 floats per row.
+//
+// The ring and its counted waits.  Each wave group has a ring of kStages = 4 chunk images: three chunks are in flight while one
+// is consumed.  A wave issues K instructions per chunk (K or K - 1 of them with a source) and the DMAs of a wave complete in
+// order, so "my part of chunk c has landed" is `s_waitcnt vmcnt(n)` with n = the instructions of the NEWER chunks in flight;
+// the barrier behind it extends that to every wave's part and says that everybody is done with chunk c - 1, whose stage takes
+// chunk c + 3 -- issued one instruction at a time between the row steps of chunk c.  ONE barrier per chunk, and no compiler-
+// visible dependence between DMA and `ds_read` (see lds_dma16_masked).  The tile's last four chunks have fewer chunks behind
+// them and get their own, smaller counts: a constant count lets a wave read the last chunks before they have landed (the race
+// that tools/micro/corr_race.py and tests/test_race_gpu.py look for).
+//
+// A chunk's arithmetic: six (channel, vertical shift) row steps, unrolled, each one target vector x three source vectors = 36
+// products as 16 `v_pk_fma_f32` + 4 `v_fmac_f32`; the three `ds_read_b128` of step s + 1 are issued into a second register set
+// in front of the products of step s (`sched_barrier` pins the order).  The loop is VALU-bound, not LDS-bound: ten reads against
+// 60 product instructions per channel (profiles/r04_pmc_corr9.txt, r05_pmc_corr9.txt).
+//
+// Template parameters.
+//   TH, TW  tile size; TW is 32 (every constant of the bank argument above depends on it).
+//   FUSE    ReLU + L2 norm over the 81 shifts in the epilogue.
+//   NTILE   wave groups per workgroup.  Without KSPLIT each owns a tile of its own (ids NTILE b, NTILE b + 1, ..), its own rings
+//           and its own DMA stream; only the barrier is shared.  Level 1 (2 x 270 x 480) runs two 16 x 32 tiles per workgroup:
+//           twelve waves per CU at 168 registers (a 6-wave workgroup's 2, 2, 1, 1 placement over the SIMDs leaves no room for a
+//           second one), and 510 tiles = 255 workgroups = one even round over the 256 CUs.
+//   KSPLIT  the NTILE = 2 or 4 wave groups walk the halves / quarters of the channels of ONE tile, each through its own ring;
+//           groups 1.. hand their 108 sums per lane to group 0 through the LDS in front of the epilogue (added in group order:
+//           deterministic).  For maps of at most one tile per CU: a CU, not a wave, is what a chunk waits for.
+//   PAIR    a map whose width leaves at most HALF a tile column over (240 = 7 x 32 + 16) would spend a whole tile per row band
+//           on it.  The left-over column band of TWO images shares one tile instead: strips 0-3 are image n's last columns,
+//           strips 4-7 image n + 1's (same rows), each half with its own halo in the 48-float row (2 x 24).  Only per-lane
+//           constants change (DMA source offsets, the source-row base, the store address).  `tilesX` then counts the FULL tile
+//           columns; tiles [0, nreg) are regular, tiles [nreg, ntiles) the (image pair, row band) edge tiles.
+//   JOIN    the cross-workgroup channel split of tiny maps in ONE launch (launch_corr9_split): gridDim.y workgroups share a tile,
+//           each walks the slice [blockIdx.y C, (blockIdx.y + 1) C) of the Ctot channels and stores its raw partial volume at
+//           out + blockIdx.y part_stride, then takes a ticket; the LAST arriver adds the slices in slice order (deterministic),
+//           applies ReLU + L2 norm and writes `joined`.  Publication across XCDs (their L2s are not coherent with each other):
+//           slab stores, vmcnt(0), barrier, agent-scope release fence, relaxed agent-scope ticket; the joining workgroup takes
+//           an agent-scope acquire fence before it reads.  The tickets are zero on entry and the joining workgroup puts its
+//           ticket back to zero: the caller zeroes them ONCE per workspace, never per launch (a memset node per launch came out
+//           stale under hipGraph replay: profiles/r05_corr_level3_one_launch.txt).
 // --------------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -276,144 +352,75 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
   }
 }
 
-// One LDS-DMA instruction (global -> LDS, 16 bytes per lane, lane i lands at lds_wave_base + 16 i), issued through
-// inline asm ON PURPOSE.  With the `__builtin_amdgcn_global_load_lds` builtin hipcc tracks the pending LDS write and,
-// whenever it cannot prove that a later `ds_read` touches a different object, inserts `s_waitcnt vmcnt(0)` in front of
-// it -- measured here: the wait landed inside the channel loop, i.e. the DMA of chunk k+1 never overlapped the FMAs of
-// chunk k (DMA-only 62 us + FMA-only 81 us = 147 us total, profiles/r01_kbench_corr_ablation.txt).  Inline asm is
-// invisible to that pass; the hand-off is then entirely ours: `s_waitcnt vmcnt(N)` + barrier before the first read.
-__device__ __forceinline__ void lds_dma16(const float* gsrc, float* lds_wave_base) {
-  const unsigned base = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lds_wave_base;
-  const unsigned sbase = __builtin_amdgcn_readfirstlane(base);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(sbase) : "memory", "m0");
-#pragma clang diagnostic pop
-}
-// The same under a lane mask, WITHOUT control flow the compiler can see: exec is narrowed and restored inside the asm
-// statement.  (An `if (ok) lds_dma16(...)` is a branch around the instruction; between the unrolled product steps of
-// corr9_pipe2_kernel such branches split the chunk into basic blocks, and the products -- pure arithmetic -- then sink
-// out of their steps: spills, and no pipeline left.)
-// (scalar 64-bit base + 32-bit byte offset per lane: one address VGPR instead of two)
+// The DMA instruction goes through inline asm, NOT `__builtin_amdgcn_global_load_lds`: with the builtin hipcc tracks the pending
+// LDS write and puts `s_waitcnt vmcnt(0)` in front of every `ds_read` it cannot prove disjoint -- inside the channel loop, so
+// that no DMA overlapped any arithmetic (profiles/r01_kbench_corr_ablation.txt).  With asm the hand-off is ours: counted waits.
+// The lane mask is applied WITHOUT control flow the compiler can see (exec is narrowed and restored inside the statement): a
+// branch around the instruction splits the unrolled chunk into basic blocks, the products sink out of their steps, and the
+// registers spill.  Scalar 64-bit base + 32-bit byte offset per lane; lane i lands at lds_wave_base + 16 i.
 __device__ __forceinline__ void lds_dma16_masked(const void* sbase, unsigned voff, unsigned lds_wave_base,
                                                  unsigned long long mask) {
   unsigned long long saved;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
   asm volatile("s_mov_b32 m0, %3\n\ts_and_saveexec_b64 %0, %4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b64 exec, %0"
                : "=&s"(saved) : "v"(voff), "s"(sbase), "s"(lds_wave_base), "s"(mask) : "memory", "m0", "scc");
-#pragma clang diagnostic pop
 }
 
-// (Rounds 1-4 kept three earlier generations of this kernel in the library behind RFN_CORR_VARIANT -- the 2-stage LDS-DMA
-// kernel `corr9_dma_kernel`, the first 4-stage ring `corr9_pipe_kernel` with its tile-tail race, and ~25 tile / chunk
-// variants of them.  Round 5 removed them: one pipelined kernel below serves every map the tiled path takes, the round-1
-// register-staged `corr9_tile_kernel` above everything else (odd widths, few channels, the fused-warp form, samples of 4 GB
-// and more).  Their measurements stay in profiles/r01-r04_*corr*.)
+constexpr int kStages = 4;                              // ring stages per wave group
+constexpr int pipe2_threads(int TH, int TW, int NTILE) { return TH * (TW / 4) * 3 * NTILE; }
 
-// NTILE = 2: the workgroup is two independent halves, each owning its own tile (ids 2b, 2b+1 of the launch's tile
-// order), its own LDS region and its own DMA stream; only the per-chunk barrier is shared.  This doubles the waves per
-// CU (6-wave workgroups do not co-reside: their 2,2,1,1 wave placement over the SIMDs leaves no room for a second one
-// at 168 VGPRs) while keeping the fine 16x32 tile granularity that fills 256 CUs evenly: K4 level 1 (2 x 270 x 480) is
-// 510 tiles = 255 workgroups = one even round over the 256 CUs.
-// ---- 4-stage variant, second take (round 4, second half) ---------------------------------------------------------
-// What the counters said about corr9_pipe_kernel (profiles/r04_pmc_corr9.txt): it is VALU-bound, not LDS-bound
-// (`ds_read_b128` moves 256 B / clock / CU on gfx950: 10 reads x 12 waves x 4 clocks = 480 clocks per channel against
-// 3 waves x 66 VALU x 4 = 792 per SIMD), with 66 VALU instructions per channel where 54 are products (5 address
-// computations + 7 moves), every `ds_read` waited for right behind its issue (the other two waves of the SIMD are the
-// only latency cover) and 24 VGPRs holding wave-uniform LDS-DMA destinations as generic pointers.  Same decomposition,
-// same products in the same order (identical results), but
-//   * the wave index is a scalar (`readfirstlane`): DMA destinations live in SGPRs;
-//   * a chunk's six (channel, vertical shift) row steps are unrolled with immediate offsets from two per-lane bases,
-//     and software-pipelined: the three `ds_read_b128` of step s + 1 are issued into a second register set before the
-//     18 packed products of step s (`sched_barrier` pins the order; hipcc's waitcnt pass then emits lgkmcnt(3));
-//   * the DMA of the chunk three ahead is issued behind the first reads of a chunk, inside their latency.
-//   * KSPLIT (NTILE == 2): the two wave groups of the workgroup walk the two HALVES of the channels of ONE tile, each through
-//     its own ring, and the second group's 108 sums per lane are added to the first's through the LDS in front of the epilogue
-//     (three rounds of 36 floats per lane in the ring's own memory).  For maps of at most one tile per CU: a chunk takes a CU
-//     0.5 us with three waves and 0.85 us with six, so half the chunks per wave is ~15-20 % off the launch (not half: the
-//     CU, not the wave, is what a chunk waits for).
-//   * PAIR (round 5; K4 level 2: 2 x 135 x 240): a map whose width leaves at most HALF a tile column over (240 = 7 x 32 + 16)
-//     spends a whole tile per row band on it -- 17 x 8 x 2 = 272 tiles, and the 16 CUs that get a second workgroup pace the
-//     launch (83 us against 64.5 us for 256 tiles, profiles/r04_corr_ksplit.txt).  With PAIR the left-over column band of TWO
-//     images shares one tile: strips 0..3 of the tile are image n's last columns, strips 4..7 image n + 1's (same rows), each
-//     half with its own 4-pixel halo in the 48-float LDS row (2 x 24).  Only per-lane constants change (DMA source offsets,
-//     the source-row base, the store address); the LDS image, the products and the hand-offs are the same.  `tilesX` then
-//     counts the FULL tile columns, tiles [0, nreg) are regular and tiles [nreg, ntiles) are the (image pair, row band) edge
-//     tiles: 2 x 17 x 7 + 17 = 255 workgroups -- one per CU, which also lets the channel split (KSPLIT) apply.
-//   * JOIN (cross-workgroup channel split of tiny maps, launch_corr9_split; 1 = raw sums, 2 = ReLU + L2 norm): gridDim.y workgroups
-//     share a tile, each writes the raw partial volume of its channel slice, takes a ticket, and the LAST arriver adds the slices in
-//     slice order (deterministic), applies the epilogue and writes the result: the level in ONE launch (round 5; before: a second
-//     kernel, 14 + 18 us for K4 level 3).  Publication across XCDs: slab stores, vmcnt(0), barrier, agent-scope release fence,
-//     relaxed agent-scope ticket; the reducer takes an agent-scope acquire fence before it reads (the L2s of the XCDs are not
-//     coherent with each other).  The tickets are zero on entry and the joining workgroup puts its ticket back to zero: the
-//     caller zeroes them once per workspace (a memset node in front of every launch was tried first: under hipGraph replay the
-//     level came out stale -- tests/test_align_gpu.py K2 golden -- while eager launches were right).
-template <int TH, int TW, bool FUSE, int MINW, int NTILE, int DEPTH = 1, int NS = 4, bool KSPLIT = false, bool PAIR = false,
-          int JOIN = 0>
-__global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_kernel(
+template <int TH, int TW, bool FUSE, int NTILE, bool KSPLIT = false, bool PAIR = false, bool JOIN = false>
+__global__ __launch_bounds__(pipe2_threads(TH, TW, NTILE), 3) void corr9_pipe2_kernel(
     const float* __restrict__ in1, const float* __restrict__ in2, float* __restrict__ out, int C, int H, int W,
     int tilesX, int tilesY, int ntiles, int xcd_remap, int nreg, int Ctot, long part_stride, float* __restrict__ joined,
     unsigned* __restrict__ tickets) {
-  // (C = the channels THIS workgroup walks, Ctot = the tensors' channel count: equal except in the cross-workgroup channel
-  // split of tiny maps, launch_corr9_split, where blockIdx.y picks the slice [blockIdx.y C, (blockIdx.y + 1) C) and the raw
-  // partial sums go to out + blockIdx.y * part_stride)
-  static_assert(TW == 64 || TW == 32, "tile width 64 or 32");
-  static_assert(!PAIR || TW == 32, "paired edge tiles: two 16-column halves with their halos fill the 48-float row of TW = 32");
-  constexpr int CC = 2;
-  constexpr int STRIPS = TW / 4;
-  constexpr int RPW = 64 / STRIPS;
-  constexpr int NT = TH * STRIPS * 3;
+  // (C = the channels THIS workgroup walks, Ctot = the tensors' channel count: equal except under launch_corr9_split)
+  static_assert(TW == 32, "the LDS row pitch and the strip permutation are worked out for 32-pixel tile rows");
+  constexpr int NS = kStages;
+  constexpr int CC = 2;                                // channels per chunk
+  constexpr int STRIPS = TW / 4;                       // 8 strips per tile row
+  constexpr int RPW = 64 / STRIPS;                     // 8 rows per wave
+  constexpr int NT = TH * STRIPS * 3;                  // threads of a wave group
   constexpr int NW = NT / 64;
-  constexpr int R2 = TH + 2 * kHalo;
+  constexpr int R2 = TH + 2 * kHalo;                   // source rows per channel
   constexpr int ROWS = R2 + TH;
-  constexpr int PITCH = (TW == 64) ? 72 : 48;        // (bank geometry: see corr9_pipe_kernel)
-  constexpr int V = PITCH / 4;
-  constexpr int VU2 = (TW + 2 * kHalo) / 4;
+  constexpr int PITCH = 48;                            // floats per LDS row (see the banner)
+  constexpr int V = PITCH / 4;                         // slots per row
+  constexpr int VU2 = (TW + 2 * kHalo) / 4;            // slots of a source row in use
   constexpr int SLOTS = CC * ROWS * V;
-  constexpr int NINSTR = (SLOTS + 63) / 64;
-  constexpr int K = (NINSTR + NW - 1) / NW;
-  constexpr int BUF = NINSTR * 64 * 4;
-  // NS ring stages of [tile of the workgroup][BUF]: NS - 1 chunks are in flight while one is consumed.  Level 1 (12 waves per
-  // CU, a chunk's arithmetic ~1 us): 4 stages.  The small-map instance (one 3-wave workgroup per CU, a chunk's arithmetic ~0.3 us)
-  // is bound by chunks-in-flight / DMA latency with 4 (3 chunks per ~2 us = what it measured: 0.67 us per chunk): 8 stages.
+  constexpr int NINSTR = (SLOTS + 63) / 64;            // DMA instructions per chunk
+  constexpr int K = (NINSTR + NW - 1) / NW;            // ... per wave
+  constexpr int BUF = NINSTR * 64 * 4;                 // floats per chunk image
+  // the rings: [stage][wave group][BUF]
   static_assert(NS >= 3 && NS * NTILE * BUF * 4 <= 160 * 1024, "ring fits the LDS");
   static_assert(!KSPLIT || ((NTILE == 2 || NTILE == 4) && NS * NTILE * BUF >= (NTILE - 1) * 36 * NT),
                 "channel split: two or four wave groups, sums exchanged in the rings");
   __shared__ __attribute__((aligned(16))) float rings_all[NS * NTILE * BUF];
   constexpr unsigned RB = NTILE * BUF * 4;             // bytes from one stage to the next
 
-  const int gw = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar: wave of the workgroup
-  const int half = gw / NW, wave = gw % NW;
+  const int gw = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // scalar: DMA destinations live in SGPRs
+  const int half = gw / NW, wave = gw % NW;            // my wave group, my wave in it
   const int lane = threadIdx.x & 63;
-  // xcd_remap: workgroup b runs on XCD b % 8 (round-robin dispatch); give every XCD a contiguous band of tiles, so that the
-  // halo rows two neighbouring tiles both fetch meet in ONE L2 (the launch is a single round: neighbours run side by side)
   int wg = blockIdx.x;
-  if (xcd_remap) {
-    const int nwg = gridDim.x, qq = nwg / 8, rr = nwg % 8, xcd = wg % 8, loc = wg / 8;
-    wg = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
-  }
+  if (xcd_remap) wg = xcd_local_order(wg, gridDim.x);
   const int tile = KSPLIT ? wg : wg * NTILE + half;
-  const bool live = tile < ntiles;
+  const bool live = tile < ntiles;                     // (an odd tile count leaves the last workgroup's second group without one)
   int bid = live ? tile : 0;
   const bool edge = PAIR && bid >= nreg;               // (scalar) a left-over column band shared by images n and n + 1
-  int tx, ty, n;
+  TileId id;
   if (edge) {
     bid -= nreg;
-    tx = tilesX;
-    ty = bid % tilesY;
-    n = 2 * (bid / tilesY);
+    id.tx = tilesX;
+    id.ty = bid % tilesY;
+    id.n = 2 * (bid / tilesY);
   } else {
-    tx = bid % tilesX; bid /= tilesX;
-    ty = bid % tilesY;
-    n = bid / tilesY;
+    id = decode_tile(bid, tilesX, tilesY);
   }
-  const int h0 = ty * TH, w0 = tx * TW;
-  constexpr int WPG = TH / RPW;
+  const int n = id.n, h0 = id.ty * TH, w0 = id.tx * TW;
+  constexpr int WPG = TH / RPW;                        // waves per vertical-shift group
   const int dyg = wave / WPG;
   const int q = lane / STRIPS, j = lane % STRIPS;
   const int row = (wave % WPG) * RPW + q;
-  const int strip = (TW == 64) ? ((q & 1) ? ((j + 14) & 15) : j) : (j ^ ((((q & 3) == 1) || ((q & 3) == 2)) ? 4 : 0));
+  const int strip = j ^ ((((q & 3) == 1) || ((q & 3) == 2)) ? 4 : 0);   // rows 1, 2 of every four swap their halves (banner)
 
   const size_t plane = (size_t)H * W;
   const int Cw = KSPLIT ? C / NTILE : C;              // the channels this wave group walks (KSPLIT: group g takes [g Cw, (g+1) Cw))
@@ -423,11 +430,7 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
   const float* const slab0 = out;                      // (JOIN) slice 0 of the partial volumes
   out += (size_t)blockIdx.y * part_stride;
 
-  // LDS image of a chunk (differs from corr9_pipe_kernel's): the TARGET rows of both channels first, then the source rows --
-  // [f1 c0 | f1 c1 | f2 c0 | f2 c1] -- so that the f1 / f2 border falls on a DMA instruction border (CC * TH * V slots = a
-  // multiple of 64): every instruction then has ONE tensor as its source, i.e. a scalar 64-bit base (the sample's plane 0) +
-  // a 32-bit byte offset per lane: half the address registers, and the loop has none to spare (a spilled pointer is reloaded
-  // through `s_waitcnt vmcnt(0)`, which also waits for every DMA in flight).
+  // per-lane DMA constants: where slot (k-th instruction of mine, lane) of a chunk comes from
   constexpr int F1SLOTS = CC * TH * V;
   static_assert(F1SLOTS % 64 == 0, "the target rows of a chunk must fill whole DMA instructions");
   constexpr int F2BASE = CC * TH * PITCH;              // float offset of the source rows in a ring buffer
@@ -493,11 +496,11 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
   // start V / 2 vectors into the row (a uniform shift per LDS lane group: strips 0..3 and 4..7 are never in one group)
   const int b_off = F2BASE + (row + dyg * 3) * PITCH + 4 * strip + ((edge && strip >= STRIPS / 2) ? 4 * (V / 2 - STRIPS / 2) : 0);
 
-  // one (channel, vertical shift) step: 36 products of 4 target pixels with 12 source pixels = 16 packed + 4 single FMAs,
-  // written as volatile asm: (a) products are pure arithmetic, and nothing else keeps instruction selection from emitting them
-  // after the block's last side effect (= behind the next chunks' barriers, every loaded row spilled: seen); volatile asm
-  // statements keep their order among themselves and with the DMA statements and barriers; (b) the broadcast of a target
-  // pixel is an op_sel of the pair it was loaded in (hipcc moved pixel 3 into a fresh pair: one move per channel).
+  // one (channel, vertical shift) row step: 36 products of 4 target pixels with 12 source pixels = 16 packed + 4 single FMAs.
+  // VOLATILE asm on purpose: products are pure arithmetic, and nothing else keeps the compiler from emitting them behind the
+  // block's last side effect (= behind the next chunks' barriers, every loaded row spilled); volatile statements keep their
+  // order among themselves and with the DMA statements and barriers.  The broadcast of a target pixel is an op_sel of the pair
+  // it was loaded in (no move).
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   auto step = [&](const f32x4& a, const f32x4* b, int dyi) {
     const f32x2 ap[2] = {a.xy, a.zw};
@@ -523,39 +526,34 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
     b[1] = lds_ld(rp + 16);
     b[2] = lds_ld(rp + 32);
   };
-  // A chunk in two parts of three row steps.  `nxt`: the ring that takes the chunk three ahead (`on` = 0 for the tile's last
+  // A chunk in two parts of three row steps.  `nxt`: the stage that takes the chunk three ahead (`on` = 0 for the tile's last
   // three chunks: nothing to fetch); its K DMA instructions go between the row steps of the part that has ISSUE set.  Each part
-  // is ONE basic block: no run-time test in here.  The row registers live across the parts (the first row of part two is
-  // requested under the last step of part one).
+  // is ONE basic block: no run-time test in here.  The source-row reads run one row step ahead of the products, into the other
+  // of two register sets; the sets live across the parts (the first row of part two is requested under the last step of part one).
   static_assert(K <= 3 && CC == 2, "one DMA instruction per row step of a part");
-  // DEPTH: how many row steps the source-row reads run ahead of the products (DEPTH + 1 register sets of three `ds_read_b128`).
-  // One step covers the LDS latency when three waves share a SIMD (level 1); a 3-wave workgroup of the small-map instance has
-  // a SIMD to itself per wave and registers to spare: two steps.
-  static_assert(DEPTH == 1 || DEPTH == 2, "read-ahead of one or two row steps");
-  f32x4 ra[CC], rb[DEPTH + 1][3];
+  f32x4 ra[CC], rb[2][3];
   unsigned pa = 0, pb = 0;                             // my target-row / first-source-row byte addresses in the ring in use
   auto part = [&](int cur, int nxt, unsigned long long on, auto second, auto with_issue) {     // stage indices
     constexpr int S0 = decltype(second)::value ? 3 : 0;
     constexpr bool ISSUE = decltype(with_issue)::value;
     const unsigned nx = lds0 + (unsigned)nxt * RB;
     if constexpr (S0 == 0) {
-      // (the ring's address passes through a volatile asm: otherwise the compiler keeps eight per-lane addresses, two per
-      // ring, alive across the loop, and at 168 registers that is eight spills reloaded through `s_waitcnt vmcnt(0)`)
+      // (the stage's address passes through a volatile asm: otherwise the compiler keeps eight per-lane addresses, two per
+      // stage, alive across the loop, and at 168 registers that is eight spills reloaded through `s_waitcnt vmcnt(0)`)
       unsigned sb = lds0 + (unsigned)cur * RB;
       asm volatile("" : "+s"(sb));
       pa = sb + (unsigned)a_off * 4u;
       pb = sb + (unsigned)b_off * 4u;
       ra[0] = lds_ld(pa);
-#pragma unroll
-      for (int d = 0; d < DEPTH; ++d) ldrow(rb[d], pb, d);
+      ldrow(rb[0], pb, 0);
       ra[1] = lds_ld(pa + (unsigned)(TH * PITCH * 4));
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
     for (int st = S0; st < S0 + 3; ++st) {
-      if (st + DEPTH < CC * 3) ldrow(rb[(st + DEPTH) % (DEPTH + 1)], pb, st + DEPTH);
+      if (st + 1 < CC * 3) ldrow(rb[(st + 1) % 2], pb, st + 1);
       __builtin_amdgcn_sched_barrier(0);
-      step(ra[st / 3], rb[st % (DEPTH + 1)], st % 3);
+      step(ra[st / 3], rb[st % 2], st % 3);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (ISSUE) {
         if (st - S0 < K) {
@@ -567,8 +565,8 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
   };
 
   const int nchunks = Cw / CC;                         // multiple of NS (checked by the launcher)
-  // chunk hand-off: my own DMA of the chunk has landed once at most NW_ newer instructions of mine are in flight (in-order
-  // completion), the barrier extends that to every wave's and says that everybody is done with the ring about to be refilled
+  // chunk hand-off: my own DMA of the chunk has landed once at most `nwait` newer instructions of mine are in flight (in-order
+  // completion); the barrier extends that to every wave's and says that everybody is done with the stage about to be refilled
   auto handoff = [&](auto nwait) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(nwait)::value) : "memory");
     __builtin_amdgcn_s_barrier();
@@ -579,9 +577,8 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
   const std::true_type second{}, do_issue{};
 #pragma unroll
   for (int r = 0; r < NS - 1; ++r) issue(lds0 + r * RB);               // chunks 0 .. NS - 2
-  // Zero padding: a slot without a source (outside the image, or the unused tail of a row) is never written by the DMA -- and
-  // is the same slot in every chunk.  Each lane zeroes ITS slots of the stages once, AFTER the first chunks are on their way
-  // (disjoint addresses): the first kernel zeroed all 120 KB and synchronised before its first DMA (~1 us).
+  // Zero padding: each lane zeroes ITS slots without a source in every stage, once, AFTER the first chunks are on their way
+  // (disjoint addresses; zeroing the whole ring in front of the first DMA costs ~1 us of synchronisation).
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int wi = wave + k * NW;
@@ -593,10 +590,9 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // visible to the others behind the first hand-off's barrier
   // barrier in FRONT of chunk c (chunk c landed; chunks c+1 .. c+NS-2 in flight), DMA of chunk c+NS-1 under its first part.
-  // (Tried and dropped, profiles/r04_corr_pipe2.txt: the workgroup's second tile half a chunk out of phase -- the same barriers
-  // in the MIDDLE of its chunks, so that one tile's waves multiply while the other's wait for the first rows of a new chunk:
-  // 100 instead of 88 us; two instruction streams per CU cost more than the bubbles.)
-  const std::integral_constant<int, (NS - 2) * (K - 1)> full_behind{};  // NS - 2 newer chunks, K or K - 1 instructions each
+  // NS - 2 newer chunks of K or K - 1 instructions each: counting K - 1 is exact for the waves with an empty last instruction
+  // and waits a little longer than needed in the others.  (Both wave groups keep the SAME phase: profiles/r04_corr_pipe2.txt.)
+  const std::integral_constant<int, (NS - 2) * (K - 1)> full_behind{};
   for (int ck = 0; ck < nchunks - NS; ck += NS) {        // nchunks is a multiple of NS (checked by the launcher)
     static_for<0, NS>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
@@ -605,8 +601,8 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
       part(r, (r + NS - 1) % NS, ~0ull, second, no_issue);
     });
   }
-  // The tile's last NS chunks, with the waits THEIR queue needs: behind chunk n - NS + r only NS - 1 - r chunks are in flight -- a
-  // constant count would let a wave read the last chunks before they have landed (the first 4-stage kernel did:
+  // The tile's last NS chunks, with the waits THEIR queue needs: behind chunk n - NS + r only NS - 1 - r chunks are in flight.
+  // Do NOT fold this into the loop's constant count: a wave would read the last chunks before they have landed (seen:
   // tools/micro/corr_race.py, 11 of 300 launches off by the last channels' products under memory load).
   static_for<0, NS>([&](auto rc) {
     constexpr int r = decltype(rc)::value;
@@ -654,7 +650,8 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
     }
   }
 
-  // ---- epilogue: ReLU + L2 norm over the 81 shifts on the register PAIRS (packed squares, the ReLU kept in the accumulators; the sum of squares is taken pair-wise, then across the three vertical-shift groups) ----
+  // ---- epilogue: ReLU + L2 norm over the 81 shifts on the register PAIRS (packed squares, the ReLU kept in the accumulators;
+  // the sum of squares is taken pair-wise, then across the three vertical-shift groups through stage 0 of the ring) ----
   auto get = [&](int dyi, int dx, int i) -> float {
     if (i & 1) return dx == 0 ? accs[dyi][i] : accp[dyi][i][(dx - 1) >> 1][(dx - 1) & 1];
     return dx == 8 ? accs[dyi][i] : accp[dyi][i][dx >> 1][dx & 1];
@@ -709,7 +706,7 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
         o += plane;                                    // (a running pointer: one 64-bit add per store instead of a 64-bit multiply-add)
       }
   }
-  if constexpr (JOIN != 0) {
+  if constexpr (JOIN) {
     static_assert(!FUSE && !PAIR && KSPLIT, "JOIN: raw partial sums of one tile per workgroup");
     constexpr int PX = TH * TW, NTH = NT * NTILE;
     static_assert((81 * PX + PX) <= NS * NTILE * BUF, "JOIN: the tile's volume fits the rings");
@@ -749,37 +746,33 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
           v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
         }
       }
-      if (JOIN == 2) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
       *reinterpret_cast<float4*>(&acc[d * PX + 4 * sp]) = v;
     }
     __syncthreads();
-    if (JOIN == 2) {
-      for (int px = threadIdx.x; px < PX; px += NTH) {
-        float tot = 0.f;
+    for (int px = threadIdx.x; px < PX; px += NTH) {
+      float tot = 0.f;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {                  // the three vertical-shift groups of the one-kernel epilogue, in its order
-          float ss = 0.f;
+      for (int k = 0; k < 3; ++k) {                    // the three vertical-shift groups of the one-kernel epilogue, in its order
+        float ss = 0.f;
 #pragma unroll
-          for (int d = 0; d < 27; ++d) {
-            const float r = acc[(k * 27 + d) * PX + px];
-            ss = fmaf(r, r, ss);
-          }
-          tot = k == 0 ? ss : tot + ss;
+        for (int d = 0; d < 27; ++d) {
+          const float r = acc[(k * 27 + d) * PX + px];
+          ss = fmaf(r, r, ss);
         }
-        scl[px] = 1.0f / fmaxf(sqrtf(tot), 1e-12f);
+        tot = k == 0 ? ss : tot + ss;
       }
-      __syncthreads();
+      scl[px] = 1.0f / fmaxf(sqrtf(tot), 1e-12f);
     }
+    __syncthreads();
     float* obase = joined + (size_t)n * 81 * plane;
     for (int idx = threadIdx.x; idx < 81 * (PX / 4); idx += NTH) {
       const int d = idx / (PX / 4), sp = idx % (PX / 4), rr = sp / STRIPS, st = sp % STRIPS;
       const int hh = h0 + rr, ww = w0 + 4 * st;
       if (hh < H && ww < W) {
         float4 v = *reinterpret_cast<const float4*>(&acc[d * PX + 4 * sp]);
-        if (JOIN == 2) {
-          const float4 sc = *reinterpret_cast<const float4*>(&scl[4 * sp]);
-          v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w;
-        }
+        const float4 sc = *reinterpret_cast<const float4*>(&scl[4 * sp]);
+        v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w;
         *reinterpret_cast<float4*>(obase + (size_t)d * plane + (size_t)hh * W + ww) = v;
       }
     }
@@ -789,69 +782,77 @@ __global__ __launch_bounds__(TH * (TW / 4) * 3 * NTILE, MINW) void corr9_pipe2_k
 // (The fp32-matrix-pipe formulation of this forward -- exact, measured slower: 166-171 vs 139 us, profiles/r02_corr_mfma_*.txt,
 // r03_corr_f16_ablation.txt -- lives in tools/experiments/matrix_pipe_corr/, outside the product library.)
 
+constexpr int kPipeTW = 32;        // tile width of the pipelined kernel
+constexpr int kSmallTH = 8;        // its tile height for all but the largest maps (and of the tiny maps' tickets)
+
+// One launch of the pipelined kernel over `ntiles` tiles of TH x 32 pixels.  A plain launch leaves the last four fields alone:
+// every workgroup walks all C channels, in the XCD-local tile order.  launch_corr9_split sets `slices` > 1: workgroup (b, y)
+// walks the y-th of `slices` channel slices and stores at out + y part_stride (tile order as dispatched: a handful of tiles).
+struct Pipe2Launch {
+  const float *in1, *in2;
+  float* out;
+  int C, H, W;
+  int tilesX;                      // tile columns (PAIR: the full ones)
+  long ntiles, nreg;               // tiles in all; PAIR: the regular ones among them
+  int slices = 1;
+  long part_stride = 0;
+  float* joined = nullptr;
+  unsigned* tickets = nullptr;
+};
+
+template <int TH, bool FUSE, int NTILE, bool KSPLIT = false, bool PAIR = false, bool JOIN = false>
+static int launch_pipe2(const Pipe2Launch& a, hipStream_t st) {
+  if (a.ntiles <= 0 || a.ntiles > 0x7fffffffL) return fail(RFN_EINVAL, "corr9: grid too large");
+  const long blocks = KSPLIT ? a.ntiles : cdiv(a.ntiles, (long)NTILE);
+  hipLaunchKernelGGL((corr9_pipe2_kernel<TH, kPipeTW, FUSE, NTILE, KSPLIT, PAIR, JOIN>), dim3((unsigned)blocks, (unsigned)a.slices),
+                     dim3(pipe2_threads(TH, kPipeTW, NTILE)), 0, st, a.in1, a.in2, a.out, a.C / a.slices, a.H, a.W, a.tilesX,
+                     cdiv(a.H, TH), (int)a.ntiles, a.slices == 1 ? 1 : 0, (int)a.nreg, a.C, a.part_stride, a.joined, a.tickets);
+  return check_launch("corr9_pipe2_kernel");
+}
+
 template <bool FUSE, bool WARP>
 static int launch_corr9(const float* in1, const float* in2, const float* flow, float* out, int B, int C, int H,
                         int W, hipStream_t st) {
-  if constexpr (!WARP) {
-    // The pipelined kernel: W % 4 == 0 (16-byte DMA pieces), C a multiple of the ring's NS x 2 = 8 channels (16 with the
-    // channel split), and -- its DMA offsets are 32-bit within a sample (a sample PAIR for edge tiles) -- samples below 4 GB.
-    // Anything else takes the register-staged kernel below.
-    const size_t sample = (size_t)C * H * W * sizeof(float);
-    if ((W & 3) == 0 && (C % 8) == 0 && C >= 16 && sample < (1ull << 32)) {
-      const int xcd = 1;      // XCD-local tile order: the halo rows two neighbours fetch meet in one L2 (DMA alone 65 -> 46 us)
-      // K4 level 1 (2 x 270 x 480) and larger: two independent 16 x 32 tiles per 12-wave workgroup, 3 waves per SIMD
-      const long pairs16 = ((long)B * cdiv(W, 32) * cdiv(H, 16) + 1) / 2;
-      if (pairs16 >= 192) {
-        const int tilesX = cdiv(W, 32), tilesY = cdiv(H, 16);
-        const long ntiles = (long)B * tilesX * tilesY, blocks = (ntiles + 1) / 2;
-        if (ntiles > 0x7fffffffL) return fail(RFN_EINVAL, "corr9: grid too large");
-        hipLaunchKernelGGL((corr9_pipe2_kernel<16, 32, FUSE, 3, 2, 1, 4>), dim3((unsigned)blocks), dim3(16 * 8 * 3 * 2), 0, st,
-                           in1, in2, out, C, H, W, tilesX, tilesY, (int)ntiles, xcd, 0, C, 0L, nullptr, nullptr);
-        return check_launch("corr9_pipe2_kernel");
-      }
-      // Smaller maps: single 8 x 32 tiles, 3-wave workgroups.  Up to 256 of them (one workgroup per CU) the workgroup's second
-      // wave group takes the second half of the tile's channels (KSPLIT: 136 tiles 59 -> 47 us, 256 tiles 64.5 -> 54.7 us,
-      // K2 level 1 33.8 -> 28.6 us; profiles/r04_corr_ksplit.txt).  A map that needs MORE than 256 because its width leaves
-      // half a tile column over (K4 level 2: 2 x 135 x 240 = 272 tiles) shares that column band between image pairs (PAIR)
-      // when that brings it to <= 256: 255 tiles there.
-      const int tilesY = cdiv(H, 8);
-      const long nt8 = (long)B * cdiv(W, 32) * tilesY;
-      const bool ksplit_ok = C >= 32 && C % 16 == 0;
-      const int rem = W % 32;
-      const long nreg = (long)B * (W / 32) * tilesY, npair = nreg + (long)(B / 2) * tilesY;
-      // (round 5) FOUR wave groups per tile when the channels allow it (C % 32 == 0: whole ring rounds per group): twelve waves per
-      // CU walk chunks at 9.2 wave-chunks / us against 7.1 with six (level 1 runs twelve) -- K4 level 2 64 -> ~50 us
-      const bool ksplit4 = ksplit_ok && C >= 64 && C % 32 == 0;
-      if (ksplit_ok && nt8 > 256 && rem > 0 && rem <= 16 && B % 2 == 0 && npair <= 256 && 2 * sample < (1ull << 32)) {
-        if (ksplit4)
-          hipLaunchKernelGGL((corr9_pipe2_kernel<8, 32, FUSE, 3, 4, 1, 4, true, true>), dim3((unsigned)npair), dim3(8 * 8 * 3 * 4), 0,
-                             st, in1, in2, out, C, H, W, W / 32, tilesY, (int)npair, xcd, (int)nreg, C, 0L, nullptr, nullptr);
-        else
-          hipLaunchKernelGGL((corr9_pipe2_kernel<8, 32, FUSE, 3, 2, 1, 4, true, true>), dim3((unsigned)npair), dim3(8 * 8 * 3 * 2), 0,
-                             st, in1, in2, out, C, H, W, W / 32, tilesY, (int)npair, xcd, (int)nreg, C, 0L, nullptr, nullptr);
-        return check_launch("corr9_pipe2_kernel");
-      }
-      if (nt8 > 0x7fffffffL) return fail(RFN_EINVAL, "corr9: grid too large");
-      if (ksplit_ok && nt8 <= 256) {
-        if (ksplit4)
-          hipLaunchKernelGGL((corr9_pipe2_kernel<8, 32, FUSE, 3, 4, 1, 4, true>), dim3((unsigned)nt8), dim3(8 * 8 * 3 * 4), 0, st,
-                             in1, in2, out, C, H, W, cdiv(W, 32), tilesY, (int)nt8, xcd, 0, C, 0L, nullptr, nullptr);
-        else
-          hipLaunchKernelGGL((corr9_pipe2_kernel<8, 32, FUSE, 3, 2, 1, 4, true>), dim3((unsigned)nt8), dim3(8 * 8 * 3 * 2), 0, st,
-                             in1, in2, out, C, H, W, cdiv(W, 32), tilesY, (int)nt8, xcd, 0, C, 0L, nullptr, nullptr);
-        return check_launch("corr9_pipe2_kernel");
-      }
-      hipLaunchKernelGGL((corr9_pipe2_kernel<8, 32, FUSE, 3, 1, 1, 4>), dim3((unsigned)nt8), dim3(8 * 8 * 3), 0, st, in1, in2,
-                         out, C, H, W, cdiv(W, 32), tilesY, (int)nt8, xcd, 0, C, 0L, nullptr, nullptr);
-      return check_launch("corr9_pipe2_kernel");
+  // 1. The pipelined kernel takes W % 4 == 0 (16-byte DMA pieces), C a multiple of the ring's 4 stages x 2 channels, and --
+  //    its DMA offsets are 32-bit within a sample (a sample PAIR for edge tiles) -- samples below 4 GB.
+  const size_t sample = (size_t)C * H * W * sizeof(float);
+  if (!WARP && (W & 3) == 0 && (C % 8) == 0 && C >= 16 && sample < (1ull << 32)) {
+    // 2. The geometry: 16 x 32 tile pairs / paired edge tiles / at most one tile per CU / otherwise (chosen under 4).
+    const int cols = cdiv(W, kPipeTW), rows8 = cdiv(H, kSmallTH), rem = W % kPipeTW;
+    const long nt16 = (long)B * cols * cdiv(H, 16), pairs16 = (nt16 + 1) / 2, nt8 = (long)B * cols * rows8;
+    const long nreg = (long)B * (W / kPipeTW) * rows8, npair = nreg + (long)(B / 2) * rows8;
+    const bool ksplit_ok = C >= 32 && C % 16 == 0;       // whole ring rounds for each of two wave groups
+    // 3. Two or four wave groups on a tile's channels: four when each gets whole ring rounds (twelve waves per CU walk 9.2
+    //    wave-chunks / us against 7.1 with six: level 2 64 -> ~50 us).
+    const bool four = C >= 64 && C % 32 == 0;
+    // 4. One call.
+    Pipe2Launch a{in1, in2, out, C, H, W, cols, nt8, 0};
+    if (pairs16 >= 192) {
+      // level 1 (2 x 270 x 480) and larger: two 16 x 32 tiles per 12-wave workgroup, three waves per SIMD
+      a.ntiles = nt16;
+      return launch_pipe2<16, FUSE, 2>(a, st);
     }
+    if (ksplit_ok && nt8 > 256 && rem > 0 && rem <= 16 && B % 2 == 0 && npair <= 256 && 2 * sample < (1ull << 32)) {
+      // more than 256 8 x 32 tiles only because the width leaves at most half a tile column over: image pairs share that band
+      // when that brings the map to one workgroup per CU (level 2, 2 x 135 x 240: 272 -> 255 tiles, 83 -> 64 us)
+      a.tilesX = W / kPipeTW, a.ntiles = npair, a.nreg = nreg;
+      if (four) return launch_pipe2<kSmallTH, FUSE, 4, true, true>(a, st);
+      return launch_pipe2<kSmallTH, FUSE, 2, true, true>(a, st);
+    }
+    if (ksplit_ok && nt8 <= 256) {
+      // at most one 8 x 32 tile per CU: the workgroup's wave groups split the channels (256 tiles 64.5 -> 54.7 us with two,
+      // profiles/r04_corr_ksplit.txt)
+      if (four) return launch_pipe2<kSmallTH, FUSE, 4, true>(a, st);
+      return launch_pipe2<kSmallTH, FUSE, 2, true>(a, st);
+    }
+    return launch_pipe2<kSmallTH, FUSE, 1>(a, st);      // 8 x 32 tiles, one 3-wave workgroup each
   }
-  constexpr int TH = 8, CC = 8;
-  const int tilesX = cdiv(W, kTW), tilesY = cdiv(H, TH);
+  // Anything else: the register-staged kernel.
+  const int tilesX = cdiv(W, kTW), tilesY = cdiv(H, kTH);
   const long blocks = (long)B * tilesX * tilesY;
   if (blocks <= 0 || blocks > 0x7fffffffL) return fail(RFN_EINVAL, "corr9: grid too large");
-  hipLaunchKernelGGL((corr9_tile_kernel<TH, CC, FUSE, WARP>), dim3((unsigned)blocks), dim3(TH * kStrips * 3), 0,
-                     st, in1, in2, flow, out, C, H, W, tilesX, tilesY);
+  hipLaunchKernelGGL((corr9_tile_kernel<FUSE, WARP>), dim3((unsigned)blocks), dim3(kTH * kStrips * 3), 0, st, in1, in2, flow,
+                     out, C, H, W, tilesX, tilesY);
   return check_launch("corr9_tile_kernel");
 }
 
@@ -865,7 +866,6 @@ static int launch_corr9(const float* in1, const float* in2, const float* flow, f
 // 32 pixels x 8 shift lanes per workgroup: lane (px, k) adds the S partials of shifts k, k+8, ... (coalesced over the
 // pixels) into an LDS tile [81][32]; three lanes per pixel then take the squares of the three vertical-shift groups in
 // the one-kernel epilogue's order, and everybody scales and stores.
-template <bool FUSE>
 __global__ __launch_bounds__(256) void corr9_split_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
                                                                  int S, long part_stride, long plane, long total) {
   __shared__ float tile[81][33];
@@ -889,55 +889,45 @@ __global__ __launch_bounds__(256) void corr9_split_reduce_kernel(const float* __
       }
       for (; s < S; ++s) v += q[(long)s * part_stride];
     }
-    tile[d][px] = FUSE ? fmaxf(v, 0.0f) : v;
+    tile[d][px] = fmaxf(v, 0.0f);
   }
   __syncthreads();
-  float scale = 1.0f;
-  if constexpr (FUSE) {
-    if (k < 3) {
-      float ss = 0.0f;
+  if (k < 3) {
+    float ss = 0.0f;
 #pragma unroll
-      for (int d = 0; d < 27; ++d) {
-        const float r = tile[k * 27 + d][px];
-        ss = fmaf(r, r, ss);
-      }
-      ssq[k][px] = ss;
+    for (int d = 0; d < 27; ++d) {
+      const float r = tile[k * 27 + d][px];
+      ss = fmaf(r, r, ss);
     }
-    __syncthreads();
-    scale = 1.0f / fmaxf(sqrtf(ssq[0][px] + ssq[1][px] + ssq[2][px]), 1e-12f);
+    ssq[k][px] = ss;
   }
+  __syncthreads();
+  const float scale = 1.0f / fmaxf(sqrtf(ssq[0][px] + ssq[1][px] + ssq[2][px]), 1e-12f);
   if (ok) {
     float* o = out + n * 81 * plane + pix;
     for (int d = k; d < 81; d += 8) o[(long)d * plane] = tile[d][px] * scale;
   }
 }
 
-template <bool FUSE>
 static int launch_corr9_split(const float* in1, const float* in2, float* out, float* workspace, int B, int C, int H, int W,
                               int S, hipStream_t st) {
-  constexpr int TH = 8, TW = 32;
-  const int Cc = C / S;
-  const int tilesX = cdiv(W, TW), tilesY = cdiv(H, TH);
-  const long ntiles = (long)B * tilesX * tilesY;
-  if (ntiles <= 0 || ntiles > 0x7fffffffL) return fail(RFN_EINVAL, "corr9 split: grid too large");
-  if ((size_t)C * H * W * sizeof(float) >= (1ull << 32)) return fail(RFN_EINVAL, "corr9 split: samples of 4 GB and more are not tiny maps");
+  const int Cc = C / S;                                  // channels per slice (the caller checks: a multiple of 8)
+  if ((size_t)C * H * W * sizeof(float) >= (1ull << 32))
+    return fail(RFN_EINVAL, "corr9 split: samples of 4 GB and more are not tiny maps");
   const long plane = (long)H * W, part_stride = (long)B * 81 * plane;
+  Pipe2Launch a{in1, in2, workspace, C, H, W, cdiv(W, kPipeTW), (long)B * cdiv(W, kPipeTW) * cdiv(H, kSmallTH), 0, S, part_stride};
   if (Cc >= 64 && Cc % 32 == 0 && (W & 3) == 0) {
     // ONE launch: four wave groups per workgroup on the quarters of its slice, the tile's last workgroup joins the slices.
     // Tickets: the ntiles unsigned ints behind the partial volumes (rfn_local_corr_layer_split_workspace_bytes).
-    unsigned* tickets = reinterpret_cast<unsigned*>(workspace + (size_t)S * part_stride);
-    hipLaunchKernelGGL((corr9_pipe2_kernel<TH, TW, false, 3, 4, 1, 4, true, false, FUSE ? 2 : 1>), dim3((unsigned)ntiles, (unsigned)S),
-                       dim3(TH * (TW / 4) * 3 * 4), 0, st, in1, in2, workspace, Cc, H, W, tilesX, tilesY, (int)ntiles, 0, 0, C,
-                       part_stride, out, tickets);
-    return check_launch("corr9_pipe2_kernel (channel split, joined in the launch)");
+    a.joined = out;
+    a.tickets = reinterpret_cast<unsigned*>(workspace + (size_t)S * part_stride);
+    return launch_pipe2<kSmallTH, false, 4, true, false, true>(a, st);
   }
-  // slice blockIdx.y of the channels per workgroup (Cc % 8 == 0: whole rounds of the 4-stage ring), raw partial volumes
-  hipLaunchKernelGGL((corr9_pipe2_kernel<TH, TW, false, 3, 1, 1, 4>), dim3((unsigned)ntiles, (unsigned)S), dim3(TH * (TW / 4) * 3),
-                     0, st, in1, in2, workspace, Cc, H, W, tilesX, tilesY, (int)ntiles, 0, 0, C, part_stride, nullptr, nullptr);
-  if (int rc = check_launch("corr9_pipe2_kernel (channel split)")) return rc;
+  // two launches: raw partial volumes from one wave group per slice (whole rounds of the ring: Cc % 8 == 0), then the reduce
+  if (int rc = launch_pipe2<kSmallTH, false, 1>(a, st)) return rc;
   const long total = (long)B * plane;
-  hipLaunchKernelGGL((corr9_split_reduce_kernel<FUSE>), dim3(cdiv(total, 32)), dim3(256), 0, st, workspace, out, S,
-                     part_stride, plane, total);
+  hipLaunchKernelGGL(corr9_split_reduce_kernel, dim3(cdiv(total, 32)), dim3(256), 0, st, workspace, out, S, part_stride, plane,
+                     total);
   return check_launch("corr9_split_reduce_kernel");
 }
 
@@ -1041,11 +1031,8 @@ __global__ __launch_bounds__(256) void corr9_bwd_tile_kernel(const float* __rest
                                                              int tilesX, int tilesY) {
   constexpr int TH = 8, TW = 32, CC = 8, RH = TH + 8, RW = TW + 8;
   __shared__ float tile[CC][RH][RW + 1];
-  int bid = blockIdx.x;
-  const int tx = bid % tilesX; bid /= tilesX;
-  const int ty = bid % tilesY;
-  const int n = bid / tilesY;
-  const int h0 = ty * TH, w0 = tx * TW;
+  const TileId id = decode_tile(blockIdx.x, tilesX, tilesY);
+  const int n = id.n, h0 = id.ty * TH, w0 = id.tx * TW;
   const int lx = threadIdx.x % TW, ly = threadIdx.x / TW;
   const int qy = h0 + ly, qx = w0 + lx;
   const bool inq = qy < H && qx < W;
@@ -1096,16 +1083,15 @@ __global__ __launch_bounds__(256) void corr9_bwd_tile_kernel(const float* __rest
   }
 }
 
-// Round 5: the same gather on register STRIPS, laid out like the forward.  A thread owns 4 adjacent pixels of a row and the
+// The same gather on register STRIPS, laid out like the forward.  A thread owns 4 adjacent pixels of a row and the
 // weights of THREE vertical shifts (27 shifts x 4 pixels = 108 registers); the three wave groups of a 192-thread workgroup split
 // the nine vertical shifts of an 8 x 32 tile.  Per channel and vertical shift a thread reads its 12 row values as three
 // ds_read_b128 and does 36 FMAs (the one-pixel kernel above: one ds_read_b32 per FMA -- LDS-bound); the groups' partial sums of
 // a chunk of 8 channels meet in LDS (group 0 adds groups 1, 2 in that order: deterministic) and leave as 16-byte stores.  The
 // next chunk's halo tile is in flight to registers while a chunk is computed (double-buffered LDS, ONE barrier per chunk).
 // Both gradients in ONE launch (blockIdx.y).  W % 4 == 0, C % 8 == 0; anything else takes the one-pixel kernel.
-// K4 level 1 (2 x 128 x 270 x 480, both gradients): 997 us (two launches of the one-pixel kernel) -> 512 (strips, plain float
-// loop) -> 324 (aligned register pairs) -> 308 us (conflict-free lane order) = 0.25 of 8 TB/s on 615 MB; matcher training step
-// 100 -> 91-93 ms (profiles/r05_corr_backward.txt).
+// Level 1 (2 x 128 x 270 x 480, both gradients): 997 us in two launches of the one-pixel kernel, 308 us here = 0.25 of 8 TB/s
+// on 615 MB (profiles/r05_corr_backward.txt; the steps in between: DESIGN.md section 4).
 template <int MODE>
 __device__ __forceinline__ void corr9_bwd_strip_body(const float* __restrict__ other, const float* __restrict__ gout,
                                                      float* __restrict__ grad, int C, int H, int W, int tilesX, int tilesY,
@@ -1124,15 +1110,8 @@ __device__ __forceinline__ void corr9_bwd_strip_body(const float* __restrict__ o
   const int quad = lane >> 2, q7 = quad & 7;
   const int ly = 2 * ((0x32130210u >> (4 * q7)) & 3) + (quad >> 3);
   const int strip = 4 * ((0xE8u >> q7) & 1) + (lane & 3);
-  int bid = blockIdx.x;
-  {                                                      // XCD-local tile order (neighbours share halo rows in one L2)
-    const int nwg = gridDim.x, qq = nwg / 8, rr = nwg % 8, xcd = bid % 8, loc = bid / 8;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + loc;
-  }
-  const int tx = bid % tilesX; bid /= tilesX;
-  const int ty = bid % tilesY;
-  const int n = bid / tilesY;
-  const int h0 = ty * TH, w0 = tx * TW;
+  const TileId id = decode_tile(xcd_local_order(blockIdx.x, gridDim.x), tilesX, tilesY);
+  const int n = id.n, h0 = id.ty * TH, w0 = id.tx * TW;
   const int qy = h0 + ly, qx0 = w0 + 4 * strip;
   const bool inq = qy < H && qx0 < W;                    // W % 4 == 0: a strip is all in or all out
   const size_t plane = (size_t)H * W;
@@ -1381,57 +1360,67 @@ static inline bool is_k1(const CorrParams& p) {
   return p.kH == 1 && p.kW == 1 && p.padH == 0 && p.padW == 0 && p.dH == 1 && p.dW == 1;
 }
 
+// grid of the one-thread-per-element kernels (grid-stride loops)
+static inline int flat_grid(long total) { return (int)std::min<long>(cdiv(total, 256), 256L * 32); }
+
+// Backward of the hot parameterisation, f32: the strip kernel, or the one-pixel kernel once per gradient.
+static int corr9_bwd_f32(const float* in1, const float* in2, const float* gout, float* g1, float* g2, const CorrParams& p,
+                         hipStream_t st) {
+  const int tilesX = cdiv(p.iW, 32), tilesY = cdiv(p.iH, 8);
+  const long blocks = (long)p.B * tilesX * tilesY;
+  if (blocks > 0x7fffffffL) return fail(RFN_EINVAL, "corr bwd: grid too large");
+  if (p.iW % 4 == 0 && p.C % 8 == 0 && (size_t)p.C * p.iH * p.iW < (1ull << 31) &&
+      (((size_t)in1 | (size_t)in2 | (size_t)gout | (size_t)g1 | (size_t)g2) & 15) == 0) {
+    hipLaunchKernelGGL(corr9_bwd_strip_kernel, dim3((unsigned)blocks, 2), dim3(192), 0, st, in1, in2, gout, g1, g2, p.C, p.iH,
+                       p.iW, tilesX, tilesY);
+    return check_launch("corr9_bwd_strip_kernel");
+  }
+  hipLaunchKernelGGL((corr9_bwd_tile_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, st, in2, gout, g1, p.C, p.iH, p.iW,
+                     tilesX, tilesY);
+  if (int rc = check_launch("corr9_bwd_tile_kernel<1>")) return rc;
+  hipLaunchKernelGGL((corr9_bwd_tile_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, st, in1, gout, g2, p.C, p.iH, p.iW,
+                     tilesX, tilesY);
+  return check_launch("corr9_bwd_tile_kernel<2>");
+}
+
+// Dispatch, by type at compile time and by parameterisation at run time.
+// Forward: the hot parameterisation in f32 -> launch_corr9 (NOT the generic kernel: a caller that wants that one launches it
+// itself); anything else -> corr_generic_fwd_kernel.
 template <typename T>
 static int corr_fwd_any(const T* in1, const T* in2, T* out, const CorrParams& p, hipStream_t st) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (is_hot_param(p)) return launch_corr9<false, false>(in1, in2, nullptr, out, p.B, p.C, p.iH, p.iW, st);
+  }
   const long total = (long)p.B * p.patchH * p.patchW * p.oH * p.oW;
-  const int grid = (int)std::min<long>(cdiv(total, 256), 256L * 32);
-  hipLaunchKernelGGL((corr_generic_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, in1, in2, out, p, total);
+  hipLaunchKernelGGL((corr_generic_fwd_kernel<T>), dim3(flat_grid(total)), dim3(256), 0, st, in1, in2, out, p, total);
   return check_launch("corr_generic_fwd_kernel");
 }
 
+// Backward: the hot parameterisation in f32 -> corr9_bwd_f32; half -> gather; kernel 1 / stride 1 / pad 0 ->
+// corr_k1_bwd_kernel; anything else -> the scatter kernel (atomics: refused in deterministic mode).
 template <typename T>
 static int corr_bwd_any(const T* in1, const T* in2, const T* gout, T* g1, T* g2, const CorrParams& p,
                         hipStream_t st) {
+  const long npix = (long)p.B * p.C * p.iH * p.iW;
   if constexpr (std::is_same<T, float>::value) {
-    if (is_hot_param(p)) {
-      const int tilesX = cdiv(p.iW, 32), tilesY = cdiv(p.iH, 8);
-      const long blocks = (long)p.B * tilesX * tilesY;
-      if (blocks > 0x7fffffffL) return fail(RFN_EINVAL, "corr bwd: grid too large");
-      if (p.iW % 4 == 0 && p.C % 8 == 0 && (size_t)p.C * p.iH * p.iW < (1ull << 31) &&
-          (((size_t)in1 | (size_t)in2 | (size_t)gout | (size_t)g1 | (size_t)g2) & 15) == 0) {
-        hipLaunchKernelGGL(corr9_bwd_strip_kernel, dim3((unsigned)blocks, 2), dim3(192), 0, st, in1, in2, gout, g1, g2, p.C, p.iH,
-                           p.iW, tilesX, tilesY);
-        return check_launch("corr9_bwd_strip_kernel");
-      }
-      hipLaunchKernelGGL((corr9_bwd_tile_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, st, in2, gout, g1, p.C,
-                         p.iH, p.iW, tilesX, tilesY);
-      if (int rc = check_launch("corr9_bwd_tile_kernel<1>")) return rc;
-      hipLaunchKernelGGL((corr9_bwd_tile_kernel<2>), dim3((unsigned)blocks), dim3(256), 0, st, in1, gout, g2, p.C,
-                         p.iH, p.iW, tilesX, tilesY);
-      return check_launch("corr9_bwd_tile_kernel<2>");
-    }
+    if (is_hot_param(p)) return corr9_bwd_f32(in1, in2, gout, g1, g2, p, st);
   }
   if constexpr (std::is_same<T, __half>::value) {
-    const long total = (long)p.B * p.C * p.iH * p.iW;
-    const int grid = (int)std::min<long>(cdiv(total, 256), 256L * 32);
-    hipLaunchKernelGGL((corr_generic_bwd_gather_kernel<T>), dim3(grid), dim3(256), 0, st, in1, in2, gout, g1, g2, p, total);
+    hipLaunchKernelGGL((corr_generic_bwd_gather_kernel<T>), dim3(flat_grid(npix)), dim3(256), 0, st, in1, in2, gout, g1, g2, p,
+                       npix);
     return check_launch("corr_generic_bwd_gather_kernel");
   } else {
-  if (is_k1(p)) {
-    const long total = (long)p.B * p.C * p.iH * p.iW;
-    const int grid = (int)std::min<long>(cdiv(total, 256), 256L * 32);
-    hipLaunchKernelGGL((corr_k1_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, in1, in2, gout, g1, g2, p, total);
-    return check_launch("corr_k1_bwd_kernel");
-  }
-  RFN_REFUSE_NONDET(true, "rfn_corr_bwd", "corr_generic_bwd_kernel, floating-point atomics (no deterministic form)");
-  const size_t bytes = sizeof(T) * (size_t)p.B * p.C * p.iH * p.iW;
-  if (hipMemsetAsync(g1, 0, bytes, st) != hipSuccess || hipMemsetAsync(g2, 0, bytes, st) != hipSuccess)
-    return fail(RFN_ELAUNCH, "corr bwd: hipMemsetAsync failed");
-  const long total = (long)p.B * p.patchH * p.patchW * p.oH * p.oW;
-  const int grid = (int)std::min<long>(cdiv(total, 256), 256L * 32);
-  hipLaunchKernelGGL((corr_generic_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, in1, in2, gout, g1, g2, p,
-                     total);
-  return check_launch("corr_generic_bwd_kernel");
+    if (is_k1(p)) {
+      hipLaunchKernelGGL((corr_k1_bwd_kernel<T>), dim3(flat_grid(npix)), dim3(256), 0, st, in1, in2, gout, g1, g2, p, npix);
+      return check_launch("corr_k1_bwd_kernel");
+    }
+    RFN_REFUSE_NONDET(true, "rfn_corr_bwd", "corr_generic_bwd_kernel, floating-point atomics (no deterministic form)");
+    const size_t bytes = sizeof(T) * (size_t)npix;
+    if (hipMemsetAsync(g1, 0, bytes, st) != hipSuccess || hipMemsetAsync(g2, 0, bytes, st) != hipSuccess)
+      return fail(RFN_ELAUNCH, "corr bwd: hipMemsetAsync failed");
+    const long total = (long)p.B * p.patchH * p.patchW * p.oH * p.oW;
+    hipLaunchKernelGGL((corr_generic_bwd_kernel<T>), dim3(flat_grid(total)), dim3(256), 0, st, in1, in2, gout, g1, g2, p, total);
+    return check_launch("corr_generic_bwd_kernel");
   }
 }
 
@@ -1441,70 +1430,29 @@ using namespace rfn;
 
 extern "C" {
 
-int rfn_corr_fwd_f32(const float* in1, const float* in2, float* out, int B, int C, int iH, int iW, int kH,
-                     int kW, int patchH, int patchW, int padH, int padW, int dilH, int dilW, int dpH, int dpW,
-                     int dH, int dW, rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && out, "rfn_corr_fwd_f32: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (is_hot_param(p)) return launch_corr9<false, false>(in1, in2, nullptr, out, B, C, iH, iW, st);
-  return corr_fwd_any<float>(in1, in2, out, p, st);
-}
-
-int rfn_corr_fwd_f64(const double* in1, const double* in2, double* out, int B, int C, int iH, int iW, int kH,
-                     int kW, int patchH, int patchW, int padH, int padW, int dilH, int dilW, int dpH, int dpW,
-                     int dH, int dW, rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && out, "rfn_corr_fwd_f64: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  return corr_fwd_any<double>(in1, in2, out, p, (hipStream_t)stream);
-}
-
-int rfn_corr_bwd_f32(const float* in1, const float* in2, const float* grad_out, float* grad_in1,
-                     float* grad_in2, int B, int C, int iH, int iW, int kH, int kW, int patchH, int patchW,
-                     int padH, int padW, int dilH, int dilW, int dpH, int dpW, int dH, int dW,
-                     rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && grad_out && grad_in1 && grad_in2, "rfn_corr_bwd_f32: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  return corr_bwd_any<float>(in1, in2, grad_out, grad_in1, grad_in2, p, (hipStream_t)stream);
-}
-
-int rfn_corr_bwd_f64(const double* in1, const double* in2, const double* grad_out, double* grad_in1,
-                     double* grad_in2, int B, int C, int iH, int iW, int kH, int kW, int patchH, int patchW,
-                     int padH, int padW, int dilH, int dilW, int dpH, int dpW, int dH, int dW,
-                     rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && grad_out && grad_in1 && grad_in2, "rfn_corr_bwd_f64: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  return corr_bwd_any<double>(in1, in2, grad_out, grad_in1, grad_in2, p, (hipStream_t)stream);
-}
-
-int rfn_corr_fwd_f16(const void* in1, const void* in2, void* out, int B, int C, int iH, int iW, int kH, int kW, int patchH,
-                     int patchW, int padH, int padW, int dilH, int dilW, int dpH, int dpW, int dH, int dW,
-                     rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && out, "rfn_corr_fwd_f16: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  return corr_fwd_any<__half>((const __half*)in1, (const __half*)in2, (__half*)out, p, (hipStream_t)stream);
-}
-
-int rfn_corr_bwd_f16(const void* in1, const void* in2, const void* grad_out, void* grad_in1, void* grad_in2, int B, int C,
-                     int iH, int iW, int kH, int kW, int patchH, int patchW, int padH, int padW, int dilH, int dilW, int dpH,
-                     int dpW, int dH, int dW, rfn_stream_t stream) {
-  RFN_REQUIRE(in1 && in2 && grad_out && grad_in1 && grad_in2, "rfn_corr_bwd_f16: null pointer");
-  CorrParams p;
-  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW))
-    return rc;
-  return corr_bwd_any<__half>((const __half*)in1, (const __half*)in2, (const __half*)grad_out, (__half*)grad_in1,
-                              (__half*)grad_in2, p, (hipStream_t)stream);
-}
+// The six sampler entry points: one body per direction.  P is the ABI's pointer type (void for half), T the kernels'.
+#define RFN_CORR_ARGS                                                                                                      \
+  int B, int C, int iH, int iW, int kH, int kW, int patchH, int patchW, int padH, int padW, int dilH, int dilW, int dpH, \
+      int dpW, int dH, int dW, rfn_stream_t stream
+#define RFN_CORR_ENTRY(SUFFIX, P, T)                                                                                      \
+  int rfn_corr_fwd_##SUFFIX(const P* in1, const P* in2, P* out, RFN_CORR_ARGS) {                                           \
+    RFN_REQUIRE(in1 && in2 && out, "rfn_corr_fwd_" #SUFFIX ": null pointer");                                              \
+    CorrParams p;                                                                                                         \
+    if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW)) return rc; \
+    return corr_fwd_any<T>((const T*)in1, (const T*)in2, (T*)out, p, (hipStream_t)stream);                                \
+  }                                                                                                                       \
+  int rfn_corr_bwd_##SUFFIX(const P* in1, const P* in2, const P* grad_out, P* grad_in1, P* grad_in2, RFN_CORR_ARGS) {      \
+    RFN_REQUIRE(in1 && in2 && grad_out && grad_in1 && grad_in2, "rfn_corr_bwd_" #SUFFIX ": null pointer");                 \
+    CorrParams p;                                                                                                         \
+    if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW)) return rc; \
+    return corr_bwd_any<T>((const T*)in1, (const T*)in2, (const T*)grad_out, (T*)grad_in1, (T*)grad_in2, p,               \
+                           (hipStream_t)stream);                                                                          \
+  }
+RFN_CORR_ENTRY(f32, float, float)
+RFN_CORR_ENTRY(f64, double, double)
+RFN_CORR_ENTRY(f16, void, __half)
+#undef RFN_CORR_ENTRY
+#undef RFN_CORR_ARGS
 
 int rfn_local_corr_layer_f32(const float* feature_target, const float* feature_source, const float* flow,
                              float* out, int B, int C, int H, int W, rfn_stream_t stream) {
@@ -1517,7 +1465,7 @@ int rfn_local_corr_layer_f32(const float* feature_target, const float* feature_s
 
 long rfn_local_corr_layer_split_workspace_bytes(int B, int H, int W, int splits) {
   if (B <= 0 || H <= 0 || W <= 0 || splits <= 0) return 0;
-  const long tickets = (long)B * rfn::cdiv(W, 32) * rfn::cdiv(H, 8);
+  const long tickets = (long)B * rfn::cdiv(W, rfn::kPipeTW) * rfn::cdiv(H, rfn::kSmallTH);   // one per tile of launch_corr9_split
   return ((long)splits * B * 81 * H * W + tickets) * 4;
 }
 
@@ -1528,7 +1476,7 @@ int rfn_local_corr_layer_split_f32(const float* feature_target, const float* fea
               B, C, H, W);
   RFN_REQUIRE(splits >= 2 && splits <= 64 && C % splits == 0 && (C / splits) % 8 == 0,
               "rfn_local_corr_layer_split_f32: %d channels in %d chunks (chunks of a multiple of 8 channels)", C, splits);
-  return launch_corr9_split<true>(feature_target, feature_source, out, workspace, B, C, H, W, splits, (hipStream_t)stream);
+  return launch_corr9_split(feature_target, feature_source, out, workspace, B, C, H, W, splits, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -83,6 +83,47 @@ def test_corr_channel_split_tiles_vs_oracle(dev, oracle, shape):
     np.testing.assert_allclose(fused.cpu().numpy(), oracle.local_correlation_layer(b, a), rtol=1e-4, atol=1e-5)
 
 
+def _corr_raw_and_fused_vs_oracle(dev, oracle, shape, seed):
+    from refign_amd.correlation import local_correlation_layer, spatial_correlation_sample
+    rng = np.random.default_rng(seed)
+    a = oracle.l2_normalize(np.maximum(rng.standard_normal(shape), 0).astype(np.float32) + 1e-3)
+    b = oracle.l2_normalize(np.maximum(rng.standard_normal(shape), 0).astype(np.float32) + 1e-3)
+    out = spatial_correlation_sample(T(a, dev), T(b, dev), patch_size=9)
+    np.testing.assert_allclose(out.cpu().numpy(), oracle.corr_forward(a, b, patch_size=9), rtol=1e-4, atol=1e-5)
+    fused = local_correlation_layer(T(b, dev), T(a, dev))
+    np.testing.assert_allclose(fused.cpu().numpy(), oracle.local_correlation_layer(b, a), rtol=1e-4, atol=1e-5)
+
+
+@pytest.mark.parametrize("shape", [(1, 24, 19, 36), (2, 40, 9, 68), (1, 32, 130, 544)])
+def test_corr_one_wave_group_tiles_vs_oracle(dev, oracle, shape):
+    """The pipelined kernel with ONE wave group per 8 x 32 tile (corr9_pipe2_kernel<8, 32, .., NTILE = 1>), raw volume and fused
+    layer against the oracle.  The first two shapes have C % 16 != 0, which rules out the in-workgroup channel split: 6 tiles
+    with ragged rows and columns and three ring rounds, 12 tiles and five ring rounds.  The third has 289 tiles -- more than one
+    per CU, and a width that is a multiple of 32 leaves no edge band to pair.  None of them takes the cross-workgroup split."""
+    from refign_amd import correlation
+    B, C, H, W = shape
+    assert W % 4 == 0 and C % 8 == 0 and C >= 16                              # pipelined-eligible
+    nt8 = B * -(-W // 32) * -(-H // 8)
+    assert (B * -(-W // 32) * -(-H // 16) + 1) // 2 < 192                     # not the paired 16 x 32 tiles
+    assert C % 16 != 0 or (nt8 > 256 and W % 32 == 0)                         # no channel split, no paired edge tiles
+    assert correlation._channel_splits(B, C, H, W) == 1
+    _corr_raw_and_fused_vs_oracle(dev, oracle, shape, sum(shape) + 3)
+
+
+def test_corr_two_tiles_per_workgroup_vs_oracle(dev, oracle):
+    """The level-1 instance (corr9_pipe2_kernel<16, 32, .., NTILE = 2>: two 16 x 32 tiles per workgroup) at the smallest map that
+    reaches it: 11 x 35 = 385 tiles = 193 workgroups (the launcher's threshold is 192).  The tile count is odd, so the second
+    wave group of the last workgroup has no tile; rows and columns are ragged (549 = 34 x 16 + 5, 340 = 10 x 32 + 20); 24 channels
+    are two trips of the main loop and the tail.  Raw volume and fused layer against the oracle."""
+    from refign_amd import correlation
+    shape = B, C, H, W = (1, 24, 549, 340)
+    tiles = B * -(-W // 32) * -(-H // 16)
+    assert tiles == 385 and tiles % 2 == 1 and (tiles + 1) // 2 == 193 >= 192  # the shape this test is about
+    assert H % 16 == 5 and W % 32 == 20 and W % 4 == 0 and C % 8 == 0 and C >= 16
+    assert correlation._channel_splits(B, C, H, W) == 1
+    _corr_raw_and_fused_vs_oracle(dev, oracle, shape, sum(shape) + 3)
+
+
 @pytest.mark.parametrize("shape", [(2, 32, 135, 240), (2, 48, 130, 236), (2, 32, 129, 228), (2, 64, 135, 240), (2, 96, 131, 240)])
 def test_corr_paired_edge_tiles_vs_oracle(dev, oracle, shape):
     """Round 5 (K4 level 2, 2 x C x 135 x 240): a map of MORE than 256 8 x 32 tiles whose width leaves at most half a tile column

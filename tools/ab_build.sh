@@ -10,7 +10,7 @@ objs=""
 for f in $R/refign_amd/lib/obj/*.o; do
   b=$(basename $f .o); use=$f
   for s in "$@"; do if [ "$b" = "$(basename $s .hip)" ]; then
-    extra=""; case $b in attn|f8|mfma_gemm) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
+    extra=""; case $b in attn|f8|mfma_gemm) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; corr) extra="-Wno-inline-asm";; esac
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function $extra $flags -c $R/refign_amd/csrc/$b.hip -o $O/$b.o
     use=$O/$b.o
   fi; done
