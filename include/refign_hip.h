@@ -835,6 +835,32 @@ int rfn_steplog_gather(const void* const* ptrs, const int* dtypes, int n, double
 int rfn_grad_sqnorm_groups(const float* flat, long n, const long* chunks, int nchunks, int ngroups, double* partials,
                            double* out, rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Warp supervision of the matcher (csrc/flowsynth.hip, refign_amd/flowsynth.py; additions to ABI 4): the reference's
+ * CompositeFlow + CenterCrop for ONE sample per call, fp32, no floating-point atomics (legal under
+ * rfn_set_deterministic(1)).  Errors (nothing is launched): a null pointer, h or w < 2, a crop that does not lie in the
+ * frame, more than 13 bumps, an unknown transform code.
+ *   rfn_flowsynth_flow_f32  flow (2, h, w) of the full frame from the parameters alone.  theta: HOST array of 39 floats
+ *                           -- the homography h0 .. h8, the spline's W_X (9), W_Y (9), A_X (3), A_Y (3), the 2 x 3
+ *                           affine matrix; kind: 0 hom, 1 affine, 2 tps, 3 afftps.  With the elastic step, field:
+ *                           DEVICE (2, h, w), the blurred and scaled perturbation (dx, dy), and bumps: HOST array of
+ *                           n_bumps x 4 floats (mu of axis 0, mu of axis 1, sigma, scale 2 / max); field NULL: no
+ *                           elastic step.  count: one DEVICE int, ZEROED by the caller; the call adds the number of
+ *                           full-frame pixels inside create_border_mask (integer atomics, one per workgroup).
+ *   rfn_flowsynth_warp_f32  the crop window (ch, cw) at (top, left): out_image (3, ch, cw) = grid_sample(image (3, h, w),
+ *                           grid + flow, align_corners=True, zeros), out_flow (2, ch, cw), out_mask (ch, cw) bytes 0 / 1:
+ *                           the warp mask, or the border mask when count[0] < h * w * min_fraction_valid.
+ *   rfn_gaussian_blur_f32   dst (planes, h, w) = the separable correlation of src with `taps` (DEVICE, ntaps odd) under
+ *                           BORDER_REFLECT_101, repeated as often as the radius asks; fp64 accumulation through both
+ *                           passes, rounded once.  tmp: planes * h * w doubles of device scratch.  src == dst is allowed.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_flowsynth_flow_f32(const float* theta, int kind, const float* bumps, int n_bumps, const float* field, int h, int w,
+                           float* flow, int* count, rfn_stream_t stream);
+int rfn_flowsynth_warp_f32(const float* image, const float* flow, const int* count, int h, int w, int top, int left, int ch, int cw,
+                           double min_fraction_valid, float* out_image, float* out_flow, void* out_mask, rfn_stream_t stream);
+int rfn_gaussian_blur_f32(const float* src, const float* taps, int ntaps, int planes, int h, int w, double* tmp, float* dst,
+                          rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

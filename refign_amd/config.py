@@ -231,3 +231,65 @@ def ingest_plan(cfg, split, dataset):
                 raise OutOfScopeError(f"ingest_plan: {path} ({split}.{dataset}) takes `same_shape_keys` (two keys) or `size`")
             plan["pad"] = "same" if keys is not None else pair(size)
     return plan
+
+
+# CompositeFlow's keywords that draw_composite carries (refign_amd/flowsynth.py), with the reference's defaults
+_COMPOSITE_DEFAULTS = {"include_transforms": ["hom", "affine"], "random_alpha": 0.065, "random_s": 0.6, "random_tx": 0.3,
+                       "random_ty": 0.1, "random_t_tps": 0, "random_t_hom": 0.3, "random_t_tps_for_afftps": 0,
+                       "parameterize_with_gaussian": False, "add_elastic": False}
+
+
+def warp_supervision_plan(cfg, split="train", dataset="MegaDepth"):
+    """The geometric half of `data.init_args.load_config[split][dataset]`'s pipeline -- transforms.CompositeFlow and the
+    transforms.CenterCrop after it -- as the keywords of refign_amd.flowsynth.WarpSupervision:
+      composite                 draw_composite's keywords: CompositeFlow's init_args over the reference's defaults
+      crop                      CenterCrop's size (h, w), or None when the section has none
+      min_fraction_valid_corr   CompositeFlow's (0.1 when absent)
+    Every other transform of the section (the photometric chain on image_prime, the conversions) is passed over: this reads two
+    entries and builds nothing.  OutOfScopeError names what cannot be carried: a section without CompositeFlow or with two, a
+    CenterCrop in front of it, apply_keys other than ['image_prime'], parameterize_with_gaussian, a transform name that
+    draw_composite does not know, an unknown keyword.  ingest_plan keeps refusing such a section: it describes the path from a
+    file to the batch tensors, this the step after it."""
+    try:
+        sec = cfg["data"]["init_args"]["load_config"][split][dataset]
+    except (KeyError, TypeError) as e:
+        raise KeyError(f"warp_supervision_plan: no data.init_args.load_config.{split}.{dataset} in this config") from e
+    from .flowsynth import TRANSFORMS
+    where = f"({split}.{dataset})"
+    composite = crop = None
+    min_fraction = 0.1
+    for spec in sec.get("transforms") or []:
+        path = spec["class_path"] if is_spec(spec) else str(spec)
+        name, args = path.rsplit(".", 1)[-1], (spec.get("init_args") or {}) if is_spec(spec) else {}
+        if not path.startswith("data_modules.transforms."):
+            continue
+        if name == "CompositeFlow":
+            if composite is not None:
+                raise OutOfScopeError(f"warp_supervision_plan: a second CompositeFlow {where}")
+            if list(args.get("apply_keys") or []) != ["image_prime"]:
+                raise OutOfScopeError(f"warp_supervision_plan: CompositeFlow with apply_keys {args.get('apply_keys', 'all')!r} {where}: "
+                                      f"['image_prime'] is what the device path warps")
+            extra = set(args) - set(_COMPOSITE_DEFAULTS) - {"apply_keys", "min_fraction_valid_corr"}
+            if extra:
+                raise OutOfScopeError(f"warp_supervision_plan: CompositeFlow with {sorted(extra)} {where}")
+            composite = {k: args.get(k, v) for k, v in _COMPOSITE_DEFAULTS.items()}
+            composite["include_transforms"] = list(composite["include_transforms"])
+            if composite["parameterize_with_gaussian"]:
+                raise OutOfScopeError(f"warp_supervision_plan: CompositeFlow with parameterize_with_gaussian {where}: the device "
+                                      f"path carries the uniform draws only")
+            unknown = [t for t in composite["include_transforms"] if t not in TRANSFORMS]
+            if unknown:
+                raise OutOfScopeError(f"warp_supervision_plan: CompositeFlow with transforms {unknown} {where} "
+                                      f"({' / '.join(TRANSFORMS)})")
+            min_fraction = float(args.get("min_fraction_valid_corr", 0.1))
+        elif name == "CenterCrop":
+            if composite is None or crop is not None:
+                raise OutOfScopeError(f"warp_supervision_plan: CenterCrop {where} in front of CompositeFlow, or a second one")
+            extra = set(args) - {"size", "apply_keys"}
+            if extra or args.get("apply_keys", "all") != "all":
+                raise OutOfScopeError(f"warp_supervision_plan: CenterCrop with {sorted(extra) or 'apply_keys'} {where}")
+            size = args["size"]
+            crop = (int(size), int(size)) if isinstance(size, int) else tuple(int(a) for a in size)
+    if composite is None:
+        raise OutOfScopeError(f"warp_supervision_plan: no data_modules.transforms.CompositeFlow {where}")
+    return {"composite": composite, "crop": crop, "min_fraction_valid_corr": min_fraction}
