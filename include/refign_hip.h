@@ -861,6 +861,37 @@ int rfn_flowsynth_warp_f32(const float* image, const float* flow, const int* cou
 int rfn_gaussian_blur_f32(const float* src, const float* taps, int ntaps, int planes, int h, int w, double* tmp, float* dst,
                           rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Matcher training through Trainer (additions to ABI 4).
+ *
+ * The multi-level flow loss (csrc/flowloss.hip, refign_amd/flowloss.py): MultiScaleFlowLoss with downsample_gt_flow=True
+ * over all levels of one call, fp32, no floating-point atomics (legal under rfn_set_deterministic(1)).
+ *   levels   HOST array of nlevels (<= 8) x 8 longs {flow (B,2,h,w), logvar (B,c,h,w) or 0, mask (B,h,w) bytes 0 / 1 or 0,
+ *            grad_flow or 0, grad_logvar or 0, h, w, c} -- DEVICE addresses; the two gradient addresses are read by the
+ *            backward only.  c: log-variance channels, 0 (no pointer), 1, or 2 (logsumexp).  B * h * w < 2^30 per level.
+ *   weights  HOST array of nlevels doubles.
+ *   loss_type 0 L1Loss, 1 L2Loss, 2 HuberLoss (2 delta smooth_l1(beta = delta)); delta > 0.
+ *   rfn_flowloss_fwd_f32  gt_flow (B,2,H,W) is resized to every level with the arithmetic of F.interpolate(mode='bilinear',
+ *            align_corners=False).  partials: 2 * nblocks doubles of device scratch, nblocks = the sum over the levels of
+ *            ceil(B h w / rfn_flowloss_block_pixels()) (checked).  loss_out: 1 + nlevels floats {the weighted total, each
+ *            level's masked mean, 0 where the level has no valid pixel}; counts: nlevels doubles, the valid pixels.
+ *   rfn_flowloss_bwd_f32  writes every non-null grad_flow / grad_logvar: grad_out[0] * weight / count times the pixel's
+ *            derivative, 0 at masked pixels and on a level without a valid pixel.  counts: what the forward wrote.
+ * Errors (nothing is launched): a null pointer, an empty shape, more than 8 levels, unknown loss type or channel count.
+ *
+ * rfn_multi_adam_f32 / rfn_multi_adam_amp_f32: torch.optim.Adam (weight decay as an L2 term of the gradient: g += wd p)
+ * with the tables, arguments and rules of rfn_multi_adamw_f32 / rfn_multi_adamw_amp_f32.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_flowloss_block_pixels(void);
+int rfn_flowloss_fwd_f32(const float* gt_flow, int B, int H, int W, const long* levels, const double* weights, int nlevels,
+                         int loss_type, float delta, double* partials, int nblocks, float* loss_out, double* counts,
+                         rfn_stream_t stream);
+int rfn_flowloss_bwd_f32(const float* gt_flow, int B, int H, int W, const long* levels, const double* weights, int nlevels,
+                         int loss_type, float delta, const double* counts, const float* grad_out, rfn_stream_t stream);
+int rfn_multi_adam_f32(const void* table, int nchunks, const float* group_args, int ngroups, rfn_stream_t stream);
+int rfn_multi_adam_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
+                           const float* step, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

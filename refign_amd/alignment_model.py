@@ -29,6 +29,12 @@ class AlignmentModel(nn.Module):
         self.selfsupervised_loss, self.unsupervised_loss = selfsupervised_loss, unsupervised_loss
         self.apply_constant_flow_weights = apply_constant_flow_weights
         self.logged = {}
+        # Lightning's default, and what the reference relies on: training_step returns the loss, the trainer does backward,
+        # optimizer step and scheduler step (Trainer.step); global_step counts the optimizer steps taken
+        self.automatic_optimization = True
+        self.global_step = 0
+        self._optimizer = None
+        self._scheduler = None
         from .metrics import build_collections
         self.valid_metrics, self.test_metrics = build_collections(metrics, config.instantiate_class)
         if pretrained is not None:
@@ -37,6 +43,12 @@ class AlignmentModel(nn.Module):
 
     def log(self, name, value, **kwargs):
         self.logged[name] = value.detach() if torch.is_tensor(value) else value
+
+    def optimizers(self):
+        return self._optimizer
+
+    def lr_schedulers(self):
+        return self._scheduler
 
     @torch.no_grad()
     def forward(self, images_i, images_j):
@@ -125,6 +137,18 @@ class AlignmentModel(nn.Module):
             return torch.clamp(loss_un / loss_ss.clamp(min=1e-8) * ratio, max=100).item(), 1.0
         return 1.0, torch.clamp(loss_ss / loss_un.clamp(min=1e-8) / ratio, max=100).item()
 
+    @staticmethod
+    @torch.no_grad()
+    def device_weights(loss_ss, loss_un, weight_ss=1.0, weight_un=1.0):
+        """weights_selfsupervised_and_unsupervised (apply_constant_weights=False) as device arithmetic on the two detached
+        losses: the same two fp32 values, as tensors, without reading either loss back."""
+        ratio = weight_ss / weight_un
+        un_larger = loss_un > loss_ss
+        up_ss = torch.clamp(loss_un / loss_ss.clamp(min=1e-8) * ratio, max=100)
+        up_un = torch.clamp(loss_ss / loss_un.clamp(min=1e-8) / ratio, max=100)
+        one = torch.ones_like(up_ss)
+        return torch.where(un_larger, up_ss, one), torch.where(un_larger, one, up_un)
+
     def _pyramids(self, images, b, n):
         """Frozen VGG-16 features of n stacked image sets at the input resolution (levels -3, -2) and at 256x256 (levels
         -2, -1), split back per set (alignment_model.py:88-104)."""
@@ -143,12 +167,18 @@ class AlignmentModel(nn.Module):
         (pyr_ref, pyr_trg, pyr_prime), (pyr_ref_256, pyr_trg_256, pyr_prime_256) = \
             self._pyramids(torch.cat([images_ref, images_trg, images_prime]), b, 3)
         with torch.no_grad():
-            # i = the image `prime` was made from, j = the other one of the pair, sample by sample
-            idx = [int(v) for v in batch['prime_trg_idx']]
+            # i = the image `prime` was made from, j = the other one of the pair, sample by sample: one select per level.
+            # prime_trg_idx: a host list (sent through pinned memory) or a device tensor; neither is read back
+            idx = batch['prime_trg_idx']
+            if not torch.is_tensor(idx):
+                idx = torch.tensor([int(v) for v in idx], dtype=torch.int64)
+                if images_trg.is_cuda:
+                    idx = idx.pin_memory()
+            from_trg = (idx.to(images_trg.device, non_blocking=True) != 0).view(b, 1, 1, 1)
 
             def pick(pair, which):
-                return [torch.stack([pair[(k if which == 0 else 1 - k)][lvl][s] for s, k in enumerate(idx)])
-                        for lvl in range(len(pair[0]))]
+                first, second = pair if which == 0 else pair[::-1]
+                return [torch.where(from_trg, t, r) for r, t in zip(first, second)]
             pyr_i, pyr_j = pick((pyr_ref, pyr_trg), 0), pick((pyr_ref, pyr_trg), 1)
             pyr_i_256, pyr_j_256 = pick((pyr_ref_256, pyr_trg_256), 0), pick((pyr_ref_256, pyr_trg_256), 1)
         head = self.alignment_head
@@ -161,8 +191,7 @@ class AlignmentModel(nn.Module):
         # with the flag False the ratio of the two weights is 0, i.e. the W-bipath loss always gets the weight cap (100)
         # when it is the smaller one and the warp-supervision loss gets weight 0 when it is the smaller one -- kept,
         # a trained reference checkpoint saw exactly this objective
-        weight_ss, weight_us = self.weights_selfsupervised_and_unsupervised(ss_loss, us_loss,
-                                                                            self.apply_constant_flow_weights)
+        weight_ss, weight_us = self.device_weights(ss_loss.detach(), us_loss.detach(), self.apply_constant_flow_weights)
         loss = weight_ss * ss_loss + weight_us * us_loss
         self.log("train_matching_loss", loss, batch_size=b)
         self.log("train_ss_loss", ss_loss)

@@ -433,6 +433,19 @@ struct AdamGroups {
   float lr[8], beta1[8], beta2[8], eps[8], wd[8], bc1[8], bc2_sqrt[8], omb1[8], omb2[8];   // omb = 1 - beta, rounded from double
 };
 
+// L2 = false: AdamW as above.  L2 = true: torch.optim.Adam, whose weight decay is an L2 term of the gradient (g += wd p) and
+// nothing else differs.
+template <bool L2>
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr, float wd, float b2, float omb1,
+                                            float omb2, float step_size, float bc2s, float eps) {
+  if (L2) g += wd * p;
+  else p -= lr * wd * p;
+  m = m + omb1 * (g - m);
+  v = b2 * v + omb2 * g * g;
+  p -= step_size * m / (sqrtf(v) / bc2s + eps);
+}
+
+template <bool L2>
 __global__ __launch_bounds__(256) void multi_adamw_kernel(const AdamChunk* __restrict__ table, AdamGroups gr) {
   const AdamChunk c = table[blockIdx.x];
   const int gi = (int)((unsigned long)c.n >> 56);
@@ -440,10 +453,7 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(const AdamChunk* __res
   const float lr = gr.lr[gi], b2 = gr.beta2[gi], eps = gr.eps[gi], wd = gr.wd[gi];
   const float step_size = lr / gr.bc1[gi], bc2s = gr.bc2_sqrt[gi], omb1 = gr.omb1[gi], omb2 = gr.omb2[gi];
   auto upd = [&](float& p, float g, float& m, float& v) {
-    p -= lr * wd * p;
-    m = m + omb1 * (g - m);
-    v = b2 * v + omb2 * g * g;
-    p -= step_size * m / (sqrtf(v) / bc2s + eps);
+    adam_update<L2>(p, g, m, v, lr, wd, b2, omb1, omb2, step_size, bc2s, eps);
   };
   const bool aligned = ((((size_t)c.p | (size_t)c.g | (size_t)c.m | (size_t)c.v) & 15) == 0);
   long i = (long)threadIdx.x * 4;
@@ -500,6 +510,7 @@ struct AdamAmpGroups {
   double beta1d[8], beta2d[8];                            // the bias corrections are taken in double, as torch's host code does
 };
 
+template <bool L2>
 __global__ __launch_bounds__(256) void multi_adamw_amp_kernel(const AdamChunk* __restrict__ table, AdamAmpGroups gr,
                                                               const float* __restrict__ found_inf, const float* __restrict__ step) {
   if (*found_inf != 0.f) return;                          // skipped step: parameters and both moments stay as they are
@@ -511,10 +522,7 @@ __global__ __launch_bounds__(256) void multi_adamw_amp_kernel(const AdamChunk* _
   const float lr = gr.lr[gi], b2 = gr.beta2[gi], eps = gr.eps[gi], wd = gr.wd[gi];
   const float step_size = lr / bc1, omb1 = gr.omb1[gi], omb2 = gr.omb2[gi];
   auto upd = [&](float& p, float g, float& m, float& v) {
-    p -= lr * wd * p;
-    m = m + omb1 * (g - m);
-    v = b2 * v + omb2 * g * g;
-    p -= step_size * m / (sqrtf(v) / bc2s + eps);
+    adam_update<L2>(p, g, m, v, lr, wd, b2, omb1, omb2, step_size, bc2s, eps);
   };
   const bool aligned = ((((size_t)c.p | (size_t)c.g | (size_t)c.m | (size_t)c.v) & 15) == 0);
   long i = (long)threadIdx.x * 4;
@@ -557,6 +565,37 @@ __global__ void amp_update_scale_kernel(float* scale, int* tracker, const float*
 
 }  // namespace rfn
 
+// the launch code of the four Adam entry points (L2: see adam_update)
+template <bool L2>
+static int launch_multi_adam(const char* what, const void* table, int nchunks, const float* group_args, int ngroups,
+                             rfn_stream_t stream) {
+  RFN_REQUIRE(table && nchunks > 0 && group_args && ngroups > 0 && ngroups <= 8, "%s: bad arguments", what);
+  rfn::AdamGroups gr{};
+  for (int g = 0; g < ngroups; ++g) {                   // host array, 9 floats per group
+    const float* a = group_args + 9 * g;
+    gr.lr[g] = a[0]; gr.beta1[g] = a[1]; gr.beta2[g] = a[2]; gr.eps[g] = a[3]; gr.wd[g] = a[4]; gr.bc1[g] = a[5];
+    gr.bc2_sqrt[g] = a[6]; gr.omb1[g] = a[7]; gr.omb2[g] = a[8];
+  }
+  hipLaunchKernelGGL(rfn::multi_adamw_kernel<L2>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
+                     (const rfn::AdamChunk*)table, gr);
+  return rfn::check_launch(what);
+}
+
+template <bool L2>
+static int launch_multi_adam_amp(const char* what, const void* table, int nchunks, const double* group_args, int ngroups,
+                                 const float* found_inf, const float* step, rfn_stream_t stream) {
+  RFN_REQUIRE(table && nchunks > 0 && group_args && ngroups > 0 && ngroups <= 8 && found_inf && step, "%s: bad arguments", what);
+  rfn::AdamAmpGroups gr{};
+  for (int g = 0; g < ngroups; ++g) {
+    const double* a = group_args + 7 * g;
+    gr.lr[g] = (float)a[0]; gr.beta1d[g] = a[1]; gr.beta2d[g] = a[2]; gr.beta2[g] = (float)a[2]; gr.eps[g] = (float)a[3];
+    gr.wd[g] = (float)a[4]; gr.omb1[g] = (float)a[5]; gr.omb2[g] = (float)a[6];
+  }
+  hipLaunchKernelGGL(rfn::multi_adamw_amp_kernel<L2>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
+                     (const rfn::AdamChunk*)table, gr, found_inf, step);
+  return rfn::check_launch(what);
+}
+
 extern "C" {
 
 int rfn_amp_unscale_f32(float* grads, long n, const float* scale, float* found_inf, rfn_stream_t stream) {
@@ -571,17 +610,12 @@ int rfn_amp_unscale_f32(float* grads, long n, const float* scale, float* found_i
 // device step count (steps taken so far), advanced by rfn_amp_update_scale
 int rfn_multi_adamw_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
                             const float* step, rfn_stream_t stream) {
-  RFN_REQUIRE(table && nchunks > 0 && group_args && ngroups > 0 && ngroups <= 8 && found_inf && step,
-              "rfn_multi_adamw_amp_f32: bad arguments");
-  rfn::AdamAmpGroups gr{};
-  for (int g = 0; g < ngroups; ++g) {
-    const double* a = group_args + 7 * g;
-    gr.lr[g] = (float)a[0]; gr.beta1d[g] = a[1]; gr.beta2d[g] = a[2]; gr.beta2[g] = (float)a[2]; gr.eps[g] = (float)a[3];
-    gr.wd[g] = (float)a[4]; gr.omb1[g] = (float)a[5]; gr.omb2[g] = (float)a[6];
-  }
-  hipLaunchKernelGGL(rfn::multi_adamw_amp_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
-                     (const rfn::AdamChunk*)table, gr, found_inf, step);
-  return rfn::check_launch("multi_adamw_amp_kernel");
+  return launch_multi_adam_amp<false>("rfn_multi_adamw_amp_f32", table, nchunks, group_args, ngroups, found_inf, step, stream);
+}
+
+int rfn_multi_adam_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
+                           const float* step, rfn_stream_t stream) {
+  return launch_multi_adam_amp<true>("rfn_multi_adam_amp_f32", table, nchunks, group_args, ngroups, found_inf, step, stream);
 }
 
 int rfn_amp_update_scale(float* scale, int* growth_tracker, const float* found_inf, float* step, float growth_factor,
@@ -607,16 +641,11 @@ int rfn_multi_transpose_cast_f32_f16(const void* table, int ntiles, rfn_stream_t
 }
 
 int rfn_multi_adamw_f32(const void* table, int nchunks, const float* group_args, int ngroups, rfn_stream_t stream) {
-  RFN_REQUIRE(table && nchunks > 0 && group_args && ngroups > 0 && ngroups <= 8, "rfn_multi_adamw_f32: bad arguments");
-  rfn::AdamGroups gr{};
-  for (int g = 0; g < ngroups; ++g) {                   // host array, 9 floats per group
-    const float* a = group_args + 9 * g;
-    gr.lr[g] = a[0]; gr.beta1[g] = a[1]; gr.beta2[g] = a[2]; gr.eps[g] = a[3]; gr.wd[g] = a[4]; gr.bc1[g] = a[5];
-    gr.bc2_sqrt[g] = a[6]; gr.omb1[g] = a[7]; gr.omb2[g] = a[8];
-  }
-  hipLaunchKernelGGL(rfn::multi_adamw_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream,
-                     (const rfn::AdamChunk*)table, gr);
-  return rfn::check_launch("multi_adamw_kernel");
+  return launch_multi_adam<false>("rfn_multi_adamw_f32", table, nchunks, group_args, ngroups, stream);
+}
+
+int rfn_multi_adam_f32(const void* table, int nchunks, const float* group_args, int ngroups, rfn_stream_t stream) {
+  return launch_multi_adam<true>("rfn_multi_adam_f32", table, nchunks, group_args, ngroups, stream);
 }
 
 int rfn_multi_ema_f32(const void* table, int nchunks, float momentum, rfn_stream_t stream) {

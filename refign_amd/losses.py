@@ -12,13 +12,20 @@ constructor keywords and forward signatures as the reference, so `configs/megade
 Plain tensor programs on top of `matching.warp` (hand-written forward and backward kernels, csrc/warp.hip); everything
 here is differentiable.  Level flows are in full-resolution pixel units at every level (heads/uawarpc.py:95-280)."""
 import math
+import os
 from collections.abc import Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import flowloss
 from .matching import get_gt_correspondence_mask, warp
+
+# MultiScaleFlowLoss.forward on fp32 CUDA inputs with downsample_gt_flow=True: all levels in one autograd node on
+# csrc/flowloss.hip (refign_amd/flowloss.py), without the per-level host decisions of the formulation below.  False (or
+# RFN_FLOW_LOSS_FUSED=0 in the environment, read once): the torch formulation everywhere.
+FUSED_LEVEL_LOSS = os.environ.get("RFN_FLOW_LOSS_FUSED", "1") != "0"
 
 
 class HuberLoss(nn.Module):
@@ -97,6 +104,14 @@ class MultiScaleFlowLoss(nn.Module):
             flow_output = [flow_output]
         weights = self.level_weights if self.level_weights else [1] * len(flow_output)
         assert len(weights) == len(flow_output)
+        if FUSED_LEVEL_LOSS and self.downsample_gt_flow:
+            levels = [level if isinstance(level, tuple) else (level, None) for level in flow_output]
+            masks = [mask[i] if mask is not None and isinstance(mask, Sequence) else mask for i in range(len(levels))]
+            if flowloss.eligible(levels, gt_flow, masks):
+                assert self.loss_type in ('L2Loss', 'HuberLoss') or all(u is None for _, u in levels)
+                masks = [None if m is None else _level_mask(m, f.shape[-2:]) for m, (f, _) in zip(masks, levels)]
+                return flowloss.multi_level_flow_loss(levels, gt_flow, masks, weights, self.loss_type,
+                                                      getattr(self.loss_function, 'delta', 1.0))
         total = 0
         for i, (level, weight) in enumerate(zip(flow_output, weights)):    # coarsest level first
             level_mask = mask[i] if mask is not None and isinstance(mask, Sequence) else mask
@@ -138,6 +153,12 @@ class WBipathLoss(nn.Module):
             estimated_flow_target_prime_to_source = [estimated_flow_target_prime_to_source]
         if not isinstance(estimated_flow_source_to_target, Sequence):
             estimated_flow_source_to_target = [estimated_flow_source_to_target]
+        # the fused path (the objective runs on csrc/flowloss.hip and the warping flow carries no gradient): no host decision
+        # -- warp() without its zero-flow check, the level scale as two scalar multiplications instead of a host tensor
+        f0 = estimated_flow_target_prime_to_source[0]
+        f0 = f0[0] if isinstance(f0, tuple) else f0
+        fused = FUSED_LEVEL_LOSS and self.detach_flow_for_warping and self.objective.downsample_gt_flow and f0.is_cuda \
+            and f0.dtype == torch.float32
         composed, masks, cyclic = [], [], []
         for first, second in zip(estimated_flow_target_prime_to_source, estimated_flow_source_to_target):
             probabilistic = isinstance(first, tuple)
@@ -145,11 +166,15 @@ class WBipathLoss(nn.Module):
             h, w = f_flow.shape[-2:]
             # the flow the second estimate is sampled with: the first one in THIS level's pixels
             wf = f_flow.detach().clone() if self.detach_flow_for_warping else f_flow.clone()
-            wf = wf * wf.new_tensor([float(w) / float(W), float(h) / float(H)]).view(1, 2, 1, 1)
-            s_warped = warp(s_flow, wf)
+            if fused:
+                wf[:, 0] *= float(w) / float(W)
+                wf[:, 1] *= float(h) / float(H)
+            else:
+                wf = wf * wf.new_tensor([float(w) / float(W), float(h) / float(H)]).view(1, 2, 1, 1)
+            s_warped = warp(s_flow, wf, check_zero=not fused)
             level = f_flow + s_warped
             if probabilistic:
-                level = (level, torch.cat((f_unc, warp(s_unc, wf)), 1))
+                level = (level, torch.cat((f_unc, warp(s_unc, wf, check_zero=not fused)), 1))
             composed.append(level)
             mask = get_gt_correspondence_mask(wf.detach())
             if mask_used is not None:

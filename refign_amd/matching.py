@@ -8,12 +8,37 @@ from . import _lib
 from ._tensor import DTYPE_CODE16, ptr, require_device_tensor, same_device
 
 
-def warp(x, flo, padding_mode='zeros', return_mask=False):
+# Set by no_zero_flow_check(): callers that pass check_zero=None (the head's LocalFeatureCorrelationLayer) skip the check.
+_CHECK_ZERO_FLOW = True
+
+
+def no_zero_flow_check():
+    """Context manager: inside it warp(..., check_zero=None) behaves as check_zero=False.  Trainer enters it around the
+    matcher's training step, whose three head passes would otherwise ask the host nine times per step."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def ctx():
+        global _CHECK_ZERO_FLOW
+        saved, _CHECK_ZERO_FLOW = _CHECK_ZERO_FLOW, False
+        try:
+            yield
+        finally:
+            _CHECK_ZERO_FLOW = saved
+    return ctx()
+
+
+def warp(x, flo, padding_mode='zeros', return_mask=False, check_zero=True):
     """warp an image/tensor back according to the flow (matching_utils.py:11-49).
 
     x: [B,C,H,W], flo: [B,2,H,W] in pixels.  Bilinear, align_corners=True, zero padding; the mask is True where the
     normalised sampling position is strictly inside (-1,1)^2.  Like the reference, an identically-zero flow returns
     `x` itself (and an all-True mask) -- that costs one host sync, as it does there (matching_utils.py:19).
+    check_zero=False skips that host decision (None: skips it inside no_zero_flow_check()).  The values are the same -- a
+    zero flow samples every pixel at itself -- and so is every gradient but one: for an identically-zero flow the
+    reference returns `x`, so the flow gets NO gradient there, while the sampling kernel's backward gives it the
+    bilinear derivative.  The mask of a zero flow differs too: the kernel's mask is False on the border rows and columns
+    (positions not strictly inside), the shortcut's is all True.
     """
     if padding_mode != 'zeros':
         raise RuntimeError("warp: only padding_mode='zeros' is used by the reference hot path")
@@ -23,7 +48,9 @@ def warp(x, flo, padding_mode='zeros', return_mask=False):
     B, C, H, W = x.shape
     if tuple(flo.shape) != (B, 2, H, W):
         raise RuntimeError("warp: flo must be (B,2,H,W)")
-    if bool(torch.all(flo == 0)):
+    if check_zero is None:
+        check_zero = _CHECK_ZERO_FLOW
+    if check_zero and bool(torch.all(flo == 0)):
         if return_mask:
             return x, torch.ones((B, H, W), dtype=torch.bool, device=dev)
         return x

@@ -26,7 +26,7 @@ class LocalFeatureCorrelationLayer(nn.Module):
                                            None if flow is None else flow.float().contiguous())
         if flow is not None:
             from .matching import warp
-            feature_source = warp(feature_source, flow)
+            feature_source = warp(feature_source, flow, check_zero=None)     # (checked, except inside the Trainer's matcher step)
         b = feature_target.shape[0]
         corr = self.local_correlation(feature_target, feature_source, patch_size=self.patch_size)
         corr = corr.view(b, self.patch_size * self.patch_size, feature_target.shape[2], feature_target.shape[3])

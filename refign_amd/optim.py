@@ -18,6 +18,10 @@ from .params import refresh
 
 
 class MultiTensorAdamW:
+    TORCH_CLASS = torch.optim.AdamW                        # exactly this class, no subclass
+    ENTRY, ENTRY_AMP = "rfn_multi_adamw_f32", "rfn_multi_adamw_amp_f32"
+    DECOUPLED = True                                       # p -= lr wd p
+
     def __init__(self, optimizer):
         self.opt = optimizer
         self._table = None
@@ -52,11 +56,13 @@ class MultiTensorAdamW:
             self._synced_t = self._t
 
     def _plain(self):
-        if type(self.opt) is not torch.optim.AdamW or len(self.opt.param_groups) > 8:
+        if type(self.opt) is not self.TORCH_CLASS or len(self.opt.param_groups) > 8:
             return False
         for g in self.opt.param_groups:
             if g.get("amsgrad") or g.get("maximize") or g.get("differentiable") or torch.is_tensor(g["lr"]):
                 return False
+            if bool(g.get("decoupled_weight_decay", self.DECOUPLED)) != self.DECOUPLED:
+                return False                                # (torch.optim.Adam(decoupled_weight_decay=True) is AdamW's arithmetic)
             for p in g["params"]:
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad is not None
                         and p.grad.dtype == torch.float32 and p.grad.is_contiguous()):
@@ -96,10 +102,18 @@ class MultiTensorAdamW:
             return False
         self._t = self._synced_t = int(ts.pop())
         dev = self.opt.param_groups[0]["params"][0].device
-        self._table = (torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows), dev)
+        self._table = (self._upload(torch.from_numpy(np.asarray(rows, dtype=np.int64)), dev), len(rows), dev)
         self._steps = steps
         self._sig = self._signature()
         return True
+
+    @staticmethod
+    def _upload(host, dev):
+        return host.to(dev)
+
+    def _updated(self):
+        """The parameters changed under torch's feet (no version counter moved): cached copies follow."""
+        refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
 
     def step(self):
         sig = self._signature()
@@ -118,16 +132,16 @@ class MultiTensorAdamW:
         host = np.asarray(args, dtype=np.float32)
         table, n, dev = self._table
         with torch.no_grad():
-            _lib.call("rfn_multi_adamw_f32", dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups))
+            _lib.call(self.ENTRY, dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups))
         self.launches += 1
         self.opt._opt_called = True                        # what Optimizer.step's wrapper tells the LR scheduler
-        refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
+        self._updated()
 
     def step_amp(self, found_inf):
         """The step under loss scaling (amp.LossScaler): the same update, skipped on the device when `found_inf` is set.
         The step count lives on the device (`device_step`, advanced by LossScaler.update when the step was taken); the
         torch state's `step` tensors are brought up to date from it when somebody looks.  Returns False where it declines
-        (first step, configuration outside plain AdamW): the caller then steps torch's optimizer itself."""
+        (first step, configuration outside the plain optimizer): the caller then steps torch's optimizer itself."""
         sig = self._signature()
         if self._table is None or sig != self._sig:
             self._sync_steps()
@@ -143,13 +157,34 @@ class MultiTensorAdamW:
         host = np.asarray(args, dtype=np.float64)
         table, n, dev = self._table
         with torch.no_grad():
-            _lib.call("rfn_multi_adamw_amp_f32", dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
+            _lib.call(self.ENTRY_AMP, dev, ptr(table), n, host.ctypes.data, len(self.opt.param_groups),
                       ptr(found_inf), ptr(self._dev_step))
         self.launches += 1
         self.opt._opt_called = True
-        refresh((p for g in self.opt.param_groups for p in g["params"]), plan_key=("optimizer", id(self.opt)))
+        self._updated()
         return True
 
     @property
     def device_step(self):
         return self._dev_step
+
+
+class MultiTensorAdam(MultiTensorAdamW):
+    """torch.optim.Adam -- weight decay as an L2 term of the gradient, `g += wd p`, the optimizer of the matcher's configs --
+    as one launch (rfn_multi_adam_f32 / rfn_multi_adam_amp_f32: the same kernels, templated on the decay form).  Same chunk
+    table, same hand-over rules, same step() / step_amp(found_inf) / device_step as MultiTensorAdamW."""
+    TORCH_CLASS = torch.optim.Adam
+    ENTRY, ENTRY_AMP = "rfn_multi_adam_f32", "rfn_multi_adam_amp_f32"
+    DECOUPLED = False                                      # g += wd p
+
+    @staticmethod
+    def _upload(host, dev):
+        """Through pinned memory, without waiting: the table is built in the SECOND step of a run (torch takes the first),
+        and the matcher's step asks the host nothing after its first call."""
+        return host.pin_memory().to(dev, non_blocking=True)
+
+    def _updated(self):
+        """... and the fp32 matcher's convolutions (split32) keep packed weights by version counter: dropped, re-made on use."""
+        super()._updated()
+        from . import split32
+        split32.drop_frozen(self._params)

@@ -219,6 +219,15 @@ def _w3_frozen(w, order):
     return packed
 
 
+def drop_frozen(params):
+    """Forget what _w3_frozen / _wb_frozen keep on `params`.  For whoever updates parameters in place WITHOUT moving their
+    version counters (optim.MultiTensorAdam): _Conv2dFn.forward runs with grad mode off, so a trainable convolution's packed
+    weight is kept too, and only the version counter would tell that it is stale."""
+    for p in params:
+        p.__dict__.pop("_rfn_w3", None)
+        p.__dict__.pop("_rfn_bpad", None)
+
+
 def _wb_frozen(weight, bias):
     """(packed split weight, bias padded to the packed row count) of a gradient-free convolution, kept like _w3_frozen."""
     wp = _w3_frozen(weight, "hlh")

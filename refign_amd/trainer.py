@@ -381,7 +381,8 @@ class StallGuard:
 
 class Trainer:
     """`step(batch)` = one reference training_step including EMA, three backward passes, the single gradient all-reduce and
-    the optimiser/scheduler step; `fit` / `validate` / `test` / `predict` = the loops of the Lightning entry points the
+    the optimiser/scheduler step (a model with automatic_optimization, the matcher: training_step, one backward pass, optimizer
+    and scheduler step -- _automatic_step); `fit` / `validate` / `test` / `predict` = the loops of the Lightning entry points the
     reference is driven through (run.py fit | validate | test | predict); `save_checkpoint` / `load_checkpoint`."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
@@ -402,7 +403,8 @@ class Trainer:
         name, `grad_norm/<optimizer group>` and `grad_norm/total` of the gradient the optimizer consumed (after the
         all-reduce and, under precision=16, the unscale; a skipped fp16 step shows its infinite or NaN norm),
         `grad_norm/nonfinite_chunks`, under precision=16 `amp/scale`, `amp/found_inf` (both this step's) and
-        `amp/skipped_steps` (before this step), and with `log_lr` `lr-AdamW/<optimizer group>`, the rate this step used.
+        `amp/skipped_steps` (before this step), and with `log_lr` `lr-<optimizer class>/<optimizer group>` (`lr-AdamW/...`,
+        `lr-Adam/...`), the rate this step used.
         The row is put together on the device between the unscale and AdamW (refign_amd/steplog.py) and reaches the host
         through a pinned mirror: the step does not wait for it.  step() hands finished rows to the logger and to
         `log_history`, a list of (step, {name: float}); validate() / test() log their results at the current global_step;
@@ -497,11 +499,18 @@ class Trainer:
             model.optimizer_init = {**model.optimizer_init,
                                     "init_args": {**model.optimizer_init["init_args"], "fused": True}}
         (opt,), (sch,) = model.configure_optimizers()
+        if isinstance(sch, dict):                            # Lightning's {'scheduler': ..., 'interval': 'step'} (AlignmentModel)
+            if sch.get("interval", "step") != "step":
+                raise ValueError(f"Trainer: lr scheduler interval {sch.get('interval')!r}: this trainer counts steps only")
+            sch = sch["scheduler"]
         self.optimizer, self.scheduler = opt, sch
         self.fast_step = None
-        if fused_optimizer and type(opt) is torch.optim.AdamW and next(model.parameters()).is_cuda:
-            from .optim import MultiTensorAdamW
-            self.fast_step = MultiTensorAdamW(opt)            # one launch per step; torch's step() where it declines
+        if fused_optimizer and next(model.parameters()).is_cuda:
+            from .optim import MultiTensorAdam, MultiTensorAdamW
+            if type(opt) is torch.optim.AdamW:
+                self.fast_step = MultiTensorAdamW(opt)        # one launch per step; torch's step() where it declines
+            elif type(opt) is torch.optim.Adam:
+                self.fast_step = MultiTensorAdam(opt)         # (the matcher's configs; the optimizer's arguments stay as given)
         groups = model.grad_ready_groups() if hasattr(model, "grad_ready_groups") else None
         self.grads = FlatGradBuffer([p for g in opt.param_groups for p in g["params"]], groups, bucket_mb)
         if getattr(self, "_grad_comm", None) is not None:
@@ -559,7 +568,7 @@ class Trainer:
         step's mixed pass runs (uda.prefetch_imnet_features)."""
         if self._steplog is not None:
             self._hand_over(self._steplog.poll())            # rows whose events have completed: no waiting
-        if next_batch is not None:
+        if next_batch is not None and not getattr(self.model, "automatic_optimization", False):
             batch = dict(batch, image_src_next=next_batch["image_src"], semantic_src_next=next_batch.get("semantic_src"),
                          image_trg_next=next_batch.get("image_trg"), image_ref_next=next_batch.get("image_ref"))
         # Python's cyclic collector fires on allocation counts; a step allocates ~10^5 autograd / tensor wrapper objects
@@ -579,8 +588,12 @@ class Trainer:
             # (the step's main-stream work on a stream of its own / of another priority: neutral, profiles/r05_main_priority_ab.txt --
             # HIP offers two priority levels here, (0, -1), and the teacher's stream already has the high one)
             from . import determinism
-            with determinism.torch_deterministic(self.deterministic), self._autocast():
-                self.model.training_step(batch, batch_idx)
+            if getattr(self.model, "automatic_optimization", False):
+                with determinism.torch_deterministic(self.deterministic):
+                    self._automatic_step(batch, batch_idx)
+            else:
+                with determinism.torch_deterministic(self.deterministic), self._autocast():
+                    self.model.training_step(batch, batch_idx)
             if self.guard is not None:
                 self.guard.note(f"step {self._steps_done} queued")
         finally:
@@ -591,6 +604,22 @@ class Trainer:
             seg._DEVICE_CROPS.clear()
         return {k: (float(v) if torch.is_tensor(v) else v) for k, v in self.model.logged.items()} \
             if os.environ.get("RFN_LOG_LOSSES") else None
+
+    def _automatic_step(self, batch, batch_idx):
+        """A model with automatic_optimization (AlignmentModel): training_step returns the loss and this trainer does what
+        Lightning does around it -- zero the gradients, backward (scaled under precision=16), optimizer step through the
+        proxy (all-reduce, unscale, step-log row, Adam, scaler update), scheduler step, global_step + 1.  The gradient
+        stays readable in `self.grads` until the next step.  Nothing here asks the host about device data after the first
+        call of a shape: the head's warps skip their zero-flow check (matching.no_zero_flow_check)."""
+        from . import matching
+        model = self.model
+        self.grads.zero()
+        with self._autocast(), matching.no_zero_flow_check():
+            loss = model.training_step(batch, batch_idx)
+        self._backward(loss, last=True)
+        model._optimizer.step()
+        self.scheduler.step()
+        model.global_step += 1
 
     # -- the record of the run -----------------------------------------------------------------------------------------
     def _record_row(self):
@@ -625,7 +654,7 @@ class Trainer:
             scalars.update({"amp/scale": self.scaler._scale, "amp/found_inf": self.scaler.found_inf,
                             "amp/skipped_steps": self.scaler._skipped})
         if self.log_lr:
-            host.update({f"lr-AdamW/{n}": float(g["lr"]) for n, g in zip(gnames, groups)})
+            host.update({f"lr-{type(self.optimizer).__name__}/{n}": float(g["lr"]) for n, g in zip(gnames, groups)})
         if self._norm_plan is None:
             self._norm_plan = steplog.GradNormPlan.for_buffer(self.grads, groups)
         log = self._steplog

@@ -3,7 +3,9 @@
 configs/megadepth/uawarpc_stage2.yaml: batch 6, 520x520 crops, VGG-16 + UAWarpCHead, Huber multi-scale flow loss +
 W-bipath loss with visibility mask, Adam(lr 5e-5, wd 4e-4).  One step = AlignmentModel.training_step + backward +
 optimizer step on synthetic images / flows.  Prints ms/step and image-triplets/s.
-    python tools/matcher_bench.py [--steps 10] [--b 6] [--size 520]"""
+    python tools/matcher_bench.py [--steps 10] [--b 6] [--size 520]
+--trainer: the same step through refign_amd.trainer.Trainer (Trainer.step: flat gradient buffer, device-side loss scaler,
+one-launch Adam, no host synchronisation) instead of the hand-driven loop with torch.amp.GradScaler."""
 import argparse
 import os
 import sys
@@ -40,6 +42,8 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp16"],
                     help="fp16 = the reference's recipe for matcher training (README.md:289-294: --trainer.precision 16): "
                          "fp16 autocast + loss scaling, correlation / warp / losses in fp32")
+    ap.add_argument("--trainer", action="store_true",
+                    help="drive the step through Trainer(model, precision=...).step instead of by hand")
     ap.add_argument("--census", action="store_true", help="torch.profiler on one step: ATen operators with device time, by input shape")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -62,8 +66,16 @@ def main():
 
     amp = args.precision == "fp16"
     scaler = torch.amp.GradScaler("cuda", enabled=amp)
+    trainer = None
+    if args.trainer:
+        from refign_amd.trainer import Trainer
+        trainer = Trainer(model, precision=16 if amp else None)
+        batch["prime_trg_idx"] = torch.tensor(batch["prime_trg_idx"], device=dev)
 
     def step():
+        if trainer is not None:
+            trainer.step(batch, 0)
+            return model.logged["train_matching_loss"]
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
             loss = model.training_step(batch, 0)
@@ -99,10 +111,15 @@ def main():
     host = (time.perf_counter() - t0) / args.steps        # what the host needs to enqueue a step (== dt: host-bound)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    print(f"matcher training step b={b} {S}x{S} {args.precision}: {dt * 1e3:.1f} ms/step (host enqueue {host * 1e3:.1f} ms), {b / dt:.2f} image-triplets/s, "
+    how = " through Trainer.step" if trainer is not None else ""
+    print(f"matcher training step{how} b={b} {S}x{S} {args.precision}: {dt * 1e3:.1f} ms/step (host enqueue {host * 1e3:.1f} ms), {b / dt:.2f} image-triplets/s, "
           f"loss {float(loss):.3f}, max mem {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
     from refign_amd import mfma as _mfma
     print("library_fallbacks:", _mfma.library_summary())
+    if trainer is not None:
+        print(f"one-launch Adam steps: {trainer.fast_step.launches}" +
+              (f", skipped fp16 steps: {trainer.scaler.skipped_steps()}" if trainer.scaler is not None else ""))
+        trainer.close()
 
 
 if __name__ == "__main__":
