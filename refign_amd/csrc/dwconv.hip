@@ -20,6 +20,9 @@
 //                 (per-thread register partials over its pixel quads -> LDS tree over the block's pixel lanes ->
 //                  one workspace row per block row -> fixed-order reduction kernel: deterministic, no atomics)
 //   backward      both of them from ONE pass over gy (dwconv3x3_bwd_kernel): gy, x and dx cross HBM once each
+// Kernels: dwconv3x3_fwd_kernel (forward; taps flipped = backward-data alone; + GELU; + the BatchNorm statistics of what it
+// stores), dwconv3x3_roll_kernel (the gradient-free forms: statistics only, convolution + BatchNorm + ReLU),
+// dwconv3x3_bwd_kernel (both gradients, or the parameter gradients alone) and dwconv3x3_bwd_weight_reduce_kernel.
 #include <hip/hip_bf16.h>
 
 #include <type_traits>
@@ -29,6 +32,10 @@
 
 namespace rfn {
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// Vector I/O of one lane: N channels as a packed Raw; unpack2 -> adjacent-channel fp32 pairs, store <- N fp32 values.
 template <typename T>
 struct VecIO;
 
@@ -37,83 +44,65 @@ struct VecIO<float> {
   static constexpr int N = 4;
   typedef float4 Raw;
   __device__ static Raw load_raw(const float* p) { return *reinterpret_cast<const float4*>(p); }
-  __device__ static void unpack(const Raw& t, float (&v)[4]) { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-  typedef float Pair __attribute__((ext_vector_type(2)));
-  __device__ static void unpack2(const Raw& t, Pair (&v)[2]) { v[0] = Pair{t.x, t.y}; v[1] = Pair{t.z, t.w}; }
-  __device__ static void load(const float* p, float (&v)[4]) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
+  __device__ static void unpack2(const Raw& t, f32x2 (&v)[2]) { v[0] = f32x2{t.x, t.y}; v[1] = f32x2{t.z, t.w}; }
   __device__ static void store(float* p, const float (&v)[4]) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   }
   __device__ static float rnd(float v) { return v; }                  // the value a store of v reads back as
 };
 
+// 16-bit activations: bf16, and fp16 (the reference's `precision: 16` recipe) in the same layout with IEEE half conversions.
+// The two conversions: pair_f32 (one packed word -> two adjacent channels) and pack16 (back).
+template <typename T>
+__device__ __forceinline__ f32x2 pair_f32(unsigned w);
 template <>
-struct VecIO<__hip_bfloat16> {
-  static constexpr int N = 8;
-  typedef uint4 Raw;
-  __device__ static Raw load_raw(const __hip_bfloat16* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static void unpack(const Raw& t, float (&v)[8]) {
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  typedef float Pair __attribute__((ext_vector_type(2)));
-  __device__ static void unpack2(const Raw& t, Pair (&v)[4]) {      // adjacent channels land in adjacent registers
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = Pair{__uint_as_float(w[i] << 16), __uint_as_float(w[i] & 0xffff0000u)};
-  }
-  __device__ static void load(const __hip_bfloat16* p, float (&v)[8]) {
-    const uint4 t = *reinterpret_cast<const uint4*>(p);
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = __uint_as_float(w[i] << 16);
-      v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-    }
-  }
-  __device__ static unsigned pack(float lo, float hi) { return bf16x2_bits(lo, hi); }   // common.h: one v_cvt_pk_bf16_f32
-  __device__ static void store(__hip_bfloat16* p, const float (&v)[8]) {
-    uint4 t;
-    t.x = pack(v[0], v[1]); t.y = pack(v[2], v[3]); t.z = pack(v[4], v[5]); t.w = pack(v[6], v[7]);
-    *reinterpret_cast<uint4*>(p) = t;
-  }
-  __device__ static float rnd(float v) { return __uint_as_float(bf16_bits(v) << 16); }
-};
+__device__ __forceinline__ f32x2 pair_f32<__hip_bfloat16>(unsigned w) {
+  return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+}
+template <>
+__device__ __forceinline__ f32x2 pair_f32<_Float16>(unsigned w) { return f32x2{f16_lo(w), f16_hi(w)}; }
 
-// fp16 (the reference's `precision: 16` recipe): the bf16 layout, IEEE half conversions
+template <typename T>
+__device__ __forceinline__ unsigned pack16(float lo, float hi);
 template <>
-struct VecIO<_Float16> {
-  static constexpr int N = 8;
-  typedef uint4 Raw;
-  __device__ static Raw load_raw(const _Float16* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static void unpack(const Raw& t, float (&v)[8]) {
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[2 * i] = f16_lo(w[i]);
-      v[2 * i + 1] = f16_hi(w[i]);
+__device__ __forceinline__ unsigned pack16<__hip_bfloat16>(float lo, float hi) { return bf16x2_bits(lo, hi); }   // common.h: one v_cvt_pk_bf16_f32
+template <>
+__device__ __forceinline__ unsigned pack16<_Float16>(float lo, float hi) { return f16x2_bits(lo, hi); }
+
+// NCH = 8 channels per lane (16-byte vectors: dwconv3x3_fwd_kernel) or 4 (8-byte vectors: dwconv3x3_roll_kernel, dwconv3x3_bwd_kernel)
+template <typename T, int NCH>
+struct Vec16 {
+  static constexpr int N = NCH, NW = NCH / 2;
+  typedef std::conditional_t<NCH == 8, uint4, uint2> Raw;
+  __device__ static Raw load_raw(const T* p) { return *reinterpret_cast<const Raw*>(p); }
+  __device__ static void unpack2(const Raw& t, f32x2 (&v)[NW]) {      // adjacent channels land in adjacent registers
+    v[0] = pair_f32<T>(t.x);
+    v[1] = pair_f32<T>(t.y);
+    if constexpr (NCH == 8) {
+      v[2] = pair_f32<T>(t.z);
+      v[3] = pair_f32<T>(t.w);
     }
   }
-  typedef float Pair __attribute__((ext_vector_type(2)));
-  __device__ static void unpack2(const Raw& t, Pair (&v)[4]) {
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = Pair{f16_lo(w[i]), f16_hi(w[i])};
+  __device__ static unsigned pack(float lo, float hi) { return pack16<T>(lo, hi); }
+  __device__ static void store(T* p, const float (&v)[NCH]) {
+    Raw t;
+    t.x = pack(v[0], v[1]);
+    t.y = pack(v[2], v[3]);
+    if constexpr (NCH == 8) {
+      t.z = pack(v[4], v[5]);
+      t.w = pack(v[6], v[7]);
+    }
+    *reinterpret_cast<Raw*>(p) = t;
   }
-  __device__ static void load(const _Float16* p, float (&v)[8]) { unpack(load_raw(p), v); }
-  __device__ static unsigned pack(float lo, float hi) { return f16x2_bits(lo, hi); }
-  __device__ static void store(_Float16* p, const float (&v)[8]) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack(v[0], v[1]), pack(v[2], v[3]), pack(v[4], v[5]), pack(v[6], v[7]));
+  __device__ static float rnd(float v) {
+    if constexpr (std::is_same<T, _Float16>::value) return (float)(_Float16)v;
+    else return __uint_as_float(bf16_bits(v) << 16);
   }
-  __device__ static float rnd(float v) { return (float)(_Float16)v; }
 };
+template <>
+struct VecIO<__hip_bfloat16> : Vec16<__hip_bfloat16, 8> {};
+template <>
+struct VecIO<_Float16> : Vec16<_Float16, 8> {};
 
 // K5: e4m3 activations, 8 channels per lane (8-byte vectors); dequantisation / quantisation scales are kernel arguments
 template <>
@@ -121,8 +110,7 @@ struct VecIO<f8e4m3> {
   static constexpr int N = 8;
   typedef uint2 Raw;
   __device__ static Raw load_raw(const f8e4m3* p) { return *reinterpret_cast<const uint2*>(p); }
-  typedef float Pair __attribute__((ext_vector_type(2)));
-  __device__ static void unpack2(const Raw& t, Pair (&v)[4]) {
+  __device__ static void unpack2(const Raw& t, f32x2 (&v)[4]) {
     v[0] = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.x, false);
     v[1] = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.x, true);
     v[2] = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.y, false);
@@ -138,7 +126,7 @@ constexpr int kPX = 4;   // pixels along W per thread
 // A "quad" is 4 pixels of one image row spaced by the dilation: w0, w0+d, w0+2d, w0+3d.  Their 3x3 dilated taps fall on
 // the 6 columns w0-d .. w0+4d, so 6 loads per row feed 4 outputs for ANY dilation (for d = 1 it is 4 adjacent pixels).
 // Per row there are d phases x ceil(ceil(W/d)/4) quads.
-__device__ __forceinline__ int quads_per_row(int W, int dil) { return dil * (((W + dil - 1) / dil + kPX - 1) / kPX); }
+__host__ __device__ __forceinline__ int quads_per_row(int W, int dil) { return dil * (((W + dil - 1) / dil + kPX - 1) / kPX); }
 
 __device__ __forceinline__ void quad_coords(long quad, int WQ, int H, int dil, int& b, int& h, int& w0) {
   const int wq = (int)(quad % WQ);
@@ -150,8 +138,98 @@ __device__ __forceinline__ void quad_coords(long quad, int WQ, int H, int dil, i
 
 // Thread layout (all three kernels): blockDim = 256 = cvb channel-vectors (fastest, so a wave reads contiguous
 // channels) x pl pixel lanes.  A thread keeps ONE channel vector for its whole life -- its 9 x V weights are loaded
-// once -- and walks "quads" (4 consecutive pixels of one image row) with stride gridDim.y * pl.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// once -- and walks items ("quads": 4 pixels of one image row; the rolling walk: strips of a row segment) with stride
+// block rows x pl.
+// Two launch geometries.
+//  * grid (channel blocks, block rows), rows in image order: the first-generation mapping.
+//  * SLICED (gridDim.y == 1, sliced != 0): a 1-D grid of 8 j blocks; block id runs on XCD id % 8 (the dispatcher's
+//    round-robin) and owns channel slice id % 8 (cvb = CV / 8 vectors) -- so the three uses of an input row (output
+//    rows h - d, h, h + d) are made by ONE XCD and the second and third find the row in that XCD's L2 -- provided they
+//    come soon enough: the blocks of an XCD walk the rows in lockstep (the grid is exactly the resident blocks), and
+//    for a dilated convolution in residue-class order r, r + d, r + 2 d, ... (h_slots = d ceil(H / d) slots per image),
+//    so the uses are 1 and 2 rows apart whatever the dilation.  With the first mapping a row's uses land on different
+//    XCDs / megabytes apart: each is a fabric read (measured round 3: tools/kbench.py --only dw).
+struct DwMap {
+  int pl, cvbase, cv;      // pixel lanes of the block; first channel vector of the block; the thread's channel vector
+  int first, stride, row;  // the thread's first item and item stride; block row (= row of a partial-sum workspace)
+  bool active;             // false: a lane past the last channel vector (or past cvb x pl), it only joins the block's folds
+};
+// (nthreads = blockDim.x, read by the kernel: in a kernel body the compiler folds the work-group size lookup to one load,
+// in a device function it keeps the partial-group select)
+__device__ __forceinline__ DwMap dw_map(int sliced, int cvb, int CV, unsigned nthreads) {
+  DwMap m;
+  if (sliced) {
+    m.pl = nthreads / cvb;
+    m.active = (int)threadIdx.x < cvb * m.pl;
+    m.cvbase = (blockIdx.x & 7) * cvb;
+    m.cv = m.cvbase + threadIdx.x % cvb;
+    m.row = blockIdx.x >> 3;
+    m.first = m.row * m.pl + threadIdx.x / cvb;
+    m.stride = (gridDim.x >> 3) * m.pl;
+  } else {
+    m.pl = 256 / cvb;
+    m.cvbase = blockIdx.x * cvb;
+    m.cv = m.cvbase + threadIdx.x % cvb;
+    m.active = m.cv < CV;
+    m.row = blockIdx.y;
+    m.first = m.row * m.pl + threadIdx.x / cvb;
+    m.stride = gridDim.y * m.pl;
+  }
+  return m;
+}
+
+// The thread's 9 x V tap-major weights (9, C) as adjacent-channel pairs: one contiguous fp32 vector per tap.  FLIP: wr[k] is
+// tap 8 - k (the backward-data stencil); SCALE (e4m3 activations): the input scale xs folded in.
+template <int V, bool FLIP, bool SCALE = false>
+__device__ __forceinline__ void load_taps(const float* wgt, int C, int c0, f32x2 (&wr)[9][V / 2], float xs = 1.f) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float* wp = wgt + (size_t)(FLIP ? 8 - k : k) * C + c0;
+#pragma unroll
+    for (int i = 0; i < V; i += 4) {
+      const float4 t4 = *reinterpret_cast<const float4*>(wp + i);
+      wr[k][i / 2] = f32x2{t4.x, t4.y};
+      wr[k][i / 2 + 1] = f32x2{t4.z, t4.w};
+      if constexpr (SCALE) {
+        wr[k][i / 2] *= xs;
+        wr[k][i / 2 + 1] *= xs;
+      }
+    }
+  }
+}
+
+// The statistics epilogue of dwconv3x3_fwd_kernel<STATS> and dwconv3x3_roll_kernel<STATS = 2>: per-thread fp32 sums (st0: sum,
+// st1: sum of squares, V channels as floats or as pairs) -> LDS -> thread (which, channel vector of the block, element) folds
+// the pixel lanes in lane order -> one fp64 atomic per channel and block, or (spart: the deterministic form) one row of 2 C
+// partial sums per block row, plain stores, added in row order afterwards.  One thread of the launch writes the row count.
+template <int N>
+__device__ __forceinline__ float stat_elem(const float (&s)[N], int i) { return s[i]; }
+template <int N>
+__device__ __forceinline__ float stat_elem(const f32x2 (&s)[N], int i) { return (i & 1) ? s[i / 2].y : s[i / 2].x; }
+
+template <int V, typename St>
+__device__ __forceinline__ void fold_stats(const DwMap& m, int cvb, int CV, int B, int H, int W, int C, const St& st0,
+                                           const St& st1, double* sums, double* spart) {
+  __shared__ float sred[2][256][V + 1];
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    sred[0][threadIdx.x][i] = m.active ? stat_elem(st0, i) : 0.f;
+    sred[1][threadIdx.x][i] = m.active ? stat_elem(st1, i) : 0.f;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < 2 * cvb * V; idx += blockDim.x) {
+    const int which = idx / (cvb * V), rem = idx % (cvb * V), v = rem / V, e = rem % V;
+    if (m.cvbase + v >= CV) continue;
+    float sum = 0.f;
+    for (int r = 0; r < m.pl; ++r) sum += sred[which][r * cvb + v][e];
+    if (spart != nullptr) spart[((size_t)m.row * 2 + which) * C + (m.cvbase + v) * V + e] = (double)sum;
+    else atomicAdd(sums + which * C + (m.cvbase + v) * V + e, (double)sum);
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+    if (spart != nullptr) sums[2 * C] = (double)B * H * W;
+    else atomicAdd(sums + 2 * C, (double)B * H * W);
+  }
+}
 
 // zero a packed load when its tap is outside the image (true zero padding; 4 selects instead of one multiply per FMA)
 __device__ __forceinline__ float4 mask_raw(const float4& t, bool ok) {
@@ -183,7 +261,7 @@ struct BnEpi {
   int relu;
 };
 
-template <typename T, bool FLIP, bool ACT = false, int STATS = 0>
+template <typename T, bool FLIP, bool ACT = false, bool STATS = false>
 __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wgt,
                                                             const float* __restrict__ bias, T* __restrict__ y, int B,
                                                             int H, int W, int C, int dil, int cvb,
@@ -191,67 +269,29 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
                                                             float oq = 1.f, int sliced = 0,
                                                             double* __restrict__ sums = nullptr,
                                                             double* __restrict__ spart = nullptr) {
-  static_assert(STATS == 0 || STATS == 1, "the gradient-free forms (statistics only, BatchNorm) are dwconv3x3_roll_kernel's");
   // xs / oq (e4m3 activations only): stored input bytes mean xs * value -- folded into the weights; outputs are stored as
   // value * oq
   constexpr bool F8 = std::is_same<T, f8e4m3>::value;
   constexpr int V = VecIO<T>::N, V2 = V / 2;
   const int CV = C / V, WQ = quads_per_row(W, dil);
-  // Two launch geometries.
-  //  * grid (channel blocks, quad chunks), rows in image order: the first-generation mapping.
-  //  * SLICED (gridDim.y == 1, sliced != 0): a 1-D grid of 8 j blocks; block id runs on XCD id % 8 (the dispatcher's
-  //    round-robin) and owns channel slice id % 8 (cvb = CV / 8 vectors) -- so the three uses of an input row (output
-  //    rows h - d, h, h + d) are made by ONE XCD and the second and third find the row in that XCD's L2 -- provided they
-  //    come soon enough: the blocks of an XCD walk the rows in lockstep (the grid is exactly the resident blocks), and
-  //    for a dilated convolution in residue-class order r, r + d, r + 2 d, ... (h_slots = d ceil(H / d) slots per image),
-  //    so the uses are 1 and 2 rows apart whatever the dilation.  With the first mapping a row's uses land on different
-  //    XCDs / megabytes apart: each is a fabric read (measured round 3: tools/kbench.py --only dw).
-  int pl, cv, qfirst, qstride;
-  bool active;
-  if (sliced) {
-    pl = blockDim.x / cvb;
-    active = (int)threadIdx.x < cvb * pl;
-    cv = (blockIdx.x & 7) * cvb + threadIdx.x % cvb;
-    qfirst = (blockIdx.x >> 3) * pl + threadIdx.x / cvb;
-    qstride = (gridDim.x >> 3) * pl;
-  } else {
-    pl = 256 / cvb;
-    cv = blockIdx.x * cvb + threadIdx.x % cvb;
-    active = cv < CV;
-    qfirst = blockIdx.y * pl + threadIdx.x / cvb;
-    qstride = gridDim.y * pl;
-  }
-  if (STATS == 0 && !active) return;
-  if (!active) cv = 0;                                   // (STATS: idle threads stay for the block reduction)
+  const DwMap m = dw_map(sliced, cvb, CV, blockDim.x);
+  if (!STATS && !m.active) return;                       // (STATS: idle threads stay for the block reduction)
   const int Hd = (H + dil - 1) / dil, h_slots = sliced ? dil * Hd : H;
-  const int c0 = cv * V;
+  const int c0 = (m.active ? m.cv : 0) * V;
   float st0[STATS ? V : 1], st1[STATS ? V : 1];
-  if constexpr (STATS != 0) {
+  if constexpr (STATS) {
 #pragma unroll
     for (int i = 0; i < V; ++i) st0[i] = st1[i] = 0.f;
   }
   // weights, bias and accumulators live as adjacent-channel PAIRS: every multiply-add below is one v_pk_fma_f32
-  f32x2 wr[9][V2];   // tap-major weights (9, C): one contiguous fp32 vector per tap
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const float* wp = wgt + (size_t)(FLIP ? 8 - k : k) * C + c0;
-#pragma unroll
-    for (int i = 0; i < V; i += 4) {
-      const float4 t4 = *reinterpret_cast<const float4*>(wp + i);
-      wr[k][i / 2] = f32x2{t4.x, t4.y};
-      wr[k][i / 2 + 1] = f32x2{t4.z, t4.w};
-      if constexpr (F8) {
-        wr[k][i / 2] *= xs;
-        wr[k][i / 2 + 1] *= xs;
-      }
-    }
-  }
+  f32x2 wr[9][V2];
+  load_taps<V, FLIP, F8>(wgt, C, c0, wr, xs);
   f32x2 bs[V2];
 #pragma unroll
   for (int i = 0; i < V2; ++i)
     bs[i] = (bias != nullptr) ? f32x2{bias[c0 + 2 * i], bias[c0 + 2 * i + 1]} : f32x2{0.0f, 0.0f};
-  const long nquads = active ? (long)B * h_slots * WQ : 0;
-  for (long quad = qfirst; quad < nquads; quad += qstride) {
+  const long nquads = m.active ? (long)B * h_slots * WQ : 0;
+  for (long quad = m.first; quad < nquads; quad += m.stride) {
     int b, h, w0;
     quad_coords(quad, WQ, h_slots, dil, b, h, w0);
     if (sliced && dil > 1) {                            // slot -> row of residue class slot / Hd
@@ -301,7 +341,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
 #pragma unroll
         for (int i = 0; i < V2; ++i) { o[2 * i] = acc[p][i].x; o[2 * i + 1] = acc[p][i].y; }
         if (!ACT || y != nullptr) VecIO<T>::store(y + obase + (size_t)(w0 + p * dil) * C, o);
-        if constexpr (STATS != 0) {
+        if constexpr (STATS) {
 #pragma unroll
           for (int i = 0; i < V; ++i) {
             const float r = VecIO<T>::rnd(o[i]);
@@ -320,30 +360,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
         }
       }
   }
-  if constexpr (STATS != 0) {
-    __shared__ float sred[2][256][V + 1];
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      sred[0][threadIdx.x][i] = active ? st0[i] : 0.f;
-      sred[1][threadIdx.x][i] = active ? st1[i] : 0.f;
-    }
-    __syncthreads();
-    // thread (which, channel vector of the block, element): fold the pixel lanes, one fp64 atomic per channel and block
-    const int cvbase = sliced ? (blockIdx.x & 7) * cvb : blockIdx.x * cvb;
-    for (int idx = threadIdx.x; idx < 2 * cvb * V; idx += blockDim.x) {
-      const int which = idx / (cvb * V), rem = idx % (cvb * V), v = rem / V, e = rem % V;
-      if (cvbase + v >= CV) continue;
-      float sum = 0.f;
-      for (int r = 0; r < pl; ++r) sum += sred[which][r * cvb + v][e];
-      // spart (deterministic form): one row of 2 C partial sums per block row, plain stores; added in row order afterwards
-      if (spart != nullptr) spart[((size_t)(sliced ? blockIdx.x >> 3 : blockIdx.y) * 2 + which) * C + (cvbase + v) * V + e] = (double)sum;
-      else atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-      if (spart != nullptr) sums[2 * C] = (double)B * H * W;
-      else atomicAdd(sums + 2 * C, (double)B * H * W);
-    }
-  }
+  if constexpr (STATS) fold_stats<V>(m, cvb, CV, B, H, W, C, st0, st1, sums, spart);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -363,8 +380,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
 //    values are bit-equal.
 //  * a segment starts from nothing: its first two rows (k0 - 1, k0) are loaded again, no sum is carried over an image, a
 //    residue class or a segment.
-// Items (image, residue class, segment, strip), strip fastest, are dealt to the pixel lanes of either launch geometry of
-// dwconv3x3_fwd_kernel (grid of channel blocks x lane blocks, or XCD-sliced); `seg` rows per segment: roll_geom().
+// Items (image, residue class, segment, strip), strip fastest, are dealt to the pixel lanes of either launch geometry
+// (dw_map: grid of channel blocks x lane blocks, or XCD-sliced); `seg` rows per segment: roll_geom().
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ uint4 g_zero_line_dw[1];          // zero-initialised: what a tap left or right of the image reads
 
@@ -373,17 +390,6 @@ constexpr int kRV = 4;                       // channels per thread of the rolli
 // more temporaries, spills with 2
 template <typename T>
 constexpr int kRollDepth = std::is_same<T, _Float16>::value ? 1 : 2;
-
-template <typename T>
-__device__ __forceinline__ f32x2 pair_f32(unsigned w);
-template <>
-__device__ __forceinline__ f32x2 pair_f32<__hip_bfloat16>(unsigned w) {
-  return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-}
-template <>
-__device__ __forceinline__ f32x2 pair_f32<_Float16>(unsigned w) { return f32x2{f16_lo(w), f16_hi(w)}; }
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 template <typename T, int STATS, bool BNE, int DEPTH>
 __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restrict__ x, const float* __restrict__ wgt,
@@ -395,24 +401,9 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
   static_assert(DEPTH == 1 || DEPTH == 2, "the walk is written for one or two rows in flight");
   constexpr int V = kRV, V2 = V / 2, NC = kPX + 2;
   const int CV = C / V, WQ = quads_per_row(W, dil);
-  int pl, cv, qfirst, qstride;
-  bool active;
-  if (sliced) {                                          // (the two geometries: dwconv3x3_fwd_kernel)
-    pl = blockDim.x / cvb;
-    active = (int)threadIdx.x < cvb * pl;
-    cv = (blockIdx.x & 7) * cvb + threadIdx.x % cvb;
-    qfirst = (blockIdx.x >> 3) * pl + threadIdx.x / cvb;
-    qstride = (gridDim.x >> 3) * pl;
-  } else {
-    pl = 256 / cvb;
-    cv = blockIdx.x * cvb + threadIdx.x % cvb;
-    active = cv < CV;
-    qfirst = blockIdx.y * pl + threadIdx.x / cvb;
-    qstride = gridDim.y * pl;
-  }
-  if (STATS == 0 && !active) return;
-  if (!active) cv = 0;                                   // (STATS: idle threads stay for the block reduction)
-  const int c0 = cv * V;
+  const DwMap m = dw_map(sliced, cvb, CV, blockDim.x);
+  if (STATS == 0 && !m.active) return;                   // (STATS: idle threads stay for the block reduction)
+  const int c0 = (m.active ? m.cv : 0) * V;
   f32x2 st0[STATS ? V2 : 1], st1[STATS ? V2 : 1];
   if constexpr (STATS != 0) {
 #pragma unroll
@@ -421,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
   f32x2 bsc[BNE ? V2 : 1], bsh[BNE ? V2 : 1];            // y = relu(conv * bsc + bsh)
   if constexpr (BNE) {
     const double cnt = sums[2 * C], inv = 1.0 / cnt;
-    const bool first = sliced ? (blockIdx.x >> 3) == 0 : blockIdx.y == 0;
+    const bool first = m.row == 0 && m.active && threadIdx.x / cvb == 0;   // the first pixel lane of the first block row
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       const int c = c0 + i;
@@ -431,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
       const float sc = rsqrtf(var + bn.eps) * g, sh = be - mean * sc;
       if (i & 1) bsc[i / 2].y = sc, bsh[i / 2].y = sh;
       else bsc[i / 2].x = sc, bsh[i / 2].x = sh;
-      if (first && active && threadIdx.x / cvb == 0 && bn.running_mean != nullptr) {
+      if (first && bn.running_mean != nullptr) {
         const float n = (float)cnt;
         bn.running_mean[c] = (1.f - bn.momentum) * bn.running_mean[c] + bn.momentum * mean;
         bn.running_var[c] = (1.f - bn.momentum) * bn.running_var[c] + bn.momentum * var * (n / fmaxf(n - 1.f, 1.f));
@@ -439,21 +430,16 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
     }
   }
   f32x2 wr[9][V2], bs[V2];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const float4 t4 = *reinterpret_cast<const float4*>(wgt + (size_t)k * C + c0);
-    wr[k][0] = f32x2{t4.x, t4.y};
-    wr[k][1] = f32x2{t4.z, t4.w};
-  }
+  load_taps<V, false>(wgt, C, c0, wr);
 #pragma unroll
   for (int i = 0; i < V2; ++i)
     bs[i] = (bias != nullptr) ? f32x2{bias[c0 + 2 * i], bias[c0 + 2 * i + 1]} : f32x2{0.0f, 0.0f};
 
   const int Hd = (H + dil - 1) / dil, nseg = (Hd + seg - 1) / seg;
-  const int nitems = active ? B * dil * nseg * WQ : 0;   // (fits: checked at launch)
+  const int nitems = m.active ? B * dil * nseg * WQ : 0; // (fits: checked at launch)
   const unsigned rs = (unsigned)((size_t)dil * W * C * sizeof(T));   // one row of a residue class down, in bytes
   const size_t dc = (size_t)dil * C;                                  // one output of the strip to the right
-  for (int it = qfirst; it < nitems; it += qstride) {
+  for (int it = m.first; it < nitems; it += m.stride) {
     const int wq = it % WQ;
     int t = it / WQ;
     const int sg = t % nseg;
@@ -578,46 +564,14 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
       }
     }
   }
-  if constexpr (STATS != 0) {
-    __shared__ float sred[2][256][V + 1];
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      const f32x2 a0 = st0[i / 2], a1 = st1[i / 2];
-      sred[0][threadIdx.x][i] = active ? ((i & 1) ? a0.y : a0.x) : 0.f;
-      sred[1][threadIdx.x][i] = active ? ((i & 1) ? a1.y : a1.x) : 0.f;
-    }
-    __syncthreads();
-    // thread (which, channel vector of the block, element): fold the pixel lanes, one fp64 atomic per channel and block
-    const int cvbase = sliced ? (blockIdx.x & 7) * cvb : blockIdx.x * cvb;
-    for (int idx = threadIdx.x; idx < 2 * cvb * V; idx += blockDim.x) {
-      const int which = idx / (cvb * V), rem = idx % (cvb * V), v = rem / V, e = rem % V;
-      if (cvbase + v >= CV) continue;
-      float sum = 0.f;
-      for (int q = 0; q < pl; ++q) sum += sred[which][q * cvb + v][e];
-      // spart (deterministic form): one row of 2 C partial sums per block row, plain stores; added in row order afterwards
-      if (spart != nullptr) spart[((size_t)(sliced ? blockIdx.x >> 3 : blockIdx.y) * 2 + which) * C + (cvbase + v) * V + e] = (double)sum;
-      else atomicAdd(sums + which * C + (cvbase + v) * V + e, (double)sum);
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-      if (spart != nullptr) sums[2 * C] = (double)B * H * W;
-      else atomicAdd(sums + 2 * C, (double)B * H * W);
-    }
-  }
+  if constexpr (STATS != 0) fold_stats<V>(m, cvb, CV, B, H, W, C, st0, st1, sums, spart);
 }
 
 // Vector I/O of dwconv3x3_bwd_kernel: 4 channels per lane for every activation type (fp32: VecIO; 16-bit: 8-byte vectors, as
 // dwconv3x3_roll_kernel) -- with 8 channels the 72 weights, 72 weight partials, 32 accumulators and 32 values of x do not fit in
 // the 256 registers of 2 waves per SIMD (the 8-channel build spilled 356 bytes per lane).
 template <typename T>
-struct BwdIO {
-  static constexpr int N = kRV;
-  typedef uint2 Raw;
-  __device__ static Raw load_raw(const T* p) { return *reinterpret_cast<const uint2*>(p); }
-  __device__ static void unpack2(const Raw& t, f32x2 (&v)[2]) { v[0] = pair_f32<T>(t.x); v[1] = pair_f32<T>(t.y); }
-  __device__ static void store(T* p, const float (&v)[4]) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(VecIO<T>::pack(v[0], v[1]), VecIO<T>::pack(v[2], v[3]));
-  }
-};
+struct BwdIO : Vec16<T, kRV> {};
 template <>
 struct BwdIO<float> : VecIO<float> {};
 
@@ -628,7 +582,7 @@ struct BwdIO<float> : VecIO<float> {};
 // gx[q] += w[8 - k] v and gw[8 - k] += x[q] v; the centre row of the window is gb's.  gy, x and gx cross HBM once each (the
 // two-kernel form read gy twice and an 18-vector window of x).  Out-of-image window values are zero (select on the packed
 // data) and x is zero for the pixels of a quad past the row end, whose gx is not stored.
-//  * either launch geometry of dwconv3x3_fwd_kernel; idle threads stay for the block's fold.
+//  * either launch geometry (dw_map); idle threads stay for the block's fold.
 //  * weight / bias partials: registers over the thread's quads -> LDS fold over the block's pixel lanes -> ONE workspace row
 //    per block row, ws[row][k][C] (k = 0..8 taps, 9 = bias) -> dwconv3x3_bwd_weight_reduce_kernel in fixed order.  No atomics:
 //    bit-reproducible.
@@ -644,38 +598,11 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_bwd_kernel(const T* __restri
   typedef BwdIO<T> IO;
   constexpr int V = IO::N, V2 = V / 2;
   const int CV = C / V, WQ = quads_per_row(W, dil);
-  int pl, qfirst, qstride, cvbase, wsrow;
-  bool active;
-  if (sliced) {                                          // (the two geometries: dwconv3x3_fwd_kernel)
-    pl = blockDim.x / cvb;
-    active = (int)threadIdx.x < cvb * pl;
-    cvbase = (blockIdx.x & 7) * cvb;
-    wsrow = blockIdx.x >> 3;
-    qfirst = wsrow * pl + threadIdx.x / cvb;
-    qstride = (gridDim.x >> 3) * pl;
-  } else {
-    pl = 256 / cvb;
-    cvbase = blockIdx.x * cvb;
-    active = cvbase + (int)(threadIdx.x % cvb) < CV;
-    wsrow = blockIdx.y;
-    qfirst = blockIdx.y * pl + threadIdx.x / cvb;
-    qstride = gridDim.y * pl;
-  }
-  const int c0 = active ? (cvbase + threadIdx.x % cvb) * V : 0;
+  const DwMap m = dw_map(sliced, cvb, CV, blockDim.x);                 // (idle threads stay for the block's fold)
+  const int c0 = (m.active ? m.cv : 0) * V;
   const int Hd = (H + dil - 1) / dil, h_slots = sliced ? dil * Hd : H;
   f32x2 wr[GX ? 9 : 1][V2];         // wr[k] = w[8 - k]: the weight of window position k in gx
-  if constexpr (GX) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float* wp = wgt + (size_t)(8 - k) * C + c0;
-#pragma unroll
-      for (int i = 0; i < V; i += 4) {
-        const float4 t4 = *reinterpret_cast<const float4*>(wp + i);
-        wr[k][i / 2] = f32x2{t4.x, t4.y};
-        wr[k][i / 2 + 1] = f32x2{t4.z, t4.w};
-      }
-    }
-  }
+  if constexpr (GX) load_taps<V, true>(wgt, C, c0, wr);
   f32x2 aw[9][V2], ab[V2];          // aw[k]: the partial of gw[8 - k]; adjacent-channel pairs: every multiply-add is one v_pk_fma_f32
 #pragma unroll
   for (int i = 0; i < V2; ++i) {
@@ -683,8 +610,8 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_bwd_kernel(const T* __restri
 #pragma unroll
     for (int k = 0; k < 9; ++k) aw[k][i] = f32x2{0.0f, 0.0f};
   }
-  const long nquads = active ? (long)B * h_slots * WQ : 0;
-  for (long quad = qfirst; quad < nquads; quad += qstride) {
+  const long nquads = m.active ? (long)B * h_slots * WQ : 0;
+  for (long quad = m.first; quad < nquads; quad += m.stride) {
     int b, h, w0;
     quad_coords(quad, WQ, h_slots, dil, b, h, w0);
     if (sliced && dil > 1) h = h / Hd + (h % Hd) * dil;  // slot -> row of residue class slot / Hd
@@ -753,7 +680,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_bwd_kernel(const T* __restri
   // fold the block's pixel lanes: two passes of 5 of the 10 rows (9 taps + bias) through LDS, every thread sums
   // (10 one-row passes with two barriers each and only the first pixel lane summing were a 3-5 us tail)
   __shared__ float red[5][256][V];
-  float* wrow = ws + (size_t)wsrow * 10 * C;
+  float* wrow = ws + (size_t)m.row * 10 * C;
   for (int pass = 0; pass < 2; ++pass) {
     __syncthreads();
 #pragma unroll
@@ -768,10 +695,10 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_bwd_kernel(const T* __restri
     __syncthreads();
     for (int o = threadIdx.x; o < 5 * cvb * V; o += 256) {
       const int kk = o / (cvb * V), rem = o - kk * cvb * V, cvj = rem / V, i = rem - cvj * V;
-      if (cvbase + cvj >= CV) continue;
+      if (m.cvbase + cvj >= CV) continue;
       float sum = 0.0f;
-      for (int p = 0; p < pl; ++p) sum += red[kk][p * cvb + cvj][i];
-      wrow[(size_t)(pass * 5 + kk) * C + (cvbase + cvj) * V + i] = sum;
+      for (int p = 0; p < m.pl; ++p) sum += red[kk][p * cvb + cvj][i];
+      wrow[(size_t)(pass * 5 + kk) * C + (m.cvbase + cvj) * V + i] = sum;
     }
   }
 }
@@ -810,11 +737,14 @@ __global__ __launch_bounds__(256) void dwconv3x3_bwd_weight_reduce_kernel(const 
 }
 
 static inline int pick_cvb(int CV) { return CV >= 64 ? 64 : (CV >= 32 ? 32 : (CV >= 16 ? 16 : 8)); }
+// block rows for `nitems` items on `pl` pixel lanes per block, `cap` at the most
+static inline int block_rows(long nitems, int pl, long cap) {
+  return (int)std::max<long>(1, std::min<long>(cdiv(nitems, pl), cap));
+}
 
-// the SLICED geometry of dwconv3x3_fwd_kernel: one channel slice of CV / 8 vectors per XCD (at least 8 vectors = 128-byte
-// runs per pixel), and exactly the blocks that are resident at once -- 2 per CU (216 VGPRs: 2 waves per SIMD), 64 per XCD
-// (or twice that: no difference measured) -- so that an XCD's blocks advance through the rows together.
-// RFN_DWCONV_SLICED=0: first-generation grid everywhere.
+// the SLICED geometry (dw_map): one channel slice of CV / 8 vectors per XCD (at least 8 vectors = 128-byte runs per pixel),
+// and exactly the blocks that are resident at once -- 2 per CU (216 VGPRs: 2 waves per SIMD), 64 per XCD (or twice that: no
+// difference measured) -- so that an XCD's blocks advance through the rows together.
 struct SlicedGeom {
   bool on;
   int cvb, grid;
@@ -824,33 +754,70 @@ struct SlicedGeom {
 // 14.4 us; Mix-FFN + GELU 40 x 34 x 60 x 1280: 160 -> 149 us.  NOT for slices under 16 vectors (512 channels: 128-byte runs
 // per pixel, 214 -> 240 us).
 static inline SlicedGeom sliced_geom(int CV, long nslots) {
-  static const int enabled = 1;
   // workgroups per XCD: 128 was the optimum of the isolated launches; inside the step (three streams share the CUs) 64 is
   // 0.6 ms per step better (152.8 vs 153.4, twice), 32 is 7 ms worse
-  static const int per_xcd = 64;
-  if (!enabled || CV % 8 != 0 || CV / 8 < 16 || CV / 8 > 64) return SlicedGeom{false, 0, 0};
-  const int cvb = CV / 8, pl = 256 / cvb;
-  const int j = (int)std::max<long>(1, std::min<long>(cdiv(nslots, pl), per_xcd));
-  return SlicedGeom{true, cvb, 8 * j};
+  constexpr int per_xcd = 64;
+  if (CV % 8 != 0 || CV / 8 < 16 || CV / 8 > 64) return SlicedGeom{false, 0, 0};
+  const int cvb = CV / 8;
+  return SlicedGeom{true, cvb, 8 * block_rows(nslots, 256 / cvb, per_xcd)};
 }
 constexpr int kMaxStripes = 128;
+
+// items of one pass over a map in quads: the residue-class slots B d ceil(H / d) WQ of the sliced geometry, else B H WQ
+static inline long quad_slots(bool sliced, int B, int H, int W, int dil) {
+  return (long)B * (sliced ? dil * cdiv(H, dil) : H) * quads_per_row(W, dil);
+}
+
+// Launch geometry of dwconv3x3_fwd_kernel for CV channel vectors (16 bytes each): sliced where sliced_geom() has it, else
+// channel blocks x block rows, at most 4096 workgroups.
+struct FwdGeom {
+  dim3 grid;
+  int cvb, sliced, rows;           // rows: block rows = rows of the deterministic statistics' partial image
+};
+static FwdGeom fwd_geom(int CV, int B, int H, int W, int dil) {
+  if (SlicedGeom sg = sliced_geom(CV, quad_slots(true, B, H, W, dil)); sg.on) return FwdGeom{dim3(sg.grid), sg.cvb, 1, sg.grid / 8};
+  const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb);
+  const int gy = block_rows(quad_slots(false, B, H, W, dil), 256 / cvb, (256L * 16) / gx);
+  return FwdGeom{dim3(gx, gy), cvb, 0, gy};
+}
+
+// a run-time bool as a template argument: fn(std::true_type{}) or fn(std::false_type{})
+template <typename Fn>
+static inline void with_bool(bool b, Fn&& fn) {
+  if (b) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
+template <typename T>
+static int launch_fwd(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int dil,
+                      int flip, hipStream_t st) {
+  const FwdGeom g = fwd_geom(C / VecIO<T>::N, B, H, W, dil);
+  with_bool(flip != 0, [&](auto f) {
+    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, decltype(f)::value>), g.grid, dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B,
+                       H, W, C, dil, g.cvb, (T*)nullptr, 1.f, 1.f, g.sliced);
+  });
+  return check_launch("dwconv3x3_fwd_kernel");
+}
 
 template <typename T>
 static int launch_fwd_gelu(const void* x, const float* w, const float* bias, void* y, void* ya, int B, int H, int W,
                            int C, hipStream_t st, float xs = 1.f, float oq = 1.f) {
-  constexpr int V = VecIO<T>::N;
-  const int CV = C / V;
-  const long nquads = (long)B * H * ((W + kPX - 1) / kPX);
-  if (SlicedGeom sg = sliced_geom(CV, nquads); sg.on) {
-    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, true>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias,
-                       (T*)y, B, H, W, C, 1, sg.cvb, (T*)ya, xs, oq, 1);
-    return check_launch("dwconv3x3_fwd_kernel<gelu, sliced>");
-  }
-  const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-  const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
-  hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, true>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
-                     (T*)y, B, H, W, C, 1, cvb, (T*)ya, xs, oq);
+  const FwdGeom g = fwd_geom(C / VecIO<T>::N, B, H, W, 1);
+  hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, true>), g.grid, dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B, H, W,
+                     C, 1, g.cvb, (T*)ya, xs, oq, g.sliced);
   return check_launch("dwconv3x3_fwd_kernel<gelu>");
+}
+
+// convolution stored + its statistics (spart: the deterministic form, one partial row per block row + the ordered column sum)
+template <typename T>
+static int launch_fwd_stats(const void* x, const float* w, const float* bias, void* y, double* sums, double* spart, int B, int H,
+                            int W, int C, int dil, hipStream_t st) {
+  const FwdGeom g = fwd_geom(C / VecIO<T>::N, B, H, W, dil);
+  hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, true>), g.grid, dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B,
+                     H, W, C, dil, g.cvb, (T*)nullptr, 1.f, 1.f, g.sliced, sums, spart);
+  if (int rc = check_launch("dwconv3x3_fwd_kernel<stats>")) return rc;
+  if (spart != nullptr) return ordered_colsum_f64(spart, sums, g.rows, 2 * C, st);
+  return RFN_OK;
 }
 
 // Launch geometry of dwconv3x3_roll_kernel (16-bit activations, 4 channels per thread): the XCD-sliced grid where
@@ -867,30 +834,22 @@ struct RollGeom {
 static RollGeom roll_geom(int B, int H, int W, int C, int dil) {
   RollGeom g{};
   const int CV = C / kRV, Hd = cdiv(H, dil);
-  const int WQ = dil * cdiv(cdiv(W, dil), kPX);
   const SlicedGeom sg = sliced_geom(C / 8, 1L << 30);
-  int pl;
-  long lanes;
-  if (sg.on) {
-    g.sliced = true, g.cvb = 2 * sg.cvb, pl = 256 / g.cvb;
-    lanes = (long)(sg.grid / 8) * pl;
-  } else {
-    g.cvb = pick_cvb(CV), g.gx = cdiv(CV, g.cvb), pl = 256 / g.cvb;
-    lanes = (256L * 16) / g.gx * pl;
-  }
-  const long per_seg = (long)B * dil * WQ;
-  const long want = std::max<long>(1, cdiv(4 * lanes, per_seg));              // segments per class for 4 items per lane
+  long cap;                                                                   // block rows at the most
+  if (sg.on) g.sliced = true, g.cvb = 2 * sg.cvb, cap = sg.grid / 8;
+  else g.cvb = pick_cvb(CV), g.gx = cdiv(CV, g.cvb), cap = (256L * 16) / g.gx;
+  const int pl = 256 / g.cvb;
+  const long per_seg = (long)B * dil * quads_per_row(W, dil);
+  const long want = std::max<long>(1, cdiv(4 * cap * pl, per_seg));           // segments per class for 4 items per lane
   g.seg = (int)std::min<long>(Hd, std::max<long>(8, cdiv(Hd, want)));
   g.nitems = per_seg * cdiv(Hd, g.seg);
-  if (sg.on) {
-    g.rows = (int)std::max<long>(1, std::min<long>(cdiv(g.nitems, pl), sg.grid / 8));
-    g.gx = 8 * g.rows, g.gy = 1;
-  } else {
-    g.rows = g.gy = (int)std::max<long>(1, std::min<long>(cdiv(g.nitems, pl), (256L * 16) / g.gx));
-  }
+  g.rows = block_rows(g.nitems, pl, cap);
+  if (sg.on) g.gx = 8 * g.rows, g.gy = 1;
+  else g.gy = g.rows;
   return g;
 }
 
+// STATS 2: statistics only; BNE: convolution + BatchNorm + activation from complete statistics
 template <typename T, int STATS, bool BNE>
 static int launch_roll(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
                        int dil, hipStream_t st, BnEpi bn, double* spart) {
@@ -907,74 +866,10 @@ static int launch_roll(const void* x, const float* w, const float* bias, void* y
   return RFN_OK;
 }
 
-// STATS 1: convolution + statistics; 2: statistics only; BNE: convolution + BatchNorm + activation from complete statistics.
-// The two gradient-free forms (2, BNE) run the rolling-window body, STATS 1 (it stores the convolution for a backward pass)
-// the first one.
-template <typename T, int STATS, bool BNE>
-static int launch_fwd_stats(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
-                            int dil, hipStream_t st, BnEpi bn = BnEpi{}, double* spart = nullptr) {
-  if constexpr (STATS == 2 || BNE) {
-    return launch_roll<T, STATS, BNE>(x, w, bias, y, sums, B, H, W, C, dil, st, bn, spart);
-  } else {
-    constexpr int V = VecIO<T>::N;
-    const int CV = C / V;
-    const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-    int rows;                                              // block rows = rows of the deterministic form's partial image
-    if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) {
-      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias,
-                         (T*)y, B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1, sums, spart);
-      if (int rc = check_launch("dwconv3x3_fwd_kernel<sliced, stats>")) return rc;
-      rows = sg.grid / 8;
-    } else {
-      const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-      const long nquads = (long)B * H * WQ;
-      const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
-      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false, false, STATS>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias,
-                         (T*)y, B, H, W, C, dil, cvb, (T*)nullptr, 1.f, 1.f, 0, sums, spart);
-      if (int rc = check_launch("dwconv3x3_fwd_kernel<stats>")) return rc;
-      rows = gy;
-    }
-    if (spart != nullptr) return ordered_colsum_f64(spart, sums, rows, 2 * C, st);
-    return RFN_OK;
-  }
-}
-
-// block rows of launch_fwd_stats for 16-bit activations: the larger of the two bodies' (one workspace size serves
+// block rows of the statistics launches for 16-bit activations: the larger of the two bodies' (one workspace size serves
 // rfn_dwconv3x3_nhwc_fwd_stats_det and rfn_dwconv3x3_nhwc_stats_det)
 static int dw_stats_rows(int B, int H, int W, int C, int dil) {
-  const int CV = C / 8;
-  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-  const int roll = roll_geom(B, H, W, C, dil).rows;
-  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) return std::max(roll, sg.grid / 8);
-  const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-  return std::max(roll, (int)std::max<long>(1, std::min<long>(cdiv((long)B * H * WQ, pl), (256L * 16) / gx)));
-}
-
-template <typename T>
-static int launch_fwd(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int dil,
-                      int flip, hipStream_t st) {
-  constexpr int V = VecIO<T>::N;
-  const int CV = C / V;
-  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-  if (SlicedGeom sg = sliced_geom(CV, (long)B * dil * ((H + dil - 1) / dil) * WQ); sg.on) {
-    if (flip)
-      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, true>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B,
-                         H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1);
-    else
-      hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false>), dim3(sg.grid), dim3(256), 0, st, (const T*)x, w, bias, (T*)y,
-                         B, H, W, C, dil, sg.cvb, (T*)nullptr, 1.f, 1.f, 1);
-    return check_launch("dwconv3x3_fwd_kernel<sliced>");
-  }
-  const int cvb = pick_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
-  const long nquads = (long)B * H * WQ;
-  const int gy = (int)std::max<long>(1, std::min<long>(cdiv(nquads, pl), (256L * 16) / gx));
-  if (flip)
-    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, true>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B,
-                       H, W, C, dil, cvb);
-  else
-    hipLaunchKernelGGL((dwconv3x3_fwd_kernel<T, false>), dim3(gx, gy), dim3(256), 0, st, (const T*)x, w, bias, (T*)y,
-                       B, H, W, C, dil, cvb);
-  return check_launch("dwconv3x3_fwd_kernel");
+  return std::max(roll_geom(B, H, W, C, dil).rows, fwd_geom(C / 8, B, H, W, dil).rows);
 }
 
 // Launch geometry of dwconv3x3_bwd_kernel (gx == nullptr: the weight / bias gradient alone) + the ordered reduction.
@@ -990,265 +885,34 @@ static int launch_bwd(const void* x, const void* gy, const float* w, void* gx, f
                       int W, int C, int dil, int flags, hipStream_t st) {
   constexpr int V = BwdIO<T>::N, V16 = 16 / (int)sizeof(T);   // channels per lane; per 16-byte vector, sliced_geom()'s unit
   const int CV = C / V;
-  const int WQ = dil * (((W + dil - 1) / dil + kPX - 1) / kPX);
-  int rows;
-  if (SlicedGeom sg = sliced_geom(C / V16, 1L << 30); sg.on) {
-    const int cvb = sg.cvb * (V16 / V), pl = 256 / cvb;
-    rows = (int)std::max<long>(1, std::min<long>(cdiv((long)B * dil * ((H + dil - 1) / dil) * WQ, pl), sg.grid / 8));
-    if (gx != nullptr)
-      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, true>), dim3(8 * rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w, (T*)gx,
-                         ws, B, H, W, C, dil, cvb, 1);
-    else
-      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, false>), dim3(8 * rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
-                         (T*)nullptr, ws, B, H, W, C, dil, cvb, 1);
+  const SlicedGeom sg = sliced_geom(C / V16, 1L << 30);
+  int cvb, rows;
+  dim3 grid;
+  if (sg.on) {
+    cvb = sg.cvb * (V16 / V);
+    rows = block_rows(quad_slots(true, B, H, W, dil), 256 / cvb, sg.grid / 8);
+    grid = dim3(8 * rows);
   } else {
-    int cvb = pick_cvb(CV);
+    cvb = pick_cvb(CV);
     while (cvb > 8 && cdiv(CV, cvb) < 4) cvb >>= 1;
-    const int gxb = cdiv(CV, cvb), pl = 256 / cvb;
-    const long nquads = (long)B * H * WQ;
-    rows = (int)std::max<long>(1, std::min<long>(std::min<long>(kMaxStripes, cdiv(nquads, pl)), std::max<long>(1, (256L * 8) / gxb)));
-    if (gx != nullptr)
-      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, true>), dim3(gxb, rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
-                         (T*)gx, ws, B, H, W, C, dil, cvb, 0);
-    else
-      hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, false>), dim3(gxb, rows), dim3(256), 0, st, (const T*)x, (const T*)gy, w,
-                         (T*)nullptr, ws, B, H, W, C, dil, cvb, 0);
+    const int gxb = cdiv(CV, cvb);
+    rows = block_rows(quad_slots(false, B, H, W, dil), 256 / cvb, std::min<long>(kMaxStripes, std::max<long>(1, (256L * 8) / gxb)));
+    grid = dim3(gxb, rows);
   }
+  with_bool(gx != nullptr, [&](auto want_gx) {
+    hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, decltype(want_gx)::value>), grid, dim3(256), 0, st, (const T*)x, (const T*)gy, w,
+                       (T*)gx, ws, B, H, W, C, dil, cvb, sg.on ? 1 : 0);
+  });
   if (int rc = check_launch("dwconv3x3_bwd_kernel")) return rc;
   hipLaunchKernelGGL(dwconv3x3_bwd_weight_reduce_kernel, dim3(cdiv(10L * C, 32)), dim3(256), 0, st, ws, dw, db, C, rows, flags);
   return check_launch("dwconv3x3_bwd_weight_reduce_kernel");
 }
 
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Three dilated depthwise branches of ONE input in one pass -- the EMA teacher's ASPP (daformer.py:46-62,65-126: dilations
-// 6 / 12 / 18 on the 40 x 135 x 240 x 1024 concatenated feature map; round 3 read that 2.65 GB map six times: three statistics
-// passes and three convolution + BatchNorm + ReLU passes, each bound by L2 -> CU traffic: 4.5 loads per output, nothing of a
-// dilated window is shared through L1).  Dilations g, 2g, 3g are plain / 2- / 3-dilated 3x3 convolutions of the g x g PHASE
-// sub-images (pixels (py + g i, px + g j)): a workgroup takes one phase of one image for 32 channels -- at most 23 x 40 pixels
-// x 64 bytes -- into LDS ONCE (every input byte is read from L2 / HBM exactly once) and computes all three branches from there:
-// statistics pass (sum, sum of squares of the rounded results of the three branches, nothing stored) and apply pass (convolution
-// + BatchNorm(batch statistics) + ReLU, three outputs).  76 KB of LDS: TWO workgroups per CU, one loading while the other
-// computes (the first version -- 64 channels, 151 KB, one workgroup of 4 waves per CU -- was latency-bound end to end: 47 us per
-// workgroup, slower than six single-branch passes).  The two 32-channel halves of a 64-channel group are taken by workgroups
-// that the dispatcher places on the SAME XCD 8 blocks apart, so that the 128-byte lines they share cross the fabric once.
-// LDS pixel pitch 80 bytes: the 16 lanes of a ds_read_b128 group (4 channel vectors x 4 quads, 4 pixels apart) cover all banks.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int kTriPitch = 80, kTriMaxPix = 944, kTriScratch = 4 * 4 * 16 * 4;
-
-struct TriArgs {
-  const float* w;            // [3][9][C] tap-major fp32
-  const float* bias;         // [3][C] or null
-  double* sums;              // [3][2 C + 1]
-  const float* gamma[3];     // apply pass (may be null)
-  const float* beta[3];
-  float* running_mean[3];    // may be null
-  float* running_var[3];
-  float eps[3], momentum[3];
-  void* y[3];                // bf16 or fp16, the input's type
-  int relu, ablate;
-};
-
-template <int M, int MODE, typename T>
-__device__ __forceinline__ void tri_branch(const unsigned char* __restrict__ img, float* __restrict__ scratch, const TriArgs& a,
-                                           int b, int B, int H, int W, int C, int g, int py, int px, int Hs, int Ws, int c0, int cv,
-                                           int pl, bool first_block, bool stat_block) {
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  constexpr int k = M - 1;
-  const int c = c0 + cv * 8;
-  f2 wr[9][4], bs[4];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const float* wp = a.w + ((size_t)k * 9 + t) * C + c;
-    const float4 lo = *reinterpret_cast<const float4*>(wp), hi = *reinterpret_cast<const float4*>(wp + 4);
-    wr[t][0] = f2{lo.x, lo.y}; wr[t][1] = f2{lo.z, lo.w}; wr[t][2] = f2{hi.x, hi.y}; wr[t][3] = f2{hi.z, hi.w};
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    bs[i] = a.bias != nullptr ? f2{a.bias[(size_t)k * C + c + 2 * i], a.bias[(size_t)k * C + c + 2 * i + 1]} : f2{0.f, 0.f};
-  float bsc[8], bsh[8], st0[8], st1[8];
-  if constexpr (MODE == 1) {
-    const double* sm = a.sums + (size_t)k * (2 * C + 1);
-    const double cnt = sm[2 * C], inv = 1.0 / cnt;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const double m = sm[c + i] * inv;
-      const float var = (float)fmax(sm[C + c + i] * inv - m * m, 0.0), mean = (float)m;
-      const float ga = a.gamma[k] != nullptr ? a.gamma[k][c + i] : 1.f, be = a.beta[k] != nullptr ? a.beta[k][c + i] : 0.f;
-      bsc[i] = rsqrtf(var + a.eps[k]) * ga;
-      bsh[i] = be - mean * bsc[i];
-      if (stat_block && pl == 0 && a.running_mean[k] != nullptr) {
-        const float n = (float)cnt;
-        a.running_mean[k][c + i] = (1.f - a.momentum[k]) * a.running_mean[k][c + i] + a.momentum[k] * mean;
-        a.running_var[k][c + i] = (1.f - a.momentum[k]) * a.running_var[k][c + i] + a.momentum[k] * var * (n / fmaxf(n - 1.f, 1.f));
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) st0[i] = st1[i] = 0.f;
-  }
-  const int QW = (Ws + 3) >> 2, nq = Hs * QW;
-  for (int q = pl; q < nq; q += 64) {
-    const int ys = q / QW, x0 = 4 * (q - ys * QW);
-    f2 acc[4][4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[p][i] = bs[i];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int yy = ys + (ky - 1) * M;
-      const bool rowok = yy >= 0 && yy < Hs;
-      const unsigned char* rowp = img + (size_t)min(max(yy, 0), Hs - 1) * Ws * kTriPitch + cv * 16;
-#pragma unroll
-      for (int o = 0; o < 4 + 2 * M; ++o) {
-        const int xx = x0 - M + o;
-        uint4 raw = *reinterpret_cast<const uint4*>(rowp + min(max(xx, 0), Ws - 1) * kTriPitch);
-        if (!(rowok && xx >= 0 && xx < Ws)) raw = make_uint4(0u, 0u, 0u, 0u);
-        f2 v[4];
-        VecIO<T>::unpack2(raw, v);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int d = o - p;                           // column offset of this load relative to output p, + M
-          if (d != 0 && d != M && d != 2 * M) continue;
-          const int kx = d / M;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[p][i] = __builtin_elementwise_fma(wr[ky * 3 + kx][i], v[i], acc[p][i]);
-        }
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (x0 + p >= Ws) continue;
-      float o[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        // the unfused path stores the convolution result in 16 bits before the statistics / BatchNorm read it back
-        o[2 * i] = VecIO<T>::rnd(acc[p][i].x);
-        o[2 * i + 1] = VecIO<T>::rnd(acc[p][i].y);
-      }
-      if constexpr (MODE == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          st0[i] += o[i];
-          st1[i] = fmaf(o[i], o[i], st1[i]);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float z = fmaf(o[i], bsc[i], bsh[i]);
-          o[i] = (a.relu && z <= 0.f) ? 0.f : z;
-        }
-        VecIO<T>::store(reinterpret_cast<T*>(a.y[k]) + (((size_t)b * H + py + g * ys) * W + px + g * (x0 + p)) * C + c, o);
-      }
-    }
-  }
-  if constexpr (MODE == 0) {
-    // lanes cv + 4 j of a wave hold partial sums of the same 8 channels: fold j, then the four waves through LDS
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int sft = 4; sft < 64; sft <<= 1) {
-        st0[i] += __shfl_xor(st0[i], sft, 64);
-        st1[i] += __shfl_xor(st1[i], sft, 64);
-      }
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < 4) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        scratch[(wave * 4 + lane) * 16 + i] = st0[i];
-        scratch[(wave * 4 + lane) * 16 + 8 + i] = st1[i];
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      const int v = threadIdx.x >> 4, e = threadIdx.x & 15;
-      const float sum = scratch[(0 * 4 + v) * 16 + e] + scratch[(1 * 4 + v) * 16 + e] + scratch[(2 * 4 + v) * 16 + e] +
-                        scratch[(3 * 4 + v) * 16 + e];
-      atomicAdd(a.sums + (size_t)k * (2 * C + 1) + (e >> 3) * C + c0 + v * 8 + (e & 7), (double)sum);
-    }
-    if (first_block && threadIdx.x == 0) atomicAdd(a.sums + (size_t)k * (2 * C + 1) + 2 * C, (double)B * H * W);
-    __syncthreads();
-  }
-}
-
-template <int MODE, typename T>
-__global__ __launch_bounds__(256, 2) void dwconv3x3_tri_kernel(const T* __restrict__ x, TriArgs a, int B, int H, int W,
-                                                               int C, int g, int nitems) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kTriMaxPix * kTriPitch + kTriScratch];
-  // block L runs on XCD L % 8 (the dispatcher's round-robin; speed only): the two halves of item i are blocks 8 apart on one XCD
-  const int L = blockIdx.x, local = L >> 3, half = local & 1, item = (local >> 1) * 8 + (L & 7);
-  if (item >= nitems) return;
-  const int gg = g * g, phase = item % gg, rest = item / gg, n64 = C / 64, b = rest / n64, c0 = (rest % n64) * 64 + half * 32;
-  const int py = phase / g, px = phase % g;
-  const int Hs = (H - py + g - 1) / g, Ws = (W - px + g - 1) / g;
-  const int cv = threadIdx.x & 3, pl = threadIdx.x >> 2;
-  const T* xb = x + (size_t)b * H * W * C + c0 + cv * 8;
-  const int npix = Hs * Ws;
-  // all of the thread's loads first (up to 15 in flight), then the LDS writes
-  constexpr int NL = (kTriMaxPix + 63) / 64;
-  uint4 v[NL];
-#pragma unroll
-  for (int it = 0; it < NL; ++it) {
-    const int p = min(pl + 64 * it, npix - 1), ys = p / Ws, xs = p - ys * Ws;
-    v[it] = (a.ablate & 1) ? uint4{0, 0, 0, 0} : *reinterpret_cast<const uint4*>(xb + ((size_t)(py + g * ys) * W + (px + g * xs)) * C);
-  }
-#pragma unroll
-  for (int it = 0; it < NL; ++it) {
-    const int p = pl + 64 * it;
-    if (p < npix) *reinterpret_cast<uint4*>(lds + (size_t)p * kTriPitch + cv * 16) = v[it];
-  }
-  __syncthreads();
-  float* scratch = reinterpret_cast<float*>(lds + kTriMaxPix * kTriPitch);
-  const bool first_block = item == 0 && half == 0, stat_block = phase == 0 && b == 0;
-  if (a.ablate & 2) return;
-  tri_branch<1, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
-  if (a.ablate & 4) return;
-  tri_branch<2, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
-  tri_branch<3, MODE, T>(lds, scratch, a, b, B, H, W, C, g, py, px, Hs, Ws, c0, cv, pl, first_block, stat_block);
-}
-
-static int tri_domain(int B, int H, int W, int C, int g) {
-  return B > 0 && g >= 1 && g <= H && g <= W && C % 64 == 0 && cdiv(H, g) * cdiv(W, g) <= kTriMaxPix &&
-         (long)g * g * (C / 64) * B < (1L << 26);
-}
-
-template <typename T>
-static int tri_stats(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C, int g,
-                     hipStream_t st) {
-  RFN_REQUIRE(x && weight3 && sums3, "rfn_dwconv3x3_tri_stats: null pointer");
-  RFN_REQUIRE(tri_domain(B, H, W, C, g), "rfn_dwconv3x3_tri_stats: B=%d H=%d W=%d C=%d g=%d outside the kernel's domain", B, H, W, C, g);
-  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_tri_stats", "dwconv3x3_tri_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det per branch)");
-  if (int rc = zero_async(sums3, 3 * (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  TriArgs a{};
-  a.w = weight3, a.bias = bias3, a.sums = sums3;
-  a.ablate = 0;
-  const long nitems = (long)g * g * (C / 64) * B;
-  hipLaunchKernelGGL((dwconv3x3_tri_kernel<0, T>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, st, (const T*)x, a,
-                     B, H, W, C, g, (int)nitems);
-  return check_launch("dwconv3x3_tri_kernel<stats>");
-}
-
-template <typename T>
-static int tri_apply(const void* x, const float* weight3, const float* bias3, const float* const* gamma3, const float* const* beta3,
-                     const double* sums3, float* const* running_mean3, float* const* running_var3, void* const* y3, int B, int H,
-                     int W, int C, int g, const float* eps3, const float* momentum3, int relu, hipStream_t st) {
-  RFN_REQUIRE(x && weight3 && sums3 && y3 && gamma3 && beta3 && running_mean3 && running_var3 && eps3 && momentum3,
-              "rfn_dwconv3x3_tri_bn_act_fwd: null pointer");
-  RFN_REQUIRE(tri_domain(B, H, W, C, g), "rfn_dwconv3x3_tri_bn_act_fwd: B=%d H=%d W=%d C=%d g=%d outside the kernel's domain", B, H, W, C, g);
-  TriArgs a{};
-  a.w = weight3, a.bias = bias3, a.sums = const_cast<double*>(sums3), a.relu = relu;
-  a.ablate = 0;
-  for (int k = 0; k < 3; ++k) {
-    RFN_REQUIRE(y3[k], "rfn_dwconv3x3_tri_bn_act_fwd: null output %d", k);
-    a.gamma[k] = gamma3[k], a.beta[k] = beta3[k], a.running_mean[k] = running_mean3[k], a.running_var[k] = running_var3[k];
-    a.eps[k] = eps3[k], a.momentum[k] = momentum3[k], a.y[k] = y3[k];
-  }
-  const long nitems = (long)g * g * (C / 64) * B;
-  hipLaunchKernelGGL((dwconv3x3_tri_kernel<1, T>), dim3((unsigned)(16 * cdiv(nitems, 8))), dim3(256), 0, st, (const T*)x, a, B, H,
-                     W, C, g, (int)nitems);
-  return check_launch("dwconv3x3_tri_kernel<apply>");
+// bf16 / fp16 for the entry points that take nothing else (dtype checked to be 1 or 2; dt_one would ask for their fp32
+// kernels, which do not exist)
+template <typename Fn>
+static inline int dt_16(int dtype, Fn&& fn) {
+  return dtype == 1 ? fn(DT<__hip_bfloat16>{}) : fn(DT<_Float16>{});
 }
 
 }  // namespace rfn
@@ -1256,42 +920,6 @@ static int tri_apply(const void* x, const float* weight3, const float* bias3, co
 using namespace rfn;
 
 extern "C" {
-// Three dilated depthwise 3x3 branches (dilations g, 2 g, 3 g; padding = dilation) of one bf16 NHWC input in ONE pass each
-// (the _f16 forms: an fp16 input, fp16 outputs):
-//   rfn_dwconv3x3_tri_stats        sums3 [3][2 C + 1] doubles <- (sum, sum of squares, rows) of the three rounded results;
-//   rfn_dwconv3x3_tri_bn_act_fwd   y[k] = act(bn_k(conv_k(x))) with the statistics in sums3 (a SyncBatchNorm all-reduces them in
-//                                  between).  weight3: [3][9][C] tap-major fp32, bias3: [3][C] or NULL; gamma / beta / running_mean /
-//                                  running_var / y / eps / momentum: HOST arrays of 3.  C % 64 == 0, ceil(H / g) ceil(W / g) <= 944.
-// rfn_dwconv3x3_tri_usable: 1 when a shape is inside that domain.
-int rfn_dwconv3x3_tri_usable(int B, int H, int W, int C, int g) { return tri_domain(B, H, W, C, g); }
-
-int rfn_dwconv3x3_tri_stats(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C, int g,
-                            rfn_stream_t stream) {
-  return tri_stats<__hip_bfloat16>(x, weight3, bias3, sums3, B, H, W, C, g, (hipStream_t)stream);
-}
-
-int rfn_dwconv3x3_tri_stats_f16(const void* x, const float* weight3, const float* bias3, double* sums3, int B, int H, int W, int C,
-                                int g, rfn_stream_t stream) {
-  return tri_stats<_Float16>(x, weight3, bias3, sums3, B, H, W, C, g, (hipStream_t)stream);
-}
-
-int rfn_dwconv3x3_tri_bn_act_fwd(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
-                                 const float* const* beta3, const double* sums3, float* const* running_mean3,
-                                 float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
-                                 const float* momentum3, int relu, rfn_stream_t stream) {
-  return tri_apply<__hip_bfloat16>(x, weight3, bias3, gamma3, beta3, sums3, running_mean3, running_var3, y3, B, H, W, C, g, eps3,
-                                   momentum3, relu, (hipStream_t)stream);
-}
-
-int rfn_dwconv3x3_tri_bn_act_fwd_f16(const void* x, const float* weight3, const float* bias3, const float* const* gamma3,
-                                     const float* const* beta3, const double* sums3, float* const* running_mean3,
-                                     float* const* running_var3, void* const* y3, int B, int H, int W, int C, int g, const float* eps3,
-                                     const float* momentum3, int relu, rfn_stream_t stream) {
-  return tri_apply<_Float16>(x, weight3, bias3, gamma3, beta3, sums3, running_mean3, running_var3, y3, B, H, W, C, g, eps3, momentum3,
-                             relu, (hipStream_t)stream);
-}
-
-
 int rfn_dwconv3x3_nhwc_fwd(const void* x, const float* weight, const float* bias, void* y, int B, int H, int W, int C,
                            int dilation, int dtype, int flip, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && y, "rfn_dwconv3x3_nhwc_fwd: null pointer");
@@ -1316,8 +944,9 @@ int rfn_dwconv3x3_nhwc_fwd_stats(const void* x, const float* weight, const float
   RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_fwd_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_fwd_stats_det)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st)
-                    : launch_fwd_stats<_Float16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st);
+  return dt_16(dtype, [&](auto t) {
+    return launch_fwd_stats<typename decltype(t)::type>(x, weight, bias, y, sums, nullptr, B, H, W, C, dilation, st);
+  });
 }
 
 // Deterministic forms of rfn_dwconv3x3_nhwc_fwd_stats / rfn_dwconv3x3_nhwc_stats: every block row stores its 2 C partial sums
@@ -1333,9 +962,10 @@ int rfn_dwconv3x3_nhwc_fwd_stats_det(const void* x, const float* weight, const f
   RFN_REQUIRE(x && weight && y && sums && workspace, "rfn_dwconv3x3_nhwc_fwd_stats_det: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bad size");
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace)
-                    : launch_fwd_stats<_Float16, 1, false>(x, weight, bias, y, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace);
+  return dt_16(dtype, [&](auto t) {
+    return launch_fwd_stats<typename decltype(t)::type>(x, weight, bias, y, sums, (double*)workspace, B, H, W, C, dilation,
+                                                        (hipStream_t)stream);
+  });
 }
 
 int rfn_dwconv3x3_nhwc_stats_det(const void* x, const float* weight, const float* bias, double* sums, void* workspace, int B, int H,
@@ -1343,9 +973,10 @@ int rfn_dwconv3x3_nhwc_stats_det(const void* x, const float* weight, const float
   RFN_REQUIRE(x && weight && sums && workspace, "rfn_dwconv3x3_nhwc_stats_det: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats_det: bad size");
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace)
-                    : launch_fwd_stats<_Float16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, (double*)workspace);
+  return dt_16(dtype, [&](auto t) {
+    return launch_roll<typename decltype(t)::type, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation,
+                                                             (hipStream_t)stream, BnEpi{}, (double*)workspace);
+  });
 }
 
 // Gradient-free depthwise 3x3 -> BatchNorm(batch statistics) -> ReLU in two passes over the INPUT (bf16 / f16):
@@ -1360,8 +991,9 @@ int rfn_dwconv3x3_nhwc_stats(const void* x, const float* weight, const float* bi
   RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_roll_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
   hipStream_t st = (hipStream_t)stream;
   if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return dtype == 1 ? launch_fwd_stats<__hip_bfloat16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st)
-                    : launch_fwd_stats<_Float16, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st);
+  return dt_16(dtype, [&](auto t) {
+    return launch_roll<typename decltype(t)::type, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, nullptr);
+  });
 }
 
 int rfn_dwconv3x3_bn_act_nhwc_fwd(const void* x, const float* weight, const float* bias, const float* gamma, const float* beta,
@@ -1372,11 +1004,10 @@ int rfn_dwconv3x3_bn_act_nhwc_fwd(const void* x, const float* weight, const floa
   RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0 && (relu == 0 || relu == 1),
               "rfn_dwconv3x3_bn_act_nhwc_fwd: bf16 / f16, C %% 8 == 0, relu 0 / 1");
   BnEpi bn{gamma, beta, running_mean, running_var, eps, momentum, relu};
-  if (dtype == 2)
-    return launch_fwd_stats<_Float16, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
-                                               (hipStream_t)stream, bn);
-  return launch_fwd_stats<__hip_bfloat16, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
-                                                   (hipStream_t)stream, bn);
+  return dt_16(dtype, [&](auto t) {
+    return launch_roll<typename decltype(t)::type, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
+                                                            (hipStream_t)stream, bn, nullptr);
+  });
 }
 
 int rfn_dwconv3x3_gelu_nhwc_fwd(const void* x, const float* weight, const float* bias, void* y_pre, void* y_act, int B,

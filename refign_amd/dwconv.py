@@ -16,6 +16,17 @@ from .params import as_dtype, derived, grad_sink
 _DW_WS_STRIPES = 128       # kMaxStripes in csrc/dwconv.hip (checked against the ABI in the GPU tests)
 
 
+def _tap_major(weight):
+    """(9, C) tap-major fp32 copy of the (C, 1, 3, 3) parameter, re-made only when the parameter changed"""
+    C = weight.shape[0]
+    return derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(), lambda t: t.reshape(C, 9).t())
+
+
+def _f32(p):
+    """fp32 contiguous view of a bias / affine parameter (None stays None)"""
+    return None if p is None else as_dtype(p, torch.float32).detach().contiguous()
+
+
 def _fwd(x, w_tap, bias, dilation, flip, stats=None):
     B, H, W, C = x.shape
     y = torch.empty_like(x)
@@ -40,11 +51,7 @@ class _DWConv3x3(torch.autograd.Function):
         if x.dtype not in DTYPE_CODE:
             x = x.float()
         x = require_device_tensor(x.contiguous(), "x")
-        C = x.shape[-1]
-        # (9, C) tap-major fp32 copy of the parameter, re-made only when the parameter changed
-        w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                        lambda t: t.reshape(C, 9).t())
-        b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
+        w_tap, b32 = _tap_major(weight), _f32(bias)
         ctx.save_for_backward(x, w_tap)
         ctx.dilation, ctx.has_bias = dilation, bias is not None
         ctx.wshape, ctx.wdtype = weight.shape, weight.dtype
@@ -67,9 +74,7 @@ class _DWConv3x3Gelu(torch.autograd.Function):
             x = x.float()
         x = require_device_tensor(x.contiguous(), "x")
         B, H, W, C = x.shape
-        w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                        lambda t: t.reshape(C, 9).t())
-        b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
+        w_tap, b32 = _tap_major(weight), _f32(bias)
         need = any(ctx.needs_input_grad)
         with_z = with_z and need
         ctx.set_materialize_grads(False)          # the non-differentiable output's "gradient" must not become a zero tensor
@@ -99,7 +104,6 @@ class _DWConv3x3Gelu(torch.autograd.Function):
             gz = grads[1].to(z.dtype).contiguous()
         else:
             gz = torch.ops.aten.gelu_backward(grads[0].to(z.dtype).contiguous(), z)
-        ctx.saved = (x, w_tap)
         return _dwconv_backward(ctx, x, w_tap, gz)[:3] + (None,)
 
 
@@ -155,8 +159,7 @@ def ffn_fc1_dw_gelu(x, fc1, dw, H, W):
             and dw.padding == (1, 1) and dw.stride == (1, 1) and dw.dilation == (1, 1)):
         return None
     w1, b1 = as_dtype(fc1.weight, x.dtype), as_dtype(fc1.bias, x.dtype)
-    w_tap = derived(dw.weight, "tap_major_f32", lambda t: t.float().reshape(HID, 9).t().contiguous(), lambda t: t.reshape(HID, 9).t())
-    bdw = as_dtype(dw.bias, torch.float32).detach().contiguous()
+    w_tap, bdw = _tap_major(dw.weight), _f32(dw.bias)
     a = torch.empty((B, N, HID), dtype=x.dtype, device=x.device)
     _lib.call("rfn_ffn_fc1_dw_gelu_f16" if x.dtype == torch.float16 else "rfn_ffn_fc1_dw_gelu_bf16", x.device, ptr(x), ptr(w1),
               ptr(b1), ptr(w_tap), ptr(bdw), ptr(a), B, H, W, C, HID)
@@ -193,11 +196,7 @@ def _stats_only(x, w_tap, b32, dilation):
 def dwconv3x3_stats_nhwc(x, weight, bias, dilation):
     """The first pass of dwconv3x3_bn_act_nhwc alone: the BatchNorm statistics of dwconv3x3_nhwc(x, weight, bias, dilation)
     (a float64 tensor of 2 C + 1: sum, sum of squares, rows) without storing the convolution.  x: (B, H, W, C) bf16 / fp16."""
-    C = x.shape[-1]
-    w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                    lambda t: t.reshape(C, 9).t())
-    b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
-    return _stats_only(x, w_tap, b32, int(dilation))
+    return _stats_only(x, _tap_major(weight), _f32(bias), int(dilation))
 
 
 @torch.no_grad()
@@ -208,11 +207,7 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
     result.  x: (B, H, W, C) bf16 / fp16 contiguous; bn: the (Sync)BatchNorm2d module (running buffers updated as in training)."""
     from . import bn as bnk
     B, H, W, C = x.shape
-    w_tap = derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                    lambda t: t.reshape(C, 9).t())
-    b32 = None if bias is None else as_dtype(bias, torch.float32).detach().contiguous()
-    g = None if bn.weight is None else as_dtype(bn.weight, torch.float32).detach().contiguous()
-    be = None if bn.bias is None else as_dtype(bn.bias, torch.float32).detach().contiguous()
+    w_tap, b32, g, be = _tap_major(weight), _f32(bias), _f32(bn.weight), _f32(bn.bias)
     y = torch.empty_like(x)
     sums = _stats_only(x, w_tap, b32, int(dilation))
     group = bnk.sync_group(bn)
@@ -223,63 +218,6 @@ def dwconv3x3_bn_act_nhwc(x, weight, bias, dilation, bn, relu):
               1 if relu else 0, DTYPE_CODE[x.dtype])
     bn.num_batches_tracked.add_(1)
     return y
-
-
-def tri_usable(x, convs, bns):
-    """the three (conv, bn) pairs are depthwise 3x3 with dilations g, 2 g, 3 g and padding = dilation on a shape the one-pass
-    kernel takes (csrc/dwconv.hip dwconv3x3_tri_kernel)"""
-    if determinism.enabled():          # the one-pass statistics kernel adds with fp64 atomics: one branch at a time instead
-        return False
-    if len(convs) != 3 or not (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 4 and x.is_contiguous()):
-        return False
-    B, H, W, C = x.shape
-    d = [c.dilation[0] for c in convs]
-    ok = all(c.groups == c.in_channels == c.out_channels == C and c.kernel_size == (3, 3) and c.stride == (1, 1)
-             and c.padding == c.dilation and c.dilation[0] == c.dilation[1] for c in convs)
-    ok = ok and d[1] == 2 * d[0] and d[2] == 3 * d[0] and all(b.momentum is not None for b in bns)
-    same_bias = all((c.bias is None) == (convs[0].bias is None) for c in convs)
-    return bool(ok and same_bias and _lib.load_library().rfn_dwconv3x3_tri_usable(B, H, W, C, d[0]))
-
-
-@torch.no_grad()
-def dwconv3x3_bn_act_nhwc_tri(x, convs, bns, relu):
-    """[act(bn_k(dwconv3x3_k(x))) for k in 0..2] with BATCH statistics, gradient-free, for three depthwise branches of dilations
-    g, 2 g, 3 g of one input (the EMA teacher's ASPP): TWO passes over x in all -- statistics of the three results, then the
-    three convolutions + normalisation + ReLU -- where dwconv3x3_bn_act_nhwc makes six."""
-    import ctypes
-    from . import bn as bnk
-    B, H, W, C = x.shape
-    g = convs[0].dilation[0]
-    w3 = torch.stack([derived(c.weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                              lambda t: t.reshape(C, 9).t()) for c in convs]).contiguous()
-    b3 = None if convs[0].bias is None else torch.stack([as_dtype(c.bias, torch.float32).detach() for c in convs]).contiguous()
-    sums = torch.empty((3, 2 * C + 1), dtype=torch.float64, device=x.device)
-    f16 = "_f16" if x.dtype == torch.float16 else ""
-    _lib.call("rfn_dwconv3x3_tri_stats" + f16, x.device, ptr(x), ptr(w3), ptr(b3), ptr(sums), B, H, W, C, int(g))
-    for k, bn in enumerate(bns):
-        group = bnk.sync_group(bn)
-        if group is not None:
-            bnk._all_reduce(sums[k], group, bnk._exchange_comm(bn))
-    ys = [torch.empty_like(x) for _ in range(3)]
-    keep = []                                              # fp32 views of the affine parameters stay alive until the launch
-
-    def f32(t):
-        if t is None:
-            return None
-        keep.append(as_dtype(t, torch.float32).detach().contiguous())
-        return keep[-1]
-
-    arr = lambda ts: (ctypes.c_void_p * 3)(*[ptr(t) for t in ts])  # noqa: E731
-    ga, be = arr([f32(b.weight) for b in bns]), arr([f32(b.bias) for b in bns])
-    rm, rv = arr([b.running_mean for b in bns]), arr([b.running_var for b in bns])
-    yp = arr(ys)
-    eps = (ctypes.c_float * 3)(*[float(b.eps) for b in bns])
-    mom = (ctypes.c_float * 3)(*[float(b.momentum) for b in bns])
-    _lib.call("rfn_dwconv3x3_tri_bn_act_fwd" + f16, x.device, ptr(x), ptr(w3), ptr(b3), ga, be, ptr(sums), rm, rv, yp, B, H, W, C,
-              int(g), eps, mom, 1 if relu else 0)
-    for b in bns:
-        b.num_batches_tracked.add_(1)
-    return ys
 
 
 def dwconv3x3_tokens(x, weight, bias, H, W):

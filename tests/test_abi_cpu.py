@@ -28,7 +28,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"librefign_hip.so does not export {s}"
         assert s in _lib.SIGNATURES, f"refign_amd/_lib.py has no ctypes signature for {s}"
     assert sorted(_lib.SIGNATURES) == _declared_symbols()
-    assert refign_amd.abi_version() == 4
+    assert refign_amd.abi_version() == 5
 
 
 def test_no_cpu_fallback():
@@ -126,5 +126,5 @@ def test_stream_is_the_last_argument():
 
 def test_abi_version_comes_from_the_header():
     from refign_amd import _lib
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
     assert _lib.ABI_VERSION == int(re.search(r"#define\s+RFN_ABI_VERSION\s+(\d+)", _header_text()).group(1))

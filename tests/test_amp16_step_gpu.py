@@ -1,6 +1,5 @@
 """GPU: the fp16 recipe (Trainer(precision=16)) on the MiT-B5 golden step, under hipGraph capture and replay, and the fp16
-forms of the teacher's fused kernels (three-branch ASPP depthwise, Mix-FFN front half)."""
-import copy
+form of the teacher's fused Mix-FFN front half."""
 import random
 
 import numpy as np
@@ -147,44 +146,6 @@ def test_fp16_steps_after_bf16_steps_equal_a_fresh_model(dev, monkeypatch):
 
 
 # --- the teacher's fused kernels in fp16 ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,H,W,C,g,relu,bias", [(2, 135, 240, 128, 6, True, True), (3, 37, 53, 64, 2, True, False),
-                                                   (2, 20, 28, 1024, 6, False, True), (1, 7, 9, 64, 1, True, True)])
-def test_three_dilations_fp16_equal_three_single_branch_passes(dev, B, H, W, C, g, relu, bias):
-    """The ASPP three-branch kernel on fp16 (rfn_dwconv3x3_tri_*_f16) == three calls of the fp16 single-branch two-pass path:
-    results at most one fp16 rounding step apart and almost everywhere equal, running buffers, batch counters; ragged phase
-    images and an image smaller than the largest dilation included."""
-    from refign_amd.dwconv import dwconv3x3_bn_act_nhwc, dwconv3x3_bn_act_nhwc_tri, tri_usable
-    gen = torch.Generator().manual_seed(C + H + g)
-    x = (torch.randn(B, H, W, C, generator=gen) + 0.2).to(dev).to(H16)
-    convs, bns_a = [], []
-    for k in range(3):
-        d = g * (k + 1)
-        conv = torch.nn.Conv2d(C, C, 3, padding=d, dilation=d, groups=C, bias=bias).to(dev)
-        with torch.no_grad():
-            conv.weight.copy_(torch.randn(C, 1, 3, 3, generator=gen).to(dev))
-            if bias:
-                conv.bias.copy_(torch.randn(C, generator=gen).to(dev))
-        bn = torch.nn.BatchNorm2d(C).to(dev).train()
-        with torch.no_grad():
-            bn.weight.copy_(torch.rand(C, generator=gen).to(dev) + 0.5)
-            bn.bias.copy_(torch.randn(C, generator=gen).to(dev))
-        convs.append(conv)
-        bns_a.append(bn)
-    bns_b = copy.deepcopy(bns_a)
-    assert tri_usable(x, convs, bns_a)
-    with torch.no_grad():
-        got = dwconv3x3_bn_act_nhwc_tri(x, convs, bns_a, relu)
-        want = [dwconv3x3_bn_act_nhwc(x, c.weight, c.bias, c.dilation[0], b, relu) for c, b in zip(convs, bns_b)]
-    for k in range(3):
-        assert got[k].dtype == H16
-        err = (got[k].float() - want[k].float()).abs()
-        assert float(err.max()) <= 2.0 ** -10 * float(want[k].float().abs().max()), k
-        assert float((err > 0).float().mean()) < 1e-3, k
-        assert torch.allclose(bns_a[k].running_mean, bns_b[k].running_mean, rtol=1e-6, atol=1e-7)
-        assert torch.allclose(bns_a[k].running_var, bns_b[k].running_var, rtol=1e-6, atol=1e-7)
-        assert int(bns_a[k].num_batches_tracked) == 1
-
-
 @pytest.mark.parametrize("views,H,W,C", [(3, 17, 30, 512), (2, 34, 60, 320), (2, 7, 45, 128), (1, 135, 240, 64), (1, 1, 1, 128),
                                          (2, 68, 120, 128)])
 def test_fused_mix_ffn_front_half_fp16(dev, views, H, W, C):

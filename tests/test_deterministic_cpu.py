@@ -15,7 +15,7 @@ def test_library_exports_the_flag_and_it_round_trips():
     raw = ctypes.CDLL(refign_amd.library_path())
     assert hasattr(raw, "rfn_set_deterministic") and hasattr(raw, "rfn_get_deterministic")
     header = open(os.path.join(ROOT, "include", "refign_hip.h")).read()
-    assert "#define RFN_ENONDET (-4)" in header and "#define RFN_ABI_VERSION 4" in header
+    assert "#define RFN_ENONDET (-4)" in header and "#define RFN_ABI_VERSION 5" in header
     lib = _lib.load_library()
     assert lib.rfn_get_deterministic() == 0
     try:
@@ -24,7 +24,7 @@ def test_library_exports_the_flag_and_it_round_trips():
     finally:
         assert lib.rfn_set_deterministic(0) == 0
     assert lib.rfn_get_deterministic() == 0
-    assert refign_amd.abi_version() == 4
+    assert refign_amd.abi_version() == 5
 
 
 def test_every_deterministic_entry_point_is_bound():

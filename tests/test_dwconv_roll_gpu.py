@@ -23,9 +23,11 @@ SHAPES = [(3, 5, 4, 2048, 18),     # every off-centre tap outside the image, XCD
 
 
 def _exact_inputs(B, H, W, C, dil, dtype, dev):
-    """integers in [-2, 2], weights in {-1, -0.5, 0, 0.5, 1}, bias multiples of 0.5: every convolution result (a multiple
-    of 0.5, |.| <= 19) is exact in bf16 / fp16 and every fp32 partial sum (of at most B H W <= 1426 values <= 19, of squares
-    <= 361, multiples of 0.25) is exact"""
+    """integers in [-2, 2], weights in {-1, -0.5, 0, 0.5, 1}, bias multiples of 0.5: every convolution result is a multiple of
+    0.5 with |.| <= 9 x 2 x 1 + 1 = 19, exact in bf16 / fp16, and its square a multiple of 0.25 <= 361.  A channel has at most
+    B H W <= 2680 results (1 x 40 x 67), so every partial sum of a channel -- a thread's, a block's -- is a multiple of 0.5
+    with |.| <= 2680 x 19 = 50 920 < 2^16, of squares a multiple of 0.25 <= 2680 x 361 = 967 480 < 2^20: as multiples of
+    0.25 both are integers below 2^22 < 2^24, exact in fp32 in any summation order, and exact in fp64 after that"""
     g = torch.Generator().manual_seed(B * 1000 + H * 10 + C + dil)
     x = torch.randint(-2, 3, (B, H, W, C), generator=g).to(dtype)
     w = torch.randint(-2, 3, (C, 1, 3, 3), generator=g).float() * 0.5
@@ -41,19 +43,49 @@ def _exact_sums(B, H, W, C, dil, dtype):
     return y.sum(dim=(0, 2, 3)), (y * y).sum(dim=(0, 2, 3))
 
 
-@pytest.mark.parametrize("det", [False, True])
+@functools.lru_cache(maxsize=None)
+def _exact_conv(B, H, W, C, dil, dtype):
+    """F.conv2d of the same inputs on the host, cast to the dtype (the values are exact in it): (B, H, W, C)"""
+    x, w, b = _exact_inputs(B, H, W, C, dil, dtype, "cpu")
+    y = F.conv2d(x.float().permute(0, 3, 1, 2), w, b, padding=dil, dilation=dil, groups=C)
+    return y.permute(0, 2, 3, 1).contiguous().to(dtype)
+
+
+def test_exact_reference_is_exact():
+    """the premise of the exact tests, on the host: the fp64 sums of every shape are multiples of 0.5 (squares: 0.25) whose
+    count of quarter units is below 2^24, and the results themselves survive the cast to bf16 and fp16"""
+    for B, H, W, C, dil in SHAPES:
+        for dtype in (torch.bfloat16, torch.float16):
+            s0, s1 = _exact_sums(B, H, W, C, dil, dtype)
+            assert torch.equal(s0 * 2, (s0 * 2).round()) and torch.equal(s1 * 4, (s1 * 4).round())
+            assert float((s0 * 4).abs().max()) < 2.0 ** 24 and float((s1 * 4).max()) < 2.0 ** 24
+            y = _exact_conv(B, H, W, C, dil, dtype).double()
+            assert float(y.abs().max()) <= 19 and torch.equal(y.sum(dim=(0, 1, 2)), s0)
+
+
+# (`storing` shares the last id with `det`: the cases without it keep the ids they had before the parameter existed)
+@pytest.mark.parametrize("det,storing", [pytest.param(d, s, id=f"{d}-storing" if s else str(d))
+                                         for s in (False, True) for d in (False, True)])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("B,H,W,C,dil", SHAPES)
-def test_store_free_statistics_are_exact(dev, B, H, W, C, dil, dtype, det):
+def test_store_free_statistics_are_exact(dev, B, H, W, C, dil, dtype, det, storing):
     """rfn_dwconv3x3_nhwc_stats (and, under `determinism`, rfn_dwconv3x3_nhwc_stats_det) on inputs whose sums are exact in
     every precision involved == the fp64 sums of F.conv2d, to the bit, including the row count: a misplaced tap, a sum
-    carried over a seam or a row counted twice at a segment edge cannot hide behind a tolerance."""
+    carried over a seam or a row counted twice at a segment edge cannot hide behind a tolerance.  `storing`: the sums of the
+    kernel that stores the convolution (dwconv3x3_nhwc(stats=...): rfn_dwconv3x3_nhwc_fwd_stats / _fwd_stats_det) instead,
+    which share the fold; its stored result == F.conv2d of the same inputs, to the bit."""
     from refign_amd import determinism
-    from refign_amd.dwconv import dwconv3x3_stats_nhwc
+    from refign_amd.dwconv import dwconv3x3_nhwc, dwconv3x3_stats_nhwc
     x, w, b = _exact_inputs(B, H, W, C, dil, dtype, dev)
     s0, s1 = _exact_sums(B, H, W, C, dil, dtype)
-    with determinism.deterministic(det):
-        sums = dwconv3x3_stats_nhwc(x, w, b, dil).cpu()
+    with determinism.deterministic(det), torch.no_grad():
+        if storing:
+            sums = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+            y = dwconv3x3_nhwc(x, w, b, dil, stats=sums)
+            sums = sums.cpu()
+            assert torch.equal(y.cpu(), _exact_conv(B, H, W, C, dil, dtype))
+        else:
+            sums = dwconv3x3_stats_nhwc(x, w, b, dil).cpu()
     assert float(sums[2 * C]) == B * H * W
     assert torch.equal(sums[:C], s0)
     assert torch.equal(sums[C:2 * C], s1)

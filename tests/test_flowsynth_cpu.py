@@ -142,7 +142,7 @@ def test_header_declares_the_entry_points():
     c = _lib.c_void_p
     import ctypes
     i, d = ctypes.c_int, ctypes.c_double
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
     assert _lib.SIGNATURES["rfn_flowsynth_flow_f32"] == (i, [c, i, c, i, c, i, i, c, c, c])
     assert _lib.SIGNATURES["rfn_flowsynth_warp_f32"] == (i, [c, c, c, i, i, i, i, i, i, d, c, c, c, c])
     assert _lib.SIGNATURES["rfn_gaussian_blur_f32"] == (i, [c, c, i, i, i, i, c, c, c])

@@ -202,6 +202,6 @@ def test_library_exports_the_new_entry_points():
     for name in ("rfn_resize_filter_u8", "rfn_resize_filter_crop_flip_norm_pad_u8", "rfn_sparse_epe_f32"):
         assert name in _lib.SIGNATURES and _lib.SIGNATURES[name][1][-1] is _lib.c_void_p, name     # the stream comes last
         assert getattr(_lib.load_library(), name) is not None
-    assert _lib.ABI_VERSION == 4 and _lib.abi_version() == 4
+    assert _lib.ABI_VERSION == 5 and _lib.abi_version() == 5
     for name in ("rfn_resize_crop_flip_norm_u8", "rfn_resize_u8", "rfn_resize_nearest_u8"):     # the old ones keep their shape
         assert len(_lib.SIGNATURES[name][1]) == {"rfn_resize_crop_flip_norm_u8": 20, "rfn_resize_u8": 13, "rfn_resize_nearest_u8": 9}[name]

@@ -31,7 +31,7 @@ def test_header_declares_and_library_binds_the_new_entry_points():
     lib = _lib.load_library()
     for name in NEW_ENTRY_POINTS:
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert refign_amd.abi_version() == 4 and _lib.ABI_VERSION == 4
+    assert refign_amd.abi_version() == 5 and _lib.ABI_VERSION == 5
     assert lib.rfn_flowloss_block_pixels() == 1024
 
 

@@ -118,7 +118,7 @@ def test_library_exports_the_resize_entry_points():
     lib = ctypes.CDLL(refign_amd.library_path())
     for s in ("rfn_resize_crop_flip_norm_u8", "rfn_resize_u8", "rfn_resize_nearest_u8"):
         assert hasattr(lib, s) and s in _lib.SIGNATURES, s
-    assert refign_amd.abi_version() == 4
+    assert refign_amd.abi_version() == 5
 
 
 def test_no_cpu_fallback():

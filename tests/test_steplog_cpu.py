@@ -467,7 +467,7 @@ def test_bindings():
     lib = ctypes.CDLL(refign_amd.library_path())
     for name in ("rfn_steplog_gather", "rfn_grad_sqnorm_groups"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert refign_amd.abi_version() == 4
+    assert refign_amd.abi_version() == 5
     # argument errors are decided on the host: nothing is launched, so they can be seen without a GPU
     bound = _lib.load_library()
     one = (ctypes.c_void_p * 1)(64)
