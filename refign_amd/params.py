@@ -215,7 +215,9 @@ _EMA_TABLES = {}
 def ema_update(ema_params, live_params, momentum, plan_key):
     """ema <- momentum * ema + (1 - momentum) * live over two aligned parameter lists (segmentation_model.py:676-689) as
     ONE kernel launch (csrc/reduce.hip: rfn_multi_ema_f32) from a chunk table that is built once per parameter set,
-    then refresh() of the teacher's cached copies.  Falls back to two multi-tensor torch ops off the GPU."""
+    then refresh() of the teacher's cached copies.  Falls back to two multi-tensor torch ops off the GPU.
+    The kernel's second coefficient is float32(1) - float32(momentum); the reference and the torch branch below multiply by
+    float32(1 - momentum) -- for momentum 0.999 the two are 1.29e-5 apart relatively."""
     ema_params, live_params = list(ema_params), list(live_params)
     if not ema_params:
         return
