@@ -100,19 +100,28 @@ class AlignmentModel(nn.Module):
     def __getstate__(self):
         d = self.__dict__.copy()
         d.pop("_fwd_graph", None)                         # copies and pickles capture their own
+        d.pop("_step_graph", None)                        # (the trainer's; a copy has no trainer)
         return d
 
+    def _drop_graphs(self):
+        """The eval-forward graph is dropped; the training step's graph (Trainer(graph_step=True) leaves it here as
+        `_step_graph`) is reset: two eager steps, then a new capture."""
+        self.__dict__.pop("_fwd_graph", None)
+        g = self.__dict__.get("_step_graph")
+        if g is not None:
+            g.reset()
+
     def _apply(self, fn, *a, **k):
-        self.__dict__.pop("_fwd_graph", None)             # cached derived tensors move with the parameters
+        self._drop_graphs()                               # cached derived tensors move with the parameters
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self.__dict__.pop("_fwd_graph", None)
+        self._drop_graphs()
         return super().load_state_dict(*a, **k)
 
     def train(self, mode=True):
         """alignment_model.py:233-238: the frozen backbone's norm layers never leave eval mode."""
-        self.__dict__.pop("_fwd_graph", None)
+        self._drop_graphs()
         super().train(mode)
         for m in self.alignment_backbone.modules():
             if isinstance(m, nn.modules.batchnorm._BatchNorm):

@@ -1416,8 +1416,9 @@ static int corr_bwd_any(const T* in1, const T* in2, const T* gout, T* g1, T* g2,
     }
     RFN_REFUSE_NONDET(true, "rfn_corr_bwd", "corr_generic_bwd_kernel, floating-point atomics (no deterministic form)");
     const size_t bytes = sizeof(T) * (size_t)npix;
-    if (hipMemsetAsync(g1, 0, bytes, st) != hipSuccess || hipMemsetAsync(g2, 0, bytes, st) != hipSuccess)
-      return fail(RFN_ELAUNCH, "corr bwd: hipMemsetAsync failed");
+    // (kernels, not memset nodes: this backward may run inside a captured pass -- capi.hip zero_async)
+    if (int rc = zero_async(g1, bytes, st)) return rc;
+    if (int rc = zero_async(g2, bytes, st)) return rc;
     const long total = (long)p.B * p.patchH * p.patchW * p.oH * p.oW;
     hipLaunchKernelGGL((corr_generic_bwd_kernel<T>), dim3(flat_grid(total)), dim3(256), 0, st, in1, in2, gout, g1, g2, p, total);
     return check_launch("corr_generic_bwd_kernel");

@@ -78,9 +78,11 @@ __global__ __launch_bounds__(256) void warp_kernel(const float* __restrict__ x, 
 // (ATen grid_sampler_2d_backward: gix = sum_c g [ (ne - nw) (1 - ty) + (se - sw) ty ], giy likewise; taps outside the
 // image contribute zero).  d ix / d flow_x = ((W - 1) / 2) (2 / max(W - 1, 1)): 1 for W > 1, 0 for a one-pixel axis.
 // One thread per pixel and channel group: grad_x is a scatter (float atomics, pre-zeroed), grad_flow the sum over the
-// channel groups (atomics on 2 floats per pixel, pre-zeroed).
+// channel groups (atomics on 2 floats per pixel, pre-zeroed).  ONE_GROUP (C <= CG, the flow compositions and every map of at
+// most CG channels): the one group's thread owns its pixel's two grad_flow values and stores them -- no zero pass, no atomics,
+// and the bits of the atomic form (0 + sum; a pixel the atomic form skips keeps its 0).
 // grid: (ceil(HW/256), channel groups, B)
-template <int CG>
+template <int CG, bool ONE_GROUP>
 __global__ __launch_bounds__(256) void warp_bwd_kernel(const float* __restrict__ x, const float* __restrict__ flow,
                                                        const float* __restrict__ gout, float* __restrict__ gx_out,
                                                        float* __restrict__ gflow, int C, int H, int W) {
@@ -129,8 +131,13 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(const float* __restrict__
   }
   if (gflow) {
     float* gf = gflow + (size_t)n * 2 * HW;
-    if (W > 1 && finite) atomicAdd(gf + pix, gix);
-    if (H > 1 && finite) atomicAdd(gf + HW + pix, giy);
+    if constexpr (ONE_GROUP) {
+      gf[pix] = (W > 1 && finite) ? 0.0f + gix : 0.0f;            // (0 + x: what the add onto the zeroed buffer gives for x = -0)
+      gf[HW + pix] = (H > 1 && finite) ? 0.0f + giy : 0.0f;
+    } else {
+      if (W > 1 && finite) atomicAdd(gf + pix, gix);
+      if (H > 1 && finite) atomicAdd(gf + HW + pix, giy);
+    }
   }
 }
 
@@ -416,13 +423,19 @@ int rfn_warp_bwd_f32(const float* x, const float* flow, const float* grad_out, f
   RFN_REFUSE_NONDET(true, "rfn_warp_bwd_f32", "warp_bwd_kernel, fp32 atomics (no deterministic form)");
   hipStream_t s = (hipStream_t)stream;
   const size_t HW = (size_t)H * W;
-  if (grad_x && hipMemsetAsync(grad_x, 0, (size_t)B * C * HW * sizeof(float), s) != hipSuccess)
-    return fail(RFN_ELAUNCH, "rfn_warp_bwd_f32: memset");
-  if (grad_flow && hipMemsetAsync(grad_flow, 0, (size_t)B * 2 * HW * sizeof(float), s) != hipSuccess)
-    return fail(RFN_ELAUNCH, "rfn_warp_bwd_f32: memset");
   constexpr int CG = 32;
+  const bool one_group = C <= CG;
+  // zero-fill as kernels on the caller's stream, not memset nodes: the matcher's training step is captured into a hipGraph
+  // (capi.hip zero_async)
+  if (grad_x)
+    if (int rc = zero_async(grad_x, (size_t)B * C * HW * sizeof(float), s)) return rc;
+  if (grad_flow && !one_group)
+    if (int rc = zero_async(grad_flow, (size_t)B * 2 * HW * sizeof(float), s)) return rc;
   dim3 grid(cdiv((long)HW, 256), cdiv(C, CG), B);
-  hipLaunchKernelGGL((warp_bwd_kernel<CG>), grid, dim3(256), 0, s, x, flow, grad_out, grad_x, grad_flow, C, H, W);
+  if (one_group)
+    hipLaunchKernelGGL((warp_bwd_kernel<CG, true>), grid, dim3(256), 0, s, x, flow, grad_out, grad_x, grad_flow, C, H, W);
+  else
+    hipLaunchKernelGGL((warp_bwd_kernel<CG, false>), grid, dim3(256), 0, s, x, flow, grad_out, grad_x, grad_flow, C, H, W);
   return check_launch("warp_bwd_kernel");
 }
 

@@ -192,17 +192,21 @@ class GraphedStep:
     The first `warmup` calls run eagerly (they create every lazily cached constant / derived tensor); a capture that
     throws leaves the pass eager for good, like GraphedNoGrad."""
 
-    def __init__(self, fn, name, warmup=2, shared=None, capture_context=None, after_capture=None, on_replay=None):
+    def __init__(self, fn, name, warmup=2, shared=None, capture_context=None, after_capture=None, on_replay=None,
+                 before_capture=None):
         """`shared`: a dict the passes of ONE model share -- they are never live at the same time, so their graphs
         capture into one memory pool (held there; it dies with the model's graphs, never outlives them).  A pass that
         may run NEXT TO another one gets a pool of its own (shared=None).
         `capture_context`: callable returning a context manager the capture runs inside (e.g. the gradient buffer the
         captured backward kernels are to accumulate into).
         `after_capture()` -> anything, kept with the graph; `on_replay(that)` is called after every replay of it (the ranges of
-        the gradient buffer whose all-reduce is part of the graph: trainer.FlatGradBuffer.end_capture / replayed)."""
+        the gradient buffer whose all-reduce is part of the graph: trainer.FlatGradBuffer.end_capture / replayed).
+        `before_capture()`: called once before each capture, outside it (the matcher's whole training step hands the blocks its
+        eager warm-up steps left in the caching allocator back first: its private pool comes on top of them otherwise)."""
         self.fn, self.name, self.warmup = fn, name, warmup
         self.capture_context = capture_context
         self.after_capture, self.on_replay = after_capture, on_replay
+        self.before_capture = before_capture
         self._last = None
         self.shared = {} if shared is None else shared
         self.generation = 0
@@ -270,6 +274,8 @@ class GraphedStep:
         inputs = [t.clone() for t in tensors]
         cur = torch.cuda.current_stream()
         torch.cuda.synchronize()
+        if self.before_capture is not None:
+            self.before_capture()
         g = torch.cuda.CUDAGraph()
         import contextlib
         ctx = self.capture_context() if self.capture_context is not None else contextlib.nullcontext()

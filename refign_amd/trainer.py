@@ -379,6 +379,30 @@ class StallGuard:
                 os._exit(17)
 
 
+# The inputs of the matcher's graphed training step (Trainer(graph_step=True)), in the order the graph takes them.
+STEP_GRAPH_INPUTS = ("image_ref", "image_trg", "image_prime", "flow_prime", "mask_prime", "prime_trg_idx")
+
+
+def prime_idx_tensor(idx, device):
+    """`prime_trg_idx` as an int64 tensor on `device`.  A host list goes through pinned memory and a non-blocking copy, as
+    AlignmentModel.training_step sends it: no synchronisation (the pinned block is the caching host allocator's, which keeps it
+    until the copy has run).  A tensor is moved if it is elsewhere."""
+    device = torch.device(device)
+    if not torch.is_tensor(idx):
+        idx = torch.tensor([int(v) for v in idx], dtype=torch.int64)
+        if device.type == "cuda":
+            idx = idx.pin_memory()
+    return idx.to(device=device, dtype=torch.int64, non_blocking=True)
+
+
+def step_graph_inputs(batch, device):
+    """The tensors of a matcher batch in the order of STEP_GRAPH_INPUTS, `prime_trg_idx` as a device tensor."""
+    missing = [k for k in STEP_GRAPH_INPUTS if k not in batch]
+    if missing:
+        raise KeyError(f"Trainer(graph_step=True): the batch has no {missing}")
+    return tuple(prime_idx_tensor(batch[k], device) if k == "prime_trg_idx" else batch[k] for k in STEP_GRAPH_INPUTS)
+
+
 class Trainer:
     """`step(batch)` = one reference training_step including EMA, three backward passes, the single gradient all-reduce and
     the optimiser/scheduler step (a model with automatic_optimization, the matcher: training_step, one backward pass, optimizer
@@ -386,7 +410,8 @@ class Trainer:
     reference is driven through (run.py fit | validate | test | predict); `save_checkpoint` / `load_checkpoint`."""
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
-                 scaler_args=None, ckpt_path=None, deterministic=False, logger=None, log_every_n_steps=50, log_lr=True):
+                 scaler_args=None, ckpt_path=None, deterministic=False, logger=None, log_every_n_steps=50, log_lr=True,
+                 graph_step=False):
         """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
         entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
         scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
@@ -409,8 +434,18 @@ class Trainer:
         through a pinned mirror: the step does not wait for it.  step() hands finished rows to the logger and to
         `log_history`, a list of (step, {name: float}); validate() / test() log their results at the current global_step;
         fit() flushes before each validation, before each checkpoint and at its end, close() flushes and closes the file.
-        Several ranks: rank 0 records and writes.  Nothing of the logger goes into a checkpoint."""
+        Several ranks: rank 0 records and writes.  Nothing of the logger goes into a checkpoint.
+        `graph_step` (a model with automatic_optimization, the matcher; one rank): training_step, loss scaling and backward
+        replay from ONE hipGraph after two eager steps (_automatic_step, graphs.GraphedStep; `step_graph`); zeroing the
+        gradients and the optimizer tail stay eager.  The graph is dropped, and captured again after two further eager steps,
+        by load_checkpoint, validate / test / predict, model.train() / eval(), model.to() / half() and close().  With
+        RFN_HIP_GRAPH=0 or off a GPU the step runs eagerly.  ValueError for a model that steps itself (the UDA model: its passes
+        are graphed on their own)."""
         from .amp import parse_precision
+        self.step_graph = None
+        if graph_step and not getattr(model, "automatic_optimization", False):
+            raise ValueError("Trainer: graph_step=True is for a model with automatic_optimization (the matcher); the UDA "
+                             "model's passes are graphed on their own (graphs.GraphedStep in refign_amd/uda.py)")
         self.log_every_n_steps, self.log_lr = int(log_every_n_steps), bool(log_lr)
         if logger is not None and self.log_every_n_steps < 1:
             raise ValueError("Trainer: log_every_n_steps must be positive")
@@ -521,6 +556,11 @@ class Trainer:
         model._grad_buffer = self.grads                      # uda: second buffer for the concurrently running mixed pass
         model._scheduler = sch
         model._backward = self._backward
+        if graph_step:
+            from .graphs import GraphedStep
+            self._graph_logged = ()
+            self.step_graph = GraphedStep(self._graphed_pass, "matcher training step", before_capture=self._before_capture)
+            model.__dict__["_step_graph"] = self.step_graph   # AlignmentModel drops it with its own graphs (train / _apply / load)
         self.scaler = None
         if self.precision == "16":
             from .amp import LossScaler
@@ -614,12 +654,38 @@ class Trainer:
         from . import matching
         model = self.model
         self.grads.zero()
-        with self._autocast(), matching.no_zero_flow_check():
-            loss = model.training_step(batch, batch_idx)
-        self._backward(loss, last=True)
+        if self.step_graph is not None:
+            # training_step + loss scaling + backward as one replay; the outputs are copies the next replay does not touch, so
+            # the step log (which reads model.logged later in stream order) and the caller see this step's values
+            self._graph_batch_idx = batch_idx
+            out = self.step_graph(*step_graph_inputs(batch, self.grads.flat.device))
+            model.logged.update(zip(self._graph_logged, out))
+        else:
+            with self._autocast(), matching.no_zero_flow_check():
+                loss = model.training_step(batch, batch_idx)
+            self._backward(loss, last=True)
         model._optimizer.step()
         self.scheduler.step()
         model.global_step += 1
+
+    def _graphed_pass(self, *tensors):
+        """What `step_graph` runs eagerly, captures and replays: the eager branch of _automatic_step on the tensors of
+        STEP_GRAPH_INPUTS (`prime_trg_idx` always a device tensor here: no pinned temporary inside a capture) -> the scalar
+        tensors training_step logged, in the order it logged them (`_graph_logged`: their names)."""
+        from . import matching
+        model = self.model
+        before = dict(model.logged)
+        with self._autocast(), matching.no_zero_flow_check():
+            loss = model.training_step(dict(zip(STEP_GRAPH_INPUTS, tensors)), self._graph_batch_idx)
+        self._backward(loss, last=True)
+        names = tuple(k for k, v in model.logged.items() if torch.is_tensor(v) and v is not before.get(k))
+        self._graph_logged = names
+        return tuple(model.logged[k] for k in names)
+
+    def _before_capture(self):
+        """The blocks the eager warm-up steps left in the caching allocator go back to the device before the step is captured
+        into a pool of its own (the same activations a second time otherwise)."""
+        torch.cuda.empty_cache()
 
     # -- the record of the run -----------------------------------------------------------------------------------------
     def _record_row(self):
@@ -983,7 +1049,10 @@ class Trainer:
 
     def close(self):
         """Give the process its cyclic garbage collector back (step() runs with it disabled between its own collections)
-        and stop the stall guard; with a logger: hand over every recorded row and close its file."""
+        and stop the stall guard; with a logger: hand over every recorded row and close its file; with graph_step: release
+        the step's graph and its memory pool."""
+        if getattr(self, "step_graph", None) is not None:
+            self.step_graph.reset()
         if getattr(self, "logger", None) is not None:
             try:
                 self.flush_log()

@@ -5,7 +5,9 @@ W-bipath loss with visibility mask, Adam(lr 5e-5, wd 4e-4).  One step = Alignmen
 optimizer step on synthetic images / flows.  Prints ms/step and image-triplets/s.
     python tools/matcher_bench.py [--steps 10] [--b 6] [--size 520]
 --trainer: the same step through refign_amd.trainer.Trainer (Trainer.step: flat gradient buffer, device-side loss scaler,
-one-launch Adam, no host synchronisation) instead of the hand-driven loop with torch.amp.GradScaler."""
+one-launch Adam, no host synchronisation) instead of the hand-driven loop with torch.amp.GradScaler.
+--trainer --graph: Trainer(graph_step=True) -- training_step, loss scaling and backward replayed from one hipGraph after two
+eager steps; reports whether the graph was captured and how many of the timed steps were replays."""
 import argparse
 import os
 import sys
@@ -44,8 +46,11 @@ def main():
                          "fp16 autocast + loss scaling, correlation / warp / losses in fp32")
     ap.add_argument("--trainer", action="store_true",
                     help="drive the step through Trainer(model, precision=...).step instead of by hand")
+    ap.add_argument("--graph", action="store_true", help="with --trainer: Trainer(graph_step=True), the step replayed from a hipGraph")
     ap.add_argument("--census", action="store_true", help="torch.profiler on one step: ATen operators with device time, by input shape")
     args = ap.parse_args()
+    if args.graph and not args.trainer:
+        ap.error("--graph needs --trainer")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = config.build_model({"model": MODEL, "optimizer": OPTIM, "lr_scheduler": SCHED}).to(dev).train()
@@ -69,12 +74,16 @@ def main():
     trainer = None
     if args.trainer:
         from refign_amd.trainer import Trainer
-        trainer = Trainer(model, precision=16 if amp else None)
+        trainer = Trainer(model, precision=16 if amp else None, **({"graph_step": True} if args.graph else {}))
         batch["prime_trg_idx"] = torch.tensor(batch["prime_trg_idx"], device=dev)
+
+    replays = [0]
 
     def step():
         if trainer is not None:
             trainer.step(batch, 0)
+            if args.graph and trainer.step_graph.captured():
+                replays[0] += 1
             return model.logged["train_matching_loss"]
         opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
@@ -105,15 +114,32 @@ def main():
         for r in rows[:40]:
             print(f"{r[0]:8.2f} {r[1]:6d}  {r[2]:34s} {r[3]}")
         return
+    replays[0] = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     host = (time.perf_counter() - t0) / args.steps        # what the host needs to enqueue a step (== dt: host-bound)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    # one step at a time on an idle device: what the host needs for a step when no full queue holds it back (in the loop above
+    # a step whose device time exceeds its enqueue time makes the host wait for queue space, and the clock counts that wait)
+    alone_host = alone = 0.0
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        step()
+        t2 = time.perf_counter()
+        torch.cuda.synchronize()
+        alone_host, alone = alone_host + (t2 - t1) / 5, alone + (time.perf_counter() - t1) / 5
     how = " through Trainer.step" if trainer is not None else ""
+    if args.graph:
+        how += " (graph_step)"
     print(f"matcher training step{how} b={b} {S}x{S} {args.precision}: {dt * 1e3:.1f} ms/step (host enqueue {host * 1e3:.1f} ms), {b / dt:.2f} image-triplets/s, "
           f"loss {float(loss):.3f}, max mem {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
+    print(f"one step at a time on an idle device: {alone * 1e3:.1f} ms/step, host enqueue {alone_host * 1e3:.1f} ms")
+    if args.graph:
+        print(f"step graph captured: {trainer.step_graph.captured()}, replayed {replays[0]} of {args.steps} timed steps, "
+              f"max reserved {torch.cuda.max_memory_reserved() / 2 ** 30:.1f} GiB")
     from refign_amd import mfma as _mfma
     print("library_fallbacks:", _mfma.library_summary())
     if trainer is not None:
