@@ -867,6 +867,34 @@ int rfn_multi_adam_f32(const void* table, int nchunks, const float* group_args, 
 int rfn_multi_adam_amp_f32(const void* table, int nchunks, const double* group_args, int ngroups, const float* found_inf,
                            const float* step, rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Photometric augmentation of the matcher's image_prime (csrc/photometric.hip, refign_amd/photometric.py; additions to
+ * ABI 5): ColorJitter (brightness, contrast, saturation; no hue) -> ChannelShuffle -> Gaussian blur (at most 7 x 7) ->
+ * u8 / 255 -> Normalize over a batch of uint8 images (B, 3, h, w), one parameter record per sample, the sample index
+ * on the grid.  Integer atomics only (legal under rfn_set_deterministic(1)); the jittered uint8 image is never stored.
+ *   records  DEVICE array of B x rfn_photometric_record_words() 32-bit words:
+ *              [0..3]   int    the order of the four steps: 0 brightness, 1 contrast, 2 saturation, 3 hue (never applied)
+ *              [4..7]   int    1 where the step has a factor (word 7 is 0)
+ *              [8..10]  float  fp32(f) of brightness, contrast, saturation;  [11..13] float  fp32(1.0 - f) of each
+ *              [14..16] int    the channel permutation: out[c] = in[perm[c]]
+ *              [17]     int    1: blur
+ *              [18..20] float  Normalize's mean;  [21..23] float  its std
+ *              [24..72] float  the 7 x 7 blur weights, row-major
+ *              [73..79] unused
+ *            Step and channel numbers are reduced into their range on the device (a record cannot address outside the image).
+ *   rfn_photometric_gray_sums_u8  sums[b] (DEVICE, B 64-bit counters; zeroed by this call with a kernel) = the integer sum
+ *            over the image of gray() after the steps that precede contrast in the sample's order; 0 for a sample
+ *            without a contrast step.
+ *   rfn_photometric_apply_u8      out (B, 3, h, w) fp32.  The contrast mean is (float)sums[b] / (float)(h * w); sums may be
+ *            NULL when no record has a contrast step (a contrast step then blends with 0).
+ * Errors (nothing is launched): a null pointer, B < 1 or > 65535, h or w < 1, h * w >= 2^31 / 3.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_photometric_record_words(void);
+int rfn_photometric_gray_sums_u8(const void* image, const void* records, int B, int h, int w, unsigned long* sums,
+                                 rfn_stream_t stream);
+int rfn_photometric_apply_u8(const void* image, const void* records, const unsigned long* sums, int B, int h, int w, float* out,
+                             rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

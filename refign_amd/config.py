@@ -293,3 +293,105 @@ def warp_supervision_plan(cfg, split="train", dataset="MegaDepth"):
     if composite is None:
         raise OutOfScopeError(f"warp_supervision_plan: no data_modules.transforms.CompositeFlow {where}")
     return {"composite": composite, "crop": crop, "min_fraction_valid_corr": min_fraction}
+
+
+# the photometric chain's transforms in the order the reference's configs apply them (refign_amd/photometric.py)
+_PHOTOMETRIC_ORDER = ("ColorJitter", "ChannelShuffle", "RandomGaussianBlur")
+_PHOTOMETRIC_ARGS = {"ColorJitter": {"apply_keys", "brightness", "contrast", "saturation", "hue"}, "ChannelShuffle": {"apply_keys"},
+                     "RandomGaussianBlur": {"apply_keys", "p", "kernel_size", "sigma"}}
+
+
+def photometric_plan(cfg, split="train", dataset="MegaDepth"):
+    """The photometric half of `data.init_args.load_config[split][dataset]`'s pipeline -- transforms.ColorJitter,
+    ChannelShuffle and RandomGaussianBlur on the uint8 image_prime, and the Normalize that follows the conversion -- as the
+    plan of refign_amd.photometric.draw / flowsynth.WarpSupervision(plan, photometric=):
+      brightness / contrast / saturation   the range (lo, hi) the factor is drawn from, [max(0, 1 - v), 1 + v] for a number v or
+                                the pair as given; None where ColorJitter has no such step (0, or a range that is 1 only)
+      shuffle                   whether the section has a ChannelShuffle
+      blur                      None, or {"p", "kernel_size", "sigma": (lo, hi)} of RandomGaussianBlur (p 0.2, sigma (0.1, 2.0)
+                                when absent, as the classes default them)
+      mean / std                Normalize's statistics (ImageNet's by default)
+    Every other transform of the section is passed over.  OutOfScopeError names what cannot be carried: a section without
+    ColorJitter or with one of the three twice, `hue` other than 0 (the hue step's HSV round trip is left out), apply_keys other
+    than ['image_prime'], an even kernel size or one above 7, the three in any order other than ColorJitter -> ChannelShuffle ->
+    RandomGaussianBlur, any of them after ConvertImageDtype (the kernel works on the uint8 image), an unknown keyword.
+    ingest_plan keeps refusing such a section."""
+    from .datastep import IMNET_MEAN, IMNET_STD
+    from .photometric import MAX_KERNEL
+    try:
+        sec = cfg["data"]["init_args"]["load_config"][split][dataset]
+    except (KeyError, TypeError) as e:
+        raise KeyError(f"photometric_plan: no data.init_args.load_config.{split}.{dataset} in this config") from e
+    where = f"({split}.{dataset})"
+    if not isinstance(sec, dict):
+        raise OutOfScopeError(f"photometric_plan: {where} is a list of sections: pass a config that holds the one meant")
+    plan = {"brightness": None, "contrast": None, "saturation": None, "shuffle": False, "blur": None,
+            "mean": tuple(IMNET_MEAN), "std": tuple(IMNET_STD)}
+
+    def jitter_range(name, value):
+        """ColorJitter._check_input for the three steps centred on 1"""
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise OutOfScopeError(f"photometric_plan: ColorJitter with {name} {value!r} {where}: a number must not be negative")
+            lo, hi = max(1.0 - float(value), 0.0), 1.0 + float(value)
+        elif isinstance(value, (list, tuple)) and len(value) == 2 and 0 <= value[0] <= value[1]:
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            raise OutOfScopeError(f"photometric_plan: ColorJitter with {name} {value!r} {where}: a number or a pair 0 <= lo <= hi")
+        return None if lo == hi == 1.0 else (lo, hi)
+
+    stage, seen, converted = -1, set(), False
+    for spec in sec.get("transforms") or []:
+        path = spec["class_path"] if is_spec(spec) else str(spec)
+        name, args = path.rsplit(".", 1)[-1], (spec.get("init_args") or {}) if is_spec(spec) else {}
+        if not path.startswith("data_modules.transforms."):
+            continue
+        if name == "ConvertImageDtype":
+            converted = True
+        elif name == "Normalize":
+            plan["mean"], plan["std"] = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
+        if name not in _PHOTOMETRIC_ORDER:
+            continue
+        if converted:
+            raise OutOfScopeError(f"photometric_plan: {name} after ConvertImageDtype {where}: the device chain works on the uint8 image")
+        if name in seen:
+            raise OutOfScopeError(f"photometric_plan: a second {name} {where}")
+        if _PHOTOMETRIC_ORDER.index(name) < stage:
+            raise OutOfScopeError(f"photometric_plan: {name} {where} comes out of the order {' -> '.join(_PHOTOMETRIC_ORDER)}")
+        stage = _PHOTOMETRIC_ORDER.index(name)
+        seen.add(name)
+        if name == "ColorJitter":
+            hue = args.get("hue", 0)
+            if isinstance(hue, (list, tuple)) and len(hue) == 2 and hue[0] == hue[1] == 0:
+                hue = 0
+            if isinstance(hue, (list, tuple)) or hue != 0:
+                raise OutOfScopeError(f"photometric_plan: ColorJitter with hue {hue!r} {where}: the hue step is outside the device "
+                                      f"chain (brightness, contrast, saturation)")
+        keys = args.get("apply_keys", "all")
+        if isinstance(keys, str) or list(keys or []) != ["image_prime"]:
+            raise OutOfScopeError(f"photometric_plan: {name} with apply_keys {keys!r} {where}: "
+                                  f"['image_prime'] is what the device chain takes")
+        extra = set(args) - _PHOTOMETRIC_ARGS[name]
+        if extra:
+            raise OutOfScopeError(f"photometric_plan: {name} with {sorted(extra)} {where}")
+        if name == "ColorJitter":
+            for k in ("brightness", "contrast", "saturation"):
+                plan[k] = jitter_range(k, args.get(k, 0))
+        elif name == "ChannelShuffle":
+            plan["shuffle"] = True
+        else:
+            ksize = args.get("kernel_size")
+            if isinstance(ksize, (list, tuple)) and len(ksize) == 2 and ksize[0] == ksize[1]:
+                ksize = ksize[0]
+            if not isinstance(ksize, int) or ksize < 1 or ksize % 2 == 0 or ksize > MAX_KERNEL:
+                raise OutOfScopeError(f"photometric_plan: RandomGaussianBlur with kernel_size {args.get('kernel_size')!r} {where}: "
+                                      f"one odd size of at most {MAX_KERNEL}")
+            sigma = args.get("sigma", (0.1, 2.0))
+            sigma = (float(sigma), float(sigma)) if isinstance(sigma, (int, float)) else tuple(float(v) for v in sigma)
+            if len(sigma) != 2 or not 0.0 < sigma[0] <= sigma[1]:
+                raise OutOfScopeError(f"photometric_plan: RandomGaussianBlur with sigma {args.get('sigma')!r} {where}: 0 < lo <= hi")
+            plan["blur"] = {"p": float(args.get("p", 0.2)), "kernel_size": ksize, "sigma": sigma}
+    if "ColorJitter" not in seen:
+        raise OutOfScopeError(f"photometric_plan: no data_modules.transforms.ColorJitter {where}: the chain's draws begin with its "
+                              f"step order")
+    return plan

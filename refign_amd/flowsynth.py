@@ -300,18 +300,34 @@ class WarpSupervision:
     plan: config.warp_supervision_plan(cfg) -- {"composite": draw_composite's keywords, "crop": (ch, cw) or None,
     "min_fraction_valid_corr": f}.  __call__(sample) takes device tensors image, image_ref, image_prime ((B, 3, h, w) each) and
     optionally image_prime_idx, and returns the keys AlignmentModel.training_step reads: image_ref, image_trg, image_prime,
-    flow_prime, mask_prime, prime_trg_idx."""
+    flow_prime, mask_prime, prime_trg_idx.
+    photometric: config.photometric_plan(cfg) or None.  With a plan the pipeline's photometric half runs in front: image_prime
+    is then the uint8 (B, 3, h, w) device tensor of the load-time resize, per sample the draws are photometric.draw followed by
+    draw_composite (the reference's order: each sample runs its whole pipeline), and the batch goes through photometric.apply
+    into synthesize.  With None every launch and every draw is as it was."""
 
-    def __init__(self, plan):
+    def __init__(self, plan, photometric=None):
         self.composite = dict(plan["composite"])
         self.crop = None if plan.get("crop") is None else tuple(plan["crop"])
         self.min_fraction_valid_corr = float(plan.get("min_fraction_valid_corr", 0.1))
+        self.photometric = None if photometric is None else dict(photometric)
 
     def __call__(self, sample):
         prime = sample["image_prime"]
         prime = prime if prime.dim() == 4 else prime.unsqueeze(0)
         B, _, h, w = prime.shape
-        params = [draw_composite(h, w, **self.composite) for _ in range(B)]
+        if self.photometric is None:
+            params = [draw_composite(h, w, **self.composite) for _ in range(B)]
+        else:
+            from . import photometric
+            if not (prime.is_cuda and prime.dtype == torch.uint8):
+                raise RuntimeError("flowsynth.WarpSupervision: with a photometric plan image_prime must be the uint8 (B, 3, h, w) "
+                                   "HIP (cuda:N) tensor the chain starts from")
+            photo, params = [], []
+            for _ in range(B):
+                photo.append(photometric.draw(self.photometric))
+                params.append(draw_composite(h, w, **self.composite))
+            prime = photometric.apply(prime, photo)
         img, flow, mask = synthesize(prime, params, self.crop, self.min_fraction_valid_corr)
         crop = (lambda x: x) if self.crop is None else (lambda x: center_crop(x, self.crop).contiguous())
         both = lambda x: crop(x if x.dim() == 4 else x.unsqueeze(0))  # noqa: E731
