@@ -869,18 +869,19 @@ int rfn_multi_adam_amp_f32(const void* table, int nchunks, const double* group_a
 
 /* ------------------------------------------------------------------------------------------------------------
  * Photometric augmentation of the matcher's image_prime (csrc/photometric.hip, refign_amd/photometric.py; additions to
- * ABI 5): ColorJitter (brightness, contrast, saturation; no hue) -> ChannelShuffle -> Gaussian blur (at most 7 x 7) ->
+ * ABI 5): ColorJitter (brightness, contrast, saturation, hue) -> ChannelShuffle -> Gaussian blur (at most 7 x 7) ->
  * u8 / 255 -> Normalize over a batch of uint8 images (B, 3, h, w), one parameter record per sample, the sample index
  * on the grid.  Integer atomics only (legal under rfn_set_deterministic(1)); the jittered uint8 image is never stored.
  *   records  DEVICE array of B x rfn_photometric_record_words() 32-bit words:
- *              [0..3]   int    the order of the four steps: 0 brightness, 1 contrast, 2 saturation, 3 hue (never applied)
- *              [4..7]   int    1 where the step has a factor (word 7 is 0)
+ *              [0..3]   int    the order of the four steps: 0 brightness, 1 contrast, 2 saturation, 3 hue
+ *              [4..7]   int    1 where the step has a factor (word 7: the hue step; 0 in every record made before it existed)
  *              [8..10]  float  fp32(f) of brightness, contrast, saturation;  [11..13] float  fp32(1.0 - f) of each
  *              [14..16] int    the channel permutation: out[c] = in[perm[c]]
  *              [17]     int    1: blur
  *              [18..20] float  Normalize's mean;  [21..23] float  its std
  *              [24..72] float  the 7 x 7 blur weights, row-major
- *              [73..79] unused
+ *              [73]     float  the hue step's factor (read when word 7 is set)
+ *              [74..79] unused
  *            Step and channel numbers are reduced into their range on the device (a record cannot address outside the image).
  *   rfn_photometric_gray_sums_u8  sums[b] (DEVICE, B 64-bit counters; zeroed by this call with a kernel) = the integer sum
  *            over the image of gray() after the steps that precede contrast in the sample's order; 0 for a sample
@@ -894,6 +895,30 @@ int rfn_photometric_gray_sums_u8(const void* image, const void* records, int B, 
                                  rfn_stream_t stream);
 int rfn_photometric_apply_u8(const void* image, const void* records, const unsigned long* sums, int B, int h, int w, float* out,
                              rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The labelled RobotCar section's geometry (configs/cityscapes_robotcar/refign_*.yaml: RandomRotation -> ToTensor -> RandomCrop
+ * -> ColorJitter -> RandomHorizontalFlip -> ConvertImageDtype -> Normalize); additions to ABI 5, nothing existing changed.
+ *   rfn_rotate_nearest_u8  PIL.Image.rotate(angle, NEAREST, expand=False) of a uint8 (C, H, W) image, C <= 4 (csrc/rotate.hip):
+ *            a0 .. a5 are Pillow's 16.16 fixed-point affine coefficients (Geometry.c `affine_fixed`; the host makes them in double:
+ *            refign_amd/resample.py), out[c][y][x] = src[c][yin][xin] with xin = (a2 + a1 y + a0 x) >> 16, yin = (a5 + a4 y +
+ *            a3 x) >> 16 where that lies inside the image, `fill` elsewhere; outside (H, W) bytes, nullable: 1 there, else 0.
+ *            Errors: a null or in-place pointer, H or W > 32767, fill outside 0 ... 255, coefficients with which |xx| or |yy| could
+ *            reach 2^31 at this size.
+ *   rfn_photometric_*_geom_u8  the two photometric passes with a GATHER in front of the chain: image is (B, 3, H, W), the passes
+ *            run over the (h, w) crop of the rotated image, mirrored where asked, which is never stored.  geom: DEVICE array of
+ *            B x 12 32-bit ints: [0..5] a0 .. a5 as above, [6] top, [7] left, [8] flip, [9..11] unused.  A pixel whose source lies
+ *            outside is the fill 0: it runs through the chain, counts in the contrast mean's h * w, and its output is 0.0f in
+ *            all three channels (Normalize's normalize_mask write, data_modules/transforms.py:475-495).  The record's blur flag
+ *            is not read (no blur here).  Loads are bounds-checked on the device; that the crop lies in the image and the
+ *            coordinates stay below 2^31 is the host's to check.  Errors as above, and H or W > 32767, h > H, w > W.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_rotate_nearest_u8(const void* src, int C, int H, int W, int a0, int a1, int a2, int a3, int a4, int a5, int fill,
+                          void* out, void* outside, rfn_stream_t stream);
+int rfn_photometric_gray_sums_geom_u8(const void* image, const void* records, const void* geom, int B, int H, int W, int h, int w,
+                                      unsigned long* sums, rfn_stream_t stream);
+int rfn_photometric_apply_geom_u8(const void* image, const void* records, const void* geom, const unsigned long* sums, int B, int H,
+                                  int W, int h, int w, float* out, rfn_stream_t stream);
 
 #ifdef __cplusplus
 }

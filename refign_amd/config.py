@@ -395,3 +395,107 @@ def photometric_plan(cfg, split="train", dataset="MegaDepth"):
         raise OutOfScopeError(f"photometric_plan: no data_modules.transforms.ColorJitter {where}: the chain's draws begin with its "
                               f"step order")
     return plan
+
+
+# the labelled RobotCar section's chain (configs/cityscapes_robotcar/refign_*.yaml), in its order
+_SECTION_ORDER = ("RandomRotation", "ToTensor", "RandomCrop", "ColorJitter", "RandomHorizontalFlip", "ConvertImageDtype", "Normalize")
+_SECTION_ARGS = {"RandomRotation": {"apply_keys", "degrees", "interpolation", "resample", "expand", "center", "fill"},
+                 "ToTensor": set(), "RandomCrop": {"size", "cat_max_ratio"},
+                 "ColorJitter": {"apply_keys", "brightness", "contrast", "saturation", "hue"}, "RandomHorizontalFlip": {"p"},
+                 "ConvertImageDtype": set(), "Normalize": {"mean", "std"}}
+
+
+def train_section_plan(cfg, dataset, section=None):
+    """One training section `data.init_args.load_config.train[dataset]` -- `section` indexes a list of sections, as RobotCar has
+    (labelled, then the adaptation pairs) -- whose pipeline is a sub-sequence of
+        RandomRotation -> ToTensor -> RandomCrop -> ColorJitter -> RandomHorizontalFlip -> ConvertImageDtype -> Normalize
+    as the plan of datastep.RotatedLabelledSampler: ingest_plan's keys (dims, crop_size, cat_max_ratio, flip, mean, std,
+    load_keys, ...; ingest_plan itself reads a section without the two new transforms) plus
+      rotation   {"degrees": (lo, hi)} of RandomRotation (a number d: (-d, d)), or None
+      jitter     photometric.draw's plan of ColorJitter: brightness / contrast / saturation as photometric_plan gives them, "hue":
+                 (lo, hi) -- (-v, v) for a number v in [0, 0.5], or the pair within [-0.5, 0.5] -- or None, "shuffle": False,
+                 "blur": None; or None without a ColorJitter
+    A keyword is read from `init_args` alone, as the reference's instantiate_class reads it: the RobotCar files indent RandomCrop's
+    `cat_max_ratio: 0.75` NEXT to init_args, where it is dropped -- the plan then says 1.0, which is what the reference runs.
+    OutOfScopeError names the cause: RandomRotation with expand, center, fill or an interpolation other than the defaults
+    (NEAREST, no expand, the image centre, fill 0) or with apply_keys other than all; ColorJitter with apply_keys other than all;
+    the transforms in another order or one of them twice; any other transform or keyword."""
+    from .datastep import IMNET_MEAN, IMNET_STD
+    try:
+        sec = cfg["data"]["init_args"]["load_config"]["train"][dataset]
+    except (KeyError, TypeError) as e:
+        raise KeyError(f"train_section_plan: no data.init_args.load_config.train.{dataset} in this config") from e
+    where = f"(train.{dataset})" if section is None else f"(train.{dataset}[{section}])"
+    if isinstance(sec, list):
+        if section is None:
+            raise OutOfScopeError(f"train_section_plan: {where} is a list of {len(sec)} sections: say which with section=")
+        if not 0 <= int(section) < len(sec):
+            raise KeyError(f"train_section_plan: no section {section} in train.{dataset} ({len(sec)} sections)")
+        sec = sec[int(section)]
+    elif section not in (None, 0):
+        raise KeyError(f"train_section_plan: train.{dataset} is one section, not a list")
+    pair = lambda v: v if isinstance(v, int) else tuple(int(a) for a in v)  # noqa: E731
+    plan = {"dims": pair(sec["dims"]) if sec.get("dims") is not None else None, "resize": None, "img_only": False,
+            "only_if_larger": False, "crop_size": None, "cat_max_ratio": 1.0, "flip": 0.0, "mean": tuple(IMNET_MEAN),
+            "std": tuple(IMNET_STD), "load_keys": list(sec.get("load_keys") or []), "interpolation": "bilinear",
+            "dims_interpolation": "bilinear", "pad": None, "rotation": None, "jitter": None}
+
+    def span(name, value, centre, lo_bound, hi_bound):
+        """torchvision's _check_input / _setup_angle: a number v -> (centre - v, centre + v), a pair as given"""
+        if isinstance(value, (int, float)) and not isinstance(value, bool):
+            if value < 0:
+                raise OutOfScopeError(f"train_section_plan: {name} {value!r} {where}: a number must not be negative")
+            lo, hi = centre - float(value), centre + float(value)
+            if name != "degrees" and centre == 1.0:
+                lo = max(lo, 0.0)
+        elif isinstance(value, (list, tuple)) and len(value) == 2 and value[0] <= value[1]:
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            raise OutOfScopeError(f"train_section_plan: {name} {value!r} {where}: a number or a pair lo <= hi")
+        if lo < lo_bound or hi > hi_bound:
+            raise OutOfScopeError(f"train_section_plan: {name} {value!r} {where}: outside [{lo_bound}, {hi_bound}]")
+        return None if lo == hi == centre else (lo, hi)
+
+    stage = -1
+    for spec in sec.get("transforms") or []:
+        path = spec["class_path"] if is_spec(spec) else str(spec)
+        name, args = path.rsplit(".", 1)[-1], (spec.get("init_args") or {}) if is_spec(spec) else {}
+        if not path.startswith("data_modules.transforms.") or name not in _SECTION_ORDER:
+            raise OutOfScopeError(f"train_section_plan: {path} {where} is outside the device data step "
+                                  f"({' / '.join(_SECTION_ORDER)})")
+        if _SECTION_ORDER.index(name) <= stage:
+            raise OutOfScopeError(f"train_section_plan: {path} {where} comes out of the order {' -> '.join(_SECTION_ORDER)}")
+        stage = _SECTION_ORDER.index(name)
+        extra = set(args) - _SECTION_ARGS[name]
+        if extra:
+            raise OutOfScopeError(f"train_section_plan: {path} {where} with {sorted(extra)} is outside the device data step")
+        if name in ("RandomRotation", "ColorJitter") and args.get("apply_keys", "all") != "all":
+            raise OutOfScopeError(f"train_section_plan: {name} with apply_keys {args['apply_keys']!r} {where}: the device path "
+                                  f"takes it on all keys")
+        if name == "RandomRotation":
+            is_zero = lambda v: isinstance(v, int) and not isinstance(v, bool) and v == 0  # noqa: E731
+            is_nearest = lambda v: is_zero(v) or (isinstance(v, str) and v.lower() == "nearest")  # noqa: E731
+            defaults = {"expand": args.get("expand") in (None, False),
+                        "center": args.get("center") is None,
+                        "fill": args.get("fill") is None or is_zero(args.get("fill")),
+                        "interpolation": args.get("interpolation") is None or is_nearest(args.get("interpolation")),
+                        # older torchvision's name for the filter; its default was False
+                        "resample": args.get("resample") in (None, False) or is_nearest(args.get("resample"))}
+            for k, is_default in defaults.items():
+                if not is_default:
+                    raise OutOfScopeError(f"train_section_plan: RandomRotation with {k} {args[k]!r} {where}: the device rotation is "
+                                          f"Pillow's NEAREST about the centre, no expand, fill 0")
+            if "degrees" not in args:
+                raise OutOfScopeError(f"train_section_plan: RandomRotation without degrees {where}")
+            deg = span("degrees", args["degrees"], 0.0, -360.0, 360.0)
+            plan["rotation"] = {"degrees": deg if deg is not None else (0.0, 0.0)}
+        elif name == "RandomCrop":
+            plan["crop_size"], plan["cat_max_ratio"] = pair(args["size"]), float(args.get("cat_max_ratio", 1.0))
+        elif name == "ColorJitter":
+            plan["jitter"] = {k: span(k, args.get(k, 0), 1.0, 0.0, float("inf")) for k in ("brightness", "contrast", "saturation")}
+            plan["jitter"].update(hue=span("hue", args.get("hue", 0), 0.0, -0.5, 0.5), shuffle=False, blur=None)
+        elif name == "RandomHorizontalFlip":
+            plan["flip"] = float(args.get("p", 0.5))
+        elif name == "Normalize":
+            plan["mean"], plan["std"] = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
+    return plan

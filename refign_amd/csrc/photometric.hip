@@ -12,6 +12,14 @@
 //                                pixel packed into one word; the jitter is applied while staging, BORDER_REFLECT_101 at the
 //                                image's border) and takes the 49 taps from there in row-major order in fp32, then rintf.
 //                                Samples with and without blur share the launch: the branch is uniform per workgroup.
+// The hue step (step 3; word 7 of the record its flag, word 73 its factor) is adjust_hue of a uint8 image: u8 / 255, _rgb2hsv,
+// h = (h + factor) % 1.0, _hsv2rgb, (x * 255) truncated -- pm_hue below.
+// With a PmGeom per sample (the *_geom entry points) both kernels GATHER their input pixel through a rotation, a crop and a
+// mirror in front of the chain: output pixel (oy, ox) of the (h, w) crop reads pixel (top + oy, left + ox') of the image
+// rotated with Pillow's NEAREST fixed-point affine transform (csrc/rotate.hip: the same six integers), ox' = w - 1 - ox when
+// mirrored.  Where that falls outside the (H, W) source the pixel is the fill 0, runs through the chain like any other, counts
+// in the contrast mean, and the output is 0.0 in all three channels (Normalize's normalize_mask write).  The rotated image is
+// never stored.  No blur there (its tile assumes unrotated neighbours): the record's blur flag is not read.
 // The arithmetic is torchvision's tensor path for uint8 images restated: every fp32 operation on its own (no contraction),
 // products summed left to right, truncation to uint8 after every step.  No floating-point atomics; the jittered uint8 image is
 // never written to memory.  Byte loads, lanes along W (64 contiguous bytes per wave and plane); 256-byte fp32 stores per wave.
@@ -27,16 +35,25 @@ constexpr int kPmRowsPerThread = kPmTileH / (kPmThreads / kPmTileW);
 constexpr int kPmMaxSumBlocks = 1024;
 
 struct PmRecord {
-  int order[4];                                // 0 brightness, 1 contrast, 2 saturation, 3 hue (never applied)
+  int order[4];                                // 0 brightness, 1 contrast, 2 saturation, 3 hue
   int present[4];
   float f[3], g[3];                            // fp32(f), fp32(1.0 - f)
   int perm[3];
   int blur;
   float mean[3], sd[3];
   float k[kPmK * kPmK];
-  int unused[7];
+  float hue;                                   // the hue step's factor (present[3])
+  int unused[6];
 };
 static_assert(sizeof(PmRecord) == kPmWords * 4, "the record of include/refign_hip.h");
+
+// the gather in front of the chain (include/refign_hip.h: 12 words per sample)
+struct PmGeom {
+  int a[6];                                    // Pillow's fixed-point affine coefficients: csrc/rotate.hip
+  int top, left, flip;
+  int unused[3];
+};
+static_assert(sizeof(PmGeom) == 12 * 4, "the geometry record of include/refign_hip.h");
 
 // _blend(a, b, f) of a uint8 image: (f * a + (1 - f) * b).clamp(0, 255).to(uint8)
 __device__ __forceinline__ int pm_blend(int a, float b, float f, float g) {
@@ -49,13 +66,51 @@ __device__ __forceinline__ int pm_gray(int r, int g, int b) {
   return (int)(0.2989f * (float)r + 0.587f * (float)g + 0.114f * (float)b);
 }
 
+// adjust_hue of a uint8 pixel (functional_tensor.py: _rgb2hsv, (h + factor) % 1.0, _hsv2rgb), one fp32 operation at a time.
+// The three masked terms of h exclude one another, so their sum is the one selected; the einsum of _hsv2rgb adds five zeros.
+// A function of its own (the pixel packed into one word each way: no scratch): inlined into the four unrolled steps of both
+// staging loops it took the apply kernel from 78 to 105 SGPRs, below the eight waves per SIMD it had; only samples with the
+// step call it.
+__device__ __noinline__ int pm_hue_packed(float factor, int rgb) {
+  const int ri = rgb & 255, gi = (rgb >> 8) & 255, bi = rgb >> 16;
+  const float r = (float)ri / 255.0f, g = (float)gi / 255.0f, b = (float)bi / 255.0f;
+  const float maxc = fmaxf(fmaxf(r, g), b), minc = fminf(fminf(r, g), b);
+  const bool eqc = maxc == minc;
+  const float cr = maxc - minc;
+  const float s = cr / (eqc ? 1.0f : maxc);
+  const float div = eqc ? 1.0f : cr;
+  const float rc = (maxc - r) / div, gc = (maxc - g) / div, bc = (maxc - b) / div;
+  float h = maxc == r ? bc - gc : (maxc == g ? (2.0f + rc) - bc : (4.0f + gc) - rc);
+  h = fmodf(h / 6.0f + 1.0f, 1.0f);
+  h = fmodf(h + factor, 1.0f);                 // torch.remainder: the sign of the divisor
+  if (h < 0.0f) h = h + 1.0f;
+  const float h6 = h * 6.0f, fl = floorf(h6), f = h6 - fl;
+  const float v = maxc;
+  const float p = fminf(fmaxf(v * (1.0f - s), 0.0f), 1.0f);
+  const float q = fminf(fmaxf(v * (1.0f - s * f), 0.0f), 1.0f);
+  const float t = fminf(fmaxf(v * (1.0f - s * (1.0f - f)), 0.0f), 1.0f);
+  const int i = (int)fl % 6;                   // fl in 0 ... 6
+  const float ro = i == 0 ? v : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : v))));
+  const float go = i == 0 ? t : (i == 1 ? v : (i == 2 ? v : (i == 3 ? q : (i == 4 ? p : p))));
+  const float bo = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? v : (i == 4 ? v : q))));
+  return (int)(ro * 255.0f) | ((int)(go * 255.0f) << 8) | ((int)(bo * 255.0f) << 16);
+}
+__device__ __forceinline__ void pm_hue(float factor, int& r, int& g, int& b) {
+  const int o = pm_hue_packed(factor, r | (g << 8) | (b << 16));
+  r = o & 255, g = (o >> 8) & 255, b = o >> 16;
+}
+
 // the jitter steps in the sample's order; UNTIL_CONTRAST: stop in front of the contrast step (what its mean is taken of)
 template <bool UNTIL_CONTRAST>
 __device__ __forceinline__ void pm_steps(const PmRecord& p, float gray_mean, int& r, int& g, int& b) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int s = p.order[i] & 3;
-    if (s == 3 || !p.present[s]) continue;
+    if (!p.present[s]) continue;
+    if (s == 3) {
+      pm_hue(p.hue, r, g, b);
+      continue;
+    }
     const float f = p.f[s], q = p.g[s];
     if (s == 0) {
       r = pm_blend(r, 0.0f, f, q), g = pm_blend(g, 0.0f, f, q), b = pm_blend(b, 0.0f, f, q);
@@ -81,17 +136,43 @@ __device__ __forceinline__ int pm_reflect(int i, int n) {
 // ConvertImageDtype and Normalize of one uint8 value
 __device__ __forceinline__ float pm_norm(int u, float mean, float sd) { return ((float)u / 255.0f - mean) / sd; }
 
+// pixel (oy, ox) of the (h, w) crop of the rotated, mirrored (H, W) image `img`: false (and the fill 0) where the source falls
+// outside.  The products wrap as unsigned numbers (the host refuses sizes at which they could pass 2^31) and the load is
+// bounds-checked: no geometry record can address outside the image.
+__device__ __forceinline__ bool pm_gather(const PmGeom& q, const unsigned char* __restrict__ img, long plane, int H, int W, int w,
+                                          int oy, int ox, int& r, int& g, int& b) {
+  const unsigned y = (unsigned)(q.top + oy), x = (unsigned)(q.left + (q.flip ? w - 1 - ox : ox));
+  const int xin = (int)((unsigned)q.a[2] + (unsigned)q.a[1] * y + (unsigned)q.a[0] * x) >> 16;
+  const int yin = (int)((unsigned)q.a[5] + (unsigned)q.a[4] * y + (unsigned)q.a[3] * x) >> 16;
+  if (xin < 0 || xin >= W || yin < 0 || yin >= H) {
+    r = g = b = 0;
+    return false;
+  }
+  const long i = (long)yin * W + xin;
+  r = img[i], g = img[plane + i], b = img[2 * plane + i];
+  return true;
+}
+
+// GEOM: the image is (B, 3, H, W) and the pass runs over the (h, w) crop gathered through geom[bi]; else H = h, W = w
+template <bool GEOM>
 __global__ __launch_bounds__(kPmThreads) void photometric_gray_sum_kernel(const unsigned char* __restrict__ image,
-                                                                         const PmRecord* __restrict__ records, int h, int w,
+                                                                         const PmRecord* __restrict__ records,
+                                                                         const PmGeom* __restrict__ geom, int H, int W, int h, int w,
                                                                          unsigned long long* __restrict__ sums) {
   const int bi = blockIdx.y;
   const PmRecord& p = records[bi];
   if (!p.present[1]) return;                   // (uniform per workgroup)
-  const long plane = (long)h * w;
-  const unsigned char* __restrict__ img = image + (long)bi * 3 * plane;
+  const long plane = (long)h * w, splane = GEOM ? (long)H * W : plane;
+  const unsigned char* __restrict__ img = image + (long)bi * 3 * splane;
   unsigned acc = 0;                            // at most plane / (256 * gridDim.x) + 1 pixels of 255 per thread: see the launch
   for (long i = (long)blockIdx.x * kPmThreads + threadIdx.x; i < plane; i += (long)gridDim.x * kPmThreads) {
-    int r = img[i], g = img[plane + i], b = img[2 * plane + i];
+    int r, g, b;
+    if (GEOM) {
+      const int oy = (int)(i / w);
+      pm_gather(geom[bi], img, splane, H, W, w, oy, (int)(i - (long)oy * w), r, g, b);
+    } else {
+      r = img[i], g = img[plane + i], b = img[2 * plane + i];
+    }
     pm_steps<true>(p, 0.0f, r, g, b);
     acc += (unsigned)pm_gray(r, g, b);
   }
@@ -108,14 +189,16 @@ __global__ __launch_bounds__(kPmThreads) void photometric_gray_sum_kernel(const 
   }
 }
 
+template <bool GEOM>
 __global__ __launch_bounds__(kPmThreads) void photometric_apply_kernel(const unsigned char* __restrict__ image,
                                                                       const PmRecord* __restrict__ records,
-                                                                      const unsigned long long* __restrict__ sums, int h, int w,
-                                                                      float* __restrict__ out) {
+                                                                      const PmGeom* __restrict__ geom,
+                                                                      const unsigned long long* __restrict__ sums, int H, int W, int h,
+                                                                      int w, float* __restrict__ out) {
   const int bi = blockIdx.z;
   const PmRecord& p = records[bi];
-  const long plane = (long)h * w;
-  const unsigned char* __restrict__ img = image + (long)bi * 3 * plane;
+  const long plane = (long)h * w, splane = GEOM ? (long)H * W : plane;
+  const unsigned char* __restrict__ img = image + (long)bi * 3 * splane;
   float* __restrict__ o = out + (long)bi * 3 * plane;
   const float gray_mean = sums != nullptr ? (float)sums[bi] / (float)plane : 0.0f;
   const int c0 = pm_channel(p.perm[0]), c1 = pm_channel(p.perm[1]), c2 = pm_channel(p.perm[2]);
@@ -123,6 +206,24 @@ __global__ __launch_bounds__(kPmThreads) void photometric_apply_kernel(const uns
   const int x0 = blockIdx.x * kPmTileW, y0 = blockIdx.y * kPmTileH;
   const int lx = threadIdx.x & (kPmTileW - 1), ly0 = threadIdx.x / kPmTileW;
   const int x = x0 + lx;
+
+  if (GEOM) {
+    if (x >= w) return;
+    const PmGeom& q = geom[bi];
+#pragma unroll
+    for (int k = 0; k < kPmRowsPerThread; ++k) {
+      const int y = y0 + ly0 + k * (kPmThreads / kPmTileW);
+      if (y >= h) break;
+      const long i = (long)y * w + x;
+      int r, g, b;
+      const bool inside = pm_gather(q, img, splane, H, W, w, y, x, r, g, b);
+      pm_steps<false>(p, gray_mean, r, g, b);
+      o[i] = inside ? pm_norm(pm_pick(c0, r, g, b), m0, s0) : 0.0f;
+      o[plane + i] = inside ? pm_norm(pm_pick(c1, r, g, b), m1, s1) : 0.0f;
+      o[2 * plane + i] = inside ? pm_norm(pm_pick(c2, r, g, b), m2, s2) : 0.0f;
+    }
+    return;
+  }
 
   if (!p.blur) {                               // (uniform per workgroup)
     if (x >= w) return;
@@ -181,6 +282,45 @@ static int pm_check(const char* entry, const void* image, const void* records, i
   return RFN_OK;
 }
 
+static int pm_check_geom(const char* entry, const void* geom, int H, int W, int h, int w) {
+  RFN_REQUIRE(geom, "%s: null pointer", entry);
+  RFN_REQUIRE(H >= 1 && W >= 1 && H < 32768 && W < 32768, "%s: H=%d W=%d (each 1 ... 32767: the fixed-point transform)", entry, H, W);
+  RFN_REQUIRE(h <= H && w <= W, "%s: a %d x %d crop of a %d x %d image", entry, h, w, H, W);
+  return RFN_OK;
+}
+
+static int pm_launch_sums(const char* entry, const void* image, const void* records, const void* geom, int B, int H, int W, int h,
+                          int w, unsigned long* sums, hipStream_t st) {
+  RFN_REQUIRE(sums, "%s: null pointer", entry);
+  int rc = zero_async(sums, (size_t)B * 8, st);
+  if (rc != RFN_OK) return rc;
+  // (a thread's 32-bit partial: with 1024 workgroups at most 2^31 / 3 / 2^18 + 1 pixels of at most 255)
+  const long plane = (long)h * w;
+  const int blocks = cdiv(plane, kPmThreads * 8) < kPmMaxSumBlocks ? cdiv(plane, kPmThreads * 8) : kPmMaxSumBlocks;
+  const dim3 grid((unsigned)blocks, (unsigned)B);
+  if (geom)
+    hipLaunchKernelGGL(photometric_gray_sum_kernel<true>, grid, dim3(kPmThreads), 0, st, (const unsigned char*)image,
+                       (const PmRecord*)records, (const PmGeom*)geom, H, W, h, w, (unsigned long long*)sums);
+  else
+    hipLaunchKernelGGL(photometric_gray_sum_kernel<false>, grid, dim3(kPmThreads), 0, st, (const unsigned char*)image,
+                       (const PmRecord*)records, (const PmGeom*)nullptr, H, W, h, w, (unsigned long long*)sums);
+  return check_launch("photometric_gray_sum_kernel");
+}
+
+static int pm_launch_apply(const char* entry, const void* image, const void* records, const void* geom, const unsigned long* sums,
+                           int B, int H, int W, int h, int w, float* out, hipStream_t st) {
+  RFN_REQUIRE(out, "%s: null pointer", entry);
+  const dim3 grid((unsigned)cdiv(w, kPmTileW), (unsigned)cdiv(h, kPmTileH), (unsigned)B);
+  RFN_REQUIRE(grid.y <= 65535, "%s: h=%d (at most %d)", entry, h, 65535 * kPmTileH);
+  if (geom)
+    hipLaunchKernelGGL(photometric_apply_kernel<true>, grid, dim3(kPmThreads), 0, st, (const unsigned char*)image,
+                       (const PmRecord*)records, (const PmGeom*)geom, (const unsigned long long*)sums, H, W, h, w, out);
+  else
+    hipLaunchKernelGGL(photometric_apply_kernel<false>, grid, dim3(kPmThreads), 0, st, (const unsigned char*)image,
+                       (const PmRecord*)records, (const PmGeom*)nullptr, (const unsigned long long*)sums, H, W, h, w, out);
+  return check_launch("photometric_apply_kernel");
+}
+
 }  // namespace rfn
 
 extern "C" {
@@ -191,29 +331,34 @@ int rfn_photometric_record_words(void) { return kPmWords; }
 
 int rfn_photometric_gray_sums_u8(const void* image, const void* records, int B, int h, int w, unsigned long* sums,
                                  rfn_stream_t stream) {
-  int rc = pm_check("rfn_photometric_gray_sums_u8", image, records, B, h, w);
+  const int rc = pm_check("rfn_photometric_gray_sums_u8", image, records, B, h, w);
   if (rc != RFN_OK) return rc;
-  RFN_REQUIRE(sums, "rfn_photometric_gray_sums_u8: null pointer");
-  rc = zero_async(sums, (size_t)B * 8, (hipStream_t)stream);
-  if (rc != RFN_OK) return rc;
-  // (a thread's 32-bit partial: with 1024 workgroups at most 2^31 / 3 / 2^18 + 1 pixels of at most 255)
-  const long plane = (long)h * w;
-  const int blocks = cdiv(plane, kPmThreads * 8) < kPmMaxSumBlocks ? cdiv(plane, kPmThreads * 8) : kPmMaxSumBlocks;
-  hipLaunchKernelGGL(photometric_gray_sum_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(kPmThreads), 0, (hipStream_t)stream,
-                     (const unsigned char*)image, (const PmRecord*)records, h, w, (unsigned long long*)sums);
-  return check_launch("photometric_gray_sum_kernel");
+  return pm_launch_sums("rfn_photometric_gray_sums_u8", image, records, nullptr, B, h, w, h, w, sums, (hipStream_t)stream);
 }
 
 int rfn_photometric_apply_u8(const void* image, const void* records, const unsigned long* sums, int B, int h, int w, float* out,
                              rfn_stream_t stream) {
-  int rc = pm_check("rfn_photometric_apply_u8", image, records, B, h, w);
+  const int rc = pm_check("rfn_photometric_apply_u8", image, records, B, h, w);
   if (rc != RFN_OK) return rc;
-  RFN_REQUIRE(out, "rfn_photometric_apply_u8: null pointer");
-  const dim3 grid((unsigned)cdiv(w, kPmTileW), (unsigned)cdiv(h, kPmTileH), (unsigned)B);
-  RFN_REQUIRE(grid.y <= 65535, "rfn_photometric_apply_u8: h=%d (at most %d)", h, 65535 * kPmTileH);
-  hipLaunchKernelGGL(photometric_apply_kernel, grid, dim3(kPmThreads), 0, (hipStream_t)stream, (const unsigned char*)image,
-                     (const PmRecord*)records, (const unsigned long long*)sums, h, w, out);
-  return check_launch("photometric_apply_kernel");
+  return pm_launch_apply("rfn_photometric_apply_u8", image, records, nullptr, sums, B, h, w, h, w, out, (hipStream_t)stream);
+}
+
+int rfn_photometric_gray_sums_geom_u8(const void* image, const void* records, const void* geom, int B, int H, int W, int h, int w,
+                                      unsigned long* sums, rfn_stream_t stream) {
+  int rc = pm_check("rfn_photometric_gray_sums_geom_u8", image, records, B, h, w);
+  if (rc != RFN_OK) return rc;
+  rc = pm_check_geom("rfn_photometric_gray_sums_geom_u8", geom, H, W, h, w);
+  if (rc != RFN_OK) return rc;
+  return pm_launch_sums("rfn_photometric_gray_sums_geom_u8", image, records, geom, B, H, W, h, w, sums, (hipStream_t)stream);
+}
+
+int rfn_photometric_apply_geom_u8(const void* image, const void* records, const void* geom, const unsigned long* sums, int B, int H,
+                                  int W, int h, int w, float* out, rfn_stream_t stream) {
+  int rc = pm_check("rfn_photometric_apply_geom_u8", image, records, B, h, w);
+  if (rc != RFN_OK) return rc;
+  rc = pm_check_geom("rfn_photometric_apply_geom_u8", geom, H, W, h, w);
+  if (rc != RFN_OK) return rc;
+  return pm_launch_apply("rfn_photometric_apply_geom_u8", image, records, geom, sums, B, H, W, h, w, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -197,6 +197,65 @@ class PairSampler:
         return a, b
 
 
+class RotatedLabelledSampler:
+    """The labelled RobotCar section (configs/cityscapes_robotcar/refign_*.yaml: RandomRotation -> ToTensor -> RandomCrop ->
+    ColorJitter -> RandomHorizontalFlip -> ConvertImageDtype -> Normalize over image + semantic) from the decoded file.
+    `load(index)` -> (decoded image uint8 (H, W, 3) channels last, label uint8 (H, W)) of any size; plan:
+    config.train_section_plan(cfg, "RobotCar", 0).  Per sample, in the reference's order of draws:
+      the reader's load-time resize to plan["dims"]: the label NEAREST, the image BILINEAR (refign_amd/resample.py);
+      RandomRotation's angle, float(torch.empty(1).uniform_(lo, hi)); the label map is rotated with fill 255 (rotate_nearest_u8);
+      RandomCrop's box over the ROTATED label map's histograms (draw_crop: one launch for a whole chain of candidates);
+      ColorJitter's draws (photometric.draw); RandomHorizontalFlip's coin, random.random() < p;
+      the image in ONE fused pass (photometric.apply(geometry=)): rotation, crop, jitter, mirror, conversion, normalisation and
+      the 0.0 under RandomRotation's normalize_mask -- neither the rotated nor the jittered image nor the mask is stored;
+      the label through the existing crop + flip.
+    Both random streams stand afterwards where the reference's pipeline leaves them.  The reader's choice of `index` and
+    `ignore_every_second_semantic_training_batch` stay with the caller.  A section without RandomRotation or ColorJitter makes
+    no such draw; a RandomHorizontalFlip with p = 0 is taken as absent."""
+
+    def __init__(self, load, plan, device, hists=None):
+        self.load, self.plan, self.device = load, plan, torch.device(device)
+        if plan.get("crop_size") is None:
+            raise ValueError("RotatedLabelledSampler: the plan has no RandomCrop size")
+        self.size = tuple(plan["crop_size"])
+        self.dims = None if plan.get("dims") is None else (int(plan["dims"][0]), int(plan["dims"][1]))
+        self.jitter = None if plan.get("jitter") is None else dict(plan["jitter"], mean=plan["mean"], std=plan["std"])
+        self._hists = hists                               # tests inject a host counter; None: the device kernel
+
+    def sample(self, index, out_image=None, out_label=None):
+        from . import photometric
+        from .resample import resize_nearest_u8, resize_u8, rotate_nearest_u8
+        img, lbl = self.load(index)
+        img, lbl = torch.as_tensor(img), torch.as_tensor(lbl)
+        img_d, lbl_d = img.to(self.device, non_blocking=True), lbl.to(self.device, non_blocking=True)
+        if self.dims is not None and tuple(lbl_d.shape) != self.dims:
+            lbl_d = resize_nearest_u8(lbl_d, self.dims)
+        if self.dims is not None and tuple(img_d.shape[:2]) != self.dims:
+            img_d = resize_u8(img_d, self.dims)
+        else:
+            img_d = img_d.permute(2, 0, 1).contiguous()
+        h, w = lbl_d.shape
+        angle = 0.0
+        if self.plan.get("rotation") is not None:
+            lo, hi = self.plan["rotation"]["degrees"]
+            angle = float(torch.empty(1).uniform_(float(lo), float(hi)).item())
+            lbl_d, _ = rotate_nearest_u8(lbl_d, angle, 255)
+        counter = self._hists if self._hists is not None else (lambda boxes: device_label_hists(lbl_d, boxes))
+        (top, left, hh, ww), _ = draw_crop(h, w, self.size, self.plan.get("cat_max_ratio", 1.0), 255, counter)
+        if self.jitter is not None:
+            pp = photometric.draw(self.jitter)
+        else:
+            pp = photometric.params_from([0, 1, 2, 3], None, None, None, [0, 1, 2], None, mean=self.plan["mean"], std=self.plan["std"])
+        p = self.plan.get("flip", 0.0)
+        flip = random.random() < p if p > 0 else False
+        if out_image is not None and not (torch.is_tensor(out_image) and tuple(out_image.shape) == (3, hh, ww)):
+            raise RuntimeError(f"RotatedLabelledSampler: out_image must be a (3, {hh}, {ww}) float32 tensor")
+        out = photometric.apply(img_d, pp, None if out_image is None else out_image.unsqueeze(0),
+                                geometry=photometric.RotateCrop(angle, top, left, hh, ww, flip))
+        _, out_label = crop_flip_normalize(None, lbl_d, top, left, hh, ww, flip, None, out_label)
+        return out[0], out_label
+
+
 def merge_batches(batch):
     """CombinedDataModule.on_before_batch_transfer in training (combined_data_module.py:263-310) for sub-batches that still arrive
     as separate dicts: the supervised one carries 'semantic', the adaptation one 'image' (+ 'image_ref')."""

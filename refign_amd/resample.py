@@ -17,7 +17,13 @@ The matcher's side (datasets/megadepth.py, robotcarmatching.py; the `test:` sect
 Pillow's LANCZOS filter and ends in transforms.PadBottomRight: `filter_tables(in, out, "lanczos")` are the same tables for that
 filter (negative taps: every row is checked against the int32 accumulator), `filter="lanczos"` / `pad_to=` select them in the
 device functions, `lanczos_reference` restates the pixels (tests/test_lanczos_*.py against tests/golden/lanczos_pillow.npz), and
-EvalIngest scales the sparse correspondences the way the reference does (`scale_points`)."""
+EvalIngest scales the sparse correspondences the way the reference does (`scale_points`).
+
+transforms.RandomRotation (transforms.py:206-247; the labelled RobotCar section) rotates the PIL image, the label map and an
+all-zero mask with `Image.rotate(angle, NEAREST)`: Pillow's fixed-point affine transform (Geometry.c `affine_fixed`), integer
+arithmetic again.  `rotation_coefficients` makes its six 16.16 integers as Pillow does, `rotate_nearest_u8` (csrc/rotate.hip)
+gives Pillow's pixels and the mask (tests/test_rotate_cpu.py, tests/test_robotcar_ingest_gpu.py against
+tests/golden/rotate_pillow.npz), and photometric.apply(geometry=) gathers through the same integers."""
 import math
 
 import numpy as np
@@ -142,6 +148,37 @@ def target_size(h, w, size, only_if_larger=False):
         new_w, new_h = (new_short, new_long) if w <= h else (new_long, new_short)
         return new_h, new_w
     return int(size[0]), int(size[1])
+
+
+ROTATE_MAX_SIDE = 32767          # Geometry.c: the fixed-point path is taken below 32768 pixels a side
+
+
+def rotation_coefficients(angle, H, W):
+    """(a0, a1, a2, a3, a4, a5): the 16.16 fixed-point coefficients with which `Image.rotate(angle, NEAREST, expand=False,
+    center=None)` of an (H, W) image reads its source -- Image.rotate's matrix (entries rounded to 15 decimals, the centre
+    (W / 2, H / 2)) in Python floats, then affine_fixed's FIX(v) = floor(v * 65536 + 0.5) with the half-pixel offset folded into
+    a2 / a5.  Output pixel (y, x) reads source (yy >> 16, xx >> 16), xx = a2 + a1 y + a0 x, yy = a5 + a4 y + a3 x.
+    ValueError for a multiple of 90 degrees other than 0 (Pillow transposes there instead) and for a size at which |xx| or |yy|
+    could pass 2^31."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H > ROTATE_MAX_SIDE or W > ROTATE_MAX_SIDE:
+        raise ValueError(f"rotation_coefficients: a {H} x {W} image (each side 1 ... {ROTATE_MAX_SIDE}: Pillow's limit for its "
+                         f"fixed-point transform)")
+    ang = float(angle) % 360.0
+    if ang in (90.0, 180.0, 270.0):
+        raise ValueError(f"rotation_coefficients: angle {angle!r}: Pillow rotates by a multiple of 90 degrees with a transpose, "
+                         f"which is not built")
+    r = -math.radians(ang)
+    cx, cy = W / 2, H / 2
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    m[2] = m[0] * (-cx) + m[1] * (-cy) + m[2] + cx
+    m[5] = m[3] * (-cx) + m[4] * (-cy) + m[5] + cy
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))  # noqa: E731
+    a = (fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
+    for a_c, a_y, a_x in ((a[2], a[1], a[0]), (a[5], a[4], a[3])):
+        if abs(a_c) + abs(a_y) * (H - 1) + abs(a_x) * (W - 1) >= 1 << 31:
+            raise ValueError(f"rotation_coefficients: at {H} x {W} the fixed-point coordinates could pass 2^31")
+    return a
 
 
 # ------------------------------------------------------------------ numpy restatements (tests, documentation)
@@ -271,6 +308,28 @@ def resize_nearest_u8(label_u8, size):
     out = torch.empty((Hd, Wd), dtype=torch.uint8, device=dev)
     _lib.call("rfn_resize_nearest_u8", dev, ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(out))
     return out
+
+
+def rotate_nearest_u8(image_u8, angle, fill=0):
+    """`PIL.Image.rotate(angle, NEAREST, expand=False, center=None, fillcolor=fill)` of a (3, H, W) or (H, W) uint8 DEVICE
+    tensor -> (rotated, outside): the same shape, and an (H, W) bool mask that is True where the source falls outside the image
+    (there the pixel is `fill`, in every channel) -- what RandomRotation makes of an image (fill 0), a label map (fill 255) and its
+    normalize_mask.  angle % 360 == 0 is a copy with an all-False mask; 90, 180 and 270 raise ValueError."""
+    if not (torch.is_tensor(image_u8) and image_u8.is_cuda):
+        raise RuntimeError("rotate_nearest_u8: device tensors required (the product path has no CPU fallback)")
+    if not (image_u8.dtype == torch.uint8 and image_u8.dim() in (2, 3) and image_u8.is_contiguous() and
+            (image_u8.dim() == 2 or image_u8.shape[0] == 3)):
+        raise RuntimeError("rotate_nearest_u8: a contiguous (3, H, W) or (H, W) uint8 tensor is required")
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError(f"rotate_nearest_u8: fill {fill} (0 ... 255)")
+    H, W = image_u8.shape[-2:]
+    a = rotation_coefficients(angle, H, W)
+    dev = image_u8.device
+    out = torch.empty_like(image_u8)
+    outside = torch.empty((H, W), dtype=torch.bool, device=dev)
+    _lib.call("rfn_rotate_nearest_u8", dev, ptr(image_u8), 1 if image_u8.dim() == 2 else 3, H, W, *a, fill, ptr(out), ptr(outside))
+    return out, outside
 
 
 def resize_crop_flip_normalize(image_hwc_u8, dims, top, left, h, w, flip, out_image=None, mean=IMNET_MEAN, std=IMNET_STD,
