@@ -49,7 +49,8 @@ const char* rfn_last_error(void);
  * rfn_conv2d_nhwc_wgrad (a bias sum with accumulate != 2), rfn_attn_bwd_dkv, rfn_attn32_bwd (more than one query
  * chunk), rfn_bn_stats_fwd / _bwd (and rfn_bn_train_fwd / _bwd), the depthwise statistics entry points
  * (rfn_dwconv3x3_nhwc_stats, _nhwc_fwd_stats), rfn_dacs_mix_jitter (when a jitter needs
- * the image mean), rfn_upsample_ce, rfn_warp_bwd_f32 and the generic (atomic) form of rfn_corr_bwd_f32 / _f64.
+ * the image mean), rfn_upsample_ce, rfn_warp_bwd_f32 and the generic (atomic) form of rfn_corr_bwd_f32 / _f64 (their
+ * deterministic forms, rfn_warp_bwd_det_f32 and rfn_corr_bwd_gather_f32, are at the end of this header).
  * The entry points named *_det below, rfn_upsample_bilinear2d_bwd and `accumulate == 2` of the weight-gradient
  * GEMMs give bit-identical results from launch to launch with or without the flag: partial sums are written
  * with plain stores and added in a fixed order.
@@ -919,6 +920,31 @@ int rfn_photometric_gray_sums_geom_u8(const void* image, const void* records, co
                                       unsigned long* sums, rfn_stream_t stream);
 int rfn_photometric_apply_geom_u8(const void* image, const void* records, const void* geom, const unsigned long* sums, int B, int H,
                                   int W, int h, int w, float* out, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic forms for matcher training (additions to ABI 5, nothing existing changed; no floating-point atomic, legal
+ * under rfn_set_deterministic(1), bit-identical from launch to launch).
+ *   rfn_warp_bwd_det_f32     the arguments and results of rfn_warp_bwd_f32 plus a workspace of
+ *            rfn_warp_bwd_det_workspace_bytes(B, C, H, W, grad_x != NULL, grad_flow != NULL) bytes, 16-byte aligned, zeroed and
+ *            consumed by the launches of the call itself: 8 B C H W + 4 B C bytes for grad_x, 8 G B H W for grad_flow over
+ *            G = ceil(C / 32) > 1 channel groups, 0 otherwise (the workspace may then be NULL).
+ *            grad_x is accumulated per (n, c) plane in 64-bit fixed point: with M the plane's largest |grad_out|, M < 2^E,
+ *            L = ceil(log2(H W)) and F = 62 - L, every term fp32(g w) is rounded to a multiple of u = 2^(E - F) and added
+ *            with an integer atomic (order-free); grad_x = fp32(sum).  Per element |grad_x - exact| <= 2^-23 S + H W u / 2 with
+ *            S the sum of |g w| over the element's terms, and H W u / 2 <= M 2^(2 L - 62).  A plane of zeros gives zeros; a
+ *            plane whose grad_out holds an inf or a NaN is NaN THROUGHOUT (rfn_warp_bwd_f32: at the touched pixels only).
+ *            grad_flow: C <= 32 gives the bits of rfn_warp_bwd_f32; above, every group's partial sums are stored and added in
+ *            ascending group order.  C <= 65535.
+ *   rfn_corr_bwd_gather_f32  the arguments and results of rfn_corr_bwd_f32 from the gather kernel (one thread per input
+ *            element, fp32 sums in a fixed order), for any parameterisation.
+ * ------------------------------------------------------------------------------------------------------------ */
+unsigned long rfn_warp_bwd_det_workspace_bytes(int B, int C, int H, int W, int want_grad_x, int want_grad_flow);
+int rfn_warp_bwd_det_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                         void* workspace, int B, int C, int H, int W, rfn_stream_t stream);
+int rfn_corr_bwd_gather_f32(const float* in1, const float* in2, const float* grad_out, float* grad_in1,
+                            float* grad_in2, int B, int C, int iH, int iW, int kH, int kW, int patchH, int patchW,
+                            int padH, int padW, int dilH, int dilW, int dpH, int dpW, int dH, int dW,
+                            rfn_stream_t stream);
 
 #ifdef __cplusplus
 }

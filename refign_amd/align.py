@@ -33,6 +33,7 @@ from ._tensor import const_tensor
 from .conv import Conv2d
 from .layers import LEAKY_SLOPE, ConvBNReLU
 from .modules import GlobalFeatureCorrelationLayer, LocalFeatureCorrelationLayer
+from .upsample import interpolate_bilinear
 
 def _leaky():
     return nn.LeakyReLU(LEAKY_SLOPE)
@@ -323,7 +324,8 @@ class VGG(nn.Module):
 # UAWarpC head
 # ---------------------------------------------------------------------------------------------------------------------
 def _up(x, size):
-    return F.interpolate(x, size=size, mode='bilinear', align_corners=False)
+    # (F.interpolate itself outside the deterministic mode; in it, a gather backward: refign_amd/upsample.py)
+    return interpolate_bilinear(x, size=size)
 
 
 class BaseHead(nn.Module):

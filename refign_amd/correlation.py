@@ -16,7 +16,7 @@ import torch
 from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
-from . import _lib
+from . import _lib, determinism
 from ._tensor import ptr, require_device_tensor, same_device
 
 # (half: the pybind module of the reference dispatches it on the device, correlation_cuda_kernel.cu:267; `forward` / `backward`
@@ -55,6 +55,12 @@ def forward(input1, input2, kH, kW, patchH, patchW, padH, padW, dilationH, dilat
     return out
 
 
+def _has_fixed_order_bwd(kH, kW, padH, padW, dH, dW):
+    """Kernel 1, stride 1, no padding (the patch-9 hot path among them): rfn_corr_bwd_f32 runs a kernel without atomics
+    (csrc/corr.hip corr_bwd_any)."""
+    return (kH, kW, padH, padW, dH, dW) == (1, 1, 0, 0, 1, 1)
+
+
 def backward(input1, input2, grad_output, kH, kW, patchH, patchW, padH, padW, dilationH, dilationW,
              dilation_patchH, dilation_patchW, dH, dW):
     require_device_tensor(input1, "input1")
@@ -69,7 +75,10 @@ def backward(input1, input2, grad_output, kH, kW, patchH, patchW, padH, padW, di
                            f"{(B, patchH, patchW, oH, oW)}")
     g1 = torch.empty_like(input1)
     g2 = torch.empty_like(input2)
-    _lib.call("rfn_corr_bwd_" + _suffix(input1), dev, ptr(input1), ptr(input2), ptr(grad_output), ptr(g1), ptr(g2), B, C, iH,
+    entry = "rfn_corr_bwd_" + _suffix(input1)
+    if entry == "rfn_corr_bwd_f32" and determinism.scatter_forms() and not _has_fixed_order_bwd(kH, kW, padH, padW, dH, dW):
+        entry = "rfn_corr_bwd_gather_f32"                  # the generic parameterisation: gather instead of the atomic scatter
+    _lib.call(entry, dev, ptr(input1), ptr(input2), ptr(grad_output), ptr(g1), ptr(g2), B, C, iH,
               iW, kH, kW, patchH, patchW, padH, padW, dilationH, dilationW, dilation_patchH, dilation_patchW, dH, dW)
     return [g1, g2]
 

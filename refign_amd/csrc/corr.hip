@@ -23,7 +23,7 @@
 //   * corr9_bwd_strip_kernel  -- the hot parameterisation, f32, W % 4 == 0, C % 8 == 0: both gradients in one launch;
 //   * corr9_bwd_tile_kernel   -- the hot parameterisation otherwise: one pixel per thread, one launch per gradient;
 //   * corr_k1_bwd_kernel      -- gather form for kernel 1 / stride 1 / pad 0 (deterministic, no atomics);
-//   * corr_generic_bwd_gather_kernel -- half, any parameterisation (deterministic);
+//   * corr_generic_bwd_gather_kernel -- half, and fp32 through rfn_corr_bwd_gather_f32; any parameterisation (deterministic);
 //   * corr_generic_bwd_kernel -- scatter with hardware float / double atomics for everything else.
 // History of the forward (three earlier kernel generations, what was tried and dropped): docs/history/DESIGN_r01-r04.md
 // section 10; their measurements are profiles/r01-r06_*corr*.
@@ -1453,6 +1453,19 @@ RFN_CORR_ENTRY(f32, float, float)
 RFN_CORR_ENTRY(f64, double, double)
 RFN_CORR_ENTRY(f16, void, __half)
 #undef RFN_CORR_ENTRY
+
+// The gather kernel for fp32, any parameterisation: no atomics, legal in deterministic mode (rfn_corr_bwd_f32 refuses its generic
+// parameterisation there).
+int rfn_corr_bwd_gather_f32(const float* in1, const float* in2, const float* grad_out, float* grad_in1, float* grad_in2,
+                            RFN_CORR_ARGS) {
+  RFN_REQUIRE(in1 && in2 && grad_out && grad_in1 && grad_in2, "rfn_corr_bwd_gather_f32: null pointer");
+  CorrParams p;
+  if (int rc = fill_params(p, B, C, iH, iW, kH, kW, patchH, patchW, padH, padW, dilH, dilW, dpH, dpW, dH, dW)) return rc;
+  const long npix = (long)p.B * p.C * p.iH * p.iW;
+  hipLaunchKernelGGL((corr_generic_bwd_gather_kernel<float>), dim3(flat_grid(npix)), dim3(256), 0, (hipStream_t)stream, in1, in2,
+                     grad_out, grad_in1, grad_in2, p, npix);
+  return check_launch("corr_generic_bwd_gather_kernel");
+}
 #undef RFN_CORR_ARGS
 
 int rfn_local_corr_layer_f32(const float* feature_target, const float* feature_source, const float* flow,

@@ -141,6 +141,123 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(const float* __restrict__
   }
 }
 
+// ---- The deterministic form of the backward (rfn_warp_bwd_det_f32): no floating-point atomic ----------------------------------
+// grad_x: every term g * w is turned into a 64-bit integer multiple of a per-plane unit u = 2^(E - F) and added with an
+// integer atomic -- integer addition is associative, so the sum has the same bits in whatever order the adds arrive.  E comes
+// from the plane's largest |grad_out| M (M < 2^E), F = 62 - ceil(log2(H W)): an output pixel sends at most one tap to a given
+// destination and every weight is <= 1, so |sum| < H W 2^F <= 2^62.  grad_flow across channel groups: every group stores its two
+// partial sums per pixel, the finalize pass adds them in ascending group order.
+// workspace: int64 acc[B C H W] | uint32 maxbits[B C] | float part[G][B][2][H W]   (the first two with grad_x, the last with
+// grad_flow over G > 1 groups)
+
+// maxbits[plane] = the largest bit pattern of |grad_out| over the plane (monotone in |g|; >= 0x7f800000: an inf or a NaN).
+// grid: (ceil(HW/1024), C, B); maxbits zeroed before.
+__global__ __launch_bounds__(256) void warp_bwd_det_scale_kernel(const float* __restrict__ gout, unsigned* __restrict__ maxbits,
+                                                                 int C, int HW) {
+  __shared__ unsigned wave_max[4];
+  const size_t plane = (size_t)blockIdx.z * C + blockIdx.y;
+  const float* g = gout + plane * HW;
+  unsigned m = 0u;
+  for (int k = 0; k < 4; ++k) {
+    const long i = (long)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+    if (i < HW) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
+  }
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicMax(maxbits + plane, max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3])));
+}
+
+// E with M < 2^E for the bit pattern of a finite M > 0 (a denormal M: below 2^-126 < 2^-125)
+__device__ __forceinline__ int det_exponent(unsigned bits) { return max((int)(bits >> 23), 1) - 126; }
+__device__ __forceinline__ double pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }   // |e| < 1023
+__device__ __forceinline__ bool det_plane_live(unsigned bits) { return bits != 0u && bits < 0x7f800000u; }
+
+// The scatter: the grid, the bilinear_tap call, the tap validity and the grad_flow arithmetic of warp_bwd_kernel.
+// grid: (ceil(HW/256), channel groups, B)
+template <int CG, bool ONE_GROUP>
+__global__ __launch_bounds__(256) void warp_bwd_det_scatter_kernel(const float* __restrict__ x, const float* __restrict__ flow,
+                                                                   const float* __restrict__ gout,
+                                                                   unsigned long long* __restrict__ acc,
+                                                                   const unsigned* __restrict__ maxbits, float* __restrict__ gflow,
+                                                                   float* __restrict__ part, int C, int H, int W, int F) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int HW = H * W;
+  if (pix >= HW) return;
+  const int n = blockIdx.z, c0 = blockIdx.y * CG;
+  const int gy = pix / W, gx = pix - gy * W;
+  const float* fl = flow + (size_t)n * 2 * HW;
+  const Tap t = bilinear_tap((float)gx, (float)gy, fl[pix], fl[HW + pix], H, W);
+  const float fxv = fl[pix], fyv = fl[HW + pix];
+  const float wm = (float)max(W - 1, 1), hm = (float)max(H - 1, 1);
+  float ix, iy;
+  {
+#pragma clang fp contract(off)
+    const float vx = 2.0f * ((float)gx + fxv) / wm - 1.0f, vy = 2.0f * ((float)gy + fyv) / hm - 1.0f;
+    ix = ((vx + 1.0f) / 2.0f) * (float)(W - 1);
+    iy = ((vy + 1.0f) / 2.0f) * (float)(H - 1);
+  }
+  const float x0f = floorf(ix), y0f = floorf(iy);
+  const float tx = ix - x0f, ty = iy - y0f, ax = 1.0f - tx, ay = 1.0f - ty;
+  const bool finite = (ix == ix) && (iy == iy) && fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;
+  const int x0 = finite ? (int)x0f : -2, y0 = finite ? (int)y0f : -2;
+  const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
+  const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
+  const bool v00 = vx0 && vy0, v01 = vx1 && vy0, v10 = vx0 && vy1, v11 = vx1 && vy1;
+  const float* src = x + ((size_t)n * C + c0) * HW;
+  const float* go = gout + ((size_t)n * C + c0) * HW + pix;
+  const int cend = min(CG, C - c0);
+  float gix = 0.f, giy = 0.f;
+  for (int c = 0; c < cend; ++c) {
+    const float g = go[(size_t)c * HW];
+    if (gflow) {
+      const float* s = src + (size_t)c * HW;
+      const float nw = v00 ? s[t.o00] : 0.f, ne = v01 ? s[t.o01] : 0.f, sw = v10 ? s[t.o10] : 0.f, se = v11 ? s[t.o11] : 0.f;
+      gix += g * ((ne - nw) * ay + (se - sw) * ty);
+      giy += g * ((sw - nw) * ax + (se - ne) * tx);
+    }
+    if (acc) {
+      const size_t plane = (size_t)n * C + c0 + c;
+      const unsigned mb = maxbits[plane];
+      if (det_plane_live(mb)) {                            // (an all-zero or a non-finite plane: written whole by the finalize pass)
+        const double scale = pow2(F - det_exponent(mb));   // exact: |g w| 2^(F - E) < 2^F
+        unsigned long long* d = acc + plane * HW;
+        if (v00) atomicAdd(d + t.o00, (unsigned long long)llrint((double)(g * t.w00) * scale));
+        if (v01) atomicAdd(d + t.o01, (unsigned long long)llrint((double)(g * t.w01) * scale));
+        if (v10) atomicAdd(d + t.o10, (unsigned long long)llrint((double)(g * t.w10) * scale));
+        if (v11) atomicAdd(d + t.o11, (unsigned long long)llrint((double)(g * t.w11) * scale));
+      }
+    }
+  }
+  if (gflow) {
+    const float fx_out = (W > 1 && finite) ? 0.0f + gix : 0.0f, fy_out = (H > 1 && finite) ? 0.0f + giy : 0.0f;
+    float* gf = ONE_GROUP ? gflow + (size_t)n * 2 * HW : part + ((size_t)blockIdx.y * gridDim.z + n) * 2 * HW;
+    gf[pix] = fx_out;
+    gf[HW + pix] = fy_out;
+  }
+}
+
+// grad_x = acc * u (a non-finite plane: NaN throughout; an all-zero plane: 0) for idx < nx, then grad_flow = the groups' partial
+// sums added in ascending order onto 0 for the nf elements behind.  Either part may be empty.
+__global__ __launch_bounds__(256) void warp_bwd_det_finalize_kernel(const long long* __restrict__ acc,
+                                                                    const unsigned* __restrict__ maxbits, float* __restrict__ gx_out,
+                                                                    const float* __restrict__ part, float* __restrict__ gflow,
+                                                                    long nx, long nf, int HW, int F, int G) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx < nx) {
+    const unsigned mb = maxbits[idx / HW];
+    float v = 0.0f;
+    if (mb >= 0x7f800000u) v = __uint_as_float(0x7fc00000u);
+    else if (mb != 0u) v = (float)((double)acc[idx] * pow2(det_exponent(mb) - F));
+    gx_out[idx] = v;
+  } else if (idx < nx + nf) {
+    const long j = idx - nx;
+    float s = 0.0f;
+    for (int g = 0; g < G; ++g) s += part[(size_t)g * nf + j];
+    gflow[j] = s;
+  }
+}
+
 // ATen upsample_bilinear2d source index, align_corners=False: max(scale*(dst+0.5)-0.5, 0)
 __device__ __forceinline__ void up_index(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
 #pragma clang fp contract(off)
@@ -437,6 +554,62 @@ int rfn_warp_bwd_f32(const float* x, const float* flow, const float* grad_out, f
   else
     hipLaunchKernelGGL((warp_bwd_kernel<CG, false>), grid, dim3(256), 0, s, x, flow, grad_out, grad_x, grad_flow, C, H, W);
   return check_launch("warp_bwd_kernel");
+}
+
+// ceil(log2(HW)) for HW >= 1
+static inline int ceil_log2(long v) {
+  int l = 0;
+  while ((1L << l) < v) ++l;
+  return l;
+}
+
+unsigned long rfn_warp_bwd_det_workspace_bytes(int B, int C, int H, int W, int want_grad_x, int want_grad_flow) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t HW = (size_t)H * W, G = (size_t)cdiv(C, 32);
+  size_t bytes = 0;
+  if (want_grad_x) bytes += 8 * (size_t)B * C * HW + 4 * (size_t)B * C;
+  if (want_grad_flow && G > 1) bytes += 8 * G * B * HW;
+  return bytes;
+}
+
+int rfn_warp_bwd_det_f32(const float* x, const float* flow, const float* grad_out, float* grad_x, float* grad_flow,
+                         void* workspace, int B, int C, int H, int W, rfn_stream_t stream) {
+  RFN_REQUIRE(x && flow && grad_out && (grad_x || grad_flow), "rfn_warp_bwd_det_f32: null pointer");
+  RFN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "rfn_warp_bwd_det_f32: non-positive size");
+  RFN_REQUIRE((long)H * W < 0x7fffffffL && B <= 65535 && C <= 65535, "rfn_warp_bwd_det_f32: tensor too large");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t HW = (size_t)H * W;
+  constexpr int CG = 32;
+  const int G = cdiv(C, CG);
+  const bool one_group = G == 1;
+  const size_t planes = (size_t)B * C, acc_bytes = grad_x ? 8 * planes * HW : 0, max_bytes = grad_x ? 4 * planes : 0;
+  const bool partials = grad_flow && !one_group;
+  RFN_REQUIRE(workspace || !(grad_x || partials), "rfn_warp_bwd_det_f32: null workspace");
+  RFN_REQUIRE(((size_t)workspace & 15) == 0, "rfn_warp_bwd_det_f32: workspace must be 16-byte aligned");
+  const long nx = grad_x ? (long)(planes * HW) : 0, nf = partials ? (long)(2 * B * HW) : 0;
+  RFN_REQUIRE((nx + nf) / 256 < 0x7fffffffL, "rfn_warp_bwd_det_f32: tensor too large");
+  unsigned long long* acc = grad_x ? (unsigned long long*)workspace : nullptr;
+  unsigned* maxbits = grad_x ? (unsigned*)((char*)workspace + acc_bytes) : nullptr;
+  float* part = partials ? (float*)((char*)workspace + acc_bytes + max_bytes) : nullptr;
+  const int F = 62 - ceil_log2((long)HW);
+  if (grad_x) {
+    // (a kernel on the caller's stream, as in rfn_warp_bwd_f32: the step is captured into a hipGraph)
+    if (int rc = zero_async(workspace, acc_bytes + max_bytes, s)) return rc;
+    hipLaunchKernelGGL(warp_bwd_det_scale_kernel, dim3(cdiv((long)HW, 1024), C, B), dim3(256), 0, s, grad_out, maxbits, C, (int)HW);
+    if (int rc = check_launch("warp_bwd_det_scale_kernel")) return rc;
+  }
+  dim3 grid(cdiv((long)HW, 256), G, B);
+  if (one_group)
+    hipLaunchKernelGGL((warp_bwd_det_scatter_kernel<CG, true>), grid, dim3(256), 0, s, x, flow, grad_out, acc, maxbits, grad_flow,
+                       part, C, H, W, F);
+  else
+    hipLaunchKernelGGL((warp_bwd_det_scatter_kernel<CG, false>), grid, dim3(256), 0, s, x, flow, grad_out, acc, maxbits, grad_flow,
+                       part, C, H, W, F);
+  if (int rc = check_launch("warp_bwd_det_scatter_kernel")) return rc;
+  if (nx + nf == 0) return RFN_OK;
+  hipLaunchKernelGGL(warp_bwd_det_finalize_kernel, dim3((unsigned)cdiv(nx + nf, 256)), dim3(256), 0, s, (const long long*)acc,
+                     maxbits, grad_x, part, grad_flow, nx, nf, (int)HW, F, G);
+  return check_launch("warp_bwd_det_finalize_kernel");
 }
 
 int rfn_align_tail_f32(const float* logits_ref, const float* flow_q, const float* logvar_q, float* warped,

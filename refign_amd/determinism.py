@@ -10,6 +10,9 @@ while it is set, every entry point that adds with floating-point atomics returns
 `enabled()` raises instead of drifting.  A Python mirror of the flag keeps `enabled()` off the ctypes path (it sits in front of
 ~1 000 launches per step).
 
+`scatter_forms` widens the mode (`acquire(scatter_forms=True)`, `deterministic(scatter_forms=True)`, `scatter_forms()`): see there.
+It follows the same rule: what the innermost block says, and outside blocks on while a holder that asked for it remains.
+
 `torch_deterministic()` is the span of one training step: torch's own switch on (ATen ops without a deterministic form raise),
 MIOpen's deterministic algorithms, and `fill_uninitialized_memory` off -- that one is a debugging aid which puts a fill launch
 behind every `torch.empty`.
@@ -21,42 +24,55 @@ import torch
 from . import _lib
 
 _ENABLED = False
+_SCATTER = False
 
 
 def enabled():
     return _ENABLED
 
 
+def scatter_forms():
+    """The widening of the mode: with it, the two scatter backwards the plain mode refuses (matching.warp, the generic fp32
+    correlation) take their order-free forms (rfn_warp_bwd_det_f32, rfn_corr_bwd_gather_f32).  A deterministic Trainer of the
+    matcher asks for it; the plain mode keeps refusing them -- the UDA step never differentiates through a warp, and the refusal
+    is the tripwire of its audit."""
+    return _ENABLED and _SCATTER
+
+
 _HOLDERS = 0            # open deterministic trainers
-_BLOCKS = []            # the `on` of every open `with deterministic(on):` block, innermost last
+_SCATTER_HOLDERS = 0    # ... of them, those that asked for the scatter forms
+_BLOCKS = []            # (on, scatter_forms) of every open `with deterministic(...):` block, innermost last
 
 
 def _apply():
     """Bring the library's flag and its mirror to what the requests say."""
-    global _ENABLED
-    on = _BLOCKS[-1] if _BLOCKS else _HOLDERS > 0
+    global _ENABLED, _SCATTER
+    on, _SCATTER = _BLOCKS[-1] if _BLOCKS else (_HOLDERS > 0, _SCATTER_HOLDERS > 0)
     if on != _ENABLED:
         _lib.check(_lib.load_library().rfn_set_deterministic(1 if on else 0), "set_deterministic")
         _ENABLED = on
 
 
-def acquire():
-    """A long-lived holder of the mode (a Trainer): on until the last holder has released it."""
-    global _HOLDERS
+def acquire(scatter_forms=False):
+    """A long-lived holder of the mode (a Trainer): on until the last holder has released it.  `scatter_forms`: the holder asks
+    for the widening too (release it with the same argument)."""
+    global _HOLDERS, _SCATTER_HOLDERS
     _HOLDERS += 1
+    _SCATTER_HOLDERS += 1 if scatter_forms else 0
     _apply()
 
 
-def release():
-    global _HOLDERS
+def release(scatter_forms=False):
+    global _HOLDERS, _SCATTER_HOLDERS
     _HOLDERS = max(0, _HOLDERS - 1)
+    _SCATTER_HOLDERS = min(_HOLDERS, max(0, _SCATTER_HOLDERS - (1 if scatter_forms else 0)))
     _apply()
 
 
 @contextlib.contextmanager
-def deterministic(on=True):
-    """`with deterministic():` -- nests, and restores the state it found."""
-    _BLOCKS.append(bool(on))
+def deterministic(on=True, scatter_forms=False):
+    """`with deterministic():` -- nests, and restores the state it found.  The widening is what the innermost block says."""
+    _BLOCKS.append((bool(on), bool(on) and bool(scatter_forms)))
     try:
         _apply()
         yield

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import flowloss
 from .matching import get_gt_correspondence_mask, warp
+from .upsample import interpolate_bilinear
 
 # MultiScaleFlowLoss.forward on fp32 CUDA inputs with downsample_gt_flow=True: all levels in one autograd node on
 # csrc/flowloss.hip (refign_amd/flowloss.py), without the per-level host decisions of the formulation below.  False (or
@@ -38,7 +39,8 @@ class HuberLoss(nn.Module):
 
 
 def _resize(x, size):
-    return F.interpolate(x, size, mode='bilinear', align_corners=False)
+    # (F.interpolate itself outside the deterministic mode; in it, a gather backward: refign_amd/upsample.py)
+    return interpolate_bilinear(x, size=size)
 
 
 def _level_mask(mask, size):

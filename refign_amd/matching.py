@@ -4,8 +4,8 @@ import os
 
 import torch
 
-from . import _lib
-from ._tensor import DTYPE_CODE16, ptr, require_device_tensor, same_device
+from . import _lib, determinism
+from ._tensor import DTYPE_CODE16, ptr, require_device_tensor, same_device, workspace
 
 
 # Set by no_zero_flow_check(): callers that pass check_zero=None (the head's LocalFeatureCorrelationLayer) skip the check.
@@ -76,7 +76,13 @@ class _WarpFn(torch.autograd.Function):
         B, C, H, W = x.shape
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gf = torch.empty_like(flo) if ctx.needs_input_grad[1] else None
-        _lib.call("rfn_warp_bwd_f32", x.device, ptr(x), ptr(flo), ptr(g), ptr(gx), ptr(gf), B, C, H, W)
+        if determinism.scatter_forms():
+            # the order-free form: 64-bit fixed-point sums for grad_x, stored per-group partials for grad_flow (csrc/warp.hip)
+            ws = workspace(_lib.load_library().rfn_warp_bwd_det_workspace_bytes(B, C, H, W, gx is not None, gf is not None),
+                           x.device)
+            _lib.call("rfn_warp_bwd_det_f32", x.device, ptr(x), ptr(flo), ptr(g), ptr(gx), ptr(gf), ptr(ws), B, C, H, W)
+        else:
+            _lib.call("rfn_warp_bwd_f32", x.device, ptr(x), ptr(flo), ptr(g), ptr(gx), ptr(gf), B, C, H, W)
         return gx, gf
 
 

@@ -420,7 +420,9 @@ class Trainer:
         `deterministic` (Lightning's `--trainer.deterministic true`): bit-reproducible steps -- same build, machine type, seeds
         and batches give the same bits in every loss, parameter, buffer and optimiser state.  Fixed for the life of the trainer
         (refign_amd/determinism.py: on here, off in close(); the kernels that add with floating-point atomics are replaced by
-        their store-and-sum forms or refuse) and not available with precision=32.  One process, one GPU.
+        their store-and-sum forms or refuse) and not available with precision=32.  One process, one GPU.  A model with
+        automatic_optimization (the matcher) gets the mode with determinism.scatter_forms() -- its warp backward adds in 64-bit
+        fixed point -- at any precision, with graph_step too (eager and replayed runs each repeat themselves, not each other).
         `logger` (a steplog.TensorBoardLogger, or anything with log_metrics(dict, step) / flush() / close(); None: nothing is
         recorded and nothing new runs), `log_every_n_steps`, `log_lr`: the record of the run.  The step that takes
         model.global_step from s to s + 1 is recorded when (s + 1) % log_every_n_steps == 0 and its row is labelled s (rows
@@ -458,7 +460,10 @@ class Trainer:
         if scaler_args and self.precision != "16":
             raise ValueError("Trainer: scaler_args needs precision=16")
         self.deterministic = bool(deterministic)
-        if self.deterministic and self.precision == "32":
+        # a model with automatic_optimization (the matcher) takes the mode with its widening: the order-free warp backward and the
+        # gather form of the generic correlation backward (determinism.scatter_forms).  It has no attention: any precision.
+        self._det_scatter = self.deterministic and bool(getattr(model, "automatic_optimization", False))
+        if self.deterministic and self.precision == "32" and not self._det_scatter:
             raise ValueError("Trainer: deterministic=True is not available with precision=32 (the fp32 parity attention adds its "
                              "dK / dV chunks with atomics)")
         self._det_held = False
@@ -573,7 +578,7 @@ class Trainer:
         # the last act before anything launches a kernel that has two forms: a constructor that raised further up holds nothing
         if self.deterministic:
             from . import determinism
-            determinism.acquire()
+            determinism.acquire(scatter_forms=self._det_scatter)
             self._det_held = True
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
@@ -1068,7 +1073,7 @@ class Trainer:
         if getattr(self, "_det_held", False):
             from . import determinism
             self._det_held = False
-            determinism.release()
+            determinism.release(scatter_forms=self._det_scatter)
 
     def __del__(self):
         try:

@@ -7,7 +7,8 @@ optimizer step on synthetic images / flows.  Prints ms/step and image-triplets/s
 --trainer: the same step through refign_amd.trainer.Trainer (Trainer.step: flat gradient buffer, device-side loss scaler,
 one-launch Adam, no host synchronisation) instead of the hand-driven loop with torch.amp.GradScaler.
 --trainer --graph: Trainer(graph_step=True) -- training_step, loss scaling and backward replayed from one hipGraph after two
-eager steps; reports whether the graph was captured and how many of the timed steps were replays."""
+eager steps; reports whether the graph was captured and how many of the timed steps were replays.
+--trainer --deterministic: Trainer(deterministic=True), the bit-reproducible step (profiles/matcher_deterministic_ab.txt)."""
 import argparse
 import os
 import sys
@@ -47,10 +48,12 @@ def main():
     ap.add_argument("--trainer", action="store_true",
                     help="drive the step through Trainer(model, precision=...).step instead of by hand")
     ap.add_argument("--graph", action="store_true", help="with --trainer: Trainer(graph_step=True), the step replayed from a hipGraph")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="with --trainer: Trainer(deterministic=True) -- bit-reproducible steps (the order-free warp backward)")
     ap.add_argument("--census", action="store_true", help="torch.profiler on one step: ATen operators with device time, by input shape")
     args = ap.parse_args()
-    if args.graph and not args.trainer:
-        ap.error("--graph needs --trainer")
+    if (args.graph or args.deterministic) and not args.trainer:
+        ap.error("--graph and --deterministic need --trainer")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = config.build_model({"model": MODEL, "optimizer": OPTIM, "lr_scheduler": SCHED}).to(dev).train()
@@ -74,7 +77,8 @@ def main():
     trainer = None
     if args.trainer:
         from refign_amd.trainer import Trainer
-        trainer = Trainer(model, precision=16 if amp else None, **({"graph_step": True} if args.graph else {}))
+        trainer = Trainer(model, precision=16 if amp else None, deterministic=args.deterministic,
+                          **({"graph_step": True} if args.graph else {}))
         batch["prime_trg_idx"] = torch.tensor(batch["prime_trg_idx"], device=dev)
 
     replays = [0]
@@ -134,6 +138,8 @@ def main():
     how = " through Trainer.step" if trainer is not None else ""
     if args.graph:
         how += " (graph_step)"
+    if args.deterministic:
+        how += " (deterministic)"
     print(f"matcher training step{how} b={b} {S}x{S} {args.precision}: {dt * 1e3:.1f} ms/step (host enqueue {host * 1e3:.1f} ms), {b / dt:.2f} image-triplets/s, "
           f"loss {float(loss):.3f}, max mem {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
     print(f"one step at a time on an idle device: {alone * 1e3:.1f} ms/step, host enqueue {alone_host * 1e3:.1f} ms")
