@@ -175,7 +175,7 @@ class UncertaintyModule(nn.Module):
         b, _, h, w = corr.shape
 
         def retile(y, k):                                # (b, C, k h + 2 - 2.., ..): valid part of every (k+2)-tile
-            r = matching.retile_valid(y, h, w, k)        # one gather kernel on channels-last memory (csrc/warp.hip)
+            r = matching.retile_valid(y, h, w, k)        # one gather kernel on channels-last memory (csrc/featmap.hip)
             if r is not None:
                 return r
             y = F.pad(y, (0, 2, 0, 2))
@@ -222,7 +222,7 @@ _POOL_KERNEL = True
 
 def _maxpool2x2(x, m):
     """nn.MaxPool2d(2, 2) (floor mode) of an NCHW-shaped tensor with channels-last 16-bit memory on the HIP kernel
-    (csrc/warp.hip rfn_maxpool2x2_nhwc16); None outside that domain."""
+    (csrc/featmap.hip rfn_maxpool2x2_nhwc16); None outside that domain."""
     def two(v):
         return v == 2 or tuple(v) == (2, 2) if not isinstance(v, int) else v == 2
     if not (two(m.kernel_size) and two(m.stride) and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1))

@@ -32,6 +32,7 @@
 
 #include <hip/hip_fp16.h>
 
+#include "bilinear.h"
 #include "common.h"
 
 namespace rfn {
@@ -69,42 +70,6 @@ constexpr int kTH = 8;             // tile height
 constexpr int kCC = 8;             // channels per chunk
 constexpr int kStrips = 16;        // 4-pixel strips per tile row
 constexpr int kPitch = kTW + 2 * kHalo;  // 72 dwords: LDS row pitch of BOTH tiles (same bank geometry)
-
-// bilinear tap of the warp (matching_utils.py:35-43): returns the 4 clamped offsets and weights (0 for taps
-// outside the image => zero padding).
-struct WarpTap {
-  int o00, o01, o10, o11;
-  float w00, w01, w10, w11;
-};
-
-__device__ __forceinline__ WarpTap make_tap(float gx, float gy, float fx, float fy, int H, int W) {
-#pragma clang fp contract(off)
-  // normalise exactly as the reference does (2*v/max(W-1,1) - 1), then ATen's align_corners=True unnormalise
-  const float wm = (float)max(W - 1, 1), hm = (float)max(H - 1, 1);
-  float vx = 2.0f * (gx + fx) / wm - 1.0f;
-  float vy = 2.0f * (gy + fy) / hm - 1.0f;
-  float ix = ((vx + 1.0f) / 2.0f) * (float)(W - 1);
-  float iy = ((vy + 1.0f) / 2.0f) * (float)(H - 1);
-  float x0f = floorf(ix), y0f = floorf(iy);
-  float tx = ix - x0f, ty = iy - y0f;
-  // guard int conversion against huge / NaN flows
-  x0f = fminf(fmaxf(x0f, -2.0f), (float)W);
-  y0f = fminf(fmaxf(y0f, -2.0f), (float)H);
-  if (!(ix == ix) || !(iy == iy)) { x0f = -2.0f; y0f = -2.0f; }
-  int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
-  bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
-  bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-  int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-  int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
-  WarpTap t;
-  t.o00 = cy0 * W + cx0; t.o01 = cy0 * W + cx1; t.o10 = cy1 * W + cx0; t.o11 = cy1 * W + cx1;
-  float ax = 1.0f - tx, ay = 1.0f - ty;
-  t.w00 = (vx0 && vy0) ? ax * ay : 0.0f;
-  t.w01 = (vx1 && vy0) ? tx * ay : 0.0f;
-  t.w10 = (vx0 && vy1) ? ax * ty : 0.0f;
-  t.w11 = (vx1 && vy1) ? tx * ty : 0.0f;
-  return t;
-}
 
 template <bool FUSE, bool WARP>
 __global__ __launch_bounds__(kTH * kStrips * 3) void corr9_tile_kernel(
@@ -191,14 +156,15 @@ __global__ __launch_bounds__(kTH * kStrips * 3) void corr9_tile_kernel(
         WarpTap t;
         if (inside) {
           const float fx = fl[(size_t)gy * W + gx], fy = fl[plane + (size_t)gy * W + gx];
-          t = make_tap((float)gx, (float)gy, fx, fy, H, W);
+          t = warp_tap((float)gx, (float)gy, fx, fy, H, W);
         }
 #pragma unroll
         for (int c = 0; c < CC; ++c) {
           float val = 0.0f;
           if (inside && c0 + c < C) {
             const float* src = p2 + (size_t)(c0 + c) * plane;
-            // same accumulation order as ATen's grid_sampler_2d (nw, ne, sw, se)
+            // ATen's grid_sampler_2d order (nw, ne, sw, se), but NOT bilinear.h tap_sample: this sum contracts into one product
+            // and three fmas, tap_sample rounds every product -- the two differ in the last bits, so the loop stays written out
             val = src[t.o00] * t.w00 + src[t.o01] * t.w01 + src[t.o10] * t.w10 + src[t.o11] * t.w11;
           }
           s2[(c * R2 + r) * kPitch + x] = val;

@@ -5,6 +5,7 @@
 //   * upsample_bilinear2d_bwd: gather form of the backward of F.interpolate(mode='bilinear', align_corners=False).  ATen's
 //     backward scatters every output gradient into its four source cells with atomics; here one thread owns one INPUT cell
 //     and adds the output pixels that read it in raster order.
+#include "bilinear.h"
 #include "common.h"
 
 namespace rfn {
@@ -45,24 +46,6 @@ int ordered_colsum_f64(const double* part, double* out, long rows, int cols, hip
   return ordered_colsum<double>(part, out, rows, cols, st);
 }
 
-// ATen area_pixel_compute_source_index (align_corners = false) + the neighbours / weight of upsample_bilinear2d (as
-// loss.hip src_index)
-__device__ __forceinline__ void bil_src(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
-
-// first output index whose i0 or i1 can be `cell`, and one past the last: a conservative window from the inverse of the
-// source-index map (the exact membership test is made per output pixel)
-__device__ __forceinline__ void bil_window(int cell, float scale, int out_size, int& lo, int& hi) {
-  const float inv = 1.f / scale;
-  // (cells 0 and 1: the outputs whose source index was clamped to 0 read them too, with weight 1 and 0)
-  lo = cell <= 1 ? 0 : max(0, (int)floorf(((float)cell - 1.f + 0.5f) * inv - 0.5f) - 1);
-  hi = min(out_size, (int)ceilf(((float)cell + 1.f + 0.5f) * inv - 0.5f) + 2);
-}
-
 template <typename T>
 __device__ __forceinline__ float bil_ld(const T* p, long i) { return (float)p[i]; }
 
@@ -77,21 +60,21 @@ __global__ __launch_bounds__(256) void upsample_bilinear2d_bwd_kernel(const T* _
     const int x = (int)(i % w), y = (int)((i / w) % h);
     const long pl = i / ((long)w * h);
     int Ylo, Yhi, Xlo, Xhi;
-    bil_window(y, sy, H, Ylo, Yhi);
-    bil_window(x, sx, W, Xlo, Xhi);
+    up_cell_window(y, sy, H, Ylo, Yhi);
+    up_cell_window(x, sx, W, Xlo, Xhi);
     const T* g = gout + pl * (long)H * W;
     float acc = 0.f;
     for (int Y = Ylo; Y < Yhi; ++Y) {
       int a0, a1;
       float ly;
-      bil_src(Y, sy, h, a0, a1, ly);
+      up_src(Y, sy, h, a0, a1, ly);
       if (a0 != y && a1 != y) continue;
       const float wy = (a0 == y ? 1.f - ly : 0.f) + (a1 == y ? ly : 0.f);
       float row = 0.f;
       for (int X = Xlo; X < Xhi; ++X) {
         int b0, b1;
         float lx;
-        bil_src(X, sx, w, b0, b1, lx);
+        up_src(X, sx, w, b0, b1, lx);
         if (b0 != x && b1 != x) continue;
         const float wx = (b0 == x ? 1.f - lx : 0.f) + (b1 == x ? lx : 0.f);
         row = fmaf(wx, bil_ld<T>(g, (long)Y * W + X), row);

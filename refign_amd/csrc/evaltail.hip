@@ -16,6 +16,7 @@
 //   * counts go to a C x C histogram in LDS (integer atomics) that is added to the global matrix once per workgroup, non-zero
 //     entries only, with 64-bit integer atomics.  Integer adds commute: the result does not depend on scheduling.
 // That every pixel lies in some box is checked on the HOST from the box list (no device-side assert, no synchronisation).
+#include "bilinear.h"
 #include "common.h"
 
 namespace rfn {
@@ -39,14 +40,6 @@ template <> struct EtElem<1> {
 template <> struct EtElem<2> {
   static __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const _Float16*)p)[i]; }
 };
-
-// ATen area_pixel_compute_source_index (align_corners = false) + the neighbour / lambda of upsample_bilinear2d
-__device__ __forceinline__ void et_src_index(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
 
 template <int DT, int CMAX>
 __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_kernel(const void* __restrict__ crops, EtBoxes boxes, int nbox,
@@ -84,10 +77,10 @@ __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_
       if (ya > yb || xa > xb) continue;
       int fy0, fy1, fx0, fx1, t0, t1;
       float l;
-      et_src_index(ya - y1, sy, h, fy0, t1, l);
-      et_src_index(yb - y1, sy, h, t0, fy1, l);
-      et_src_index(xa - x1, sx, w, fx0, t1, l);
-      et_src_index(xb - x1, sx, w, t0, fx1, l);
+      up_src(ya - y1, sy, h, fy0, t1, l);
+      up_src(yb - y1, sy, h, t0, fy1, l);
+      up_src(xa - x1, sx, w, fx0, t1, l);
+      up_src(xb - x1, sx, w, t0, fx1, l);
       const int nfy = fy1 - fy0 + 1, nfx = fx1 - fx0 + 1, cells = nfy * nfx;
       const bool staged = cells * S <= kEtCap;
       const long base = ((long)k * B + b) * C * plane;             // crop k of image b: row k * B + b
@@ -104,8 +97,8 @@ __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_
       if (live && y >= y1 && y < y2 && x >= x1 && x < x2) {
         int a0, a1, b0, b1;
         float ly, lx;
-        et_src_index(y - y1, sy, h, a0, a1, ly);
-        et_src_index(x - x1, sx, w, b0, b1, lx);
+        up_src(y - y1, sy, h, a0, a1, ly);
+        up_src(x - x1, sx, w, b0, b1, lx);
         const float hy = 1.f - ly, hx = 1.f - lx;
         ++cnt;
         if (staged) {

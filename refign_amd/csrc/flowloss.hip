@@ -11,6 +11,7 @@
 // (nothing per pixel is saved) and scales by grad_out * weight / count, all read on the device.
 #include <cmath>
 
+#include "bilinear.h"
 #include "common.h"
 
 namespace rfn {
@@ -31,16 +32,6 @@ struct FlTable {
   FlLevel l[kFlMaxLevels];
   int n;
 };
-
-// one axis of upsample_bilinear2d, align_corners=False: two taps and their weights
-__device__ __forceinline__ void fl_taps(int o, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-  float s = scale * ((float)o + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
 
 // the per-channel term and its derivative.  loss_type: 0 L1Loss, 1 L2Loss (MSE), 2 HuberLoss = 2 delta smooth_l1(beta = delta)
 __device__ __forceinline__ float fl_term(float d, int loss_type, float delta, float& dd) {
@@ -71,9 +62,10 @@ struct FlPixel {
 __device__ __forceinline__ FlPixel fl_pixel(const FlLevel& L, const float* __restrict__ gt, int H, int W, int b, int y, int x,
                                             int loss_type, float delta) {
   int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-  fl_taps(y, (float)H / (float)L.h, H, y0, y1, ly0, ly1);
-  fl_taps(x, (float)W / (float)L.w, W, x0, x1, lx0, lx1);
+  float ly1, lx1;
+  up_src(y, (float)H / (float)L.h, H, y0, y1, ly1);
+  up_src(x, (float)W / (float)L.w, W, x0, x1, lx1);
+  const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
   const long hw = (long)L.h * L.w, pix = (long)y * L.w + x;
   FlPixel r;
   float loss = 0.f, dd[2];

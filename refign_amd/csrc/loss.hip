@@ -18,6 +18,7 @@
 // upstream gradient.  Scale factors >= 2 in both directions (the footprint bound above); anything else stays on ATen.
 #include <hip/hip_bf16.h>
 
+#include "bilinear.h"
 #include "common.h"
 #include "mfma.h"
 
@@ -45,14 +46,6 @@ template <> struct LossElem<2> {
   static __device__ __forceinline__ float round(float v) { return (float)(_Float16)v; }
 };
 
-// ATen area_pixel_compute_source_index (align_corners = false, not cubic) + the neighbour / lambda of upsample_bilinear2d
-__device__ __forceinline__ void src_index(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-  const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
-
 // FULLC: C == kLossMaxC, no per-class guards (with a run-time class count every class of every loop is a branch)
 template <int DT, bool FULLC>
 __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict__ logits, const long* __restrict__ target,
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
   if (tid < kLossTH) {
     int i0, i1;
     float l;
-    src_index(min(Y0 + tid, H - 1), sy, h, i0, i1, l);
+    up_src(min(Y0 + tid, H - 1), sy, h, i0, i1, l);
     ry0[tid] = i0;
     ry1[tid] = i1;
     rl[tid] = l;
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
     const int t = tid - 64;
     int i0, i1;
     float l;
-    src_index(min(X0 + t, W - 1), sx, w, i0, i1, l);
+    up_src(min(X0 + t, W - 1), sx, w, i0, i1, l);
     cx0[t] = i0;
     cx1[t] = i1;
     cl[t] = l;
@@ -205,14 +198,6 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
   }
 }
 
-// first output index whose source cells can include `cell`, and one past the last: a conservative window from the inverse of
-// src_index (membership is tested exactly per tile)
-__device__ __forceinline__ void cell_window(int cell, float scale, int out_size, int& lo, int& hi) {
-  const float inv = 1.f / scale;
-  lo = cell <= 1 ? 0 : max(0, (int)floorf(((float)cell - 0.5f) * inv - 0.5f) - 1);
-  hi = min(out_size, (int)ceilf(((float)cell + 1.5f) * inv - 0.5f) + 2);
-}
-
 // Deterministic form, second launch: grad_lo[b][c][y][x] = sum, over the tiles whose footprint holds the cell (tile rows outer,
 // tile columns inner, ascending), of that tile's partial.  One thread per low-resolution cell.
 __global__ __launch_bounds__(256) void upsample_ce_gather_kernel(const float* __restrict__ tile_part, float* __restrict__ grad_lo,
@@ -222,21 +207,21 @@ __global__ __launch_bounds__(256) void upsample_ce_gather_kernel(const float* __
   if (i >= total) return;
   const int x = (int)(i % w), y = (int)((i / w) % h), c = (int)((i / ((long)w * h)) % C), b = (int)(i / ((long)w * h * C));
   int Ylo, Yhi, Xlo, Xhi;
-  cell_window(y, sy, H, Ylo, Yhi);
-  cell_window(x, sx, W, Xlo, Xhi);
+  up_cell_window(y, sy, H, Ylo, Yhi);
+  up_cell_window(x, sx, W, Xlo, Xhi);
   float acc = 0.f;
   for (int TY = Ylo / kLossTH; TY <= (Yhi - 1) / kLossTH; ++TY) {
     const int Y0 = TY * kLossTH, YN = min(kLossTH, H - Y0);
     int f0, f1, t0, t1;
     float l;
-    src_index(Y0, sy, h, f0, t1, l);
-    src_index(Y0 + YN - 1, sy, h, t0, f1, l);
+    up_src(Y0, sy, h, f0, t1, l);
+    up_src(Y0 + YN - 1, sy, h, t0, f1, l);
     if (y < f0 || y > f1) continue;
     for (int TX = Xlo / kLossTW; TX <= (Xhi - 1) / kLossTW; ++TX) {
       const int X0 = TX * kLossTW, XN = min(kLossTW, W - X0);
       int g0, g1;
-      src_index(X0, sx, w, g0, t1, l);
-      src_index(X0 + XN - 1, sx, w, t0, g1, l);
+      up_src(X0, sx, w, g0, t1, l);
+      up_src(X0 + XN - 1, sx, w, t0, g1, l);
       if (x < g0 || x > g1) continue;
       const long tile = ((long)b * tiles_y + TY) * tiles_x + TX;
       acc += tile_part[((tile * C + c) * kLossFY + (y - f0)) * kLossFX + (x - g0)];

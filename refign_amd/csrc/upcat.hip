@@ -15,6 +15,7 @@
 
 #include <type_traits>
 
+#include "bilinear.h"
 #include "common.h"
 
 namespace rfn {
@@ -78,9 +79,12 @@ __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restr
   const T* s = reinterpret_cast<const T*>(a.src[l]) + (size_t)n * hl * wl * CVl * 8 + (size_t)cl * 8;
   const size_t st = (size_t)CVl * 8;
   const bool same = hl == H && wl == W;
-  const float sy = fmaxf(((float)y + 0.5f) * ((float)hl / (float)H) - 0.5f, 0.0f);
-  const int y0 = same ? y : (int)sy, y1 = min(y0 + 1, hl - 1);
-  const float ly = same ? 0.f : sy - (float)y0;
+  // bilinear.h up_src without its clamp of i0, here and below: this file never clamped i0 and relies on up-sampling (hl <= H,
+  // wl <= W: s < in - 0.5 for every dst < out), so the clamp would be a no-op; a level of the output's own size has scale 1:
+  // s = dst exactly, weight 0.
+  int y0, y1;
+  float ly;
+  up_src<false>(y, (float)hl / (float)H, hl, y0, y1, ly);
   typedef typename std::conditional<sizeof(T) == 2, uint4, float4>::type V16;     // 16 bytes: 8 bf16 or 4 floats
   constexpr int NV = sizeof(T) == 2 ? 1 : 2;
   V16 v[kUpPX][4][NV];
@@ -88,9 +92,8 @@ __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restr
 #pragma unroll
   for (int p = 0; p < kUpPX; ++p) {
     const int x = min(xq * kUpPX + p, W - 1);
-    const float sx = fmaxf(((float)x + 0.5f) * ((float)wl / (float)W) - 0.5f, 0.0f);
-    const int x0 = same ? x : (int)sx, x1 = min(x0 + 1, wl - 1);
-    lx[p] = same ? 0.f : sx - (float)x0;
+    int x0, x1;
+    up_src<false>(x, (float)wl / (float)W, wl, x0, x1, lx[p]);
     const T* p00 = s + ((size_t)y0 * wl + x0) * st;
     const T* p01 = s + ((size_t)y0 * wl + x1) * st;
     const T* p10 = s + ((size_t)y1 * wl + x0) * st;
@@ -186,21 +189,23 @@ __global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, con
     add(gb + ((size_t)ys * W + xs) * CV * 8, 1.0f);
   } else {
     const float ry = (float)hl / (float)H, rx = (float)wl / (float)W;       // the forward's scales
+    // (not bilinear.h up_cell_window: this window divides by the scale and does not widen cells 0 and 1 to output 0, so it leaves
+    // out zero-weight outputs that the shared one would visit -- the terms skipped below either way)
     const int ylo = max(0, (int)floorf(((float)ys - 0.5f) / ry - 0.5f) - 1);
     const int yhi = min(H - 1, (int)ceilf(((float)ys + 1.5f) / ry - 0.5f) + 1);
     const int xlo = max(0, (int)floorf(((float)xs - 0.5f) / rx - 0.5f) - 1);
     const int xhi = min(W - 1, (int)ceilf(((float)xs + 1.5f) / rx - 0.5f) + 1);
     for (int y = ylo; y <= yhi; ++y) {
-      const float sy = fmaxf(((float)y + 0.5f) * ry - 0.5f, 0.0f);
-      const int y0 = (int)sy, y1 = min(y0 + 1, hl - 1);
-      const float ly = sy - (float)y0;
+      int y0, y1;
+      float ly;
+      up_src<false>(y, ry, hl, y0, y1, ly);
       const float wy = (y0 == ys ? 1.0f - ly : 0.0f) + (y1 == ys ? ly : 0.0f);
       if (wy == 0.0f) continue;
       const T* row = gb + (size_t)y * W * CV * 8;
       for (int x = xlo; x <= xhi; ++x) {
-        const float sx = fmaxf(((float)x + 0.5f) * rx - 0.5f, 0.0f);
-        const int x0 = (int)sx, x1 = min(x0 + 1, wl - 1);
-        const float lx = sx - (float)x0;
+        int x0, x1;
+        float lx;
+        up_src<false>(x, rx, wl, x0, x1, lx);
         const float wx = (x0 == xs ? 1.0f - lx : 0.0f) + (x1 == xs ? lx : 0.0f);
         if (wx != 0.0f) add(row + (size_t)x * CV * 8, wy * wx);
       }

@@ -1,5 +1,6 @@
 """Host mirror of helpers/matching_utils.py for the functions on the hot path (warp, mapping->flow, confidence),
-backed by the HIP kernels in csrc/warp.hip.  Same names, argument meaning and return conventions."""
+backed by the HIP kernels in csrc/warp.hip (warp, align tail) and csrc/featmap.hip (L2 norm, area resize, max-pool,
+re-tile).  Same names, argument meaning and return conventions."""
 import os
 
 import torch
@@ -136,7 +137,7 @@ def uncertainty9_frontend(corr, packed_weights, half_matrix=False):
 
 
 class _RetileFn(torch.autograd.Function):
-    """csrc/warp.hip rfn_retile_copy under autograd: y (B, C, (k+2) h - 2, (k+2) w - 2) with channels-last memory (pixels `S` elements
+    """csrc/featmap.hip rfn_retile_copy under autograd: y (B, C, (k+2) h - 2, (k+2) w - 2) with channels-last memory (pixels `S` elements
     apart, S >= C: the convolution kernels pad their output channels) -> (B, C, k h, k w), channels-last."""
 
     @staticmethod

@@ -508,7 +508,7 @@ def test_label_majority_kernel_matches_one_hot_pooling(H, W, scale, minr):
 @pytest.mark.parametrize("B,C,H,W", [(2, 64, 18, 22), (1, 128, 17, 19), (3, 8, 2, 2), (1, 256, 33, 62)])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_maxpool2x2_kernel_equals_max_pool2d(B, C, H, W, dtype):
-    """csrc/warp.hip rfn_maxpool2x2_nhwc16 (the VGG pyramid's nn.MaxPool2d(2, 2), floor mode) on channels-last 16-bit maps,
+    """csrc/featmap.hip rfn_maxpool2x2_nhwc16 (the VGG pyramid's nn.MaxPool2d(2, 2), floor mode) on channels-last 16-bit maps,
     odd extents included: bit-equal to F.max_pool2d."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
@@ -525,7 +525,7 @@ def test_maxpool2x2_kernel_equals_max_pool2d(B, C, H, W, dtype):
 @pytest.mark.parametrize("B,C,h,w,k,dt", [(2, 32, 5, 7, 7, torch.float16), (1, 16, 9, 4, 3, torch.float32), (3, 32, 4, 6, 5, torch.bfloat16),
                                           (1, 8, 3, 3, 1, torch.float16)])
 def test_retile_valid_equals_pad_view_slice(dev, B, C, h, w, k, dt):
-    """csrc/warp.hip rfn_retile_copy (the uncertainty head's micro-image chain under autograd, models/modules.py:528-545 as tiles of
+    """csrc/featmap.hip rfn_retile_copy (the uncertainty head's micro-image chain under autograd, models/modules.py:528-545 as tiles of
     one image): the k x k valid part of every (k + 2)-tile == F.pad + 6-d view + slice + reshape, forward and gradient, bit for bit
     (a gather each way)."""
     import torch.nn.functional as F

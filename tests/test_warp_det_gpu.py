@@ -3,8 +3,8 @@ per-group partials for grad_flow) and the fp32 gather backward of the generic co
 through determinism.deterministic(scatter_forms=True).
 
 The reference of the warp is an fp64 restatement on the CPU built from the SAME fp32 tap weights: the operations of the kernels'
-bilinear_tap, in its order, on fp32 CPU tensors (every one of them an IEEE operation on both sides), then products and sums in
-fp64.  Bounds (include/refign_hip.h), per element:
+warp_tap (csrc/bilinear.h, which also states the tap validity and `finite`), in its order, on fp32 CPU tensors (every one of them
+an IEEE operation on both sides), then products and sums in fp64.  Bounds (include/refign_hip.h), per element:
   grad_x     |got - ref| <= 2^-22 S + 2^-30 M,  S = sum |g w| over the element's terms, M = the plane's largest |g|
              (2^-23 S: the fp32 product of every term and the final rounding; the quantisation is H W u / 2 <= M 2^(2 L - 62),
              below 2^-38 M at these sizes; the factor 2 absorbs a last-bit difference of a tap weight between host and device);
@@ -26,7 +26,7 @@ _MEMO = {}
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
 def _taps(flow):
-    """bilinear_tap and the validity of warp_bwd_kernel on fp32 CPU tensors -> offsets (4, B, H, W) int64, validity (4, ...) bool,
+    """warp_tap (csrc/bilinear.h), its validity flags and its `finite`, on fp32 CPU tensors -> offsets (4, B, H, W) int64, validity (4, ...) bool,
     weights (4, ...) fp32 in the order nw, ne, sw, se, the fractions (tx, ty, ax, ay) and `finite`."""
     B, _, H, W = flow.shape
     f32 = torch.float32
@@ -212,6 +212,46 @@ def test_general_case_within_the_rounding_bound(dev, shape):
     assert torch.equal(_det_entry(xd, fd, gd, want_f=False)[0].view(torch.int32), gx.view(torch.int32))
     gx2, gf2 = _det_entry(xd, fd, gd)
     assert torch.equal(gx2.view(torch.int32), gx.view(torch.int32)) and torch.equal(gf2.view(torch.int32), gf.view(torch.int32))
+
+
+def _odd_flow_inputs(C):
+    """(1, C, 5, 7) exact inputs whose first pixels carry the flows on which a guard of the int conversion decides: NaN, the
+    infinities, +-2e9 (beyond int32), +-1e5 (finite, far outside), W + 0.5 and -1.5, in either component; quarter-pixel flows
+    elsewhere (drawn as in _exact_inputs, so every surviving tap weight is a multiple of 1/16).  -> x, flow, grad_out, the
+    reference, and the mask of the pixels that are non-finite or far."""
+    key = ("odd", C)
+    if key not in _MEMO:
+        B, H, W = 1, 5, 7
+        x, flo, go, _ = _exact_inputs((B, C, H, W))
+        nan, inf = float("nan"), float("inf")
+        odd = [(nan, None), (None, nan), (nan, nan), (inf, None), (None, -inf), (-inf, inf), (2e9, None), (None, -2e9), (-2e9, 2e9),
+               (1e5, None), (None, -1e5), (-1e5, 1e5), (W + 0.5, None), (None, H + 0.5), (-1.5, None), (None, -1.5), (None, -1.5)]
+        flo = flo.clone()
+        # (None: the component keeps its exact draw.  -1.5 along x is pixel 14 = column 0: both taps outside)
+        for p, (fx, fy) in enumerate(odd):
+            for c, f in enumerate((fx, fy)):
+                if f is not None:
+                    flo[0, c, p // W, p % W] = f
+        _, valid, w, _, finite = _taps(flo)
+        assert bool((w * 16 == torch.floor(w * 16)).all()) and bool(valid.any(0)[0, 2, 1:3].all())    # (the two -1.5 rows keep taps)
+        far = ~finite | (flo.abs() >= 1e5).any(1)
+        assert int(far.sum()) == 12 and not bool(valid[:, far].any())
+        _MEMO[key] = (x, flo, go, _reference(x, flo, go), far)
+    return _MEMO[key]
+
+
+@pytest.mark.parametrize("C", [3, 40])                      # one channel group, two
+def test_non_finite_and_far_flows(dev, C):
+    """The tap validity (warp_tap, csrc/bilinear.h) where the conversion to int is guarded: both forms of the backward drop every
+    tap of such a pixel, give it no flow gradient, and agree with the fp64 reference bit for bit."""
+    x, flo, go, (gx_ref, _, gf_ref, _), far = _odd_flow_inputs(C)
+    xd, fd, gd = x.to(dev), flo.to(dev), go.to(dev)
+    want = (gx_ref.float() + 0.0).view(torch.int32)
+    for name, (gx, gf) in (("rfn_warp_bwd_det_f32", _det_entry(xd, fd, gd)), ("rfn_warp_bwd_f32", _default_entry(xd, fd, gd))):
+        gf = gf.cpu()
+        assert bool((gf[:, 0][far] == 0).all()) and bool((gf[:, 1][far] == 0).all()), f"{name}: flow gradient at a far pixel"
+        assert torch.equal(gx.cpu().view(torch.int32), want), f"{name}: grad_x differs from fp64"
+        assert torch.equal(gf, gf_ref.float()), f"{name}: grad_flow differs from fp64"
 
 
 def test_collision_case_repeats_its_bits(dev):

@@ -1,6 +1,6 @@
 // tools/experiments/matrix_pipe_corr/split_f16.hip -- operand producer of the matrix-pipe correlation experiment (round 3):
 // fp32 NCHW features -> split-fp16 chunk-major, optionally warped on the way.  Uses the bilinear-tap helpers of the product's
-// warp.hip (included as source: this is a tools build, its copies of warp's entry points stay inside this library).
+// bilinear.h through warp.hip (included as source: this is a tools build, its copies of warp's entry points stay inside this library).
 #include "../../../refign_amd/csrc/warp.hip"
 
 namespace rfn {
@@ -19,11 +19,11 @@ __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict_
   if (pix >= HW) return;
   const int n = blockIdx.z, chunk = blockIdx.y, NC = C / 32;
   const float* src = x + ((size_t)n * C + (size_t)chunk * 32) * HW;
-  Tap t;
+  WarpTap t;
   if (flow != nullptr) {
     const int gy = pix / W, gx = pix - gy * W;
     const float* fl = flow + (size_t)n * 2 * HW;
-    t = bilinear_tap((float)gx, (float)gy, fl[pix], fl[HW + pix], H, W);
+    t = warp_tap((float)gx, (float)gy, fl[pix], fl[HW + pix], H, W);
   }
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   unsigned hi[16], lo[16];
