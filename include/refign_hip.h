@@ -812,6 +812,36 @@ int rfn_grad_sqnorm_groups(const float* flat, long n, const long* chunks, int nc
                            double* out, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Gradient clipping (csrc/steplog.hip, refign_amd/steplog.py; additions to ABI 5): Lightning's gradient_clip_val /
+ * gradient_clip_algorithm on the flat fp32 gradient buffer, decided and applied on the device with no host
+ * synchronisation.  No floating-point atomics: legal under rfn_set_deterministic(1), bit-identical from launch to launch.
+ *   rfn_grad_clip_coef      torch.nn.utils.clip_grad_norm_'s coefficient, one small launch: total = sqrt(sqnorms[0] + ... +
+ *                           sqnorms[ngroups - 1]) added in that order in fp64 (sqnorms: the first ngroups values of
+ *                           rfn_grad_sqnorm_groups' out), c = max_norm / (total + 1e-6), coef[0] = (float)(c > 1 ? 1 : c),
+ *                           coef[1] = (float)total.  A NaN norm gives a NaN coefficient, an infinite one 0.  coef: 2 DEVICE
+ *                           floats.  Errors: a null pointer, ngroups outside 1 ... 32, max_norm negative or NaN.
+ *   rfn_grad_scale_f32      grads[i] *= coef[0] in place (n fp32, 16-byte aligned; coef in DEVICE memory).  Every workgroup
+ *                           returns at once when coef[0] == 1: a step that does not clip pays the launch and one read, and
+ *                           the buffer keeps every bit (the product with 1 would change none).
+ *   rfn_grad_clamp_f32      torch.nn.utils.clip_grad_value_: grads[i] into [-clip_value, clip_value] in place; a NaN stays
+ *                           a NaN.  Errors: clip_value negative or NaN.
+ *   rfn_amp_unscale_sqnorm_groups_f32
+ *                           rfn_amp_unscale_f32 and rfn_grad_sqnorm_groups in ONE pass over the gradient, bit-equal to the
+ *                           two calls one after the other in grads, found_inf (zeroed by the caller) and all ngroups + 1
+ *                           values of out: inside every chunk of the table each element is tested for inf / NaN as it
+ *                           stands, multiplied by float(1 / double(*scale)) and stored, and the fp64 partial is taken of the
+ *                           stored values in rfn_grad_sqnorm_groups' order.  Elements outside every chunk are NOT touched
+ *                           (the caller's table covers everything but zero-filled alignment gaps); a chunk outside [0, n)
+ *                           or with a group outside [0, ngroups) is neither read nor written and counts as a non-finite
+ *                           partial.  chunks / partials / out: as rfn_grad_sqnorm_groups.
+ * ------------------------------------------------------------------------------------------------------------ */
+int rfn_grad_clip_coef(const double* sqnorms, int ngroups, float max_norm, float* coef, rfn_stream_t stream);
+int rfn_grad_scale_f32(float* grads, long n, const float* coef, rfn_stream_t stream);
+int rfn_grad_clamp_f32(float* grads, long n, float clip_value, rfn_stream_t stream);
+int rfn_amp_unscale_sqnorm_groups_f32(float* grads, long n, const long* chunks, int nchunks, int ngroups, const float* scale,
+                                      float* found_inf, double* partials, double* out, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Warp supervision of the matcher (csrc/flowsynth.hip, refign_amd/flowsynth.py; additions to ABI 4): the reference's
  * CompositeFlow + CenterCrop for ONE sample per call, fp32, no floating-point atomics (legal under
  * rfn_set_deterministic(1)).  Errors (nothing is launched): a null pointer, h or w < 2, a crop that does not lie in the

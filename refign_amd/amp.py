@@ -4,7 +4,8 @@ torch.amp.GradScaler around a non-fused torch.optim.AdamW), with every decision 
 torch's GradScaler reads `found_inf` on the host in every `step()` to decide whether to call the optimizer.  Here the
 scale, the found-inf flag and the growth tracker are device tensors, and the three kernels of csrc/reduce.hip run in
 stream order with no host synchronisation:
-  unscale_   g *= 1 / scale over the flat gradient buffer, found_inf = 1 if any gradient is inf / NaN;
+  unscale_   g *= 1 / scale over the flat gradient buffer, found_inf = 1 if any gradient is inf / NaN
+             (unscale_sqnorm_: the same with the squared norms per optimizer group from the same pass, csrc/steplog.hip);
   (AdamW)    optim.MultiTensorAdamW.step_amp: the update is a no-op when found_inf is set (step count on the device);
   update     backoff on inf, growth after `growth_interval` clean steps (torch._amp_update_scale_).
 `state_dict()` / `load_state_dict()` speak GradScaler's format, so a Lightning checkpoint's `native_amp_scaling_state`
@@ -37,6 +38,20 @@ class LossScaler:
             raise RuntimeError("LossScaler.unscale_: a contiguous, 16-byte aligned fp32 CUDA buffer is required")
         self.found_inf.zero_()
         _lib.call("rfn_amp_unscale_f32", grads.device, ptr(grads), grads.numel(), ptr(self._scale), ptr(self.found_inf))
+
+    def unscale_sqnorm_(self, grads, plan, out):
+        """unscale_ and steplog.grad_sqnorm_groups(grads, plan, out) in ONE pass over the buffer, bit-equal to the two calls one
+        after the other (norm clipping decides on the unscaled gradient's norm: steplog.GradClip).  Only the chunks of `plan`
+        are touched: what lies between them must be the zero-filled alignment gaps of a trainer.FlatGradBuffer."""
+        if not (grads.is_cuda and grads.dtype == torch.float32 and grads.is_contiguous() and grads.data_ptr() % 16 == 0):
+            raise RuntimeError("LossScaler.unscale_sqnorm_: a contiguous, 16-byte aligned fp32 CUDA buffer is required")
+        if grads.numel() != plan.numel or grads.device != plan.device or not plan.chunks:
+            raise RuntimeError("LossScaler.unscale_sqnorm_: the plan was made for another buffer, or is empty")
+        if out.dtype != torch.float64 or out.numel() != plan.ngroups + 1 or not out.is_contiguous() or out.device != grads.device:
+            raise RuntimeError("LossScaler.unscale_sqnorm_: out must hold G + 1 contiguous fp64 values on the buffer's device")
+        self.found_inf.zero_()
+        _lib.call("rfn_amp_unscale_sqnorm_groups_f32", grads.device, ptr(grads), grads.numel(), ptr(plan.table), len(plan.chunks),
+                  plan.ngroups, ptr(self._scale), ptr(self.found_inf), ptr(plan.partials), ptr(out))
 
     def update(self, optimizer_step=None):
         """After the optimizer: new scale from found_inf; `optimizer_step` (a device float tensor of the optimizer's step

@@ -132,6 +132,21 @@ def trainer_deterministic(cfg):
     return bool(v)
 
 
+def trainer_gradients(cfg):
+    """What shapes the gradient between the backward pass and the optimizer, from a loaded YAML's `trainer:` section:
+    `gradient_clip_val` (None when absent), `gradient_clip_algorithm` ("norm") and `accumulate_grad_batches` (1), checked as
+    Trainer checks them (ValueError for a negative or non-numeric threshold, an unknown algorithm, and an accumulation that
+    is no int >= 1 -- Lightning's per-epoch dict among them).  Kept out of trainer_kwargs like trainer_deterministic.
+    -> the three keywords of Trainer(model, ...)."""
+    from .trainer import parse_accumulate, parse_gradient_clip
+    tr = (cfg or {}).get("trainer") or {}
+    val, alg = tr.get("gradient_clip_val"), tr.get("gradient_clip_algorithm")
+    acc = tr.get("accumulate_grad_batches")
+    alg, acc = "norm" if alg is None else alg, 1 if acc is None else acc
+    parse_gradient_clip(val, alg)
+    return {"gradient_clip_val": val, "gradient_clip_algorithm": alg, "accumulate_grad_batches": parse_accumulate(acc)}
+
+
 def trainer_logging(cfg):
     """The record of the run as a loaded YAML asks for it: `trainer.logger` (one spec or a list; the first
     pytorch_lightning.loggers.TensorBoardLogger with its `save_dir` / `name` / `version` becomes a

@@ -1,7 +1,8 @@
 """A record of the run without the step ever waiting for the device: `StepLog`, a device ring of fp64 rows with a pinned
 host mirror and one event per row (csrc/steplog.hip fills a row: rfn_steplog_gather for the step's device scalars,
-rfn_grad_sqnorm_groups for the gradient norms per optimizer group), and `TensorBoardLogger`, which writes the rows as a
-TensorBoard event file with no dependency on the `tensorboard` package.
+rfn_grad_sqnorm_groups for the gradient norms per optimizer group), `GradClip`, which decides on those norms whether and
+how far the gradient is clipped, and `TensorBoardLogger`, which writes the rows as a TensorBoard event file with no
+dependency on the `tensorboard` package.
 
 What the reference gets from Lightning's TensorBoardLogger + LearningRateMonitor + `self.log(...)`; Trainer(logger=...)
 drives both (refign_amd/trainer.py).  With CPU tensors (the CPU tests' stand-in models) StepLog has the same interface
@@ -106,6 +107,95 @@ def grad_sqnorm_groups(flat, plan, out):
     return out
 
 
+class GradClip:
+    """Lightning's `gradient_clip_val` / `gradient_clip_algorithm` on a flat fp32 gradient buffer (Trainer drives it from
+    _OptimizerProxy.step, after the all-reduce and in front of the logged row and the optimizer).
+
+    "norm": torch.nn.utils.clip_grad_norm_(params, value) -- the 2-norm over the whole buffer, eps 1e-6, the coefficient
+    at most 1; a NaN norm multiplies NaN in, an infinite one gives coefficient 0.  "value": clip_grad_value_, every element
+    into [-value, value], a NaN kept.  On a device buffer the decision and the scaling stay on the device (csrc/steplog.hip;
+    no host synchronisation, no floating-point atomics):
+      norm            rfn_grad_sqnorm_groups, rfn_grad_clip_coef, rfn_grad_scale_f32 (which returns at once at coefficient 1)
+      norm under fp16 rfn_amp_unscale_sqnorm_groups_f32 (the scaler's unscale and the norm in one pass), coef, scale
+      value           the scaler's unscale (under fp16), rfn_grad_clamp_f32
+    On a CPU buffer it is torch's two functions themselves on the parameters whose `.grad` are the buffer's views.
+    `sqnorms` (G + 1 fp64: rfn_grad_sqnorm_groups' out, the gradient BEFORE clipping; under "value" filled only when
+    asked for) and `coef` (2 fp32: the coefficient and the total norm; "norm" only) are what the logged row takes."""
+
+    ALGORITHMS = ("norm", "value")
+
+    def __init__(self, value, algorithm="norm"):
+        if algorithm not in self.ALGORITHMS:
+            raise ValueError(f"GradClip: algorithm {algorithm!r} (one of {self.ALGORITHMS})")
+        self.value, self.algorithm = float(value), algorithm
+        self.sqnorms = self.coef = None
+
+    def __call__(self, grads, plan, scaler=None, want_norms=False):
+        """`grads`: a trainer.FlatGradBuffer; `plan`: its GradNormPlan; `scaler`: an amp.LossScaler whose unscale is still
+        to be done (it is done here, in front of the clip), or None; `want_norms`: fill `sqnorms` under "value" too."""
+        flat, G = grads.flat, plan.ngroups
+        if self.sqnorms is None:
+            self.sqnorms = torch.zeros(G + 1, dtype=torch.float64, device=flat.device)
+            self.coef = torch.ones(2, dtype=torch.float32, device=flat.device)
+        norm = self.algorithm == "norm"
+        if not flat.is_cuda:
+            if scaler is not None:
+                scaler.unscale_(flat)                         # (raises: loss scaling has no CPU form)
+            if norm or want_norms:
+                grad_sqnorm_groups(flat, plan, self.sqnorms)
+            if norm:
+                total = torch.nn.utils.clip_grad_norm_(grads.params, self.value)
+                self.coef.copy_(torch.stack([torch.clamp(self.value / (total + 1e-6), max=1.0), total]))
+            else:
+                torch.nn.utils.clip_grad_value_(grads.params, self.value)
+            return
+        if norm:
+            if scaler is not None:
+                scaler.unscale_sqnorm_(flat, plan, self.sqnorms)
+            else:
+                grad_sqnorm_groups(flat, plan, self.sqnorms)
+            grad_clip_coef(self.sqnorms, G, self.value, self.coef)
+            grad_scale_(flat, self.coef)
+            return
+        if scaler is not None:
+            scaler.unscale_(flat)
+        if want_norms:
+            grad_sqnorm_groups(flat, plan, self.sqnorms)
+        grad_clamp_(flat, self.value)
+
+
+def _flat_f32(flat, what):
+    if not (flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous() and flat.data_ptr() % 16 == 0 and flat.numel()):
+        raise RuntimeError(f"{what}: a non-empty contiguous, 16-byte aligned fp32 device buffer is required")
+
+
+def grad_clip_coef(sqnorms, ngroups, max_norm, coef):
+    """coef[0] <- min(1, max_norm / (sqrt(sqnorms[0] + ... + sqnorms[ngroups - 1]) + 1e-6)), coef[1] <- that norm: one launch,
+    fp64 inside.  `sqnorms`: contiguous fp64 device values (grad_sqnorm_groups' out), `coef`: 2 contiguous fp32 next to them."""
+    if sqnorms.dtype != torch.float64 or not sqnorms.is_contiguous() or sqnorms.numel() < ngroups or not sqnorms.is_cuda:
+        raise RuntimeError("grad_clip_coef: sqnorms must hold `ngroups` contiguous fp64 device values")
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() != 2 or coef.device != sqnorms.device:
+        raise RuntimeError("grad_clip_coef: coef must hold 2 contiguous fp32 values on the device of sqnorms")
+    _lib.call("rfn_grad_clip_coef", coef.device, sqnorms.data_ptr(), int(ngroups), float(max_norm), coef.data_ptr())
+    return coef
+
+
+def grad_scale_(flat, coef):
+    """flat *= coef[0] in place, the coefficient read on the device (nothing is written when it is exactly 1)."""
+    _flat_f32(flat, "grad_scale_")
+    if coef.dtype != torch.float32 or coef.device != flat.device or coef.numel() < 1:
+        raise RuntimeError("grad_scale_: coef must be fp32 on the buffer's device")
+    _lib.call("rfn_grad_scale_f32", flat.device, flat.data_ptr(), flat.numel(), coef.data_ptr())
+    return flat
+
+
+def grad_clamp_(flat, clip_value):
+    """Every element of flat into [-clip_value, clip_value] in place; a NaN stays a NaN."""
+    _flat_f32(flat, "grad_clamp_")
+    _lib.call("rfn_grad_clamp_f32", flat.device, flat.data_ptr(), flat.numel(), float(clip_value))
+    return flat
+
+
 def gather_scalars(tensors, row):
     """row[i] <- double(tensors[i]) for one-element device tensors of mixed dtype (f32, bf16, f16, f64, i32), one launch per
     32 values on the current stream; CPU tensors: torch."""
@@ -171,17 +261,21 @@ class StepLog:
         self._next = 0
         self.stalls = 0
 
-    def record(self, step, scalars, grads=None, host=None):
+    def record(self, step, scalars, grads=None, host=None, sqnorms=None):
         """`scalars`: {name: one-element tensor on the device} for every name of the log; `grads`: (flat buffer, GradNormPlan)
-        or None; `host`: {name: python number} that goes with the row as it is.  Never waits for the device, unless all rows
-        are pending: then for the oldest row's event (counted in `stalls`)."""
+        or None; `sqnorms`: instead of `grads`, the G + 1 values grad_sqnorm_groups has already computed (GradClip.sqnorms: the
+        norms the clip decided on; they are copied, not computed again); `host`: {name: python number} that goes with the row
+        as it is.  Never waits for the device, unless all rows are pending: then for the oldest row's event (counted in
+        `stalls`)."""
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("StepLog.record: the current stream is capturing a graph; the copy to the host mirror and the "
                                "row's event would be replayed with every replay of that graph")
         if set(scalars) != set(self.names):
             raise KeyError(f"StepLog.record: got {sorted(scalars)}, the log was made for {sorted(self.names)}")
-        if grads is not None and self.group_names is None:
+        if (grads is not None or sqnorms is not None) and self.group_names is None:
             raise ValueError("StepLog.record: this log was made without group names")
+        if grads is not None and sqnorms is not None:
+            raise ValueError("StepLog.record: grads or sqnorms, not both")
         if len(self._pending) == self.rows:
             while self._pending and self.events[self._pending[0][0]].query():
                 self._take()                                  # rows that are complete but were not polled yet
@@ -198,11 +292,15 @@ class StepLog:
             if plan.ngroups != len(self.group_names):
                 raise ValueError("StepLog.record: the plan's group count differs from the log's")
             grad_sqnorm_groups(flat, plan, row[len(self.names):len(self.names) + plan.ngroups + 1])
+        if sqnorms is not None:
+            if sqnorms.numel() != len(self.group_names) + 1:
+                raise ValueError("StepLog.record: sqnorms must hold one value per group and the non-finite count")
+            row[len(self.names):len(self.names) + sqnorms.numel()].copy_(sqnorms)
         if self.mirror is not self.ring:
             self.mirror[slot].copy_(row, non_blocking=True)
         self.events[slot].record()
         self._next = (slot + 1) % self.rows
-        self._pending.append((slot, int(step), dict(host or {}), grads is not None, tensors))
+        self._pending.append((slot, int(step), dict(host or {}), grads is not None or sqnorms is not None, tensors))
 
     def _take(self):
         """The oldest pending row (its event has completed) from the mirror into the ready list."""

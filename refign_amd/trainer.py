@@ -82,6 +82,27 @@ def _atomic_save(obj, filepath):
         raise
 
 
+def parse_gradient_clip(val, algorithm="norm"):
+    """Lightning's `gradient_clip_val` / `gradient_clip_algorithm` -> (threshold or None, algorithm): None and 0 mean off; a
+    negative value, a NaN or a non-number and an algorithm other than "norm" / "value" raise ValueError."""
+    if algorithm not in ("norm", "value"):
+        raise ValueError(f"Trainer: gradient_clip_algorithm must be 'norm' or 'value' (got {algorithm!r})")
+    if val is None:
+        return None, algorithm
+    if isinstance(val, bool) or not isinstance(val, (int, float)) or not val >= 0:
+        raise ValueError(f"Trainer: gradient_clip_val must be None or a number >= 0 (got {val!r})")
+    return (float(val) or None), algorithm
+
+
+def parse_accumulate(k):
+    """Lightning's `accumulate_grad_batches` -> int >= 1.  Its per-epoch schedule (a dict) has no meaning for a trainer that
+    counts steps only: that, like anything else that is no positive int, raises ValueError."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        what = "a per-epoch schedule (dict): this trainer has no epochs" if isinstance(k, dict) else repr(k)
+        raise ValueError(f"Trainer: accumulate_grad_batches must be an int >= 1 (got {what})")
+    return k
+
+
 class LinearWarmupPolynomialLR(torch.optim.lr_scheduler.LRScheduler):
     """helpers/lr_scheduler.py:10-57: linear warm-up from warmup_ratio*lr over warmup_iters, then polynomial decay to
     min_lr at max_steps."""
@@ -411,7 +432,7 @@ class Trainer:
 
     def __init__(self, model, sync_batchnorm=False, bucket_mb=64, fused_optimizer=True, gc_interval=None, precision=None,
                  scaler_args=None, ckpt_path=None, deterministic=False, logger=None, log_every_n_steps=50, log_lr=True,
-                 graph_step=False):
+                 graph_step=False, gradient_clip_val=None, gradient_clip_algorithm="norm", accumulate_grad_batches=1):
         """`precision` (the reference's `--trainer.precision`): None -- step() runs under whatever autocast the caller
         entered, no loss scaling (what bench.py does); 16 / '16' / '16-mixed' -- step() enters fp16 autocast itself and
         scales the loss (`self.scaler`, amp.LossScaler; `scaler_args`: its init_scale / growth_factor / backoff_factor /
@@ -442,8 +463,33 @@ class Trainer:
         gradients and the optimizer tail stay eager.  The graph is dropped, and captured again after two further eager steps,
         by load_checkpoint, validate / test / predict, model.train() / eval(), model.to() / half() and close().  With
         RFN_HIP_GRAPH=0 or off a GPU the step runs eagerly.  ValueError for a model that steps itself (the UDA model: its passes
-        are graphed on their own)."""
+        are graphed on their own).
+        `gradient_clip_val`, `gradient_clip_algorithm` (Lightning's; None or 0: off): the gradient is clipped in
+        _OptimizerProxy.step -- after the all-reduce and, under precision=16, the unscale (Lightning unscales before it clips),
+        in front of the logged row and the optimizer -- in place in `self.grads.flat`, so every `p.grad` holds the clipped
+        gradient afterwards.  That serves both kinds of model: for one that steps itself (the UDA model: manual optimization)
+        it is the place where its training_step would call `self.clip_gradients(...)`.  "norm": clip_grad_norm_ over all
+        optimizer parameters together (eps 1e-6, coefficient at most 1; a NaN norm multiplies NaN in, an infinite one gives
+        0); "value": clip_grad_value_ (a NaN stays).  Decided and applied on the device (steplog.GradClip); a CPU buffer goes
+        through torch's two functions.  Logged rows then hold the norms BEFORE clipping (computed once, shared with the
+        clip) and, under "norm", `grad_clip/coef`.
+        `accumulate_grad_batches` = k (an int; k > 1 needs a model with automatic_optimization, as in Lightning): step() call
+        j = 1 .. k of a window zeroes the gradients for j = 1 only and backpropagates loss / k (divided in front of the loss
+        scaling; model.logged keeps the undivided losses); call k alone all-reduces, unscales, clips, steps optimizer and
+        scheduler, updates the loss scaler and adds 1 to global_step.  `optimizer_stepped` tells whether the last step() did.
+        The window starts anew here and in load_checkpoint; save_checkpoint inside an open window raises.  With graph_step the
+        division is part of the graph.  fit() counts optimizer steps."""
         from .amp import parse_precision
+        clip_val, clip_alg = parse_gradient_clip(gradient_clip_val, gradient_clip_algorithm)
+        self.accumulate_grad_batches = parse_accumulate(accumulate_grad_batches)
+        if self.accumulate_grad_batches > 1 and not getattr(model, "automatic_optimization", False):
+            raise ValueError("Trainer: accumulate_grad_batches > 1 needs a model with automatic_optimization (the matcher); a "
+                             "model that steps itself (the UDA model) decides on its own when its optimizer steps")
+        self._clip = None
+        if clip_val is not None:
+            from .steplog import GradClip
+            self._clip = GradClip(clip_val, clip_alg)
+        self._micro, self.optimizer_stepped = 0, False       # calls made in the open accumulation window
         self.step_graph = None
         if graph_step and not getattr(model, "automatic_optimization", False):
             raise ValueError("Trainer: graph_step=True is for a model with automatic_optimization (the matcher); the UDA "
@@ -639,6 +685,7 @@ class Trainer:
             else:
                 with determinism.torch_deterministic(self.deterministic), self._autocast():
                     self.model.training_step(batch, batch_idx)
+                self.optimizer_stepped = True
             if self.guard is not None:
                 self.guard.note(f"step {self._steps_done} queued")
         finally:
@@ -653,12 +700,16 @@ class Trainer:
     def _automatic_step(self, batch, batch_idx):
         """A model with automatic_optimization (AlignmentModel): training_step returns the loss and this trainer does what
         Lightning does around it -- zero the gradients, backward (scaled under precision=16), optimizer step through the
-        proxy (all-reduce, unscale, step-log row, Adam, scaler update), scheduler step, global_step + 1.  The gradient
-        stays readable in `self.grads` until the next step.  Nothing here asks the host about device data after the first
-        call of a shape: the head's warps skip their zero-flow check (matching.no_zero_flow_check)."""
+        proxy (all-reduce, unscale, clip, step-log row, Adam, scaler update), scheduler step, global_step + 1.  With
+        accumulate_grad_batches = k the head (zeroing) belongs to the first call of a window and the tail (from the proxy on)
+        to its last one, and every call backpropagates loss / k (Lightning's closure_loss / accumulate_grad_batches).  The
+        gradient stays readable in `self.grads` until the next window.  Nothing here asks the host about device data after
+        the first call of a shape: the head's warps skip their zero-flow check (matching.no_zero_flow_check)."""
         from . import matching
         model = self.model
-        self.grads.zero()
+        closes = self._closes_window()
+        if self._micro == 0:
+            self.grads.zero()
         if self.step_graph is not None:
             # training_step + loss scaling + backward as one replay; the outputs are copies the next replay does not touch, so
             # the step log (which reads model.logged later in stream order) and the caller see this step's values
@@ -668,21 +719,35 @@ class Trainer:
         else:
             with self._autocast(), matching.no_zero_flow_check():
                 loss = model.training_step(batch, batch_idx)
-            self._backward(loss, last=True)
+            self._backward(self._window_share(loss), last=closes)
+        self._micro = 0 if closes else self._micro + 1
+        self.optimizer_stepped = closes
+        if not closes:
+            return
         model._optimizer.step()
         self.scheduler.step()
         model.global_step += 1
 
+    def _closes_window(self):
+        """Whether the next step() call is the last of its accumulation window (always, without accumulation)."""
+        return self._micro == self.accumulate_grad_batches - 1
+
+    def _window_share(self, loss):
+        k = self.accumulate_grad_batches
+        return loss / k if k > 1 else loss
+
     def _graphed_pass(self, *tensors):
         """What `step_graph` runs eagerly, captures and replays: the eager branch of _automatic_step on the tensors of
         STEP_GRAPH_INPUTS (`prime_trg_idx` always a device tensor here: no pinned temporary inside a capture) -> the scalar
-        tensors training_step logged, in the order it logged them (`_graph_logged`: their names)."""
+        tensors training_step logged, in the order it logged them (`_graph_logged`: their names).  One graph serves every call
+        of an accumulation window (the division by k is in it), so under data parallelism no call releases ranges to the
+        all-reduce from inside its backward: the window's last call reduces in the optimizer tail."""
         from . import matching
         model = self.model
         before = dict(model.logged)
         with self._autocast(), matching.no_zero_flow_check():
             loss = model.training_step(dict(zip(STEP_GRAPH_INPUTS, tensors)), self._graph_batch_idx)
-        self._backward(loss, last=True)
+        self._backward(self._window_share(loss), last=self.accumulate_grad_batches == 1)
         names = tuple(k for k, v in model.logged.items() if torch.is_tensor(v) and v is not before.get(k))
         self._graph_logged = names
         return tuple(model.logged[k] for k in names)
@@ -697,11 +762,9 @@ class Trainer:
         """Called by _OptimizerProxy.step between the unscale and AdamW: the losses are in model.logged and the current stream
         has joined the streams that made them, the gradients are final, the scaler has not been updated, and
         model.global_step is still the label of this step."""
-        if self.logger is None:
+        if not self._row_due():
             return
         label = int(self.model.global_step)
-        if (label + 1) % self.log_every_n_steps != 0:
-            return
         from . import steplog
         flat = self.grads.flat
         if flat.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -726,15 +789,36 @@ class Trainer:
                             "amp/skipped_steps": self.scaler._skipped})
         if self.log_lr:
             host.update({f"lr-{type(self.optimizer).__name__}/{n}": float(g["lr"]) for n, g in zip(gnames, groups)})
-        if self._norm_plan is None:
-            self._norm_plan = steplog.GradNormPlan.for_buffer(self.grads, groups)
+        clip = self._clip
+        if clip is not None and clip.algorithm == "norm":
+            scalars["grad_clip/coef"] = clip.coef[:1]
         log = self._steplog
         if log is None or log.names != list(scalars):
             if log is not None:                              # another set of logged names (a model stepped by hand): a new ring
                 self._hand_over(log.flush())
                 self.log_stalls += log.stalls
             log = self._steplog = steplog.StepLog(flat.device, list(scalars), group_names=gnames)
-        log.record(label, scalars, grads=(flat, self._norm_plan), host=host)
+        if clip is not None:                                 # the norms the clip took before it changed the gradient
+            log.record(label, scalars, sqnorms=clip.sqnorms, host=host)
+        else:
+            log.record(label, scalars, grads=(flat, self._grad_norm_plan()), host=host)
+
+    def _row_due(self):
+        """Whether the optimizer step in progress is one whose row is recorded."""
+        return self.logger is not None and (int(self.model.global_step) + 1) % self.log_every_n_steps == 0
+
+    def _grad_norm_plan(self):
+        if self._norm_plan is None:
+            from .steplog import GradNormPlan
+            self._norm_plan = GradNormPlan.for_buffer(self.grads, self.optimizer.param_groups)
+        return self._norm_plan
+
+    def _unscale_and_clip(self):
+        """Called by _OptimizerProxy.step after the all-reduce: the loss scaler's unscale (precision=16), then the clip."""
+        if self._clip is not None:
+            self._clip(self.grads, self._grad_norm_plan(), self.scaler, want_norms=self._row_due())
+        elif self.scaler is not None:
+            self.scaler.unscale_(self.grads.flat)
 
     def _hand_over(self, rows):
         for step, row in rows:
@@ -877,6 +961,8 @@ class Trainer:
         exhausted; WHERE in it a resumed run continues is the caller's to restore (hand in an iterable that starts at the
         batch the saved run would have taken next): the checkpoint holds no loader state.  The loop looks one batch ahead and
         hands it to step(..., next_batch=), which prefetches what depends on the next inputs only; the last step gets None.
+        With accumulate_grad_batches = k, max_steps and val_every_n_steps count optimizer steps (k calls of step() each),
+        step()'s batch_idx counts calls, and only the very last call gets None.
         After every step whose new global_step is a non-zero multiple of `val_every_n_steps` (helpers/callbacks.py:19) it
         runs validate(val_loaders); with `ckpt_dir` and `save_last` it writes `<ckpt_dir>/last.ckpt` (save_checkpoint) after
         each validation and at the end (ModelCheckpoint(save_last=True)).  max_steps=None: the scheduler's max_steps.
@@ -905,11 +991,14 @@ class Trainer:
         batch = self._to_device(next(it))
         while int(model.global_step) < max_steps:
             start = int(model.global_step)
-            nxt = self._to_device(next(it)) if start + 1 < max_steps else None
-            self.step(batch, start, next_batch=nxt)
+            closes = self._closes_window()
+            nxt = self._to_device(next(it)) if start + 1 < max_steps or not closes else None
+            self.step(batch, start * self.accumulate_grad_batches + self._micro, next_batch=nxt)
+            batch = nxt
+            if not closes:
+                continue                                     # inside a window: nothing has advanced, nothing is due
             if int(model.global_step) <= start:
                 raise RuntimeError("Trainer.fit: the model's training_step did not advance global_step")
-            batch = nxt
             if rule.should_validate(int(model.global_step)):
                 self.flush_log()
                 history.append((int(model.global_step), self.validate(val_loaders)))
@@ -944,7 +1033,11 @@ class Trainer:
         Call between steps, on every rank: the ranks' RNG states are gathered to rank 0, which alone writes -- to a
         temporary file in the same directory, moved into place when complete, so a save that fails part-way leaves the
         previous file as it was -- and every rank returns once the file is in place (an error on rank 0 raises on all).
-        Not exact under precision=32 (parity mode): see DESIGN.md, Checkpoints."""
+        Not exact under precision=32 (parity mode): see DESIGN.md, Checkpoints.  RuntimeError inside an open accumulation
+        window (accumulate_grad_batches > 1): neither this file nor Lightning's keeps a partial gradient."""
+        if self._micro:
+            raise RuntimeError(f"Trainer.save_checkpoint: {self._micro} of {self.accumulate_grad_batches} calls of an accumulation "
+                               f"window are done; the file has no place for a partial gradient -- save after the window's last call")
         dist_on = dist.is_available() and dist.is_initialized()
         rank = dist.get_rank() if dist_on else 0
         dev = self.grads.flat.device
@@ -1000,6 +1093,7 @@ class Trainer:
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist_on else (0, 1)
         dev = self.grads.flat.device
         model = self.model
+        self._micro = 0                                      # an accumulation window starts with the next step()
         with self._io(f"load_checkpoint {filepath}"):
             # (full pickle, as Lightning 1.5 loads: a reference file carries its hyper-parameters as python objects)
             ckpt = torch.load(filepath, map_location="cpu", weights_only=False)
@@ -1084,7 +1178,8 @@ class Trainer:
 
 class _OptimizerProxy:
     """What `self.optimizers()` returns inside training_step: zero_grad() clears the flat buffer (keeping the views),
-    step() all-reduces once and then steps the real optimiser."""
+    step() all-reduces once, unscales (precision=16), clips (Trainer(gradient_clip_val=...): where a LightningModule under
+    manual optimization calls self.clip_gradients) and then steps the real optimiser."""
 
     def __init__(self, trainer):
         self.t = trainer
@@ -1099,14 +1194,22 @@ class _OptimizerProxy:
         if record is not None:
             record()
 
+    def _unscale_and_clip(self):
+        """Trainer._unscale_and_clip; a stand-in for the trainer without it gets the unscale alone."""
+        both = getattr(self.t, "_unscale_and_clip", None)
+        if both is not None:
+            both()
+        elif self.t.scaler is not None:
+            self.t.scaler.unscale_(self.t.grads.flat)
+
     def step(self):
         self.t.grads.all_reduce_mean(self.t.bucket_mb)        # (and what a concurrently run pass accumulated on the side)
         sc = self.t.scaler
+        self._unscale_and_clip()
         if sc is not None:
             # GradScaler.step + update: the reduced (scaled) gradients are unscaled in place -- an inf on any rank reached every
             # rank through the sum, so all ranks skip together -- then AdamW, skipped on the device when found_inf is set, then
             # the new scale.  torch's own step (first step, non-plain configurations) needs the flag on the host.
-            sc.unscale_(self.t.grads.flat)
             self._record_row()                                # this step's scale and found_inf: the scaler is updated below
             if self.t.fast_step is not None and self.t.fast_step.step_amp(sc.found_inf):
                 sc.update(self.t.fast_step.device_step)
