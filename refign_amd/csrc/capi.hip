@@ -52,6 +52,14 @@ int zero_async(void* p, size_t bytes, hipStream_t st) {
   return check_launch("zero_fill_kernel");
 }
 
+__device__ uint4 g_zero_page[4];          // zero-initialised: DMA source of out-of-image / padding pieces
+// its device address, looked up once (a library's first call is an eager warm-up, never inside a capture); null: lookup failed
+const void* zero_page() {
+  static void* page = nullptr;
+  if (page == nullptr && hipGetSymbolAddress(&page, HIP_SYMBOL(g_zero_page)) != hipSuccess) page = nullptr;
+  return page;
+}
+
 }  // namespace rfn
 
 extern "C" {

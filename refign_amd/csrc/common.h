@@ -5,6 +5,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/refign_hip.h"
 
@@ -81,6 +82,22 @@ inline int dt_pair(int a, int b, const char* what, Fn&& fn) {
   return fail(RFN_EINVAL, "%s: dtype codes (%d, %d): each 0 (f32), 1 (bf16) or 2 (f16), bf16 and f16 not mixed", what, a, b);
 }
 
+// The 16-bit matrix-core kernels are templated on the code itself: fn(std::integral_constant<int, 1 or 2>).
+template <typename Fn>
+inline int dt16(int a, const char* what, Fn&& fn) {
+  if (a == 1) return fn(std::integral_constant<int, 1>{});
+  if (a == 2) return fn(std::integral_constant<int, 2>{});
+  return fail(RFN_EINVAL, "%s: dtype %d (1 = bf16, 2 = f16)", what, a);
+}
+
+// compile-time loop: f(std::integral_constant<int, I>) for I = B .. N - 1 (register arrays need literal indices)
+template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    static_for<I + 1, N>(f);
+  }
+}
+
 // rfn_set_deterministic() / rfn_get_deterministic(): process-wide (capi.hip)
 int deterministic();
 
@@ -93,6 +110,10 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // zero-fill as a kernel on `st` (capi.hip: why not hipMemsetAsync)
 int zero_async(void* p, size_t bytes, hipStream_t st);
+
+// 64 bytes of zeros in device memory (capi.hip): what an LDS-DMA piece or a tap outside the image / past the last k reads.
+// Null if the look-up failed.
+const void* zero_page();
 
 }  // namespace rfn
 

@@ -29,8 +29,6 @@
 
 namespace rfn {
 
-__device__ uint4 g_zero_page_c3[4];          // zero-initialised: DMA source of halo pixels outside the image
-
 constexpr int kC3TH = 8, kC3TW = 32;
 constexpr int kC3HW = kC3TW + 2, kC3HP = (kC3TH + 2) * kC3HW;      // 34 columns, 340 halo pixels
 constexpr int kC3AI = 44;                                           // halo DMA instructions per chunk (8 rows each, 352 rows)
@@ -53,13 +51,6 @@ __device__ __forceinline__ void wait_dma_rt(int n) {               // wave-unifo
     case 11: wait_dma_upto<11>(); break;
     case 12: wait_dma_upto<12>(); break;
     default: wait_dma_upto<0>(); break;
-  }
-}
-
-template <int I, int N, typename F> __device__ __forceinline__ void c3_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    c3_static_for<I + 1, N>(f);
   }
 }
 
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(NA == 1 ? 256 : 512) void conv3x3_halo_kernel(const
   for (int c = 0; c < nchunks; ++c) {
     const bool notlast = c + 1 < nchunks;
     const unsigned char* as = smem + (c & (NA - 1)) * kC3AB;
-    c3_static_for<0, 9>([&](auto tt) {
+    static_for<0, 9>([&](auto tt) {
       constexpr int t = decltype(tt)::value;
       constexpr int dy = t / 3, dx = t % 3;
       const int s = 9 * c + t;
@@ -327,13 +318,11 @@ int launch_conv3x3_halo(const void* X, const void* W, const void* bias, void* Y,
   const int BN = (N % 128 == 0 && !one_chunk) ? 128 : 64;
   const long blocks = (long)B * tiles_y * tiles_x * cdiv(N, BN);
   if (blocks >= (1L << 31)) return 1;
-  static void* zero_page = nullptr;          // looked up once (first call is an eager warm-up, never inside a capture)
-  if (zero_page == nullptr && hipGetSymbolAddress(&zero_page, HIP_SYMBOL(g_zero_page_c3)) != hipSuccess)
-    return fail(RFN_ELAUNCH, "conv3x3_halo: zero page symbol");
+  const void* zero = zero_page();            // DMA source of halo pixels outside the image
+  if (zero == nullptr) return fail(RFN_ELAUNCH, "conv3x3_halo: zero page symbol");
 #define RFN_C3(DT_, BN_, NA_, O32_)                                                                                               \
   hipLaunchKernelGGL((conv3x3_halo_kernel<DT_, BN_, NA_, O32_>), dim3((unsigned)blocks), dim3(NA_ == 1 ? 256 : 512), 0, s,          \
-                     (const uint16_t*)X, (const uint16_t*)W, bias, Y, H, Wd, C, N, ldw, ldy, tiles_y, tiles_x, act,                \
-                     (const void*)zero_page)
+                     (const uint16_t*)X, (const uint16_t*)W, bias, Y, H, Wd, C, N, ldw, ldy, tiles_y, tiles_x, act, zero)
   if (out32) {
     if (one_chunk) RFN_C3(1, 64, 1, true); else if (BN == 128) RFN_C3(1, 128, 2, true); else RFN_C3(1, 64, 2, true);
   } else if (dtype == 1) {

@@ -310,13 +310,6 @@ __global__ __launch_bounds__(kTH * kStrips * 3) void corr9_tile_kernel(
 // --------------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. N - 1
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 // The DMA instruction goes through inline asm, NOT `__builtin_amdgcn_global_load_lds`: with the builtin hipcc tracks the pending
 // LDS write and puts `s_waitcnt vmcnt(0)` in front of every `ds_read` it cannot prove disjoint -- inside the channel loop, so

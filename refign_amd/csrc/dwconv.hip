@@ -383,8 +383,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_fwd_kernel(const T* __restrict_
 // Items (image, residue class, segment, strip), strip fastest, are dealt to the pixel lanes of either launch geometry
 // (dw_map: grid of channel blocks x lane blocks, or XCD-sliced); `seg` rows per segment: roll_geom().
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ uint4 g_zero_line_dw[1];          // zero-initialised: what a tap left or right of the image reads
-
 constexpr int kRV = 4;                       // channels per thread of the rolling body
 // rows in flight per thread: 2 for bf16 (measured against 1, profiles/dwconv_roll_kbench.txt); fp16, whose conversions need
 // more temporaries, spills with 2
@@ -853,14 +851,13 @@ static RollGeom roll_geom(int B, int H, int W, int C, int dil) {
 template <typename T, int STATS, bool BNE>
 static int launch_roll(const void* x, const float* w, const float* bias, void* y, double* sums, int B, int H, int W, int C,
                        int dil, hipStream_t st, BnEpi bn, double* spart) {
-  static void* zero_line = nullptr;          // looked up once (first call is an eager warm-up, never inside a capture)
-  if (zero_line == nullptr && hipGetSymbolAddress(&zero_line, HIP_SYMBOL(g_zero_line_dw)) != hipSuccess)
-    return fail(RFN_ELAUNCH, "dwconv3x3_roll_kernel: zero line symbol");
+  const void* zero_line = zero_page();       // its first 16 bytes: what a tap left or right of the image reads
+  if (zero_line == nullptr) return fail(RFN_ELAUNCH, "dwconv3x3_roll_kernel: zero line symbol");
   const RollGeom g = roll_geom(B, H, W, C, dil);
   RFN_REQUIRE(g.nitems < (1L << 30) && (long)dil * W * C * (long)sizeof(T) < (1L << 32),
               "dwconv3x3_roll_kernel: B=%d H=%d W=%d C=%d dilation=%d too large", B, H, W, C, dil);
   hipLaunchKernelGGL((dwconv3x3_roll_kernel<T, STATS, BNE, kRollDepth<T>>), dim3(g.gx, g.gy), dim3(256), 0, st, (const T*)x, w, bias, (T*)y, B, H,
-                     W, C, dil, g.cvb, g.seg, g.sliced ? 1 : 0, sums, bn, spart, (const void*)zero_line);
+                     W, C, dil, g.cvb, g.seg, g.sliced ? 1 : 0, sums, bn, spart, zero_line);
   if (int rc = check_launch("dwconv3x3_roll_kernel")) return rc;
   if (spart != nullptr) return ordered_colsum_f64(spart, sums, g.rows, 2 * C, st);
   return RFN_OK;

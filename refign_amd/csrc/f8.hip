@@ -51,12 +51,6 @@ struct F8Epi {
   float outq;               // fp8 output: value * outq is stored
 };
 
-__device__ uint4 g_zero_page_f8[4];
-
-template <int N> __device__ __forceinline__ void wait_dma_upto_f8() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // OUT8: e4m3 output (1 byte per element, ldy in bytes); otherwise bf16 (ldy in elements)
 template <int BM, int BN, bool OUT8, int NW = 4>
 __global__ __launch_bounds__(NW * 64) void gemm_nt_f8_kernel(const unsigned char* __restrict__ X,
@@ -245,9 +239,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_f8_kernel(const unsigned char
 template <bool OUT8>
 static int launch_nt_f8(const void* X, const void* W, void* Y, long M, long N, long K, long ldx, long ldw, long ldy,
                         const F8Epi& epi, hipStream_t s) {
-  static void* zero_page = nullptr;
-  if (zero_page == nullptr && hipGetSymbolAddress(&zero_page, HIP_SYMBOL(g_zero_page_f8)) != hipSuccess)
-    return fail(RFN_ELAUNCH, "gemm_nt_f8: zero page symbol");
+  const void* zero = zero_page();
+  if (zero == nullptr) return fail(RFN_ELAUNCH, "gemm_nt_f8: zero page symbol");
   int bn = (N % 128 == 0) ? 128 : 64;
   int bm = ((long)cdiv(M, 128) * cdiv(N, bn) >= 256) ? 128 : 64;
   if (N % 256 == 0 && (long)cdiv(M, 256) * (N / 256) >= 256) bm = bn = 256;
@@ -262,8 +255,7 @@ static int launch_nt_f8(const void* X, const void* W, void* Y, long M, long N, l
   dim3 grid((unsigned)std::min<long>(total, slots)), block(256);
 #define RFN_NT8(BM_, BN_)                                                                                                \
   hipLaunchKernelGGL((gemm_nt_f8_kernel<BM_, BN_, OUT8>), grid, block, 0, s, (const unsigned char*)X,                    \
-                     (const unsigned char*)W, Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total, epi,        \
-                     (const void*)zero_page)
+                     (const unsigned char*)W, Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total, epi, zero)
   const int key = bm * 1000 + bn;
   switch (key) {
     case 128128: RFN_NT8(128, 128); break;
@@ -273,8 +265,7 @@ static int launch_nt_f8(const void* X, const void* W, void* Y, long M, long N, l
     case 256256:
       grid = dim3((unsigned)std::min<long>(total, persistent ? 256 : 0x7fffffff));
       hipLaunchKernelGGL((gemm_nt_f8_kernel<256, 256, OUT8, 8>), grid, dim3(512), 0, s, (const unsigned char*)X,
-                         (const unsigned char*)W, Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total, epi,
-                         (const void*)zero_page);
+                         (const unsigned char*)W, Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tiles_n, (int)total, epi, zero);
       break;
     default: return fail(RFN_EINVAL, "gemm_nt_f8: no kernel for tile %dx%d", bm, bn);
   }

@@ -27,19 +27,14 @@
 #pragma once
 #include <type_traits>
 
+#include "common.h"
 #include "mfma.h"
 
 namespace rfn {
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. N - 1 (register arrays need literal indices)
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
+// literal index for common.h's static_for
 template <int V> using ic = std::integral_constant<int, V>;
 
 struct Gemm2Epi {
@@ -80,12 +75,6 @@ __device__ __forceinline__ void buf_store16_dyn(u32x4 v, unsigned voff, i32x4 rs
   asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rsrc) : "memory");
 }
 
-template <int ACT> __device__ __forceinline__ float act2(float v) {
-  if constexpr (ACT == 1) return fmaxf(v, 0.f);
-  if constexpr (ACT == 3) return fmaxf(v, 0.1f * v);      // LeakyReLU(0.1)
-  return v;
-}
-
 // DT 1 = bf16, 2 = f16.  BM x BN tile, WGM x WGN waves (wave tile BM / WGM x BN / WGN, both multiples of 32).
 // NSK: K-steps of the next tile that carry the stores of a tile (K / 64 >= NSK).  D0, D1, D3: LDS-DMA instructions a wave
 // issues in sub-steps 0, 1 and 3 (3: behind the barrier, for the step after next; sub-step 2 carries stores only).
@@ -95,7 +84,7 @@ template <int ACT> __device__ __forceinline__ float act2(float v) {
 // MFMAs; their stores are issued by the epilogue (K >= 128; NSK is ignored).
 // (Tiles of 256 x 256 were built and dropped: 256 accumulators + a held tile + two fragment sets do not fit the two
 // 256-entry register files -- the allocator shuffles accumulators through scratch; 192 x 320 / 192 x 256 fit.)
-template <int DT, int BM, int BN, int WGM, int WGN, bool BIAS, bool RES, int ACT, int NSK, int D0, int D1, int D3,
+template <int DT, int BM, int BN, int WGM, int WGN, bool BIAS, bool RES, int NSK, int D0, int D1, int D3,
           int ABL = 0, bool TRACE = false>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_nt2_kernel(const uint16_t* __restrict__ X,
                                                                 const uint16_t* __restrict__ W, uint16_t* __restrict__ Y,
@@ -392,11 +381,6 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_nt2_kernel(const uint16_t*
                 a[e] += ba[e];
                 b[e] += bb[e];
               }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              a[e] = act2<ACT>(a[e]);
-              b[e] = act2<ACT>(b[e]);
             }
             const int ent = (j * IB + i) * 2 + pr;  // after the swap: 8 consecutive columns from i * 32 + 16 pr + 8 g
             if constexpr (RES) {

@@ -20,7 +20,7 @@ int launch_nt2(const void* X, const void* W, void* Y, long M, long N, long K, lo
   const long rounds = cdiv(t2, 256L);
   dim3 grid((unsigned)cdiv(t2, rounds)), block(256);
 #define RFN_G2(BN_, NSK_, D3_, BIAS_, RES_)                                                                              \
-  hipLaunchKernelGGL((gemm_nt2_kernel<1, 192, BN_, 2, 2, BIAS_, RES_, 0, NSK_, 4, 4, D3_>), grid, block, 0, s,           \
+  hipLaunchKernelGGL((gemm_nt2_kernel<1, 192, BN_, 2, 2, BIAS_, RES_, NSK_, 4, 4, D3_>), grid, block, 0, s,           \
                      (const uint16_t*)X, (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, tn,    \
                      (int)t2, e2)
 #define RFN_G2E(BN_, NSK_, D3_)                                                                                          \

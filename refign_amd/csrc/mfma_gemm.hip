@@ -29,14 +29,6 @@
 
 namespace rfn {
 
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. N - 1
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 struct GemmEpi {
   // OUT32 kernels (fp32 result: the split-bf16 parity mode) read bias / res as fp32 through the same pointers
   const uint16_t* bias;     // [N] or null, same 16-bit type as the operands
@@ -87,37 +79,70 @@ struct ConvGeom {
   int transposed, sshift;
 };
 
-// Persistent workgroups: a workgroup owns every G-th output tile (m-major, n fastest) and runs ONE software pipeline
-// over all their K-steps through an NS-deep
-// LDS ring: NS - 1 steps are in flight under the MFMAs of the current one -- also across tile boundaries, so the first
-// steps of tile i+1 stream in under the last MFMAs and the whole epilogue of tile i.  The hand-off is a COUNTED
-// `s_waitcnt vmcnt((NS - 2) * DMA instructions per step)` + one barrier per step; after an epilogue (its stores share the
-// counter and need not retire in order with the loads) the wait is vmcnt(0).  Measured on MI355X (profiles/): K-steps of
-// 64 (full 128-byte lines per row) with a 2-deep ring beat K-steps of 32 with a 4-deep ring by 1.3-1.6x on the K >= 512
-// shapes -- half-line requests double the L2 request count -- so BK = 64, NS = 2 is what the host launches.
+// The fp32-result epilogue of gemm_nt_kernel (OUT32; parity mode: correctness path, not a fast one): stores the tile at
+// (m0, n0) straight from the accumulators of wave (wm, wn) and clears them for the next tile.  Lane (g, frow) holds, of row
+// frow of block (i, j), the runs of 4 consecutive columns 8 k + 4 g, k = 0..3: one 16-byte store each; bias / residual are
+// fp32.  WN = the columns of a wave's part of the tile.  (The 16-bit epilogue stays in the kernel: as a function of its own
+// it moved the register allocation of the 128- and 256-wide instances -- profiles/nt_refactor_build.txt.)
+template <int BM, int WN, int IB, int JB>
+__device__ __forceinline__ void nt_store_f32(f32x16 (&acc)[IB][JB], float* Y32, int M, int N, long ldy, int m0,
+                                             int n0, const GemmEpi& epi, int wm, int wn, int g, int frow) {
+  const float* bias32 = (const float*)epi.bias;
+  const float* res32 = (const float*)epi.res;
+#pragma unroll
+  for (int j = 0; j < JB; ++j)
+#pragma unroll
+    for (int i = 0; i < IB; ++i) {
+      const int m = m0 + wm * (BM / 2) + j * 32 + frow;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int n = n0 + wn * WN + i * 32 + 8 * k + 4 * g;
+        f32x4 v = {acc[i][j][4 * k], acc[i][j][4 * k + 1], acc[i][j][4 * k + 2], acc[i][j][4 * k + 3]};
+        if (m < M && n < N) {
+          if (bias32 != nullptr) v += *(const f32x4*)(bias32 + n);
+          if (epi.act != 0) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act);
+          }
+          if (res32 != nullptr || epi.rowscale != nullptr) {
+            const float rs = epi.rowscale != nullptr ? epi.rowscale[m / epi.rows_per_sample] : 1.f;
+            const f32x4 rr = res32 != nullptr ? *(const f32x4*)(res32 + (long)m * ldy + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+            v = rr + rs * v;
+          }
+          *(f32x4*)(Y32 + (long)m * ldy + n) = v;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    }
+}
 
-template <int DT, int BM, int BN, int BK, int NS, bool GATHER, int NW = 4, bool OUT32 = false>
+// Persistent workgroups: a workgroup owns every G-th output tile (m-major, n fastest) and runs ONE software pipeline over
+// all their K-steps through a two-stage LDS ring: while the MFMAs of step s read one stage, the DMA of step s + 1 fills the
+// other -- also across tile boundaries, so the first step of tile i + 1 streams in under the last MFMAs and the whole
+// epilogue of tile i.  The hand-off is one `s_waitcnt vmcnt(0)` (this wave's DMA of the step, and the stores of an epilogue
+// before it, which share the counter) plus one barrier per K-step.  Measured on MI355X (profiles/): K-steps of 64 (full
+// 128-byte lines per row) with this ring beat K-steps of 32 with a 4-deep ring and counted waits by 1.3-1.6x on the
+// K >= 512 shapes -- half-line requests double the L2 request count.
+template <int DT, int BM, int BN, bool GATHER, int NW = 4, bool OUT32 = false>
 __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W,
                                                       uint16_t* __restrict__ Y, int M, int N, int K, long ldx, long ldw,
                                                       long ldy, int tiles_n, int total_tiles, GemmEpi epi, ConvGeom cg) {
   using E = Elem<DT>;
   using vec8 = typename E::vec8;
-  static_assert(BK == 32 || BK == 64, "K-step of 32 or 64");
+  constexpr int BK = 64, NS = 2;           // K-step, stages of the LDS ring
+  constexpr int ROWB = 128, PPR = 8, RPI = 8;   // bytes per LDS row, its 16-byte pieces, tile rows per DMA instruction
   // NW waves as 2 (m) x NW / 2 (n); 8 waves (a 256 x 256 tile, wave tile 128 x 64) halve the LDS-DMA instructions a wave
   // issues per MFMA -- their issue cost, not the data volume, is what paces the 4-wave 128 x 128 tile (2 MFMAs per DMA)
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   constexpr int WNW = NW / 2;              // waves along n
   constexpr int IB = BN / (32 * WNW);      // 32-wide n blocks per wave
   constexpr int JB = BM / 64;              // 32-wide m blocks per wave
-  constexpr int ROWB = BK * 2;             // bytes per LDS row
-  constexpr int PPR = BK / 8;              // 16-byte pieces per row (4 or 8)
-  constexpr int RPI = 64 / PPR;            // tile rows per DMA instruction (16 or 8)
   constexpr int XBYTES = BM * ROWB, WBYTES = BN * ROWB, STAGE = XBYTES + WBYTES;
   constexpr int XI = BM / (NW * RPI), WI = BN / (NW * RPI);   // DMA instructions per wave and step
-  constexpr int IPS = XI + WI;
-  // piece c of row r sits at c ^ swizzle(r): rows of 128 B: (r >> 1) & 7, rows of 64 B: (r >> 2) & 3 -- either way every
-  // ds_read_b128 lane group covers 16 distinct 16-byte slots of the 256-byte bank row
-  auto swizzle = [](int r) { return BK == 64 ? (r >> 1) & 7 : (r >> 2) & 3; };
+  // piece c of row r sits at c ^ swizzle(r): every ds_read_b128 lane group covers 16 distinct 16-byte slots of the 256-byte
+  // bank row
+  auto swizzle = [](int r) { return (r >> 1) & 7; };
   __shared__ __attribute__((aligned(16))) unsigned char smem[NS * STAGE];
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -261,24 +286,23 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
       }
     }
   };
+  // step 0 (written as the one-trip loop it has always compiled from: as a plain call hipcc schedules every instance
+  // differently and two of them take two more VGPRs)
 #pragma unroll
   for (int q = 0; q < NS - 1; ++q) produce();
 
   int c_tile = t_begin, c_kt = 0;
-  bool drained = false;                       // stores of an epilogue are outstanding: next wait is vmcnt(0)
   for (long s = 0; s < S; ++s) {
-    // step s has landed once at most the two younger steps are still in flight (loads complete in order)
-    if (NS == 2 || drained || s + (NS - 2) >= S) wait_dma_all();
-    else wait_dma_upto<(NS - 2) * IPS>();
+    wait_dma_all();                           // this wave's part of step s has landed (and an epilogue's stores are out)
     wg_barrier();                             // ... everybody's part of it; and everybody is done reading step s - 1
-    produce();                                // step s + 3 into the buffer step s - 1 occupied
-    drained = false;
-    const unsigned char* st = smem + (int)(s % NS) * STAGE;
+    produce();                                // step s + 1 into the stage step s - 1 occupied, under the MFMAs below
+    unsigned char* st = smem + (int)(s % NS) * STAGE;
     // fragment reads ONE k-sub-step ahead of the MFMAs (round 4, second half): left to itself hipcc re-uses one register set
     // and emits read, `s_waitcnt lgkmcnt(0)`, MFMA, read, wait, MFMA ... -- four LDS latencies in a row per K-step and wave,
     // which on the student's 64 x 64 tiles (one MFMA per sub-step) IS the K-step.  `sched_barrier` pins the order.
     // (one MFMA per sub-step -- the 64 x 64 tile: all four sub-steps' fragments up front, 32 registers it has to spare)
-    constexpr int FD = (IB * JB == 1) ? BK / 16 : 2;     // fragment register sets
+    constexpr int KS = BK / 16;                          // MFMA sub-steps of a K-step
+    constexpr int FD = (IB * JB == 1) ? KS : 2;          // fragment register sets
     vec8 wf[FD][IB], xf[FD][JB];
     auto read_frags = [&](int ks, int b) {
       const int coff = ((2 * ks + g) ^ swz) * 16;
@@ -290,8 +314,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
 #pragma unroll
     for (int ks = 0; ks < FD - 1; ++ks) read_frags(ks, ks);
 #pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      if (ks + FD - 1 < BK / 16) read_frags(ks + FD - 1, (ks + FD - 1) % FD);
+    for (int ks = 0; ks < KS; ++ks) {
+      if (ks + FD - 1 < KS) read_frags(ks + FD - 1, (ks + FD - 1) % FD);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < IB; ++i)
@@ -300,120 +324,86 @@ __global__ __launch_bounds__(NW * 64) void gemm_nt_kernel(const uint16_t* __rest
       __builtin_amdgcn_sched_barrier(0);
     }
     if (++c_kt == nk) {
-      // ---- epilogue.  Registers -> (bias, activation, 16-bit rounding) -> a per-wave LDS staging block -> row-contiguous
-      // 16-byte stores: an instruction then writes 8 rows x 128 B (or 16 x 64 B) instead of 64 scattered 16-byte runs
-      // (one cache-line request per run made the K <= 128 shapes store-bound).  The staging block lives in the LDS stage
-      // that was just consumed, hence the barrier; the next steps' DMA (other stage) is in flight meanwhile.  `tile` is
-      // laundered through an empty asm so that the address arithmetic below (loop-invariant for the step loop) is not
-      // hoisted out of this block, where it would hold ~80 VGPRs.
+      // tile done: store it and clear the accumulators.  `tile` is laundered through an empty asm so that the epilogue's
+      // address arithmetic (loop-invariant for the step loop) is not hoisted out of this block, where it would hold ~80 VGPRs.
       int tl = c_tile;
       asm volatile("" : "+s"(tl));
       const int m0 = (tl / tiles_n) * BM, n0 = (tl % tiles_n) * BN;
-      constexpr int WN = BN / WNW;                     // columns of a wave's tile
-      constexpr int PITCH = WN * 2 + 16;               // staging row pitch in bytes (16-byte aligned, 2-way at worst)
-      constexpr int RPP = 64 / (WN / 8);               // rows per store instruction (8 pieces of 16 B per 64-column row)
-      static_assert(NW * 32 * PITCH <= STAGE, "staging block fits the consumed stage");
+      constexpr int WN = BN / WNW;                       // columns of a wave's tile
       if constexpr (OUT32) {
-        // fp32 result straight from the accumulators (parity mode: correctness path, not a fast one): a lane's run of 4
-        // consecutive n of row m is one 16-byte store; bias / residual are fp32
-        float* Y32 = (float*)Y;
-        const float* bias32 = (const float*)epi.bias;
-        const float* res32 = (const float*)epi.res;
+        nt_store_f32<BM, WN>(acc, (float*)Y, M, N, ldy, m0, n0, epi, wm, wn, g, frow);
+      } else {
+        // 16-bit result.  Registers -> (bias, activation, 16-bit rounding) -> a per-wave LDS staging block -> row-contiguous
+        // 16-byte stores: an instruction then writes 8 rows x 128 B (or 16 x 64 B) instead of 64 scattered 16-byte runs
+        // (one cache-line request per run made the K <= 128 shapes store-bound).  The staging block lives in the LDS stage
+        // that was just consumed, hence the barrier; the next step's DMA (other stage) is in flight meanwhile.
+        constexpr int PITCH = WN * 2 + 16;               // staging row pitch in bytes (16-byte aligned, 2-way at worst)
+        constexpr int RPP = 64 / (WN / 8);               // rows per store instruction (8 pieces of 16 B per 64-column row)
+        static_assert(NW * 32 * PITCH <= STAGE, "staging block fits the consumed stage");
+        wg_barrier();                                    // every wave is done reading this stage's operands
+        unsigned char* stg = st + wave * 32 * PITCH;
 #pragma unroll
-        for (int j = 0; j < JB; ++j)
+        for (int j = 0; j < JB; ++j) {
 #pragma unroll
           for (int i = 0; i < IB; ++i) {
-            const int m = m0 + wm * (BM / 2) + j * 32 + frow;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              const int n = n0 + wn * WN + i * 32 + 8 * k + 4 * g;
-              f32x4 v = {acc[i][j][4 * k], acc[i][j][4 * k + 1], acc[i][j][4 * k + 2], acc[i][j][4 * k + 3]};
-              if (m < M && n < N) {
-                if (bias32 != nullptr) v += *(const f32x4*)(bias32 + n);
-                if (epi.act != 0) {
+              const int cl = i * 32 + 8 * k + 4 * g;       // this lane's run: local columns cl .. cl + 3 of row frow
+              const int n = n0 + wn * WN + cl;
+              float v[4] = {acc[i][j][4 * k], acc[i][j][4 * k + 1], acc[i][j][4 * k + 2], acc[i][j][4 * k + 3]};
+              if (epi.bias != nullptr && n < N) {          // N % 8 == 0: a run is all in or all out
+                float b[4];
+                unpack4<DT>(*(const u32x2*)(epi.bias + n), b);
 #pragma unroll
-                  for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act);
-                }
-                if (res32 != nullptr || epi.rowscale != nullptr) {
-                  const float rs = epi.rowscale != nullptr ? epi.rowscale[m / epi.rows_per_sample] : 1.f;
-                  const f32x4 rr = res32 != nullptr ? *(const f32x4*)(res32 + (long)m * ldy + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-                  v = rr + rs * v;
-                }
-                *(f32x4*)(Y32 + (long)m * ldy + n) = v;
+                for (int e = 0; e < 4; ++e) v[e] += b[e];
               }
+              if (epi.act != 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act);
+              }
+              *(u32x2*)(stg + frow * PITCH + cl * 2) = pack4<DT>(v[0], v[1], v[2], v[3]);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
           }
-        c_kt = 0;
-        c_tile += G;
-        drained = true;
-        continue;
-      }
-      wg_barrier();                                    // every wave is done reading this stage's operands
-      unsigned char* stg = const_cast<unsigned char*>(st) + wave * 32 * PITCH;
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own staging writes (no other wave touches them)
 #pragma unroll
-      for (int j = 0; j < JB; ++j) {
-#pragma unroll
-        for (int i = 0; i < IB; ++i) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int cl = i * 32 + 8 * k + 4 * g;       // this lane's run: local columns cl .. cl + 3 of row frow
-            const int n = n0 + wn * WN + cl;
-            float v[4] = {acc[i][j][4 * k], acc[i][j][4 * k + 1], acc[i][j][4 * k + 2], acc[i][j][4 * k + 3]};
-            if (epi.bias != nullptr && n < N) {          // N % 8 == 0: a run is all in or all out
-              float b[4];
-              unpack4<DT>(*(const u32x2*)(epi.bias + n), b);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] += b[e];
-            }
-            if (epi.act != 0) {
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], epi.act);
-            }
-            *(u32x2*)(stg + frow * PITCH + cl * 2) = pack4<DT>(v[0], v[1], v[2], v[3]);
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own staging writes (no other wave touches them)
-#pragma unroll
-        for (int it = 0; it < 32 / RPP; ++it) {
-          const int row = it * RPP + lane / (WN / 8), piece = lane % (WN / 8);
-          const int m = m0 + wm * (BM / 2) + j * 32 + row, n = n0 + wn * WN + piece * 8;
-          u32x4 o = *(const u32x4*)(stg + row * PITCH + piece * 16);
-          if (m < M && n < N) {
-            if (epi.res != nullptr || epi.rowscale != nullptr) {
-              const float rs = epi.rowscale != nullptr ? epi.rowscale[m / epi.rows_per_sample] : 1.f;
-              const u32x4 rr = epi.res != nullptr ? *(const u32x4*)(epi.res + (long)m * ldy + n) : u32x4{0u, 0u, 0u, 0u};
-              float a[4], b[4], c[4], d[4];
-              unpack4<DT>(u32x2{o[0], o[1]}, a);
-              unpack4<DT>(u32x2{o[2], o[3]}, b);
-              unpack4<DT>(u32x2{rr[0], rr[1]}, c);
-              unpack4<DT>(u32x2{rr[2], rr[3]}, d);
-              u32x2 lo, hi;
-              if (epi.act == 4) {
-                // `res` carries the PRE-ACTIVATION z of an exact-erf GELU that sits in front of this layer's input: the result is
-                // the gradient with respect to z, (rs * branch) * gelu'(z) -- the Mix-FFN's fc2 input gradient handed straight to
-                // the depthwise backward (mix_transformer.py:99-102), no separate gelu_backward pass
-                lo = pack4<DT>(rs * a[0] * gelu_grad(c[0]), rs * a[1] * gelu_grad(c[1]), rs * a[2] * gelu_grad(c[2]),
-                               rs * a[3] * gelu_grad(c[3]));
-                hi = pack4<DT>(rs * b[0] * gelu_grad(d[0]), rs * b[1] * gelu_grad(d[1]), rs * b[2] * gelu_grad(d[2]),
-                               rs * b[3] * gelu_grad(d[3]));
-              } else {
-                lo = pack4<DT>(c[0] + rs * a[0], c[1] + rs * a[1], c[2] + rs * a[2], c[3] + rs * a[3]);
-                hi = pack4<DT>(d[0] + rs * b[0], d[1] + rs * b[1], d[2] + rs * b[2], d[3] + rs * b[3]);
+          for (int it = 0; it < 32 / RPP; ++it) {
+            const int row = it * RPP + lane / (WN / 8), piece = lane % (WN / 8);
+            const int m = m0 + wm * (BM / 2) + j * 32 + row, n = n0 + wn * WN + piece * 8;
+            u32x4 o = *(const u32x4*)(stg + row * PITCH + piece * 16);
+            if (m < M && n < N) {
+              if (epi.res != nullptr || epi.rowscale != nullptr) {
+                const float rs = epi.rowscale != nullptr ? epi.rowscale[m / epi.rows_per_sample] : 1.f;
+                const u32x4 rr = epi.res != nullptr ? *(const u32x4*)(epi.res + (long)m * ldy + n) : u32x4{0u, 0u, 0u, 0u};
+                float a[4], b[4], c[4], d[4];
+                unpack4<DT>(u32x2{o[0], o[1]}, a);
+                unpack4<DT>(u32x2{o[2], o[3]}, b);
+                unpack4<DT>(u32x2{rr[0], rr[1]}, c);
+                unpack4<DT>(u32x2{rr[2], rr[3]}, d);
+                u32x2 lo, hi;
+                if (epi.act == 4) {
+                  // `res` carries the PRE-ACTIVATION z of an exact-erf GELU that sits in front of this layer's input: the result is
+                  // the gradient with respect to z, (rs * branch) * gelu'(z) -- the Mix-FFN's fc2 input gradient handed straight to
+                  // the depthwise backward (mix_transformer.py:99-102), no separate gelu_backward pass
+                  lo = pack4<DT>(rs * a[0] * gelu_grad(c[0]), rs * a[1] * gelu_grad(c[1]), rs * a[2] * gelu_grad(c[2]),
+                                 rs * a[3] * gelu_grad(c[3]));
+                  hi = pack4<DT>(rs * b[0] * gelu_grad(d[0]), rs * b[1] * gelu_grad(d[1]), rs * b[2] * gelu_grad(d[2]),
+                                 rs * b[3] * gelu_grad(d[3]));
+                } else {
+                  lo = pack4<DT>(c[0] + rs * a[0], c[1] + rs * a[1], c[2] + rs * a[2], c[3] + rs * a[3]);
+                  hi = pack4<DT>(d[0] + rs * b[0], d[1] + rs * b[1], d[2] + rs * b[2], d[3] + rs * b[3]);
+                }
+                o = u32x4{lo[0], lo[1], hi[0], hi[1]};
               }
-              o = u32x4{lo[0], lo[1], hi[0], hi[1]};
+              *(u32x4*)(Y + (long)m * ldy + n) = o;
             }
-            *(u32x4*)(Y + (long)m * ldy + n) = o;
           }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // staging reads done before the next j block overwrites
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // staging reads done before the next j block overwrites
       }
       c_kt = 0;
       c_tile += G;
-      drained = true;
     }
   }
 }
@@ -988,17 +978,68 @@ __global__ __launch_bounds__(256) void gemm_tn_group_kernel(TnGroup grp, const v
                                                q.rows_per_sample, zero, WgradGeom{}, (int)blockIdx.x - q.first, q.nblk);
 }
 
-__device__ uint4 g_zero_page[4];          // zero-initialised: DMA source of out-of-image / padding pieces
-// its device address, looked up once (a library's first call is an eager warm-up, never inside a capture); null: lookup failed
-static const void* zero_page() {
-  static void* page = nullptr;
-  if (page == nullptr && hipGetSymbolAddress(&page, HIP_SYMBOL(g_zero_page)) != hipSuccess) page = nullptr;
-  return page;
-}
-
 // gemm2.hip (its own translation unit: this file is built with MFMA results in VGPRs, gemm2.h pins its accumulators to AGPRs)
 int launch_nt2(const void* X, const void* W, void* Y, long M, long N, long K, long ldx, long ldw, long ldy, const void* bias,
                const void* res, const float* rowscale, int rows_per_sample, int bn2, long t2, hipStream_t s);
+
+// Second-generation kernel (gemm2.h: software-pipelined K loop, stores dripped under the next tile's MFMAs) for the big bf16
+// Linear layers whose column count is a multiple of 320 -- every GEMM of MiT-B5's stage 3 on the teacher's 40 views:
+// 1.2-1.5x on those shapes (profiles/r04_gemm2_v3_probe.txt); bit-identical results -- and, as 192 x 256 tiles, for the
+// other big problems with N % 256 == 0 (stages 2 / 4, the decode heads' 1 x 1 convolutions), which the 8-wave 256 x 256
+// tile of the first generation served (192 x 256 from K = 256 on: at K = 128 the 8-wave tile is 3-7 % faster, at K >= 512
+// the new one 1.1-1.45 x -- profiles/r04_gemm2_256_ab.txt).  nt2_width: its tile width for (N, K), 0 = none.
+static int nt2_width(long N, long K) { return N % 320 == 0 ? 320 : (N % 256 == 0 && K >= 256 ? 256 : 0); }
+static bool nt2_takes(const void* X, const void* W, const void* Y, long M, long K, long ldx, long ldw, long ldy,
+                      const GemmEpi& epi, bool out32, int bn2, long t2) {
+  return bn2 != 0 && !out32 && epi.act == 0 &&                                      // a 16-bit result, no activation
+         K >= 192 && K % 64 == 0 &&                                                 // K-steps that carry the previous tile's stores
+         t2 >= 200 &&                                                               // enough 192-row tiles to fill the chip
+         (M + 192) * ldy * 2 < (1L << 32) && ldx < (1L << 22) && ldw < (1L << 22) &&   // its 32-bit offsets
+         (((size_t)X | (size_t)W | (size_t)Y) & 15) == 0 &&                         // 16-byte aligned operands
+         (epi.res == nullptr || ((size_t)epi.res & 15) == 0);
+}
+
+// Which first-generation instance a problem gets, and its grid.
+struct NtTile {
+  int bm, bn, nw;          // 256 x 256 on 8 waves; 128 x 128, 128 x 64 or 64 x 64 on 4 (bm drops to 64 only after bn has)
+  bool persistent;
+  int tiles_n;
+  long total;
+  unsigned grid;
+};
+static NtTile nt_tile(long M, long N, long K, bool out32) {
+  int bm = 128, bn = (N % 128 == 0) ? 128 : 64;
+  bool persistent = false;
+  if (out32) {
+    // fp32 result (split-bf16 parity mode): two square tile shapes, one tile per workgroup
+    bm = bn;
+  } else {
+    // the largest of 128 x 128 (N % 128 == 0), 128 x 64, 64 x 64 that still gives ~1000 tiles (2-4 workgroups per CU
+    // are resident; a launch of 300-600 big tiles is one and a bit rounds of a latency chain -- swept on replayed graphs in
+    // round 3, profiles/r03_gemm_sweep.txt: 8160 x 320 -> 1280: 21.6 -> 18.1 us, 8160 x 1280 -> 320: 19.5 -> 17.5,
+    // 2040 x 512 -> 2048: 13.7 -> 11.1).  ~2000 since the end of round 4: in the step, next to two other streams, the smaller
+    // tiles of the 1000-2000 band win (profiles/r04_knob_sweep.txt, r04_knob_ab.txt).
+    constexpr long min_tiles = 2000;
+    if ((long)cdiv(M, 128) * cdiv(N, bn) < min_tiles) {
+      bn = 64;
+      if ((long)cdiv(M, 128) * cdiv(N, 64) < min_tiles) bm = 64;
+    }
+    // big problems whose n extent fills 256-wide tiles: 8 waves on a 256 x 256 tile (1 workgroup per CU); with a long
+    // reduction (K >= 1024) already from 128 tiles on (20400 x 2048 -> 512: 74.8 -> 59.7 us)
+    if (N % 256 == 0 && (long)cdiv(M, 256) * (N / 256) >= (K >= 1024 ? 128 : 256)) bm = bn = 256;
+    // persistent (one pipeline across tiles) pays when a tile has only a few K-steps: the next tile's loads hide under the
+    // epilogue.  With many K-steps per tile the plain one-tile-per-workgroup launch measured faster (dispatcher refills a CU
+    // the moment a workgroup retires; its stores drain behind it).
+    persistent = K <= 256;
+  }
+  const int tiles_n = cdiv(N, bn);
+  const long total = (long)cdiv(M, bm) * tiles_n;
+  // persistent: workgroups per CU by LDS (two stages of (bm + bn) * 128 bytes; 160 KB per CU), at most 4, on 256 CUs
+  const int ring = 2 * (bm + bn) * 128;
+  const int per_cu = std::max(1, std::min(160 * 1024 / ring, 4));
+  const long slots = persistent ? 256 * per_cu : 0x7fffffff;
+  return {bm, bn, bm == 256 ? 8 : 4, persistent, tiles_n, total, (unsigned)std::min(total, slots)};
+}
 
 template <int DT, bool GATHER>
 static int launch_nt(const void* X, const void* W, void* Y, long M, long N, long K, long ldx, long ldw, long ldy,
@@ -1007,75 +1048,25 @@ static int launch_nt(const void* X, const void* W, void* Y, long M, long N, long
     cg.zero = zero_page();
     if (cg.zero == nullptr) return fail(RFN_ELAUNCH, "conv2d_nhwc: zero page symbol");
   }
-  // second-generation kernel (gemm2.h: software-pipelined K loop, stores dripped under the next tile's MFMAs) for the big
-  // Linear layers whose column count is a multiple of 320 -- every GEMM of MiT-B5's stage 3 on the teacher's 40 views:
-  // 1.2-1.5x on those shapes (profiles/r04_gemm2_v3_probe.txt); bit-identical results -- and, as 192 x 256 tiles, for the
-  // other big problems with N % 256 == 0 (stages 2 / 4, the decode heads' 1 x 1 convolutions), which the 8-wave 256 x 256
-  // tile of the first generation served.  
   if constexpr (!GATHER && DT == 1) {
-    constexpr long g2_min = 200;
-    // (192 x 256 from K = 256 on: at K = 128 the 8-wave tile is 3-7 % faster, at K >= 512 the new one 1.1-1.45 x --
-    // profiles/r04_gemm2_256_ab.txt)
-    const int bn2 = N % 320 == 0 ? 320 : (N % 256 == 0 && K >= 256 ? 256 : 0);
+    const int bn2 = nt2_width(N, K);
     const long t2 = bn2 ? (long)cdiv(M, 192) * (N / bn2) : 0;
-    if (bn2 && !out32 && K >= 192 && K % 64 == 0 && epi.act == 0 && t2 >= g2_min &&
-        (M + 192) * ldy * 2 < (1L << 32) && ldx < (1L << 22) && ldw < (1L << 22) && (((size_t)X | (size_t)W | (size_t)Y) & 15) == 0 &&
-        (epi.res == nullptr || ((size_t)epi.res & 15) == 0)) {
+    if (nt2_takes(X, W, Y, M, K, ldx, ldw, ldy, epi, out32, bn2, t2))
       return launch_nt2(X, W, Y, M, N, K, ldx, ldw, ldy, epi.bias, epi.res, epi.rowscale, epi.rows_per_sample, bn2, t2, s);
-    }
   }
-  // tile: the largest of 128 x 128 (N % 128 == 0), 128 x 64, 64 x 64 that still gives ~1000 tiles (2-4 workgroups per CU
-  // are resident; a launch of 300-600 big tiles is one and a bit rounds of a latency chain -- swept on replayed graphs in
-  // round 3, profiles/r03_gemm_sweep.txt: 8160 x 320 -> 1280: 21.6 -> 18.1 us, 8160 x 1280 -> 320: 19.5 -> 17.5,
-  // 2040 x 512 -> 2048: 13.7 -> 11.1).  ~2000 since the end of round 4: in the step, next to two other streams, the smaller
-  // tiles of the 1000-2000 band win (profiles/r04_knob_sweep.txt, r04_knob_ab.txt).
-  constexpr long min_tiles = 2000;
-  int bn = (N % 128 == 0) ? 128 : 64, bm = 128;
-  if ((long)cdiv(M, 128) * cdiv(N, bn) < min_tiles) {
-    bn = 64;
-    if ((long)cdiv(M, 128) * cdiv(N, 64) < min_tiles) bm = 64;
-  }
-  // big problems whose n extent fills 256-wide tiles: 8 waves on a 256 x 256 tile (1 workgroup per CU); with a long
-  // reduction (K >= 1024) already from 128 tiles on (20400 x 2048 -> 512: 74.8 -> 59.7 us)
-  if (N % 256 == 0 && (long)cdiv(M, 256) * (N / 256) >= (K >= 1024 ? 128 : 256)) bm = bn = 256;
-  const int tiles_m = cdiv(M, bm), tiles_n = cdiv(N, bn);
-  const long total = (long)tiles_m * tiles_n;
-  // workgroups per CU by LDS (2-deep ring of (bm + bn) * 128 bytes; 160 KB per CU), at most 4
-  const int ring = 2 * (bm + bn) * 128;
-  const int per_cu = std::max(1, std::min(160 * 1024 / ring, 4));
-  // persistent (one pipeline across tiles) pays when a tile has only a few K-steps: the next tile's loads hide under the
-  // epilogue.  With many K-steps per tile the plain one-tile-per-workgroup launch measured faster (dispatcher refills a CU
-  // the moment a workgroup retires; its stores drain behind it).
-  const bool persistent = K <= 256;
-  const int slots = persistent ? 256 * per_cu : 0x7fffffff;
-  dim3 grid((unsigned)std::min<long>(total, slots));
-#define RFN_NT(BM_, BN_, NW_, OUT32_, GRID_, TILES_N_, TOTAL_)                                                            \
-  hipLaunchKernelGGL((gemm_nt_kernel<DT, BM_, BN_, 64, 2, GATHER, NW_, OUT32_>), GRID_, dim3(64 * NW_), 0, s,              \
-                     (const uint16_t*)X, (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, TILES_N_, \
-                     (int)(TOTAL_), epi, cg)
-  if (out32) {                                  // fp32 result (split-bf16 parity mode): two tile shapes, no persistence
-    bn = (N % 128 == 0) ? 128 : 64;
-    bm = bn;
-    const int tn = cdiv(N, bn);
-    const long tot = (long)cdiv(M, bm) * tn;
-    dim3 g32((unsigned)tot);
-    if (bn == 128) RFN_NT(128, 128, 4, true, g32, tn, tot);
-    else RFN_NT(64, 64, 4, true, g32, tn, tot);
-    return check_launch("gemm_nt (fp32 result)");
-  }
-  // (bm, bn) is one of 256 x 256, 128 x 128, 128 x 64, 64 x 64: bm drops to 64 only after bn has
-  if (bm == 256) {
-    grid = dim3((unsigned)std::min<long>(total, persistent ? 256 : 0x7fffffff));
-    RFN_NT(256, 256, 8, false, grid, tiles_n, total);
-  } else if (bn == 128) {
-    RFN_NT(128, 128, 4, false, grid, tiles_n, total);
-  } else if (bm == 128) {
-    RFN_NT(128, 64, 4, false, grid, tiles_n, total);
-  } else {
-    RFN_NT(64, 64, 4, false, grid, tiles_n, total);
-  }
+  const NtTile t = nt_tile(M, N, K, out32);
+#define RFN_NT(BM_, BN_, NW_, OUT32_)                                                                                      \
+  hipLaunchKernelGGL((gemm_nt_kernel<DT, BM_, BN_, GATHER, NW_, OUT32_>), dim3(t.grid), dim3(64 * t.nw), 0, s,             \
+                     (const uint16_t*)X, (const uint16_t*)W, (uint16_t*)Y, (int)M, (int)N, (int)K, ldx, ldw, ldy, t.tiles_n, \
+                     (int)t.total, epi, cg)
+  if (out32 && t.bn == 128) RFN_NT(128, 128, 4, true);
+  else if (out32) RFN_NT(64, 64, 4, true);
+  else if (t.bm == 256) RFN_NT(256, 256, 8, false);
+  else if (t.bn == 128) RFN_NT(128, 128, 4, false);
+  else if (t.bm == 128) RFN_NT(128, 64, 4, false);
+  else RFN_NT(64, 64, 4, false);
 #undef RFN_NT
-  return check_launch("gemm_nt");
+  return check_launch(out32 ? "gemm_nt (fp32 result)" : "gemm_nt");
 }
 
 template <int DT, bool GATHER = false>
@@ -1130,6 +1121,16 @@ static ConvGeom conv_geom_dgrad(int H, int Wd, int N, int KH, int KW, int stride
   return {conv_out(H, KH, stride, pad, dil), conv_out(Wd, KW, stride, pad, dil), N, H, Wd, KH, KW, stride, pad, dil, N / 8,
           magic(N / 8), magic(KW), nullptr, 1, sshift};
 }
+// what rfn_conv2d_nhwc, rfn_conv2d_nhwc_o32 and rfn_conv2d_nhwc_dgrad ask of sizes and geometry alike; transposed: the data
+// gradient, whose stride is a power of two
+static int conv_check(const char* entry, int B, int H, int Wd, int C, int N, int KH, int KW, int stride, int pad, int dil,
+                      bool transposed) {
+  RFN_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 8 == 0 && N > 0 && N % 8 == 0, "%s: B=%d H=%d W=%d C=%d N=%d (C %% 8, N %% 8)",
+              entry, B, H, Wd, C, N);
+  RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0 && (!transposed || (stride & (stride - 1)) == 0),
+              "%s: kernel %dx%d stride %d%s pad %d dil %d", entry, KH, KW, stride, transposed ? " (power of two)" : "", pad, dil);
+  return RFN_OK;
+}
 static WgradGeom wgrad_geom(int H, int Wd, int C, int KH, int KW, int stride, int pad, int dil) {
   return {H, Wd, C, conv_out(H, KH, stride, pad, dil), conv_out(Wd, KW, stride, pad, dil), KH, KW, stride, pad, dil, magic(C),
           magic(KW)};
@@ -1144,7 +1145,6 @@ int rfn_gemm_nt(const void* X, const void* W, const void* bias, const void* res,
                 rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(X && W && Y, "gemm_nt: null operand");
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "gemm_nt: dtype %d (1 = bf16, 2 = f16)", dtype);
   RFN_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0, "gemm_nt: M=%ld N=%ld K=%ld (K %% 64, N %% 8)", M, N, K);
   RFN_REQUIRE(ldx % 8 == 0 && ldw % 8 == 0 && ldy % 8 == 0 && ldx >= K && ldw >= K && ldy >= N,
               "gemm_nt: leading dimensions must be multiples of 8 elements");
@@ -1154,8 +1154,9 @@ int rfn_gemm_nt(const void* X, const void* W, const void* bias, const void* res,
               "gemm_nt: act (0 none, 1 ReLU, 3 LeakyReLU 0.1, 4 = times gelu'(res), needs res)");
   GemmEpi epi{(const uint16_t*)bias, (const uint16_t*)res, rowscale, rows_per_sample > 0 ? rows_per_sample : 1, act};
   hipStream_t s = (hipStream_t)stream;
-  return dtype == 1 ? launch_nt<1, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, s)
-                    : launch_nt<2, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, s);
+  return dt16(dtype, "gemm_nt", [&](auto dt) {
+    return launch_nt<decltype(dt)::value, false>(X, W, Y, M, N, K, ldx, ldw, ldy, epi, ConvGeom{}, s);
+  });
 }
 
 int rfn_conv2d_nhwc(const void* X, const void* W, const void* bias, const void* res, int act, void* Y, int B, int H,
@@ -1163,11 +1164,7 @@ int rfn_conv2d_nhwc(const void* X, const void* W, const void* bias, const void* 
                     rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(X && W && Y, "conv2d_nhwc: null operand");
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "conv2d_nhwc: dtype %d (1 = bf16, 2 = f16)", dtype);
-  RFN_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 8 == 0 && N > 0 && N % 8 == 0, "conv2d_nhwc: B=%d H=%d W=%d C=%d N=%d "
-              "(C %% 8, N %% 8)", B, H, Wd, C, N);
-  RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_nhwc: kernel %dx%d stride %d pad %d dil %d",
-              KH, KW, stride, pad, dil);
+  if (const int rc = conv_check("conv2d_nhwc", B, H, Wd, C, N, KH, KW, stride, pad, dil, false)) return rc;
   const ConvGeom cg = conv_geom(H, Wd, C, KH, KW, stride, pad, dil);
   RFN_REQUIRE(cg.OH > 0 && cg.OW > 0, "conv2d_nhwc: empty output");
   const long K = conv_kpad(KH, KW, C), M = (long)B * cg.OH * cg.OW;
@@ -1177,13 +1174,14 @@ int rfn_conv2d_nhwc(const void* X, const void* W, const void* bias, const void* 
   RFN_REQUIRE(act == 0 || act == 1 || act == 3, "conv2d_nhwc: act (0 none, 1 ReLU, 3 LeakyReLU 0.1)");
   GemmEpi epi{(const uint16_t*)bias, (const uint16_t*)res, nullptr, 1, act};
   hipStream_t s = (hipStream_t)stream;
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && res == nullptr) {
-    // halo-tiled form (conv3x3.hip): the input tile staged once per 64 channels instead of once per tap
-    const int rc = launch_conv3x3_halo(X, W, bias, Y, B, H, Wd, C, N, ldw, ldy, act, dtype, 0, s);
-    if (rc != 1) return rc;
-  }
-  return dtype == 1 ? launch_nt<1, true>(X, W, Y, M, N, K, 0, ldw, ldy, epi, cg, s)
-                    : launch_nt<2, true>(X, W, Y, M, N, K, 0, ldw, ldy, epi, cg, s);
+  return dt16(dtype, "conv2d_nhwc", [&](auto dt) {
+    if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && dil == 1 && res == nullptr) {
+      // halo-tiled form (conv3x3.hip): the input tile staged once per 64 channels instead of once per tap
+      const int rc = launch_conv3x3_halo(X, W, bias, Y, B, H, Wd, C, N, ldw, ldy, act, dtype, 0, s);
+      if (rc != 1) return rc;
+    }
+    return launch_nt<decltype(dt)::value, true>(X, W, Y, M, N, K, 0, ldw, ldy, epi, cg, s);
+  });
 }
 
 int rfn_gemm_nt_o32(const void* X, const void* W, const float* bias, const float* res, const float* rowscale,
@@ -1205,9 +1203,7 @@ int rfn_conv2d_nhwc_o32(const void* X, const void* W, const float* bias, int act
                         rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(X && W && Y, "conv2d_nhwc_o32: null operand");
-  RFN_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 8 == 0 && N > 0 && N % 8 == 0, "conv2d_nhwc_o32: sizes (C %% 8, N %% 8)");
-  RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0 && (!transposed || (stride & (stride - 1)) == 0),
-              "conv2d_nhwc_o32: geometry");
+  if (const int rc = conv_check("conv2d_nhwc_o32", B, H, Wd, C, N, KH, KW, stride, pad, dil, transposed != 0)) return rc;
   RFN_REQUIRE(act == 0 || act == 1 || act == 3, "conv2d_nhwc_o32: act");
   // forward: X (B, H, W, C) -> Y (B, OH, OW, N), W[n][(tap, c)];  data gradient: X = grad_y (B, OH, OW, N), Y = dx (B, H, W, C),
   // W = Wt[c][(tap, n)].  Either way the GEMM's rows are Y's pixels, its reduction X's (tap, channel), its columns Y's channels
@@ -1228,11 +1224,7 @@ int rfn_conv2d_nhwc_dgrad(const void* GY, const void* Wt, void* DX, int B, int H
                           int stride, int pad, int dil, long ldw, long ldy, int dtype, rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(GY && Wt && DX, "conv2d_nhwc_dgrad: null operand");
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "conv2d_nhwc_dgrad: dtype %d (1 = bf16, 2 = f16)", dtype);
-  RFN_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 8 == 0 && N > 0 && N % 8 == 0, "conv2d_nhwc_dgrad: B=%d H=%d W=%d C=%d "
-              "N=%d (C %% 8, N %% 8)", B, H, Wd, C, N);
-  RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && (stride & (stride - 1)) == 0 && dil > 0 && pad >= 0,
-              "conv2d_nhwc_dgrad: kernel %dx%d stride %d (power of two) pad %d dil %d", KH, KW, stride, pad, dil);
+  if (const int rc = conv_check("conv2d_nhwc_dgrad", B, H, Wd, C, N, KH, KW, stride, pad, dil, true)) return rc;
   const ConvGeom cg = conv_geom_dgrad(H, Wd, N, KH, KW, stride, pad, dil);
   const int OH = cg.H, OW = cg.W;                    // grad_y's extent
   RFN_REQUIRE(OH > 0 && OW > 0, "conv2d_nhwc_dgrad: empty output");
@@ -1243,8 +1235,9 @@ int rfn_conv2d_nhwc_dgrad(const void* GY, const void* Wt, void* DX, int B, int H
   RFN_REQUIRE(M < (1L << 31) && K / 8 < 65536 && (long)OH * OW * N < (1L << 31), "conv2d_nhwc_dgrad: extent");
   GemmEpi epi{nullptr, nullptr, nullptr, 1, 0};
   hipStream_t s = (hipStream_t)stream;
-  return dtype == 1 ? launch_nt<1, true>(GY, Wt, DX, M, C, K, 0, ldw, ldy, epi, cg, s)
-                    : launch_nt<2, true>(GY, Wt, DX, M, C, K, 0, ldw, ldy, epi, cg, s);
+  return dt16(dtype, "conv2d_nhwc_dgrad", [&](auto dt) {
+    return launch_nt<decltype(dt)::value, true>(GY, Wt, DX, M, C, K, 0, ldw, ldy, epi, cg, s);
+  });
 }
 
 int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_bias, int B, int H, int Wd, int C, int N, int KH,
@@ -1252,7 +1245,6 @@ int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_b
                           int dtype, rfn_stream_t stream) {
   using namespace rfn;
   RFN_REQUIRE(GY && X && P, "conv2d_nhwc_wgrad: null operand");
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "conv2d_nhwc_wgrad: dtype %d", dtype);
   RFN_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 2 == 0 && N > 0 && N % 64 == 0, "conv2d_nhwc_wgrad: B=%d H=%d W=%d C=%d N=%d "
               "(C %% 2, N %% 64)", B, H, Wd, C, N);
   RFN_REQUIRE(KH > 0 && KW > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d_nhwc_wgrad: kernel %dx%d stride %d pad %d dil %d", KH,
@@ -1265,11 +1257,12 @@ int rfn_conv2d_nhwc_wgrad(const void* GY, const void* X, float* P, float* grad_b
               "conv2d_nhwc_wgrad: extent / rows_per_slab");
   RFN_REQUIRE(Kpad < 65536, "conv2d_nhwc_wgrad: Kpad=%ld", Kpad);
   RFN_REQUIRE(accumulate >= 0 && accumulate <= 2, "conv2d_nhwc_wgrad: accumulate %d (0, 1 or 2)", accumulate);
-  RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_conv2d_nhwc_wgrad",
-                    "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
   hipStream_t s = (hipStream_t)stream;
-  return dtype == 1 ? launch_tn<1, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg)
-                    : launch_tn<2, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg);
+  return dt16(dtype, "conv2d_nhwc_wgrad", [&](auto dt) {
+    RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_conv2d_nhwc_wgrad",
+                      "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
+    return launch_tn<decltype(dt)::value, true>(GY, X, P, T, N, Kpad, ldg, 0, rows_per_slab, accumulate, grad_bias, nullptr, 0, s, wg);
+  });
 }
 
 int rfn_gemm_tn(const void* G, const void* X, float* P, long T, long N, long K, long ldg, long ldx, int rows_per_slab,
@@ -1278,16 +1271,16 @@ int rfn_gemm_tn(const void* G, const void* X, float* P, long T, long N, long K, 
   using namespace rfn;
   RFN_REQUIRE(G && X && P, "gemm_tn: null operand");
   RFN_REQUIRE(rowscale == nullptr || rows_per_sample > 0, "gemm_tn: rowscale needs rows_per_sample");
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "gemm_tn: dtype %d", dtype);
   RFN_REQUIRE(T > 0 && T < (1L << 31) && rows_per_slab > 0 && rows_per_slab % 32 == 0,
               "gemm_tn: T=%ld rows_per_slab=%d (%% 32)", T, rows_per_slab);
   RFN_REQUIRE(N % 64 == 0 && K % 64 == 0 && ldg % 2 == 0 && ldx % 2 == 0, "gemm_tn: N=%ld K=%ld (%% 64)", N, K);
   RFN_REQUIRE(accumulate >= 0 && accumulate <= 2, "gemm_tn: accumulate %d (0, 1 or 2)", accumulate);
-  RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_gemm_tn",
-                    "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
   hipStream_t s = (hipStream_t)stream;
-  return dtype == 1 ? launch_tn<1>(G, X, P, T, N, K, ldg, ldx, rows_per_slab, accumulate, grad_bias, rowscale, rows_per_sample, s)
-                    : launch_tn<2>(G, X, P, T, N, K, ldg, ldx, rows_per_slab, accumulate, grad_bias, rowscale, rows_per_sample, s);
+  return dt16(dtype, "gemm_tn", [&](auto dt) {
+    RFN_REFUSE_NONDET(accumulate == 1 || (grad_bias != nullptr && accumulate != 2), "rfn_gemm_tn",
+                      "gemm_tn kernels, fp32 atomics (use accumulate = 2)");
+    return launch_tn<decltype(dt)::value>(G, X, P, T, N, K, ldg, ldx, rows_per_slab, accumulate, grad_bias, rowscale, rows_per_sample, s);
+  });
 }
 
 int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, float* const* P, float* const* grad_bias,
@@ -1327,14 +1320,11 @@ int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, f
   if (zero == nullptr) return fail(RFN_ELAUNCH, "gemm_tn_grouped: zero page symbol");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)blocks), block(256);
-  if (dtype == 1) {
-    if (seg) hipLaunchKernelGGL((gemm_tn_group_kernel<1, true>), grid, block, 0, s, grp, zero);
-    else hipLaunchKernelGGL((gemm_tn_group_kernel<1, false>), grid, block, 0, s, grp, zero);
-  } else {
-    if (seg) hipLaunchKernelGGL((gemm_tn_group_kernel<2, true>), grid, block, 0, s, grp, zero);
-    else hipLaunchKernelGGL((gemm_tn_group_kernel<2, false>), grid, block, 0, s, grp, zero);
-  }
-  return check_launch("gemm_tn_group_kernel");
+  return dt16(dtype, "gemm_tn_grouped", [&](auto dt) {
+    if (seg) hipLaunchKernelGGL((gemm_tn_group_kernel<decltype(dt)::value, true>), grid, block, 0, s, grp, zero);
+    else hipLaunchKernelGGL((gemm_tn_group_kernel<decltype(dt)::value, false>), grid, block, 0, s, grp, zero);
+    return check_launch("gemm_tn_group_kernel");
+  });
 }
 
 }  // extern "C"

@@ -197,6 +197,112 @@ def test_conv2d_autograd_on_mfma_kernels_matches_fp32_autograd(dev, dtype, B, H,
     assert float((b.grad - b16.grad).abs().max()) <= tol * float(b16.grad.abs().max()) + 1e-3
 
 
+# ---- the big tiles of gemm_nt_kernel.  Every shape above lands on the 64 x 64 tile (too few rows for the tile-count rules of
+# launch_nt); these are the smallest that its rules send to 128 x 128, 128 x 64 and 256 x 256.  With t(b) = ceil(M / b):
+_BF, _HF = torch.bfloat16, torch.float16
+BIG_TILE_GEMMS = [  # M, N, K, dtype, epilogue ("" = bias only, "act" = ReLU, "res" = residual + per-sample scale)
+    # 128 x 128: t(128) * 3 = 667 * 3 = 2001 >= 2000; N % 256 != 0 and N % 320 != 0 keep it off 256 x 256 and gemm2.h;
+    # K <= 256: persistent, 2001 tiles on 512 workgroups
+    (85300, 384, 128, _BF, ""), (85300, 384, 128, _HF, ""),
+    (85300, 384, 320, _BF, ""),                # K > 256: one tile per workgroup, 5 K-steps
+    # 128 x 64: N % 128 != 0, 667 * 3 = 2001
+    (85300, 192, 128, _BF, ""), (85300, 192, 128, _HF, ""), (85300, 192, 320, _BF, ""),
+    (127950, 128, 64, _BF, ""),                # 128 x 64 by the fall-through: 1000 tiles of 128 x 128 < 2000 = 1000 * 2; one K-step
+    (63950, 200, 128, _BF, ""),                # 128 x 64, ragged column tile: ceil(200 / 64) = 4, 500 * 4 = 2000
+    # 256 x 256: t(256) * 1 = 256 >= 256 (128 x 128 would be 511 * 2 < 2000); K < 192 keeps bf16 off gemm2.h
+    (65300, 256, 128, _BF, ""), (65300, 256, 128, _HF, ""),
+    (65300, 512, 128, _HF, ""),                # persistent: 512 tiles on 256 workgroups
+    # 256 x 256 by the K >= 1024 rule: t(256) = 128 >= 128; bf16: ceil(32700 / 192) = 171 tiles of gemm2.h < 200
+    (32700, 256, 1024, _BF, ""), (32700, 256, 1024, _HF, ""),
+    (85300, 384, 320, _BF, "act"), (85300, 384, 320, _BF, "res"),       # the other arms of the 128 x 128 epilogue
+]
+
+
+@pytest.mark.parametrize("M,N,K,dtype,epilogue", BIG_TILE_GEMMS)
+def test_gemm_nt_big_tiles(dev, M, N, K, dtype, epilogue):
+    """The 128 x 128, 128 x 64 and 256 x 256 instances of gemm_nt_kernel, ragged last row tile throughout, checked like
+    test_gemm_nt_second_generation_kernel: against the fp32 product of the same 16-bit operands (one 16-bit rounding of the
+    result, two with residual / scale), and against the same product in row chunks of 4096 rows, which run 64 x 64 tiles --
+    a row of y depends on its own row of x only and every tile shape walks k in the same order with the same MFMA, so the
+    results are identical; a stale LDS stage, a lost store or a tile mix-up cannot pass."""
+    from refign_amd.mfma import gemm_nt
+    x = _rand((M, K), dev, dtype, 51)
+    w = _rand((N, K), dev, dtype, 52, K ** -0.5)
+    b = _rand((N,), dev, dtype, 53)
+    rps = 2040
+    r = rows = None
+    if epilogue == "res":
+        r = _rand((M, N), dev, dtype, 54)
+        rs = (0.5 + torch.rand((M + rps - 1) // rps, device=dev)).float()
+        rs[1] = 0.0                                                   # a dropped sample
+        rows = rs.repeat_interleave(rps)[:M].contiguous()             # the same scales per row, for the chunks
+        got = gemm_nt(x, w, b, res=r, rowscale=rs, rows_per_sample=rps)
+    else:
+        got = gemm_nt(x, w, b, act=1 if epilogue == "act" else 0)
+    assert got is not None and got.dtype == dtype and got.shape == (M, N)
+    want = x.float() @ w.float().t() + b.float()
+    if epilogue == "act":
+        want = torch.relu(want)
+    if epilogue == "res":
+        want = r.float() + rows[:, None] * want
+        assert torch.equal(got[rps:2 * rps], r[rps:2 * rps])           # dropped sample: the residual passes through exactly
+    bound = (3 if epilogue == "res" else 2) * EPS[dtype] * float(want.abs().max())
+    assert float((got.float() - want).abs().max()) <= bound
+    parts = []
+    for m0 in range(0, M, 4096):
+        m1 = min(M, m0 + 4096)
+        if epilogue == "res":
+            parts.append(gemm_nt(x[m0:m1], w, b, res=r[m0:m1], rowscale=rows[m0:m1], rows_per_sample=1))
+        else:
+            parts.append(gemm_nt(x[m0:m1], w, b, act=1 if epilogue == "act" else 0))
+    chunked = torch.cat(parts)
+    if epilogue == "res":                                             # the allowance of the second-generation test
+        diff = (got.float() - chunked.float()).abs()
+        assert int((diff > 0).sum()) <= M * N // 100000 + 8 and float(diff.max()) <= 2 * EPS[dtype] * float(want.abs().max())
+    else:
+        assert torch.equal(got, chunked)
+
+
+BIG_TILE_CONVS = [  # B, H, W, C, N: 3 x 3, dilation 2, padding 2, stride 1 (never the halo kernel of conv3x3.hip)
+    (1, 506, 506, 64, 128),     # 128 x 128: 256 036 rows -> 2001 tiles; C % 64 == 0: the per-tap source pointers (`fastc`)
+    (1, 293, 293, 8, 192),      # 128 x 64: 85 849 rows -> 671 * 3 = 2013 tiles; C8 = 1: per-piece tap arithmetic, K = 72 -> 128
+    (1, 256, 256, 64, 256),     # 256 x 256: 65 536 rows -> 256 tiles, K = 576
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,H,W,C,N", BIG_TILE_CONVS)
+def test_conv2d_implicit_gemm_big_tiles(dev, dtype, B, H, W, C, N):
+    """The gathered 128 x 128, 128 x 64 and 256 x 256 instances against the fp32 convolution of the same 16-bit operands,
+    summed tap by tap (nine fp32 products of the shifted, zero-padded input); bias + LeakyReLU epilogue."""
+    from refign_amd.mfma import conv2d_nhwc, pack_conv_weight
+    import torch.nn.functional as F
+    x = _rand((B, H, W, C), dev, dtype, 60)
+    w = _rand((N, C, 3, 3), dev, dtype, 61, (C * 9) ** -0.5)
+    b = _rand((N,), dev, dtype, 62)
+    xp = F.pad(x.float(), (0, 0, 2, 2, 2, 2))
+    want = b.float().expand(B, H, W, N).clone()
+    for ky in range(3):
+        for kx in range(3):
+            want += xp[:, 2 * ky:2 * ky + H, 2 * kx:2 * kx + W] @ w[:, :, ky, kx].float().t()
+    want = F.leaky_relu(want, 0.1)
+    got = conv2d_nhwc(x, pack_conv_weight(w, dtype), b, 3, 3, 1, 2, 2, act=3)
+    assert got is not None and got.shape == want.shape
+    assert float((got.float() - want).abs().max()) <= 2 * EPS[dtype] * float(want.abs().max())
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("B,H,W,C,N,k,stride,pad,dil", [
+    # the input gradient has B H W = 86 436 rows (676 row tiles of 128) and C columns:
+    (1, 294, 294, 192, 64, 3, 2, 1, 1),       # 676 * 3 = 2028 >= 2000: the transposed gather on 128 x 64
+    (1, 294, 294, 64, 192, 3, 2, 1, 1),       # the mirrored channel counts: 676 < 2000, its 64 x 64 form at the same extent
+])
+def test_conv2d_input_gradient_big_tile(dev, dtype, B, H, W, C, N, k, stride, pad, dil):
+    """The data gradient (transposed-gather mode) on a tile larger than 64 x 64, through the autograd wrapper and with the
+    bounds of test_conv2d_autograd_on_mfma_kernels_matches_fp32_autograd."""
+    test_conv2d_autograd_on_mfma_kernels_matches_fp32_autograd(dev, dtype, B, H, W, C, N, k, stride, pad, dil)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("T,N,K,rows", [(8160, 320, 320, None), (2040, 512, 2048, None), (1000, 64, 256, 96),
                                         (4111, 128, 128, 512), (129600, 64, 64, None)])

@@ -72,7 +72,7 @@ def test_correlation_backward_is_repeatable_under_memory_load(B, C, H, W, reps):
 @pytest.mark.parametrize("M,N,K,res", [(81600, 320, 320, True), (81600, 320, 1280, True), (20400, 512, 2048, False),
                                        (8160, 1280, 320, False)])
 def test_gemm_nt_is_repeatable_under_memory_load(M, N, K, res):
-    """gemm_nt2_kernel (counted hand-off behind dripped stores) and gemm_nt_kernel (ring with counted waits): 60 launches."""
+    """gemm_nt2_kernel (counted hand-off behind dripped stores) and gemm_nt_kernel (two-stage ring, vmcnt(0) + one barrier per K-step): 60 launches."""
     from refign_amd import mfma
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(1)

@@ -59,10 +59,10 @@ static void launch_v(const uint16_t* X, const uint16_t* W, uint16_t* Y, int M, i
   static const int cap = getenv("G2_GRID") ? atoi(getenv("G2_GRID")) : 256;
   dim3 grid(total < cap ? total : cap), block(256);
   if (res)
-    hipLaunchKernelGGL((gemm_nt2_kernel<1, BM, BN, 2, 2, true, true, 0, NSK, D0, D1, D3, ABL>), grid, block, 0, s, X, W, Y,
+    hipLaunchKernelGGL((gemm_nt2_kernel<1, BM, BN, 2, 2, true, true, NSK, D0, D1, D3, ABL>), grid, block, 0, s, X, W, Y,
                        M, N, K, ldx, ldw, ldy, tiles_n, total, epi);
   else
-    hipLaunchKernelGGL((gemm_nt2_kernel<1, BM, BN, 2, 2, true, false, 0, NSK, D0, D1, D3, ABL>), grid, block, 0, s, X, W, Y,
+    hipLaunchKernelGGL((gemm_nt2_kernel<1, BM, BN, 2, 2, true, false, NSK, D0, D1, D3, ABL>), grid, block, 0, s, X, W, Y,
                        M, N, K, ldx, ldw, ldy, tiles_n, total, epi);
 }
 
@@ -249,7 +249,7 @@ int main(int argc, char** argv) {
       const int tiles_n = (int)N / 320, total = (int)((M + 191) / 192) * tiles_n;
       dim3 grid(total < 256 ? total : 256);
       CK(hipEventRecord(e0, st));
-      hipLaunchKernelGGL((gemm_nt2_kernel<1, 192, 320, 2, 2, true, false, 0, 3, 5, 5, 6, 0, true>), grid, dim3(256), 0, st, dx[0], dw,
+      hipLaunchKernelGGL((gemm_nt2_kernel<1, 192, 320, 2, 2, true, false, 3, 5, 5, 6, 0, true>), grid, dim3(256), 0, st, dx[0], dw,
                          dy[0], (int)M, (int)N, (int)K, K, K, N, tiles_n, total, epi);
       CK(hipEventRecord(e1, st));
       CK(hipStreamSynchronize(st));
