@@ -1,0 +1,356 @@
+"""refign_amd/datamodule.py -- the `data:` section of a Cityscapes -> ACDC / Cityscapes -> Dark Zurich configuration, from a
+directory of data sets to the batches Trainer.fit / validate / test / predict take.
+
+SegmentationDataModule reads `data.init_args` the way the reference's CombinedDataModule.__init__ does (sections, idx_to_name,
+batch sizes), builds the readers of refign_amd/datasets.py and feeds what exists already: config.train_section_plan /
+config.ingest_plan, datastep.RareClassSourceSampler / PairSampler / UDABatchAssembler, resample.EvalIngest.  No new kernel,
+no worker process.
+
+Who does what:
+  * every random draw and every piece of device work happens on the thread that calls next(): a second thread issuing HIP work
+    would break a graph capture in progress, and draws made elsewhere would interleave with the step's own;
+  * only opening and decoding files runs in a ThreadPoolExecutor (`num_workers` threads, the YAML's value, at most 16), into
+    pinned buffers that are used again once the copy that read them has finished.
+
+What is pinned, and what is not: the epoch's index order is torch's RandomSampler (epoch_permutation), the readers are the
+reference's, and with prefetch=0 the `random` stream is consumed in the reference's order (the source loader's samples, then
+the target loader's).  Lightning is not installed here: the order in which ITS loops create and advance the loaders' iterators
+(and the base seed a DataLoader iterator draws for its workers) is not restated, so parity with a Lightning run's batches is
+not claimed."""
+import collections
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import torch
+
+from . import config
+from .datasets import READERS
+
+MAX_WORKERS = 16
+_EVAL_KEYS = ("dims", "resize", "img_only", "only_if_larger", "mean", "std", "interpolation", "dims_interpolation", "pad")
+_SPLITS = ("train", "val", "test", "predict")
+
+
+def epoch_permutation(n):
+    """One epoch's index order as torch.utils.data.RandomSampler draws it: one int64 seed from the global torch stream, then
+    torch.randperm under a generator of its own."""
+    seed = int(torch.empty((), dtype=torch.int64).random_().item())
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed)).tolist()
+
+
+def _sections(load_config, split):
+    """[(data set, section)] of a split: a dict is one section, a list under a data set several"""
+    out = []
+    for ds, conf in (load_config.get(split) or {}).items():
+        if isinstance(conf, dict):
+            out.append((ds, conf))
+        elif isinstance(conf, list):
+            out.extend((ds, el) for el in conf)
+    return out
+
+
+def _one_section_cfg(split, name, conf):
+    """a config that holds this one section where the plan readers of refign_amd/config.py look for it"""
+    return {"data": {"init_args": {"load_config": {split: {name: conf}}}}}
+
+
+class _PinnedPool:
+    """uint8 pinned host buffers by shape.  A buffer comes back with the event behind the copy that read it; it is handed out
+    again after that event (waited for on the host, by the thread that asks)."""
+
+    def __init__(self, pin):
+        self.pin, self.free = pin, collections.defaultdict(list)
+
+    def take(self, shape):
+        shape = tuple(int(v) for v in shape)
+        if self.free[shape]:
+            buf, ev = self.free[shape].pop(0)
+            if ev is not None:
+                ev.synchronize()
+            return buf
+        return torch.empty(shape, dtype=torch.uint8, pin_memory=self.pin)
+
+    def give(self, bufs, ev):
+        for b in bufs:
+            self.free[tuple(b.shape)].append((b, ev))
+
+
+class _Source:
+    """what UDABatchAssembler asks of its source: `size` and sample(out_image, out_label); hands the sampler the (class, index)
+    pairs that were drawn ahead, when there are any"""
+
+    def __init__(self, sampler):
+        self.sampler, self.size, self.chosen = sampler, sampler.size, collections.deque()
+
+    def sample(self, out_image=None, out_label=None):
+        return self.sampler.sample(out_image, out_label, chosen=self.chosen.popleft() if self.chosen else None)
+
+
+class _EvalLoader:
+    """One evaluation section: decoded files through EvalIngest, stacked to the split's batch size, with `filename`.  Can be
+    iterated again (Trainer.fit validates more than once).  With a pool the next batch's files are decoded meanwhile."""
+
+    def __init__(self, reader, ingest, batch_size, pool):
+        self.reader, self.ingest, self.b, self.pool = reader, ingest, int(batch_size), pool
+
+    def __len__(self):
+        return -(-len(self.reader) // self.b)
+
+    def _decode(self, start):
+        idx = range(start, min(start + self.b, len(self.reader)))
+        if self.pool is None:
+            return [self.reader.decode(i) for i in idx]
+        return [self.pool.submit(self.reader.decode, i) for i in idx]
+
+    def __iter__(self):
+        starts = list(range(0, len(self.reader), self.b))
+        ahead = self._decode(starts[0]) if starts else None
+        for n, start in enumerate(starts):
+            now, ahead = ahead, (self._decode(starts[n + 1]) if n + 1 < len(starts) else None)
+            parts = []
+            for s in now:
+                s = s if isinstance(s, dict) else s.result()
+                parts.append(self.ingest(s["image"], semantic=s.get("semantic"), image_ref=s.get("image_ref")))
+            batch = {k: (parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts], dim=0)) for k in parts[0]}
+            batch["filename"] = [self.reader.filename(i) for i in range(start, min(start + self.b, len(self.reader)))]
+            yield batch
+
+
+class SegmentationDataModule:
+    """SegmentationDataModule(cfg, data_dir, device, prefetch=None): `cfg` is the loaded YAML; the data sets lie in
+    <data_dir>/Cityscapes, /ACDC and /DarkZurich.
+      train_on / val_on / test_on / predict_on, idx_to_name, batch_size, val_batch_size, test_batch_size: as CombinedDataModule
+      train_batches()              an endless iterator of {image_src, semantic_src, image_trg, image_ref} on the device
+      loaders(split, datasets)     {data set: iterable of batches} for Trainer.validate / test / predict
+      orig_dims[name]              the size Trainer.predict(orig_size=) interpolates to
+      close()                      ends the decoding threads
+    A data set without a reader here (RobotCar, NighttimeDriving, BDD100kNight, MegaDepth, RobotCarMatching) and
+    `ignore_every_second_semantic_training_batch` raise config.OutOfScopeError when the section is asked for, not before: a
+    Dark Zurich user picks the supported test sets with loaders('test', datasets=['DarkZurich']).
+    prefetch=0: files are decoded inside next(), and `random` is consumed in the reference's order.  prefetch=k > 0 (2 by default
+    when the YAML's num_workers > 0): files are decoded k batches ahead, within the epoch.  The target indices are known from the
+    permutation; the source loader's (class, file) choices are drawn ahead from a random.Random of its own, seeded once from the
+    global stream at the first next(); crop and flip draws stay in next(), on the global stream."""
+
+    orig_dims = {name: cls.orig_dims for name, cls in READERS.items()}
+
+    def __init__(self, cfg, data_dir, device, prefetch=None):
+        args = dict(((cfg or {}).get("data") or {}).get("init_args") or {})
+        self.cfg, self.data_dir, self.device = cfg, str(data_dir), torch.device(device)
+        self.load_config = args.get("load_config") or {}
+        self.num_workers = min(max(int(args.get("num_workers", 0)), 0), MAX_WORKERS)
+        batch_size, divisor = int(args.get("batch_size", 8)), int(args.get("batch_size_divisor", 1))
+        assert batch_size % divisor == 0, "batch_size must be divisible by batch_size_divisor"
+        self.batch_size = batch_size // divisor
+        self.pin_memory = bool(args.get("pin_memory", True))
+        self.ignore_every_second_semantic_training_batch = bool(args.get("ignore_every_second_semantic_training_batch", False))
+        self._sec = {split: _sections(self.load_config, split) for split in _SPLITS}
+        self.train_on, self.val_on = [n for n, _ in self._sec["train"]], [n for n, _ in self._sec["val"]]
+        self.test_on, self.predict_on = [n for n, _ in self._sec["test"]], [n for n, _ in self._sec["predict"]]
+        self.idx_to_name = {split: {i: n for i, (n, _) in enumerate(self._sec[split])} for split in _SPLITS}
+        if self.train_on:
+            assert self.batch_size % len(self.train_on) == 0, "batch size should be divisible by number of train datasets"
+        self.val_batch_size = max(1, self.batch_size // max(len(self.train_on), 1) // 2)
+        self.test_batch_size = 1
+        self.prefetch = (2 if self.num_workers > 0 else 0) if prefetch is None else int(prefetch)
+        if self.prefetch < 0:
+            raise ValueError("SegmentationDataModule: prefetch must not be negative")
+        self._pool = None
+        self._iters = []
+
+    # -- shared ------------------------------------------------------------------------------------------------------------
+    def _executor(self):
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max(1, self.num_workers), thread_name_prefix="refign-decode")
+        return self._pool
+
+    def _reader(self, split, name, conf):
+        if name not in READERS:
+            raise config.OutOfScopeError(f"SegmentationDataModule: {name} ({split}) has no reader here ({' / '.join(READERS)}); "
+                                         f"select the supported sections with datasets=")
+        kwargs = {k: v for k, v in conf.items() if k != "transforms"}
+        return READERS[name](f"{self.data_dir}/{name}", stage=split, **kwargs)
+
+    def close(self):
+        """ends the iterators' look-ahead and the decoding threads (waits for them)"""
+        for it in self._iters:
+            it.close()
+        self._iters = []
+        if self._pool is not None:
+            self._pool.shutdown(wait=True, cancel_futures=True)
+            self._pool = None
+
+    # -- evaluation ----------------------------------------------------------------------------------------------------------
+    def loaders(self, split, datasets=None):
+        """{data set: iterable of batches} in idx_to_name[split]'s order.  A batch: resample.EvalIngest(**config.ingest_plan(cfg,
+        split, name)) over the decoded files, stacked to the split's batch size (val: val_batch_size; test / predict: 1), plus
+        `filename` (a list).  datasets: the names to keep (every section by default)."""
+        if split not in ("val", "test", "predict"):
+            raise ValueError(f"SegmentationDataModule.loaders: split must be 'val', 'test' or 'predict', got {split!r}")
+        from .resample import EvalIngest
+        out = {}
+        for name, conf in self._sec[split]:
+            if datasets is not None and name not in datasets:
+                continue
+            if name in out:
+                raise config.OutOfScopeError(f"SegmentationDataModule: two sections of {name} in {split}: the loaders and the "
+                                             f"metrics are named by data set")
+            reader = self._reader(split, name, conf)
+            plan = config.ingest_plan(_one_section_cfg(split, name, conf), split, name)
+            kw = {k: plan[k] for k in _EVAL_KEYS}
+            if kw["dims"] is None:
+                kw["dims"] = tuple(reader.dims)                     # the reader's own default, which it resizes to as well
+            ingest = EvalIngest(device=self.device, **kw)
+            out[name] = _EvalLoader(reader, ingest, self.val_batch_size if split == "val" else self.test_batch_size,
+                                    self._executor() if self.num_workers > 0 else None)
+        return out
+
+    # -- training ------------------------------------------------------------------------------------------------------------
+    def train_batches(self):
+        """An endless iterator of training batches.  Per epoch and per loader (the source's, then the target's) one
+        epoch_permutation is drawn when the epoch's first batch is asked for; the epoch has min over the loaders of
+        len // per-loader batch size batches (`drop_last`, `multiple_trainloader_mode: min_size`).  Under rcs_enabled the source
+        loader ignores its indices.  A yielded batch has been waited for on the current stream; its buffers are written again two
+        batches later, after the work that was queued on the current stream by then (UDABatchAssembler.consumed for the batch that
+        held them), which fits Trainer.fit's look-ahead of one batch as well as a plain `for batch in ...: step(batch)`."""
+        if self.ignore_every_second_semantic_training_batch:
+            raise config.OutOfScopeError("SegmentationDataModule: ignore_every_second_semantic_training_batch (the semi-supervised "
+                                         "RobotCar recipe) is outside this module")
+        readers = [self._reader("train", name, conf) for name, conf in self._sec["train"]]
+        if self.device.type != "cuda":
+            raise RuntimeError("SegmentationDataModule.train_batches: a HIP device is required (no CPU fallback)")
+        it = _TrainIterator(self, readers)
+        self._iters.append(it)
+        return it
+
+
+class _TrainIterator:
+    def __init__(self, dm, readers):
+        from .datastep import PairSampler, RareClassSourceSampler, UDABatchAssembler
+        self.dm = dm
+        secs = dm._sec["train"]
+        plans = [config.train_section_plan(_one_section_cfg("train", name, conf), name) for name, conf in secs]
+        src = [i for i, r in enumerate(readers) if "semantic" in r.load_keys]
+        trg = [i for i, r in enumerate(readers) if "semantic" not in r.load_keys]
+        if len(secs) != 2 or len(src) != 1 or len(trg) != 1 or not {"image", "image_ref"} <= set(readers[trg[0]].load_keys):
+            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: one labelled source "
+                                         f"section and one (image, image_ref) target section is what the device data step assembles")
+        s, t = src[0], trg[0]
+        if s > t:
+            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: the source section "
+                                         f"comes first in every configuration carried here (its samples draw first)")
+        self.src, self.trg = readers[s], readers[t]
+        if not getattr(self.src, "rcs_enabled", False):
+            raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[s][0]} without rcs_enabled: the source sampler on the "
+                                         f"device is the rare-class one")
+        for (name, _), plan in zip(secs, plans):
+            if plan["crop_size"] is None or plan["flip"] != 0.5 or plan["rotation"] is not None or plan["jitter"] is not None:
+                raise config.OutOfScopeError(f"SegmentationDataModule: train.{name}: RandomCrop + RandomHorizontalFlip(p=0.5) is the "
+                                             f"pipeline the two samplers run")
+        self.per_loader = dm.batch_size // len(secs)
+        dims = [tuple(plans[i]["dims"] or readers[i].dims) for i in (s, t)]
+        self.source = _Source(RareClassSourceSampler(
+            self._load_src, self.src.rcs_classes, self.src.rcs_classprob, self.src.indices_with_class, plans[s]["crop_size"],
+            dm.device, cat_max_ratio=plans[s]["cat_max_ratio"], rcs_min_pixels=self.src.rcs_min_pixels,
+            rcs_min_crop_ratio=self.src.rcs_min_crop_ratio, mean=plans[s]["mean"], std=plans[s]["std"], dims=dims[0]))
+        self.pairs = PairSampler(self._load_trg, plans[t]["crop_size"], dm.device, mean=plans[t]["mean"], std=plans[t]["std"],
+                                 dims=dims[1])
+        self.asm = UDABatchAssembler(self.source, self.pairs, self.per_loader, dm.device)
+        self.n_batches = min(len(self.src), len(self.trg)) // self.per_loader
+        if self.n_batches == 0:
+            raise ValueError("SegmentationDataModule: a training set holds fewer files than one loader's batch")
+        self.pool = _PinnedPool(dm.pin_memory)
+        self.k = dm.prefetch
+        self.exe = dm._executor() if self.k > 0 else None
+        self.private = None                                  # the source loader's own stream (prefetch > 0)
+        self.order, self.pos = [], 0                         # the epoch's target indices and the next one to plan
+        self.pending = collections.deque()                   # planned batches: {"src": [...], "trg": [...], "bufs": [...]}
+        self.current = None
+        self.handed = collections.deque(maxlen=2)
+        self.sizes = {}
+        self.epoch, self.host_seconds = 0, 0.0
+
+    def __iter__(self):
+        return self
+
+    # -- decoding ------------------------------------------------------------------------------------------------------------
+    def _job(self, reader, which, index, bufs):
+        """start (or, without threads, do) the decoding of one file set into pinned buffers -> a future or the sample"""
+        key = (which, index)
+        if key not in self.sizes:
+            self.sizes[key] = {k: reader.size(index, k) for k in reader.load_keys}
+        out = {}
+        for k, (h, w) in self.sizes[key].items():
+            out[k] = self.pool.take((h, w) if k == "semantic" else (h, w, 3))
+            bufs.append(out[k])
+        views = {k: v.numpy() for k, v in out.items()}
+        if self.exe is None:
+            reader.decode(index, views)
+            return out
+        return self.exe.submit(lambda: (reader.decode(index, views), out)[1])
+
+    @staticmethod
+    def _done(x):
+        return x if isinstance(x, dict) else x.result()
+
+    def _load_src(self, index):
+        cur = self.current
+        s = self._done(cur["src"].popleft()[2]) if cur["src"] else self._job(self.src, "src", index, cur["bufs"])
+        return s["image"], s["semantic"]
+
+    def _load_trg(self, index):
+        cur = self.current
+        s = self._done(cur["trg"].popleft()[1]) if cur["trg"] else self._job(self.trg, "trg", index, cur["bufs"])
+        return s["image"], s["image_ref"]
+
+    # -- planning ------------------------------------------------------------------------------------------------------------
+    def _new_epoch(self):
+        epoch_permutation(len(self.src))                     # the source loader's: drawn, and ignored under rcs_enabled
+        self.order = epoch_permutation(len(self.trg))[:self.n_batches * self.per_loader]
+        self.pos = 0
+        self.epoch += 1
+
+    def _plan(self):
+        """one more batch of the current epoch: its target indices; with prefetch, its source choices and its decoding jobs"""
+        idx = self.order[self.pos:self.pos + self.per_loader]
+        self.pos += self.per_loader
+        entry = {"indices": idx, "src": collections.deque(), "trg": collections.deque(), "bufs": []}
+        if self.k > 0:
+            sam = self.source.sampler
+            for _ in range(self.per_loader):
+                c = self.private.choices(sam.rcs_classes, weights=sam.rcs_classprob, k=1)[0]
+                i = self.private.choice(sam.indices_with_class[c])
+                entry["src"].append((c, i, self._job(self.src, "src", i, entry["bufs"])))
+            for i in idx:
+                entry["trg"].append((i, self._job(self.trg, "trg", i, entry["bufs"])))
+        self.pending.append(entry)
+
+    def __next__(self):
+        import time
+        t0 = time.perf_counter()
+        if self.k > 0 and self.private is None:
+            self.private = random.Random(random.getrandbits(64))
+        if not self.pending:
+            if self.pos >= len(self.order):
+                self._new_epoch()
+            self._plan()
+        cur = self.current = self.pending.popleft()
+        while self.k > 0 and len(self.pending) < self.k and self.pos < len(self.order):
+            self._plan()
+        if len(self.handed) == 2:                            # the set that is written next was handed out two batches ago
+            self.asm.consumed(self.handed[0])
+        self.source.chosen.extend((c, i) for c, i, _ in cur["src"])
+        batch, ev = self.asm.assemble(cur["indices"])
+        self.pool.give(cur["bufs"], ev)
+        torch.cuda.current_stream(self.dm.device).wait_event(ev)
+        self.handed.append(batch)
+        self.current = None
+        self.host_seconds += time.perf_counter() - t0
+        return batch
+
+    def close(self):
+        for entry in self.pending:
+            for job in [j[-1] for j in list(entry["src"]) + list(entry["trg"])]:
+                if not isinstance(job, dict) and not job.cancel():
+                    job.result()
+        self.pending.clear()

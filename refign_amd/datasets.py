@@ -1,0 +1,246 @@
+"""refign_amd/datasets.py -- the readers of the three data sets behind the Cityscapes -> ACDC and Cityscapes -> Dark Zurich
+configurations: which files a stage reads, how an image is paired with its reference and its label map, and how a file becomes
+an array.  The semantics are the reference readers' (data_modules/datasets/{cityscapes,acdc,darkzurich}.py), restated:
+
+  * stage -> split: train -> train, val -> val, test -> val, predict -> test (ACDC / Dark Zurich: or `predict_on`);
+  * the walk is `os.listdir` as it comes (the file system's order: `paths` are parallel lists, their order carries no meaning);
+  * a missing folder is a RuntimeError;
+  * `decode(index)` stops at the DECODED file: the load-time resize to `dims` is the device's job (`dims=` of the samplers in
+    refign_amd/datastep.py, resample.EvalIngest), and so is everything after it.  `transforms` is accepted and ignored.
+
+No reader opens a file before `decode` is called, none starts a process or a thread."""
+import json
+import os
+
+import numpy as np
+
+_MISSING = ('Dataset not found or incomplete: {} must hold the folders {} of the split asked for')
+_STAGES = ("train", "val", "test", "predict")
+
+
+def _listed(x):
+    return [x] if isinstance(x, str) else list(x)
+
+
+class _Reader:
+    """what the three readers share: parallel path lists, `len`, `filename`, `decode`"""
+    orig_dims = None
+    keys = ("image", "image_ref", "semantic")
+
+    def _stage(self, stage, predict_on=None):
+        if stage not in _STAGES:
+            raise AssertionError(f"{type(self).__name__}: stage must be one of {_STAGES}, got {stage!r}")
+        self.stage = stage
+        # test runs on the val split; predict on the test split unless the section names another
+        self.split = {"train": "train", "val": "val", "test": "val", "predict": predict_on or "test"}[stage]
+
+    def _need(self, *dirs):
+        if not all(os.path.isdir(d) for d in dirs):
+            raise RuntimeError(_MISSING.format(self.root, " and ".join(os.path.relpath(d, self.root) for d in dirs)))
+
+    def __len__(self):
+        return len(next(iter(self.paths.values())))
+
+    def filename(self, index):
+        return self.paths["image"][index].split("/")[-1]
+
+    def decode(self, index, out=None):
+        """{key: uint8 array} of the section's load_keys: images (H, W, 3) through `convert('RGB')`, label maps (H, W) as
+        stored -- not resized.  out = {key: array of the decoded shape}: the pixels are written there (a pinned buffer)."""
+        from PIL import Image
+        sample = {}
+        for k in self.load_keys:
+            if k not in ("image", "image_ref", "semantic"):
+                raise ValueError(f"{type(self).__name__}: invalid load_key {k!r}")
+            with Image.open(self.paths[k][index]) as im:
+                a = np.array(im.convert("RGB") if k != "semantic" else im)         # a copy: writable, as torch wants it
+            if a.dtype != np.uint8:
+                raise ValueError(f"{self.paths[k][index]}: a uint8 file is required, got {a.dtype}")
+            if out is not None and k in out:
+                np.copyto(out[k], a)
+                a = out[k]
+            sample[k] = a
+        return sample
+
+    def size(self, index, key="image"):
+        """(H, W) of a file from its header"""
+        from PIL import Image
+        with Image.open(self.paths[key][index]) as im:
+            return im.size[1], im.size[0]
+
+
+class Cityscapes(_Reader):
+    """<root>/leftImg8bit/<split>/<city>/*_leftImg8bit.png with <root>/gtFine/<split>/<city>/*_gtFine_labelTrainIds.png.
+    rcs_enabled: `rcs_classes`, `rcs_classprob` (fp32 numpy) and `indices_with_class` of rare-class sampling from
+    <root>/sample_class_stats.json and <root>/samples_with_class.json (write_class_stats makes them)."""
+    orig_dims = (1024, 2048)
+
+    def __init__(self, root, stage="train", load_keys=("image", "semantic"), dims=(1024, 2048), transforms=None,
+                 rcs_enabled=False, rcs_class_temp=0.01, rcs_min_crop_ratio=0.5, rcs_min_pixels=3000, **kwargs):
+        self.root, self.dims = root, dims
+        self._stage(stage)
+        self.load_keys = _listed(load_keys)
+        self.paths = {k: [] for k in self.load_keys}
+        images, labels = os.path.join(root, "leftImg8bit", self.split), os.path.join(root, "gtFine", self.split)
+        self._need(images, labels)
+        for city in os.listdir(images):
+            for name in os.listdir(os.path.join(images, city)):
+                for k in self.load_keys:
+                    if k == "image":
+                        self.paths[k].append(os.path.join(images, city, name))
+                    elif k == "semantic":
+                        self.paths[k].append(os.path.join(labels, city,
+                                                          name.replace("leftImg8bit.png", "gtFine_labelTrainIds.png")))
+        self.rcs_enabled, self.rcs_class_temp = rcs_enabled, rcs_class_temp
+        self.rcs_min_crop_ratio, self.rcs_min_pixels = rcs_min_crop_ratio, rcs_min_pixels
+        if rcs_enabled:
+            self.rcs_classes, self.rcs_classprob = rcs_class_probs(root, rcs_class_temp)
+            with open(os.path.join(root, "samples_with_class.json")) as f:
+                with_class = {int(c): v for c, v in json.load(f).items()}
+            self.indices_with_class = {}
+            for c in self.rcs_classes:
+                self.indices_with_class[c] = [self.paths["semantic"].index(os.path.expandvars(file))
+                                              for file, pixels in with_class[c] if pixels > rcs_min_pixels]
+                assert len(self.indices_with_class[c]) > 0, f"Cityscapes: no file with more than {rcs_min_pixels} pixels of class {c}"
+
+
+def rcs_class_probs(root, temperature):
+    """-> (classes from the rarest to the most frequent, their sampling probabilities as fp32 numpy): the pixel counts of
+    <root>/sample_class_stats.json summed per class, sorted by count, softmax((1 - frequency) / temperature) -- in torch, with
+    the operations and their order as the reference has them (get_rcs_class_probs), so that the probabilities agree to the bit."""
+    import torch
+    with open(os.path.join(root, "sample_class_stats.json")) as f:
+        stats = json.load(f)
+    total = {}
+    for entry in stats:
+        for c, n in entry.items():
+            if c != "file":
+                total[int(c)] = total.get(int(c), 0) + n
+    total = dict(sorted(total.items(), key=lambda item: item[1]))
+    freq = torch.tensor(list(total.values()))
+    freq = freq / torch.sum(freq)
+    freq = 1 - freq
+    freq = torch.softmax(freq / temperature, dim=-1)
+    return list(total.keys()), freq.numpy()
+
+
+class ACDC(_Reader):
+    """<root>/rgb_anon/<condition>/<split>/<recording>/*_rgb_anon.png, its reference under <split>_ref with the file name's
+    `rgb_anon` -> `rgb_ref_anon`, its labels under <root>/gt/... as *_gt_labelTrainIds.png."""
+    orig_dims = (1080, 1920)
+
+    def __init__(self, root, stage="train", condition=("fog", "night", "rain", "snow"), load_keys=("image_ref", "image", "semantic"),
+                 dims=(1080, 1920), transforms=None, predict_on=None, **kwargs):
+        self.root, self.dims = root, dims
+        self._stage(stage, predict_on)
+        self.condition, self.load_keys = _listed(condition), _listed(load_keys)
+        self.paths = {k: [] for k in self.keys}
+        images, labels = os.path.join(root, "rgb_anon"), os.path.join(root, "gt")
+        self._need(images, labels)
+        for cond in self.condition:
+            parent = os.path.join(images, cond, self.split)
+            for recording in os.listdir(parent):
+                img_dir = os.path.join(parent, recording)
+                for name in os.listdir(img_dir):
+                    self.paths["image"].append(os.path.join(img_dir, name))
+                    # the reference pairs them by str.replace on the directory's path; here on the part below the root only,
+                    # so that a root whose own path holds the split's name pairs the same way
+                    ref_dir = os.path.join(images, os.path.join(cond, self.split, recording).replace(self.split, self.split + "_ref"))
+                    self.paths["image_ref"].append(os.path.join(ref_dir, name.replace("rgb_anon", "rgb_ref_anon")))
+                    self.paths["semantic"].append(os.path.join(labels, cond, self.split, recording,
+                                                               name.replace("rgb_anon.png", "gt_labelTrainIds.png")))
+
+
+class DarkZurich(_Reader):
+    """train: <root>/rgb_anon/<night>_rgb_anon.png with <root>/rgb_anon/<day>_rgb_anon.png for every `night,day` line of the
+    pair list; no labels.  val / test: <root>/rgb_anon/<split>/night/<recording>/*_rgb_anon.png, the reference under
+    <split>_ref/day/<recording>_ref -- val: the file name's `rgb_anon.png` -> `ref_rgb_anon.png`; test: the first file of that
+    directory (as os.listdir gives them) that starts with the frame's prefix -- and the labels under <root>/gt/....
+    pairs_csv: the list of training pairs, <root>/lists/zurich_dn_pair_train.csv when not given.  It is no part of this package:
+    the reference ships it as data_modules/datasets/lists/zurich_dn_pair_train.csv (it comes from the DANNet / MGCDA projects)."""
+    orig_dims = (1080, 1920)
+
+    def __init__(self, root, stage="train", load_keys=("image_ref", "image"), dims=(1080, 1920), transforms=None,
+                 predict_on=None, pairs_csv=None, **kwargs):
+        self.root, self.dims = root, dims
+        self._stage(stage, predict_on)
+        self.load_keys = _listed(load_keys)
+        if "semantic" in self.load_keys:
+            assert self.split != "train", "DarkZurich: the training split has no annotations"
+        self.paths = {k: [] for k in self.keys}
+        images, labels = os.path.join(root, "rgb_anon"), os.path.join(root, "gt")
+        self._need(images, labels)
+        if self.split == "train":
+            pairs_csv = pairs_csv or os.path.join(root, "lists", "zurich_dn_pair_train.csv")
+            if not os.path.isfile(pairs_csv):
+                raise FileNotFoundError(f"DarkZurich: the list of training pairs {pairs_csv} is missing (one `night,day` line per "
+                                        f"pair; the reference ships it as data_modules/datasets/lists/zurich_dn_pair_train.csv: "
+                                        f"copy it there or pass pairs_csv=)")
+            with open(pairs_csv) as f:
+                for line in f:
+                    night, day = line.strip().split(",")
+                    self.paths["image"].append(os.path.join(images, night + "_rgb_anon.png"))
+                    self.paths["image_ref"].append(os.path.join(images, day + "_rgb_anon.png"))
+            return
+        parent = os.path.join(images, self.split, "night")
+        for recording in os.listdir(parent):
+            img_dir = os.path.join(parent, recording)
+            # the reference's chain of str.replace, applied to the part of the path below the root only
+            ref_dir = os.path.join(images, os.path.join(self.split, "night", recording).replace(self.split, self.split + "_ref")
+                                   .replace("night", "day").replace(recording, recording + "_ref"))
+            for name in os.listdir(img_dir):
+                self.paths["image"].append(os.path.join(img_dir, name))
+                if self.split == "val":
+                    self.paths["image_ref"].append(os.path.join(ref_dir, name.replace("rgb_anon.png", "ref_rgb_anon.png")))
+                elif self.split == "test":
+                    start = name.split("rgb_anon.png")[0]
+                    self.paths["image_ref"].append(os.path.join(ref_dir, next(f for f in os.listdir(ref_dir) if f.startswith(start))))
+                self.paths["semantic"].append(os.path.join(labels, self.split, "night", recording,
+                                                           name.replace("rgb_anon.png", "gt_labelTrainIds.png")))
+
+
+READERS = {"Cityscapes": Cityscapes, "ACDC": ACDC, "DarkZurich": DarkZurich}
+
+
+def write_class_stats(root, out_dir=None, device=None, num_classes=19):
+    """The rare-class tables of a Cityscapes tree from the *_labelTrainIds.png files of its train split that are already there
+    (making those from the polygon files needs cityscapesscripts and is not done here):
+      sample_class_stats.json       [{class: pixels, ..., "file": label file}] -- classes with no pixel left out
+      sample_class_stats_dict.json  {label file: {class: pixels}}
+      samples_with_class.json       {class: [[label file, pixels], ...]}
+    in `out_dir` (the root when not given).  device: the counts come from datastep.device_label_hists, one whole-image box per
+    file; None: from numpy.  -> the list written to the first file."""
+    labels = os.path.join(root, "gtFine", "train")
+    if not os.path.isdir(labels):
+        raise RuntimeError(_MISSING.format(root, "gtFine/train"))
+    out_dir = out_dir or root
+    os.makedirs(out_dir, exist_ok=True)
+    files = sorted(os.path.join(d, f) for d, _, names in os.walk(labels) for f in names if f.endswith("_labelTrainIds.png"))
+    from PIL import Image
+    stats = []
+    for path in files:
+        with Image.open(path) as im:
+            lbl = np.ascontiguousarray(np.asarray(im))
+        if lbl.dtype != np.uint8 or lbl.ndim != 2:
+            raise ValueError(f"{path}: a single-channel uint8 label map is required")
+        if device is None:
+            hist = np.bincount(lbl.ravel(), minlength=256)
+        else:
+            import torch
+            from .datastep import device_label_hists
+            hist = device_label_hists(torch.from_numpy(lbl).to(device), [(0, 0, lbl.shape[0], lbl.shape[1])])[0]
+        entry = {int(c): int(hist[c]) for c in range(num_classes) if hist[c] > 0}
+        entry["file"] = path
+        stats.append(entry)
+    with open(os.path.join(out_dir, "sample_class_stats.json"), "w") as f:
+        json.dump(stats, f, indent=2)
+    by_file = {e["file"]: {c: n for c, n in e.items() if c != "file"} for e in stats}
+    with open(os.path.join(out_dir, "sample_class_stats_dict.json"), "w") as f:
+        json.dump(by_file, f, indent=2)
+    with_class = {}
+    for file, counts in by_file.items():
+        for c, n in counts.items():
+            with_class.setdefault(c, []).append((file, n))
+    with open(os.path.join(out_dir, "samples_with_class.json"), "w") as f:
+        json.dump(with_class, f, indent=2)
+    return stats

@@ -138,10 +138,15 @@ class RareClassSourceSampler:
             hist = counter([box])[0]
         return box, flip, hist
 
-    def draw(self):
-        """the random part of one sample -> (index, image_dev, label_dev, box, flip)"""
-        c = random.choices(self.rcs_classes, weights=self.rcs_classprob, k=1)[0]
-        index = random.choice(self.indices_with_class[c])
+    def draw(self, chosen=None):
+        """the random part of one sample -> (index, image_dev, label_dev, box, flip).  chosen=(c, index): the class and the file
+        were drawn elsewhere (a loader that decodes ahead, refign_amd/datamodule.py) -- the two draws are not made here, the crop
+        and flip draws are."""
+        if chosen is None:
+            c = random.choices(self.rcs_classes, weights=self.rcs_classprob, k=1)[0]
+            index = random.choice(self.indices_with_class[c])
+        else:
+            c, index = chosen
         img, lbl = self.load(index)
         if self.dims is not None:                          # np.asarray(PIL image) as it comes
             img, lbl = torch.as_tensor(img), torch.as_tensor(lbl)
@@ -160,8 +165,8 @@ class RareClassSourceSampler:
                 box, flip, hist = self._augment_params(lbl_d, h, w)   # "a new random crop" of the same image
         return index, img_d, lbl_d, box, flip
 
-    def sample(self, out_image=None, out_label=None):
-        _, img_d, lbl_d, (top, left, hh, ww), flip = self.draw()
+    def sample(self, out_image=None, out_label=None, chosen=None):
+        _, img_d, lbl_d, (top, left, hh, ww), flip = self.draw(chosen)
         if self.dims is not None:
             from .resample import resize_crop_flip_normalize
             out_image = resize_crop_flip_normalize(img_d, self.dims, top, left, hh, ww, flip, out_image, self.mean, self.std)
