@@ -34,7 +34,7 @@ extern "C" {
  *    the transpose-cast table holds rfn_multi_transpose_tile() x rfn_multi_transpose_tile() tiles (64; 32 before).
  * 4: new entry points, none changed: rfn_attn32_fwd / rfn_attn32_bwd (fp32 attention), rfn_split3_bf16 / rfn_split3_cat_bf16
  *    (operands of the split-bf16 products), rfn_ffn_fc1_dw_gelu_bf16 (fused Mix-FFN front half).
- * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed. */
+ * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed.  Added since, none changed: rfn_kv_path. */
 #define RFN_ABI_VERSION 5
 
 typedef void* rfn_stream_t; /* hipStream_t */
@@ -513,6 +513,24 @@ int rfn_ffn_fc1_dw_gelu_bf16(const void* x, const void* w1, const void* b1, cons
 /* The same with fp16 x, w1, b1 and a (fp16 MFMA). */
 int rfn_ffn_fc1_dw_gelu_f16(const void* x, const void* w1, const void* b1, const float* wdw_tap, const float* bdw, void* a,
                             int views, int H, int W, int C, int HID, rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Key / value path of a MiT attention block on gradient-free passes (mix_transformer.py:142-150) in one kernel:
+ *   x (B, H*W, C) tokens -> r x r / stride r convolution as a Linear over (ry, rx, c) patches + b_sr -> LayerNorm(gamma, beta,
+ *   eps) over C -> kv Linear (2C, C) + b_kv -> K's R-pack and V's T-pack as rfn_attn_fwd reads them: block
+ *   (b * 2 * heads + head) * nkblk + blk of 4 096 bytes, heads = C / 64, V's head h at head index heads + h, in k_rpack and
+ *   v_tpack (each B * 2 * heads * nkblk blocks; only K's blocks of k_rpack and V's blocks of v_tpack are written).  Rows past
+ *   Nkv = (H / r) * (W / r) -- the tail of a block and the block that makes nkblk even -- are written as zeros; rows and
+ *   columns of the map past (H / r) * r, (W / r) * r are dropped, as the convolution drops them.
+ * w_sr (C, r * r * C) rows of (ry, rx, c); b_sr (C); w_kv (2C, C); b_kv (2C): 16-bit, dtype 1 = bf16, 2 = f16; gamma, beta
+ * fp32.  kv_out: null, or the plain (B, Nkv, 2C) kv tensor (bit-equal to what the packs hold).
+ * r = 1: x rows are the kv Linear's operand (H * W rows per image); w_sr, b_sr, gamma, beta are not read.
+ * Built for (C, r) = (64, 8), (128, 4), (320, 2), (512, 1); anything else: RFN_EINVAL.  nkblk even, B * H * W * C < 2^31.
+ * blocks_per_wg: pack blocks per workgroup, 3 or 1; 0 = 3 unless that makes fewer than 128 workgroups (results do not depend on it).
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_kv_path(const void* x, const void* w_sr, const void* b_sr, const float* gamma, const float* beta, float eps,
+                const void* w_kv, const void* b_kv, void* k_rpack, void* v_tpack, void* kv_out, int B, int H, int W, int C,
+                int r, int nkblk, int blocks_per_wg, int dtype, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Training-mode BatchNorm2d (+ ReLU) on channels-last 16-bit tensors viewed as (T = B*H*W, C): the norm + activation of

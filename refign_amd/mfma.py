@@ -392,18 +392,91 @@ def _dims(q, kv):
     return B, N, C, Nkv, nkblk, nqblk, nqblk * 32
 
 
+def _nkblk(Nkv):
+    nkblk = -(-Nkv // 32)
+    return nkblk + (nkblk & 1)
+
+
+def _fwd_packed(q, kvr, kvt, heads, scale, Nkv, nkblk):
+    """The forward on ready packs: K's R-pack in `kvr`, V's T-pack in `kvt`, both in the 2 * heads layout of _fwd."""
+    B, N, C = q.shape
+    nqpad = -(-N // 32) * 32
+    voff = heads * nkblk * _PACK_BLOCK
+    o = torch.empty_like(q)
+    lse2 = torch.empty((B * heads, nqpad), dtype=torch.float32, device=q.device)
+    _lib.call("rfn_attn_fwd", q.device, ptr(q), q.stride(0), q.stride(1), kvr.data_ptr(), kvt.data_ptr() + voff, ptr(o), o.stride(0),
+              o.stride(1), ptr(lse2), B, heads, N, Nkv, nkblk, nqpad, float(scale), 2 * heads, _DT16[q.dtype])
+    return o, lse2
+
+
 def _fwd(q, kv, heads, scale, need_bwd):
     B, N, C, Nkv, nkblk, nqblk, nqpad = _dims(q, kv)
-    dev = q.device
     # K and V in one launch: the kv tensor is (B, Nkv, 2 * heads, 64), i.e. 2 * heads "heads"; V's head h is pack head
     # heads + h.  The forward needs K's R-pack and V's T-pack, the backward also V's R-pack and K's T-pack.
     (kvr, kvt), _ = _pack(kv, kv.stride(0), kv.stride(1), B, 2 * heads, Nkv, nkblk)
-    voff = heads * nkblk * _PACK_BLOCK
-    o = torch.empty_like(q)
-    lse2 = torch.empty((B * heads, nqpad), dtype=torch.float32, device=dev)
-    _lib.call("rfn_attn_fwd", dev, ptr(q), q.stride(0), q.stride(1), kvr.data_ptr(), kvt.data_ptr() + voff, ptr(o), o.stride(0),
-              o.stride(1), ptr(lse2), B, heads, N, Nkv, nkblk, nqpad, float(scale), 2 * heads, _DT16[q.dtype])
+    o, lse2 = _fwd_packed(q, kvr, kvt, heads, scale, Nkv, nkblk)
     return o, lse2, (kvr, kvt)
+
+
+KV_PATH_SHAPES = ((64, 8), (128, 4), (320, 2), (512, 1))     # (C, sr_ratio) csrc/kvpath.hip is built for: MiT-B1 ... B5
+
+
+def kv_packs(x, H, W, sr, norm, kv, want_kv=False, blocks_per_wg=0):
+    """Gradient-free key / value path of a MiT attention block in ONE kernel (csrc/kvpath.hip): `x` (B, H*W, C) = norm1 of the
+    block's input -> `sr` (the r x r / stride r convolution; None: no spatial reduction) -> `norm` -> `kv` Linear -> the packs
+    rfn_attn_fwd reads.  Returns (kvr, kvt, Nkv, nkblk, kv tensor or None) -- the first four are _fwd_packed's arguments -- or None
+    outside the kernel's domain (the caller then runs the layers one by one).  `blocks_per_wg`: 0 = the kernel's choice (tests force 1 or 3)."""
+    if not (ENABLED and x.is_cuda and x.dtype in _DT16 and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and not torch.is_grad_enabled()):
+        return None
+    from .params import as_dtype, compute_dtype, derived
+    B, N, C = x.shape
+    cd = x.dtype
+    if compute_dtype(x) != cd or N != H * W or x.numel() >= 2 ** 31 or kv.bias is None or kv.weight.shape != (2 * C, C):
+        return None
+    if sr is None:
+        r, Nkv = 1, N
+        w_sr = b_sr = gamma = beta = None
+        eps = 0.0
+    else:
+        r = sr.kernel_size[0]
+        if not (sr.kernel_size == (r, r) and sr.stride == (r, r) and sr.padding == (0, 0) and sr.dilation == (1, 1)
+                and sr.groups == 1 and sr.bias is not None and sr.weight.shape[:2] == (C, C) and H >= r and W >= r
+                and tuple(norm.normalized_shape) == (C,) and norm.weight is not None and norm.bias is not None):
+            return None
+        Nkv = (H // r) * (W // r)
+    if (C, r) not in KV_PATH_SHAPES:
+        return None
+    if sr is not None:
+        # the (Co, ry, rx, c) copy conv.patch_conv_tokens keeps (same cache entry, re-filled in place by params.refresh)
+        w_sr = derived(sr.weight, (cd, "patch_linear"), lambda t: t.to(cd).permute(0, 2, 3, 1).contiguous(),
+                       lambda t: t.permute(0, 2, 3, 1))
+        b_sr = as_dtype(sr.bias, cd)
+        gamma, beta = as_dtype(norm.weight, torch.float32).detach(), as_dtype(norm.bias, torch.float32).detach()
+        eps = float(norm.eps)
+        if not (gamma.is_contiguous() and beta.is_contiguous()):
+            return None
+    w_kv, b_kv = as_dtype(kv.weight, cd), as_dtype(kv.bias, cd)
+    if not (w_kv.is_contiguous() and b_kv.is_contiguous()):
+        return None
+    heads, nkblk = C // 64, _nkblk(Nkv)
+    nbytes = B * 2 * heads * nkblk * _PACK_BLOCK
+    packs = torch.empty(2 * nbytes, dtype=torch.uint8, device=x.device)
+    kvr, kvt = packs[:nbytes], packs[nbytes:]
+    kv_out = torch.empty((B, Nkv, 2 * C), dtype=cd, device=x.device) if want_kv else None
+    _lib.call("rfn_kv_path", x.device, ptr(x), ptr(w_sr), ptr(b_sr), ptr(gamma), ptr(beta), eps, ptr(w_kv), ptr(b_kv), ptr(kvr),
+              ptr(kvt), ptr(kv_out), B, H if sr is not None else N, W if sr is not None else 1, C, r, nkblk,
+              int(blocks_per_wg), _DT16[cd])
+    return kvr, kvt, Nkv, nkblk, kv_out
+
+
+def attention_packed(q, packs, heads, scale):
+    """attention() of a gradient-free pass on the packs kv_packs made; None outside the forward kernel's domain."""
+    if not (ENABLED and q.is_cuda and q.dtype in _DT16 and q.dim() == 3 and q.shape[2] == heads * 64 and q.is_contiguous()
+            and q.data_ptr() % 16 == 0 and not torch.is_grad_enabled()):
+        return None
+    kvr, kvt, Nkv, nkblk, _ = packs
+    return _fwd_packed(q, kvr, kvt, heads, scale, Nkv, nkblk)[0]
 
 
 def _chunk_blocks(nqblk, Nkv, BH):

@@ -156,6 +156,7 @@ def _fused_upcat_here():
     graph -- the library's bilinear backward on channel slices of the fused gradient was 34 ms/step slower than that)"""
     return _FUSED_UPCAT
 _SR_AS_LINEAR = True     # spatial-reduction conv as a Linear over patches
+_KV_FUSED = True         # gradient-free passes: spatial reduction + LayerNorm + kv Linear + K / V packs in one kernel
 
 
 class Attention(nn.Module):
@@ -184,13 +185,23 @@ class Attention(nn.Module):
         q = self.q(x)                                                        # (B,N,C) = (B,N,h,d)
         if x_kv is not None:
             x = x_kv
+        p = self.attn_drop.p if self.training else 0.0
+        if _KV_FUSED and not torch.is_grad_enabled() and x.is_cuda and d == 64 and p == 0.0 and _SDPA_BACKEND is None \
+                and q.dtype == x.dtype and type(self.kv) is Linear and not _f8.active() \
+                and (self.sr_ratio == 1 or (_SR_AS_LINEAR and type(self.norm) is LayerNorm)):
+            # gradient-free passes (EMA teacher's 40 views, ImageNet encoder): spatial reduction, LayerNorm, kv Linear and the
+            # attention kernel's K / V packs in ONE kernel (csrc/kvpath.hip); None outside its domain: the layers one by one
+            packs = mfma.kv_packs(x, H, W, self.sr if self.sr_ratio > 1 else None, self.norm if self.sr_ratio > 1 else None,
+                                  self.kv)
+            o = mfma.attention_packed(q, packs, h, self.scale) if packs is not None else None
+            if o is not None:
+                return self._project(o, res, rowscale)
         if self.sr_ratio > 1:
             r = patch_conv_tokens(x, H, W, self.sr) if _SR_AS_LINEAR else None   # (B, N/sr^2, C) tokens directly
             if r is None:
                 r = self.sr(x.transpose(1, 2).reshape(B, C, H, W)).flatten(2).transpose(1, 2)
             x = self.norm(r)
         kv = self.kv(x)                                                      # (B,Nkv,2C) = (B,Nkv,2,h,d)
-        p = self.attn_drop.p if self.training else 0.0
         # hand-written MFMA attention (csrc/attn.hip): head_dim 64, 16-bit operands, no attention dropout
         o = mfma.attention(q, kv, h, self.scale) if (d == 64 and p == 0.0 and _SDPA_BACKEND is None) else None
         if o is None and q.is_cuda and q.dtype == torch.float32 and p == 0.0 and _SDPA_BACKEND is None:
@@ -209,6 +220,9 @@ class Attention(nn.Module):
                 with torch.nn.attention.sdpa_kernel([_SDPA_BACKEND]):
                     o = F.scaled_dot_product_attention(q, k, v, dropout_p=p, scale=self.scale)
             o = o.transpose(1, 2).reshape(B, N, C)
+        return self._project(o, res, rowscale)
+
+    def _project(self, o, res, rowscale):
         if res is not None and self.proj_drop.p == 0.:
             return self.proj(o, res=res, rowscale=rowscale)
         y = self.proj_drop(self.proj(o))
