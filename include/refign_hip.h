@@ -447,7 +447,9 @@ int rfn_gemm_tn_grouped(int count, const void* const* G, const void* const* X, f
  *                     of a kv tensor are packed in ONE call as 2 x heads "heads" (V's head h is pack head heads + h):
  *                     the kernels take the pack pointers of K / V and kv_pack_heads = 2 x heads.
  *   rfn_attn_fwd      O and lse2[b*heads+h][nqpad] (base-2 log-sum-exp of the scaled scores), nkblk even.
- *   rfn_attn_bwd_dq   dQ, and delta[bh][nqpad] = rowsum(dO o O) for the dK/dV kernel.
+ *   rfn_attn_bwd_dq   dQ, and delta[bh][nqpad] = rowsum(dO o O) for the dK/dV kernel.  dO is addressed with O's strides.
+ *                     nqpad >= Nq (dK/dV: >= 32 * nqblk) is the row count of both statistics; their rows Nq .. nqpad - 1
+ *                     are written as 0.  Every base pointer is 16-byte aligned, every stride a multiple of 8 elements.
  *   rfn_attn_bwd_dkv  dKV (B, Nkv, 2, heads, 64); accT: fp32 scratch of B*heads*2*64*nkpad floats; the query dimension is
  *                     split into chunks of `blocks_per_chunk` 32-row blocks per workgroup.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -117,7 +117,9 @@ __device__ __forceinline__ void to_operands(const float (&p)[16], typename Elem<
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// forward.  grid (ceil(Nq / 128), B * heads), 4 waves x 32 queries.  K/V stream: stages of 64 keys, 2-deep LDS ring.
+// forward.  grid (ceil(nqpad / 128), B * heads), 4 waves x 32 queries.  K/V stream: stages of 64 keys, 2-deep LDS ring.
+// nqpad >= Nq is the row count of lse2 (and of dQ's delta): rows Nq .. nqpad - 1 are written as 0, which is what dK/dV streams
+// in beside its zero packs (tests/test_attention_gpu.py::test_statistics_rows_beyond_the_packs).
 // ---------------------------------------------------------------------------------------------------------------------
 template <int DT>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const uint16_t* __restrict__ Q, long qsb, long qsr,
@@ -629,7 +631,7 @@ int rfn_attn_fwd(const void* Q, long q_batch_stride, long q_row_stride, const vo
   RFN_REQUIRE(q_row_stride % 8 == 0 && o_row_stride % 8 == 0 && q_batch_stride % 8 == 0 && o_batch_stride % 8 == 0,
               "attn_fwd: strides must be multiples of 8 elements");
   RFN_REQUIRE(kv_pack_heads >= heads, "attn_fwd: kv_pack_heads");
-  dim3 grid(cdiv(Nq, 128), B * heads);
+  dim3 grid(cdiv(nqpad, 128), B * heads);      // nqpad >= Nq: every row of the statistics is written, 0 past Nq
   if (dtype == 1)
     hipLaunchKernelGGL(attn_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Q, q_batch_stride,
                        q_row_stride, (const unsigned char*)k_rpack, (const unsigned char*)v_tpack, (uint16_t*)O,
@@ -650,7 +652,11 @@ int rfn_attn_bwd_dq(const void* Q, long q_batch_stride, long q_row_stride, const
   RFN_REQUIRE(Q && dO && O && k_rpack && v_rpack && k_tpack && lse2 && delta && dQ, "attn_bwd_dq: null pointer");
   RFN_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0 && nkblk % 2 == 0 && nkblk * 32 >= Nkv && nqpad >= Nq,
               "attn_bwd_dq: B=%d heads=%d Nq=%d Nkv=%d nkblk=%d nqpad=%d", B, heads, Nq, Nkv, nkblk, nqpad);
-  dim3 grid(cdiv(Nq, 128), B * heads);
+  RFN_REQUIRE(q_row_stride % 8 == 0 && o_row_stride % 8 == 0 && dq_row_stride % 8 == 0 && q_batch_stride % 8 == 0 &&
+                  o_batch_stride % 8 == 0 && dq_batch_stride % 8 == 0,
+              "attn_bwd_dq: strides must be multiples of 8 elements");
+  RFN_REQUIRE(kv_pack_heads >= heads, "attn_bwd_dq: kv_pack_heads");
+  dim3 grid(cdiv(nqpad, 128), B * heads);      // nqpad >= Nq: every row of the statistics is written, 0 past Nq
 #define RFN_DQ_LAUNCH(D)                                                                                                \
   hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)Q, q_batch_stride, \
                      q_row_stride, (const uint16_t*)dO, (const uint16_t*)O, o_batch_stride, o_row_stride,               \
@@ -673,6 +679,7 @@ static int attn_bwd_dkv_impl(bool det, const void* K, const void* V, long kv_bat
                   nkpad % 32 == 0 && blocks_per_chunk > 0,
               "attn_bwd_dkv: B=%d heads=%d Nq=%d Nkv=%d nqblk=%d nqpad=%d nkpad=%d chunk=%d", B, heads, Nq, Nkv, nqblk,
               nqpad, nkpad, blocks_per_chunk);
+  RFN_REQUIRE(kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0, "attn_bwd_dkv: strides must be multiples of 8 elements");
   hipStream_t s = (hipStream_t)stream;
   // (a kernel, not a memset node, when the pass is captured into a hipGraph: capi.hip zero_async)
   const long image = (long)B * heads * 2 * 64 * nkpad, chunk_stride = det ? image : 0;
