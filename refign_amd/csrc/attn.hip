@@ -605,8 +605,6 @@ extern "C" {
 
 using namespace rfn;
 
-#define ATTN_DT_OK(dt) RFN_REQUIRE((dt) == 1 || (dt) == 2, "attention: dtype %d (1 = bf16, 2 = f16)", (dt))
-
 int rfn_attn_pack(const void* src, long batch_stride, long row_stride, int B, int heads, int nrows, int nblk, void* rpack,
                   void* tpack, const void* src2, void* rpack2, void* tpack2, rfn_stream_t stream) {
   RFN_REQUIRE(src && (rpack || tpack), "attn_pack: null pointer");
@@ -624,7 +622,7 @@ int rfn_attn_pack(const void* src, long batch_stride, long row_stride, int B, in
 int rfn_attn_fwd(const void* Q, long q_batch_stride, long q_row_stride, const void* k_rpack, const void* v_tpack, void* O,
                  long o_batch_stride, long o_row_stride, float* lse2, int B, int heads, int Nq, int Nkv, int nkblk,
                  int nqpad, float scale, int kv_pack_heads, int dtype, rfn_stream_t stream) {
-  ATTN_DT_OK(dtype);
+  if (int rc = dt16_check(dtype, "rfn_attn_fwd")) return rc;
   RFN_REQUIRE(Q && k_rpack && v_tpack && O && lse2, "attn_fwd: null pointer");
   RFN_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0 && nkblk % 2 == 0 && nkblk * 32 >= Nkv && nqpad >= Nq,
               "attn_fwd: B=%d heads=%d Nq=%d Nkv=%d nkblk=%d nqpad=%d", B, heads, Nq, Nkv, nkblk, nqpad);
@@ -648,7 +646,7 @@ int rfn_attn_bwd_dq(const void* Q, long q_batch_stride, long q_row_stride, const
                     const float* lse2, float* delta, void* dQ, long dq_batch_stride, long dq_row_stride, int B, int heads,
                     int Nq, int Nkv, int nkblk, int nqpad, float scale, int kv_pack_heads, int dtype,
                     rfn_stream_t stream) {
-  ATTN_DT_OK(dtype);
+  if (int rc = dt16_check(dtype, "rfn_attn_bwd_dq")) return rc;
   RFN_REQUIRE(Q && dO && O && k_rpack && v_rpack && k_tpack && lse2 && delta && dQ, "attn_bwd_dq: null pointer");
   RFN_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0 && nkblk % 2 == 0 && nkblk * 32 >= Nkv && nqpad >= Nq,
               "attn_bwd_dq: B=%d heads=%d Nq=%d Nkv=%d nkblk=%d nqpad=%d", B, heads, Nq, Nkv, nkblk, nqpad);
@@ -672,7 +670,7 @@ static int attn_bwd_dkv_impl(bool det, const void* K, const void* V, long kv_bat
                              const void* q_tpack, const void* do_rpack, const void* do_tpack, const float* lse2,
                              const float* delta, float* accT, void* dKV, int B, int heads, int Nq, int Nkv, int nqblk, int nqpad,
                              int nkpad, int blocks_per_chunk, float scale, int dtype, rfn_stream_t stream) {
-  ATTN_DT_OK(dtype);
+  if (int rc = dt16_check(dtype, det ? "rfn_attn_bwd_dkv_det" : "rfn_attn_bwd_dkv")) return rc;
   RFN_REQUIRE(K && V && q_rpack && q_tpack && do_rpack && do_tpack && lse2 && delta && accT && dKV,
               "attn_bwd_dkv: null pointer");
   RFN_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0 && nqblk * 32 >= Nq && nqpad >= nqblk * 32 && nkpad >= Nkv &&

@@ -27,25 +27,9 @@
 #include <type_traits>
 
 #include "common.h"
-#include "mfma.h"
+#include "elem.h"
 
 namespace rfn {
-
-template <int DT> __device__ __forceinline__ void load8(const uint16_t* p, float (&f)[8]) {
-  const u32x4 v = *(const u32x4*)p;
-  float a[4], b[4];
-  unpack4<DT>(u32x2{v[0], v[1]}, a);
-  unpack4<DT>(u32x2{v[2], v[3]}, b);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[i] = a[i];
-    f[4 + i] = b[i];
-  }
-}
-template <int DT> __device__ __forceinline__ void store8(uint16_t* p, const float (&f)[8]) {
-  const u32x2 lo = pack4<DT>(f[0], f[1], f[2], f[3]), hi = pack4<DT>(f[4], f[5], f[6], f[7]);
-  *(u32x4*)p = u32x4{lo[0], lo[1], hi[0], hi[1]};
-}
 
 // per-channel constants from the forward sums
 __device__ __forceinline__ float batch_var(const double* sums, int C, int c, double invT, float& mean) {
@@ -258,32 +242,41 @@ static int bn_launch(bool bwd, bool apply, const void* x, const void* g, const d
 extern "C" {
 using namespace rfn;
 
-#define RFN_BN_DISPATCH(...) (dtype == 1 ? bn_launch<1>(__VA_ARGS__) : bn_launch<2>(__VA_ARGS__))
-
 // activation code of the entry points (as rfn_gemm_nt): 0 none, 1 ReLU, 3 LeakyReLU(0.1)
 static inline float bn_slope(int act) { return act == 3 ? 0.1f : 0.f; }
 
-static int bn_check(const char* what, long T, int C, int dtype) {
+static int bn_check(const char* what, long T, int C) {
   RFN_REQUIRE(T >= 1 && C > 0 && C % 8 == 0, "%s: T=%ld C=%d (C %% 8)", what, T, C);
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "%s: dtype %d (1 = bf16, 2 = f16)", what, dtype);
   return RFN_OK;
 }
 
 int rfn_bn_stats_fwd(const void* x, double* sums, long T, int C, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && sums, "bn_stats_fwd: null pointer");
-  if (int rc = bn_check("bn_stats_fwd", T, C, dtype)) return rc;
-  RFN_REFUSE_NONDET(true, "rfn_bn_stats_fwd", "bn_stats_kernel, fp64 atomics (use rfn_bn_stats_fwd_det)");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), s)) return rc;   // kernel, not a memset node (capi.hip)
-  return RFN_BN_DISPATCH(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C, 0.f, 0.f, 0, 0.f, s);
+  if (int rc = bn_check("bn_stats_fwd", T, C)) return rc;
+  return dt16(dtype, "rfn_bn_stats_fwd", [&](auto dt) {
+    RFN_REFUSE_NONDET(true, "rfn_bn_stats_fwd", "bn_stats_kernel, fp64 atomics (use rfn_bn_stats_fwd_det)");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), s)) return rc;   // kernel, not a memset node (capi.hip)
+    return bn_launch<decltype(dt)::value>(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C,
+                                          0.f, 0.f, 0, 0.f, s);
+  });
+}
+
+// y may be a channel slice of a wider channels-last tensor: ld_y (0 = C) is its row pitch in elements
+static int bn_apply_fwd(const char* who, const void* x, const float* gamma, const float* beta, void* y, long ld_y, const double* sums,
+                        float* running_mean, float* running_var, long T, int C, float eps, float momentum, int relu, int dtype,
+                        rfn_stream_t stream) {
+  return dt16(dtype, who, [&](auto dt) {
+    return bn_launch<decltype(dt)::value>(false, true, x, nullptr, sums, nullptr, gamma, beta, y, running_mean, running_var, T, C, eps,
+                                          momentum, relu != 0, bn_slope(relu), (hipStream_t)stream, ld_y);
+  });
 }
 
 int rfn_bn_apply_fwd(const void* x, const float* gamma, const float* beta, void* y, const double* sums, float* running_mean,
                      float* running_var, long T, int C, float eps, float momentum, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && y && sums, "bn_apply_fwd: null pointer");
-  if (int rc = bn_check("bn_apply_fwd", T, C, dtype)) return rc;
-  return RFN_BN_DISPATCH(false, true, x, nullptr, sums, nullptr, gamma, beta, y, running_mean, running_var, T, C, eps, momentum,
-                         relu != 0, bn_slope(relu), (hipStream_t)stream);
+  if (int rc = bn_check("bn_apply_fwd", T, C)) return rc;
+  return bn_apply_fwd("rfn_bn_apply_fwd", x, gamma, beta, y, 0, sums, running_mean, running_var, T, C, eps, momentum, relu, dtype, stream);
 }
 
 // rfn_bn_apply_fwd with the result written at a row pitch of ld_y elements (>= C, multiple of 8): y is a channel slice of a
@@ -293,19 +286,29 @@ int rfn_bn_apply_fwd_ld(const void* x, const float* gamma, const float* beta, vo
                         rfn_stream_t stream) {
   RFN_REQUIRE(x && y && sums, "bn_apply_fwd_ld: null pointer");
   RFN_REQUIRE(ld_y >= C && ld_y % 8 == 0 && ((size_t)y & 15) == 0, "bn_apply_fwd_ld: pitch %ld (>= C = %d, %% 8, 16-byte base)", ld_y, C);
-  if (int rc = bn_check("bn_apply_fwd_ld", T, C, dtype)) return rc;
-  return RFN_BN_DISPATCH(false, true, x, nullptr, sums, nullptr, gamma, beta, y, running_mean, running_var, T, C, eps, momentum,
-                         relu != 0, bn_slope(relu), (hipStream_t)stream, ld_y);
+  if (int rc = bn_check("bn_apply_fwd_ld", T, C)) return rc;
+  return bn_apply_fwd("rfn_bn_apply_fwd_ld", x, gamma, beta, y, ld_y, sums, running_mean, running_var, T, C, eps, momentum, relu, dtype,
+                      stream);
+}
+
+// the backward statistics launch; workspace != null: the deterministic form's partial rows
+static int bn_stats_bwd(const char* who, const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
+                        float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, hipStream_t s) {
+  return dt16(dtype, who, [&](auto dt) {
+    if (workspace == nullptr) {
+      RFN_REFUSE_NONDET(true, "rfn_bn_stats_bwd", "bn_stats_kernel, fp32 atomics (use rfn_bn_stats_bwd_det)");
+      if (int rc = zero_async(bwd_sums, 2 * (size_t)C * sizeof(float), s)) return rc;
+    }
+    return bn_launch<decltype(dt)::value>(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps,
+                                          0.f, relu != 0, bn_slope(relu), s, 0, workspace);
+  });
 }
 
 int rfn_bn_stats_bwd(const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
                      float* bwd_sums, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums, "bn_stats_bwd: null pointer");
-  if (int rc = bn_check("bn_stats_bwd", T, C, dtype)) return rc;
-  RFN_REFUSE_NONDET(true, "rfn_bn_stats_bwd", "bn_stats_kernel, fp32 atomics (use rfn_bn_stats_bwd_det)");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = zero_async(bwd_sums, 2 * (size_t)C * sizeof(float), s)) return rc;
-  return RFN_BN_DISPATCH(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps, 0.f, relu != 0, bn_slope(relu), s);
+  if (int rc = bn_check("bn_stats_bwd", T, C)) return rc;
+  return bn_stats_bwd("rfn_bn_stats_bwd", x, grad_y, fwd_sums, gamma, beta, bwd_sums, nullptr, T, C, eps, relu, dtype, (hipStream_t)stream);
 }
 
 // Deterministic forms of the two statistics passes: every workgroup row stores its 2 C partial sums into `workspace`
@@ -317,10 +320,12 @@ unsigned long rfn_bn_stats_det_workspace_bytes(long T, int C) {
 
 int rfn_bn_stats_fwd_det(const void* x, double* sums, void* workspace, long T, int C, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && sums && workspace, "bn_stats_fwd_det: null pointer");
-  if (int rc = bn_check("bn_stats_fwd_det", T, C, dtype)) return rc;
+  if (int rc = bn_check("bn_stats_fwd_det", T, C)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = RFN_BN_DISPATCH(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C, 0.f,
-                               0.f, 0, 0.f, s, 0, workspace))
+  if (int rc = dt16(dtype, "rfn_bn_stats_fwd_det", [&](auto dt) {
+        return bn_launch<decltype(dt)::value>(false, false, x, nullptr, nullptr, sums, nullptr, nullptr, nullptr, nullptr, nullptr, T, C,
+                                              0.f, 0.f, 0, 0.f, s, 0, workspace);
+      }))
     return rc;
   return ordered_colsum_f64((const double*)workspace, sums, bn_stats_rows(T, C), 2 * C, s);
 }
@@ -328,10 +333,9 @@ int rfn_bn_stats_fwd_det(const void* x, double* sums, void* workspace, long T, i
 int rfn_bn_stats_bwd_det(const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
                          float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums && workspace, "bn_stats_bwd_det: null pointer");
-  if (int rc = bn_check("bn_stats_bwd_det", T, C, dtype)) return rc;
+  if (int rc = bn_check("bn_stats_bwd_det", T, C)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = RFN_BN_DISPATCH(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps,
-                               0.f, relu != 0, bn_slope(relu), s, 0, workspace))
+  if (int rc = bn_stats_bwd("rfn_bn_stats_bwd_det", x, grad_y, fwd_sums, gamma, beta, bwd_sums, workspace, T, C, eps, relu, dtype, s))
     return rc;
   return ordered_colsum_f32((const float*)workspace, bwd_sums, bn_stats_rows(T, C), 2 * C, s);
 }
@@ -339,9 +343,11 @@ int rfn_bn_stats_bwd_det(const void* x, const void* grad_y, const double* fwd_su
 int rfn_bn_apply_bwd(const void* x, const void* grad_y, const double* fwd_sums, const float* bwd_sums, const float* gamma,
                      const float* beta, void* grad_x, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums && grad_x, "bn_apply_bwd: null pointer");
-  if (int rc = bn_check("bn_apply_bwd", T, C, dtype)) return rc;
-  return RFN_BN_DISPATCH(true, true, x, grad_y, fwd_sums, (void*)bwd_sums, gamma, beta, grad_x, nullptr, nullptr, T, C, eps,
-                         0.f, relu != 0, bn_slope(relu), (hipStream_t)stream);
+  if (int rc = bn_check("bn_apply_bwd", T, C)) return rc;
+  return dt16(dtype, "rfn_bn_apply_bwd", [&](auto dt) {
+    return bn_launch<decltype(dt)::value>(true, true, x, grad_y, fwd_sums, (void*)bwd_sums, gamma, beta, grad_x, nullptr, nullptr, T, C,
+                                          eps, 0.f, relu != 0, bn_slope(relu), (hipStream_t)stream);
+  });
 }
 
 // one rank: stats + apply back to back (`sums`: 2 C + 1 doubles)

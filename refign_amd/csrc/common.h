@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/refign_hip.h"
+#include "elem.h"
 
 namespace rfn {
 
@@ -34,60 +35,44 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// fp32 -> bf16 bits, round to nearest even (torch's conversion; NaN stays NaN): gfx950 has the conversion in hardware
-// (v_cvt_pk_bf16_f32, two values per instruction).  The integer formulation (add 0x7fff + lsb, NaN select) is 5-6
-// instructions per element -- it made up a third of the instructions of the 16-bit element-wise kernels.
-__device__ __forceinline__ unsigned bf16_bits(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
-__device__ __forceinline__ unsigned bf16x2_bits(float lo, float hi) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-
-// fp32 -> fp16 bits, round to nearest even (torch's .to(torch.float16): overflow -> inf, NaN stays NaN), and back
-__device__ __forceinline__ unsigned f16_bits(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-__device__ __forceinline__ unsigned f16x2_bits(float lo, float hi) {
-  typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-  const f16x2 v = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float f16_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
-__device__ __forceinline__ float f16_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
-
-// Activation dtype codes of the C ABI: 0 = float32, 1 = bfloat16, 2 = float16.  dt_one / dt_pair call fn with a DT<T> tag
-// per code (dt_pair: the pairs that meet in one call -- equal codes, or one of them fp32; bf16 and fp16 never mix) and return
-// RFN_EINVAL with `what` in the message for anything else.
-template <typename T>
-struct DT {
-  using type = T;
-};
+// Activation dtype codes of the C ABI: 0 = float32, 1 = bfloat16, 2 = float16 (elem.h: ElemOf).  dt_one / dt_pair call fn with
+// an ElemTag<T> per code (dt_pair: the pairs that meet in one call -- equal codes, or one of them fp32; bf16 and fp16 never
+// mix) and return RFN_EINVAL with `what` in the message for anything else.
 template <typename Fn>
 inline int dt_one(int a, const char* what, Fn&& fn) {
   switch (a) {
-    case 0: return fn(DT<float>{});
-    case 1: return fn(DT<__hip_bfloat16>{});
-    case 2: return fn(DT<_Float16>{});
+    case 0: return fn(ElemOf<0>{});
+    case 1: return fn(ElemOf<1>{});
+    case 2: return fn(ElemOf<2>{});
   }
   return fail(RFN_EINVAL, "%s: dtype code must be 0 (f32), 1 (bf16) or 2 (f16) (got %d)", what, a);
 }
 template <typename Fn>
 inline int dt_pair(int a, int b, const char* what, Fn&& fn) {
-  if (a == 0 && b == 0) return fn(DT<float>{}, DT<float>{});
-  if (a == 0 && b == 1) return fn(DT<float>{}, DT<__hip_bfloat16>{});
-  if (a == 1 && b == 0) return fn(DT<__hip_bfloat16>{}, DT<float>{});
-  if (a == 1 && b == 1) return fn(DT<__hip_bfloat16>{}, DT<__hip_bfloat16>{});
-  if (a == 0 && b == 2) return fn(DT<float>{}, DT<_Float16>{});
-  if (a == 2 && b == 0) return fn(DT<_Float16>{}, DT<float>{});
-  if (a == 2 && b == 2) return fn(DT<_Float16>{}, DT<_Float16>{});
+  if (a == 0 && b == 0) return fn(ElemOf<0>{}, ElemOf<0>{});
+  if (a == 0 && b == 1) return fn(ElemOf<0>{}, ElemOf<1>{});
+  if (a == 1 && b == 0) return fn(ElemOf<1>{}, ElemOf<0>{});
+  if (a == 1 && b == 1) return fn(ElemOf<1>{}, ElemOf<1>{});
+  if (a == 0 && b == 2) return fn(ElemOf<0>{}, ElemOf<2>{});
+  if (a == 2 && b == 0) return fn(ElemOf<2>{}, ElemOf<0>{});
+  if (a == 2 && b == 2) return fn(ElemOf<2>{}, ElemOf<2>{});
   return fail(RFN_EINVAL, "%s: dtype codes (%d, %d): each 0 (f32), 1 (bf16) or 2 (f16), bf16 and f16 not mixed", what, a, b);
 }
 
-// The 16-bit matrix-core kernels are templated on the code itself: fn(std::integral_constant<int, 1 or 2>).
+// The entry points that take 16-bit activations only.  dt16: the matrix-core kernels are templated on the code itself,
+// fn(std::integral_constant<int, 1 or 2>); dt16_type: fn(ElemTag<T>) as dt_one, for kernels templated on the storage type.
+inline int dt16_check(int a, const char* what) {      // the check alone, for entry points that keep their own launch code
+  return a == 1 || a == 2 ? RFN_OK : fail(RFN_EINVAL, "%s: dtype %d (1 = bf16, 2 = f16)", what, a);
+}
 template <typename Fn>
 inline int dt16(int a, const char* what, Fn&& fn) {
   if (a == 1) return fn(std::integral_constant<int, 1>{});
   if (a == 2) return fn(std::integral_constant<int, 2>{});
-  return fail(RFN_EINVAL, "%s: dtype %d (1 = bf16, 2 = f16)", what, a);
+  return dt16_check(a, what);
+}
+template <typename Fn>
+inline int dt16_type(int a, const char* what, Fn&& fn) {
+  return dt16(a, what, [&](auto code) { return fn(ElemOf<decltype(code)::value>{}); });
 }
 
 // compile-time loop: f(std::integral_constant<int, I>) for I = B .. N - 1 (register arrays need literal indices)

@@ -28,11 +28,10 @@
 #include <type_traits>
 
 #include "common.h"
-#include "mfma.h"
+#include "elem.h"
 
 namespace rfn {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // Vector I/O of one lane: N channels as a packed Raw; unpack2 -> adjacent-channel fp32 pairs, store <- N fp32 values.
@@ -48,27 +47,11 @@ struct VecIO<float> {
   __device__ static void store(float* p, const float (&v)[4]) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
   }
-  __device__ static float rnd(float v) { return v; }                  // the value a store of v reads back as
+  __device__ static float rnd(float v) { return round_to<float>(v); }   // the value a store of v reads back as
 };
 
-// 16-bit activations: bf16, and fp16 (the reference's `precision: 16` recipe) in the same layout with IEEE half conversions.
-// The two conversions: pair_f32 (one packed word -> two adjacent channels) and pack16 (back).
-template <typename T>
-__device__ __forceinline__ f32x2 pair_f32(unsigned w);
-template <>
-__device__ __forceinline__ f32x2 pair_f32<__hip_bfloat16>(unsigned w) {
-  return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-}
-template <>
-__device__ __forceinline__ f32x2 pair_f32<_Float16>(unsigned w) { return f32x2{f16_lo(w), f16_hi(w)}; }
-
-template <typename T>
-__device__ __forceinline__ unsigned pack16(float lo, float hi);
-template <>
-__device__ __forceinline__ unsigned pack16<__hip_bfloat16>(float lo, float hi) { return bf16x2_bits(lo, hi); }   // common.h: one v_cvt_pk_bf16_f32
-template <>
-__device__ __forceinline__ unsigned pack16<_Float16>(float lo, float hi) { return f16x2_bits(lo, hi); }
-
+// 16-bit activations: bf16, and fp16 (the reference's `precision: 16` recipe) in the same layout with IEEE half conversions
+// (elem.h: widen2, one packed word -> two adjacent channels, and narrow2, back).
 // NCH = 8 channels per lane (16-byte vectors: dwconv3x3_fwd_kernel) or 4 (8-byte vectors: dwconv3x3_roll_kernel, dwconv3x3_bwd_kernel)
 template <typename T, int NCH>
 struct Vec16 {
@@ -76,14 +59,14 @@ struct Vec16 {
   typedef std::conditional_t<NCH == 8, uint4, uint2> Raw;
   __device__ static Raw load_raw(const T* p) { return *reinterpret_cast<const Raw*>(p); }
   __device__ static void unpack2(const Raw& t, f32x2 (&v)[NW]) {      // adjacent channels land in adjacent registers
-    v[0] = pair_f32<T>(t.x);
-    v[1] = pair_f32<T>(t.y);
+    v[0] = widen2<T>(t.x);
+    v[1] = widen2<T>(t.y);
     if constexpr (NCH == 8) {
-      v[2] = pair_f32<T>(t.z);
-      v[3] = pair_f32<T>(t.w);
+      v[2] = widen2<T>(t.z);
+      v[3] = widen2<T>(t.w);
     }
   }
-  __device__ static unsigned pack(float lo, float hi) { return pack16<T>(lo, hi); }
+  __device__ static unsigned pack(float lo, float hi) { return narrow2<T>(lo, hi); }
   __device__ static void store(T* p, const float (&v)[NCH]) {
     Raw t;
     t.x = pack(v[0], v[1]);
@@ -94,10 +77,7 @@ struct Vec16 {
     }
     *reinterpret_cast<Raw*>(p) = t;
   }
-  __device__ static float rnd(float v) {
-    if constexpr (std::is_same<T, _Float16>::value) return (float)(_Float16)v;
-    else return __uint_as_float(bf16_bits(v) << 16);
-  }
+  __device__ static float rnd(float v) { return round_to<T, true>(v); }   // BITS: elem.h
 };
 template <>
 struct VecIO<__hip_bfloat16> : Vec16<__hip_bfloat16, 8> {};
@@ -116,9 +96,7 @@ struct VecIO<f8e4m3> {
     v[2] = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.y, false);
     v[3] = __builtin_amdgcn_cvt_pk_f32_fp8((int)t.y, true);
   }
-  __device__ static void store(f8e4m3* p, const float (&v)[8]) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(quant4(v[0], v[1], v[2], v[3]), quant4(v[4], v[5], v[6], v[7]));
-  }
+  __device__ static void store(f8e4m3* p, const float (&v)[8]) { store8(p, v); }
 };
 
 constexpr int kPX = 4;   // pixels along W per thread
@@ -486,8 +464,8 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
       f32x2 row[NC][V2];
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
-        row[j][0] = pair_f32<T>(raw[j].x);
-        row[j][1] = pair_f32<T>(raw[j].y);
+        row[j][0] = widen2<T>(raw[j].x);
+        row[j][1] = widen2<T>(raw[j].y);
       }
       fetch(raw, q + DEPTH);
 #pragma unroll
@@ -511,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_roll_kernel(const T* __restr
             unsigned o[V2];
 #pragma unroll
             for (int i = 0; i < V2; ++i) {
-              const f32x2 rv = pair_f32<T>(VecIO<T>::pack(aa[p][i].x, aa[p][i].y));
+              const f32x2 rv = widen2<T>(VecIO<T>::pack(aa[p][i].x, aa[p][i].y));
               if constexpr (BNE) {
                 const f32x2 z = __builtin_elementwise_fma(rv, bsc[i], bsh[i]);
                 o[i] = VecIO<T>::pack((bn.relu && z.x <= 0.f) ? 0.f : z.x, (bn.relu && z.y <= 0.f) ? 0.f : z.y);
@@ -905,13 +883,6 @@ static int launch_bwd(const void* x, const void* gy, const float* w, void* gx, f
   return check_launch("dwconv3x3_bwd_weight_reduce_kernel");
 }
 
-// bf16 / fp16 for the entry points that take nothing else (dtype checked to be 1 or 2; dt_one would ask for their fp32
-// kernels, which do not exist)
-template <typename Fn>
-static inline int dt_16(int dtype, Fn&& fn) {
-  return dtype == 1 ? fn(DT<__hip_bfloat16>{}) : fn(DT<_Float16>{});
-}
-
 }  // namespace rfn
 
 using namespace rfn;
@@ -937,11 +908,11 @@ int rfn_dwconv3x3_nhwc_fwd_stats(const void* x, const float* weight, const float
                                  int W, int C, int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && y && sums, "rfn_dwconv3x3_nhwc_fwd_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats: bad size");
-  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_fwd_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_fwd_stats_det)");
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return dt_16(dtype, [&](auto t) {
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats: C %% 8 == 0");
+  return dt16_type(dtype, "rfn_dwconv3x3_nhwc_fwd_stats", [&](auto t) {
+    RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_fwd_stats", "dwconv3x3_fwd_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_fwd_stats_det)");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
     return launch_fwd_stats<typename decltype(t)::type>(x, weight, bias, y, sums, nullptr, B, H, W, C, dilation, st);
   });
 }
@@ -958,8 +929,8 @@ int rfn_dwconv3x3_nhwc_fwd_stats_det(const void* x, const float* weight, const f
                                      int B, int H, int W, int C, int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && y && sums && workspace, "rfn_dwconv3x3_nhwc_fwd_stats_det: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bad size");
-  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  return dt_16(dtype, [&](auto t) {
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_fwd_stats_det: C %% 8 == 0");
+  return dt16_type(dtype, "rfn_dwconv3x3_nhwc_fwd_stats_det", [&](auto t) {
     return launch_fwd_stats<typename decltype(t)::type>(x, weight, bias, y, sums, (double*)workspace, B, H, W, C, dilation,
                                                         (hipStream_t)stream);
   });
@@ -969,8 +940,8 @@ int rfn_dwconv3x3_nhwc_stats_det(const void* x, const float* weight, const float
                                  int W, int C, int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && sums && workspace, "rfn_dwconv3x3_nhwc_stats_det: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats_det: bad size");
-  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats_det: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  return dt_16(dtype, [&](auto t) {
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_stats_det: C %% 8 == 0");
+  return dt16_type(dtype, "rfn_dwconv3x3_nhwc_stats_det", [&](auto t) {
     return launch_roll<typename decltype(t)::type, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation,
                                                              (hipStream_t)stream, BnEpi{}, (double*)workspace);
   });
@@ -984,11 +955,11 @@ int rfn_dwconv3x3_nhwc_stats(const void* x, const float* weight, const float* bi
                              int dilation, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && sums, "rfn_dwconv3x3_nhwc_stats: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_nhwc_stats: bad size");
-  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: bf16 / f16 (dtype 1 / 2), C %% 8 == 0");
-  RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_roll_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
-  return dt_16(dtype, [&](auto t) {
+  RFN_REQUIRE(C % 8 == 0, "rfn_dwconv3x3_nhwc_stats: C %% 8 == 0");
+  return dt16_type(dtype, "rfn_dwconv3x3_nhwc_stats", [&](auto t) {
+    RFN_REFUSE_NONDET(true, "rfn_dwconv3x3_nhwc_stats", "dwconv3x3_roll_kernel<stats>, fp64 atomics (use rfn_dwconv3x3_nhwc_stats_det)");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = zero_async(sums, (2 * (size_t)C + 1) * sizeof(double), st)) return rc;
     return launch_roll<typename decltype(t)::type, 2, false>(x, weight, bias, nullptr, sums, B, H, W, C, dilation, st, BnEpi{}, nullptr);
   });
 }
@@ -998,10 +969,9 @@ int rfn_dwconv3x3_bn_act_nhwc_fwd(const void* x, const float* weight, const floa
                                   int C, int dilation, float eps, float momentum, int relu, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && weight && sums && y, "rfn_dwconv3x3_bn_act_nhwc_fwd: null pointer");
   RFN_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && dilation > 0, "rfn_dwconv3x3_bn_act_nhwc_fwd: bad size");
-  RFN_REQUIRE((dtype == 1 || dtype == 2) && C % 8 == 0 && (relu == 0 || relu == 1),
-              "rfn_dwconv3x3_bn_act_nhwc_fwd: bf16 / f16, C %% 8 == 0, relu 0 / 1");
+  RFN_REQUIRE(C % 8 == 0 && (relu == 0 || relu == 1), "rfn_dwconv3x3_bn_act_nhwc_fwd: C %% 8 == 0, relu 0 / 1");
   BnEpi bn{gamma, beta, running_mean, running_var, eps, momentum, relu};
-  return dt_16(dtype, [&](auto t) {
+  return dt16_type(dtype, "rfn_dwconv3x3_bn_act_nhwc_fwd", [&](auto t) {
     return launch_roll<typename decltype(t)::type, 0, true>(x, weight, bias, y, const_cast<double*>(sums), B, H, W, C, dilation,
                                                             (hipStream_t)stream, bn, nullptr);
   });

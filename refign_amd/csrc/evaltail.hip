@@ -18,6 +18,7 @@
 // That every pixel lies in some box is checked on the HOST from the box list (no device-side assert, no synchronisation).
 #include "bilinear.h"
 #include "common.h"
+#include "elem.h"
 
 namespace rfn {
 
@@ -30,24 +31,12 @@ struct EtBoxes {
   int v[kEtMaxBox * 4];                        // (y1, y2, x1, x2) per box; travels in the kernel arguments
 };
 
-template <int DT> struct EtElem;
-template <> struct EtElem<0> {
-  static __device__ __forceinline__ float ld(const void* p, long i) { return ((const float*)p)[i]; }
-};
-template <> struct EtElem<1> {
-  static __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const __bf16*)p)[i]; }
-};
-template <> struct EtElem<2> {
-  static __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const _Float16*)p)[i]; }
-};
-
 template <int DT, int CMAX>
 __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_kernel(const void* __restrict__ crops, EtBoxes boxes, int nbox,
                                                                    int B, int C, int h, int w, int H, int W, float sy,
                                                                    float sx, const long* __restrict__ target,
                                                                    int ignore_index, unsigned char* __restrict__ labels,
                                                                    unsigned long long* __restrict__ confmat) {
-  using E = EtElem<DT>;
   // a cell's classes side by side, rows of S floats: 16-byte aligned, and S / 4 odd so that neighbouring cells start in other banks
   constexpr int S = ((CMAX + 3) / 4 * 4) + ((CMAX + 3) / 4 % 2 ? 0 : 4);
   __shared__ __attribute__((aligned(16))) float lo[kEtCap];      // [fy][fx][S]
@@ -90,7 +79,7 @@ __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_
         for (int q = tid & 63; q < cells; q += 64) {
           const int fy = q / nfx, fx = q - fy * nfx;
           const long off = base + (long)(fy0 + fy) * w + fx0 + fx;
-          for (int c = tid >> 6; c < C; c += 4) lo[q * S + c] = E::ld(crops, off + c * plane);
+          for (int c = tid >> 6; c < C; c += 4) lo[q * S + c] = ldf<DT>(crops, off + c * plane);
         }
         __syncthreads();
       }
@@ -117,8 +106,8 @@ __global__ __launch_bounds__(256, CMAX <= 19 ? 4 : 3) void slide_argmax_confmat_
           for (int c = 0; c < CMAX; ++c) {
             if (c < C) {
               const long pc = c * plane;
-              acc[c] += hy * (hx * E::ld(crops, o00 + pc) + lx * E::ld(crops, o01 + pc)) +
-                        ly * (hx * E::ld(crops, o10 + pc) + lx * E::ld(crops, o11 + pc));
+              acc[c] += hy * (hx * ldf<DT>(crops, o00 + pc) + lx * ldf<DT>(crops, o01 + pc)) +
+                        ly * (hx * ldf<DT>(crops, o10 + pc) + lx * ldf<DT>(crops, o11 + pc));
             }
           }
         }
@@ -197,7 +186,6 @@ int rfn_slide_argmax_confmat(const void* crop_logits, int dtype, int B, int C, i
   RFN_REQUIRE(crop_logits && boxes, "slide_argmax_confmat: null pointer");
   RFN_REQUIRE(labels || confmat, "slide_argmax_confmat: labels and confmat are both NULL: nothing to compute");
   RFN_REQUIRE(!confmat || target, "slide_argmax_confmat: confmat needs a target");
-  RFN_REQUIRE(dtype >= 0 && dtype <= 2, "slide_argmax_confmat: dtype %d (0 = f32, 1 = bf16, 2 = f16)", dtype);
   RFN_REQUIRE(B > 0 && C > 0 && C <= kEtMaxC && h > 0 && w > 0 && H > 0 && W > 0,
               "slide_argmax_confmat: B=%d C=%d (<= %d) h=%d w=%d H=%d W=%d", B, C, kEtMaxC, h, w, H, W);
   RFN_REQUIRE(nbox > 0 && nbox <= kEtMaxBox, "slide_argmax_confmat: %d boxes (1 ... %d)", nbox, kEtMaxBox);
@@ -219,24 +207,13 @@ int rfn_slide_argmax_confmat(const void* crop_logits, int dtype, int B, int C, i
   const long ntiles = (long)B * cdiv(H, kEtTH) * cdiv(W, kEtTW);
   const dim3 grid((unsigned)(ntiles < kEtMaxGrid ? ntiles : kEtMaxGrid));
   hipStream_t s = (hipStream_t)stream;
-#define RFN_ET(D, CM)                                                                                                     \
-  hipLaunchKernelGGL((slide_argmax_confmat_kernel<D, CM>), grid, dim3(256), 0, s, crop_logits, bx, nbox, B, C, h, w, H, W, \
-                     sy, sx, target, ignore_index, labels, (unsigned long long*)confmat)
-#define RFN_ET_C(D)      \
-  if (C <= 19)           \
-    RFN_ET(D, 19);       \
-  else                   \
-    RFN_ET(D, kEtMaxC)
-  if (dtype == 0) {
-    RFN_ET_C(0);
-  } else if (dtype == 1) {
-    RFN_ET_C(1);
-  } else {
-    RFN_ET_C(2);
-  }
-#undef RFN_ET_C
-#undef RFN_ET
-  return check_launch("slide_argmax_confmat");
+  return dt_one(dtype, "rfn_slide_argmax_confmat", [&](auto t) {
+    constexpr int D = code_of<typename decltype(t)::type>;
+    const auto kernel = C <= 19 ? slide_argmax_confmat_kernel<D, 19> : slide_argmax_confmat_kernel<D, kEtMaxC>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, crop_logits, bx, nbox, B, C, h, w, H, W, sy, sx, target, ignore_index, labels,
+                       (unsigned long long*)confmat);
+    return check_launch("slide_argmax_confmat");
+  });
 }
 
 }  // extern "C"

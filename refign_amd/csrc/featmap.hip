@@ -5,6 +5,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "elem.h"
 
 namespace rfn {
 
@@ -62,17 +63,6 @@ __global__ __launch_bounds__(256) void l2norm_channels_reg_kernel(const float* _
 // sum the squares, and the write-out runs along the pixels (32 consecutive floats per channel; LDS pitch C + 1 keeps
 // both directions conflict-free).
 template <typename T16>
-__device__ __forceinline__ float to_f32(uint16_t raw);
-template <>
-__device__ __forceinline__ float to_f32<__half>(uint16_t raw) {
-  return __half2float(__ushort_as_half(raw));
-}
-template <>
-__device__ __forceinline__ float to_f32<__hip_bfloat16>(uint16_t raw) {
-  return __uint_as_float((uint32_t)raw << 16);
-}
-
-template <typename T16>
 __global__ __launch_bounds__(256) void l2norm_nhwc16_to_nchw_kernel(const uint16_t* __restrict__ x,
                                                                     float* __restrict__ out, int C, int HW) {
   extern __shared__ float tile[];                 // [32][C + 1] + inv[32]
@@ -88,8 +78,9 @@ __global__ __launch_bounds__(256) void l2norm_nhwc16_to_nchw_kernel(const uint16
     const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      tile[px * P + c + 2 * k] = to_f32<T16>((uint16_t)(w[k] & 0xffffu));
-      tile[px * P + c + 2 * k + 1] = to_f32<T16>((uint16_t)(w[k] >> 16));
+      const f32x2 f = widen2<T16>(w[k]);
+      tile[px * P + c + 2 * k] = f.x;
+      tile[px * P + c + 2 * k + 1] = f.y;
     }
   }
   __syncthreads();
@@ -168,10 +159,13 @@ __global__ __launch_bounds__(256) void retile_copy_kernel(const uint4* __restric
 // 2 x 2 / stride 2 max-pool of a channels-last 16-bit map (the pools of the VGG-16 pyramid, models/backbones/vgg.py:33-60:
 // nn.MaxPool2d(2, 2), floor mode): a thread owns 8 channels of 2 adjacent output pixels -- 8 independent 16-byte loads in
 // flight (ATen's channels-last pool: 0.54 ms for 4 x 1080 x 1920 x 64 = 2.4 TB/s).  Max of representable values: exact.
-template <typename S>
-__global__ __launch_bounds__(256) void maxpool2x2_nhwc16_kernel(const S* __restrict__ x, S* __restrict__ y, int H, int W,
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2x2_nhwc16_kernel(const T* __restrict__ x_, T* __restrict__ y_, int H, int W,
                                                                 int OH, int OW, int CV, long total) {
+  using S = native_t<T>;
   typedef S V8 __attribute__((ext_vector_type(8)));
+  const S* __restrict__ x = reinterpret_cast<const S*>(x_);
+  S* __restrict__ y = reinterpret_cast<S*>(y_);
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;                                // total = B * OH * ceil(OW / 2) * CV
   const int OWP = (OW + 1) / 2;
@@ -239,23 +233,17 @@ int rfn_l2norm_channels_nhwc16_f32(const void* x, float* out, int B, int C, int 
   RFN_REQUIRE(x && out, "rfn_l2norm_channels_nhwc16_f32: null pointer");
   RFN_REQUIRE(B > 0 && B <= 65535 && C > 0 && C % 8 == 0 && C <= 2048 && HW > 0,
               "rfn_l2norm_channels_nhwc16_f32: B=%d C=%d (multiple of 8, <= 2048) HW=%d", B, C, HW);
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "rfn_l2norm_channels_nhwc16_f32: dtype %d (1 = bf16, 2 = f16)", dtype);
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = ((size_t)32 * (C + 1) + 32) * sizeof(float);
   dim3 grid(cdiv(HW, 32), B);
-  if (dtype == 2) {
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2norm_nhwc16_to_nchw_kernel<__half>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  return dt16_type(dtype, "rfn_l2norm_channels_nhwc16_f32", [&](auto t) {
+    const auto kernel = l2norm_nhwc16_to_nchw_kernel<typename decltype(t)::type>;
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return fail(RFN_ELAUNCH, "l2norm_nhwc16_to_nchw_kernel: %zu bytes of LDS", lds);
-    hipLaunchKernelGGL(l2norm_nhwc16_to_nchw_kernel<__half>, grid, dim3(256), lds, st, (const uint16_t*)x, out, C, HW);
-  } else {
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)l2norm_nhwc16_to_nchw_kernel<__hip_bfloat16>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return fail(RFN_ELAUNCH, "l2norm_nhwc16_to_nchw_kernel: %zu bytes of LDS", lds);
-    hipLaunchKernelGGL(l2norm_nhwc16_to_nchw_kernel<__hip_bfloat16>, grid, dim3(256), lds, st, (const uint16_t*)x, out, C,
-                       HW);
-  }
-  return check_launch("l2norm_nhwc16_to_nchw_kernel");
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, (const uint16_t*)x, out, C, HW);
+    return check_launch("l2norm_nhwc16_to_nchw_kernel");
+  });
 }
 
 // y (B, H / 2, W / 2, C) = 2 x 2 / stride 2 max-pool (floor mode) of the channels-last 16-bit x (B, H, W, C), C % 8 == 0; dtype 1
@@ -263,18 +251,16 @@ int rfn_l2norm_channels_nhwc16_f32(const void* x, float* out, int B, int C, int 
 int rfn_maxpool2x2_nhwc16(const void* x, void* y, int B, int H, int W, int C, int dtype, rfn_stream_t stream) {
   RFN_REQUIRE(x && y, "maxpool2x2_nhwc16: null pointer");
   RFN_REQUIRE(B > 0 && H >= 2 && W >= 2 && C > 0 && C % 8 == 0, "maxpool2x2_nhwc16: B=%d H=%d W=%d C=%d (C %% 8)", B, H, W, C);
-  RFN_REQUIRE(dtype == 1 || dtype == 2, "maxpool2x2_nhwc16: dtype %d (1 = bf16, 2 = f16)", dtype);
   const int OH = H / 2, OW = W / 2, CV = C / 8;
   const long total = (long)B * OH * ((OW + 1) / 2) * CV;
   RFN_REQUIRE(total / 256 < 0x7fffffffL, "maxpool2x2_nhwc16: too large");
   const int grid = cdiv(total, 256);
-  if (dtype == 1)
-    hipLaunchKernelGGL(maxpool2x2_nhwc16_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x,
-                       (__bf16*)y, H, W, OH, OW, CV, total);
-  else
-    hipLaunchKernelGGL(maxpool2x2_nhwc16_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const _Float16*)x,
-                       (_Float16*)y, H, W, OH, OW, CV, total);
-  return check_launch("maxpool2x2_nhwc16");
+  return dt16_type(dtype, "rfn_maxpool2x2_nhwc16", [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(maxpool2x2_nhwc16_kernel<T>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, H, W, OH, OW,
+                       CV, total);
+    return check_launch("maxpool2x2_nhwc16");
+  });
 }
 
 int rfn_retile_copy(const void* src, void* dst, int B, int h, int w, int k, int units16, int src_stride16, int backward,

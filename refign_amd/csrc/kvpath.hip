@@ -28,6 +28,7 @@
 // for the five launches.  Stages 1-2 are within 2 x of one pass over the map; stages 3-4 are bound by the weight stream from L2 (214
 // workgroups x 1.0-1.2 MB), not by the map.  In the step: profiles/kvpath_ab.txt.
 #include "common.h"
+#include "elem.h"
 #include "mfma.h"
 
 namespace rfn {
@@ -49,18 +50,6 @@ template <int C, int R, int NB> struct KvGeom {
   static_assert(C % 64 == 0 && (R == 1 || (R * C) % KSTEP == 0), "a K-step never straddles a run of the gather");
   static_assert(LDS <= 160 * 1024, "LDS");
 };
-
-template <int DT> __device__ __forceinline__ void kv_ld8(const uint16_t* p, float (&v)[8]) {
-  const u32x4 t = *(const u32x4*)p;
-  float a[4], b[4];
-  unpack4<DT>(u32x2{t[0], t[1]}, a);
-  unpack4<DT>(u32x2{t[2], t[3]}, b);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[i] = a[i];
-    v[4 + i] = b[i];
-  }
-}
 
 template <int DT, int C, int R, int NB>
 __global__ __launch_bounds__(256) void kvpath_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Wsr,
@@ -252,7 +241,7 @@ __global__ __launch_bounds__(256) void kvpath_kernel(const uint16_t* __restrict_
       for (int it = 0; it < kKvRows / (4 * RPW); ++it) {
         uint16_t* p = yt + ((it * 4 + wave) * RPW + grp) * YP + (act ? c : 0);
         float v[8];
-        if (act) kv_ld8<DT>(p, v);
+        if (act) load8<DT>(p, v);
         else {
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = 0.0f;

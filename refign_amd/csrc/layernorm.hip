@@ -15,36 +15,12 @@
 #include <hip/hip_bf16.h>
 
 #include "common.h"
-#include "mfma.h"
+#include "elem.h"
 
 namespace rfn {
 
 constexpr int kLnMaxPerLane = 16;   // C <= 1024
 constexpr int kLnMaxBlocks = 256;   // workspace rows for dgamma/dbeta partials (one workgroup per CU)
-
-template <typename T>
-__device__ __forceinline__ float ld(const T* p);
-template <>
-__device__ __forceinline__ float ld<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ld<__hip_bfloat16>(const __hip_bfloat16* p) {
-  return __uint_as_float(((unsigned)*reinterpret_cast<const unsigned short*>(p)) << 16);
-}
-template <>
-__device__ __forceinline__ float ld<_Float16>(const _Float16* p) { return (float)*p; }
-template <typename T>
-__device__ __forceinline__ void st(T* p, float v);
-template <>
-__device__ __forceinline__ void st<_Float16>(_Float16* p, float v) { *p = (_Float16)v; }
-template <>
-__device__ __forceinline__ void st<float>(float* p, float v) { *p = v; }
-template <>
-__device__ __forceinline__ void st<__hip_bfloat16>(__hip_bfloat16* p, float v) {
-  *reinterpret_cast<unsigned short*>(p) = (unsigned short)bf16_bits(v);
-}
-
-template <>
-__device__ __forceinline__ void st<f8e4m3>(f8e4m3* p, float v) { p->v = (unsigned char)(quant4(v, 0.f, 0.f, 0.f) & 0xffu); }
 
 template <typename TI, typename TO, int NPL>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const TI* __restrict__ x, const float* __restrict__ gamma,
@@ -67,7 +43,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const TI* __restrict
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
       const int c = lane + 64 * i;
-      v[i] = c < C ? ld<TI>(xr + c) : 0.0f;
+      v[i] = c < C ? ldf<TI>(xr + c) : 0.0f;
       s += v[i];
     }
     const float mu = wave_sum(s) * invC;
@@ -83,7 +59,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const TI* __restrict
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
       const int c = lane + 64 * i;
-      if (c < C) st<TO>(yr + c, fmaf((v[i] - mu) * rs, g[i], b[i]));
+      if (c < C) stf<TO>(yr + c, fmaf((v[i] - mu) * rs, g[i], b[i]));
     }
     if (lane == 0) {
       mean[r] = mu;
@@ -117,8 +93,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict
     for (int i = 0; i < NPL; ++i) {
       const int c = lane + 64 * i;
       const bool ok = c < C;
-      const float xv = ok ? ld<TX>(x + r * C + c) : 0.0f;
-      const float gv = ok ? ld<TG>(gy + r * C + c) : 0.0f;
+      const float xv = ok ? ldf<TX>(x + r * C + c) : 0.0f;
+      const float gv = ok ? ldf<TG>(gy + r * C + c) : 0.0f;
       xh[i] = ok ? (xv - mu) * rs : 0.0f;
       gg[i] = gv * gm[i];
       s1 += gg[i];
@@ -131,7 +107,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
       const int c = lane + 64 * i;
-      if (c < C) st<TX>(dx + r * C + c, rs * (gg[i] - s1 - xh[i] * s2));
+      if (c < C) stf<TX>(dx + r * C + c, rs * (gg[i] - s1 - xh[i] * s2));
     }
   }
   // combine the 4 waves' partials, one workspace row per workgroup: ws[block][2][C]
@@ -155,58 +131,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict
 // LPR = 8/16/32/64 lanes, so narrow rows share a wave (C = 64: 8 rows per wave) and reductions are shuffles inside the
 // LPR-lane group.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void ld8(const T* p, float (&v)[8]);
-template <>
-__device__ __forceinline__ void ld8<float>(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void ld8<__hip_bfloat16>(const __hip_bfloat16* p, float (&v)[8]) {
-  const uint4 t = *reinterpret_cast<const uint4*>(p);
-  const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-template <>
-__device__ __forceinline__ void ld8<_Float16>(const _Float16* p, float (&v)[8]) {
-  const uint4 t = *reinterpret_cast<const uint4*>(p);
-  const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = f16_lo(w[i]);
-    v[2 * i + 1] = f16_hi(w[i]);
-  }
-}
-template <typename T>
-__device__ __forceinline__ void st8(T* p, const float (&v)[8]);
-template <>
-__device__ __forceinline__ void st8<_Float16>(_Float16* p, const float (&v)[8]) {
-  *reinterpret_cast<uint4*>(p) = make_uint4(f16x2_bits(v[0], v[1]), f16x2_bits(v[2], v[3]), f16x2_bits(v[4], v[5]),
-                                            f16x2_bits(v[6], v[7]));
-}
-template <>
-__device__ __forceinline__ void st8<float>(float* p, const float (&v)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
-}
-template <>
-__device__ __forceinline__ void st8<__hip_bfloat16>(__hip_bfloat16* p, const float (&v)[8]) {
-  uint4 t;
-  t.x = bf16x2_bits(v[0], v[1]);
-  t.y = bf16x2_bits(v[2], v[3]);
-  t.z = bf16x2_bits(v[4], v[5]);
-  t.w = bf16x2_bits(v[6], v[7]);
-  *reinterpret_cast<uint4*>(p) = t;
-}
-template <>
-__device__ __forceinline__ void st8<f8e4m3>(f8e4m3* p, const float (&v)[8]) {       // K5: e4m3 bytes, saturating RNE
-  *reinterpret_cast<uint2*>(p) = make_uint2(quant4(v[0], v[1], v[2], v[3]), quant4(v[4], v[5], v[6], v[7]));
-}
 template <int LPR>
 __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
@@ -229,8 +153,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const TI* __rest
   for (int j = 0; j < NV; ++j) {
     const int c = (sub + LPR * j) * 8;
     act[j] = c < C;
-    ld8<float>(gamma + (act[j] ? c : 0), g[j]);      // two 16-byte loads each (c is a multiple of 8)
-    ld8<float>(beta + (act[j] ? c : 0), b[j]);
+    load8<float>(gamma + (act[j] ? c : 0), g[j]);      // two 16-byte loads each (c is a multiple of 8)
+    load8<float>(beta + (act[j] ? c : 0), b[j]);
   }
   const float invC = 1.0f / (float)C;
   for (long r0 = ((long)blockIdx.x * 4 + wave) * RPW; r0 < rows; r0 += (long)gridDim.x * 4 * RPW) {
@@ -240,7 +164,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const TI* __rest
     float s = 0.0f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-      if (valid && act[j]) ld8<TI>(x + r * C + (sub + LPR * j) * 8, v[j]);
+      if (valid && act[j]) load8<TI>(x + r * C + (sub + LPR * j) * 8, v[j]);
       else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[j][i] = 0.0f;
@@ -264,7 +188,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const TI* __rest
         float o[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = fmaf((v[j][i] - mu) * rs, g[j][i], b[j][i]) * oscale;
-        st8<TO>(y + r * C + (sub + LPR * j) * 8, o);
+        store8<TO>(y + r * C + (sub + LPR * j) * 8, o);
       }
     if (valid && sub == 0 && mean != nullptr) {
       mean[r] = mu;
@@ -294,7 +218,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const TX* __rest
   for (int j = 0; j < NV; ++j) {
     const int c = (sub + LPR * j) * 8;
     act[j] = c < C;
-    ld8<float>(gamma + (act[j] ? c : 0), gm[j]);
+    load8<float>(gamma + (act[j] ? c : 0), gm[j]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       dg[j][i] = 0.0f;
@@ -312,17 +236,17 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const TX* __rest
     for (int j = 0; j < NV; ++j) {
       float xv[8], gv[8];
       if (valid && act[j]) {
-        ld8<TX>(x + r * C + (sub + LPR * j) * 8, xv);
-        ld8<TG>(gy + r * C + (sub + LPR * j) * 8, gv);
+        load8<TX>(x + r * C + (sub + LPR * j) * 8, xv);
+        load8<TG>(gy + r * C + (sub + LPR * j) * 8, gv);
         if (gy2 != nullptr) {
           float g2[8];
-          ld8<TG>(gy2 + r * C + (sub + LPR * j) * 8, g2);
+          load8<TG>(gy2 + r * C + (sub + LPR * j) * 8, g2);
 #pragma unroll
           for (int i = 0; i < 8; ++i) gv[i] += g2[i];
         }
         // the residual gradient is requested WITH the row, not after the two row reductions (a second exposed load latency
         // per row: the launch is a chain of <= 8 row iterations per wave)
-        if (add != nullptr) ld8<TX>(add + r * C + (sub + LPR * j) * 8, av[j]);
+        if (add != nullptr) load8<TX>(add + r * C + (sub + LPR * j) * 8, av[j]);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { xv[i] = mu; gv[i] = 0.0f; }
@@ -349,7 +273,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const TX* __rest
 #pragma unroll
           for (int i = 0; i < 8; ++i) o[i] += av[j][i];
         }
-        st8<TX>(dx + r * C + (sub + LPR * j) * 8, o);
+        store8<TX>(dx + r * C + (sub + LPR * j) * 8, o);
       }
   }
   // the RPW row groups of a wave hold partials for the same channels: fold them, then the 4 waves through LDS

@@ -20,7 +20,7 @@
 
 #include "bilinear.h"
 #include "common.h"
-#include "mfma.h"
+#include "elem.h"
 
 namespace rfn {
 
@@ -28,23 +28,6 @@ constexpr int kLossTH = 16, kLossTW = 16, kLossPX = kLossTH * kLossTW;     // la
 constexpr int kLossFY = kLossTH / 2 + 2, kLossFX = kLossTW / 2 + 2;         // footprint bound at scale 2
 constexpr int kLossSlots = 64;                                              // partial loss sums
 constexpr int kLossMaxC = 19;                                               // classes (Cityscapes); LDS is sized for it
-
-template <int DT> struct LossElem;
-template <> struct LossElem<0> {
-  using T = float;
-  static __device__ __forceinline__ float ld(const void* p, long i) { return ((const float*)p)[i]; }
-  static __device__ __forceinline__ float round(float v) { return v; }
-};
-template <> struct LossElem<1> {
-  using T = __bf16;
-  static __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const __bf16*)p)[i]; }
-  static __device__ __forceinline__ float round(float v) { return (float)(__bf16)v; }
-};
-template <> struct LossElem<2> {
-  using T = _Float16;
-  static __device__ __forceinline__ float ld(const void* p, long i) { return (float)((const _Float16*)p)[i]; }
-  static __device__ __forceinline__ float round(float v) { return (float)(_Float16)v; }
-};
 
 // FULLC: C == kLossMaxC, no per-class guards (with a run-time class count every class of every loop is a branch)
 template <int DT, bool FULLC>
@@ -54,7 +37,6 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
                                                           float sy, float sx, int ignore_index, int round16,
                                                           float* __restrict__ tile_part = nullptr,
                                                           double* __restrict__ loss_part = nullptr) {
-  using E = LossElem<DT>;
   // the footprint logits (steps 1-2) and the x-reduced gradient (step 3) share their LDS
   __shared__ float tmp[kLossMaxC * kLossTH * kLossFX];         // [c][ty][fx]
   float* const lo = tmp;                                       // [c][fy][fx], dead before step 3a writes tmp
@@ -89,7 +71,7 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
   const char* lg = (const char*)logits;
   for (int i = tid; i < C * nfy * nfx; i += 256) {
     const int c = i / (nfy * nfx), r = i - c * nfy * nfx, fy = r / nfx, fx = r - fy * nfx;
-    lo[(c * kLossFY + fy) * kLossFX + fx] = E::ld(lg, ((long)b * C + c) * plane + (long)(fy0 + fy) * w + fx0 + fx);
+    lo[(c * kLossFY + fy) * kLossFX + fx] = ldf<DT>(lg, ((long)b * C + c) * plane + (long)(fy0 + fy) * w + fx0 + fx);
   }
   __syncthreads();
   // ---- 2. per pixel
@@ -107,7 +89,7 @@ __global__ __launch_bounds__(256) void upsample_ce_kernel(const void* __restrict
       if (FULLC || c < C) {
         const float* p = lo + c * kLossFY * kLossFX;
         float v = hy * (hx * p[a0 + b0] + lx * p[a0 + b1]) + ly * (hx * p[a1 + b0] + lx * p[a1 + b1]);
-        if (round16) v = E::round(v);
+        if (round16) v = round_to<DT>(v);
         z[c] = v;
         m = fmaxf(m, v);
       }
@@ -247,36 +229,30 @@ static int upsample_ce_impl(void* workspace, const void* logits, const long* tar
   RFN_REQUIRE(logits && target && grad_lo && loss_sum, "upsample_ce: null pointer");
   RFN_REQUIRE(B > 0 && C > 0 && C <= kLossMaxC && h > 0 && w > 0, "upsample_ce: B=%d C=%d (<= %d) h=%d w=%d", B, C, kLossMaxC, h, w);
   RFN_REQUIRE(H >= 2 * h && W >= 2 * w, "upsample_ce: %dx%d -> %dx%d (scale factors >= 2 only)", h, w, H, W);
-  RFN_REQUIRE(dtype >= 0 && dtype <= 2, "upsample_ce: dtype %d (0 = f32, 1 = bf16, 2 = f16)", dtype);
-  hipStream_t s = (hipStream_t)stream;
   const bool det = workspace != nullptr;
-  if (!det)
-    if (int rc = zero_async(grad_lo, (size_t)B * C * h * w * sizeof(float), s)) return rc;
-  if (int rc = zero_async(loss_sum, kLossSlots * sizeof(double), s)) return rc;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;      // ATen: area_pixel_compute_scale with size=
-  dim3 grid(cdiv(W, kLossTW), cdiv(H, kLossTH), B);
-  // deterministic form: workspace = [tiles doubles: loss][tiles x C x kLossFY x kLossFX floats: footprint gradients]
-  const long tiles = (long)grid.x * grid.y * grid.z;
-  double* loss_part = det ? (double*)workspace : nullptr;
-  float* tile_part = det ? (float*)((char*)workspace + ce_loss_part_bytes(tiles)) : nullptr;
-#define RFN_UCE(D)                                                                                                     \
-  if (C == kLossMaxC)                                                                                                  \
-    hipLaunchKernelGGL((upsample_ce_kernel<D, true>), grid, dim3(256), 0, s, logits, target, weight, grad_lo, loss_sum, \
-                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0, tile_part, loss_part);                   \
-  else                                                                                                                  \
-    hipLaunchKernelGGL((upsample_ce_kernel<D, false>), grid, dim3(256), 0, s, logits, target, weight, grad_lo, loss_sum, \
-                       C, h, w, H, W, sy, sx, ignore_index, round16 && D != 0, tile_part, loss_part)
-  if (dtype == 0) RFN_UCE(0);
-  else if (dtype == 1) RFN_UCE(1);
-  else RFN_UCE(2);
-#undef RFN_UCE
-  if (int rc = check_launch("upsample_ce")) return rc;
-  if (!det) return RFN_OK;
-  const long total = (long)B * C * h * w;
-  hipLaunchKernelGGL(upsample_ce_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, (const float*)tile_part, grad_lo, total, C,
-                     h, w, H, W, sy, sx, (int)grid.x, (int)grid.y);
-  if (int rc = check_launch("upsample_ce_gather_kernel")) return rc;
-  return ordered_colsum_f64(loss_part, loss_sum, tiles, 1, s);          // slot 0 <- every tile's loss in tile order
+  return dt_one(dtype, det ? "rfn_upsample_ce_det" : "rfn_upsample_ce", [&](auto t) {
+    constexpr int D = code_of<typename decltype(t)::type>;
+    hipStream_t s = (hipStream_t)stream;
+    if (!det)
+      if (int rc = zero_async(grad_lo, (size_t)B * C * h * w * sizeof(float), s)) return rc;
+    if (int rc = zero_async(loss_sum, kLossSlots * sizeof(double), s)) return rc;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;      // ATen: area_pixel_compute_scale with size=
+    dim3 grid(cdiv(W, kLossTW), cdiv(H, kLossTH), B);
+    // deterministic form: workspace = [tiles doubles: loss][tiles x C x kLossFY x kLossFX floats: footprint gradients]
+    const long tiles = (long)grid.x * grid.y * grid.z;
+    double* loss_part = det ? (double*)workspace : nullptr;
+    float* tile_part = det ? (float*)((char*)workspace + ce_loss_part_bytes(tiles)) : nullptr;
+    const auto kernel = C == kLossMaxC ? upsample_ce_kernel<D, true> : upsample_ce_kernel<D, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, logits, target, weight, grad_lo, loss_sum, C, h, w, H, W, sy, sx, ignore_index,
+                       round16 && D != 0, tile_part, loss_part);
+    if (int rc = check_launch("upsample_ce")) return rc;
+    if (!det) return (int)RFN_OK;
+    const long total = (long)B * C * h * w;
+    hipLaunchKernelGGL(upsample_ce_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, (const float*)tile_part, grad_lo, total, C,
+                       h, w, H, W, sy, sx, (int)grid.x, (int)grid.y);
+    if (int rc = check_launch("upsample_ce_gather_kernel")) return rc;
+    return ordered_colsum_f64(loss_part, loss_sum, tiles, 1, s);          // slot 0 <- every tile's loss in tile order
+  });
 }
 
 int rfn_upsample_ce(const void* logits, const long* target, const float* weight, float* grad_lo, double* loss_sum, int B,

@@ -26,6 +26,7 @@
 // fc2 (+ residual) stays the second-generation GEMM.  Numerics: the same roundings as the three-kernel path (bf16 hidden map, fp32
 // stencil, bf16 activation); only the fp32 summation order of the stencil differs.
 #include "common.h"
+#include "elem.h"
 #include "mfma.h"
 
 namespace rfn {
@@ -43,7 +44,7 @@ constexpr int kFfnHBytes = kFfnTY * kFfnTX * kFfnHPitch * 2;        // 69 632
 constexpr int kFfnLds = kFfnHBytes > kFfnStage ? kFfnHBytes : kFfnStage;   // the hidden tile lies over the operand stage
 constexpr int kFfnStrip = 6;                           // interior outputs per stencil strip (30 = 5 strips per row)
 static_assert(kFfnIX % kFfnStrip == 0, "strips tile the interior row");
-typedef float f32p __attribute__((ext_vector_type(2)));
+typedef f32x2 f32p;
 
 // exact-erf GELU on two adjacent channels in packed fp32 math.  erfc(z) = 2^q(z) with q a degree-7 polynomial fitted to log2(erfc)
 // on [0, 3.3] (relative error of the GELU 7e-5 where |gelu| > 1e-3, absolute 1e-5 beyond: three orders below a bf16 step) -- ONE
@@ -70,12 +71,6 @@ struct FfnRows {
 };
 
 // DT: 1 = bf16, 2 = fp16 operands, hidden tile and output (mfma.h Elem<DT>: the 32x32x16 bf16 / f16 MFMA, same cycles on gfx950)
-template <int DT>
-__device__ __forceinline__ f32p widen2(unsigned w) {
-  if constexpr (DT == 2) return f32p{f16_lo(w), f16_hi(w)};
-  else return f32p{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-}
-
 template <int DT>
 __global__ __launch_bounds__(256, 2) void ffn_fc1_dw_gelu_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ W1,
                                                               const uint16_t* __restrict__ b1, const float* __restrict__ wdw,

@@ -17,37 +17,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "elem.h"
 
 namespace rfn {
-
-template <typename T>
-__device__ __forceinline__ void load8(const T* p, float (&v)[8]);
-template <>
-__device__ __forceinline__ void load8<float>(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <>
-__device__ __forceinline__ void load8<__hip_bfloat16>(const __hip_bfloat16* p, float (&v)[8]) {
-  const uint4 t = *reinterpret_cast<const uint4*>(p);
-  const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-
-template <>
-__device__ __forceinline__ void load8<_Float16>(const _Float16* p, float (&v)[8]) {
-  const uint4 t = *reinterpret_cast<const uint4*>(p);
-  const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = f16_lo(w[i]);
-    v[2 * i + 1] = f16_hi(w[i]);
-  }
-}
 
 constexpr int kMaxSumStripes = 512;
 constexpr int kFlatMaxS = 64;
@@ -271,16 +243,10 @@ struct CastChunk {
   long n;
 };
 
-__device__ __forceinline__ unsigned f32_to_bf16_bits(float f) { return bf16_bits(f); }   // common.h
-
 // F16: fp16 copies instead (the fp16 recipe, Trainer(precision=16)): bit-equal to tensor.to(torch.float16)
-__device__ __forceinline__ unsigned f32_to_16_bits(float f, bool f16) { return f16 ? f16_bits(f) : bf16_bits(f); }
-__device__ __forceinline__ unsigned f32x2_to_16_bits(float lo, float hi, bool f16) {
-  return f16 ? f16x2_bits(lo, hi) : bf16x2_bits(lo, hi);
-}
-
 template <bool F16>
 __global__ __launch_bounds__(256) void multi_cast_f32_16_kernel(const CastChunk* __restrict__ table) {
+  using T16 = elem_t<F16 ? 2 : 1>;
   const CastChunk c = table[blockIdx.x];
   const bool aligned = (((size_t)c.src & 15) == 0) && (((size_t)c.dst & 7) == 0);
   long i = (long)threadIdx.x * 4;
@@ -288,14 +254,14 @@ __global__ __launch_bounds__(256) void multi_cast_f32_16_kernel(const CastChunk*
     for (; i + 3 < c.n; i += 256 * 4) {
       const float4 v = *reinterpret_cast<const float4*>(c.src + i);
       uint2 o;
-      o.x = f32x2_to_16_bits(v.x, v.y, F16);
-      o.y = f32x2_to_16_bits(v.z, v.w, F16);
+      o.x = narrow2<T16>(v.x, v.y);
+      o.y = narrow2<T16>(v.z, v.w);
       *reinterpret_cast<uint2*>(c.dst + i) = o;
     }
   }
   // tail (and unaligned tensors): scalar
   for (long j = aligned ? (c.n & ~3L) + threadIdx.x : threadIdx.x; j < c.n; j += 256)
-    c.dst[j] = (unsigned short)f32_to_16_bits(c.src[j], F16);
+    c.dst[j] = (unsigned short)bits16<T16>(c.src[j]);
 }
 
 // Layout-changing copies of a parameter set in one launch: dst (contiguous, up to 4-D, fp32 / bf16 / f16) <- a strided fp32 view
@@ -358,7 +324,7 @@ __global__ __launch_bounds__(256) void multi_ema_kernel(const EmaChunk* __restri
   for (long j = aligned ? (c.n & ~3L) + threadIdx.x : threadIdx.x; j < c.n; j += 256) {
     const float e = c.ema[j] * m + c.live[j] * one_minus_m;
     c.ema[j] = e;
-    if (c.dst16 != nullptr) c.dst16[j] = (unsigned short)f32_to_bf16_bits(e);
+    if (c.dst16 != nullptr) c.dst16[j] = (unsigned short)bf16_bits(e);
   }
 }
 
@@ -377,6 +343,7 @@ template <bool F16>
 __global__ __launch_bounds__(256) void multi_transpose_cast_kernel(const TransposeTile* __restrict__ table) {
   // 64 x 64 tile: rows of 64 floats read as 16-byte pieces (256 B per row), columns written as 16-byte pieces of 8 bf16 (128 B per
   // destination row).  (Round 5; 32 x 32 tiles with 2-byte stores: 0.94 ms for MiT-B5's 82 M weights, 64-byte write segments.)
+  using T16 = elem_t<F16 ? 2 : 1>;
   constexpr int T = kTransposeTile;
   __shared__ float tile[T][T + 1];
   const TransposeTile t = table[blockIdx.x];
@@ -407,14 +374,14 @@ __global__ __launch_bounds__(256) void multi_transpose_cast_kernel(const Transpo
     if (k >= t.K || n >= t.N) continue;
     if (vec_out && n + 7 < t.N) {
       uint4 o;
-      o.x = f32x2_to_16_bits(tile[8 * c8][r], tile[8 * c8 + 1][r], F16);
-      o.y = f32x2_to_16_bits(tile[8 * c8 + 2][r], tile[8 * c8 + 3][r], F16);
-      o.z = f32x2_to_16_bits(tile[8 * c8 + 4][r], tile[8 * c8 + 5][r], F16);
-      o.w = f32x2_to_16_bits(tile[8 * c8 + 6][r], tile[8 * c8 + 7][r], F16);
+      o.x = narrow2<T16>(tile[8 * c8][r], tile[8 * c8 + 1][r]);
+      o.y = narrow2<T16>(tile[8 * c8 + 2][r], tile[8 * c8 + 3][r]);
+      o.z = narrow2<T16>(tile[8 * c8 + 4][r], tile[8 * c8 + 5][r]);
+      o.w = narrow2<T16>(tile[8 * c8 + 6][r], tile[8 * c8 + 7][r]);
       *reinterpret_cast<uint4*>(t.dst + (size_t)k * t.N + n) = o;
     } else {
       for (int e = 0; e < 8 && n + e < t.N; ++e)
-        t.dst[(size_t)k * t.N + n + e] = (unsigned short)f32_to_16_bits(tile[8 * c8 + e][r], F16);
+        t.dst[(size_t)k * t.N + n + e] = (unsigned short)bits16<T16>(tile[8 * c8 + e][r]);
     }
   }
 }

@@ -17,6 +17,7 @@
 
 #include "bilinear.h"
 #include "common.h"
+#include "elem.h"
 
 namespace rfn {
 
@@ -26,38 +27,10 @@ struct UpcatArgs {
   int nlev;
 };
 
-__device__ __forceinline__ void unpack8(const uint4& t, float (&v)[8]) {
-  const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-
 // one thread = one 8-channel vector of kUpPX consecutive output pixels of a row (bf16: 16 bytes per pixel; fp32: 32 bytes): the
 // 4 x kUpPX source loads are issued together -- with one pixel per thread the kernel was a chain of dependent latencies
 // (index arithmetic -> 4 loads -> blend -> store) at 2.6 TB/s of a 6.7 TB/s write rate
 constexpr int kUpPX = 4;
-
-// 8 channels of a 16-bit type (bf16 or fp16) as one 16-byte vector <-> 8 floats
-template <typename T>
-__device__ __forceinline__ void widen8(const uint4& t, float (&f)[8]) {
-  if constexpr (std::is_same<T, _Float16>::value) {
-    const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) f[2 * i] = f16_lo(w[i]), f[2 * i + 1] = f16_hi(w[i]);
-  } else {
-    unpack8(t, f);
-  }
-}
-template <typename T>
-__device__ __forceinline__ uint4 narrow8(const float (&r)[8]) {
-  if constexpr (std::is_same<T, _Float16>::value)
-    return make_uint4(f16x2_bits(r[0], r[1]), f16x2_bits(r[2], r[3]), f16x2_bits(r[4], r[5]), f16x2_bits(r[6], r[7]));
-  else
-    return make_uint4(bf16x2_bits(r[0], r[1]), bf16x2_bits(r[2], r[3]), bf16x2_bits(r[4], r[5]), bf16x2_bits(r[6], r[7]));
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void upcat_nhwc_kernel(UpcatArgs a, T* __restrict__ out, int H, int W, long total) {

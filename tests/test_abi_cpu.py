@@ -128,3 +128,55 @@ def test_abi_version_comes_from_the_header():
     from refign_amd import _lib
     assert _lib.ABI_VERSION == 5
     assert _lib.ABI_VERSION == int(re.search(r"#define\s+RFN_ABI_VERSION\s+(\d+)", _header_text()).group(1))
+
+
+# entry points whose dtype check goes through csrc/common.h's dispatchers since the element header (csrc/elem.h):
+# 16-bit activations only (dt16 / dt16_type / dt16_check) ...
+_DT16_ONLY = ["rfn_bn_stats_fwd", "rfn_bn_apply_fwd", "rfn_bn_apply_fwd_ld", "rfn_bn_stats_bwd", "rfn_bn_stats_fwd_det",
+              "rfn_bn_stats_bwd_det", "rfn_bn_apply_bwd", "rfn_l2norm_channels_nhwc16_f32", "rfn_maxpool2x2_nhwc16",
+              "rfn_attn_fwd", "rfn_attn_bwd_dq", "rfn_attn_bwd_dkv", "rfn_attn_bwd_dkv_det", "rfn_dwconv3x3_nhwc_fwd_stats",
+              "rfn_dwconv3x3_nhwc_fwd_stats_det", "rfn_dwconv3x3_nhwc_stats_det", "rfn_dwconv3x3_nhwc_stats",
+              "rfn_dwconv3x3_bn_act_nhwc_fwd"]
+# ... and fp32 / bf16 / f16 (dt_one)
+_DT_ANY = ["rfn_upsample_ce", "rfn_upsample_ce_det"]
+# valid sizes by parameter name (every *_stride is 64); what an entry point needs differently
+_SIZES = dict(T=64, C=64, B=1, H=8, W=8, HW=64, h=4, w=4, heads=1, Nq=32, Nkv=32, nkblk=2, nqblk=1, nqpad=128, nkpad=32,
+              blocks_per_chunk=1, kv_pack_heads=1, dilation=1, relu=0, ignore_index=255, round16=0, ld_y=64, eps=1e-5,
+              momentum=0.1, scale=1.0)
+_SIZES_OF = {"rfn_upsample_ce": dict(C=19), "rfn_upsample_ce_det": dict(C=19)}
+
+
+def _parameters(name):
+    """[(is_pointer, parameter name)] of a declaration of the header"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", _header_text(), flags=re.S)
+    args = re.search(r"\b%s\s*\(([^()]*)\)\s*;" % name, text).group(1)
+    return [("*" in a, a.replace("*", " ").split()[-1]) for a in args.split(",")]
+
+
+@pytest.mark.parametrize("name,code", [(n, c) for n in _DT16_ONLY for c in (7, 0)] + [(n, 7) for n in _DT_ANY])
+def test_bad_dtype_code_is_an_argument_error_that_names_the_entry_point(name, code):
+    """A dtype code outside an entry point's set is decided on the host: with non-null pointers (a host buffer that nothing
+    may touch: there is no GPU here) and valid sizes the call returns RFN_EINVAL and rfn_last_error() names the entry point
+    and the code -- code 7 everywhere, and fp32 (code 0) where only 16-bit activations are taken.
+    Left out: rfn_slide_argmax_confmat (csrc/evaltail.hip), which reads its host array of boxes before the dispatch, and
+    rfn_bn_train_fwd / rfn_bn_train_bwd, which are calls of rfn_bn_stats_* and rfn_bn_apply_* and report under their names."""
+    import ctypes
+    from refign_amd import _lib
+    lib = _lib.load_library()
+    buf = ctypes.create_string_buffer(4096 + 16)
+    ptr = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
+    sizes = dict(_SIZES, **_SIZES_OF.get(name, {}))
+    args = []
+    for is_pointer, p in _parameters(name):
+        if p == "stream":
+            args.append(None)
+        elif p == "dtype":
+            args.append(code)
+        elif is_pointer:
+            args.append(ptr)
+        else:
+            args.append(64 if p.endswith("_stride") else sizes[p])
+    assert getattr(lib, name)(*args) == -1                                    # RFN_EINVAL
+    msg = lib.rfn_last_error().decode()
+    assert name in msg and re.search(r"\b%d\b" % code, msg), msg
+    assert buf.raw == bytes(len(buf))                                         # nothing was written

@@ -41,6 +41,30 @@ def test_dwconv_matches_conv2d(dev, B, H, W, C, dil, dtype):
     assert torch.allclose(b.grad, br.grad, **wtol)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_dwconv_input_gradient_alone_with_frozen_parameters(dev, dtype):
+    """Frozen weight and bias: the input gradient is the forward kernel on flipped taps (dwconv3x3_fwd_kernel<FLIP>), which
+    no other test launches.  Reference: fp32 conv2d backward on the same rounded operands.  Bound: one rounding of the result
+    to the activation type (2^-8 of it for bf16, 2^-11 for fp16 covers half an ulp with a factor 2 to spare) on top of the
+    fp32 accumulation of 9 products, 1e-5 absolute and relative."""
+    from refign_amd.dwconv import dwconv3x3_nhwc
+    B, H, W, C, dil = 2, 11, 13, 24, 2                       # ragged last quad, two dilation phases, 3 channel vectors
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, H, W, C, generator=g).to(dev).to(dtype).requires_grad_()
+    w = (0.3 * torch.randn(C, 1, 3, 3, generator=g)).to(dev)
+    b = (0.1 * torch.randn(C, generator=g)).to(dev)
+    gy = torch.randn(B, H, W, C, generator=g).to(dev).to(dtype)
+    dwconv3x3_nhwc(x, w, b, dil).backward(gy)
+    xr = x.detach().float().permute(0, 3, 1, 2).requires_grad_()
+    F.conv2d(xr, w, b, padding=dil, dilation=dil, groups=C).backward(gy.float().permute(0, 3, 1, 2))
+    want = xr.grad.permute(0, 2, 3, 1)
+    rel = {torch.float32: 1e-5, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype]
+    assert x.grad.dtype == dtype
+    err = (x.grad.float() - want).abs()
+    print(f"\n{dtype}: max error {float(err.max()):.3e}, max excess over the bound {float((err - rel * want.abs()).max()):.3e}")
+    assert bool((err <= rel * want.abs() + 1e-5).all())
+
+
 def test_mix_ffn_dwconv_tokens_equals_reference_formulation(dev):
     """DWConv on tokens == transpose -> NCHW depthwise conv -> transpose (mix_transformer.py:563-567)"""
     from refign_amd.seg import DWConv

@@ -70,6 +70,8 @@ CASES = [
     (1, 27, 97, 131, (64, 48), (33, 29), (16, 12), "f16"),           # more than 19 classes: the 32-class instantiation
     (2, 19, 40, 56, (32, 32), (8, 24), (32, 32), "f32"),             # scale 1: the footprint is read from global memory
     (1, 5, 40, 56, (32, 32), (8, 24), (64, 80), "bf16"),             # logits finer than the image (scale 2 and 2.5)
+    (1, 27, 97, 131, (64, 48), (33, 29), (16, 12), "f32"),           # the 32-class instantiation in the other two dtypes
+    (1, 27, 97, 131, (64, 48), (33, 29), (16, 12), "bf16"),
 ]
 
 

@@ -94,7 +94,7 @@ def test_quant_rows_matches_amax_scaling():
     assert torch.allclose(wsb, amax / 896.0, rtol=1e-6)
 
 
-@pytest.mark.parametrize("C", [64, 128, 320, 512])
+@pytest.mark.parametrize("C", [64, 128, 320, 512, 256, 1024])
 def test_layernorm_f8(C):
     from refign_amd import f8
     from refign_amd.layernorm import LayerNorm

@@ -1,5 +1,5 @@
 """GPU: hand-written LayerNorm (csrc/layernorm.hip) forward/backward against torch's fp32 layer_norm, for the MiT
-channel widths, fp32 and bf16 activations, ragged row counts."""
+channel widths and widths that are no multiple of 8 (the scalar kernels), fp32 / bf16 / fp16 activations, ragged row counts."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -7,9 +7,13 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("rows,C", [(1, 64), (7, 32), (1000, 128), (4097, 320), (513, 512), (33, 1024), (5, 160)])
+@pytest.mark.parametrize("rows,C", [(1, 64), (7, 32), (1000, 128), (4097, 320), (513, 512), (33, 1024), (5, 160),
+                                    # C % 8 != 0: the scalar kernels, 1 / 2 / 4 / 8 / 16 channels per lane
+                                    (9, 30), (131, 100), (67, 204), (35, 500), (21, 1001)])
 @pytest.mark.parametrize("in_dt,out_dt", [(torch.float32, torch.float32), (torch.float32, torch.bfloat16),
-                                          (torch.bfloat16, torch.bfloat16)])
+                                          (torch.bfloat16, torch.bfloat16), (torch.bfloat16, torch.float32),
+                                          (torch.float16, torch.float16), (torch.float32, torch.float16),
+                                          (torch.float16, torch.float32)])
 def test_layernorm_fwd_bwd(dev, rows, C, in_dt, out_dt):
     from refign_amd.layernorm import layer_norm
     g = torch.Generator().manual_seed(rows + C)
@@ -24,7 +28,7 @@ def test_layernorm_fwd_bwd(dev, rows, C, in_dt, out_dt):
     wr, br = w.detach().clone().requires_grad_(), b.detach().clone().requires_grad_()
     yr = F.layer_norm(xr, (C,), wr, br, 1e-6)
     yr.backward(gy.float())
-    lo = out_dt == torch.bfloat16 or in_dt == torch.bfloat16
+    lo = out_dt != torch.float32 or in_dt != torch.float32
     tol = dict(rtol=2e-2, atol=2e-2) if lo else dict(rtol=1e-4, atol=1e-5)
     assert torch.allclose(y.float(), yr, **tol)
     assert x.grad.dtype == in_dt

@@ -30,7 +30,7 @@ def _reference(logits, size, target, weight, ignore):
                                          (1, 19, 16, 20, 35, 47),       # non-integer scales >= 2, odd sizes
                                          (2, 7, 5, 8, 40, 48),          # fewer classes, scale 8 / 6
                                          (1, 19, 34, 60, 136, 240)])    # several tiles in both directions
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("weighted", [False, True])
 def test_fused_upsample_ce_matches_interpolate_then_cross_entropy(dev, B, C, h, w, H, W, dtype, weighted):
     from refign_amd import seg
