@@ -8,8 +8,6 @@ to ATen: CPU tensors (host-side tests) and geometries outside the kernels' domai
 convolutions other than depthwise) -- each such GPU call is recorded by mfma.note_library.
 Same parameters / state_dict keys as nn.Conv2d.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -17,7 +15,8 @@ import torch.nn.functional as F
 from . import _lib
 from . import mfma as _mfma
 from ._tensor import DTYPE_CODE, ptr
-from .params import _identity, as_dtype, compute_dtype, derived, grad_sink
+from .params import _identity, as_dtype, channels_last, compute_dtype, derived, grad_sink, nhwc_view, patch_linear, \
+    patch_linear_t
 
 
 class _Conv2dFn(torch.autograd.Function):
@@ -70,8 +69,7 @@ class Conv2d(nn.Conv2d):
                     return y
         # the MiT token tensors reach the convolutions as channels-last views, and the library then wants the filter in
         # channels-last too: keep the cached copy in that layout instead of converting it at every call
-        w_c = derived(self.weight, (cd, "channels_last"),
-                      lambda t: t.to(cd).contiguous(memory_format=torch.channels_last), _identity)
+        w_c = channels_last(self.weight, cd)
         b_c = as_dtype(self.bias, cd)
         if x.dtype != cd:
             x = x.to(cd)
@@ -155,10 +153,6 @@ def _from_patches(gp, B, H, W, C, r, Hr, Wr, cmajor=False):
     return g.reshape(B, H * W, C)
 
 
-def _krsc_view(p):
-    return p.permute(2, 3, 1, 0)
-
-
 class _PatchLinearFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
@@ -197,8 +191,7 @@ class _PatchLinearFn(torch.autograd.Function):
                 from .params import transposed
                 wT = transposed(ctx.weight, w2.dtype)
             else:
-                wT = derived(ctx.weight, (w2.dtype, "patch_linear_T"),
-                             lambda t: t.to(w2.dtype).permute(2, 3, 1, 0).contiguous(), _krsc_view).view(K, Co)
+                wT = patch_linear_t(ctx.weight, w2.dtype).view(K, Co)
             gp = _mfma.gemm_nt(g2, wT)
             if gp is None and _split_ok(g2, wT):
                 gp = _split32().gemm_nt(g2, wT)
@@ -253,8 +246,7 @@ def patch_conv_tokens(x, H, W, conv):
     if cmajor:
         w2 = as_dtype(conv.weight, cd).detach().view(Co, C * r * r)
     else:
-        w2 = derived(conv.weight, (cd, "patch_linear"), lambda t: t.to(cd).permute(0, 2, 3, 1).contiguous(),
-                     lambda t: t.permute(0, 2, 3, 1)).view(Co, r * r * C)
+        w2 = patch_linear(conv.weight, cd).view(Co, r * r * C)
     b_c = as_dtype(conv.bias, cd)
     if x.dtype != cd:
         x = x.to(cd)
@@ -276,40 +268,32 @@ def patch_conv_tokens(x, H, W, conv):
 # Tensors keep their NCHW SHAPE and carry channels-last strides between layers, so consecutive layers hand each other
 # NHWC memory without a copy; bias, folded BatchNorm and ReLU / LeakyReLU ride in the epilogue.
 # ---------------------------------------------------------------------------------------------------------------------
-import os as _os
-
 _ACT = {None: 0, 'relu': 1, 'leaky': 3}
 _CONV_MFMA = True
 
 
-def _nhwc_view(p):
-    return p.permute(0, 2, 3, 1)
+def _tap_rows(src, row_mult, col_mult, dtype):
+    """(zero-padded [Rp, Kp] buffer, its (R, KH, KW, I) view filled from `src`): tap-major rows of the implicit-GEMM kernels, R
+    padded to `row_mult`, I to `col_mult` inside each tap, a row to a multiple of 64.  params.refresh() re-fills the view IN
+    PLACE after an optimizer / EMA update, so a captured graph keeps pointing at live weights; callers get the buffer."""
+    R, KH, KW, I = src.shape
+    Rp, Ip = -(-R // row_mult) * row_mult, -(-I // col_mult) * col_mult
+    base = torch.zeros((Rp, -(-(KH * KW * Ip) // 64) * 64), dtype=dtype, device=src.device)
+    view = base[:R, :KH * KW * Ip].view(R, KH, KW, Ip)[..., :I]
+    view.copy_(src)
+    return base, view
 
 
 def _packed(weight, bias, dtype, n_mult=8):
-    """Cached ([Np, Kpad] tap-major 16-bit weight with the output channels padded to `n_mult`, bias padded likewise).  What is
-    cached per parameter is the (N, KH, KW, C) VIEW into the padded buffer -- the same shape as `weight.permute(0, 2, 3, 1)`
-    -- so that params.refresh() re-fills it IN PLACE after an optimizer / EMA update: a captured graph keeps pointing
-    at live weights (a re-made copy would leave the replay with stale ones)."""
-    def make(t):
-        N, C, KH, KW = t.shape
-        N8, Cp = -(-N // n_mult) * n_mult, -(-C // 8) * 8
-        Kp = -(-(KH * KW * Cp) // 64) * 64
-        base = torch.zeros((N8, Kp), dtype=dtype, device=t.device)
-        view = base[:N, :KH * KW * Cp].view(N, KH, KW, Cp)[..., :C]
-        view.copy_(t.permute(0, 2, 3, 1))
-        view._rfn_base = base
-        return view
-    wp = derived(weight, ("igemm", dtype, n_mult), make, _nhwc_view)._rfn_base
+    """Cached ([Np, Kpad] tap-major 16-bit weight with the output channels padded to `n_mult`, bias padded likewise)."""
+    wp = derived(weight, ("igemm", dtype, n_mult), lambda t: _tap_rows(nhwc_view(t), n_mult, 8, dtype), nhwc_view)
     bp = None
     if bias is not None:
         def makeb(t):
             base = torch.zeros(-(-t.shape[0] // n_mult) * n_mult, dtype=dtype, device=t.device)
-            view = base[:t.shape[0]]
-            view.copy_(t)
-            view._rfn_base = base
-            return view
-        bp = derived(bias, ("igemm_bias", dtype, n_mult), makeb, _identity)._rfn_base
+            base[:t.shape[0]].copy_(t)
+            return base, base[:t.shape[0]]
+        bp = derived(bias, ("igemm_bias", dtype, n_mult), makeb, _identity)
     return wp, bp
 
 
@@ -320,16 +304,7 @@ def _cnhw_view(p):
 def _packed_t(weight, dtype, n_mult):
     """The filter of the DATA-gradient product: rows c (padded to 8), columns [tap][n] with n padded to `n_mult` like the
     forward's output channels -- Wt of rfn_conv2d_nhwc_dgrad.  Cached / re-filled in place like _packed."""
-    def make(t):
-        N, C, KH, KW = t.shape
-        Np, Cp = -(-N // n_mult) * n_mult, -(-C // 8) * 8
-        Kp = -(-(KH * KW * Np) // 64) * 64
-        base = torch.zeros((Cp, Kp), dtype=dtype, device=t.device)
-        view = base[:C, :KH * KW * Np].view(C, KH, KW, Np)[..., :N]
-        view.copy_(t.permute(1, 2, 3, 0))
-        view._rfn_base = base
-        return view
-    return derived(weight, ("igemm_T", dtype, n_mult), make, _cnhw_view)._rfn_base
+    return derived(weight, ("igemm_T", dtype, n_mult), lambda t: _tap_rows(_cnhw_view(t), 8, n_mult, dtype), _cnhw_view)
 
 
 def _nhwc16(x, dtype, Cp):

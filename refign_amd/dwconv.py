@@ -11,15 +11,9 @@ import torch
 
 from . import _lib, determinism
 from ._tensor import DTYPE_CODE, ptr, require_device_tensor, workspace
-from .params import as_dtype, derived, grad_sink
+from .params import as_dtype, grad_sink, tap_major_f32 as _tap_major
 
 _DW_WS_STRIPES = 128       # kMaxStripes in csrc/dwconv.hip (checked against the ABI in the GPU tests)
-
-
-def _tap_major(weight):
-    """(9, C) tap-major fp32 copy of the (C, 1, 3, 3) parameter, re-made only when the parameter changed"""
-    C = weight.shape[0]
-    return derived(weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(), lambda t: t.reshape(C, 9).t())
 
 
 def _f32(p):

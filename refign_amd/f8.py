@@ -65,9 +65,7 @@ def _src_2d(p, kind):
     if kind == "linear":
         return params.as_dtype(p, torch.bfloat16).view(p.shape[0], -1)
     if kind == "patch":                                           # sr conv as a Linear over (ry, rx, c) patches
-        Co = p.shape[0]
-        return params.derived(p, (torch.bfloat16, "patch_linear"), lambda t: t.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous(),
-                              lambda t: t.permute(0, 2, 3, 1)).view(Co, -1)
+        return params.patch_linear(p, torch.bfloat16).view(p.shape[0], -1)
     raise ValueError(kind)
 
 
@@ -170,8 +168,7 @@ def layernorm(x, ln, out_q=ACT_Q):
 def dwconv_gelu(h8, dw, B, H, W, x_scale=1.0 / ACT_Q, out_q=ACT_Q):
     """gelu(depthwise3x3(h) + bias) on e4m3 tokens (B, H*W, C) -> e4m3, `dw` = the nn.Conv2d(C, C, 3, groups=C)."""
     C = h8.shape[-1]
-    w_tap = params.derived(dw.weight, "tap_major_f32", lambda t: t.float().reshape(C, 9).t().contiguous(),
-                           lambda t: t.reshape(C, 9).t())
+    w_tap = params.tap_major_f32(dw.weight)
     b32 = None if dw.bias is None else params.as_dtype(dw.bias, torch.float32).detach()
     y = _u8(h8.shape, h8.device)
     _lib.call("rfn_dwconv3x3_gelu_nhwc_fwd_f8", h8.device, ptr(h8), ptr(w_tap), ptr(b32), ptr(y), B, H, W, C, float(x_scale),

@@ -429,7 +429,7 @@ def kv_packs(x, H, W, sr, norm, kv, want_kv=False, blocks_per_wg=0):
     if not (ENABLED and x.is_cuda and x.dtype in _DT16 and x.dim() == 3 and x.is_contiguous() and x.data_ptr() % 16 == 0
             and not torch.is_grad_enabled()):
         return None
-    from .params import as_dtype, compute_dtype, derived
+    from .params import as_dtype, compute_dtype, patch_linear
     B, N, C = x.shape
     cd = x.dtype
     if compute_dtype(x) != cd or N != H * W or x.numel() >= 2 ** 31 or kv.bias is None or kv.weight.shape != (2 * C, C):
@@ -449,8 +449,7 @@ def kv_packs(x, H, W, sr, norm, kv, want_kv=False, blocks_per_wg=0):
         return None
     if sr is not None:
         # the (Co, ry, rx, c) copy conv.patch_conv_tokens keeps (same cache entry, re-filled in place by params.refresh)
-        w_sr = derived(sr.weight, (cd, "patch_linear"), lambda t: t.to(cd).permute(0, 2, 3, 1).contiguous(),
-                       lambda t: t.permute(0, 2, 3, 1))
+        w_sr = patch_linear(sr.weight, cd)
         b_sr = as_dtype(sr.bias, cd)
         gamma, beta = as_dtype(norm.weight, torch.float32).detach(), as_dtype(norm.bias, torch.float32).detach()
         eps = float(norm.eps)

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._tensor import ptr
-from .params import refresh
+from .params import chunk_rows, refresh
 
 
 class MultiTensorAdamW:
@@ -94,9 +94,9 @@ class MultiTensorAdamW:
                 if not (m.dtype == torch.float32 and v.dtype == torch.float32 and m.is_contiguous() and v.is_contiguous()):
                     return False
                 steps.append(st["step"])
-                n, pp, gp, mp, vp = p.numel(), p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()
-                rows += [(pp + 4 * o, gp + 4 * o, mp + 4 * o, vp + 4 * o, min(chunk, n - o) | (gi << 56))
-                         for o in range(0, n, chunk)]
+                pp, gp, mp, vp = p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()
+                rows += [(pp + 4 * o, gp + 4 * o, mp + 4 * o, vp + 4 * o, cnt | (gi << 56))
+                         for o, cnt in chunk_rows(p.numel(), chunk)]
         ts = {float(s) for s in steps[:1] + steps[-1:]}
         if len(ts) != 1:
             return False
@@ -182,9 +182,3 @@ class MultiTensorAdam(MultiTensorAdamW):
         """Through pinned memory, without waiting: the table is built in the SECOND step of a run (torch takes the first),
         and the matcher's step asks the host nothing after its first call."""
         return host.pin_memory().to(dev, non_blocking=True)
-
-    def _updated(self):
-        """... and the fp32 matcher's convolutions (split32) keep packed weights by version counter: dropped, re-made on use."""
-        super()._updated()
-        from . import split32
-        split32.drop_frozen(self._params)

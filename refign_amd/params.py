@@ -8,8 +8,7 @@ passes per Refign step) add up to ~7 000 launches of tiny kernels (profiles/r01_
     backward kernels (sum_rows, layernorm_bwd, dwconv3x3_bwd_weight) ACCUMULATE straight into the parameter's view of
     the flat fp32 gradient buffer and return None to autograd.
 """
-import os
-
+import numpy as np
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
@@ -17,22 +16,79 @@ from . import _lib
 from ._tensor import DTYPE_CODE, ptr, workspace
 
 
+class _Entry:
+    """One cached copy of a parameter: `value` goes to callers, refresh() copies `refill(p)` into `fill` (the value, or the
+    parameter-shaped view of a padded value); `epoch`: the parameter's epoch cell when the copy was made (no refill only)."""
+    __slots__ = ("value", "fill", "refill", "version", "ptr", "epoch")
+
+    def __init__(self, value, fill, refill, version, ptr, epoch):
+        self.value, self.fill, self.refill, self.version, self.ptr, self.epoch = value, fill, refill, version, ptr, epoch
+
+
+def _epoch(d):
+    cell = d.get("_rfn_epoch")
+    return None if cell is None else cell[0]
+
+
+def _capturing(t):
+    return t.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
 def derived(p, key, fn, refill=None):
-    """fn(p.detach()) cached on the parameter, recomputed when p was modified in place or re-allocated.
-    `refill(p.detach())`, if given, is a VIEW of the parameter with the cached tensor's shape: refresh() then updates
-    the cached tensor in place with one multi-tensor copy (dtype / layout conversions) instead of dropping it."""
-    cache = p.__dict__.setdefault("_rfn_derived", {})
+    """fn(p.detach()) cached on the parameter, recomputed when p was modified in place or re-allocated.  Two kinds of entry:
+      * `refill(p.detach())` given -- a VIEW of the parameter with the cached tensor's shape: refresh() updates the cached
+        tensor in place with one multi-tensor copy (dtype / layout conversions), so captured graphs keep pointing at live
+        values.  fn may return (value, fill_target) where callers get a padded buffer and refresh() fills a view of it.
+      * no refill -- valid until the next refresh() of a set that holds the parameter, then re-made on use; in no plan.
+        Inside a stream capture it is computed but not kept (a tensor allocated there holds no data until the first
+        replay), and a kept one of a refreshed set is not used (the next refresh gives up the tensor the graph points at)."""
+    d = p.__dict__
+    cache = d.setdefault("_rfn_derived", {})
     ent = cache.get(key)
-    if ent is None or ent[1] != p._version or ent[2] != p.data_ptr():
-        with torch.no_grad():
-            t = fn(p.detach())
-        cache[key] = ent = (t, p._version, p.data_ptr(), refill)
+    if ent is not None and ent.version == p._version and ent.ptr == p.data_ptr():
+        if ent.refill is not None:
+            return ent.value
+        epoch = _epoch(d)
+        if ent.epoch == epoch and (epoch is None or not _capturing(ent.value)):
+            return ent.value
+    with torch.no_grad():
+        value = fn(p.detach())
+    value, fill = value if isinstance(value, tuple) else (value, value)
+    if refill is not None:
         _GENERATION[0] += 1                            # cached refresh plans are stale
-    return ent[0]
+    elif _capturing(value):
+        return value
+    cache[key] = _Entry(value, fill, refill, p._version, p.data_ptr(), _epoch(d))
+    return value
 
 
-_GENERATION = [0]        # bumped whenever a derived entry is created, replaced or dropped
+def entries(p):
+    """(key, tensor, refill) of every cached copy of `p` that stands: `tensor` is the one refresh() fills (refill given), or
+    the cached value (refill None)."""
+    d = p.__dict__
+    for key, ent in d.get("_rfn_derived", {}).items():
+        if ent.refill is not None or (ent.version == p._version and ent.ptr == p.data_ptr() and ent.epoch == _epoch(d)):
+            yield key, ent.fill, ent.refill
+
+
+def forget(plan_key):
+    """Drop what refresh() and ema_update() keep for one named parameter set."""
+    _PLANS.pop(plan_key, None)
+    _EMA_TABLES.pop(plan_key, None)
+
+
+_GENERATION = [0]        # bumped whenever an entry WITH a refill view is created, replaced or dropped
 _PLANS = {}              # plan key -> what refresh() does for one fixed parameter set (see refresh)
+_EMA_TABLES = {}         # plan key -> chunk table of ema_update
+
+
+def _table(rows, dev):
+    return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
+
+
+def chunk_rows(n, chunk):
+    """(offset, count) of every `chunk`-element piece of an n-element tensor: one row each in the multi-tensor kernels' tables."""
+    return [(off, min(chunk, n - off)) for off in range(0, n, chunk)]
 
 
 def _identity(t):
@@ -40,74 +96,57 @@ def _identity(t):
 
 
 def _build_plan(params):
-    """One pass over the parameters' caches: which cached tensors are re-filled from which views of their parameter.
-    The views alias the parameters' storage, so the same (dst, src) lists serve every later refresh of this parameter
-    set for as long as no cache entry is created or dropped and no parameter is re-allocated."""
+    """One pass over the parameters' caches: which cached tensors are re-filled from which views of their parameter; entries
+    without a refill view are dropped.  The views alias the parameters' storage, so the same (dst, src) lists serve every later
+    refresh of this parameter set for as long as no refillable entry is created or dropped and no parameter is re-allocated."""
     entries, dst, src = [], [], []
     for p in params:
-        cache = p.__dict__.get("_rfn_derived")
-        if not cache:
-            continue
+        cache = p.__dict__.get("_rfn_derived", {})
         for key in list(cache):
-            t, _, dptr, refill = cache[key]
-            if refill is not None and dptr == p.data_ptr():
-                v = refill(p.detach())
-                if v.shape == t.shape:
-                    dst.append(t)
+            ent = cache[key]
+            if ent.refill is None:
+                del cache[key]
+                continue
+            if ent.ptr == p.data_ptr():
+                v = ent.refill(p.detach())
+                if v.shape == ent.fill.shape:
+                    dst.append(ent.fill)
                     src.append(v)
-                    cache[key] = (t, p._version, dptr, refill)
+                    ent.version = p._version
                     entries.append((cache, key, p))
                     continue
             del cache[key]
             _GENERATION[0] += 1
+    skip = set()
+
+    def launches(idx, make_table, by_dtype=True):
+        """One table per device (and copy dtype) over the pairs `idx`, from 4 pairs on; fewer stay with the per-tensor copies.
+        (The tensors are kept next to the table: they own the memory the table points into.)"""
+        if len(idx) < 4:
+            return []
+        skip.update(idx)
+        groups = {}
+        for i in idx:
+            groups.setdefault((dst[i].device, dst[i].dtype if by_dtype else None), []).append(i)
+        return [make_table([dst[i] for i in g], [src[i] for i in g], dev) + (dev, [dst[i] for i in g], [src[i] for i in g])
+                for (dev, _), g in groups.items()]
+
     # plain fp32 -> bf16 / fp16 casts of contiguous tensors: ONE launch of the multi-tensor cast kernel per device and dtype
-    # (csrc/reduce.hip); torch._foreach_copy_ with a dtype change is one tiny kernel per tensor.  Layout-changing copies stay
-    # per tensor.
-    fast = [i for i, (d, s_) in enumerate(zip(dst, src))
-            if d.is_cuda and d.dtype in _CAST16 and s_.dtype == torch.float32 and d.is_contiguous()
-            and s_.is_contiguous() and d.numel() == s_.numel() and d.numel() > 0]
-    casts = {}
-    if len(fast) >= 4:
-        for i in fast:
-            casts.setdefault((dst[i].device, dst[i].dtype), []).append(i)
-        skip = set(fast)
-    else:
-        skip = set()
-    # transposed bf16 copies (W^T of the Linear weights): one launch of the tile-transpose kernel instead of one strided
+    # (csrc/reduce.hip); torch._foreach_copy_ with a dtype change is one tiny kernel per tensor
+    casts = launches([i for i, (d, s_) in enumerate(zip(dst, src))
+                      if d.is_cuda and d.dtype in _CAST16 and s_.dtype == torch.float32 and d.is_contiguous()
+                      and s_.is_contiguous() and d.numel() == s_.numel() and d.numel() > 0], _cast_table)
+    # transposed 16-bit copies (W^T of the Linear weights): one launch of the tile-transpose kernel instead of one strided
     # copy per tensor
-    rest = [i for i in range(len(dst)) if i not in skip]
-    tr = [i for i in rest if dst[i].is_cuda and dst[i].dtype in _CAST16 and src[i].dtype == torch.float32
-          and dst[i].dim() == 2 and dst[i].is_contiguous() and src[i].dim() == 2 and src[i].t().is_contiguous()
-          and src[i].numel() > 0]
-    transposes = []
-    if len(tr) >= 4:
-        by_dev = {}
-        for i in tr:
-            by_dev.setdefault((dst[i].device, dst[i].dtype), []).append(i)
-        for (dev, _), idx in by_dev.items():
-            transposes.append(_transpose_table([dst[i] for i in idx], [src[i] for i in idx], dev) +
-                              (dev, [dst[i] for i in idx], [src[i] for i in idx]))
-        skip = skip | set(tr)
+    transposes = launches([i for i, (d, s_) in enumerate(zip(dst, src))
+                           if i not in skip and d.is_cuda and d.dtype in _CAST16 and s_.dtype == torch.float32 and d.dim() == 2
+                           and d.is_contiguous() and s_.dim() == 2 and s_.t().is_contiguous() and s_.numel() > 0], _transpose_table)
     # every other layout-changing copy of an fp32 parameter view into a contiguous <= 4-D tensor: one launch
     # (csrc/reduce.hip multi_permute_cast_kernel) instead of one strided-copy kernel per tensor
-    rest = [i for i in range(len(dst)) if i not in skip]
-    pm = [i for i in rest if dst[i].is_cuda and dst[i].is_contiguous() and dst[i].dtype in DTYPE_CODE
-          and src[i].dtype == torch.float32 and 1 <= dst[i].dim() <= 4 and dst[i].numel() > 0
-          and src[i].shape == dst[i].shape]
-    permutes = []
-    if len(pm) >= 4:
-        by_dev = {}
-        for i in pm:
-            by_dev.setdefault(dst[i].device, []).append(i)
-        for dev, idx in by_dev.items():
-            permutes.append(_permute_table([dst[i] for i in idx], [src[i] for i in idx], dev) +
-                            (dev, [dst[i] for i in idx], [src[i] for i in idx]))
-        skip = skip | set(pm)
-    return {"entries": entries, "transposes": transposes, "permutes": permutes,
-            # (the tensors are kept next to the table: they own the memory the table points into)
-            "casts": [_cast_table([dst[i] for i in idx], [src[i] for i in idx], dev) + (dev, [dst[i] for i in idx],
-                                                                                         [src[i] for i in idx])
-                      for (dev, _), idx in casts.items()],
+    permutes = launches([i for i, (d, s_) in enumerate(zip(dst, src))
+                         if i not in skip and d.is_cuda and d.is_contiguous() and d.dtype in DTYPE_CODE and s_.dtype == torch.float32
+                         and 1 <= d.dim() <= 4 and d.numel() > 0 and s_.shape == d.shape], _permute_table, by_dtype=False)
+    return {"entries": entries, "casts": casts, "transposes": transposes, "permutes": permutes,
             "rest": ([d for i, d in enumerate(dst) if i not in skip], [s_ for i, s_ in enumerate(src) if i not in skip]),
             "gen": _GENERATION[0]}
 
@@ -119,7 +158,6 @@ _CAST16 = {torch.bfloat16: ("rfn_multi_cast_f32_bf16", "rfn_multi_transpose_cast
 
 def _permute_table(dst, src, dev):
     """Chunk table of the multi-tensor layout-changing copy: 12 int64 per chunk (csrc/reduce.hip PermChunk), built once."""
-    import numpy as np
     chunk = _lib.load_library().rfn_multi_permute_chunk_elems()
     rows = []
     for d, s_ in zip(dst, src):
@@ -128,25 +166,23 @@ def _permute_table(dst, src, dev):
         n = d.numel()
         assert n < 2 ** 31, "the permute kernel indexes one tensor with 32 bits"
         rows += [(s_.data_ptr(), d.data_ptr(), shape[1], shape[2], shape[3], strides[0], strides[1], strides[2], strides[3],
-                  off, min(chunk, n - off), DTYPE_CODE[d.dtype]) for off in range(0, n, chunk)]
-    return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
+                  off, cnt, DTYPE_CODE[d.dtype]) for off, cnt in chunk_rows(n, chunk)]
+    return _table(rows, dev)
 
 
 def _cast_table(dst, src, dev):
     """Chunk table of the multi-tensor fp32 -> bf16 / fp16 cast kernel (one dst dtype per table): {src*, dst*, n}, 24 bytes per chunk, built once."""
-    import numpy as np
     chunk = _lib.load_library().rfn_multi_cast_chunk_elems()
     rows = []
     for s_, d in zip(src, dst):
-        n, sp, dp = s_.numel(), s_.data_ptr(), d.data_ptr()
-        rows += [(sp + 4 * off, dp + 2 * off, min(chunk, n - off)) for off in range(0, n, chunk)]
-    return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
+        sp, dp = s_.data_ptr(), d.data_ptr()
+        rows += [(sp + 4 * off, dp + 2 * off, cnt) for off, cnt in chunk_rows(s_.numel(), chunk)]
+    return _table(rows, dev)
 
 
 def _transpose_table(dst, src, dev):
     """Tile table of the multi-tensor transpose + cast kernel: src views are (K, N) transposes of contiguous (N, K)
     fp32 parameters, dst the contiguous (K, N) bf16 or fp16 copies (one dtype per table)."""
-    import numpy as np
     rows = []
     T = _lib.load_library().rfn_multi_transpose_tile()
     for s_, d in zip(src, dst):
@@ -155,7 +191,7 @@ def _transpose_table(dst, src, dev):
         for n0 in range(0, N, T):
             for k0 in range(0, K, T):
                 rows.append((sp, dp, N | (K << 32), n0 | (k0 << 32)))
-    return torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows)
+    return _table(rows, dev)
 
 
 def _multi_cast(table, nrows, dev, dtype=torch.bfloat16):
@@ -173,31 +209,39 @@ def refresh(params, plan_key=None):
     """Bring the cached copies of `params` up to date after the parameters were updated in place by something that
     does not bump their version counters (fused / foreach optimizers, EMA updates through `.data`): copies with a
     refill view are re-filled with ONE multi-tensor cast launch + one multi-tensor copy, every other derived tensor is
-    dropped and re-made on next use.  Called by an optimizer-step post hook (every torch optimizer) and by the EMA
-    update.  `plan_key`: callers that refresh the SAME parameter set every step name it; the (dst, src) lists are then
-    built once (walking 1 000 parameters and building their views costs ~3 ms of host time per call) and reused until
-    a cache entry is created / dropped or a parameter moves."""
+    invalid from here on and re-made on next use.  Called by an optimizer-step post hook (every torch optimizer) and by
+    the EMA update.  `plan_key`: callers that refresh the SAME parameter set every step name it; the (dst, src) lists are
+    then built once (walking 1 000 parameters and building their views costs ~3 ms of host time per call) and reused
+    until a refillable entry is created / dropped or a parameter moves.  The parameters of a planned set share an epoch
+    cell (`_rfn_epoch`; one from another set is kept): bumping the set's cells ends its entries without a refill."""
     plan = _PLANS.get(plan_key) if plan_key is not None else None
     if plan is not None and plan["gen"] == _GENERATION[0]:
         ents = plan["entries"]
         # the parameters of a set are updated (and moved) together: the first and the last entry tell whether the
         # version stamps need a pass and whether the storage is still where the plan's views point
         probe = [(c.get(k), p) for c, k, p in ((ents[0], ents[-1]) if ents else ())]
-        if any(e is None or e[2] != p.data_ptr() for e, p in probe):
+        if any(e is None or e.ptr != p.data_ptr() for e, p in probe):
             plan = None                                # parameter re-allocated or entry gone: rebuild
-        elif any(e[1] != p._version for e, p in probe):
+        elif any(e.version != p._version for e, p in probe):
             for cache, key, p in ents:
                 ent = cache.get(key)
-                if ent is not None and ent[1] != p._version:
-                    cache[key] = (ent[0], p._version, ent[2], ent[3])
+                if ent is not None:
+                    ent.version = p._version
     else:
         plan = None
     if plan is None:
-        plan = _build_plan(list(params))
+        params = list(params)
+        plan = _build_plan(params)                     # (drops the entries without a refill itself)
         if plan_key is not None:
+            shared = [0]                                # (a parameter that has a cell from another set keeps it)
+            cells = [p.__dict__.setdefault("_rfn_epoch", shared) for p in params]
+            plan["cells"] = list({id(c): c for c in cells}.values())
             if len(_PLANS) >= 8:
                 _PLANS.clear()
             _PLANS[plan_key] = plan
+    else:
+        for cell in plan["cells"]:
+            cell[0] += 1
     with torch.no_grad():
         for table, nrows, dev, dsts, _ in plan["casts"]:
             _multi_cast(table, nrows, dev, dsts[0].dtype)
@@ -207,9 +251,6 @@ def refresh(params, plan_key=None):
             _lib.call("rfn_multi_permute_cast_f32", dev, ptr(table), nrows)
         if plan["rest"][0]:
             torch._foreach_copy_(*plan["rest"])
-
-
-_EMA_TABLES = {}
 
 
 def ema_update(ema_params, live_params, momentum, plan_key):
@@ -228,14 +269,12 @@ def ema_update(ema_params, live_params, momentum, plan_key):
         ent = _EMA_TABLES.get(plan_key)
         lib = _lib.load_library()
         if ent is None or ent[0] != sig:
-            import numpy as np
             chunk = lib.rfn_multi_cast_chunk_elems()
             rows = []
             for e, l_ in zip(ema_params, live_params):
-                n, ep, lp = e.numel(), e.data_ptr(), l_.data_ptr()
-                rows += [(ep + 4 * off, lp + 4 * off, 0, min(chunk, n - off)) for off in range(0, n, chunk)]
-            table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
-            ent = _EMA_TABLES[plan_key] = (sig, table, len(rows))
+                ep, lp = e.data_ptr(), l_.data_ptr()
+                rows += [(ep + 4 * off, lp + 4 * off, 0, cnt) for off, cnt in chunk_rows(e.numel(), chunk)]
+            ent = _EMA_TABLES[plan_key] = (sig,) + _table(rows, dev)
         _lib.call("rfn_multi_ema_f32", dev, ptr(ent[1]), ent[2], float(momentum))
     else:
         ema, live = [p.data for p in ema_params], [p.data for p in live_params]
@@ -260,6 +299,40 @@ def transposed(p, dtype):
     input-gradient GEMM dx = dy W run as an NT product (csrc/mfma_gemm.hip).  Cached like the plain 16-bit copy and
     re-filled in place after optimizer / EMA updates."""
     return derived(p, ("T", dtype), lambda t: t.reshape(t.shape[0], -1).to(dtype).t().contiguous(), _t_view)
+
+
+# Named layouts of a convolution weight (N, C, KH, KW).  Each function owns its key and its build / refill pair, so every
+# user of a layout shares one entry per parameter and dtype.
+def nhwc_view(t):
+    return t.permute(0, 2, 3, 1)
+
+
+def _krsc_view(t):
+    return t.permute(2, 3, 1, 0)
+
+
+def patch_linear(p, dtype):
+    """(Co, ry, rx, c) copy: the weight of a kernel == stride convolution as a Linear over (ry, rx, c) patch rows."""
+    return derived(p, (dtype, "patch_linear"), lambda t: nhwc_view(t.to(dtype)).contiguous(), nhwc_view)
+
+
+def patch_linear_t(p, dtype):
+    """(ry, rx, c, Co) copy: the transpose of patch_linear, the B operand of the patch Linear's input-gradient GEMM."""
+    return derived(p, (dtype, "patch_linear_T"), lambda t: _krsc_view(t.to(dtype)).contiguous(), _krsc_view)
+
+
+def channels_last(p, dtype):
+    """The weight in the compute dtype with channels-last strides: what the library wants next to channels-last activations."""
+    return derived(p, (dtype, "channels_last"), lambda t: t.to(dtype).contiguous(memory_format=torch.channels_last), _identity)
+
+
+def _tap_view(t):
+    return t.reshape(t.shape[0], 9).t()
+
+
+def tap_major_f32(p):
+    """(9, C) tap-major fp32 copy of a depthwise 3x3 weight (C, 1, 3, 3)."""
+    return derived(p, "tap_major_f32", lambda t: _tap_view(t.float()).contiguous(), _tap_view)
 
 
 def compute_dtype(x):

@@ -13,12 +13,11 @@ kernel's result is fp32 anyway).  The dropped lo.lo' term and the second roundin
 (fp32: 2^-24): far inside the 1e-3 parity bar of the goldens.  Three times the MFMA work of the 16-bit path; the operand
 splits are one launch each (csrc/split3.hip), and attention runs on the fp32 matrix pipe itself (csrc/attn32.hip).
 """
-import os
-
 import torch
 
 from . import _lib, mfma
 from ._tensor import ptr
+from .params import derived
 
 ENABLED = True
 BF = torch.bfloat16
@@ -203,49 +202,17 @@ def _w3(w, order):
     return packed
 
 
-def _w3_frozen(w, order):
-    """_w3 with the result kept on the weight tensor for gradient-free calls (the frozen matcher's decoders run ~60 of these per
-    align()): valid while the tensor's version counter stands; never created inside a stream capture (a tensor allocated there
-    holds no data until the first replay)."""
-    if torch.is_grad_enabled():
-        return _w3(w, order)
-    key = (w._version, order)
-    ent = w.__dict__.get("_rfn_w3")
-    if ent is not None and ent[0] == key:
-        return ent[1]
-    packed = _w3(w, order)
-    if not torch.cuda.is_current_stream_capturing():
-        w.__dict__["_rfn_w3"] = (key, packed)
-    return packed
-
-
-def drop_frozen(params):
-    """Forget what _w3_frozen / _wb_frozen keep on `params`.  For whoever updates parameters in place WITHOUT moving their
-    version counters (optim.MultiTensorAdam): _Conv2dFn.forward runs with grad mode off, so a trainable convolution's packed
-    weight is kept too, and only the version counter would tell that it is stale."""
-    for p in params:
-        p.__dict__.pop("_rfn_w3", None)
-        p.__dict__.pop("_rfn_bpad", None)
-
-
-def _wb_frozen(weight, bias):
-    """(packed split weight, bias padded to the packed row count) of a gradient-free convolution, kept like _w3_frozen."""
-    wp = _w3_frozen(weight, "hlh")
+def _wb(weight, bias):
+    """(packed split weight, bias padded to the packed row count) of a convolution's forward: params.derived entries without a
+    refill view, which stand until the parameter changes or a params.refresh() of a set that holds it.  The frozen matcher's
+    decoders pack their ~60 weights per align() once; a trainable convolution re-packs once per step."""
+    wp = derived(weight, ("split3", "hlh"), lambda t: _w3(t, "hlh"))
     if bias is None:
         return wp, None
     N, Np = bias.shape[0], wp.shape[0]
     if Np == N and bias.is_contiguous():
         return wp, bias
-    if torch.is_grad_enabled():
-        return wp, torch.nn.functional.pad(bias, (0, Np - N)).contiguous()
-    key = (bias._version, Np)
-    ent = bias.__dict__.get("_rfn_bpad")
-    if ent is not None and ent[0] == key:
-        return wp, ent[1]
-    bp = torch.nn.functional.pad(bias.detach(), (0, Np - N)).contiguous()
-    if not torch.cuda.is_current_stream_capturing():
-        bias.__dict__["_rfn_bpad"] = (key, bp)
-    return wp, bp
+    return wp, derived(bias, ("split3_bias", Np), lambda t: torch.nn.functional.pad(t, (0, Np - N)).contiguous())
 
 
 def cat_split(parts):
@@ -282,7 +249,7 @@ def conv2d_parts(parts, weight, bias=None, stride=1, padding=0, dilation=1, act=
         return None
     x3, Cp, _ = got
     B, H, W = x3.shape[:3]
-    wp, b = _wb_frozen(weight, bias)
+    wp, b = _wb(weight, bias)
     OH = (H + 2 * padding - dilation * (KH - 1) - 1) // stride + 1
     OW = (W + 2 * padding - dilation * (KW - 1) - 1) // stride + 1
     y = _conv_o32(x3, wp, b, B, H, W, 3 * Cp, wp.shape[0], KH, KW, stride, padding, dilation, act, False, (OH, OW))
@@ -306,7 +273,7 @@ class _Conv2dFn(torch.autograd.Function):
         B, _, H, W = x.shape
         x3, Cp = _nhwc3(x, "hhl")
         Np = -(-N // 8) * 8
-        wp, b = _wb_frozen(weight, bias)
+        wp, b = _wb(weight, bias)
         OH = (H + 2 * p - d * (KH - 1) - 1) // s + 1
         OW = (W + 2 * p - d * (KW - 1) - 1) // s + 1
         y = _conv_o32(x3, wp, b, B, H, W, 3 * Cp, Np, KH, KW, s, p, d, act, False, (OH, OW))

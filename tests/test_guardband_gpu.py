@@ -1303,8 +1303,7 @@ def test_ema_kernel_directly(dev, momentum, skew):
                 table = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev)
                 _lib.call("rfn_multi_ema_f32", dev, ptr(table), len(rows), float(momentum))
         finally:
-            params._EMA_TABLES.pop(key, None)
-            params._PLANS.pop(key, None)
+            params.forget(key)
         arena.check()
         for i, (e, l_, e0, l0) in enumerate(zip(E, L, E0, L0)):
             assert torch.equal(l_, l0), "the live parameters are read only"

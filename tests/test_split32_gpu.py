@@ -153,3 +153,125 @@ def test_fp32_goldens_stay_off_the_libraries():
     y = head(net(x))
     y.float().square().mean().backward()
     assert not mfma.LIBRARY_CALLS, mfma.library_summary()
+
+
+def _conv_outputs(x, w, b):
+    """The three routes into the split convolution's forward: under autograd, gradient-free on parts, gradient-free."""
+    from refign_amd import split32
+    y = split32.conv2d(x, w, b)
+    with torch.no_grad():
+        yp = split32.conv2d_parts([x[:, :2], x[:, 2:]], w, b, 1, 1, 1)
+        yn = split32.conv2d(x, w, b)
+    assert y is not None and yp is not None and yn is not None
+    return [y.detach(), yp, yn]
+
+
+def test_conv2d_follows_every_kind_of_parameter_update(monkeypatch):
+    """The packed split weight and the padded bias are cached on the parameters (params.derived, no refill view).  Whatever
+    updates the parameters -- with or without moving their version counters -- the next forward computes with the live values:
+    bit-equal to the same call on fresh clones (same kernel, same operands, no cache), and different from the output before the
+    update (steps of 0.1: far above rounding).  N = 5 takes the padded-bias entry, N = 8 hands the live bias over."""
+    from refign_amd import params
+    from refign_amd.optim import MultiTensorAdam, MultiTensorAdamW
+    x = _r((1, 3, 9, 11), 70)
+    ps = [torch.nn.Parameter(t) for t in (_r((5, 3, 3, 3), 71, 27 ** -0.5), _r((5,), 72), _r((8, 3, 3, 3), 73, 27 ** -0.5),
+                                          _r((8,), 74))]
+    pairs = [(ps[0], ps[1]), (ps[2], ps[3])]
+    grads = [_r(tuple(p.shape), 80 + i) for i, p in enumerate(ps)]
+    last = [_conv_outputs(x, w, b) for w, b in pairs]
+
+    def check(what):
+        for i, (w, b) in enumerate(pairs):
+            got, want = _conv_outputs(x, w, b), _conv_outputs(x, w.detach().clone(), b.detach().clone())
+            for route, g, wnt, old in zip(("autograd", "parts", "no_grad"), got, want, last[i]):
+                assert torch.equal(g, wnt), f"{what}: N = {w.shape[0]}, {route}: computed with stale parameters"
+                assert not torch.equal(g, old), f"{what}: N = {w.shape[0]}, {route}: the update did not show"
+            last[i] = got
+
+    def set_grads():
+        for p, g in zip(ps, grads):
+            p.grad = g
+
+    with torch.no_grad():
+        for p in ps:
+            p.add_(0.1)
+    check("in-place op under no_grad")
+    for p in ps:
+        p.data.sub_(0.2)
+    params.refresh(ps)
+    check(".data write + refresh")
+    set_grads()
+    torch.optim.SGD(ps, lr=0.1).step()
+    check("SGD.step")
+    for cls, topt in ((MultiTensorAdamW, torch.optim.AdamW), (MultiTensorAdam, torch.optim.Adam)):
+        set_grads()
+        fused = cls(topt(ps, lr=0.1))
+        fused.step()                                               # torch's own: it creates the state
+        check(f"{cls.__name__}, torch's first step")
+        fused.step()
+        assert fused.launches == 1, "the one-launch step did not run"
+        check(f"{cls.__name__}, one-launch step")
+    live = [_r(tuple(p.shape), 90 + i) for i, p in enumerate(ps)]
+    key = ("test_split32", "ema")
+    tables = []
+    rows = params.chunk_rows
+    monkeypatch.setattr(params, "chunk_rows", lambda n, c: tables.append(n) or rows(n, c))
+    try:
+        params.ema_update(ps, live, 0.5, key)
+        check("ema_update")
+        assert len(tables) == len(ps)                              # (the kernel path: its chunk table was built)
+        params.ema_update(ps, live, 0.5, key)
+        check("ema_update, second")
+        assert len(tables) == len(ps)
+        params.forget(key)
+        params.ema_update(ps, live, 0.5, key)
+        assert len(tables) == 2 * len(ps), "forget() left the EMA chunk table behind"
+    finally:
+        params.forget(key)
+
+
+def test_frozen_pack_is_reused_and_not_kept_from_a_capture():
+    from refign_amd import params, split32
+    x = _r((1, 3, 9, 11), 75)
+    w, b = _r((5, 3, 3, 3), 76, 27 ** -0.5), _r((5,), 77)
+    with torch.no_grad():
+        y = split32.conv2d(x, w, b)
+        packs = [t for _, t, _ in params.entries(w)]
+        assert len(packs) == 1 and len(list(params.entries(b))) == 1
+        assert torch.equal(split32.conv2d(x, w, b), y)
+        assert [t for _, t, _ in params.entries(w)][0] is packs[0]
+        other, key = [torch.nn.Parameter(_r((4, 4), 78))], ("test_split32", "unrelated")
+        try:
+            for _ in range(2):                                     # plan built, then the planned path
+                params.refresh(other, key)
+                split32.conv2d(x, w, b)
+                assert [t for _, t, _ in params.entries(w)][0] is packs[0]
+        finally:
+            params.forget(key)
+        w2 = _r((5, 3, 3, 3), 79, 27 ** -0.5)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = split32.conv2d(x, w2, b)
+        assert list(params.entries(w2)) == [], "a pack allocated inside a capture was kept"
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, split32.conv2d(x, w2, b))
+        assert len(list(params.entries(w2))) == 1
+        # a weight of a refreshed set with a pack kept by an eager call: the graph packs for itself (the next refresh gives
+        # the kept pack up), so the replay after an update computes with the live weight
+        wt, key = torch.nn.Parameter(_r((5, 3, 3, 3), 81, 27 ** -0.5)), ("test_split32", "captured")
+        try:
+            params.refresh([wt], key)
+            stale = split32.conv2d(x, wt, b)
+            assert len(list(params.entries(wt))) == 1
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                out = split32.conv2d(x, wt, b)
+            wt.data.mul_(1.5)
+            params.refresh([wt], key)
+            g.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(out, split32.conv2d(x, wt.detach().clone(), b)) and not torch.equal(out, stale)
+        finally:
+            params.forget(key)
