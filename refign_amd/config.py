@@ -514,3 +514,75 @@ def train_section_plan(cfg, dataset, section=None):
         elif name == "Normalize":
             plan["mean"], plan["std"] = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
     return plan
+
+
+# the matcher's training section (configs/megadepth/uawarpc_stage*.yaml), in its order; the photometric three are optional
+_MATCHING_ORDER = ("ToTensor", "ColorJitter", "ChannelShuffle", "RandomGaussianBlur", "ConvertImageDtype", "Normalize",
+                   "CompositeFlow", "CenterCrop")
+_MATCHING_READER_KEYS = ("load_keys", "dims", "exchange_images_with_proba", "store_scene_info_in_memory")
+
+
+def matching_train_plan(cfg, dataset="MegaDepth"):
+    """One training section `data.init_args.load_config.train[dataset]` of the matcher, whose pipeline is
+        ToTensor -> [ColorJitter -> ChannelShuffle -> RandomGaussianBlur on image_prime] -> ConvertImageDtype -> Normalize
+        -> CompositeFlow(image_prime) -> CenterCrop
+    as what datamodule.MatchingDataModule runs:
+      reader        the reader's keywords as the section gives them (load_keys, dims, exchange_images_with_proba,
+                    store_scene_info_in_memory)
+      dims          the load-time size (h, w)
+      crop          CenterCrop's size (h, w), applied to every key
+      mean / std    Normalize's statistics (ImageNet's by default)
+      photometric   photometric_plan(cfg), or None for a section without the three photometric transforms
+      warp          warp_supervision_plan(cfg)
+    OutOfScopeError names the cause: a transform outside the chain, out of its order or twice; a section without image_prime
+    among its load_keys, without dims, without CompositeFlow or without the CenterCrop after it; and whatever photometric_plan
+    and warp_supervision_plan refuse (apply_keys other than ['image_prime'], hue, parameterize_with_gaussian, ...)."""
+    from .datastep import IMNET_MEAN, IMNET_STD
+    try:
+        sec = cfg["data"]["init_args"]["load_config"]["train"][dataset]
+    except (KeyError, TypeError) as e:
+        raise KeyError(f"matching_train_plan: no data.init_args.load_config.train.{dataset} in this config") from e
+    where = f"(train.{dataset})"
+    if not isinstance(sec, dict):
+        raise OutOfScopeError(f"matching_train_plan: {where} is a list of sections: pass a config that holds the one meant")
+    keys = list(sec.get("load_keys") or [])
+    if "image_prime" not in keys or "image" not in keys or "image_ref" not in keys:
+        raise OutOfScopeError(f"matching_train_plan: load_keys {keys} {where}: image, image_ref and image_prime are what the "
+                              f"matcher's training step reads (no image_prime: no warp supervision)")
+    if sec.get("dims") is None:
+        raise OutOfScopeError(f"matching_train_plan: no dims {where}: the batch needs one load-time size")
+    stage, seen = -1, []
+    mean, std = tuple(IMNET_MEAN), tuple(IMNET_STD)
+    for spec in sec.get("transforms") or []:
+        path = spec["class_path"] if is_spec(spec) else str(spec)
+        name, args = path.rsplit(".", 1)[-1], (spec.get("init_args") or {}) if is_spec(spec) else {}
+        if not path.startswith("data_modules.transforms.") or name not in _MATCHING_ORDER:
+            raise OutOfScopeError(f"matching_train_plan: {path} {where} is outside the matcher's pipeline "
+                                  f"({' / '.join(_MATCHING_ORDER)})")
+        if name in seen:
+            raise OutOfScopeError(f"matching_train_plan: a second {name} {where}")
+        if _MATCHING_ORDER.index(name) < stage:
+            raise OutOfScopeError(f"matching_train_plan: {name} {where} comes out of the order {' -> '.join(_MATCHING_ORDER)}")
+        stage = _MATCHING_ORDER.index(name)
+        seen.append(name)
+        if name in ("ToTensor", "ConvertImageDtype") and args:
+            raise OutOfScopeError(f"matching_train_plan: {name} with {sorted(args)} {where}")
+        if name == "Normalize":
+            extra = set(args) - {"mean", "std"}
+            if extra:
+                raise OutOfScopeError(f"matching_train_plan: Normalize with {sorted(extra)} {where}")
+            mean, std = tuple(args.get("mean", IMNET_MEAN)), tuple(args.get("std", IMNET_STD))
+    for name in ("ToTensor", "ConvertImageDtype", "Normalize", "CompositeFlow", "CenterCrop"):
+        if name not in seen:
+            raise OutOfScopeError(f"matching_train_plan: no data_modules.transforms.{name} {where}")
+    one = {"data": {"init_args": {"load_config": {"train": {dataset: sec}}}}}
+    photo = None
+    if any(n in seen for n in _PHOTOMETRIC_ORDER):
+        photo = photometric_plan(one, "train", dataset)
+    warp = warp_supervision_plan(one, "train", dataset)
+    dims = tuple(int(v) for v in sec["dims"])
+    crop = warp["crop"]
+    if crop[0] > dims[0] or crop[1] > dims[1]:
+        raise OutOfScopeError(f"matching_train_plan: CenterCrop {crop} of dims {dims} {where}: the crop does not pad")
+    return {"reader": {k: sec[k] for k in _MATCHING_READER_KEYS if k in sec}, "dims": dims, "crop": crop, "mean": mean,
+            "std": std, "photometric": photo, "warp": warp}

@@ -16,7 +16,11 @@ What is pinned, and what is not: the epoch's index order is torch's RandomSample
 reference's, and with prefetch=0 the `random` stream is consumed in the reference's order (the source loader's samples, then
 the target loader's).  Lightning is not installed here: the order in which ITS loops create and advance the loaders' iterators
 (and the base seed a DataLoader iterator draws for its workers) is not restated, so parity with a Lightning run's batches is
-not claimed."""
+not claimed.
+
+MatchingDataModule, at the end, is the same for the matcher's configurations (configs/megadepth/uawarpc_*.yaml): MegaDepth pairs
+with warp supervision for AlignmentModel.training_step, MegaDepth / RobotCarMatching with their correspondences for
+validate / test.  Same division of work between the threads, and again no new kernel."""
 import collections
 import random
 from concurrent.futures import ThreadPoolExecutor
@@ -351,6 +355,327 @@ class _TrainIterator:
     def close(self):
         for entry in self.pending:
             for job in [j[-1] for j in list(entry["src"]) + list(entry["trg"])]:
+                if not isinstance(job, dict) and not job.cancel():
+                    job.result()
+        self.pending.clear()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The matcher's `data:` section (configs/megadepth/uawarpc_*.yaml): MegaDepth pairs with warp supervision for training,
+# MegaDepth / RobotCarMatching with their sparse correspondences for evaluation.
+class _PinnedArena:
+    """uint8 pinned host buffers by CAPACITY: a request is rounded up to a multiple of `step` bytes and served by a flat buffer
+    of that many bytes, viewed at the shape asked for.  MegaDepth's files have hundreds of sizes; staging memory grows with the
+    number of capacity classes in flight, not with the number of shapes seen.  A buffer comes back with the event behind the copy
+    that read it and is handed out again after that event (waited for on the host, by the thread that asks)."""
+    STEP = 1 << 20
+
+    def __init__(self, pin, step=STEP):
+        self.pin, self.step, self.free, self.allocated = pin, int(step), collections.defaultdict(list), 0
+
+    def take(self, shape):
+        """-> (the flat buffer, to give back; its view at `shape`)"""
+        shape = tuple(int(v) for v in shape)
+        n = 1
+        for v in shape:
+            n *= v
+        cap = max(1, -(-n // self.step)) * self.step
+        if self.free[cap]:
+            buf, ev = self.free[cap].pop(0)
+            if ev is not None:
+                ev.synchronize()
+        else:
+            buf = torch.empty(cap, dtype=torch.uint8, pin_memory=self.pin)
+            self.allocated += cap
+        return buf, buf[:n].view(shape)
+
+    def give(self, bufs, ev):
+        for b in bufs:
+            self.free[b.numel()].append((b, ev))
+
+
+def _exchange_coin(rng, proba):
+    """the reference's `random.random() < self.exchange_images_with_proba`: thrown whatever the probability"""
+    return rng.random() < proba
+
+
+class _MatchingEvalLoader:
+    """One evaluation section of the matcher: decoded pairs through EvalIngest (which scales the points with each resize),
+    images stacked to the split's batch size, `corr_pts` / `corr_pts_ref` lists of per-sample (n, 2) device tensors (the
+    reference's my_collate), plus `filename`.  Can be iterated again.  `coin`: the section's samples throw the exchange coin
+    (MegaDepth's val split), on the calling thread, in file order, one batch ahead of the decoding at most."""
+
+    def __init__(self, reader, ingest, batch_size, pool, coin):
+        self.reader, self.ingest, self.b, self.pool, self.coin = reader, ingest, int(batch_size), pool, coin
+
+    def __len__(self):
+        return -(-len(self.reader) // self.b)
+
+    def _decode(self, start):
+        jobs = []
+        for i in range(start, min(start + self.b, len(self.reader))):
+            ex = _exchange_coin(random, self.reader.exchange_images_with_proba) if self.coin else False
+            jobs.append(self.reader.decode(i, ex) if self.pool is None else self.pool.submit(self.reader.decode, i, ex))
+        return jobs
+
+    def __iter__(self):
+        starts = list(range(0, len(self.reader), self.b))
+        ahead = self._decode(starts[0]) if starts else None
+        for n, start in enumerate(starts):
+            now, ahead = ahead, (self._decode(starts[n + 1]) if n + 1 < len(starts) else None)
+            parts = []
+            for s in now:
+                s = s if isinstance(s, dict) else s.result()
+                parts.append(self.ingest(s["image"], image_ref=s["image_ref"], corr_pts=s["corr_pts"],
+                                         corr_pts_ref=s["corr_pts_ref"]))
+            if len({tuple(p[k].shape) for p in parts for k in ("image", "image_ref")}) > 1:
+                raise ValueError(f"MatchingDataModule: a batch of {len(parts)} images of different sizes cannot be stacked: give the "
+                                 f"section dims, or a batch size of 1")
+            batch = {k: (parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts], dim=0)) for k in ("image", "image_ref")}
+            for k in ("corr_pts", "corr_pts_ref"):
+                batch[k] = [t for p in parts for t in p[k]]
+            batch["filename"] = [self.reader.filename(i) for i in range(start, min(start + self.b, len(self.reader)))]
+            yield batch
+
+
+class MatchingDataModule:
+    """MatchingDataModule(cfg, data_dir, device, prefetch=None): `cfg` is the loaded YAML of a matcher configuration; the data
+    sets lie in <data_dir>/MegaDepth (<data_dir>/MegaDepth_debug under `debug: true`) and <data_dir>/RobotCarMatching.
+      train_on / val_on / test_on / predict_on, idx_to_name, batch_size, val_batch_size, test_batch_size: as CombinedDataModule
+      train_batches()              an endless iterator of {image_ref, image_trg, image_prime, flow_prime, mask_prime,
+                                   prime_trg_idx} on the device: what AlignmentModel.training_step reads
+      loaders(split, datasets)     {data set: iterable of batches} for Trainer.validate / test
+      close()                      ends the decoding threads
+    Training, per sample: the exchange coin, the two files decoded, image_ref through resize_crop_flip_normalize (Lanczos to
+    `dims`, the centre crop) into its batch slot, the target resized once (resize_u8, Lanczos) -- that uint8 frame is
+    image_prime's input, and image_trg is its crop_flip_normalize -- then the sample's photometric and composite draws; one
+    WarpSupervision call for the batch.  Per epoch the draws are epoch_permutation(len) (`drop_last`), then for the samples in
+    batch order coin, photometric.draw, draw_composite: the reference's __getitem__-then-transforms order for one loader
+    without workers.  prime_trg_idx is a device int64 tensor of ones (the prime image is always made from the target).
+    prefetch=0: files are decoded inside next() and the coin is on the global `random` stream.  prefetch=k > 0 (2 by default when
+    the YAML's num_workers > 0): files are decoded k batches ahead within the epoch, in at most min(num_workers, 16) threads; the
+    coins are then drawn ahead from a random.Random of the loader's own, seeded once from the global stream at the first next().
+    Every draw and all device work happen on the thread that calls next().
+    Not here: worker processes, several ranks (every rank would read the same batches), parity with the batch order of a
+    Lightning run, `predict` (OutOfScopeError: the reference's matcher has no predict_step)."""
+
+    def __init__(self, cfg, data_dir, device, prefetch=None):
+        args = dict(((cfg or {}).get("data") or {}).get("init_args") or {})
+        self.cfg, self.data_dir, self.device = cfg, str(data_dir), torch.device(device)
+        self.load_config = args.get("load_config") or {}
+        self.debug = bool(args.get("debug", False))
+        self.num_workers = min(max(int(args.get("num_workers", 0)), 0), MAX_WORKERS)
+        batch_size, divisor = int(args.get("batch_size", 8)), int(args.get("batch_size_divisor", 1))
+        assert batch_size % divisor == 0, "batch_size must be divisible by batch_size_divisor"
+        self.batch_size = batch_size // divisor
+        self.pin_memory = bool(args.get("pin_memory", True))
+        self._sec = {split: _sections(self.load_config, split) for split in _SPLITS}
+        self.train_on, self.val_on = [n for n, _ in self._sec["train"]], [n for n, _ in self._sec["val"]]
+        self.test_on, self.predict_on = [n for n, _ in self._sec["test"]], [n for n, _ in self._sec["predict"]]
+        self.idx_to_name = {split: {i: n for i, (n, _) in enumerate(self._sec[split])} for split in _SPLITS}
+        if self.train_on:
+            assert self.batch_size % len(self.train_on) == 0, "batch size should be divisible by number of train datasets"
+        self.val_batch_size = max(1, self.batch_size // max(len(self.train_on), 1) // 2)
+        self.test_batch_size = 1
+        self.prefetch = (2 if self.num_workers > 0 else 0) if prefetch is None else int(prefetch)
+        if self.prefetch < 0:
+            raise ValueError("MatchingDataModule: prefetch must not be negative")
+        self._pool = None
+        self._iters = []
+
+    def _executor(self):
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max(1, self.num_workers), thread_name_prefix="refign-decode")
+        return self._pool
+
+    def root(self, name):
+        return f"{self.data_dir}/{name}" + ("_debug" if self.debug and name == "MegaDepth" else "")
+
+    def _reader(self, split, name, conf):
+        from .datasets import MATCHING_READERS
+        if name not in MATCHING_READERS:
+            raise config.OutOfScopeError(f"MatchingDataModule: {name} ({split}) has no reader here ({' / '.join(MATCHING_READERS)}); "
+                                         f"select the supported sections with datasets=")
+        kwargs = {k: v for k, v in conf.items() if k != "transforms"}
+        if name == "MegaDepth":
+            kwargs["debug"] = self.debug
+        return MATCHING_READERS[name](self.root(name), stage=split, **kwargs)
+
+    def close(self):
+        """ends the iterators' look-ahead and the decoding threads (waits for them); harmless when called again"""
+        for it in self._iters:
+            it.close()
+        self._iters = []
+        if self._pool is not None:
+            self._pool.shutdown(wait=True, cancel_futures=True)
+            self._pool = None
+
+    # -- evaluation ----------------------------------------------------------------------------------------------------------
+    def loaders(self, split, datasets=None):
+        """{data set: iterable of batches} in idx_to_name[split]'s order.  A batch: resample.EvalIngest(**config.ingest_plan(cfg,
+        split, name)) over the decoded pairs -- image, image_ref stacked to the split's batch size (val: val_batch_size; test:
+        1), corr_pts / corr_pts_ref as lists of per-sample (n, 2) device tensors in the pixels of the batch's images -- plus
+        `filename`.  MegaDepth's val samples throw their exchange coin, as the reference's do.  datasets: the names to keep."""
+        if split == "predict":
+            raise config.OutOfScopeError("MatchingDataModule: predict is outside this module: the reference's matcher "
+                                         "(AlignmentModel) has no predict_step")
+        if split not in ("val", "test"):
+            raise ValueError(f"MatchingDataModule.loaders: split must be 'val' or 'test', got {split!r}")
+        from .resample import EvalIngest
+        out = {}
+        for name, conf in self._sec[split]:
+            if datasets is not None and name not in datasets:
+                continue
+            if name in out:
+                raise config.OutOfScopeError(f"MatchingDataModule: two sections of {name} in {split}: the loaders and the metrics "
+                                             f"are named by data set")
+            reader = self._reader(split, name, conf)
+            plan = config.ingest_plan(_one_section_cfg(split, name, conf), split, name)
+            kw = {k: plan[k] for k in _EVAL_KEYS}
+            if kw["dims"] is None and reader.dims is not None:
+                kw["dims"] = tuple(reader.dims)                     # the reader's own default (RobotCarMatching: 1024 x 1024)
+            ingest = EvalIngest(device=self.device, **kw)
+            out[name] = _MatchingEvalLoader(reader, ingest, self.val_batch_size if split == "val" else self.test_batch_size,
+                                            self._executor() if self.num_workers > 0 else None,
+                                            coin=getattr(reader, "split", "test") != "test")
+        return out
+
+    # -- training ------------------------------------------------------------------------------------------------------------
+    def train_batches(self):
+        """An endless iterator of training batches.  One epoch_permutation per epoch, drawn when the epoch's first batch is asked
+        for; the epoch has len // batch_size batches (`drop_last`).  A yielded batch consists of fresh tensors made on the current
+        stream: nothing writes to it again."""
+        secs = self._sec["train"]
+        if len(secs) != 1:
+            raise config.OutOfScopeError(f"MatchingDataModule: training sections {[n for n, _ in secs]}: one MegaDepth section is "
+                                         f"what the matcher's configurations train on")
+        name, conf = secs[0]
+        plan = config.matching_train_plan(_one_section_cfg("train", name, conf), name)
+        reader = self._reader("train", name, conf)
+        if self.device.type != "cuda":
+            raise RuntimeError("MatchingDataModule.train_batches: a HIP device is required (no CPU fallback)")
+        it = _MatchingTrainIterator(self, reader, plan)
+        self._iters.append(it)
+        return it
+
+
+class _MatchingTrainIterator:
+    def __init__(self, dm, reader, plan):
+        from .flowsynth import WarpSupervision, crop_origin
+        self.dm, self.reader, self.plan = dm, reader, plan
+        self.b = dm.batch_size
+        self.n_batches = len(reader) // self.b
+        if self.n_batches == 0:
+            raise ValueError("MatchingDataModule: the training set holds fewer pairs than one batch")
+        self.dims, self.crop = plan["dims"], plan["crop"]
+        self.top, self.left = crop_origin(*self.dims, *self.crop)
+        self.supervise = WarpSupervision(plan["warp"], photometric=plan["photometric"])
+        self.proba = reader.exchange_images_with_proba
+        self.arena = _PinnedArena(dm.pin_memory)
+        self.k = dm.prefetch
+        self.exe = dm._executor() if self.k > 0 else None
+        self.private = None                                  # the coins' own stream (prefetch > 0)
+        self.order, self.pos = [], 0
+        self.pending = collections.deque()                   # planned batches: {"indices", "jobs": [(exchange, job)], "bufs"}
+        self.sizes = {}
+        self.ones = torch.ones(self.b, dtype=torch.int64, device=dm.device)
+        # clocks for tools/matching_datamodule_bench.py: all of next(); the decoding itself (summed over the threads); next()
+        # waiting for a file (prefetch=0: decoding it); the photometric and composite draws
+        self.epoch, self.batches = 0, 0
+        self.host_seconds, self.decode_seconds, self.wait_seconds, self.draw_seconds = 0.0, 0.0, 0.0, 0.0
+
+    def __iter__(self):
+        return self
+
+    def _job(self, index, exchange, bufs):
+        """start (or, without threads, do) the decoding of one pair into pinned buffers -> a future or the sample"""
+        key = (index, exchange)
+        if key not in self.sizes:
+            self.sizes[key] = self.reader.sizes(index, exchange)
+        out = {}
+        for k, (h, w) in self.sizes[key].items():
+            buf, out[k] = self.arena.take((h, w, 3))
+            bufs.append(buf)
+        views = {k: v.numpy() for k, v in out.items()}
+
+        def work():
+            import time
+            t0 = time.perf_counter()
+            s = self.reader.decode(index, exchange, views)
+            s.update(out)                                    # the pinned tensors in place of their numpy views
+            s["decode_seconds"] = time.perf_counter() - t0
+            return s
+        return work() if self.exe is None else self.exe.submit(work)
+
+    def _new_epoch(self):
+        self.order = epoch_permutation(len(self.reader))[:self.n_batches * self.b]
+        self.pos = 0
+        self.epoch += 1
+
+    def _plan(self):
+        """one more batch of the current epoch: its indices; with prefetch, its coins and its decoding jobs"""
+        entry = {"indices": self.order[self.pos:self.pos + self.b], "jobs": collections.deque(), "bufs": []}
+        self.pos += self.b
+        if self.k > 0:
+            for i in entry["indices"]:
+                ex = _exchange_coin(self.private, self.proba)
+                entry["jobs"].append((ex, self._job(i, ex, entry["bufs"])))
+        self.pending.append(entry)
+
+    def __next__(self):
+        import time
+        from .datastep import crop_flip_normalize
+        from .resample import resize_crop_flip_normalize, resize_u8
+        t0 = time.perf_counter()
+        dev, plan = self.dm.device, self.plan
+        if self.k > 0 and self.private is None:
+            self.private = random.Random(random.getrandbits(64))
+        if not self.pending:
+            if self.pos >= len(self.order):
+                self._new_epoch()
+            self._plan()
+        cur = self.pending.popleft()
+        while self.k > 0 and len(self.pending) < self.k and self.pos < len(self.order):
+            self._plan()
+        (Hd, Wd), (ch, cw) = self.dims, self.crop
+        ref = torch.empty((self.b, 3, ch, cw), dtype=torch.float32, device=dev)
+        trg = torch.empty((self.b, 3, ch, cw), dtype=torch.float32, device=dev)
+        prime = torch.empty((self.b, 3, Hd, Wd), dtype=torch.uint8, device=dev)
+        draws, exchanged = [], []
+        for j, index in enumerate(cur["indices"]):
+            t1 = time.perf_counter()
+            if cur["jobs"]:
+                ex, job = cur["jobs"].popleft()
+                s = job if isinstance(job, dict) else job.result()
+            else:
+                ex = _exchange_coin(random, self.proba)
+                s = self._job(index, ex, cur["bufs"])
+            self.wait_seconds += time.perf_counter() - t1
+            self.decode_seconds += s["decode_seconds"]
+            exchanged.append(ex)
+            a = s["image_ref"].to(dev, non_blocking=True)
+            t = s["image"].to(dev, non_blocking=True)
+            resize_crop_flip_normalize(a, self.dims, self.top, self.left, ch, cw, False, ref[j], plan["mean"], plan["std"],
+                                       filter="lanczos")
+            if tuple(t.shape[:2]) == (Hd, Wd):               # Pillow's reader leaves a file of that size as it is
+                prime[j].copy_(t.permute(2, 0, 1))
+            else:
+                prime[j].copy_(resize_u8(t, self.dims, filter="lanczos"))
+            crop_flip_normalize(prime[j], None, self.top, self.left, ch, cw, False, trg[j], None, plan["mean"], plan["std"])
+            t1 = time.perf_counter()
+            draws.append(self.supervise.draw(Hd, Wd))
+            self.draw_seconds += time.perf_counter() - t1
+        self.arena.give(cur["bufs"], torch.cuda.current_stream(dev).record_event())
+        batch = self.supervise({"image": trg, "image_ref": ref, "image_prime": prime}, draws=draws)
+        batch["prime_trg_idx"] = self.ones
+        self.exchanged = exchanged
+        self.batches += 1
+        self.host_seconds += time.perf_counter() - t0
+        return batch
+
+    def close(self):
+        for entry in self.pending:
+            for _, job in entry["jobs"]:
                 if not isinstance(job, dict) and not job.cancel():
                     job.result()
         self.pending.clear()

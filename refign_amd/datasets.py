@@ -8,7 +8,8 @@ an array.  The semantics are the reference readers' (data_modules/datasets/{city
   * `decode(index)` stops at the DECODED file: the load-time resize to `dims` is the device's job (`dims=` of the samplers in
     refign_amd/datastep.py, resample.EvalIngest), and so is everything after it.  `transforms` is accepted and ignored.
 
-No reader opens a file before `decode` is called, none starts a process or a thread."""
+No reader opens a file before `decode` is called, none starts a process or a thread.
+The matcher's two data sets (MegaDepth, RobotCarMatching) follow at the end, in a registry of their own (MATCHING_READERS)."""
 import json
 import os
 
@@ -244,3 +245,234 @@ def write_class_stats(root, out_dir=None, device=None, num_classes=19):
     with open(os.path.join(out_dir, "samples_with_class.json"), "w") as f:
         json.dump(with_class, f, indent=2)
     return stats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The matcher's two data sets (data_modules/datasets/{megadepth,robotcarmatching}.py, restated).  They are NOT in READERS:
+# SegmentationDataModule keeps refusing them; datamodule.MatchingDataModule reads them through MATCHING_READERS.
+def _read_pairs_csv(path):
+    """the rows of test1600Pairs.csv / test6511.csv as dicts of strings (the reference reads them with pandas, dtype=str)"""
+    import csv
+    with open(path, newline="") as f:
+        return list(csv.DictReader(f))
+
+
+def _floats(text):
+    return np.array(list(map(float, text.split(";")))).astype(np.float32)
+
+
+class _PairReader:
+    """what the two matching readers share: the CSV form of a sample, `filename`, `pair_paths`, `sizes`, `decode`.
+    decode(index, exchange=False, out=None) -> {"image_ref", "image": uint8 (H, W, 3) as stored; "corr_pts_ref", "corr_pts":
+    fp32 (n, 2) (x, y) in the pixels of the stored files; "exchange": bool}.  Neither the images nor the points are brought to
+    `dims`: the resize and the points' scaling (dims[1] / w, dims[0] / h) belong to the place that resizes (resample.EvalIngest,
+    MatchingDataModule's training path)."""
+    keys = ("image_ref", "image")
+
+    def _csv_sample(self, index):
+        row = self.rows[index]
+        scene = "." if row["scene"] == "/" else row["scene"]
+        pts = np.stack((_floats(row["XB"]), _floats(row["YB"])), axis=1)          # of the target image: corr_pts
+        pts_ref = np.stack((_floats(row["XA"]), _floats(row["YA"])), axis=1)      # of the source image: corr_pts_ref
+        return os.path.join(scene, row["source_image"]), os.path.join(scene, row["target_image"]), pts_ref, pts
+
+    def filename(self, index):
+        return self.pair_paths(index)[1].split("/")[-1]
+
+    def pair_paths(self, index, exchange=False):
+        """(image_ref's path, image's path) below `images_dir`"""
+        ref, img = self._sample(index)[:2]
+        return (img, ref) if exchange else (ref, img)
+
+    def sizes(self, index, exchange=False):
+        """{key: (H, W)} of the two files, from their headers"""
+        from PIL import Image
+        out = {}
+        for k, rel in zip(self.keys, self.pair_paths(index, exchange)):
+            with Image.open(os.path.join(self.images_dir, rel)) as im:
+                out[k] = (im.size[1], im.size[0])
+        return out
+
+    def decode(self, index, exchange=False, out=None):
+        from PIL import Image
+        ref, img, pts_ref, pts = self._sample(index)
+        if exchange:
+            ref, img, pts_ref, pts = img, ref, pts, pts_ref
+        sample = {}
+        for k, rel in (("image_ref", ref), ("image", img)):
+            with Image.open(os.path.join(self.images_dir, rel)) as im:
+                a = np.array(im.convert("RGB"))
+            if out is not None and k in out:
+                np.copyto(out[k], a)
+                a = out[k]
+            sample[k] = a
+        sample.update(corr_pts_ref=np.array(pts_ref, dtype=np.float32), corr_pts=np.array(pts, dtype=np.float32),
+                      exchange=bool(exchange))
+        return sample
+
+
+class MegaDepth(_PairReader):
+    """stage -> split: train -> train, val -> val, test / predict -> test; debug: train_debug whatever the stage.
+    test: <root>/Test/test1600Pairs.csv (scene, source_image, target_image, XA / YA / XB / YB as `;`-separated floats) with the
+    images under <root>/Test/test1600Pairs; image_ref is the source image.
+    train / val: for every scene of the split's list, <root>/scene_info/<scene>.0.npz (image_paths, depth_paths,
+    points3D_id_to_2D, overlap_matrix); images without a path or a depth map are dropped, the pairs with an overlap in (0.3, 1.0]
+    are the candidates, at most `*_num_per_scene` of them are kept per scene (RandomState(400).choice(len(pairs), num,
+    replace=False)) and the list of all scenes' items is shuffled once (RandomState(400).shuffle).  An item's points are the 2-D
+    positions of the 3-D points both images see, in the iteration order of `keys() & keys()`.
+    store_scene_info_in_memory: the scenes' tables are kept and an item is (scene, i, j, overlap), resolved when it is read;
+    otherwise an item is the resolved bundle.  `item(index)` gives the bundle in both forms.
+    The scene lists are <lists_dir>/{train,train_debug,validation,test}_scenes_MegaDepth.txt, <root>/lists when not given.  They
+    are no part of this package: the reference ships them as data_modules/datasets/lists/*_scenes_MegaDepth.txt.
+    len: the reference returns 30000 for `train` whatever the number of items and would index past the end of a shorter list;
+    here it is min(30000, len(items)).
+    The coin `random.random() < exchange_images_with_proba` of a two-view sample is NOT thrown here: decode(index, exchange=)
+    takes the decision from the caller, who draws it on the thread that owns the stream."""
+    cfg = {"train_split": "train_scenes_MegaDepth.txt", "train_debug_split": "train_debug_scenes_MegaDepth.txt",
+           "val_split": "validation_scenes_MegaDepth.txt", "test_split": "test_scenes_MegaDepth.txt",
+           "train_debug_num_per_scene": 10, "train_num_per_scene": 300, "val_num_per_scene": 25,
+           "min_overlap_ratio": 0.3, "max_overlap_ratio": 1.0}
+    TRAIN_LEN = 30000
+
+    def __init__(self, root, stage="train", load_keys=("image_ref", "image", "image_prime"), dims=None,
+                 exchange_images_with_proba=0, store_scene_info_in_memory=False, debug=False, transforms=None, lists_dir=None):
+        self.root, self.dims, self.exchange_images_with_proba = root, dims, exchange_images_with_proba
+        if stage not in _STAGES:
+            raise AssertionError(f"MegaDepth: stage must be one of {_STAGES}, got {stage!r}")
+        self.stage = stage
+        self.split = "train_debug" if debug else {"train": "train", "val": "val", "test": "test", "predict": "test"}[stage]
+        self.load_keys = _listed(load_keys)
+        if self.split == "test":
+            assert "image_prime" not in self.load_keys, "MegaDepth: the test split has no image_prime"
+            assert self.exchange_images_with_proba == 0, "MegaDepth: the test split does not exchange its images"
+            self.rows = _read_pairs_csv(os.path.join(root, "Test", "test1600Pairs.csv"))
+            self.images_dir = os.path.join(root, "Test", "test1600Pairs")
+            return
+        self.images_dir = root
+        self.scene_info_path = os.path.join(root, "scene_info")
+        name = self.cfg[self.split + "_split"]
+        path = os.path.join(lists_dir or os.path.join(root, "lists"), name)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"MegaDepth: the scene list {path} is missing (scene names separated by white space; the "
+                                    f"reference ships it as data_modules/datasets/lists/{name}: copy it there or pass lists_dir=)")
+        with open(path) as f:
+            self.scenes = f.read().split()
+        if not ("image_ref" in self.load_keys and "image" in self.load_keys):
+            raise NotImplementedError(f"MegaDepth: load_keys {self.load_keys}: the single-view form is not read here (image_ref "
+                                      f"and image together are what the matcher trains and validates on)")
+        self.store_scene_info_in_memory = bool(store_scene_info_in_memory)
+        self.items = []
+        if self.store_scene_info_in_memory:
+            self.save_scene_info()
+        self.sample_new_items()
+
+    def _info(self, scene, **kw):
+        path = os.path.join(self.scene_info_path, "%s.0.npz" % scene)
+        return np.load(path, allow_pickle=True, **kw) if os.path.exists(path) else None
+
+    def _tables(self, info):
+        """-> (paths, points3D_id_to_2D, overlap matrix) of the images that have a path and a depth map, [N, 2] candidate pairs"""
+        valid = ((info["image_paths"] != None) & (info["depth_paths"] != None))  # noqa: E711  (element-wise, object arrays)
+        mat = info["overlap_matrix"][valid][:, valid]
+        pairs = (mat > self.cfg["min_overlap_ratio"]) & (mat <= self.cfg["max_overlap_ratio"])
+        return info["image_paths"][valid], info["points3D_id_to_2D"][valid], mat, np.stack(np.where(pairs), -1)
+
+    def save_scene_info(self):
+        self.images, self.points3D_id_to_2D, self.pairs = {}, {}, {}
+        for scene in self.scenes:
+            info = self._info(scene)
+            if info is None:
+                continue
+            paths, points, mat, pairs = self._tables(info)
+            self.images[scene], self.points3D_id_to_2D[scene] = paths.copy(), points.copy()
+            self.pairs[scene] = [(i, j, mat[i, j]) for i, j in pairs]
+
+    @staticmethod
+    def _bundle(paths, points, idx1, idx2):
+        matches = np.array(list(points[idx1].keys() & points[idx2].keys()))
+        return {"image_path1": paths[idx1], "image_path2": paths[idx2],
+                "2d_matches_1": [np.array(points[idx1][m], dtype=np.float32).reshape(1, 2) for m in matches],
+                "2d_matches_2": [np.array(points[idx2][m], dtype=np.float32).reshape(1, 2) for m in matches]}
+
+    def sample_new_items(self, seed=400):
+        self.items = []
+        num = self.cfg[self.split + "_num_per_scene"]
+        for scene in self.scenes:
+            if self.store_scene_info_in_memory:
+                if scene not in self.pairs:
+                    continue
+                pairs = np.array(self.pairs[scene])
+                if len(pairs) > num:
+                    pairs = pairs[np.random.RandomState(seed).choice(len(pairs), num, replace=False)]
+                self.items.extend((scene, int(i), int(j), k) for i, j, k in pairs)
+            else:
+                info = self._info(scene, mmap_mode="r")
+                if info is None:
+                    continue
+                paths, points, _, pairs = self._tables(info)
+                if len(pairs) > num:
+                    pairs = pairs[np.random.RandomState(seed).choice(len(pairs), num, replace=False)]
+                self.items.extend(self._bundle(paths, points, pairs[n, 0], pairs[n, 1]) for n in range(len(pairs)))
+        if "debug" in self.split:
+            import copy
+            orig = copy.deepcopy(self.items)
+            for _ in range(10):
+                self.items = self.items + copy.deepcopy(orig)
+        np.random.RandomState(seed).shuffle(self.items)
+
+    def __len__(self):
+        if self.split == "test":
+            return len(self.rows)
+        return min(self.TRAIN_LEN, len(self.items)) if self.split == "train" else len(self.items)
+
+    def item(self, index):
+        """the pair bundle {image_path1, image_path2, 2d_matches_1, 2d_matches_2} of a train / val item, in either form"""
+        it = self.items[index]
+        if isinstance(it, dict):
+            return it
+        scene, idx1, idx2, _ = it
+        return self._bundle(self.images[scene], self.points3D_id_to_2D[scene], idx1, idx2)
+
+    def _sample(self, index):
+        if self.split == "test":
+            return self._csv_sample(index)
+        it = self.item(index)
+        cat = lambda parts: np.concatenate(parts, axis=0) if parts else np.zeros((0, 2), np.float32)  # noqa: E731
+        return it["image_path1"], it["image_path2"], cat(it["2d_matches_1"]), cat(it["2d_matches_2"])
+
+    def decode(self, index, exchange=False, out=None):
+        if exchange and self.split == "test":
+            raise AssertionError("MegaDepth: the test split does not exchange its images")
+        return super().decode(index, exchange, out)
+
+
+class RobotCarMatching(_PairReader):
+    """<root>/test6511.csv (the columns of MegaDepth's test file) with the images under <root>/images; stages test and predict.
+    dims and resize_filter are kept for the caller (the reader's own default dims are (1024, 1024), Lanczos)."""
+
+    def __init__(self, root, stage="test", load_keys=("image_ref", "image"), dims=(1024, 1024), resize_filter="lanczos",
+                 transforms=None, **kwargs):
+        self.root, self.dims, self.resize_filter = root, dims, resize_filter
+        assert stage in ["test", "predict"], f"RobotCarMatching: stage must be 'test' or 'predict', got {stage!r}"
+        self.stage, self.load_keys = stage, _listed(load_keys)
+        for k in self.load_keys:
+            if k not in self.keys:
+                raise ValueError(f"RobotCarMatching: invalid load_key {k!r}")
+        if not os.path.isdir(root):
+            raise RuntimeError(_MISSING.format(root, "images"))
+        self.rows = _read_pairs_csv(os.path.join(root, "test6511.csv"))
+        self.images_dir = os.path.join(root, "images")
+
+    def __len__(self):
+        return len(self.rows)
+
+    def _sample(self, index):
+        return self._csv_sample(index)
+
+    def decode(self, index, exchange=False, out=None):
+        if exchange:
+            raise AssertionError("RobotCarMatching does not exchange its images")
+        return super().decode(index, False, out)
+
+
+MATCHING_READERS = {"MegaDepth": MegaDepth, "RobotCarMatching": RobotCarMatching}

@@ -304,7 +304,10 @@ class WarpSupervision:
     photometric: config.photometric_plan(cfg) or None.  With a plan the pipeline's photometric half runs in front: image_prime
     is then the uint8 (B, 3, h, w) device tensor of the load-time resize, per sample the draws are photometric.draw followed by
     draw_composite (the reference's order: each sample runs its whole pipeline), and the batch goes through photometric.apply
-    into synthesize.  With None every launch and every draw is as it was."""
+    into synthesize.  With None every launch and every draw is as it was.
+    draw(h, w) makes one sample's draws in that order and returns them; __call__(sample, draws=[...]) takes a batch's draws made
+    that way instead of drawing -- for a caller that has draws of its own to make between two samples' (the data module's
+    exchange coin comes in front of each sample's pipeline, as in the reference's __getitem__)."""
 
     def __init__(self, plan, photometric=None):
         self.composite = dict(plan["composite"])
@@ -312,21 +315,29 @@ class WarpSupervision:
         self.min_fraction_valid_corr = float(plan.get("min_fraction_valid_corr", 0.1))
         self.photometric = None if photometric is None else dict(photometric)
 
-    def __call__(self, sample):
+    def draw(self, h, w):
+        """one sample's draws for an (h, w) frame -> (PhotoParams or None, FlowParams)"""
+        photo = None
+        if self.photometric is not None:
+            from . import photometric
+            photo = photometric.draw(self.photometric)
+        return photo, draw_composite(h, w, **self.composite)
+
+    def __call__(self, sample, draws=None):
         prime = sample["image_prime"]
         prime = prime if prime.dim() == 4 else prime.unsqueeze(0)
         B, _, h, w = prime.shape
+        if draws is not None and len(draws) != B:
+            raise RuntimeError(f"flowsynth.WarpSupervision: {len(draws)} sets of draws for {B} samples")
         if self.photometric is None:
-            params = [draw_composite(h, w, **self.composite) for _ in range(B)]
+            params = [draw_composite(h, w, **self.composite) for _ in range(B)] if draws is None else [d[1] for d in draws]
         else:
             from . import photometric
             if not (prime.is_cuda and prime.dtype == torch.uint8):
                 raise RuntimeError("flowsynth.WarpSupervision: with a photometric plan image_prime must be the uint8 (B, 3, h, w) "
                                    "HIP (cuda:N) tensor the chain starts from")
-            photo, params = [], []
-            for _ in range(B):
-                photo.append(photometric.draw(self.photometric))
-                params.append(draw_composite(h, w, **self.composite))
+            draws = [self.draw(h, w) for _ in range(B)] if draws is None else draws
+            photo, params = [d[0] for d in draws], [d[1] for d in draws]
             prime = photometric.apply(prime, photo)
         img, flow, mask = synthesize(prime, params, self.crop, self.min_fraction_valid_corr)
         crop = (lambda x: x) if self.crop is None else (lambda x: center_crop(x, self.crop).contiguous())

@@ -1,18 +1,20 @@
 """refign_amd/run.py -- the reference's `python tools/run.py fit | validate | test | predict --config X`, from dataset folders:
 
     python -m refign_amd.run {fit,validate,test,predict} --config X --data_dir D [--ckpt_path P] [--save_dir S]
-                             [--set dotted.key=value ...]
+                             [--set dotted.key=value ...] [--graph_step]
 
 `--set` edits the loaded YAML before anything is built; the value is parsed by yaml.safe_load (`--set trainer.precision=16`,
 `--set model.init_args.backbone.init_args.pretrained=null`, `--set data.init_args.batch_size=2`).  The reference's
 `--trainer.*` / `--model.*` flags of LightningCLI are not reproduced: `--set trainer.precision=16` is the equivalent.
 The model comes from config.build_model, the Trainer from config.trainer_kwargs / trainer_logging / trainer_gradients /
-trainer_deterministic, the batches from datamodule.SegmentationDataModule; the run is seeded as Lightning's seed_everything
-seeds it (`seed_everything:` of the YAML: python's random, numpy, torch).
+trainer_deterministic, the batches from datamodule.SegmentationDataModule -- or, when the model is the matcher
+(AlignmentModel: configs/megadepth/uawarpc_*.yaml), from datamodule.MatchingDataModule; the run is seeded as Lightning's
+seed_everything seeds it (`seed_everything:` of the YAML: python's random, numpy, torch).  --graph_step is
+Trainer(graph_step=True): the matcher's training step replayed from one hipGraph (a ValueError for the UDA model).
   fit        Trainer.fit over train_batches() with the `val` loaders; checkpoints (`last.ckpt`) go to --save_dir, or to
              `checkpoints` under the TensorBoard logger's directory, or to ./checkpoints
   validate / test / predict   the split's loaders; predict writes under --save_dir (default: the current directory) at the data
-             set's original size
+             set's original size (the matcher has no predict: config.OutOfScopeError)
 A data set without a reader here makes the split that names it fail with config.OutOfScopeError; --datasets picks the ones
 to run (`test` of the Dark Zurich configurations: --datasets DarkZurich)."""
 import argparse
@@ -55,11 +57,13 @@ def parse_args(argv):
     p = argparse.ArgumentParser(prog="python -m refign_amd.run", description="fit / validate / test / predict from dataset folders")
     p.add_argument("command", choices=("fit", "validate", "test", "predict"))
     p.add_argument("--config", required=True, help="a configuration of the reference (YAML)")
-    p.add_argument("--data_dir", default=os.environ.get("DATA_DIR"), help="holds Cityscapes/, ACDC/, DarkZurich/ ($DATA_DIR)")
+    p.add_argument("--data_dir", default=os.environ.get("DATA_DIR"),
+                   help="holds Cityscapes/, ACDC/, DarkZurich/; for the matcher MegaDepth/, RobotCarMatching/ ($DATA_DIR)")
     p.add_argument("--ckpt_path", default=None, help="a checkpoint of Trainer.save_checkpoint (or Lightning's layout) to start from")
     p.add_argument("--save_dir", default=None)
     p.add_argument("--set", dest="edits", action="append", default=[], metavar="dotted.key=value")
     p.add_argument("--datasets", nargs="+", default=None, help="the evaluation sections to run (default: all)")
+    p.add_argument("--graph_step", action="store_true", help="Trainer(graph_step=True): the matcher's step from one hipGraph")
     args = p.parse_args(argv)
     if not args.data_dir:
         p.error("--data_dir (or $DATA_DIR) is required")
@@ -69,7 +73,8 @@ def parse_args(argv):
 def main(argv=None, handles=None):
     """-> what the loop returns: fit's [(global_step, metrics)], validate's / test's metrics, predict's number of files.
     handles (a dict): receives `trainer` and `datamodule`, which are then left open for the caller to close."""
-    from .datamodule import SegmentationDataModule
+    from .alignment_model import AlignmentModel
+    from .datamodule import MatchingDataModule, SegmentationDataModule
     from .trainer import Trainer
     args = parse_args(sys.argv[1:] if argv is None else argv)
     cfg = apply_set(config.load_config(args.config), args.edits)
@@ -83,8 +88,9 @@ def main(argv=None, handles=None):
     kw = config.trainer_kwargs(cfg)
     logging = config.trainer_logging(cfg)
     trainer = Trainer(model, sync_batchnorm=kw["sync_batchnorm"], precision=kw["precision"], ckpt_path=args.ckpt_path,
-                      deterministic=config.trainer_deterministic(cfg), **logging, **config.trainer_gradients(cfg))
-    dm = SegmentationDataModule(cfg, args.data_dir, device)
+                      deterministic=config.trainer_deterministic(cfg), graph_step=args.graph_step, **logging,
+                      **config.trainer_gradients(cfg))
+    dm = (MatchingDataModule if isinstance(model, AlignmentModel) else SegmentationDataModule)(cfg, args.data_dir, device)
     try:
         if args.command == "fit":
             ckpt_dir = args.save_dir or os.path.join(getattr(logging["logger"], "log_dir", None) or ".", "checkpoints")
