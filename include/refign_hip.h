@@ -34,7 +34,8 @@ extern "C" {
  *    the transpose-cast table holds rfn_multi_transpose_tile() x rfn_multi_transpose_tile() tiles (64; 32 before).
  * 4: new entry points, none changed: rfn_attn32_fwd / rfn_attn32_bwd (fp32 attention), rfn_split3_bf16 / rfn_split3_cat_bf16
  *    (operands of the split-bf16 products), rfn_ffn_fc1_dw_gelu_bf16 (fused Mix-FFN front half).
- * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed.  Added since, none changed: rfn_kv_path. */
+ * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed.  Added since, none changed: rfn_kv_path,
+ *    rfn_hrda_merge_slide / rfn_hrda_fuse_crop_fwd / rfn_hrda_fuse_crop_bwd. */
 #define RFN_ABI_VERSION 5
 
 typedef void* rfn_stream_t; /* hipStream_t */
@@ -995,6 +996,42 @@ int rfn_corr_bwd_gather_f32(const float* in1, const float* in2, const float* gra
                             float* grad_in2, int B, int C, int iH, int iW, int kH, int kW, int patchH, int patchW,
                             int padH, int padW, int dilH, int dilW, int dpH, int dpW, int dH, int dW,
                             rfn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The HRDA logit merge at the end of the decode head (models/hrda.py:139-235) in one kernel per direction
+ * (csrc/hrdatail.hip).  a: scale-attention logits BEFORE the sigmoid and lr: low-resolution class logits, both
+ * (n, K, h, w); hr: class logits of the high-resolution crop(s), (., K, hc, wc); up2 = bilinear x2, align_corners =
+ * False.  Every operand comes with a HOST array of its four element strides (n, K, rows, cols): the decode head's
+ * channels-last views of padded buffers are read in place.  dtype of a / lr / hr: 1 (bf16) only, the step's autocast: the
+ * forward rounds every element-wise step to bf16 as the unfused chain under autocast stores it and blends in fp32 (ATen's
+ * operand order), so that out -- fp32, dense channels-last (n, 2h, 2w, K) -- is that chain's, bit for bit (fp32 operands
+ * would leave the blend's fma choice visible: RFN_EINVAL, the caller keeps them on the chain).  No atomics anywhere:
+ * deterministic with or without the flag.
+ *
+ * rfn_hrda_merge_slide (teacher / eval, gradient-free): hr is crop-major (nb * nl, K, hc, wc); boxes: HOST array of nb x
+ * (y1, y2, x1, x2) on the (2h, 2w) grid.  out = up2(sigmoid(a)) * (sum_i crop_i / count) + up2((1 - sigmoid(a)) * lr), the
+ * crop sum in box order.  *accepted <- 0 and NOTHING is launched when the problem is outside the kernel's domain (more than 16
+ * boxes, a box that is not a whole crop inside the grid, boxes that leave a pixel of (2h, 2w) uncovered or do not reach its
+ * last row / column): the caller takes the unfused path.  *accepted <- 1 otherwise.
+ *
+ * rfn_hrda_fuse_crop_fwd / _bwd (student): ONE random crop whose offset is DEVICE data, off = int64 (oy, ox) in image pixels,
+ * read by the kernels (a captured graph follows the host's refresh).  att = sigmoid(a) * mask, mask = ones on rows
+ * [oy / div_mask, oy / div_mask + mh) and columns [ox / div_mask, ox / div_mask + mw) of the (h, w) grid;
+ * out = up2(att) * insert(hr) + up2((1 - att) * lr), insert = hr (n, K, hc, wc) written at (oy / div_ins, ox / div_ins) of a
+ * zero (2h, 2w) map.  _bwd: grad_out fp32 with its strides -> grad_a, grad_lr (n, h, w, K) and grad_hr (n, hc, wc, K), dense
+ * channels-last in bf16, every element WRITTEN (nothing to zero, nothing accumulated); one gather launch, fp64
+ * arithmetic, sigmoid and up2(att) recomputed.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_hrda_merge_slide(const void* a, const long* a_strides, const void* lr, const long* lr_strides, const void* hr,
+                         const long* hr_strides, const int* boxes, int nb, float* out, int nl, int K, int h, int w, int hc, int wc,
+                         int dtype, int* accepted, rfn_stream_t stream);
+int rfn_hrda_fuse_crop_fwd(const void* a, const long* a_strides, const void* lr, const long* lr_strides, const void* hr,
+                           const long* hr_strides, const long* off, float* out, int n, int K, int h, int w, int hc, int wc, int mh,
+                           int mw, int div_mask, int div_ins, int dtype, rfn_stream_t stream);
+int rfn_hrda_fuse_crop_bwd(const float* grad_out, const long* g_strides, const void* a, const long* a_strides, const void* lr,
+                           const long* lr_strides, const void* hr, const long* hr_strides, const long* off, void* grad_a,
+                           void* grad_lr, void* grad_hr, int n, int K, int h, int w, int hc, int wc, int mh, int mw, int div_mask,
+                           int div_ins, int dtype, rfn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from . import f8 as _f8
 from . import linear as _linear
-from . import determinism, mfma
+from . import determinism, hrdatail, mfma
 from ._tensor import const_tensor
 from ._tensor import DTYPE_CODE as _CE_DT          # (the name the GPU tests read the codes under)
 from .align import BaseHead
@@ -752,6 +752,7 @@ def hrda_backbone(self, head_os: int, is_teacher: bool = False) -> Callable:
 
 
 _REJOIN = True
+_HRDA_TAIL_FUSED = True     # the logit merge at the end of hrda_head in one kernel per direction (csrc/hrdatail.hip, hrdatail.py)
 
 
 def _rejoin(a, b):
@@ -782,18 +783,23 @@ def hrda_head(self, hrda_scale_attention: nn.Module, head_os: int, is_teacher: b
         @wraps(fn)
         def inner(inp, *args, **kwargs):
             lr_feats, hr_feats, boxes = inp
-            att = torch.sigmoid(hrda_scale_attention(lr_feats))
+            att_logits = hrda_scale_attention(lr_feats)
             nl, nh = lr_feats[0].shape[0], hr_feats[0].shape[0]
             seg = fn([_rejoin(*p) for p in zip(lr_feats, hr_feats)], *args, **kwargs)
             lr_seg, hr_seg = torch.split(seg, [nl, nh])
             if self.training and not is_teacher and isinstance(boxes[0], DeviceBox):
                 box = boxes[0]
+                fused = hrdatail.fuse_crop(att_logits, lr_seg, hr_seg, box, head_os) if _HRDA_TAIL_FUSED else None
+                if fused is not None:
+                    return fused, defer_logits(hr_seg, (box.h, box.w), fused_ce_consumer(self)), box
+                att = torch.sigmoid(att_logits)
                 att = att * box.mask(lr_seg.shape[2], lr_seg.shape[3], 2.0 * head_os, lr_seg)
                 up_lr = interpolate_bilinear((1 - att) * lr_seg, scale_factor=2)
                 up_att = interpolate_bilinear(att, scale_factor=2)
                 inserted = box.insert(hr_seg, up_lr.shape[2:], head_os)
                 return up_att * inserted + up_lr, defer_logits(hr_seg, (box.h, box.w), fused_ce_consumer(self)), box
             if self.training and not is_teacher:
+                att = torch.sigmoid(att_logits)
                 box = boxes[0]
                 crop_size = (box[1] - box[0], box[3] - box[2])
                 mask = lr_seg.new_zeros([nl, 1, *lr_seg.shape[2:]])
@@ -807,10 +813,14 @@ def hrda_head(self, hrda_scale_attention: nn.Module, head_os: int, is_teacher: b
                 inserted[:, :, sy, sx] = hr_seg
                 hr_logits = defer_logits(hr_seg, crop_size, fused_ce_consumer(self))
                 return up_att * inserted + up_lr, hr_logits, box
-            up_lr = F.interpolate((1 - att) * lr_seg, scale_factor=2, mode='bilinear', align_corners=False)
             # overlap-average the sliding crops (the reference rescales `hr_boxes` in place, hrda.py:207-208)
             for i in range(len(boxes)):
                 boxes[i] = scale_box(boxes[i], head_os)
+            fused = hrdatail.merge_slide(att_logits, lr_seg, hr_seg, boxes) if _HRDA_TAIL_FUSED else None
+            if fused is not None:
+                return fused
+            att = torch.sigmoid(att_logits)
+            up_lr = F.interpolate((1 - att) * lr_seg, scale_factor=2, mode='bilinear', align_corners=False)
             Hh, Ww = max(b[1] for b in boxes), max(b[3] for b in boxes)
             preds = lr_seg.new_zeros((nl, self.num_classes, Hh, Ww))
             count = lr_seg.new_zeros((nl, 1, Hh, Ww))
