@@ -35,7 +35,8 @@ extern "C" {
  * 4: new entry points, none changed: rfn_attn32_fwd / rfn_attn32_bwd (fp32 attention), rfn_split3_bf16 / rfn_split3_cat_bf16
  *    (operands of the split-bf16 products), rfn_ffn_fc1_dw_gelu_bf16 (fused Mix-FFN front half).
  * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed.  Added since, none changed: rfn_kv_path,
- *    rfn_hrda_merge_slide / rfn_hrda_fuse_crop_fwd / rfn_hrda_fuse_crop_bwd. */
+ *    rfn_hrda_merge_slide / rfn_hrda_fuse_crop_fwd / rfn_hrda_fuse_crop_bwd, rfn_bn_apply_fwd_drop, rfn_bn_stats_bwd_ld /
+ *    rfn_bn_stats_bwd_det_ld / rfn_bn_apply_bwd_ld, rfn_upsample_concat_nhwc_bwd_sum. */
 #define RFN_ABI_VERSION 5
 
 typedef void* rfn_stream_t; /* hipStream_t */
@@ -48,7 +49,7 @@ const char* rfn_last_error(void);
  * every entry point whose result depends on the arrival order of floating-point atomics returns RFN_ENONDET
  * instead of launching: rfn_gemm_tn (accumulate == 1, or a bias sum with accumulate == 0), rfn_gemm_tn_grouped,
  * rfn_conv2d_nhwc_wgrad (a bias sum with accumulate != 2), rfn_attn_bwd_dkv, rfn_attn32_bwd (more than one query
- * chunk), rfn_bn_stats_fwd / _bwd (and rfn_bn_train_fwd / _bwd), the depthwise statistics entry points
+ * chunk), rfn_bn_stats_fwd / _bwd / _bwd_ld (and rfn_bn_train_fwd / _bwd), the depthwise statistics entry points
  * (rfn_dwconv3x3_nhwc_stats, _nhwc_fwd_stats), rfn_dacs_mix_jitter (when a jitter needs
  * the image mean), rfn_upsample_ce, rfn_warp_bwd_f32 and the generic (atomic) form of rfn_corr_bwd_f32 / _f64 (their
  * deterministic forms, rfn_warp_bwd_det_f32 and rfn_corr_bwd_gather_f32, are at the end of this header).
@@ -377,6 +378,12 @@ int rfn_upsample_concat_nhwc(const void* src0, const void* src1, const void* src
 int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs,
                                  const int* ws, const int* cs, int nlev, int n, int H, int W, int dtype,
                                  rfn_stream_t stream);
+/* The same on the sum of the first `ngrad` (1 .. 4) of grad_out0 .. 3 -- gradients of the concatenation from several consumers
+ * (the four branches of the ASPP), same shape, dtype and layout, 16-byte bases: added in fp32 at every tap in that order and
+ * rounded once, instead of by element-wise additions in front of the gather.  No atomics. */
+int rfn_upsample_concat_nhwc_bwd_sum(const void* grad_out0, const void* grad_out1, const void* grad_out2, const void* grad_out3,
+                                     int ngrad, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs, const int* ws,
+                                     const int* cs, int nlev, int n, int H, int W, int dtype, rfn_stream_t stream);
 
 /* Token map (B, H*W, C) -> non-overlapping r x r patches (B*(H/r)*(W/r), r*r*C) with (ry, rx, c) fastest (inverse = 0),
  * or back (inverse = 1; a ragged border of the token map is NOT written -- zero it first): gather / scatter around the
@@ -565,6 +572,22 @@ int rfn_bn_stats_bwd(const void* x, const void* grad_y, const double* fwd_sums, 
                      float* bwd_sums, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream);
 int rfn_bn_apply_bwd(const void* x, const void* grad_y, const double* fwd_sums, const float* bwd_sums, const float* gamma,
                      const float* beta, void* grad_x, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream);
+/* Dropout2d of the decode heads (daformer.py:224, segformer.py:108) folded into the passes, and grad_y read in place from a
+ * channel slice.  drop: (T / rows_per_sample, C) multipliers in the activation dtype, 16-byte base.
+ *   rfn_bn_apply_fwd_drop   y = round16(relu?(bn(x))) * drop[t / rows_per_sample][c]: bit for bit the 16-bit result followed
+ *                           by a 16-bit multiply; ld_y as rfn_bn_apply_fwd_ld, 0 = C
+ *   rfn_bn_stats_bwd_ld, rfn_bn_apply_bwd_ld (and rfn_bn_stats_bwd_det_ld further down)
+ *                           the backward passes with grad_y at a row pitch of ld_g elements (0 = C; >= C, % 8, 16-byte base)
+ *                           and, drop != NULL, g = round16(grad_y * drop[t / rows_per_sample][c]) as it is loaded */
+int rfn_bn_apply_fwd_drop(const void* x, const float* gamma, const float* beta, void* y, long ld_y, const double* sums,
+                          float* running_mean, float* running_var, const void* drop, long rows_per_sample, long T, int C,
+                          float eps, float momentum, int relu, int dtype, rfn_stream_t stream);
+int rfn_bn_stats_bwd_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample,
+                        const double* fwd_sums, const float* gamma, const float* beta, float* bwd_sums, long T, int C, float eps,
+                        int relu, int dtype, rfn_stream_t stream);
+int rfn_bn_apply_bwd_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample,
+                        const double* fwd_sums, const float* bwd_sums, const float* gamma, const float* beta, void* grad_x, long T,
+                        int C, float eps, int relu, int dtype, rfn_stream_t stream);
 int rfn_bn_train_fwd(const void* x, const float* gamma, const float* beta, void* y, double* sums, float* running_mean,
                      float* running_var, long T, int C, float eps, float momentum, int relu, int dtype,
                      rfn_stream_t stream);
@@ -771,6 +794,7 @@ int rfn_attn_fwd_f8(const void* q8, long q_batch_stride, long q_row_stride, cons
  * stands in for plus a workspace for the partial sums; results agree with the atomic form to rounding and are
  * bit-identical from launch to launch.
  *   rfn_bn_stats_fwd_det / _bwd_det        BatchNorm statistics; workspace rfn_bn_stats_det_workspace_bytes(T, C)
+ *   rfn_bn_stats_bwd_det_ld                the same for grad_y at a row pitch and / or with the Dropout2d multiplier
  *   rfn_dwconv3x3_nhwc_fwd_stats_det,
  *   rfn_dwconv3x3_nhwc_stats_det           depthwise 3x3 (+ statistics of its result); workspace
  *                                          rfn_dwconv3x3_stats_det_workspace_bytes(B, H, W, C, dilation)
@@ -790,6 +814,9 @@ unsigned long rfn_bn_stats_det_workspace_bytes(long T, int C);
 int rfn_bn_stats_fwd_det(const void* x, double* sums, void* workspace, long T, int C, int dtype, rfn_stream_t stream);
 int rfn_bn_stats_bwd_det(const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
                          float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, rfn_stream_t stream);
+int rfn_bn_stats_bwd_det_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample,
+                            const double* fwd_sums, const float* gamma, const float* beta, float* bwd_sums, void* workspace, long T,
+                            int C, float eps, int relu, int dtype, rfn_stream_t stream);
 unsigned long rfn_dwconv3x3_stats_det_workspace_bytes(int B, int H, int W, int C, int dilation);
 int rfn_dwconv3x3_nhwc_fwd_stats_det(const void* x, const float* weight, const float* bias, void* y, double* sums, void* workspace,
                                      int B, int H, int W, int C, int dilation, int dtype, rfn_stream_t stream);

@@ -126,8 +126,14 @@ def _stats_fwd(xh, sums):
     _lib.call("rfn_bn_stats_fwd", xh.device, ptr(xh), ptr(sums), T, C, _DT16[xh.dtype])
 
 
-def _apply_fwd(xh, weight, bias, y, sums, bn, relu):
+def _apply_fwd(xh, weight, bias, y, sums, bn, relu, drop=None):
+    # drop: (B, C) Dropout2d multipliers in xh's dtype, folded into the store (csrc/bn.hip BnExt)
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
+    if drop is not None:
+        _lib.call("rfn_bn_apply_fwd_drop", xh.device, ptr(xh), ptr(weight), ptr(bias), ptr(y), y.stride(-2), ptr(sums),
+                  ptr(bn.running_mean), ptr(bn.running_var), ptr(drop), T // drop.shape[0], T, C, float(bn.eps),
+                  float(bn.momentum), int(relu), _DT16[xh.dtype])
+        return
     if y.stride(-2) != C:                                  # a channel slice of a wider channels-last tensor
         _lib.call("rfn_bn_apply_fwd_ld", xh.device, ptr(xh), ptr(weight), ptr(bias), ptr(y), y.stride(-2), ptr(sums),
                   ptr(bn.running_mean), ptr(bn.running_var), T, C, float(bn.eps), float(bn.momentum), int(relu),
@@ -137,73 +143,150 @@ def _apply_fwd(xh, weight, bias, y, sums, bn, relu):
               ptr(bn.running_var), T, C, float(bn.eps), float(bn.momentum), int(relu), _DT16[xh.dtype])
 
 
-def _stats_bwd(xh, gy, sums, weight, bias, bsums, eps, relu):
+def _stats_bwd(xh, gy, sums, weight, bias, bsums, eps, relu, drop=None):
+    # gy: dense, or a channel slice of a wider channels-last tensor (read in place by row pitch); drop: as _apply_fwd, on gy
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
+    ext = drop is not None or gy.stride(-2) != C
+    rps = T // drop.shape[0] if drop is not None else 1
     if determinism.enabled():
         ws = workspace(_lib.load_library().rfn_bn_stats_det_workspace_bytes(T, C), xh.device)
+        if ext:
+            _lib.call("rfn_bn_stats_bwd_det_ld", xh.device, ptr(xh), ptr(gy), gy.stride(-2), ptr(drop), rps, ptr(sums), ptr(weight),
+                      ptr(bias), ptr(bsums), ptr(ws), T, C, eps, int(relu), _DT16[xh.dtype])
+            return
         _lib.call("rfn_bn_stats_bwd_det", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), ptr(ws),
                   T, C, eps, int(relu), _DT16[xh.dtype])
+        return
+    if ext:
+        _lib.call("rfn_bn_stats_bwd_ld", xh.device, ptr(xh), ptr(gy), gy.stride(-2), ptr(drop), rps, ptr(sums), ptr(weight),
+                  ptr(bias), ptr(bsums), T, C, eps, int(relu), _DT16[xh.dtype])
         return
     _lib.call("rfn_bn_stats_bwd", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(weight), ptr(bias), ptr(bsums), T, C, eps,
               int(relu), _DT16[xh.dtype])
 
 
-def _apply_bwd(xh, gy, sums, bsums, weight, bias, gx, eps, relu):
+def _apply_bwd(xh, gy, sums, bsums, weight, bias, gx, eps, relu, drop=None):
     T, C = xh.numel() // xh.shape[-1], xh.shape[-1]
+    if drop is not None or gy.stride(-2) != C:
+        _lib.call("rfn_bn_apply_bwd_ld", xh.device, ptr(xh), ptr(gy), gy.stride(-2), ptr(drop),
+                  T // drop.shape[0] if drop is not None else 1, ptr(sums), ptr(bsums), ptr(weight), ptr(bias), ptr(gx), T, C,
+                  eps, int(relu), _DT16[xh.dtype])
+        return
     _lib.call("rfn_bn_apply_bwd", xh.device, ptr(xh), ptr(gy), ptr(sums), ptr(bsums), ptr(weight), ptr(bias), ptr(gx), T, C,
               eps, int(relu), _DT16[xh.dtype])
 
 
+def _kw(drop):
+    """The launchers above keep their positional signatures (tests put restatements in their place): what is new is a keyword
+    argument, passed only when it is in use."""
+    return {} if drop is None else {"drop": drop}
+
+
+def _forward_passes(xh, weight, bias, bn, relu, group, y, sums=None, drop=None):
+    """Statistics (unless the producer of xh left them), their exchange, the apply pass into y, num_batches_tracked; -> (sums, comm)."""
+    if sums is None:                                        # (else: the producer of xh left them, csrc/dwconv.hip STATS)
+        sums = torch.empty(2 * xh.shape[-1] + 1, dtype=torch.float64, device=xh.device)     # fp64: csrc/bn.hip header
+        _stats_fwd(xh, sums)
+    comm = _exchange_comm(bn) if group is not None else None
+    if group is not None:
+        _all_reduce(sums, group, comm)
+    _apply_fwd(xh, weight, bias, y, sums, bn, relu, **_kw(drop))
+    bn.num_batches_tracked.add_(1)
+    return sums, comm
+
+
+def _row_pitch_ok(g, C):
+    """`g` (B, H, W, C) is dense or a channel slice of a contiguous (B, H, W, C') tensor that the kernels can read in place."""
+    p = g.stride(-2)
+    return (g.stride(-1) == 1 and p % 8 == 0 and p >= C and g.stride(-3) == g.shape[-2] * p
+            and g.stride(0) == g.shape[1] * g.shape[2] * p and g.data_ptr() % 16 == 0)
+
+
+def _backward_passes(xh, sums, weight, bias, gy, eps, relu, group, comm, needs, drop=None):
+    """Both backward passes of one BatchNorm on gy (dense or pitched); parameter gradients go into the flat gradient buffer
+    where there is one; -> (grad_x, grad_weight, grad_bias), None where not needed or routed."""
+    C = xh.shape[-1]
+    if gy.dtype != xh.dtype:
+        gy = gy.to(xh.dtype)
+    if not gy.is_contiguous() and not _row_pitch_ok(gy, C):
+        gy = gy.contiguous()
+    gx = torch.empty_like(xh)
+    bsums = torch.empty((2, C), dtype=torch.float32, device=xh.device)
+    _stats_bwd(xh, gy, sums, weight, bias, bsums, eps, relu, **_kw(drop))
+    local = bsums
+    if group is not None:                                   # parameter gradients: this replica's sums
+        local = bsums.clone()
+        _all_reduce(bsums, group, comm)
+    _apply_bwd(xh, gy, sums, bsums, weight, bias, gx, eps, relu, **_kw(drop))
+    gw = gb = None
+    if needs[1]:
+        sink = grad_sink(weight)
+        if sink is not None:
+            sink.add_(local[1])
+        else:
+            gw = local[1].to(weight.dtype)
+    if needs[2]:
+        sink = grad_sink(bias)
+        if sink is not None:
+            sink.add_(local[0])
+        else:
+            gb = local[0].to(bias.dtype)
+    return (gx if needs[0] else None), gw, gb
+
+
 class _BNActTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xh, weight, bias, bn, relu, group, out=None, sums=None):
+    def forward(ctx, xh, weight, bias, bn, relu, group, out=None, sums=None, drop=None):
         # xh: (B, H, W, C) contiguous, 16-bit; out (gradient-free callers): where the result goes -- (B, H, W, C) with the
-        # strides of a channel slice of a contiguous (B, H, W, C') tensor
-        C = xh.shape[-1]
+        # strides of a channel slice of a contiguous (B, H, W, C') tensor; drop: (B, C) Dropout2d multipliers (no gradient)
         y = torch.empty_like(xh) if out is None else out
-        if sums is None:                                    # (else: the producer of xh left them, csrc/dwconv.hip STATS)
-            sums = torch.empty(2 * C + 1, dtype=torch.float64, device=xh.device)     # fp64: csrc/bn.hip header
-            _stats_fwd(xh, sums)
-        comm = _exchange_comm(bn) if group is not None else None
-        if group is not None:
-            _all_reduce(sums, group, comm)
-        _apply_fwd(xh, weight, bias, y, sums, bn, relu)
-        bn.num_batches_tracked.add_(1)
+        sums, comm = _forward_passes(xh, weight, bias, bn, relu, group, y, sums, drop)
         if any(ctx.needs_input_grad[:3]):
             ctx.save_for_backward(xh, sums, weight, bias)
-            ctx.eps, ctx.relu, ctx.group, ctx.comm = float(bn.eps), relu, group, comm
+            ctx.eps, ctx.relu, ctx.group, ctx.comm, ctx.drop = float(bn.eps), relu, group, comm, drop
         return y
 
     @staticmethod
     def backward(ctx, gy):
         xh, sums, weight, bias = ctx.saved_tensors
-        C = xh.shape[-1]
-        if gy.dtype != xh.dtype:
-            gy = gy.to(xh.dtype)
         if not gy.is_contiguous():
             gy = gy.contiguous()
-        gx = torch.empty_like(xh)
-        bsums = torch.empty((2, C), dtype=torch.float32, device=xh.device)
-        _stats_bwd(xh, gy, sums, weight, bias, bsums, ctx.eps, ctx.relu)
-        local = bsums
-        if ctx.group is not None:                           # parameter gradients: this replica's sums
-            local = bsums.clone()
-            _all_reduce(bsums, ctx.group, ctx.comm)
-        _apply_bwd(xh, gy, sums, bsums, weight, bias, gx, ctx.eps, ctx.relu)
-        gw = gb = None
-        if ctx.needs_input_grad[1]:
-            sink = grad_sink(weight)
-            if sink is not None:
-                sink.add_(local[1])
-            else:
-                gw = local[1].to(weight.dtype)
-        if ctx.needs_input_grad[2]:
-            sink = grad_sink(bias)
-            if sink is not None:
-                sink.add_(local[0])
-            else:
-                gb = local[0].to(bias.dtype)
-        return (gx if ctx.needs_input_grad[0] else None), gw, gb, None, None, None, None, None
+        return _backward_passes(xh, sums, weight, bias, gy, ctx.eps, ctx.relu, ctx.group, ctx.comm, ctx.needs_input_grad,
+                                ctx.drop) + (None,) * 6
+
+
+class _BNActCat(torch.autograd.Function):
+    """act(bn_i(x_i)) of several BatchNorms written side by side into ONE (B, H, W, sum C_i) tensor: the branches of the student's
+    ASPP (daformer.py:110-118) without the torch.cat, and -- in the backward -- without copies of the channel slices of the
+    concatenation's gradient, which the passes read in place by row pitch.  tensors = (x_0, weight_0, bias_0, x_1, ...)."""
+
+    @staticmethod
+    def forward(ctx, bns, relu, *tensors):
+        xs, ws, bs = tensors[0::3], tensors[1::3], tensors[2::3]
+        cs = [x.shape[-1] for x in xs]
+        cat = torch.empty(xs[0].shape[:-1] + (sum(cs),), dtype=xs[0].dtype, device=xs[0].device)
+        saved, meta, o = [], [], 0
+        for x, w, b, bn, c in zip(xs, ws, bs, bns, cs):
+            group = sync_group(bn)
+            sums, comm = _forward_passes(x, w, b, bn, relu, group, cat[..., o:o + c])
+            saved += [x, sums, w, b]
+            meta.append((float(bn.eps), group, comm, o, c))
+            o += c
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(*saved)
+            ctx.relu, ctx.meta = relu, meta
+        return cat
+
+    @staticmethod
+    def backward(ctx, gcat):
+        if not gcat.is_contiguous():
+            gcat = gcat.contiguous()
+        out = [None, None]
+        for i, (eps, group, comm, o, c) in enumerate(ctx.meta):
+            x, sums, w, b = ctx.saved_tensors[4 * i:4 * i + 4]
+            out += _backward_passes(x, sums, w, b, gcat[..., o:o + c], eps, ctx.relu, group, comm,
+                                    ctx.needs_input_grad[2 + 3 * i:5 + 3 * i])
+        return tuple(out)
 
 
 def slice_out_ok(out, xshape):
@@ -216,10 +299,7 @@ def slice_out_ok(out, xshape):
     return out.stride(2) == W * p and out.stride(0) == H * W * p and out.data_ptr() % 16 == 0
 
 
-def bn_act_train(x, bn, relu, dtype, out=None, sums=None):
-    """act(bn(x)) with batch statistics, `relu`: False / 0 none, True / 1 ReLU, 3 LeakyReLU(0.1) (the activation codes of
-    the GEMM entry points); x NCHW-shaped (any memory format, converted to channels-last 16-bit if it is
-    not already); returns an NCHW-shaped channels-last tensor."""
+def _operands(x, bn, dtype):
     xh = x.permute(0, 2, 3, 1)
     if xh.dtype != dtype:
         xh = xh.to(dtype)
@@ -227,10 +307,39 @@ def bn_act_train(x, bn, relu, dtype, out=None, sums=None):
         xh = xh.contiguous()
     w = bn.weight if bn.weight.dtype == torch.float32 else bn.weight.float()
     b = bn.bias if bn.bias.dtype == torch.float32 else bn.bias.float()
+    return xh, w, b
+
+
+def dropout2d_noise(x_like, channels, dtype, p):
+    """The (B, C, 1, 1) multipliers of Dropout2d(p) in training mode, drawn with the two calls ATen's feature_dropout makes
+    (Dropout.cpp: make_feature_noise, bernoulli_, div_), so that the generator is consumed as by the module -- eagerly and
+    under graph capture; what the kernels fold in is only the multiply (bn_act_train(drop=...))."""
+    return torch.empty((x_like.shape[0], channels, 1, 1), dtype=dtype, device=x_like.device).bernoulli_(1 - p).div_(1 - p)
+
+
+def bn_act_train(x, bn, relu, dtype, out=None, sums=None, drop=None):
+    """act(bn(x)) with batch statistics, `relu`: False / 0 none, True / 1 ReLU, 3 LeakyReLU(0.1) (the activation codes of
+    the GEMM entry points); x NCHW-shaped (any memory format, converted to channels-last 16-bit if it is
+    not already); returns an NCHW-shaped channels-last tensor.  drop: (B, C, 1, 1) Dropout2d multipliers in `dtype`
+    (dropout2d_noise): the result is the 16-bit act(bn(x)) times drop, bit for bit what the multiply after it gave."""
+    xh, w, b = _operands(x, bn, dtype)
+    if drop is not None:
+        if tuple(drop.shape) != (x.shape[0], x.shape[1], 1, 1) or drop.dtype != dtype or not drop.is_contiguous() or drop.requires_grad:
+            raise RuntimeError("bn_act_train(drop=...): (B, C, 1, 1) multipliers in the compute dtype, without a gradient")
+        drop = drop.view(x.shape[0], x.shape[1])
     if out is not None:
         if torch.is_grad_enabled() and (xh.requires_grad or w.requires_grad) or out.dtype != dtype \
                 or not slice_out_ok(out, x.shape):
             raise RuntimeError("bn_act_train(out=...): gradient-free calls into a channels-last channel slice only")
-        _BNActTrain.apply(xh, w, b, bn, relu, sync_group(bn), out.permute(0, 2, 3, 1), sums)
+        _BNActTrain.apply(xh, w, b, bn, relu, sync_group(bn), out.permute(0, 2, 3, 1), sums, drop)
         return out
-    return _BNActTrain.apply(xh, w, b, bn, relu, sync_group(bn), None, sums).permute(0, 3, 1, 2)
+    return _BNActTrain.apply(xh, w, b, bn, relu, sync_group(bn), None, sums, drop).permute(0, 3, 1, 2)
+
+
+def bn_act_train_cat(xs, bns, relu, dtype):
+    """torch.cat([bn_act_train(x, bn, relu, dtype) for x, bn in zip(xs, bns)], 1) under autograd without the concatenation pass
+    and without copies of its gradient's channel slices (_BNActCat); every x NCHW-shaped with the same (B, H, W)."""
+    tensors = []
+    for x, bn in zip(xs, bns):
+        tensors += _operands(x, bn, dtype)
+    return _BNActCat.apply(list(bns), relu, *tensors).permute(0, 3, 1, 2)

@@ -42,13 +42,48 @@ __device__ __forceinline__ void norm_consts(const double* sums, int C, int c, do
   rstd = rsqrtf(batch_var(sums, C, c, invT, mean) + eps);
 }
 
+// The operands of the `_ext` kernels (the decode heads' Dropout2d folded in, and grad_y read in place from a channel slice):
+//   drop  (B, C) multipliers in the activation dtype, sample = row / rps; nullptr: none.  Forward: y = round16(act(bn(x))) * drop,
+//         rounded again by the store -- the bits of the 16-bit y followed by ATen's 16-bit mul.  Backward: g = round16(g * drop)
+//         as it is loaded -- what that mul's backward stored.
+//   ldg   row pitch of grad_y in elements (C: dense).
+struct BnExt {
+  const uint16_t* drop;
+  long rps, ldg;
+};
+
+// sample index of a row, kept by addition (rows advance by the grid's stride, which may exceed a sample in small launches)
+struct SampleCursor {
+  long b, rem;
+  __device__ __forceinline__ SampleCursor(long t, long rps) : b(t / rps), rem(t % rps) {}
+  __device__ __forceinline__ void advance(long by, long rps) {
+    rem += by;
+    while (rem >= rps) {
+      rem -= rps;
+      ++b;
+    }
+  }
+};
+
+// g <- round16(g * drop[b]): the gradient the dropout multiply's backward hands to BatchNorm
+template <int DT>
+__device__ __forceinline__ void drop_grad(const uint16_t* __restrict__ drop, long b, int C, int c0, float (&gv)[8]) {
+  float dv[8];
+  load8<DT>(drop + b * C + c0, dv);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) gv[i] = round_to<DT>(gv[i] * dv[i]);
+}
+
 // BWD = false: sums of x and x^2.  BWD = true: sums of g' and g' * xhat (fwd_sums give mean / rstd, gamma / beta the sign of y)
-template <int DT, bool BWD>
-__global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
-                                                       const double* __restrict__ fwd_sums, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, void* __restrict__ sums_, long T,
-                                                       int C, int cvb, float eps, int relu, float slope,
-                                                       void* __restrict__ part_ = nullptr) {
+// EXT (backward only): grad_y at a row pitch and / or multiplied by the dropout noise (BnExt)
+template <int DT, bool BWD, bool EXT>
+__device__ __forceinline__ void bn_stats_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                              const double* __restrict__ fwd_sums, const float* __restrict__ gamma,
+                                              const float* __restrict__ beta, void* __restrict__ sums_, long T,
+                                              int C, int cvb, float eps, int relu, float slope,
+                                              void* __restrict__ part_, const BnExt ext) {
+  static_assert(BWD || !EXT, "the forward statistics have no extended form");
+  const long ldg = EXT ? ext.ldg : C;
   using ST = typename std::conditional<BWD, float, double>::type;      // forward sums: doubles (header)
   ST* __restrict__ sums = (ST*)sums_;
   // deterministic form: part[gridDim.y][2 C], one row per workgroup row with plain stores (every element is written);
@@ -95,12 +130,21 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restric
     // 1.5-2.1 TB/s on the decode head's backward statistics (section 4.5 of DESIGN.md: memory-level parallelism per thread)
     const long stride = (long)gridDim.y * pl;
     long t = (long)blockIdx.y * pl + rl;
+    const bool dropped = EXT && ext.drop != nullptr;
+    SampleCursor cur(dropped ? t : 0, dropped ? ext.rps : 1);
     for (; t + 3 * stride < T; t += 4 * stride) {
       float xv[4][8], gv[4][8];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         load8<DT>(x + (t + u * stride) * C + c0, xv[u]);
-        if (BWD) load8<DT>(g + (t + u * stride) * C + c0, gv[u]);
+        if (BWD) load8<DT>(g + (t + u * stride) * ldg + c0, gv[u]);
+      }
+      if (dropped) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          drop_grad<DT>(ext.drop, cur.b, C, c0, gv[u]);
+          cur.advance(stride, ext.rps);
+        }
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) accumulate(xv[u], gv[u]);
@@ -108,7 +152,11 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restric
     for (; t < T; t += stride) {
       float xv[8], gv[8];
       load8<DT>(x + t * C + c0, xv);
-      if (BWD) load8<DT>(g + t * C + c0, gv);
+      if (BWD) load8<DT>(g + t * ldg + c0, gv);
+      if (dropped) {
+        drop_grad<DT>(ext.drop, cur.b, C, c0, gv);
+        cur.advance(stride, ext.rps);
+      }
       accumulate(xv, gv);
     }
   }
@@ -135,12 +183,32 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restric
 }
 
 template <int DT, bool BWD>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
-                                                       const double* __restrict__ fwd_sums, const float* __restrict__ bwd_sums,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       uint16_t* __restrict__ out, float* __restrict__ running_mean,
-                                                       float* __restrict__ running_var, long T, int C, int cvb, float eps,
-                                                       float momentum, int relu, float slope, long ldo) {
+__global__ __launch_bounds__(256) void bn_stats_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                                       const double* __restrict__ fwd_sums, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, void* __restrict__ sums_, long T,
+                                                       int C, int cvb, float eps, int relu, float slope,
+                                                       void* __restrict__ part_ = nullptr) {
+  bn_stats_body<DT, BWD, false>(x, g, fwd_sums, gamma, beta, sums_, T, C, cvb, eps, relu, slope, part_, BnExt{nullptr, 1, 0});
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void bn_stats_bwd_ext_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                                               const double* __restrict__ fwd_sums,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               void* __restrict__ sums_, long T, int C, int cvb, float eps,
+                                                               int relu, float slope, void* __restrict__ part_, BnExt ext) {
+  bn_stats_body<DT, true, true>(x, g, fwd_sums, gamma, beta, sums_, T, C, cvb, eps, relu, slope, part_, ext);
+}
+
+// EXT: BnExt's multiplier on the result (forward) or on grad_y (backward), grad_y at a row pitch
+template <int DT, bool BWD, bool EXT>
+__device__ __forceinline__ void bn_apply_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                              const double* __restrict__ fwd_sums, const float* __restrict__ bwd_sums,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              uint16_t* __restrict__ out, float* __restrict__ running_mean,
+                                              float* __restrict__ running_var, long T, int C, int cvb, float eps,
+                                              float momentum, int relu, float slope, long ldo, const BnExt ext) {
+  const long ldg = EXT ? ext.ldg : C;
   // ldo: row pitch of `out` in elements (C for a dense result; larger when the result is a channel slice of a wider
   // channels-last tensor -- the branches of the ASPP write straight into their concatenation, daformer.py:110-118)
   const int CV = C / 8, pl = 256 / cvb;
@@ -171,7 +239,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
       k1[i] = bwd_sums[C + c0 + i] * invT;
     }
   }
-  for (long t = (long)blockIdx.y * pl + rl; t < T; t += (long)gridDim.y * pl) {
+  const long stride = (long)gridDim.y * pl;
+  long t = (long)blockIdx.y * pl + rl;
+  const bool dropped = EXT && ext.drop != nullptr;
+  SampleCursor cur(dropped ? t : 0, dropped ? ext.rps : 1);
+  for (; t < T; t += stride) {
     float xv[8], o[8];
     load8<DT>(x + t * C + c0, xv);
     if (!BWD) {
@@ -180,9 +252,20 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
         const float z = (xv[i] - mean[i]) * rstd[i] * gm[i] + bt[i];
         o[i] = (relu && z <= 0.f) ? slope * z : z;
       }
+      if (dropped) {
+        float dv[8];
+        load8<DT>(ext.drop + cur.b * C + c0, dv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = round_to<DT>(o[i]) * dv[i];
+        cur.advance(stride, ext.rps);
+      }
     } else {
       float gv[8];
-      load8<DT>(g + t * C + c0, gv);
+      load8<DT>(g + t * ldg + c0, gv);
+      if (dropped) {
+        drop_grad<DT>(ext.drop, cur.b, C, c0, gv);
+        cur.advance(stride, ext.rps);
+      }
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float xh = (xv[i] - mean[i]) * rstd[i];
@@ -193,6 +276,28 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restric
     }
     store8<DT>(out + t * ldo + c0, o);
   }
+}
+
+template <int DT, bool BWD>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                                       const double* __restrict__ fwd_sums, const float* __restrict__ bwd_sums,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                       uint16_t* __restrict__ out, float* __restrict__ running_mean,
+                                                       float* __restrict__ running_var, long T, int C, int cvb, float eps,
+                                                       float momentum, int relu, float slope, long ldo) {
+  bn_apply_body<DT, BWD, false>(x, g, fwd_sums, bwd_sums, gamma, beta, out, running_mean, running_var, T, C, cvb, eps, momentum,
+                                relu, slope, ldo, BnExt{nullptr, 1, 0});
+}
+
+template <int DT, bool BWD>
+__global__ __launch_bounds__(256) void bn_apply_ext_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ g,
+                                                           const double* __restrict__ fwd_sums, const float* __restrict__ bwd_sums,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           uint16_t* __restrict__ out, float* __restrict__ running_mean,
+                                                           float* __restrict__ running_var, long T, int C, int cvb, float eps,
+                                                           float momentum, int relu, float slope, long ldo, BnExt ext) {
+  bn_apply_body<DT, BWD, true>(x, g, fwd_sums, bwd_sums, gamma, beta, out, running_mean, running_var, T, C, cvb, eps, momentum,
+                               relu, slope, ldo, ext);
 }
 
 static inline int bn_cvb(int CV) { return CV >= 64 ? 64 : (CV >= 32 ? 32 : (CV >= 16 ? 16 : 8)); }
@@ -206,7 +311,9 @@ static inline int bn_stats_rows(long T, int C) {
 template <int DT>
 static int bn_launch(bool bwd, bool apply, const void* x, const void* g, const double* fwd_sums, void* sums_or_bwd,
                      const float* gamma, const float* beta, void* out, float* rmean, float* rvar, long T, int C, float eps,
-                     float momentum, int relu, float slope, hipStream_t s, long ldo = 0, void* part = nullptr) {
+                     float momentum, int relu, float slope, hipStream_t s, long ldo = 0, void* part = nullptr,
+                     const BnExt* ext = nullptr) {
+  // ext: the `_ext` kernels (same grid, same lane and row mapping; the forward statistics have none)
   if (ldo == 0) ldo = C;
   const int CV = C / 8, cvb = bn_cvb(CV), gx = cdiv(CV, cvb), pl = 256 / cvb;
   // workgroups per launch.  A statistics workgroup ends with 2 x (its channels) atomics on the SAME 2C sums: 512 of them
@@ -219,7 +326,18 @@ static int bn_launch(bool bwd, bool apply, const void* x, const void* g, const d
   const int gy = apply ? (int)std::max<long>(1, std::min<long>(cdiv(T, (long)pl * 4), std::max<long>(1, wgs / gx)))
                        : bn_stats_rows(T, C);
   dim3 grid(gx, gy), block(256);
-  if (!apply) {
+  if (ext != nullptr) {
+    if (!apply)
+      hipLaunchKernelGGL((bn_stats_bwd_ext_kernel<DT>), grid, block, 0, s, (const uint16_t*)x, (const uint16_t*)g, fwd_sums, gamma,
+                         beta, sums_or_bwd, T, C, cvb, eps, relu, slope, part, *ext);
+    else if (bwd)
+      hipLaunchKernelGGL((bn_apply_ext_kernel<DT, true>), grid, block, 0, s, (const uint16_t*)x, (const uint16_t*)g, fwd_sums,
+                         (const float*)sums_or_bwd, gamma, beta, (uint16_t*)out, nullptr, nullptr, T, C, cvb, eps, momentum, relu,
+                         slope, ldo, *ext);
+    else
+      hipLaunchKernelGGL((bn_apply_ext_kernel<DT, false>), grid, block, 0, s, (const uint16_t*)x, nullptr, fwd_sums, nullptr, gamma,
+                         beta, (uint16_t*)out, rmean, rvar, T, C, cvb, eps, momentum, relu, slope, ldo, *ext);
+  } else if (!apply) {
     if (bwd)
       hipLaunchKernelGGL((bn_stats_kernel<DT, true>), grid, block, 0, s, (const uint16_t*)x, (const uint16_t*)g, fwd_sums,
                          gamma, beta, sums_or_bwd, T, C, cvb, eps, relu, slope, part);
@@ -291,16 +409,44 @@ int rfn_bn_apply_fwd_ld(const void* x, const float* gamma, const float* beta, vo
                       stream);
 }
 
-// the backward statistics launch; workspace != null: the deterministic form's partial rows
+// the operands of the extended forms: grad_y's pitch (0 = C) and the dropout multiplier (may be null) -> BnExt
+static int bn_ext(const char* who, long ld_g, const void* drop, long rows_per_sample, long T, int C, const void* g, BnExt* ext) {
+  RFN_REQUIRE(ld_g == 0 || (ld_g >= C && ld_g % 8 == 0), "%s: pitch %ld (>= C = %d, %% 8)", who, ld_g, C);
+  RFN_REQUIRE(g == nullptr || ((size_t)g & 15) == 0, "%s: grad_y needs a 16-byte base", who);
+  RFN_REQUIRE(drop == nullptr || (((size_t)drop & 15) == 0 && rows_per_sample >= 1 && T % rows_per_sample == 0),
+              "%s: drop needs a 16-byte base and T=%ld a multiple of rows_per_sample=%ld", who, T, rows_per_sample);
+  *ext = BnExt{(const uint16_t*)drop, drop ? rows_per_sample : 1, ld_g ? ld_g : (long)C};
+  return RFN_OK;
+}
+
+// rfn_bn_apply_fwd_ld with Dropout2d folded in: y = round16(relu?(bn(x))) * drop[t / rows_per_sample][c], drop (T / rows_per_sample, C)
+// in the activation dtype -- bit for bit the 16-bit result followed by ATen's 16-bit multiply.  ld_y: 0 = C.
+int rfn_bn_apply_fwd_drop(const void* x, const float* gamma, const float* beta, void* y, long ld_y, const double* sums,
+                          float* running_mean, float* running_var, const void* drop, long rows_per_sample, long T, int C, float eps,
+                          float momentum, int relu, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && y && sums && drop, "bn_apply_fwd_drop: null pointer");
+  if (int rc = bn_check("bn_apply_fwd_drop", T, C)) return rc;
+  RFN_REQUIRE((ld_y == 0 || (ld_y >= C && ld_y % 8 == 0)) && ((size_t)y & 15) == 0, "bn_apply_fwd_drop: pitch %ld (>= C = %d, %% 8, 16-byte base)",
+              ld_y, C);
+  BnExt ext;
+  if (int rc = bn_ext("bn_apply_fwd_drop", 0, drop, rows_per_sample, T, C, nullptr, &ext)) return rc;
+  return dt16(dtype, "rfn_bn_apply_fwd_drop", [&](auto dt) {
+    return bn_launch<decltype(dt)::value>(false, true, x, nullptr, sums, nullptr, gamma, beta, y, running_mean, running_var, T, C, eps,
+                                          momentum, relu != 0, bn_slope(relu), (hipStream_t)stream, ld_y, nullptr, &ext);
+  });
+}
+
+// the backward statistics launch; workspace != null: the deterministic form's partial rows; ext != null: the extended kernel
 static int bn_stats_bwd(const char* who, const void* x, const void* grad_y, const double* fwd_sums, const float* gamma, const float* beta,
-                        float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, hipStream_t s) {
+                        float* bwd_sums, void* workspace, long T, int C, float eps, int relu, int dtype, hipStream_t s,
+                        const BnExt* ext = nullptr) {
   return dt16(dtype, who, [&](auto dt) {
     if (workspace == nullptr) {
       RFN_REFUSE_NONDET(true, "rfn_bn_stats_bwd", "bn_stats_kernel, fp32 atomics (use rfn_bn_stats_bwd_det)");
       if (int rc = zero_async(bwd_sums, 2 * (size_t)C * sizeof(float), s)) return rc;
     }
     return bn_launch<decltype(dt)::value>(true, false, x, grad_y, fwd_sums, bwd_sums, gamma, beta, nullptr, nullptr, nullptr, T, C, eps,
-                                          0.f, relu != 0, bn_slope(relu), s, 0, workspace);
+                                          0.f, relu != 0, bn_slope(relu), s, 0, workspace, ext);
   });
 }
 
@@ -347,6 +493,46 @@ int rfn_bn_apply_bwd(const void* x, const void* grad_y, const double* fwd_sums, 
   return dt16(dtype, "rfn_bn_apply_bwd", [&](auto dt) {
     return bn_launch<decltype(dt)::value>(true, true, x, grad_y, fwd_sums, (void*)bwd_sums, gamma, beta, grad_x, nullptr, nullptr, T, C,
                                           eps, 0.f, relu != 0, bn_slope(relu), (hipStream_t)stream);
+  });
+}
+
+// The backward passes with grad_y read at a row pitch of ld_g elements (0 = C; a channel slice of a wider channels-last tensor:
+// the ASPP branches read the bottleneck's input gradient in place) and, with drop != NULL, multiplied by the Dropout2d noise as it
+// is loaded: g = round16(grad_y * drop[t / rows_per_sample][c]).  Same lane and row mapping as the dense entry points.
+int rfn_bn_stats_bwd_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample, const double* fwd_sums,
+                        const float* gamma, const float* beta, float* bwd_sums, long T, int C, float eps, int relu, int dtype,
+                        rfn_stream_t stream) {
+  RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums, "bn_stats_bwd_ld: null pointer");
+  if (int rc = bn_check("bn_stats_bwd_ld", T, C)) return rc;
+  BnExt ext;
+  if (int rc = bn_ext("bn_stats_bwd_ld", ld_g, drop, rows_per_sample, T, C, grad_y, &ext)) return rc;
+  return bn_stats_bwd("rfn_bn_stats_bwd_ld", x, grad_y, fwd_sums, gamma, beta, bwd_sums, nullptr, T, C, eps, relu, dtype, (hipStream_t)stream,
+                      &ext);
+}
+
+int rfn_bn_stats_bwd_det_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample, const double* fwd_sums,
+                            const float* gamma, const float* beta, float* bwd_sums, void* workspace, long T, int C, float eps, int relu,
+                            int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums && workspace, "bn_stats_bwd_det_ld: null pointer");
+  if (int rc = bn_check("bn_stats_bwd_det_ld", T, C)) return rc;
+  BnExt ext;
+  if (int rc = bn_ext("bn_stats_bwd_det_ld", ld_g, drop, rows_per_sample, T, C, grad_y, &ext)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = bn_stats_bwd("rfn_bn_stats_bwd_det_ld", x, grad_y, fwd_sums, gamma, beta, bwd_sums, workspace, T, C, eps, relu, dtype, s, &ext))
+    return rc;
+  return ordered_colsum_f32((const float*)workspace, bwd_sums, bn_stats_rows(T, C), 2 * C, s);
+}
+
+int rfn_bn_apply_bwd_ld(const void* x, const void* grad_y, long ld_g, const void* drop, long rows_per_sample, const double* fwd_sums,
+                        const float* bwd_sums, const float* gamma, const float* beta, void* grad_x, long T, int C, float eps, int relu,
+                        int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(x && grad_y && fwd_sums && bwd_sums && grad_x, "bn_apply_bwd_ld: null pointer");
+  if (int rc = bn_check("bn_apply_bwd_ld", T, C)) return rc;
+  BnExt ext;
+  if (int rc = bn_ext("bn_apply_bwd_ld", ld_g, drop, rows_per_sample, T, C, grad_y, &ext)) return rc;
+  return dt16(dtype, "rfn_bn_apply_bwd_ld", [&](auto dt) {
+    return bn_launch<decltype(dt)::value>(true, true, x, grad_y, fwd_sums, (void*)bwd_sums, gamma, beta, grad_x, nullptr, nullptr, T, C,
+                                          eps, 0.f, relu != 0, bn_slope(relu), (hipStream_t)stream, 0, nullptr, &ext);
   });
 }
 

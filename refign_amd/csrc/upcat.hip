@@ -129,9 +129,17 @@ struct UpcatBwdArgs {
   int nlev;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, const T* __restrict__ g, int H, int W,
-                                                             long total) {
+// NG > 1: the concatenated gradient arrives as NG operands of the same shape (the consumers of the forward's result each
+// left one: the four branches of the ASPP, daformer.py:110-118); they are added in fp32 at every tap, in operand order, so
+// the element-wise additions of the autograd engine -- three passes over the whole tensor, a 16-bit rounding each -- are not
+// made.  `more` holds operands 1 .. NG - 1.  Still a gather: no atomics, the result does not depend on the launch.
+struct UpcatBwdMore {
+  const void* g[3];
+};
+
+template <typename T, int NG>
+__device__ __forceinline__ void upcat_bwd_nhwc_body(const UpcatBwdArgs& a, const T* __restrict__ g, const UpcatBwdMore& more,
+                                                    int H, int W, long total) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   int l = 0;
@@ -148,12 +156,25 @@ __global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, con
   const int n = (int)(loc / hl);
   const T* gb = g + (size_t)n * H * W * CV * 8 + (size_t)(a.cv0[l] + cl) * 8;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto add = [&](const T* p, float wgt) {
-    float v[8];
+  auto load = [&](const T* p, float (&v)[8]) {
     if constexpr (sizeof(T) == 2) widen8<T>(*reinterpret_cast<const uint4*>(p), v);
     else {
       const float4 u = *reinterpret_cast<const float4*>(p), t = *reinterpret_cast<const float4*>(p + 4);
       v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; v[4] = t.x; v[5] = t.y; v[6] = t.z; v[7] = t.w;
+    }
+  };
+  auto add = [&](const T* p, float wgt) {
+    float v[8];
+    load(p, v);
+    if constexpr (NG > 1) {
+      const long at = p - g;                                  // the same element of every operand
+      float o[NG - 1][8];
+#pragma unroll
+      for (int k = 0; k < NG - 1; ++k) load(reinterpret_cast<const T*>(more.g[k]) + at, o[k]);
+#pragma unroll
+      for (int k = 0; k < NG - 1; ++k)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] += o[k][i];
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = fmaf(wgt, v[i], acc[i]);
@@ -193,6 +214,18 @@ __global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, con
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void upcat_bwd_nhwc_kernel(UpcatBwdArgs a, const T* __restrict__ g, int H, int W,
+                                                             long total) {
+  upcat_bwd_nhwc_body<T, 1>(a, g, UpcatBwdMore{}, H, W, total);
+}
+
+template <typename T, int NG>
+__global__ __launch_bounds__(256) void upcat_bwd_nhwc_sum_kernel(UpcatBwdArgs a, const T* __restrict__ g, UpcatBwdMore more,
+                                                                 int H, int W, long total) {
+  upcat_bwd_nhwc_body<T, NG>(a, g, more, H, W, total);
+}
+
 }  // namespace rfn
 
 using namespace rfn;
@@ -230,11 +263,17 @@ int rfn_upsample_concat_nhwc(const void* src0, const void* src1, const void* src
   });
 }
 
-int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs,
-                                 const int* ws, const int* cs, int nlev, int n, int H, int W, int dtype,
-                                 rfn_stream_t stream) {
+// ngrad operands (grad_out and ngrad - 1 more, same shape and dtype), added inside the gather
+static int upcat_bwd(const char* who, const void* grad_out, const void* const* more_grads, int ngrad, void* grad0, void* grad1,
+                     void* grad2, void* grad3, const int* hs, const int* ws, const int* cs, int nlev, int n, int H, int W, int dtype,
+                     rfn_stream_t stream) {
   RFN_REQUIRE(nlev >= 1 && nlev <= 4 && grad_out && hs && ws && cs && n > 0 && H > 0 && W > 0,
               "rfn_upsample_concat_nhwc_bwd: bad arguments");
+  UpcatBwdMore more{};
+  for (int k = 1; k < ngrad; ++k) {
+    RFN_REQUIRE(more_grads[k - 1] != nullptr && ((size_t)more_grads[k - 1] & 15) == 0, "%s: operand %d: null or not 16-byte aligned", who, k);
+    more.g[k - 1] = more_grads[k - 1];
+  }
   UpcatBwdArgs a;
   void* dsts[4] = {grad0, grad1, grad2, grad3};
   a.nlev = nlev;
@@ -258,12 +297,34 @@ int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1,
   const long total = a.vec0[nlev];
   RFN_REQUIRE(total / 256 < 0x7fffffffL, "rfn_upsample_concat_nhwc_bwd: too large");
   const int grid = cdiv(total, 256);
-  return dt_one(dtype, "rfn_upsample_concat_nhwc_bwd", [&](auto t) {
+  return dt_one(dtype, who, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((upcat_bwd_nhwc_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, (const T*)grad_out, H, W,
-                       total);
+    hipStream_t s = (hipStream_t)stream;
+    const T* g = (const T*)grad_out;
+    if (ngrad == 1) hipLaunchKernelGGL((upcat_bwd_nhwc_kernel<T>), dim3(grid), dim3(256), 0, s, a, g, H, W, total);
+    else if (ngrad == 2) hipLaunchKernelGGL((upcat_bwd_nhwc_sum_kernel<T, 2>), dim3(grid), dim3(256), 0, s, a, g, more, H, W, total);
+    else if (ngrad == 3) hipLaunchKernelGGL((upcat_bwd_nhwc_sum_kernel<T, 3>), dim3(grid), dim3(256), 0, s, a, g, more, H, W, total);
+    else hipLaunchKernelGGL((upcat_bwd_nhwc_sum_kernel<T, 4>), dim3(grid), dim3(256), 0, s, a, g, more, H, W, total);
     return check_launch("upcat_bwd_nhwc_kernel");
   });
+}
+
+int rfn_upsample_concat_nhwc_bwd(const void* grad_out, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs,
+                                 const int* ws, const int* cs, int nlev, int n, int H, int W, int dtype,
+                                 rfn_stream_t stream) {
+  return upcat_bwd("rfn_upsample_concat_nhwc_bwd", grad_out, nullptr, 1, grad0, grad1, grad2, grad3, hs, ws, cs, nlev, n, H, W, dtype,
+                   stream);
+}
+
+// The same on the SUM of up to four gradients of the concatenation (grad_out0 .. 3, the first `ngrad` of them; same shape, dtype
+// and layout): added in fp32 at every tap in that order, one rounding at the end.
+int rfn_upsample_concat_nhwc_bwd_sum(const void* grad_out0, const void* grad_out1, const void* grad_out2, const void* grad_out3,
+                                     int ngrad, void* grad0, void* grad1, void* grad2, void* grad3, const int* hs, const int* ws,
+                                     const int* cs, int nlev, int n, int H, int W, int dtype, rfn_stream_t stream) {
+  RFN_REQUIRE(ngrad >= 1 && ngrad <= 4, "rfn_upsample_concat_nhwc_bwd_sum: ngrad=%d (1 .. 4)", ngrad);
+  const void* more[3] = {grad_out1, grad_out2, grad_out3};
+  return upcat_bwd("rfn_upsample_concat_nhwc_bwd_sum", grad_out0, more, ngrad, grad0, grad1, grad2, grad3, hs, ws, cs, nlev, n, H, W,
+                   dtype, stream);
 }
 
 }  // extern "C"

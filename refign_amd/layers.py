@@ -177,9 +177,21 @@ class ConvBNReLU(nn.Module):
                 and c.groups == c.in_channels == c.out_channels and c.kernel_size == (3, 3) and c.stride == (1, 1)
                 and c.padding == c.dilation and c.dilation[0] == c.dilation[1] and c.in_channels % 8 == 0)
 
-    def _bn_train(self, x, cd, out=None):
+    def bn_kernel_ok(self, x):
+        """forward(x) of this block ends in the fused BatchNorm(train) + activation pass (csrc/bn.hip) -- the pass that takes
+        the decode heads' Dropout2d with it (forward(x, drop=...)) and whose input a caller may compute itself (pre_norm)."""
+        if self.depthwise_separable or not (x.is_cuda and self.use_norm and self.training and os.environ.get("RFN_BN_KERNEL", "1") != "0"
+                                            and (self.act in (None, 'relu') or (self.act == 'leaky' and self.act_slope == LEAKY_SLOPE))):
+            return False
+        from . import bn as bnk
+        from .params import compute_dtype
+        return bnk.usable(x, self.bn, compute_dtype(x), channels=self.conv.out_channels, count=self._out_count(x))
+
+    def _bn_train(self, x, cd, out=None, drop=None):
         from . import bn as bnk
         act = {None: 0, 'relu': 1, 'leaky': 3}[self.act]
+        if drop is not None:
+            return bnk.bn_act_train(self._conv_train(x, cd), self.bn, act, cd, out=out, drop=drop)
         if self._dw_stats_ok(x, cd) and not torch.is_grad_enabled() and out is None and act in (0, 1) and _DW_BN_FUSED \
                 and self.bn.momentum is not None:
             # gradient-free (EMA teacher): statistics pass without a store, then convolution + BatchNorm + ReLU in one pass
@@ -195,7 +207,13 @@ class ConvBNReLU(nn.Module):
             return bnk.bn_act_train(self._conv2d(x, c.weight, c.bias, stats=sums), self.bn, act, cd, out=out, sums=sums)
         return bnk.bn_act_train(self._conv_train(x, cd), self.bn, act, cd, out=out)
 
-    def forward(self, x, out=None):
+    def forward(self, x, out=None, drop=None):
+        # drop: (B, C, 1, 1) Dropout2d multipliers folded into the BatchNorm pass -- only where bn_kernel_ok(x) holds
+        if drop is not None:
+            from .params import compute_dtype
+            if isinstance(x, (list, tuple)) or not self.bn_kernel_ok(x):
+                raise RuntimeError("ConvBNReLU(drop=...): on the fused BatchNorm(train) pass only (bn_kernel_ok)")
+            return self._bn_train(x, compute_dtype(x), out=out, drop=drop)
         if isinstance(x, (list, tuple)):
             # a channel concatenation handed over as its parts (the matcher's decoders: cat(correlation, flow, ...)): on the
             # gradient-free split-bf16 path the parts go straight into the convolution's operand (split32.conv2d_parts)

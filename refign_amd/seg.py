@@ -500,6 +500,20 @@ class DepthwiseSeparableASPPModule(nn.ModuleList):
 
 
 _ASPP_NOCAT = True
+_ASPP_NOCAT_GRAD = True     # the same under autograd (the student): one autograd node for the four BatchNorm + ReLU passes (bn._BNActCat)
+_UPCAT_FANIN = True         # DAFormerHead under autograd: the four gradients of the ASPP input are added inside upcat's backward kernel
+_DROPOUT_FUSED = True       # the heads' Dropout2d multiply inside the BatchNorm passes of the block in front of it (csrc/bn.hip BnExt)
+
+
+def _fused_dropout_noise(dropout, block, x):
+    """The multipliers of `dropout` (the head's nn.Dropout2d) for `block`(x, drop=...), or None: the module itself runs.
+    Drawn here, in front of the block: nothing inside it consumes the generator, so the stream is the module's."""
+    if not (_DROPOUT_FUSED and dropout is not None and dropout.training and 0.0 < dropout.p < 1.0 and not dropout.inplace
+            and x.is_cuda and block.bn_kernel_ok(x)):
+        return None
+    from . import bn as bnk
+    from .params import compute_dtype
+    return bnk.dropout2d_noise(x, block.conv.out_channels, compute_dtype(x), dropout.p)
 
 
 class ASPPWrapper(nn.Module):
@@ -517,10 +531,17 @@ class ASPPWrapper(nn.Module):
         self.bottleneck = ConvBNReLU(len(dilations) * channels, channels, kernel_size=3, padding=1,
                                      norm_layer=norm_layer, activation_layer=activation_layer)
 
-    def forward(self, x):
-        if x.is_cuda:
-            x = x.contiguous(memory_format=torch.channels_last)   # depthwise branches + 1x1 convs run channels-last
+    def forward(self, x, drop=None):
+        # drop: Dropout2d multipliers for the bottleneck's BatchNorm pass (_fused_dropout_noise)
+        kw = {} if drop is None else {"drop": drop}
         mods = list(self.aspp_modules)
+        # x: the input, or one handle on it per branch (upcat.upsample_concat(handles=...): the branches' gradients are then
+        # added where they are consumed)
+        xs = list(x) if isinstance(x, (list, tuple)) else [x] * len(mods)
+        assert len(xs) == len(mods)
+        if xs[0].is_cuda:
+            xs = [t.contiguous(memory_format=torch.channels_last) for t in xs]   # depthwise branches + 1x1 convs run channels-last
+        x = xs[0]
         if x.is_cuda and not torch.is_grad_enabled() and _ASPP_NOCAT and all(m.fused_out_ok(x) for m in mods):
             # gradient-free (the EMA teacher: 42 maps): every branch's BatchNorm + ReLU writes its 256 channels straight
             # into the concatenated channels-last tensor -- the torch.cat was 5.3 GB of traffic, 1.1 ms per step
@@ -533,8 +554,20 @@ class ASPPWrapper(nn.Module):
                 for m, c in zip(mods, ch):
                     m(x, out=cat[..., o:o + c].permute(0, 3, 1, 2))
                     o += c
-                return self.bottleneck(cat.permute(0, 3, 1, 2))
-        return self.bottleneck(torch.cat(self.aspp_modules(x), dim=1))
+                return self.bottleneck(cat.permute(0, 3, 1, 2), **kw)
+        last = [m.pointwise_conv if m.depthwise_separable else m for m in mods]
+        if x.is_cuda and torch.is_grad_enabled() and _ASPP_NOCAT_GRAD and all(m.act in (None, 'relu') for m in last) \
+                and len({m.act for m in last}) == 1 and all(m.bn_kernel_ok(x) for m in last):
+            # under autograd (the student): the branches' last BatchNorm + ReLU passes write into the concatenation, and their
+            # backward passes read their channel slices of its gradient in place -- no torch.cat, no slice copies.  (The
+            # depthwise convolutions keep the shape of x: what bn_kernel_ok says of x holds for their results.)
+            from . import bn as bnk
+            from .params import compute_dtype
+            cd = compute_dtype(x)
+            pre = [m._conv_train(b.depthwise_conv(t) if b.depthwise_separable else t, cd) for b, m, t in zip(mods, last, xs)]
+            cat = bnk.bn_act_train_cat(pre, [m.bn for m in last], 1 if last[0].act == 'relu' else 0, cd)
+            return self.bottleneck(cat, **kw)
+        return self.bottleneck(torch.cat([m(t) for m, t in zip(mods, xs)], dim=1), **kw)
 
 
 class DAFormerHead(BaseHead):
@@ -562,7 +595,9 @@ class DAFormerHead(BaseHead):
         size = x[0].shape[2:]
         toks = [self.embed_layers[str(i)](f) for i, f in enumerate(x)]          # (n, h_l*w_l, embed) token maps
         # one pass (csrc/upcat.hip), forward and backward
-        cat = upsample_concat(toks, [f.shape[2:] for f in x], size) if _fused_upcat_here() else None
+        fan = len(self.fuse_layer.aspp_modules) if _UPCAT_FANIN and torch.is_grad_enabled() else 1
+        cat = upsample_concat(toks, [f.shape[2:] for f in x], size, handles=fan if 2 <= fan <= 4 else 1) \
+            if _fused_upcat_here() else None
         if cat is None:
             cs = []
             for c, f in zip(toks, x):
@@ -570,6 +605,9 @@ class DAFormerHead(BaseHead):
                 c = c.transpose(1, 2).reshape(n, -1, h, w)
                 cs.append(c if (h, w) == tuple(size) else _up(c, size).to(c.dtype))
             cat = torch.cat(cs, dim=1)
+        noise = _fused_dropout_noise(self.dropout, self.fuse_layer.bottleneck, cat[0] if isinstance(cat, tuple) else cat)
+        if noise is not None:
+            return _class_logits(self.conv_seg, self.fuse_layer(cat, drop=noise))
         y = self.fuse_layer(cat)
         if self.dropout is not None:
             y = self.dropout(y)
@@ -611,6 +649,9 @@ class SegFormerHead(BaseHead):
                 t = t.transpose(1, 2).reshape(n, -1, h, w)
                 parts.append(t if (h, w) == tuple(size) else _up(t, size))
             cat = torch.cat(parts, dim=1)
+        noise = _fused_dropout_noise(self.dropout, self.linear_fuse, cat)
+        if noise is not None:
+            return _class_logits(self.linear_pred, self.linear_fuse(cat, drop=noise))
         y = self.linear_fuse(cat)
         if self.dropout is not None:
             y = self.dropout(y)
