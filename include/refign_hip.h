@@ -1060,6 +1060,26 @@ int rfn_hrda_fuse_crop_bwd(const float* grad_out, const long* g_strides, const v
                            void* grad_lr, void* grad_hr, int n, int K, int h, int w, int hc, int wc, int mh, int mw, int div_mask,
                            int div_ins, int dtype, rfn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The DeepLabV2 classifier (models/heads/deeplabv2.py: the sum of R dilated 3x3 convolutions, dilation = padding) as a
+ * tap-GEMM plus a shifted sum (csrc/aspp.hip); additions to ABI 5, nothing existing changed.  The caller stacks the T taps
+ * whose offset (dy, dx) = ((ky - 1) d, (kx - 1) d) can land inside the map into one (T Np, C) matrix, Np = classes rounded
+ * up to 8, and computes Z = X_tokens @ Wt^T with rfn_gemm_nt: Z is (B H W, ldz) rows of 16-bit values, tap t in columns
+ * [t Np, (t + 1) Np).  taps: HOST array of T x (dy, dx), read by the call (not kept); T <= 64, offsets within 16 bits.
+ * dtype: 1 (bf16) or 2 (f16).  Gathers without atomics: deterministic with or without the flag; no host read, no allocation.
+ *   rfn_aspp_tapsum      Y[b, y, x, :] = sum_r bias[r, :] + sum_t Z[b, y + dy_t, x + dx_t, t, :], terms outside the map
+ *            dropped; fp32 sums in (bias rows, then taps) order, one rounding.  bias: DEVICE fp32 (nbias, Np), nbias <= 8,
+ *            NULL with nbias 0.  Y: (B, H, W, Np) dense, every element written.
+ *   rfn_aspp_tapsum_bwd  dZ[b, y, x, t, :] = gY[b, y - dy_t, x - dx_t, :], zero outside the map and in the columns
+ *            [T Np, ldz); gY: (B, H, W, Np) dense; every element of dZ (B H W, ldz) written.
+ * Errors (nothing is launched): a null or misaligned (16 bytes) pointer, Np or ldz no multiple of 8, ldz < T Np, T outside
+ * 1 .. 64, H or W > 32767.
+ * ---------------------------------------------------------------------------------------------------------- */
+int rfn_aspp_tapsum(const void* Z, long ldz, const float* bias, int nbias, const int* taps, int T, void* Y, int B, int H, int W,
+                    int Np, int dtype, rfn_stream_t stream);
+int rfn_aspp_tapsum_bwd(const void* gY, const int* taps, int T, void* dZ, long ldz, int B, int H, int W, int Np, int dtype,
+                        rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

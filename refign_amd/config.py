@@ -28,6 +28,12 @@ ALIASES = {
     "helpers.lr_scheduler.LinearWarmupPolynomialLR": "refign_amd.trainer.LinearWarmupPolynomialLR",
     "helpers.callbacks.ValEveryNSteps": "refign_amd.trainer.ValEveryNSteps",
 }
+# Opt-in model families: reference class path -> implementation, per family.  build_model(cfg, families=("deeplabv2",)) adds a
+# family's map for that one call; ALIASES itself never changes, so a build without the keyword keeps refusing these classes.
+FAMILIES = {
+    "deeplabv2": {"models.backbones.ResNet": "refign_amd.resnet.ResNet",
+                  "models.heads.DeepLabV2Head": "refign_amd.resnet.DeepLabV2Head"},
+}
 # subsystems that are out of scope here (host I/O, logging, evaluation): accepted in a config, not instantiated
 IGNORED_PREFIXES = ("pytorch_lightning.", "data_modules.", "helpers.metrics.")
 # class paths accepted in a config but kept as specs (none at present: the matcher-training losses of row N1 are built)
@@ -43,12 +49,28 @@ class OutOfScopeError(NotImplementedError):
     pass
 
 
-def resolve(class_path):
+def family_aliases(families):
+    """The alias map of the named opt-in families (a name or a sequence of names of FAMILIES), merged; {} for none."""
+    extra = {}
+    for name in ((families,) if isinstance(families, str) else tuple(families or ())):
+        if name not in FAMILIES:
+            raise ValueError(f"unknown model family {name!r} (one of {sorted(FAMILIES)})")
+        extra.update(FAMILIES[name])
+    return extra
+
+
+def resolve(class_path, extra=None):
+    """`extra`: an alias map looked up after ALIASES (family_aliases(...)); None: ALIASES alone."""
     path = ALIASES.get(class_path)
+    if path is None and extra:
+        path = extra.get(class_path)
     if path is None:
         if class_path.startswith(_REFERENCE_PACKAGES):
+            optin = [name for name, m in sorted(FAMILIES.items()) if class_path in m]
+            hint = (f"; it belongs to the opt-in family {optin[0]!r}: build_model(cfg, families=({optin[0]!r},)), which "
+                    f"`python -m refign_amd.run` passes") if optin else ""
             raise OutOfScopeError(f"{class_path} is out of scope of refign_amd (the align-and-refine hot path: "
-                                  f"{', '.join(sorted(ALIASES))})")
+                                  f"{', '.join(sorted(ALIASES))}){hint}")
         path = class_path
     mod, _, name = path.rpartition(".")
     return getattr(importlib.import_module(mod), name)
@@ -58,15 +80,16 @@ def is_spec(x):
     return isinstance(x, dict) and "class_path" in x
 
 
-def build(spec):
-    """Recursively instantiate a {class_path, init_args} tree (nested specs inside init_args are built first)."""
+def build(spec, extra=None):
+    """Recursively instantiate a {class_path, init_args} tree (nested specs inside init_args are built first).
+    `extra`: the alias map of the opt-in families, handed down to resolve."""
     if is_spec(spec):
         if spec["class_path"].startswith(IGNORED_PREFIXES) or spec["class_path"] in DEFERRED:
             return spec
-        kwargs = {k: build(v) for k, v in spec.get("init_args", {}).items()}
-        return resolve(spec["class_path"])(**kwargs)
+        kwargs = {k: build(v, extra) for k, v in spec.get("init_args", {}).items()}
+        return resolve(spec["class_path"], extra)(**kwargs)
     if isinstance(spec, list):
-        return [build(v) for v in spec]
+        return [build(v, extra) for v in spec]
     return spec
 
 
@@ -81,9 +104,12 @@ def load_config(path):
         return yaml.safe_load(f)
 
 
-def build_model(cfg, overrides=None):
+def build_model(cfg, overrides=None, families=()):
     """Build `cfg['model']` with the optimizer / lr_scheduler sections linked in as dicts (helpers/cli.py:17-21).
-    `overrides` (dict) is merged into model.init_args first, e.g. {'backbone.init_args.pretrained': None}."""
+    `overrides` (dict) is merged into model.init_args first, e.g. {'backbone.init_args.pretrained': None}.
+    `families`: names of FAMILIES whose classes this call may build (("deeplabv2",): ResNet-v1c + DeepLabV2Head); without it
+    those class paths raise OutOfScopeError as before.  Nothing is remembered between calls."""
+    extra = family_aliases(families)
     model = dict(cfg["model"])
     init = dict(model.get("init_args", {}))
     init["optimizer_init"] = cfg.get("optimizer", init.get("optimizer_init"))
@@ -96,8 +122,8 @@ def build_model(cfg, overrides=None):
         node[keys[-1]] = val
     # metrics are evaluation-only (helpers.metrics, torchmetrics): kept as config, not built
     metrics = init.pop("metrics", {})
-    kwargs = {k: (v if k in ("optimizer_init", "lr_scheduler_init") else build(v)) for k, v in init.items()}
-    return resolve(model["class_path"])(metrics=metrics, **kwargs)
+    kwargs = {k: (v if k in ("optimizer_init", "lr_scheduler_init") else build(v, extra)) for k, v in init.items()}
+    return resolve(model["class_path"], extra)(metrics=metrics, **kwargs)
 
 
 def trainer_kwargs(cfg):

@@ -335,6 +335,67 @@ def tap_major_f32(p):
     return derived(p, "tap_major_f32", lambda t: _tap_view(t.float()).contiguous(), _tap_view)
 
 
+def _stacked(params, key, alloc, slot, views):
+    """ONE buffer shared by the cached copies of several parameters: entry `key` of params[i] hands out the buffer and is
+    re-filled, by refresh() like every other entry with a refill view, through slot(buffer, i) <- views[i](params[i]).  The first
+    parameter's entry owns the allocation (alloc(p)); an entry that points at an older buffer is re-made into the current one."""
+    base = None
+    for i, p in enumerate(params):
+        def make(t, i=i):
+            buf = alloc(t) if base is None else base
+            fill = slot(buf, i)
+            fill.copy_(views[i](t))
+            return buf, fill
+        got = derived(p, key, make, views[i])
+        if base is not None and got is not base:
+            p.__dict__["_rfn_derived"].pop(key, None)
+            _GENERATION[0] += 1
+            got = derived(p, key, make, views[i])
+        if base is None:
+            base = got
+    return base
+
+
+def _tap_block_view(box, transpose):
+    y0, y1, x0, x1 = box
+
+    def view(t):                                       # (K, C, 3, 3) -> (ny, nx, K, C), or (C, ny, nx, K)
+        s = t[:, :, y0:y1, x0:x1]
+        return s.permute(1, 2, 3, 0) if transpose else s.permute(2, 3, 0, 1)
+    return view
+
+
+def tap_stack(weights, dtype, live, n_pad, rows, transpose=False):
+    """The live taps of several 3x3 convolution weights (K, C, 3, 3) stacked into one zero-padded matrix in `dtype`: `live`
+    gives per weight the (y0, y1, x0, x1) box of its taps that are kept, tap-major in (weight, ky, kx) order, K padded to
+    `n_pad` per tap, `rows` rows in all -> (rows, C), the W operand of the DeepLabV2 tap-GEMM (csrc/aspp.hip); `transpose`:
+    its (C, rows) transpose, the W operand of the data-gradient GEMM.  One buffer, one refill view per weight."""
+    C = weights[0].shape[1]
+    starts, t = [], 0
+    for y0, y1, x0, x1 in live:
+        starts.append(t)
+        t += (y1 - y0) * (x1 - x0)
+
+    def slot(buf, i):
+        y0, y1, x0, x1 = live[i]
+        ny, nx, K = y1 - y0, x1 - x0, weights[i].shape[0]
+        a, b = starts[i] * n_pad, (starts[i] + ny * nx) * n_pad
+        if transpose:
+            return buf[:, a:b].view(C, ny, nx, n_pad)[..., :K]
+        return buf[a:b].view(ny, nx, n_pad, C)[:, :, :K]
+
+    return _stacked(weights, ("tap_stack_T" if transpose else "tap_stack", dtype, tuple(live), n_pad, rows),
+                    lambda p: torch.zeros((C, rows) if transpose else (rows, C), dtype=dtype, device=p.device), slot,
+                    [_tap_block_view(box, transpose) for box in live])
+
+
+def bias_stack(biases, n_pad):
+    """(R, n_pad) fp32 rows of R bias vectors, zero padded: what rfn_aspp_tapsum adds in row order."""
+    return _stacked(biases, ("bias_stack", len(biases), n_pad),
+                    lambda p: torch.zeros((len(biases), n_pad), dtype=torch.float32, device=p.device),
+                    lambda buf, i: buf[i, :biases[i].shape[0]], [_identity] * len(biases))
+
+
 def compute_dtype(x):
     """dtype the dense ops run in: the autocast dtype inside an autocast region, else x's."""
     if x.is_cuda and torch.is_autocast_enabled("cuda"):

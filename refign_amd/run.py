@@ -6,7 +6,8 @@
 `--set` edits the loaded YAML before anything is built; the value is parsed by yaml.safe_load (`--set trainer.precision=16`,
 `--set model.init_args.backbone.init_args.pretrained=null`, `--set data.init_args.batch_size=2`).  The reference's
 `--trainer.*` / `--model.*` flags of LightningCLI are not reproduced: `--set trainer.precision=16` is the equivalent.
-The model comes from config.build_model, the Trainer from config.trainer_kwargs / trainer_logging / trainer_gradients /
+The model comes from config.build_model with every opt-in family of config.FAMILIES switched on (the refign_deeplabv2
+configurations: ResNet-101-v1c + DeepLabV2Head, refign_amd/resnet.py), the Trainer from config.trainer_kwargs / trainer_logging / trainer_gradients /
 trainer_deterministic, the batches from datamodule.SegmentationDataModule -- or, when the model is the matcher
 (AlignmentModel: configs/megadepth/uawarpc_*.yaml), from datamodule.MatchingDataModule; the run is seeded as Lightning's
 seed_everything seeds it (`seed_everything:` of the YAML: python's random, numpy, torch).  --graph_step is
@@ -84,7 +85,7 @@ def main(argv=None, handles=None):
     if not torch.cuda.is_available():
         raise RuntimeError("refign_amd.run: a HIP device is required (the product path has no CPU fallback)")
     device = torch.device("cuda", torch.cuda.current_device())
-    model = config.build_model(cfg).to(device).train()
+    model = config.build_model(cfg, families=tuple(config.FAMILIES)).to(device).train()
     kw = config.trainer_kwargs(cfg)
     logging = config.trainer_logging(cfg)
     trainer = Trainer(model, sync_batchnorm=kw["sync_batchnorm"], precision=kw["precision"], ckpt_path=args.ckpt_path,

@@ -443,6 +443,8 @@ class DomainAdaptationSegmentationModel(nn.Module):
         same route as the graphed one (device-side HRDA crops, teacher branch queued first); RFN_GRAPH_SEGMENTS=0: all eager."""
         if not (x.is_cuda and os.environ.get("RFN_GRAPH_SEGMENTS", "1") != "0"):
             return False
+        if getattr(self.backbone, "has_batchnorm", False):
+            return False                                   # (ResNet: SyncBatchNorm exchanges inside the backbone -- it runs eagerly)
         from . import graphs
         from .bn import data_parallel, ddp_mode
         return graphs.enabled() and data_parallel() and ddp_mode() == "torch"
