@@ -623,6 +623,17 @@ int rfn_upsample_ce(const void* logits, const long* target, const float* weight,
 int rfn_slide_argmax_confmat(const void* crop_logits, int dtype, int B, int C, int h, int w, const int* boxes, int nbox, int H,
                              int W, const long* target, int ignore_index, unsigned char* labels, long* confmat,
                              rfn_stream_t stream);
+/* The same tail for labels and predictions at ANOTHER size -- forward(x, out_size) of segmentation_model.py:304-312: target,
+ * labels and the counts live on the (B, Ho, Wo) grid; H, W stay the image grid that the boxes are checked against.  Per output
+ * pixel (Y, X) and class: m = the mean above at the image pixels (rounded to fp32 where rfn_slide_argmax_confmat has it), then
+ * upsample_bilinear2d(align_corners = False) of m from (H, W) to (Ho, Wo) -- ATen's source index with scale H / Ho, W / Wo,
+ * clamped (Ho < H is allowed), blended as hy (hx m00 + lx m01) + ly (hx m10 + lx m11) in fp32 -- then the first largest class.
+ * With Ho == H and Wo == W the second tap's weight is exactly 0: labels and counts have the bits of rfn_slide_argmax_confmat.
+ * Errors (nothing is launched): those above, Ho or Wo <= 0, B * Ho * Wo >= 2^31.
+ * (Added within ABI 5.) */
+int rfn_slide_argmax_confmat_resized(const void* crop_logits, int dtype, int B, int C, int h, int w, const int* boxes, int nbox,
+                                     int H, int W, int Ho, int Wo, const long* target, int ignore_index, unsigned char* labels,
+                                     long* confmat, rfn_stream_t stream);
 
 /* fp32-RESULT variants (split-bf16 parity mode, refign_amd/split32.py): bf16 operands whose reduction index carries the
  * three split products side by side, fp32 accumulate, fp32 bias / residual / result (leading dimension ldy in floats).

@@ -6,8 +6,17 @@ that crop's logits; the mean over those boxes in fp32; the first largest class. 
 `ignore_index` or outside [0, C) are skipped, the others counted in a (C, C) int64 matrix (rows = target).  That is what
 forward() -> arg-max -> IoU.update computes when the label size equals the image size, without the up-sampled logits, the
 image-sized sum and count tensors and the host synchronisation of slide_inference's cover assert (the cover is checked on
-the host from the box list).  One difference: under 16-bit autocast forward() rounds every up-sampled crop to 16 bits before
-averaging; the kernel averages the fp32 samples.
+the host from the box list).
+
+Labels or predictions at ANOTHER size (the `test:` sections that resize the image only, predict_step's orig_dims):
+rfn_slide_argmax_confmat_resized does the second interpolation of forward(x, out_size) as well -- per output pixel the bilinear
+sample (align_corners=False, scale H / Ho, clamped) of those fp32 means on the image grid, then the first largest class -- so
+neither the image-sized nor the label-sized logits exist.  With equal sizes it is bit-equal to the first entry, which is the
+one such calls keep launching.
+
+One difference, in both stages: under 16-bit autocast forward() rounds its intermediate tensors to 16 bits (every up-sampled
+crop before the averaging, the averaged logits before the second interpolation, its result); the kernel keeps fp32 from the crop
+logits to the arg-max.
 
 The matcher (AlignmentModel) has a fused step of its own: after its forward, SparseEPE.update is one kernel per batch
 (csrc/sparseepe.hip through refign_amd/sparse_epe.py) instead of a hundred-odd small launches and a host synchronisation per
@@ -40,10 +49,12 @@ def _c_boxes(boxes):
     return arr
 
 
-def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255, want_labels=True, confmat=None):
+def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255, want_labels=True, confmat=None, out_size=None):
     """The kernel call.  crop_logits (nbox * B, C, h, w) on the device, crop k of image b at row k * B + b; boxes: nbox x
-    (y1, y2, x1, x2); size = (H, W).  -> labels (B, H, W) uint8 or None; with `confmat` (C, C) int64 the counts against
-    `target` (B, H, W) int64 are ADDED to it.  Nothing here waits for the device."""
+    (y1, y2, x1, x2); size = (H, W), the image.  `out_size` = (Ho, Wo): the size of target, labels and counts -- None or the
+    image's: rfn_slide_argmax_confmat; another: rfn_slide_argmax_confmat_resized, the second interpolation of
+    forward(x, out_size) inside the kernel.  -> labels (B, Ho, Wo) uint8 or None; with `confmat` (C, C) int64 the counts
+    against `target` (B, Ho, Wo) int64 are ADDED to it.  Nothing here waits for the device."""
     if not crop_logits.is_cuda:
         raise RuntimeError("evaltail: crop_logits must be a HIP (cuda:N) tensor: refign_amd has no CPU path")
     if crop_logits.dtype not in DTYPE_CODE or crop_logits.dim() != 4:
@@ -53,20 +64,25 @@ def slide_argmax_confmat(crop_logits, boxes, size, target=None, ignore_index=255
     N, C, h, w = crop_logits.shape
     if nbox == 0 or N % nbox:
         raise RuntimeError(f"evaltail: {N} crop logits for {nbox} boxes")
-    B, (H, W) = N // nbox, size
+    B, (H, W) = N // nbox, (int(v) for v in size)
+    Ho, Wo = (H, W) if out_size is None else (int(v) for v in out_size)
     lg = crop_logits.contiguous()
     dev = lg.device
     if target is not None:
-        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W) or target.device != dev:
-            raise RuntimeError(f"evaltail: target ({B}, {H}, {W}) int64 on {dev} expected, got {tuple(target.shape)} "
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, Ho, Wo) or target.device != dev:
+            raise RuntimeError(f"evaltail: target ({B}, {Ho}, {Wo}) int64 on {dev} expected, got {tuple(target.shape)} "
                                f"{target.dtype} on {target.device}")
         target = target.contiguous()
     if confmat is not None and (confmat.dtype != torch.int64 or tuple(confmat.shape) != (C, C) or confmat.device != dev
                                 or not confmat.is_contiguous()):
         raise RuntimeError(f"evaltail: confmat ({C}, {C}) int64 contiguous on {dev} expected")
-    labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_labels else None
-    _lib.call("rfn_slide_argmax_confmat", dev, ptr(lg), DTYPE_CODE[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
-              ptr(target), int(ignore_index), ptr(labels), ptr(confmat))
+    labels =torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev) if want_labels else None
+    if (Ho, Wo) == (H, W):
+        _lib.call("rfn_slide_argmax_confmat", dev, ptr(lg), DTYPE_CODE[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
+                  ptr(target), int(ignore_index), ptr(labels), ptr(confmat))
+    else:
+        _lib.call("rfn_slide_argmax_confmat_resized", dev, ptr(lg), DTYPE_CODE[lg.dtype], B, C, h, w, _c_boxes(boxes), nbox, H, W,
+                  Ho, Wo, ptr(target), int(ignore_index), ptr(labels), ptr(confmat))
     return labels
 
 
@@ -74,25 +90,33 @@ def _size(x, out_size):
     H, W = x.shape[-2:]
     if out_size is not None and tuple(int(v) for v in out_size) != (H, W):
         raise ValueError(f"evaltail: output size {tuple(out_size)} != image size {(H, W)}: the second interpolation of "
-                         f"forward(x, out_size) is not the identity; use forward()")
+                         f"forward(x, out_size) is not the identity; use labels_resized()")
     return H, W
 
 
 @torch.no_grad()
 def labels(model, x, out_size=None):
-    """-> (B, H, W) uint8: arg-max of model.forward(x) without the full-resolution logits.  `out_size`: None or the image size."""
+    """-> (B, H, W) uint8: arg-max of model.forward(x) without the full-resolution logits.  `out_size`: None or the image size
+    (another size: labels_resized)."""
     size = _size(x, out_size)
     logits, boxes = model.crop_logits(x)
     return slide_argmax_confmat(logits, boxes, size)
 
 
 @torch.no_grad()
+def labels_resized(model, x, out_size):
+    """-> (B, Ho, Wo) uint8: arg-max of model.forward(x, out_size) without the logits at the image's or at the output size."""
+    logits, boxes = model.crop_logits(x)
+    return slide_argmax_confmat(logits, boxes, x.shape[-2:], out_size=out_size)
+
+
+@torch.no_grad()
 def confusion(model, x, target, ignore_index=255):
-    """-> (C, C) int64 on the device: counts of (target, arg-max of model.forward(x, target.shape[-2:]))."""
-    size = _size(x, target.shape[-2:])
+    """-> (C, C) int64 on the device: counts of (target, arg-max of model.forward(x, target.shape[-2:])); a target of any size."""
     logits, boxes = model.crop_logits(x)
     out = torch.zeros((logits.shape[1],) * 2, dtype=torch.int64, device=logits.device)
-    slide_argmax_confmat(logits, boxes, size, target, ignore_index, want_labels=False, confmat=out)
+    slide_argmax_confmat(logits, boxes, x.shape[-2:], target, ignore_index, want_labels=False, confmat=out,
+                         out_size=target.shape[-2:])
     return out
 
 
@@ -133,16 +157,17 @@ def _matcher_eval_step(model, metrics, batch, src_name):
 def eval_step(model, metrics, batch, src_name):
     """The fused validation / test step: one kernel call, its count matrix added to every metric of this dataset.  -> True when
     it ran; False when a condition does not hold (RFN_EVAL_FUSED=0; not a segmentation model with crop_logits; tensors not on
-    the device; more than 32 classes; label size != image size; a selected metric that is not an IoU over the head's classes
-    with one common ignore_index; no metric selected) -- the caller then runs the model's own step.  An AlignmentModel takes
-    the matcher's fused step (_matcher_eval_step: one sparse-EPE kernel per batch) under its own conditions."""
+    the device; more than 32 classes; the label not a (B, Ho, Wo) int64 tensor with 0 < B * Ho * Wo < 2^31 -- Ho x Wo need not
+    be the image's size; a selected metric that is not an IoU over the head's classes with one common ignore_index; no metric
+    selected) -- the caller then runs the model's own step.  An AlignmentModel takes the matcher's fused step
+    (_matcher_eval_step: one sparse-EPE kernel per batch) under its own conditions."""
     from .alignment_model import AlignmentModel
     from .metrics import IoU
     if isinstance(model, AlignmentModel):
         return _matcher_eval_step(model, metrics, batch, src_name)
     x, y = batch.get('image'), batch.get('semantic')
-    if not _model_ok(model, x) or not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.int64 or \
-            tuple(y.shape) != (x.shape[0], *x.shape[-2:]):
+    if not _model_ok(model, x) or not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.int64 or y.dim() != 3 or \
+            y.shape[0] != x.shape[0] or not 0 < y.numel() < 2 ** 31:
         return False
     chosen = [m for k, m in metrics.items() if src_name in k]
     C = model.head.num_classes
@@ -155,12 +180,19 @@ def eval_step(model, metrics, batch, src_name):
     return True
 
 
-def predict_step(model, batch, save_dir, orig_size=None, dataset_name=None):
-    """The fused predict step -> the (B, H, W) uint8 label maps written (numpy), or None when a condition does not hold."""
+def predict_step(model, batch, save_dir, orig_size=None, dataset_name=None, resize=False):
+    """The fused predict step -> the (B, H, W) uint8 label maps written (numpy), or None when a condition does not hold.
+    `orig_size` other than the image size: with `resize` the maps come from labels_resized() at that size, without it None."""
     x = batch.get('image')
-    if not _model_ok(model, x) or (orig_size is not None and tuple(int(v) for v in orig_size) != tuple(x.shape[-2:])):
+    if not _model_ok(model, x):
         return None
-    preds = labels(model, x).cpu().numpy()
+    if orig_size is None or tuple(int(v) for v in orig_size) == tuple(x.shape[-2:]):
+        preds = labels(model, x)
+    elif resize:
+        preds = labels_resized(model, x, orig_size)
+    else:
+        return None
+    preds = preds.cpu().numpy()
     if save_dir is not None:
         model.write_label_pngs(preds, batch['filename'], save_dir, dataset_name)
     return preds

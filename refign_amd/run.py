@@ -107,7 +107,9 @@ def main(argv=None, handles=None):
         if len(sizes) > 1:
             raise config.OutOfScopeError(f"refign_amd.run predict: data sets of different original sizes ({sorted(sizes)}): run them "
                                          f"one at a time with --datasets")
-        return trainer.predict(loaders, args.save_dir or ".", orig_size=sizes.pop() if sizes else None)
+        # (fused_resize: the interpolation to the original size happens inside the evaluation tail's kernel; RFN_EVAL_FUSED=0
+        # keeps model.predict_step)
+        return trainer.predict(loaders, args.save_dir or ".", orig_size=sizes.pop() if sizes else None, fused_resize=True)
     finally:
         if handles is not None:
             handles.update(trainer=trainer, datamodule=dm)

@@ -938,16 +938,19 @@ class Trainer:
         """Lightning's `test`: as validate(), through test_step / test_epoch_end and the model's test metrics."""
         return self._metric_loop("test", loaders)
 
-    def predict(self, loaders, save_dir, orig_size=None):
+    def predict(self, loaders, save_dir, orig_size=None, fused_resize=False):
         """Lightning's `predict`: arg-max label maps of every batch (`image`, `filename`) as PNGs under
         `<save_dir>/preds/<dataset>/<filename>` and `<save_dir>/color_preds/<dataset>/<filename>` (segmentation_model.py:
         283-302; no sub-directory for a bare iterable).  `orig_size`: the size the predictions are interpolated to (the
-        reference's datamodule.predict_ds[i].orig_dims); None: the image size.  -> the number of files written."""
+        reference's datamodule.predict_ds[i].orig_dims); None: the image size.  An `orig_size` other than the image size goes
+        through model.predict_step, or with `fused_resize` through the fused evaluation tail as well (evaltail.labels_resized:
+        the interpolation to `orig_size` inside the kernel; under 16-bit autocast it keeps fp32 where predict_step rounds its
+        intermediate logits).  -> the number of files written."""
         from . import evaltail
         model, written = self.model, [0]
 
         def per_batch(batch, i, idx, name):
-            preds = evaltail.predict_step(model, batch, save_dir, orig_size, name or None)
+            preds = evaltail.predict_step(model, batch, save_dir, orig_size, name or None, resize=fused_resize)
             if preds is None:
                 preds = model.predict_step(batch, i, idx, save_dir=save_dir, orig_size=orig_size, dataset_name=name or None)
             written[0] += 2 * len(preds) if save_dir is not None else 0
