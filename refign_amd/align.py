@@ -183,18 +183,13 @@ class UncertaintyModule(nn.Module):
             return y.view(b, c, h, k + 2, w, k + 2)[:, :, :, :k, :, :k].reshape(b, c, k * h, k * w)
 
         from . import bn as bnk
-        from .params import compute_dtype
+        from .conv import activate, conv2d
         x = corr.view(b, 9, 9, h, w).permute(0, 3, 1, 4, 2).reshape(b, 1, 9 * h, 9 * w)
         for m, k in ((self.conv_0, 7), (self.conv_1, 5), (self.conv_2, 3)):
-            x = retile(m._conv2d(x, m.conv.weight, m.conv.bias), k)
-            cd = compute_dtype(x)
-            if m.use_norm and m.act == 'leaky' and m.act_slope == LEAKY_SLOPE and x.is_cuda and \
-                    os.environ.get("RFN_BN_KERNEL", "1") != "0" and bnk.usable(x, m.bn, cd):
-                x = bnk.bn_act_train(x, m.bn, 3, cd)         # BatchNorm(train) + LeakyReLU in two passes (csrc/bn.hip)
-                continue
-            if m.use_norm:
-                x = m.bn(x)
-            x = F.leaky_relu(x, m.act_slope, inplace=True) if m.act == 'leaky' else F.relu(x, inplace=True)
+            c = m.conv
+            x = retile(conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, c.groups), k)
+            # BatchNorm(train) + LeakyReLU of the re-tiled image in two passes (csrc/bn.hip) where they apply
+            x = bnk.bn_act(x, m.bn, m.act, m.act_slope) if m.use_norm else activate(x, m.act, m.act_slope)
         y = self.predict_uncertainty(x)                                                    # (b, 6, 3 h - 2, 3 w - 2)
         return F.pad(y, (0, 2, 0, 2)).view(b, 6, h, 3, w, 3)[:, :, :, 0, :, 0]
 

@@ -12,10 +12,13 @@ backward; the affine gradients are the local sums, averaged over the ranks with 
 collectives are ordinary torch.distributed calls on the module's process group: RCCL calls are capturable, so the passes
 stay replayable from hipGraphs (tools/micro/rccl_capture.py).
 """
+import os
+
 import torch
 import torch.distributed as dist
 
 from . import _lib, determinism
+from .conv import ACT_CODE, act_fusable, activate
 from ._tensor import ptr, workspace
 from ._tensor import DTYPE_CODE16 as _DT16          # (the name the GPU tests read the codes under)
 from .params import grad_sink
@@ -26,7 +29,6 @@ def data_parallel():
     RFN_DDP_REHEARSAL=1, which makes every exchange of the N > 1 step for real on the one GPU of a development box
     (SyncBatchNorm all-reduces inside the captured student passes, the communicators of the teacher and of the mixed
     pass, the flat gradient all-reduce): everything but the link traffic and the waiting for peers."""
-    import os
     if not (dist.is_available() and dist.is_initialized()):
         return False
     return dist.get_world_size() > 1 or os.environ.get("RFN_DDP_REHEARSAL", "0") == "1"
@@ -48,7 +50,6 @@ def ddp_mode():
     `direct` / `direct3` have only ever run with ONE rank (RFN_DDP_REHEARSAL=1 on a one-GPU box): concurrent communicators on
     one device can deadlock if two ranks' queues serialise their collectives in different orders, which no one-rank run can
     show -- they stay opt-in until a multi-GPU run has passed tools/ddp_first_contact.sh."""
-    import os
     m = os.environ.get("RFN_DDP_MODE", "torch")
     if m not in DDP_MODES:
         raise RuntimeError(f"RFN_DDP_MODE={m!r}: one of {DDP_MODES}")
@@ -99,6 +100,22 @@ def sync_group(bn):
     if not isinstance(bn, torch.nn.SyncBatchNorm) or not data_parallel():
         return None
     return bn.process_group if bn.process_group is not None else dist.group.WORLD
+
+
+def kernel_enabled():
+    """RFN_BN_KERNEL=0: BatchNorm(train) stays on the library everywhere (read at call time: tests flip it)."""
+    return os.environ.get("RFN_BN_KERNEL", "1") != "0"
+
+
+def fold(weight, bias, bn):
+    """(weight, bias) of a convolution with the eval-mode BatchNorm `bn` behind it folded in."""
+    inv = torch.rsqrt(bn.running_var + bn.eps)
+    g = inv if bn.weight is None else bn.weight * inv
+    shift = -bn.running_mean * g
+    if bn.bias is not None:
+        shift = shift + bn.bias
+    b = shift if bias is None else bias * g + shift
+    return (weight * g.view(-1, 1, 1, 1)).detach().contiguous(), b.detach().contiguous()
 
 
 def usable(x, bn, dtype, channels=None, count=None):
@@ -343,3 +360,16 @@ def bn_act_train_cat(xs, bns, relu, dtype):
     for x, bn in zip(xs, bns):
         tensors += _operands(x, bn, dtype)
     return _BNActCat.apply(list(bns), relu, *tensors).permute(0, 3, 1, 2)
+
+
+def bn_act(y, bn, act, slope=0.0, note=False):
+    """act(bn(y)) of an already computed convolution result `y`: the fused BatchNorm(train) + activation passes where they apply
+    (kernel_enabled, act_fusable, usable), else the modules; `note`: the library BatchNorm is recorded (mfma.note_library)."""
+    from .params import compute_dtype
+    cd = compute_dtype(y)
+    if y.is_cuda and kernel_enabled() and act_fusable(act, slope) and usable(y, bn, cd):
+        return bn_act_train(y, bn, ACT_CODE[act], cd)
+    if note:
+        from .mfma import note_library
+        note_library("batch_norm", y)                      # (no-op for CPU tensors)
+    return activate(bn(y), act, slope)

@@ -1,5 +1,6 @@
 """nn.Conv2d for the MiT patch-embedding / spatial-reduction convolutions, with the parameter plumbing of params.py.
 
+conv2d() below is the one dispatcher of a convolution (Conv2d, layers.ConvBNReLU, seg._class_logits and align call it).
 On a GPU the convolution runs on the hand-written kernels: the implicit-GEMM MFMA kernel (conv2d_mfma: forward; conv2d_mfma_grad:
 forward + data gradient + weight gradient under autograd), the patch GEMM for kernel == stride (patch_conv_tokens), split-bf16
 products for fp32 tensors (split32.conv2d).  Weights are used through cached 16-bit copies (params.derived) refreshed in place after
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import mfma as _mfma
-from ._tensor import DTYPE_CODE, ptr
+from ._tensor import DTYPE_CODE, DTYPE_CODE16, ptr
 from .params import _identity, as_dtype, channels_last, compute_dtype, derived, grad_sink, nhwc_view, patch_linear, \
     patch_linear_t
 
@@ -55,38 +56,100 @@ class _Conv2dFn(torch.autograd.Function):
         return gx, gw, gb, None, None, None, None, None, None
 
 
+# Activation codes of the GEMM / convolution / BatchNorm entry points (include/refign_hip.h), by ConvBNReLU.act
+ACT_CODE = {None: 0, 'relu': 1, 'leaky': 3}
+LEAKY_SLOPE = 0.1   # activation_layer = partial(nn.LeakyReLU, negative_slope=0.1)  (modules.py:407,459,498): code 3's slope
+
+
+def act_fusable(act, slope=0.0):
+    """The kernels' epilogues can apply this activation: none, ReLU, or LeakyReLU with the one slope they know."""
+    return act in (None, 'relu') or (act == 'leaky' and slope == LEAKY_SLOPE)
+
+
+def activate(y, act, slope=0.0):
+    """`act` applied in place, as a pass of its own."""
+    if act == 'leaky':
+        return F.leaky_relu(y, slope, inplace=True)
+    return F.relu(y, inplace=True) if act == 'relu' else y
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else v if isinstance(v, str) else (v, v)
+
+
+def is_depthwise3x3(weight, stride, padding, dilation, groups):
+    """The shapes of the channels-last depthwise stencil (csrc/dwconv.hip): one filter per channel, 3x3, stride 1, 'same' padding
+    by one dilation, channels a multiple of 8."""
+    N, Cg, KH, KW = weight.shape
+    d = _pair(dilation)
+    return groups == N and Cg == 1 and (KH, KW) == (3, 3) and _pair(stride) == (1, 1) and _pair(padding) == d and d[0] == d[1] \
+        and N % 8 == 0
+
+
+def conv2d(x, weight, bias, stride, padding, dilation, groups=1, *, act=None, slope=0.0, stats=None, module=False, needs_grad=None):
+    """activate(F.conv2d(x, weight, bias, stride, padding, dilation, groups), act, slope): THE place that chooses the kernel of a
+    convolution, and the only one that records a library convolution (mfma.note_library).  On the GPU, in this order:
+      depthwise 3x3            the channels-last HIP stencil (the library's grouped path for group size 1 is ~50x off the HBM
+                               roofline); `stats`: it leaves the batch statistics of its result behind (csrc/dwconv.hip STATS)
+      fp32 operands, groups 1  split-bf16 products (split32.conv2d: fp32 parity mode)
+      16-bit pass, groups 1    the implicit-GEMM kernels: conv2d_mfma_grad where a gradient is needed, else conv2d_mfma
+      anything else            the ROCm library, recorded -- that includes a 16-bit call in grad mode whose operands need no
+                               gradient (a frozen layer outside no_grad): conv2d_mfma is for gradient-free passes only
+    Gradient-free calls get a fusable activation (act_fusable) in the kernel's epilogue; otherwise it is a pass of its own.
+    "fp32 operands" is compute_dtype(x) == float32: torch switches a float32 cuda autocast region off, so this is "x is fp32
+    outside autocast", the test split32.usable completes.
+    module      the call is conv.Conv2d's forward on its own parameters.  A library call then uses the cached channels-last 16-bit
+                filter and _Conv2dFn (gradients added straight into the flat buffer) and is recorded by whether a gradient is
+                needed, not by the grad mode; and depthwise shapes stay on the library, where this class has always run them.
+    needs_grad  default: grad mode and x or weight requires a gradient.  A training-mode block passes the grad mode alone
+                (ConvBNReLU.pre_norm: its operands train), which keeps a frozen block inside enable_grad on the kernels."""
+    if not x.is_cuda:
+        return activate(F.conv2d(x, weight, bias, stride, padding, dilation, groups), act, slope)
+    grad_mode = torch.is_grad_enabled()
+    fuse = act is not None and not grad_mode and act_fusable(act, slope)
+    if not module and is_depthwise3x3(weight, stride, padding, dilation, groups):
+        from .dwconv import dwconv3x3_nhwc
+        xh = x.permute(0, 2, 3, 1)                       # free for channels_last inputs
+        y = dwconv3x3_nhwc(xh if xh.is_contiguous() else xh.contiguous(), weight, bias, _pair(dilation)[0], stats=stats)
+        return activate(y.permute(0, 3, 1, 2), act, slope)   # NCHW-shaped, channels_last strides
+    if stats is not None:
+        raise RuntimeError("conv2d(stats=...): depthwise 3x3 on the HIP kernel only")
+    if needs_grad is None:
+        needs_grad = grad_mode and (x.requires_grad or weight.requires_grad)
+    cd = compute_dtype(x)
+    y = None
+    if groups == 1 and cd == torch.float32 and _split32().usable(x):
+        y = _split32().conv2d(x, weight, bias, stride, padding, dilation, act=ACT_CODE[act] if fuse else 0)
+    if y is None and module:
+        # the MiT token tensors reach the convolutions as channels-last views, and the library then wants the filter in
+        # channels-last too: keep the cached copy in that layout instead of converting it at every call
+        w_c, b_c = channels_last(weight, cd), as_dtype(bias, cd)
+        if x.dtype != cd:
+            x = x.to(cd)
+    if y is None and groups == 1 and cd in DTYPE_CODE16:
+        if needs_grad:
+            y, fuse = conv2d_mfma_grad(x, weight, bias, stride, padding, dilation, cd), False
+        elif not grad_mode:                                  # (conv2d_mfma is the gradient-free kernel path and says so itself)
+            y = conv2d_mfma(x, weight, bias, stride, padding, dilation, act=act if fuse else None, dtype=cd)
+    if y is not None:
+        return y if fuse else activate(y, act, slope)
+    if module:
+        _mfma.note_library("conv2d.autograd" if needs_grad else "conv2d", x, weight)
+        if needs_grad:
+            y = _Conv2dFn.apply(x, weight, bias, w_c, b_c, stride, padding, dilation, groups)
+        else:
+            y = F.conv2d(x, w_c, b_c, stride, padding, dilation, groups)
+    else:
+        _mfma.note_library("conv2d.autograd" if grad_mode else "conv2d", x, weight)
+        y = F.conv2d(x, weight, bias, stride, padding, dilation, groups)
+    return activate(y, act, slope)
+
+
 class Conv2d(nn.Conv2d):
     def forward(self, x):
         if not x.is_cuda or self.padding_mode != 'zeros' or isinstance(self.padding, str):
             return super().forward(x)
-        cd = compute_dtype(x)
-        if cd == torch.float32 and self.groups == 1:
-            # fp32 parity mode: split-bf16 products on the matrix-core kernels (refign_amd/split32.py)
-            from . import split32
-            if split32.usable(x):
-                y = split32.conv2d(x.float(), self.weight, self.bias, self.stride, self.padding, self.dilation)
-                if y is not None:
-                    return y
-        # the MiT token tensors reach the convolutions as channels-last views, and the library then wants the filter in
-        # channels-last too: keep the cached copy in that layout instead of converting it at every call
-        w_c = channels_last(self.weight, cd)
-        b_c = as_dtype(self.bias, cd)
-        if x.dtype != cd:
-            x = x.to(cd)
-        if torch.is_grad_enabled() and (self.weight.requires_grad or x.requires_grad):
-            if self.groups == 1:
-                y = conv2d_mfma_grad(x, self.weight, self.bias, self.stride, self.padding, self.dilation, cd)
-                if y is not None:
-                    return y
-            _mfma.note_library("conv2d.autograd", x, self.weight)
-            return _Conv2dFn.apply(x, self.weight, self.bias, w_c, b_c, self.stride, self.padding, self.dilation,
-                                   self.groups)
-        if self.groups == 1 and not torch.is_grad_enabled():
-            y = conv2d_mfma(x, self.weight, self.bias, self.stride, self.padding, self.dilation, dtype=cd)
-            if y is not None:
-                return y
-        _mfma.note_library("conv2d", x, self.weight)
-        return F.conv2d(x, w_c, b_c, self.stride, self.padding, self.dilation, self.groups)
+        return conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups, module=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -268,7 +331,6 @@ def patch_conv_tokens(x, H, W, conv):
 # Tensors keep their NCHW SHAPE and carry channels-last strides between layers, so consecutive layers hand each other
 # NHWC memory without a copy; bias, folded BatchNorm and ReLU / LeakyReLU ride in the epilogue.
 # ---------------------------------------------------------------------------------------------------------------------
-_ACT = {None: 0, 'relu': 1, 'leaky': 3}
 _CONV_MFMA = True
 
 
@@ -448,7 +510,7 @@ def conv2d_mfma(x, weight, bias, stride=1, padding=0, dilation=1, act=None, dtyp
             xh = buf
         else:
             xh = xh.to(dtype).contiguous()
-    y = _mfma.conv2d_nhwc(xh, wp, bp, KH, KW, s, p, d, act=_ACT[act])
+    y = _mfma.conv2d_nhwc(xh, wp, bp, KH, KW, s, p, d, act=ACT_CODE[act])
     if y is None:
         return None
     if y.shape[-1] != N:

@@ -3,16 +3,15 @@
 These hold parameters under the same state_dict keys as the reference (`conv.weight`, `bn.running_mean`,
 `depthwise_conv.conv.weight`, `pointwise_conv.bn.bias`, `proj.weight`) and execute either the training formulation
 (conv -> BatchNorm with batch statistics -> activation) or, for frozen/eval networks under no_grad, a folded one
-(BatchNorm merged into the conv weights once, activation applied in place on the conv output).
+(BatchNorm merged into the conv weights once, activation in the convolution kernel's epilogue).  ConvBNReLU.route() says
+which; conv.conv2d chooses the convolution's kernel.
 """
-import os
-
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-LEAKY_SLOPE = 0.1   # activation_layer = partial(nn.LeakyReLU, negative_slope=0.1)  (modules.py:407,459,498)
-
+from . import bn as bnk
+from .conv import ACT_CODE, LEAKY_SLOPE, act_fusable, activate, conv2d, is_depthwise3x3   # noqa: F401  (LEAKY_SLOPE: align.py)
+from .params import compute_dtype
 
 _DW_BN_STATS = True
 _DW_BN_FUSED = True
@@ -55,17 +54,9 @@ class ConvBNReLU(nn.Module):
     def folded(self):
         """(weight, bias) with eval-mode BatchNorm folded in; cached until train() / load_state_dict()."""
         if self._folded is None:
-            w, b = self.conv.weight, self.conv.bias
-            if self.use_norm:
-                bn = self.bn
-                inv = torch.rsqrt(bn.running_var + bn.eps)
-                g = inv if bn.weight is None else bn.weight * inv
-                w = w * g.view(-1, 1, 1, 1)
-                shift = -bn.running_mean * g
-                if bn.bias is not None:
-                    shift = shift + bn.bias
-                b = shift if b is None else b * g + shift
-            self._folded = (w.detach().contiguous(), None if b is None else b.detach().contiguous())
+            c = self.conv
+            self._folded = bnk.fold(c.weight, c.bias, self.bn) if self.use_norm else \
+                (c.weight.detach().contiguous(), None if c.bias is None else c.bias.detach().contiguous())
         return self._folded
 
     def train(self, mode=True):
@@ -80,6 +71,12 @@ class ConvBNReLU(nn.Module):
         self._folded = None
         return super()._apply(fn, *a, **k)
 
+    # -- what a caller may ask of a block ----------------------------------------------------------------------------
+    @property
+    def last(self):
+        """the module whose BatchNorm + activation ends this block"""
+        return self.pointwise_conv if self.depthwise_separable else self
+
     def _out_count(self, x):
         """values per channel of this block's convolution result on `x` (batch x OH x OW)"""
         c = self.conv
@@ -89,50 +86,31 @@ class ConvBNReLU(nn.Module):
             n *= max(0, (x.shape[2 + i] + 2 * pad - c.dilation[i] * (c.kernel_size[i] - 1) - 1) // c.stride[i] + 1)
         return n
 
-    def _conv2d(self, x, w, b, stats=None):
-        """The convolution itself.  Depthwise 3x3 (the DAFormer ASPP branches) goes to the hand-written channels-last
-        HIP kernel on the GPU -- the library's grouped-conv path for group size 1 is ~50x off the HBM roofline; every
-        other shape is a dense conv on the ROCm library."""
-        c = self.conv
-        if (x.is_cuda and c.groups == c.in_channels == c.out_channels and c.kernel_size == (3, 3)
-                and c.stride == (1, 1) and c.padding == c.dilation and c.dilation[0] == c.dilation[1]
-                and c.in_channels % 8 == 0):
-            from .dwconv import dwconv3x3_nhwc
-            xh = x.permute(0, 2, 3, 1)                       # free for channels_last inputs
-            y = dwconv3x3_nhwc(xh if xh.is_contiguous() else xh.contiguous(), w, b, c.dilation[0], stats=stats)
-            return y.permute(0, 3, 1, 2)                     # NCHW-shaped, channels_last strides
-        if stats is not None:
-            raise RuntimeError("ConvBNReLU._conv2d(stats=...): depthwise 3x3 on the HIP kernel only")
-        if x.is_cuda:
-            from . import mfma, split32
-            if c.groups == 1 and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda") and split32.usable(x):
-                y = split32.conv2d(x, w, b, c.stride, c.padding, c.dilation)     # fp32 parity mode (split-bf16 products)
-                if y is not None:
-                    return y
-            from .params import compute_dtype
-            cd = compute_dtype(x)
-            if c.groups == 1 and cd in (torch.float16, torch.bfloat16):
-                # blocks without a norm layer / with a BatchNorm the fused kernel does not take (the matcher's decoders,
-                # refinement and uncertainty networks under fp16 autocast -- alignment_model.py:81-146, SURVEY row N1):
-                # forward, data and weight gradient on the implicit-GEMM kernels, as the student's 3x3 bottleneck
-                from .conv import conv2d_mfma, conv2d_mfma_grad
-                if torch.is_grad_enabled() and (x.requires_grad or w.requires_grad):
-                    y = conv2d_mfma_grad(x, w, b, c.stride, c.padding, c.dilation, cd)
-                else:
-                    y = conv2d_mfma(x, w, b, c.stride, c.padding, c.dilation, dtype=cd)
-                if y is not None:
-                    return y
-            mfma.note_library("conv2d.autograd" if torch.is_grad_enabled() else "conv2d", x, w)
-        return F.conv2d(x, w, b, c.stride, c.padding, c.dilation, c.groups)
+    def _bn_kernel(self, x):
+        """BatchNorm(train) + activation of this (plain) block's convolution on `x` go on csrc/bn.hip: THE predicate behind
+        bn_kernel_ok, fused_out_ok and route()."""
+        return (x.is_cuda and self.use_norm and self.training and act_fusable(self.act, self.act_slope) and bnk.kernel_enabled()
+                and bnk.usable(x, self.bn, compute_dtype(x), channels=self.conv.out_channels, count=self._out_count(x)))
 
-    def _conv_train(self, x, cd):
-        """The convolution of a training-mode block on the GPU in the 16-bit compute dtype `cd`.  1x1 (the ASPP / fusion
-        projections): a Linear over channels-last tokens on the MFMA GEMM kernels, forward and both gradients; depthwise
-        3x3: the HIP stencil; dense k x k without autograd (EMA teacher): the implicit-GEMM kernel; dense k x k under
-        autograd (the student's 3x3 bottleneck): the library convolution."""
+    def bn_kernel_ok(self, x):
+        """forward(x) of this block ends in the fused BatchNorm(train) + activation pass (csrc/bn.hip) -- the pass that takes
+        the decode heads' Dropout2d with it (forward(x, drop=...)) and whose input a caller may compute itself (pre_norm)."""
+        return not self.depthwise_separable and self._bn_kernel(x)
+
+    def fused_out_ok(self, x):
+        """forward(x, out=...) is available: gradient-free, training-mode BatchNorm on the fused kernel (the EMA teacher's
+        decode head) -- the block's result can be written straight into a channel slice of a wider tensor."""
+        m = self.last
+        return not torch.is_grad_enabled() and m.act in (None, 'relu') and m._bn_kernel(x)
+
+    def pre_norm(self, x, cd):
+        """The convolution of a training-mode block on the GPU in the 16-bit compute dtype `cd`: what the fused BatchNorm pass
+        normalises.  1x1 (the ASPP / fusion projections): a Linear over channels-last tokens on the MFMA GEMM kernels, forward
+        and both gradients -- a route of the block, since it pays only where a BatchNorm pass reads the tokens next; every other
+        shape: conv.conv2d (depthwise 3x3: the HIP stencil; dense k x k: the implicit-GEMM kernels)."""
         c = self.conv
-        # (under autograd the Linear's gradient GEMMs want N % 64 == 0; other widths take the implicit-GEMM path below, which
-        # pads its output channels itself)
+        # (under autograd the Linear's gradient GEMMs want N % 64 == 0; other widths take the implicit-GEMM path, which pads its
+        # output channels itself)
         if c.groups == 1 and c.kernel_size == (1, 1) and c.stride == (1, 1) and c.padding == (0, 0) and \
                 c.in_channels % 64 == 0 and c.out_channels % (64 if torch.is_grad_enabled() else 8) == 0:
             from .linear import linear_tokens
@@ -144,139 +122,100 @@ class ConvBNReLU(nn.Module):
             B, H, W, C = xh.shape
             y = linear_tokens(xh.reshape(B * H * W, C), c.weight, c.bias, cd)
             return y.view(B, H, W, -1).permute(0, 3, 1, 2)
-        if c.groups == 1 and not torch.is_grad_enabled():
-            from .conv import conv2d_mfma
-            y = conv2d_mfma(x, c.weight, c.bias, c.stride, c.padding, c.dilation, dtype=cd)
-            if y is not None:
-                return y
-        if c.groups == 1 and torch.is_grad_enabled():
-            # dense k x k under autograd (the student's 3x3 bottleneck): forward, data and weight gradient on the implicit-GEMM
-            # kernels (conv._ConvMfmaFn)
-            from .conv import conv2d_mfma_grad
-            y = conv2d_mfma_grad(x, c.weight, c.bias, c.stride, c.padding, c.dilation, cd)
-            if y is not None:
-                return y
-        return self._conv2d(x, c.weight, c.bias)
+        return conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, c.groups, needs_grad=torch.is_grad_enabled())
 
-    def fused_out_ok(self, x):
-        """forward(x, out=...) is available: gradient-free, training-mode BatchNorm on the fused kernel (the EMA teacher's
-        decode head) -- the block's result can be written straight into a channel slice of a wider tensor."""
-        m = self.pointwise_conv if self.depthwise_separable else self
-        if not (x.is_cuda and not torch.is_grad_enabled() and m.use_norm and m.training and m.act in (None, 'relu')
-                and os.environ.get("RFN_BN_KERNEL", "1") != "0"):
+    # -- one route decision, one body per route ----------------------------------------------------------------------
+    ROUTES = ("parts-split32", "separable", "bn-kernel", "folded", "plain")
+
+    def route(self, x, out=None, drop=None):
+        """Which body forward(x, out, drop) runs (ROUTES); the kernel of the convolution inside it is conv.conv2d's choice.
+          parts-split32  a list of fp32 parts, gradient-free, eval-mode or no BatchNorm: the parts go straight into the split-bf16
+                         convolution's operand (a list outside that domain is routed as its concatenation)
+          separable      depthwise block, then pointwise block
+          bn-kernel      convolution (pre_norm, or the depthwise stencil with statistics), then ONE fused BatchNorm(train) +
+                         activation pass (csrc/bn.hip); the only route that takes out= and drop=
+          folded         gradient-free, BatchNorm in eval mode: folded into the weights, activation in the kernel's epilogue
+          plain          convolution, the BatchNorm module if there is one, activation
+        Raises where forward does (drop= off the bn-kernel route)."""
+        parts = isinstance(x, (list, tuple))
+        if drop is not None:
+            if parts or not self.bn_kernel_ok(x):
+                raise RuntimeError("ConvBNReLU(drop=...): on the fused BatchNorm(train) pass only (bn_kernel_ok)")
+            return "bn-kernel"
+        if parts:
+            if self._parts_ok(x, out):
+                return "parts-split32"
+            x = x[0]                       # device, dtype and (B, H, W) of the concatenation
+        if self.depthwise_separable:
+            return "separable"
+        if out is not None or self._bn_kernel(x):     # out=: the caller asked fused_out_ok
+            return "bn-kernel"
+        return "folded" if self.use_norm and not self.training and not torch.is_grad_enabled() else "plain"
+
+    def forward(self, x, out=None, drop=None):
+        # out: a channel slice of a wider channels-last tensor for the result -- where fused_out_ok(x) holds
+        # drop: (B, C, 1, 1) Dropout2d multipliers folded into the BatchNorm pass -- only where bn_kernel_ok(x) holds
+        r = self.route(x, out, drop)
+        if isinstance(x, (list, tuple)):
+            # a channel concatenation handed over as its parts (the matcher's decoders: cat(correlation, flow, ...))
+            if r == "parts-split32":
+                return self._run_parts(x)
+            x = torch.cat(list(x), 1)
+        if r == "separable":
+            return self.pointwise_conv(self.depthwise_conv(x), out=out)
+        if r == "bn-kernel":
+            return self._run_bn_kernel(x, out, drop)
+        # folded / plain.  The frozen matcher's blocks are ONE launch: folded norm in the weights, bias and ReLU / LeakyReLU in the
+        # epilogue of the implicit-GEMM kernel (16-bit) or of the split-bf16 one (fp32: parity mode, align.HEAD_SPLIT)
+        c = self.conv
+        w, b = self.folded() if r == "folded" else (c.weight, c.bias)
+        if self.use_norm and r == "plain":
+            return activate(self.bn(conv2d(x, w, b, c.stride, c.padding, c.dilation, c.groups)), self.act, self.act_slope)
+        return conv2d(x, w, b, c.stride, c.padding, c.dilation, c.groups, act=self.act, slope=self.act_slope)
+
+    def _parts_ok(self, x, out):
+        c = getattr(self, "conv", None)
+        if not (c is not None and out is None and x[0].is_cuda and c.groups == 1 and not torch.is_grad_enabled()
+                and (not self.use_norm or not self.training) and act_fusable(self.act, self.act_slope)
+                and all(t.dtype == torch.float32 for t in x) and not torch.is_autocast_enabled("cuda")
+                and c.stride[0] == c.stride[1] and c.padding[0] == c.padding[1] and c.dilation[0] == c.dilation[1]):
             return False
-        from . import bn as bnk
-        from .params import compute_dtype
-        return bnk.usable(x, m.bn, compute_dtype(x), channels=m.conv.out_channels, count=m._out_count(x))
+        from . import split32
+        return split32.usable(*x) and split32.parts_ok(x, c.weight)
+
+    def _run_parts(self, x):
+        """split32.conv2d_parts on the parts (_parts_ok has asked for its whole domain)"""
+        from . import split32
+        c = self.conv
+        w, b = self.folded() if self.use_norm else (c.weight, c.bias)
+        y = split32.conv2d_parts(list(x), w, b, c.stride[0], c.padding[0], c.dilation[0], act=ACT_CODE[self.act])
+        if y is None:
+            raise RuntimeError("ConvBNReLU: split32.conv2d_parts declined a call that split32.parts_ok admits")
+        return y
 
     def _dw_stats_ok(self, x, cd):
         """depthwise 3x3 -> BatchNorm(train): the convolution kernel leaves the batch statistics of its result behind
         (csrc/dwconv.hip STATS), the BatchNorm skips its statistics pass.  (_DW_BN_STATS = False: two passes.)"""
         c = self.conv
         return (_DW_BN_STATS and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and cd == x.dtype
-                and c.groups == c.in_channels == c.out_channels and c.kernel_size == (3, 3) and c.stride == (1, 1)
-                and c.padding == c.dilation and c.dilation[0] == c.dilation[1] and c.in_channels % 8 == 0)
+                and is_depthwise3x3(c.weight, c.stride, c.padding, c.dilation, c.groups))
 
-    def bn_kernel_ok(self, x):
-        """forward(x) of this block ends in the fused BatchNorm(train) + activation pass (csrc/bn.hip) -- the pass that takes
-        the decode heads' Dropout2d with it (forward(x, drop=...)) and whose input a caller may compute itself (pre_norm)."""
-        if self.depthwise_separable or not (x.is_cuda and self.use_norm and self.training and os.environ.get("RFN_BN_KERNEL", "1") != "0"
-                                            and (self.act in (None, 'relu') or (self.act == 'leaky' and self.act_slope == LEAKY_SLOPE))):
-            return False
-        from . import bn as bnk
-        from .params import compute_dtype
-        return bnk.usable(x, self.bn, compute_dtype(x), channels=self.conv.out_channels, count=self._out_count(x))
-
-    def _bn_train(self, x, cd, out=None, drop=None):
-        from . import bn as bnk
-        act = {None: 0, 'relu': 1, 'leaky': 3}[self.act]
-        if drop is not None:
-            return bnk.bn_act_train(self._conv_train(x, cd), self.bn, act, cd, out=out, drop=drop)
-        if self._dw_stats_ok(x, cd) and not torch.is_grad_enabled() and out is None and act in (0, 1) and _DW_BN_FUSED \
-                and self.bn.momentum is not None:
-            # gradient-free (EMA teacher): statistics pass without a store, then convolution + BatchNorm + ReLU in one pass
-            from .dwconv import dwconv3x3_bn_act_nhwc
-            c = self.conv
-            xh = x.permute(0, 2, 3, 1)
-            y = dwconv3x3_bn_act_nhwc(xh if xh.is_contiguous() else xh.contiguous(), c.weight, c.bias, c.dilation[0], self.bn,
-                                      act == 1)
-            return y.permute(0, 3, 1, 2)
-        if self._dw_stats_ok(x, cd):
-            c = self.conv
+    def _run_bn_kernel(self, x, out=None, drop=None):
+        cd, act, c = compute_dtype(x), ACT_CODE[self.act], self.conv
+        if drop is None and self._dw_stats_ok(x, cd):
+            if not torch.is_grad_enabled() and out is None and act in (0, 1) and _DW_BN_FUSED and self.bn.momentum is not None:
+                # gradient-free (EMA teacher): statistics pass without a store, then convolution + BatchNorm + ReLU in one pass
+                from .dwconv import dwconv3x3_bn_act_nhwc
+                xh = x.permute(0, 2, 3, 1)
+                y = dwconv3x3_bn_act_nhwc(xh if xh.is_contiguous() else xh.contiguous(), c.weight, c.bias, c.dilation[0], self.bn,
+                                          act == 1)
+                return y.permute(0, 3, 1, 2)
             sums = torch.empty(2 * c.out_channels + 1, dtype=torch.float64, device=x.device)
-            return bnk.bn_act_train(self._conv2d(x, c.weight, c.bias, stats=sums), self.bn, act, cd, out=out, sums=sums)
-        return bnk.bn_act_train(self._conv_train(x, cd), self.bn, act, cd, out=out)
-
-    def forward(self, x, out=None, drop=None):
-        # drop: (B, C, 1, 1) Dropout2d multipliers folded into the BatchNorm pass -- only where bn_kernel_ok(x) holds
-        if drop is not None:
-            from .params import compute_dtype
-            if isinstance(x, (list, tuple)) or not self.bn_kernel_ok(x):
-                raise RuntimeError("ConvBNReLU(drop=...): on the fused BatchNorm(train) pass only (bn_kernel_ok)")
-            return self._bn_train(x, compute_dtype(x), out=out, drop=drop)
-        if isinstance(x, (list, tuple)):
-            # a channel concatenation handed over as its parts (the matcher's decoders: cat(correlation, flow, ...)): on the
-            # gradient-free split-bf16 path the parts go straight into the convolution's operand (split32.conv2d_parts)
-            c = getattr(self, "conv", None)
-            if c is not None and out is None and x[0].is_cuda and c.groups == 1 and not torch.is_grad_enabled() \
-                    and (not self.use_norm or not self.training) and self.act_slope in (0.0, LEAKY_SLOPE) \
-                    and all(t.dtype == torch.float32 for t in x) and not torch.is_autocast_enabled("cuda") \
-                    and c.stride[0] == c.stride[1] and c.padding[0] == c.padding[1] and c.dilation[0] == c.dilation[1]:
-                from . import split32
-                if split32.usable(*x):
-                    w, b = self.folded() if self.use_norm else (c.weight, c.bias)
-                    y = split32.conv2d_parts(list(x), w, b, c.stride[0], c.padding[0], c.dilation[0],
-                                             act={None: 0, 'relu': 1, 'leaky': 3}[self.act])
-                    if y is not None:
-                        return y
-            x = torch.cat(list(x), 1)
-        if self.depthwise_separable:
-            return self.pointwise_conv(self.depthwise_conv(x), out=out)
-        c = self.conv
-        if out is not None:
-            from .params import compute_dtype
-            return self._bn_train(x, compute_dtype(x), out=out)
-        if x.is_cuda and c.groups == 1 and not torch.is_grad_enabled() and (not self.use_norm or not self.training) \
-                and self.act_slope in (0.0, LEAKY_SLOPE):
-            # gradient-free, BatchNorm in eval mode (the frozen matcher): ONE launch of the hand-written implicit-GEMM
-            # kernel -- folded norm in the weights, bias and ReLU / LeakyReLU in its epilogue (refign_amd/conv.py)
-            from .conv import conv2d_mfma
-            from .params import compute_dtype
-            w, b = self.folded() if self.use_norm else (c.weight, c.bias)
-            y = conv2d_mfma(x, w, b, c.stride, c.padding, c.dilation, act=self.act, dtype=compute_dtype(x))
-            if y is not None:
-                return y
-        if x.is_cuda and c.groups == 1 and not torch.is_grad_enabled() and (not self.use_norm or not self.training) \
-                and self.act_slope in (0.0, LEAKY_SLOPE) and x.dtype == torch.float32 and not torch.is_autocast_enabled("cuda"):
-            # the same block on fp32 tensors (parity mode; the matcher's head inside the timed step, align.HEAD_SPLIT): split-bf16
-            # products, folded norm, bias and activation in the epilogue of the one launch
-            from . import split32
-            if split32.usable(x):
-                w, b = self.folded() if self.use_norm else (c.weight, c.bias)
-                y = split32.conv2d(x, w, b, c.stride, c.padding, c.dilation, act={None: 0, 'relu': 1, 'leaky': 3}[self.act])
-                if y is not None:
-                    return y
-        if self.use_norm and not self.training and not torch.is_grad_enabled():
-            x = self._conv2d(x, *self.folded())
-        else:
-            if x.is_cuda and self.use_norm and self.training and \
-                    (self.act in (None, 'relu') or (self.act == 'leaky' and self.act_slope == LEAKY_SLOPE)) and \
-                    os.environ.get("RFN_BN_KERNEL", "1") != "0":
-                # decode heads (student and EMA teacher run BatchNorm with batch statistics, SURVEY D9): convolution on the
-                # hand-written kernels where they exist for the pass, then ONE fused BatchNorm(train) + ReLU (csrc/bn.hip)
-                from . import bn as bnk
-                from .params import compute_dtype
-                cd = compute_dtype(x)
-                if bnk.usable(x, self.bn, cd, channels=c.out_channels, count=self._out_count(x)):
-                    return self._bn_train(x, cd)
-            x = self._conv2d(x, c.weight, c.bias)
-            if self.use_norm:
-                x = self.bn(x)
-        if self.act == 'leaky':
-            x = F.leaky_relu(x, self.act_slope, inplace=True)
-        elif self.act == 'relu':
-            x = F.relu(x, inplace=True)
-        return x
+            y = conv2d(x, c.weight, c.bias, c.stride, c.padding, c.dilation, c.groups, stats=sums)
+            return bnk.bn_act_train(y, self.bn, act, cd, out=out, sums=sums)
+        # decode heads (student and EMA teacher run BatchNorm with batch statistics, SURVEY D9): convolution on the hand-written
+        # kernels where they exist for the pass, then ONE fused BatchNorm(train) + ReLU (csrc/bn.hip)
+        return bnk.bn_act_train(self.pre_norm(x, cd), self.bn, act, cd, out=out, drop=drop)
 
 
 class MLP(nn.Module):

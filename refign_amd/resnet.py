@@ -37,11 +37,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import bn as bnk
 from . import mfma as _mfma
 from ._tensor import DTYPE_CODE16, ptr, workspace
 from .align import BaseHead
 from .config import OutOfScopeError
-from .conv import Conv2d, _nhwc16
+from .conv import ACT_CODE, Conv2d, _nhwc16
 from .params import bias_stack, compute_dtype, grad_sink, sum_rows, tap_stack
 
 ARCH = {"resnet18_v1c": ("basic", (2, 2, 2, 2)), "resnet50_v1c": ("bottleneck", (3, 4, 6, 3)),
@@ -49,26 +50,12 @@ ARCH = {"resnet18_v1c": ("basic", (2, 2, 2, 2)), "resnet50_v1c": ("bottleneck", 
 # file names of the ImageNet checkpoints the reference downloads (open-mmlab third_party); looked up locally only
 IMAGENET_FILES = {"resnet18_v1c": "resnet18_v1c-b5776b93.pth", "resnet50_v1c": "resnet50_v1c-2cccc1ad.pth",
                   "resnet101_v1c": "resnet101_v1c-e67eebb6.pth"}
-_ACT_RELU = 1
 FP32_LIBRARY = True       # fp32 GPU passes of the backbone on the library's fp32 convolution (False: conv.Conv2d's split-bf16 products)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # convolution + BatchNorm (+ ReLU) (+ residual), the unit every block is made of
 # ---------------------------------------------------------------------------------------------------------------------
-def _fold(conv, bn):
-    """(weight, bias) of conv with eval-mode bn folded in (layers.ConvBNReLU.folded)."""
-    inv = torch.rsqrt(bn.running_var + bn.eps)
-    g = inv if bn.weight is None else bn.weight * inv
-    w = conv.weight * g.view(-1, 1, 1, 1)
-    b = -bn.running_mean * g
-    if bn.bias is not None:
-        b = b + bn.bias
-    if conv.bias is not None:
-        b = b + conv.bias * g
-    return w.detach().contiguous(), b.detach().contiguous()
-
-
 class _Folding(nn.Module):
     """A module whose (convolution, BatchNorm) pairs can run folded: the folded weights are cached per pair and dropped by the
     three hooks layers.ConvBNReLU uses (train(), _load_from_state_dict(), _apply())."""
@@ -82,7 +69,7 @@ class _Folding(nn.Module):
         else: the folded tensors are no parameters, so they get no params.derived entry (and no refresh plan is disturbed)."""
         got = self._folded.get((name, dtype))
         if got is None:
-            w, b = _fold(conv, bn)
+            w, b = bnk.fold(conv.weight, conv.bias, bn)
             got = self._folded[(name, dtype)] = (_mfma.pack_conv_weight(w, dtype), b.to(dtype))
         return got
 
@@ -107,14 +94,6 @@ class _Folding(nn.Module):
                 y = _conv_folded(x, self, name, conv, bn, cd, relu, res)
                 if y is not None:
                     return y, res is not None
-            if cd in DTYPE_CODE16 and bn.training and os.environ.get("RFN_BN_KERNEL", "1") != "0":
-                from . import bn as bnk
-                y = conv(x)
-                if bnk.usable(y, bn, cd):
-                    return bnk.bn_act_train(y, bn, _ACT_RELU if relu else 0, cd), False
-                _mfma.note_library("batch_norm", y)
-                y = bn(y)
-                return (F.relu(y, inplace=True) if relu else y), False
         if FP32_LIBRARY and x.is_cuda and x.dtype == torch.float32 and compute_dtype(x) == torch.float32:
             # fp32 passes: the library's fp32 convolution, not conv.Conv2d's split-bf16 products.  Their 2^-16 per product, carried
             # through 33 batch-normalised blocks, left the reference step's BatchNorm gradient norm 3.7 % off (bound 2 %); the
@@ -123,9 +102,7 @@ class _Folding(nn.Module):
             y = conv._conv_forward(x, conv.weight, conv.bias)
         else:
             y = conv(x)
-        _mfma.note_library("batch_norm", y)                 # (no-op for CPU tensors)
-        y = bn(y)
-        return (F.relu(y, inplace=True) if relu else y), False
+        return bnk.bn_act(y, bn, 'relu' if relu else None, note=True), False
 
 
 def _conv_folded(x, owner, name, conv, bn, dtype, relu, res):
@@ -139,7 +116,7 @@ def _conv_folded(x, owner, name, conv, bn, dtype, relu, res):
     wp, bp = owner.folded(name, conv, bn, dtype)
     xh = _nhwc16(x, dtype, -(-C // 8) * 8)
     rh = None if res is None else _nhwc16(res, dtype, res.shape[1])
-    y = _mfma.conv2d_nhwc(xh, wp, bp, KH, KW, s[0], p[0], d[0], act=_ACT_RELU if relu else 0, res=rh)
+    y = _mfma.conv2d_nhwc(xh, wp, bp, KH, KW, s[0], p[0], d[0], act=ACT_CODE['relu' if relu else None], res=rh)
     return None if y is None else y.permute(0, 3, 1, 2)
 
 

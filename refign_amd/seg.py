@@ -461,23 +461,8 @@ def _class_logits(conv, y):
     runs on the implicit-GEMM kernels (output channels padded to 64 inside, conv._ConvMfmaFn / conv2d_mfma); elsewhere
     it is the module itself."""
     if y.is_cuda and conv.kernel_size == (1, 1):
-        from .conv import conv2d_mfma, conv2d_mfma_grad
-        from .params import compute_dtype
-        cd = compute_dtype(y)
-        if cd in (torch.float16, torch.bfloat16):
-            if torch.is_grad_enabled() and (conv.weight.requires_grad or y.requires_grad):
-                o = conv2d_mfma_grad(y, conv.weight, conv.bias, 1, 0, 1, cd)
-            else:
-                o = conv2d_mfma(y, conv.weight, conv.bias, 1, 0, 1, dtype=cd)
-            if o is not None:
-                return o
-        if cd == torch.float32:
-            from . import split32
-            if split32.usable(y):
-                o = split32.conv2d(y.float(), conv.weight, conv.bias, 1, 0, 1)
-                if o is not None:
-                    return o
-        mfma.note_library("conv2d.autograd" if torch.is_grad_enabled() else "conv2d", y, conv.weight)
+        from .conv import conv2d
+        return conv2d(y, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
     return conv(y)
 
 
@@ -547,7 +532,7 @@ class ASPPWrapper(nn.Module):
             # into the concatenated channels-last tensor -- the torch.cat was 5.3 GB of traffic, 1.1 ms per step
             from .params import compute_dtype
             B, _, H, W = x.shape
-            ch = [(m.pointwise_conv if m.depthwise_separable else m).conv.out_channels for m in mods]
+            ch = [m.last.conv.out_channels for m in mods]
             if all(c % 8 == 0 for c in ch):
                 cat = torch.empty((B, H, W, sum(ch)), dtype=compute_dtype(x), device=x.device)
                 o = 0
@@ -555,17 +540,18 @@ class ASPPWrapper(nn.Module):
                     m(x, out=cat[..., o:o + c].permute(0, 3, 1, 2))
                     o += c
                 return self.bottleneck(cat.permute(0, 3, 1, 2), **kw)
-        last = [m.pointwise_conv if m.depthwise_separable else m for m in mods]
+        last = [m.last for m in mods]
         if x.is_cuda and torch.is_grad_enabled() and _ASPP_NOCAT_GRAD and all(m.act in (None, 'relu') for m in last) \
                 and len({m.act for m in last}) == 1 and all(m.bn_kernel_ok(x) for m in last):
             # under autograd (the student): the branches' last BatchNorm + ReLU passes write into the concatenation, and their
             # backward passes read their channel slices of its gradient in place -- no torch.cat, no slice copies.  (The
             # depthwise convolutions keep the shape of x: what bn_kernel_ok says of x holds for their results.)
             from . import bn as bnk
+            from .conv import ACT_CODE
             from .params import compute_dtype
             cd = compute_dtype(x)
-            pre = [m._conv_train(b.depthwise_conv(t) if b.depthwise_separable else t, cd) for b, m, t in zip(mods, last, xs)]
-            cat = bnk.bn_act_train_cat(pre, [m.bn for m in last], 1 if last[0].act == 'relu' else 0, cd)
+            pre = [m.pre_norm(b.depthwise_conv(t) if b.depthwise_separable else t, cd) for b, m, t in zip(mods, last, xs)]
+            cat = bnk.bn_act_train_cat(pre, [m.bn for m in last], ACT_CODE[last[0].act], cd)
             return self.bottleneck(cat, **kw)
         return self.bottleneck(torch.cat([m(t) for m, t in zip(mods, xs)], dim=1), **kw)
 

@@ -235,6 +235,16 @@ def cat_split(parts):
     return out, Cp, C
 
 
+def parts_ok(parts, weight):
+    """The shapes conv2d_parts takes (gradient-free, int geometry: the caller's to see): at most 4 fp32 HIP maps of one
+    (B, H, W), channels that add up to the filter's, within cat_split's 96 channels and the kernel's reduction length."""
+    N, C, KH, KW = weight.shape
+    B, hw = parts[0].shape[0], parts[0].shape[2:]
+    return (1 <= len(parts) <= 4 and sum(p.shape[1] for p in parts) == C and _cp(C) <= 96 and 3 * _cp(C) * KH * KW // 8 < 65536
+            and all(p.is_cuda and p.dtype == torch.float32 and p.dim() == 4 and p.shape[0] == B and p.shape[2:] == hw
+                    for p in parts))
+
+
 def conv2d_parts(parts, weight, bias=None, stride=1, padding=0, dilation=1, act=0):
     """conv2d(torch.cat(parts, 1), ...) for gradient-free fp32 HIP maps without materialising the concatenation: the parts are
     gathered, split and laid out channels-last in one pass (cat_split), then the one-launch split-bf16 convolution.  None outside
