@@ -36,7 +36,7 @@ extern "C" {
  *    (operands of the split-bf16 products), rfn_ffn_fc1_dw_gelu_bf16 (fused Mix-FFN front half).
  * 5: removed rfn_dwconv3x3_tri_* (five entry points); nothing else changed.  Added since, none changed: rfn_kv_path,
  *    rfn_hrda_merge_slide / rfn_hrda_fuse_crop_fwd / rfn_hrda_fuse_crop_bwd, rfn_bn_apply_fwd_drop, rfn_bn_stats_bwd_ld /
- *    rfn_bn_stats_bwd_det_ld / rfn_bn_apply_bwd_ld, rfn_upsample_concat_nhwc_bwd_sum. */
+ *    rfn_bn_stats_bwd_det_ld / rfn_bn_apply_bwd_ld, rfn_upsample_concat_nhwc_bwd_sum, rfn_resize_nearest_lut_u8. */
 #define RFN_ABI_VERSION 5
 
 typedef void* rfn_stream_t; /* hipStream_t */
@@ -726,6 +726,12 @@ int rfn_resize_u8(const void* image_hwc, int H, int W, int Hd, int Wd, const int
                   const int* bounds_y, const int* coef_y, int kmax_y, void* out_chw, rfn_stream_t stream);
 int rfn_resize_nearest_u8(const void* label, int H, int W, int Hd, int Wd, const int* ytab, const int* xtab, void* out,
                           rfn_stream_t stream);
+/* rfn_resize_nearest_lut_u8 (added since ABI 5): out[y][x] = lut[label[ytab[y]][xtab[x]]], lut a DEVICE array of 256 bytes, staged
+ * in LDS once per workgroup -- RobotCar's raw label ids to train ids (datasets/robotcar.py encode_semantic_map) on the way of
+ * the load-time NEAREST resize, one launch, the output written once.  Hd == H, Wd == W (identity tables) is the encode alone.
+ * Errors as rfn_resize_nearest_u8, plus a null lut. */
+int rfn_resize_nearest_lut_u8(const void* label, int H, int W, int Hd, int Wd, const int* ytab, const int* xtab, const void* lut,
+                              void* out, rfn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * The same two passes with the filter as an argument (additions to ABI 4; the three entry points above keep their signatures and

@@ -11,6 +11,9 @@
 //                     the crop's footprint of the source is read.  int32 accumulation: 255 * 2^22 + 2^21 fits.
 //   resize_kernel<1>  the same two passes, bytes out: Pillow's pixels as a (3, Hd, Wd) image.
 //   resize_nearest_kernel  label map through the two index tables (nearest_table: Pillow ACCUMULATES the source coordinate).
+//   resize_nearest_lut_kernel  the same gather with a 256-entry code table on the way (RobotCar's raw ids -> train ids,
+//                     datasets/robotcar.py encode_semantic_map): the table is staged in LDS once per workgroup, the output is
+//                     written once and no encoded map at the file's size exists.  Hd == H, Wd == W is the encode alone.
 // The kernel knows nothing of the filter: Pillow's LANCZOS (sinc(x) sinc(x / 3) on [-3, 3), the matcher's data sets and `test:`
 // sections) is the same two passes over longer tables with negative taps (refign_amd/resample.py: filter_tables checks
 // 255 * sum |coef| + 2^21 < 2^31 per row, so the int32 accumulation holds), and the clip to a byte between the passes is where its
@@ -111,6 +114,20 @@ __global__ __launch_bounds__(256) void resize_nearest_kernel(const unsigned char
   if (x >= Wd) return;
   const int sy = min(max(ytab[y], 0), H - 1), sx = min(max(xtab[x], 0), W - 1);
   out[(size_t)y * Wd + x] = lbl[(size_t)sy * W + sx];
+}
+
+// the same geometry; lut[256] goes to LDS (a byte per thread) before anybody may leave
+__global__ __launch_bounds__(256) void resize_nearest_lut_kernel(const unsigned char* __restrict__ lbl, int H, int W, int Hd, int Wd,
+                                                                 const int* __restrict__ ytab, const int* __restrict__ xtab,
+                                                                 const unsigned char* __restrict__ lut,
+                                                                 unsigned char* __restrict__ out) {
+  __shared__ unsigned char codes[256];
+  codes[threadIdx.x] = lut[threadIdx.x];
+  __syncthreads();
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= Wd) return;
+  const int sy = min(max(ytab[y], 0), H - 1), sx = min(max(xtab[x], 0), W - 1);
+  out[(size_t)y * Wd + x] = codes[lbl[(size_t)sy * W + sx]];
 }
 
 // taps per output pixel of Pillow's bilinear filter from `in` to `out` pixels: ceil(max(in / out, 1)) * 2 + 1
@@ -219,6 +236,17 @@ int rfn_resize_nearest_u8(const void* label, int H, int W, int Hd, int Wd, const
   hipLaunchKernelGGL(resize_nearest_kernel, dim3((unsigned)cdiv(Wd, 256), (unsigned)Hd), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned char*)label, H, W, Hd, Wd, ytab, xtab, (unsigned char*)out);
   return check_launch("resize_nearest_kernel");
+}
+
+int rfn_resize_nearest_lut_u8(const void* label, int H, int W, int Hd, int Wd, const int* ytab, const int* xtab, const void* lut,
+                              void* out, rfn_stream_t stream) {
+  using namespace rfn;
+  RFN_REQUIRE(label && ytab && xtab && lut && out, "rfn_resize_nearest_lut_u8: null pointer");
+  RFN_REQUIRE(H > 0 && W > 0 && Hd > 0 && Wd > 0 && Hd <= 65535, "rfn_resize_nearest_lut_u8: sizes must be positive, Hd <= 65535 (%d x %d -> %d x %d)",
+              H, W, Hd, Wd);
+  hipLaunchKernelGGL(resize_nearest_lut_kernel, dim3((unsigned)cdiv(Wd, 256), (unsigned)Hd), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)label, H, W, Hd, Wd, ytab, xtab, (const unsigned char*)lut, (unsigned char*)out);
+  return check_launch("resize_nearest_lut_kernel");
 }
 
 }  // extern "C"

@@ -3,8 +3,8 @@ directory of data sets to the batches Trainer.fit / validate / test / predict ta
 
 SegmentationDataModule reads `data.init_args` the way the reference's CombinedDataModule.__init__ does (sections, idx_to_name,
 batch sizes), builds the readers of refign_amd/datasets.py and feeds what exists already: config.train_section_plan /
-config.ingest_plan, datastep.RareClassSourceSampler / PairSampler / UDABatchAssembler, resample.EvalIngest.  No new kernel,
-no worker process.
+config.ingest_plan, datastep.RareClassSourceSampler / RotatedLabelledSampler / PairSampler / UDABatchAssembler,
+resample.EvalIngest.  No worker process.
 
 Who does what:
   * every random draw and every piece of device work happens on the thread that calls next(): a second thread issuing HIP work
@@ -13,8 +13,9 @@ Who does what:
     pinned buffers that are used again once the copy that read them has finished.
 
 What is pinned, and what is not: the epoch's index order is torch's RandomSampler (epoch_permutation), the readers are the
-reference's, and with prefetch=0 the `random` stream is consumed in the reference's order (the source loader's samples, then
-the target loader's).  Lightning is not installed here: the order in which ITS loops create and advance the loaders' iterators
+reference's, and with prefetch=0 the `random` and torch streams are consumed in the reference's order for loaders without
+workers (the first loader's samples one after the other, then the second's, then the third's, then the coin of
+`ignore_every_second_semantic_training_batch`).  Lightning is not installed here: the order in which ITS loops create and advance the loaders' iterators
 (and the base seed a DataLoader iterator draws for its workers) is not restated, so parity with a Lightning run's batches is
 not claimed.
 
@@ -22,13 +23,14 @@ MatchingDataModule, at the end, is the same for the matcher's configurations (co
 with warp supervision for AlignmentModel.training_step, MegaDepth / RobotCarMatching with their correspondences for
 validate / test.  Same division of work between the threads, and again no new kernel."""
 import collections
+import os
 import random
 from concurrent.futures import ThreadPoolExecutor
 
 import torch
 
 from . import config
-from .datasets import READERS
+from .datasets import SEGMENTATION_READERS as READERS
 
 MAX_WORKERS = 16
 _EVAL_KEYS = ("dims", "resize", "img_only", "only_if_larger", "mean", "std", "interpolation", "dims_interpolation", "pad")
@@ -56,6 +58,11 @@ def _sections(load_config, split):
 def _one_section_cfg(split, name, conf):
     """a config that holds this one section where the plan readers of refign_amd/config.py look for it"""
     return {"data": {"init_args": {"load_config": {split: {name: conf}}}}}
+
+
+class SemiSupervisedOnly(config.OutOfScopeError, ValueError):
+    """`ignore_every_second_semantic_training_batch` over one labelled section: the reference's assertion ("can only ignore in
+    semi-supervised case") as a ValueError, and, like every shape of sections this module does not assemble, an OutOfScopeError"""
 
 
 class _PinnedPool:
@@ -122,21 +129,25 @@ class _EvalLoader:
 
 class SegmentationDataModule:
     """SegmentationDataModule(cfg, data_dir, device, prefetch=None): `cfg` is the loaded YAML; the data sets lie in
-    <data_dir>/Cityscapes, /ACDC and /DarkZurich.
+    <data_dir>/Cityscapes, /ACDC, /DarkZurich, /RobotCar, /NighttimeDriving and /BDD100kNight.
       train_on / val_on / test_on / predict_on, idx_to_name, batch_size, val_batch_size, test_batch_size: as CombinedDataModule
       train_batches()              an endless iterator of {image_src, semantic_src, image_trg, image_ref} on the device
       loaders(split, datasets)     {data set: iterable of batches} for Trainer.validate / test / predict
-      orig_dims[name]              the size Trainer.predict(orig_size=) interpolates to
+      orig_dims[name]              the size Trainer.predict(orig_size=) interpolates to, for the data sets the configuration names
       close()                      ends the decoding threads
-    A data set without a reader here (RobotCar, NighttimeDriving, BDD100kNight, MegaDepth, RobotCarMatching) and
-    `ignore_every_second_semantic_training_batch` raise config.OutOfScopeError when the section is asked for, not before: a
-    Dark Zurich user picks the supported test sets with loaders('test', datasets=['DarkZurich']).
+    A data set without a reader here (MegaDepth, RobotCarMatching: the matcher's) or without its folder under data_dir raises
+    config.OutOfScopeError naming the section when the section is asked for, not before; loaders(split, datasets=[...]) picks
+    sections.
+    Training sections: one rcs_enabled Cityscapes section, optionally one further labelled section (RobotCar's, whatever
+    config.train_section_plan accepts: datastep.RotatedLabelledSampler with the reader's label_lut()), one (image, image_ref)
+    section; a list under a data set (RobotCar's) gives one loader per entry, and a loader's batch is batch_size // loaders.
+    `ignore_every_second_semantic_training_batch`: after a batch's samples ONE random.random() < 0.5 is drawn in next(); on
+    heads image_src / semantic_src are views of the first half (the Cityscapes samples) of the assembled buffers.
     prefetch=0: files are decoded inside next(), and `random` is consumed in the reference's order.  prefetch=k > 0 (2 by default
     when the YAML's num_workers > 0): files are decoded k batches ahead, within the epoch.  The target indices are known from the
-    permutation; the source loader's (class, file) choices are drawn ahead from a random.Random of its own, seeded once from the
+    permutation, and so are the second labelled section's; the source loader's (class, file) choices are drawn ahead from a random.Random of its own, seeded once from the
     global stream at the first next(); crop and flip draws stay in next(), on the global stream."""
 
-    orig_dims = {name: cls.orig_dims for name, cls in READERS.items()}
 
     def __init__(self, cfg, data_dir, device, prefetch=None):
         args = dict(((cfg or {}).get("data") or {}).get("init_args") or {})
@@ -152,6 +163,8 @@ class SegmentationDataModule:
         self.train_on, self.val_on = [n for n, _ in self._sec["train"]], [n for n, _ in self._sec["val"]]
         self.test_on, self.predict_on = [n for n, _ in self._sec["test"]], [n for n, _ in self._sec["predict"]]
         self.idx_to_name = {split: {i: n for i, (n, _) in enumerate(self._sec[split])} for split in _SPLITS}
+        # of the data sets this configuration names (and that have a reader here)
+        self.orig_dims = {n: READERS[n].orig_dims for split in _SPLITS for n, _ in self._sec[split] if n in READERS}
         if self.train_on:
             assert self.batch_size % len(self.train_on) == 0, "batch size should be divisible by number of train datasets"
         self.val_batch_size = max(1, self.batch_size // max(len(self.train_on), 1) // 2)
@@ -172,8 +185,14 @@ class SegmentationDataModule:
         if name not in READERS:
             raise config.OutOfScopeError(f"SegmentationDataModule: {name} ({split}) has no reader here ({' / '.join(READERS)}); "
                                          f"select the supported sections with datasets=")
+        root = f"{self.data_dir}/{name}"
+        if not os.path.isdir(root):
+            # a configuration may name more data sets than a user holds (the Dark Zurich files test on three): the section is
+            # named, and so is the way round it.  (OutOfScopeError is a RuntimeError, as the readers' own for a missing folder.)
+            raise config.OutOfScopeError(f"SegmentationDataModule: {name} ({split}): dataset not found: there is no folder {root}; "
+                                         f"select the sections to run with datasets=")
         kwargs = {k: v for k, v in conf.items() if k != "transforms"}
-        return READERS[name](f"{self.data_dir}/{name}", stage=split, **kwargs)
+        return READERS[name](root, stage=split, **kwargs)
 
     def close(self):
         """ends the iterators' look-ahead and the decoding threads (waits for them)"""
@@ -204,7 +223,8 @@ class SegmentationDataModule:
             kw = {k: plan[k] for k in _EVAL_KEYS}
             if kw["dims"] is None:
                 kw["dims"] = tuple(reader.dims)                     # the reader's own default, which it resizes to as well
-            ingest = EvalIngest(device=self.device, **kw)
+            lut = reader.label_lut() if hasattr(reader, "label_lut") else None   # RobotCar: raw ids, encoded on the device
+            ingest = EvalIngest(device=self.device, label_lut=lut, **kw)
             out[name] = _EvalLoader(reader, ingest, self.val_batch_size if split == "val" else self.test_batch_size,
                                     self._executor() if self.num_workers > 0 else None)
         return out
@@ -217,10 +237,11 @@ class SegmentationDataModule:
         loader ignores its indices.  A yielded batch has been waited for on the current stream; its buffers are written again two
         batches later, after the work that was queued on the current stream by then (UDABatchAssembler.consumed for the batch that
         held them), which fits Trainer.fit's look-ahead of one batch as well as a plain `for batch in ...: step(batch)`."""
-        if self.ignore_every_second_semantic_training_batch:
-            raise config.OutOfScopeError("SegmentationDataModule: ignore_every_second_semantic_training_batch (the semi-supervised "
-                                         "RobotCar recipe) is outside this module")
         readers = [self._reader("train", name, conf) for name, conf in self._sec["train"]]
+        if self.ignore_every_second_semantic_training_batch and sum("semantic" in r.load_keys for r in readers) < 2:
+            # the reference asserts len(image_src) > batch_size // len(train_on) in on_before_batch_transfer
+            raise SemiSupervisedOnly("SegmentationDataModule: ignore_every_second_semantic_training_batch with one labelled "
+                                     "training section: can only ignore in semi-supervised case")
         if self.device.type != "cuda":
             raise RuntimeError("SegmentationDataModule.train_batches: a HIP device is required (no CPU fallback)")
         it = _TrainIterator(self, readers)
@@ -230,27 +251,36 @@ class SegmentationDataModule:
 
 class _TrainIterator:
     def __init__(self, dm, readers):
-        from .datastep import PairSampler, RareClassSourceSampler, UDABatchAssembler
+        from .datastep import PairSampler, RareClassSourceSampler, RotatedLabelledSampler, UDABatchAssembler
         self.dm = dm
         secs = dm._sec["train"]
         plans = [config.train_section_plan(_one_section_cfg("train", name, conf), name) for name, conf in secs]
         src = [i for i, r in enumerate(readers) if "semantic" in r.load_keys]
         trg = [i for i, r in enumerate(readers) if "semantic" not in r.load_keys]
-        if len(secs) != 2 or len(src) != 1 or len(trg) != 1 or not {"image", "image_ref"} <= set(readers[trg[0]].load_keys):
-            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: one labelled source "
-                                         f"section and one (image, image_ref) target section is what the device data step assembles")
+        if len(src) not in (1, 2) or len(trg) != 1 or not {"image", "image_ref"} <= set(readers[trg[0]].load_keys):
+            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: one rare-class source "
+                                         f"section, optionally one further labelled section, and one (image, image_ref) target "
+                                         f"section is what the device data step assembles")
         s, t = src[0], trg[0]
-        if s > t:
-            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: the source section "
-                                         f"comes first in every configuration carried here (its samples draw first)")
+        lab = src[1] if len(src) == 2 else None
+        if src[-1] > t:
+            raise config.OutOfScopeError(f"SegmentationDataModule: training sections {[n for n, _ in secs]}: the labelled sections "
+                                         f"come first in every configuration carried here (their samples draw first)")
         self.src, self.trg = readers[s], readers[t]
+        self.lab = None if lab is None else readers[lab]
         if not getattr(self.src, "rcs_enabled", False):
-            raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[s][0]} without rcs_enabled: the source sampler on the "
-                                         f"device is the rare-class one")
-        for (name, _), plan in zip(secs, plans):
+            raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[s][0]} without rcs_enabled: the first labelled "
+                                         f"section's sampler on the device is the rare-class one")
+        if lab is not None and getattr(self.lab, "rcs_enabled", False):
+            raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[lab][0]}: a second rcs_enabled section")
+        for i in (s, t):
+            plan = plans[i]
             if plan["crop_size"] is None or plan["flip"] != 0.5 or plan["rotation"] is not None or plan["jitter"] is not None:
-                raise config.OutOfScopeError(f"SegmentationDataModule: train.{name}: RandomCrop + RandomHorizontalFlip(p=0.5) is the "
-                                             f"pipeline the two samplers run")
+                raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[i][0]}: RandomCrop + RandomHorizontalFlip(p=0.5) "
+                                             f"is the pipeline the rare-class and the pair sampler run")
+        if lab is not None and (plans[lab]["crop_size"] is None or tuple(plans[lab]["crop_size"]) != tuple(plans[s]["crop_size"])):
+            raise config.OutOfScopeError(f"SegmentationDataModule: train.{secs[lab][0]}: the two labelled sections share image_src, "
+                                         f"so they need one RandomCrop size ({plans[lab]['crop_size']} and {plans[s]['crop_size']})")
         self.per_loader = dm.batch_size // len(secs)
         dims = [tuple(plans[i]["dims"] or readers[i].dims) for i in (s, t)]
         self.source = _Source(RareClassSourceSampler(
@@ -259,8 +289,15 @@ class _TrainIterator:
             rcs_min_crop_ratio=self.src.rcs_min_crop_ratio, mean=plans[s]["mean"], std=plans[s]["std"], dims=dims[0]))
         self.pairs = PairSampler(self._load_trg, plans[t]["crop_size"], dm.device, mean=plans[t]["mean"], std=plans[t]["std"],
                                  dims=dims[1])
-        self.asm = UDABatchAssembler(self.source, self.pairs, self.per_loader, dm.device)
-        self.n_batches = min(len(self.src), len(self.trg)) // self.per_loader
+        self.labelled = None
+        if lab is not None:
+            lut = self.lab.label_lut() if hasattr(self.lab, "label_lut") else None
+            self.labelled = RotatedLabelledSampler(self._load_lab, dict(plans[lab], dims=tuple(plans[lab]["dims"] or self.lab.dims)),
+                                                   dm.device, label_lut=lut)
+        self.asm = UDABatchAssembler(self.source, self.pairs, self.per_loader, dm.device, labelled=self.labelled)
+        self.halve = dm.ignore_every_second_semantic_training_batch
+        self.halved = 0                                      # batches handed out with the first half of the source samples
+        self.n_batches = min(len(r) for r in readers) // self.per_loader
         if self.n_batches == 0:
             raise ValueError("SegmentationDataModule: a training set holds fewer files than one loader's batch")
         self.pool = _PinnedPool(dm.pin_memory)
@@ -268,7 +305,8 @@ class _TrainIterator:
         self.exe = dm._executor() if self.k > 0 else None
         self.private = None                                  # the source loader's own stream (prefetch > 0)
         self.order, self.pos = [], 0                         # the epoch's target indices and the next one to plan
-        self.pending = collections.deque()                   # planned batches: {"src": [...], "trg": [...], "bufs": [...]}
+        self.lab_order = []                                  # ... and the second labelled loader's
+        self.pending = collections.deque()                   # planned batches: {"src": [...], "lab": [...], "trg": [...], "bufs"}
         self.current = None
         self.handed = collections.deque(maxlen=2)
         self.sizes = {}
@@ -302,6 +340,11 @@ class _TrainIterator:
         s = self._done(cur["src"].popleft()[2]) if cur["src"] else self._job(self.src, "src", index, cur["bufs"])
         return s["image"], s["semantic"]
 
+    def _load_lab(self, index):
+        cur = self.current
+        s = self._done(cur["lab"].popleft()[1]) if cur["lab"] else self._job(self.lab, "lab", index, cur["bufs"])
+        return s["image"], s["semantic"]
+
     def _load_trg(self, index):
         cur = self.current
         s = self._done(cur["trg"].popleft()[1]) if cur["trg"] else self._job(self.trg, "trg", index, cur["bufs"])
@@ -310,21 +353,28 @@ class _TrainIterator:
     # -- planning ------------------------------------------------------------------------------------------------------------
     def _new_epoch(self):
         epoch_permutation(len(self.src))                     # the source loader's: drawn, and ignored under rcs_enabled
+        if self.lab is not None:                             # one permutation per loader, in loader order
+            self.lab_order = epoch_permutation(len(self.lab))[:self.n_batches * self.per_loader]
         self.order = epoch_permutation(len(self.trg))[:self.n_batches * self.per_loader]
         self.pos = 0
         self.epoch += 1
 
     def _plan(self):
-        """one more batch of the current epoch: its target indices; with prefetch, its source choices and its decoding jobs"""
+        """one more batch of the current epoch: its target (and second labelled) indices; with prefetch, its source choices
+        and its decoding jobs"""
         idx = self.order[self.pos:self.pos + self.per_loader]
+        lab_idx = self.lab_order[self.pos:self.pos + self.per_loader] if self.lab is not None else None
         self.pos += self.per_loader
-        entry = {"indices": idx, "src": collections.deque(), "trg": collections.deque(), "bufs": []}
+        entry = {"indices": idx, "lab_indices": lab_idx, "src": collections.deque(), "lab": collections.deque(),
+                 "trg": collections.deque(), "bufs": []}
         if self.k > 0:
             sam = self.source.sampler
             for _ in range(self.per_loader):
                 c = self.private.choices(sam.rcs_classes, weights=sam.rcs_classprob, k=1)[0]
                 i = self.private.choice(sam.indices_with_class[c])
                 entry["src"].append((c, i, self._job(self.src, "src", i, entry["bufs"])))
+            for i in lab_idx or ():
+                entry["lab"].append((i, self._job(self.lab, "lab", i, entry["bufs"])))
             for i in idx:
                 entry["trg"].append((i, self._job(self.trg, "trg", i, entry["bufs"])))
         self.pending.append(entry)
@@ -344,9 +394,13 @@ class _TrainIterator:
         if len(self.handed) == 2:                            # the set that is written next was handed out two batches ago
             self.asm.consumed(self.handed[0])
         self.source.chosen.extend((c, i) for c, i, _ in cur["src"])
-        batch, ev = self.asm.assemble(cur["indices"])
+        batch, ev = self.asm.assemble(cur["indices"], cur["lab_indices"])
         self.pool.give(cur["bufs"], ev)
         torch.cuda.current_stream(self.dm.device).wait_event(ev)
+        if self.halve and random.random() < 0.5:             # the reference's coin, after every sample's draws, on this thread
+            n = batch["image_src"].shape[0] // 2             # views: the buffers stay the assembler's (consumed() knows them)
+            batch = dict(batch, image_src=batch["image_src"][:n], semantic_src=batch["semantic_src"][:n])
+            self.halved += 1
         self.handed.append(batch)
         self.current = None
         self.host_seconds += time.perf_counter() - t0
@@ -354,7 +408,7 @@ class _TrainIterator:
 
     def close(self):
         for entry in self.pending:
-            for job in [j[-1] for j in list(entry["src"]) + list(entry["trg"])]:
+            for job in [j[-1] for j in list(entry["src"]) + list(entry["lab"]) + list(entry["trg"])]:
                 if not isinstance(job, dict) and not job.cancel():
                     job.result()
         self.pending.clear()

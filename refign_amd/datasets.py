@@ -1,8 +1,10 @@
-"""refign_amd/datasets.py -- the readers of the three data sets behind the Cityscapes -> ACDC and Cityscapes -> Dark Zurich
-configurations: which files a stage reads, how an image is paired with its reference and its label map, and how a file becomes
-an array.  The semantics are the reference readers' (data_modules/datasets/{cityscapes,acdc,darkzurich}.py), restated:
+"""refign_amd/datasets.py -- the readers of the data sets behind the Cityscapes -> ACDC, Cityscapes -> Dark Zurich and
+Cityscapes -> RobotCar configurations and of the night test sets (NighttimeDriving, BDD100kNight): which files a stage reads,
+how an image is paired with its reference and its label map, and how a file becomes an array.  The semantics are the reference
+readers' (data_modules/datasets/{cityscapes,acdc,darkzurich,robotcar,nighttimedriving,bdd100knight}.py), restated:
 
-  * stage -> split: train -> train, val -> val, test -> val, predict -> test (ACDC / Dark Zurich: or `predict_on`);
+  * stage -> split: train -> train, val -> val, test -> val, predict -> test (ACDC / Dark Zurich: or `predict_on`); RobotCar has a
+    test split of its own, the two night sets have nothing else;
   * the walk is `os.listdir` as it comes (the file system's order: `paths` are parallel lists, their order carries no meaning);
   * a missing folder is a RuntimeError;
   * `decode(index)` stops at the DECODED file: the load-time resize to `dims` is the device's job (`dims=` of the samplers in
@@ -24,7 +26,7 @@ def _listed(x):
 
 
 class _Reader:
-    """what the three readers share: parallel path lists, `len`, `filename`, `decode`"""
+    """what the readers share: parallel path lists, `len`, `filename`, `decode`"""
     orig_dims = None
     keys = ("image", "image_ref", "semantic")
 
@@ -42,6 +44,9 @@ class _Reader:
     def __len__(self):
         return len(next(iter(self.paths.values())))
 
+    def _check_label(self, a, path):
+        """a reader's own demands on a decoded label map, checked before it is copied anywhere"""
+
     def filename(self, index):
         return self.paths["image"][index].split("/")[-1]
 
@@ -55,6 +60,8 @@ class _Reader:
                 raise ValueError(f"{type(self).__name__}: invalid load_key {k!r}")
             with Image.open(self.paths[k][index]) as im:
                 a = np.array(im.convert("RGB") if k != "semantic" else im)         # a copy: writable, as torch wants it
+            if k == "semantic":
+                self._check_label(a, self.paths[k][index])
             if a.dtype != np.uint8:
                 raise ValueError(f"{self.paths[k][index]}: a uint8 file is required, got {a.dtype}")
             if out is not None and k in out:
@@ -200,7 +207,165 @@ class DarkZurich(_Reader):
                                                            name.replace("rgb_anon.png", "gt_labelTrainIds.png")))
 
 
+ROBOTCAR_PAIRS_CSV = os.path.join("lists", "correspondence_pairs.csv")
+# raw RobotCar label id -> train id (datasets/robotcar.py `id_to_trainid`, ids 0 ... 33; its key -1 never matches a uint8 pixel)
+_ROBOTCAR_TRAIN_IDS = {7: 0, 8: 1, 11: 2, 12: 3, 13: 4, 17: 5, 19: 6, 20: 7, 21: 8, 22: 9, 23: 10, 24: 11, 25: 12, 26: 13, 27: 14,
+                       28: 15, 31: 16, 32: 17, 33: 18}
+
+
+class RobotCar(_Reader):
+    """Three forms (datasets/robotcar.py, restated):
+      train with `semantic` among the load_keys: <root>/segmented_images/training/imgs/* with .../annos/<the same name>;
+      train with image + image_ref: one pair per line `im_i_path,im_j_path` of <root>/lists/correspondence_pairs.csv, both
+        relative to <root>/images; im_i_path is image_ref, im_j_path is image, `filename` the basename of im_j_path.  The
+        reference reads the two names out of the MATLAB v7.3 files <root>/correspondence_data/*.mat with h5py, one file per
+        sample, in the order of that directory's listing; write_robotcar_pairs(root) writes the CSV from them in that order.
+        pairs_csv: another place for the list;
+      val / test / predict: <root>/segmented_images/{validation,testing}/imgs with .../annos (predict reads testing); image_ref
+        is refused, as the reference asserts.
+    The label files hold RAW ids: decode returns them as stored (a 2-D uint8 array, or ValueError), and label_lut() is the table
+    that makes train ids of them -- applied on the device (resample.resize_nearest_u8(lut=))."""
+    orig_dims = (1024, 1024)
+
+    def __init__(self, root, stage="train", load_keys=("image_ref", "image", "semantic"), dims=(1024, 1024), transforms=None,
+                 pairs_csv=None, **kwargs):
+        self.root, self.dims = root, dims
+        if not os.path.isdir(root):
+            raise RuntimeError(_MISSING.format(root, "segmented_images (and images, lists for the training pairs)"))
+        if stage not in _STAGES:
+            raise AssertionError(f"RobotCar: stage must be one of {_STAGES}, got {stage!r}")
+        self.stage = stage
+        self.split = {"train": "train", "val": "val", "test": "test", "predict": "test"}[stage]
+        self.load_keys = _listed(load_keys)
+        if self.split == "train" and "semantic" not in self.load_keys:
+            self.paths = {"image": [], "image_ref": []}
+            self.images_dir = os.path.join(root, "images")
+            pairs_csv = pairs_csv or os.path.join(root, ROBOTCAR_PAIRS_CSV)
+            if not os.path.isfile(pairs_csv):
+                raise FileNotFoundError(f"RobotCar: the list of training pairs {pairs_csv} is missing (one `im_i_path,im_j_path` line "
+                                        f"per file of correspondence_data/; datasets.write_robotcar_pairs(root) writes it from the "
+                                        f".mat files and needs h5py for that)")
+            with open(pairs_csv) as f:
+                for line in f:
+                    if line.strip():
+                        ref, img = line.strip().split(",")
+                        self.paths["image_ref"].append(os.path.join(self.images_dir, ref))
+                        self.paths["image"].append(os.path.join(self.images_dir, img))
+            return
+        if self.split != "train":
+            assert "image_ref" not in self.load_keys, "RobotCar: the val and test splits have no image_ref"
+        folder = {"train": "training", "val": "validation", "test": "testing"}[self.split]
+        images = os.path.join(root, "segmented_images", folder, "imgs")
+        labels = os.path.join(root, "segmented_images", folder, "annos")
+        self._need(images, labels)
+        self.paths = {k: [] for k in self.load_keys}
+        for name in os.listdir(images):
+            for k in self.load_keys:
+                if k == "image":
+                    self.paths[k].append(os.path.join(images, name))
+                elif k == "semantic":
+                    self.paths[k].append(os.path.join(labels, name))
+
+    def _check_label(self, a, path):
+        if a.ndim != 2 or a.dtype != np.uint8:
+            raise ValueError(f"{path}: a single-channel uint8 map of raw label ids is required, got {a.dtype} {a.shape}")
+
+    @staticmethod
+    def label_lut():
+        """the 256-entry uint8 table of encode_semantic_map: ids 0 ... 33 to their train id or 255, every other code to itself
+        (the reference leaves a code outside its map unchanged)"""
+        lut = np.arange(256, dtype=np.uint8)
+        lut[:34] = 255
+        for raw, train in _ROBOTCAR_TRAIN_IDS.items():
+            lut[raw] = train
+        return lut
+
+
+def write_robotcar_pairs(root, out_csv=None):
+    """<root>/lists/correspondence_pairs.csv (or out_csv) from <root>/correspondence_data/*.mat: per file, in the order of the
+    directory's listing filtered to names ending in `mat` (the reference's), one line `im_i_path,im_j_path` -- the two datasets of
+    that name, (n, 1) arrays of character codes.  Needs h5py (the files are MATLAB v7.3, i.e. HDF5).  -> the number of lines."""
+    try:
+        import h5py
+    except ImportError as e:
+        raise ImportError("datasets.write_robotcar_pairs needs h5py to read the MATLAB v7.3 files under correspondence_data/ (it is "
+                          "needed for this one conversion only; the RobotCar reader itself reads the CSV it writes)") from e
+    corr_dir = os.path.join(root, "correspondence_data")
+    if not os.path.isdir(corr_dir):
+        raise RuntimeError(_MISSING.format(root, "correspondence_data"))
+    lines = []
+    for name in [fn for fn in os.listdir(corr_dir) if fn.endswith("mat")]:
+        f = h5py.File(os.path.join(corr_dir, name), "r")
+        try:
+            content = {k: np.array(v) for k, v in f.items()}
+        finally:
+            if hasattr(f, "close"):
+                f.close()
+        pair = ["".join(chr(int(a[0])) for a in content[k]) for k in ("im_i_path", "im_j_path")]
+        if any("," in p or "\n" in p for p in pair):
+            raise ValueError(f"{name}: an image path with a comma or a line break cannot go into the list")
+        lines.append(",".join(pair) + "\n")
+    out_csv = out_csv or os.path.join(root, ROBOTCAR_PAIRS_CSV)
+    os.makedirs(os.path.dirname(out_csv), exist_ok=True)
+    with open(out_csv, "w") as f:
+        f.writelines(lines)
+    return len(lines)
+
+
+class NighttimeDriving(_Reader):
+    """test only: <root>/leftImg8bit/test/night/*_leftImg8bit.png with <root>/gtCoarse_daytime_trainvaltest/test/night/
+    *_gtCoarse_labelTrainIds.png (datasets/nighttimedriving.py, restated)"""
+    orig_dims = (1080, 1920)
+
+    def __init__(self, root, stage="test", load_keys=("image", "semantic"), dims=(1080, 1920), transforms=None, **kwargs):
+        self.root, self.dims = root, dims
+        images, labels = os.path.join(root, "leftImg8bit"), os.path.join(root, "gtCoarse_daytime_trainvaltest")
+        self._need(images, labels)
+        assert stage == "test", f"NighttimeDriving: stage must be 'test', got {stage!r}"
+        self.stage = self.split = "test"
+        self.load_keys = _listed(load_keys)
+        self.paths = {"image": [], "semantic": []}
+        for name in os.listdir(os.path.join(images, "test", "night")):
+            self.paths["image"].append(os.path.join(images, "test", "night", name))
+            self.paths["semantic"].append(os.path.join(labels, "test", "night",
+                                                       name.replace("leftImg8bit.png", "gtCoarse_labelTrainIds.png")))
+
+
+class BDD100kNight(_Reader):
+    """test only: every line `a/b/<split>/<name>.jpg` of the file list gives <root>/images/10k/<split>/<name>.jpg with
+    <root>/labels/sem_seg/masks/<split>/<name>.png (datasets/bdd100knight.py, restated).
+    file_list: <root>/lists/images_trainval_night_correct_filenames.txt when not given.  It is no part of this package: the
+    reference ships it as data_modules/datasets/lists/images_trainval_night_correct_filenames.txt."""
+    orig_dims = (720, 1280)
+    LIST = "images_trainval_night_correct_filenames.txt"
+
+    def __init__(self, root, stage="test", load_keys=("image", "semantic"), dims=(720, 1280), transforms=None, file_list=None,
+                 **kwargs):
+        self.root, self.dims = root, dims
+        if not os.path.isdir(root):
+            raise RuntimeError(_MISSING.format(root, "images/10k and labels/sem_seg/masks"))
+        assert stage == "test", f"BDD100kNight: stage must be 'test', got {stage!r}"
+        self.stage = self.split = "test"
+        self.load_keys = _listed(load_keys)
+        file_list = file_list or os.path.join(root, "lists", self.LIST)
+        if not os.path.isfile(file_list):
+            raise FileNotFoundError(f"BDD100kNight: the file list {file_list} is missing (one `a/b/<split>/<name>.jpg` line per "
+                                    f"image; the reference ships it as data_modules/datasets/lists/{self.LIST}: copy it there or "
+                                    f"pass file_list=)")
+        self.paths = {"image": [], "semantic": []}
+        with open(file_list) as f:
+            for line in f:
+                _, _, split, name = line.strip().split("/")
+                self.paths["image"].append(os.path.join(root, "images", "10k", split, name))
+                self.paths["semantic"].append(os.path.join(root, "labels", "sem_seg", "masks", split, name.replace(".jpg", ".png")))
+
+
+# READERS: the three data sets of the Cityscapes -> ACDC / -> Dark Zurich training configurations, as before.  MORE_READERS: the
+# RobotCar configurations' data set and the two night test sets.  SEGMENTATION_READERS, both together, is the registry that
+# SegmentationDataModule reads; the matcher's two data sets (below) stay in a registry of their own.
 READERS = {"Cityscapes": Cityscapes, "ACDC": ACDC, "DarkZurich": DarkZurich}
+MORE_READERS = {"RobotCar": RobotCar, "NighttimeDriving": NighttimeDriving, "BDD100kNight": BDD100kNight}
+SEGMENTATION_READERS = {**READERS, **MORE_READERS}
 
 
 def write_class_stats(root, out_dir=None, device=None, num_classes=19):

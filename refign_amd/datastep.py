@@ -207,7 +207,9 @@ class RotatedLabelledSampler:
     ColorJitter -> RandomHorizontalFlip -> ConvertImageDtype -> Normalize over image + semantic) from the decoded file.
     `load(index)` -> (decoded image uint8 (H, W, 3) channels last, label uint8 (H, W)) of any size; plan:
     config.train_section_plan(cfg, "RobotCar", 0).  Per sample, in the reference's order of draws:
-      the reader's load-time resize to plan["dims"]: the label NEAREST, the image BILINEAR (refign_amd/resample.py);
+      the reader's load-time resize to plan["dims"]: the label NEAREST, the image BILINEAR (refign_amd/resample.py); with
+      label_lut (256 uint8 codes, RobotCar.label_lut()) the file's raw ids are encoded by the same launch (the encode alone
+      when the file already has that size);
       RandomRotation's angle, float(torch.empty(1).uniform_(lo, hi)); the label map is rotated with fill 255 (rotate_nearest_u8);
       RandomCrop's box over the ROTATED label map's histograms (draw_crop: one launch for a whole chain of candidates);
       ColorJitter's draws (photometric.draw); RandomHorizontalFlip's coin, random.random() < p;
@@ -218,8 +220,12 @@ class RotatedLabelledSampler:
     `ignore_every_second_semantic_training_batch` stay with the caller.  A section without RandomRotation or ColorJitter makes
     no such draw; a RandomHorizontalFlip with p = 0 is taken as absent."""
 
-    def __init__(self, load, plan, device, hists=None):
+    def __init__(self, load, plan, device, hists=None, label_lut=None):
         self.load, self.plan, self.device = load, plan, torch.device(device)
+        self.label_lut = None                              # 256 uint8 codes on the device: the reader's encode_semantic_map
+        if label_lut is not None:
+            from .resample import device_lut
+            self.label_lut = device_lut(label_lut, self.device)
         if plan.get("crop_size") is None:
             raise ValueError("RotatedLabelledSampler: the plan has no RandomCrop size")
         self.size = tuple(plan["crop_size"])
@@ -233,7 +239,9 @@ class RotatedLabelledSampler:
         img, lbl = self.load(index)
         img, lbl = torch.as_tensor(img), torch.as_tensor(lbl)
         img_d, lbl_d = img.to(self.device, non_blocking=True), lbl.to(self.device, non_blocking=True)
-        if self.dims is not None and tuple(lbl_d.shape) != self.dims:
+        if self.label_lut is not None:                     # encode + resize in one launch; at the file's size the encode alone
+            lbl_d = resize_nearest_u8(lbl_d, self.dims if self.dims is not None else tuple(lbl_d.shape), self.label_lut)
+        elif self.dims is not None and tuple(lbl_d.shape) != self.dims:
             lbl_d = resize_nearest_u8(lbl_d, self.dims)
         if self.dims is not None and tuple(img_d.shape[:2]) != self.dims:
             img_d = resize_u8(img_d, self.dims)
@@ -288,23 +296,33 @@ def merge_batches(batch):
 class UDABatchAssembler:
     """{image_src, semantic_src, image_trg, image_ref} assembled ON the device: every sample's crop is written into its slot of
     the batch tensors (no torch.cat, no host-side float images), on a side stream, into one of two buffer sets -- so that batch
-    n + 1 is built while step n runs and can be handed to `Trainer.step(batch, next_batch=...)`."""
+    n + 1 is built while step n runs and can be handed to `Trainer.step(batch, next_batch=...)`.
+    labelled: a second labelled source (RotatedLabelledSampler over the labelled RobotCar section: `size`, sample(index,
+    out_image, out_label)) -- image_src / semantic_src then have 2 * batch_size slots, filled loader by loader in the
+    reference's order of loaders: the rare-class samples, the labelled samples at the indices given, then the pairs."""
 
-    def __init__(self, source, pairs, batch_size, device):
+    def __init__(self, source, pairs, batch_size, device, labelled=None):
         self.source, self.pairs, self.b, self.device = source, pairs, int(batch_size), torch.device(device)
+        self.labelled = labelled
         th, tw = source.size
-        self._sets = [{"image_src": torch.empty((self.b, 3, th, tw), dtype=torch.float32, device=self.device),
-                       "semantic_src": torch.empty((self.b, th, tw), dtype=torch.int64, device=self.device),
+        if labelled is not None and tuple(labelled.size) != (th, tw):
+            raise ValueError(f"UDABatchAssembler: the two labelled sources crop to {tuple(source.size)} and {tuple(labelled.size)}: "
+                             f"one image_src tensor takes one size")
+        ns = self.b * (1 if labelled is None else 2)
+        self._sets = [{"image_src": torch.empty((ns, 3, th, tw), dtype=torch.float32, device=self.device),
+                       "semantic_src": torch.empty((ns, th, tw), dtype=torch.int64, device=self.device),
                        "image_trg": torch.empty((self.b, 3, *pairs.size), dtype=torch.float32, device=self.device),
                        "image_ref": torch.empty((self.b, 3, *pairs.size), dtype=torch.float32, device=self.device)} for _ in range(2)]
         self._turn = 0
         self._stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         self._read_done = [None, None]       # per buffer set: event behind the last step that read it (consumed())
 
-    def assemble(self, pair_indices):
+    def assemble(self, pair_indices, labelled_indices=None):
         """-> (batch dict, event): the batch is complete once `event` has fired (wait on it from the consuming stream)"""
         if len(pair_indices) != self.b:
             raise RuntimeError("UDABatchAssembler: one target index per sample of the batch")
+        if (self.labelled is None) != (labelled_indices is None) or (labelled_indices is not None and len(labelled_indices) != self.b):
+            raise RuntimeError("UDABatchAssembler: one index per sample of the second labelled source, and none without one")
         out = self._sets[self._turn]
         done, self._read_done[self._turn] = self._read_done[self._turn], None
         self._turn ^= 1
@@ -317,18 +335,21 @@ class UDABatchAssembler:
             self._stream.wait_stream(torch.cuda.current_stream(self.device))
         ctx = torch.cuda.stream(self._stream)
         with ctx:
-            for i in range(self.b):                          # the source loader's samples, then the target loader's (two loaders)
+            for i in range(self.b):                          # loader by loader: the source's samples, ...
                 self.source.sample(out["image_src"][i], out["semantic_src"][i])
-            for i, idx in enumerate(pair_indices):
+            for i, idx in enumerate(labelled_indices or ()):  # ... the second labelled source's, ...
+                self.labelled.sample(idx, out["image_src"][self.b + i], out["semantic_src"][self.b + i])
+            for i, idx in enumerate(pair_indices):           # ... the target loader's
                 self.pairs.sample(idx, out["image_trg"][i], out["image_ref"][i])
             ev = self._stream.record_event()
         return out, ev
 
     def consumed(self, batch):
-        """Call on the consuming stream right after queueing the last work that reads `batch` (a dict assemble() returned): the
-        set may be re-filled as soon as that work is done."""
+        """Call on the consuming stream right after queueing the last work that reads `batch` (a dict assemble() returned, or a
+        copy of it whose image_src / semantic_src are views of the set's -- the halved source batch of the semi-supervised
+        recipe): the set may be re-filled as soon as that work is done."""
         for i, st in enumerate(self._sets):
-            if batch is st or batch.get("image_src") is st["image_src"]:
+            if batch is st or batch.get("image_trg") is st["image_trg"] or batch.get("image_src") is st["image_src"]:
                 self._read_done[i] = torch.cuda.current_stream(self.device).record_event()
                 return
         raise RuntimeError("UDABatchAssembler.consumed: not a batch of this assembler")

@@ -231,11 +231,21 @@ def scale_points(pts, h, w, new_h, new_w):
     return pts
 
 
-def resize_nearest_reference(lbl_u8, size):
-    """`Image.fromarray(lbl).resize((w, h), NEAREST)` of an (H, W) uint8 array -> (h, w) uint8"""
+def _check_lut_host(lut, who):
+    lut = np.asarray(lut)
+    if lut.dtype != np.uint8 or lut.shape != (256,):
+        raise ValueError(f"{who}: lut must be a 256-element uint8 table")
+    return lut
+
+
+def resize_nearest_reference(lbl_u8, size, lut=None):
+    """`Image.fromarray(lbl).resize((w, h), NEAREST)` of an (H, W) uint8 array -> (h, w) uint8.  lut (256 uint8 codes): the map is
+    encoded first, lut[lbl], as a reader with raw label ids does in front of its resize (RobotCar.encode_semantic_map)"""
     lbl = np.asarray(lbl_u8)
     if lbl.dtype != np.uint8 or lbl.ndim != 2:
         raise ValueError("resize_nearest_reference: an (H, W) uint8 array is required")
+    if lut is not None:
+        lbl = _check_lut_host(lut, "resize_nearest_reference")[lbl]
     h, w = int(size[0]), int(size[1])
     if lbl.shape == (h, w):
         return lbl.copy()
@@ -295,8 +305,10 @@ def resize_u8(image_hwc_u8, size, filter="bilinear"):
     return out
 
 
-def resize_nearest_u8(label_u8, size):
-    """Pillow's NEAREST resize of an (H, W) uint8 DEVICE label map -> (h, w) uint8"""
+def resize_nearest_u8(label_u8, size, lut=None):
+    """Pillow's NEAREST resize of an (H, W) uint8 DEVICE label map -> (h, w) uint8.  lut: a contiguous 256-element uint8 DEVICE
+    tensor; the output is lut[label] resized -- encode and resize in one launch, the encoded map at the input's size is never
+    stored; size == the input's size is the encode alone.  lut=None launches the plain gather."""
     if not label_u8.is_cuda:
         raise RuntimeError("resize_nearest_u8: device tensors required (the product path has no CPU fallback)")
     if not (label_u8.dtype == torch.uint8 and label_u8.dim() == 2 and label_u8.is_contiguous()):
@@ -304,10 +316,22 @@ def resize_nearest_u8(label_u8, size):
     H, W = label_u8.shape
     Hd, Wd = int(size[0]), int(size[1])
     dev = label_u8.device
+    if lut is not None and not (torch.is_tensor(lut) and lut.dtype == torch.uint8 and tuple(lut.shape) == (256,) and
+                                lut.is_contiguous() and lut.device == dev):
+        raise RuntimeError("resize_nearest_u8: lut must be a contiguous 256-element uint8 tensor on the label's device")
     ty, tx = _device_tables("nearest", H, Hd, dev), _device_tables("nearest", W, Wd, dev)
     out = torch.empty((Hd, Wd), dtype=torch.uint8, device=dev)
-    _lib.call("rfn_resize_nearest_u8", dev, ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(out))
+    if lut is None:
+        _lib.call("rfn_resize_nearest_u8", dev, ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(out))
+    else:
+        _lib.call("rfn_resize_nearest_lut_u8", dev, ptr(label_u8), H, W, Hd, Wd, ptr(ty), ptr(tx), ptr(lut), ptr(out))
     return out
+
+
+def device_lut(lut, device):
+    """a 256-entry uint8 code table (numpy / tensor) as the contiguous device tensor resize_nearest_u8(lut=) takes"""
+    t = torch.as_tensor(np.ascontiguousarray(_check_lut_host(lut.cpu().numpy() if torch.is_tensor(lut) else lut, "device_lut")))
+    return t.to(device).contiguous()
 
 
 def rotate_nearest_u8(image_u8, angle, fill=0):
@@ -373,6 +397,8 @@ class EvalIngest:
     a uint8 image in between (they are NOT merged: the intermediate rounding is part of the result); the last one is fused with
     the conversion and the padding (a whole-image crop, no flip).  The filters are "bilinear" (the segmentation data sets) or
     "lanczos" (the matcher's: MegaDepth / RobotCarMatching readers and `test:` sections).
+    label_lut: a 256-entry uint8 table the label map's codes go through (RobotCar's raw ids -> train ids), fused into the label's
+    first NEAREST resize, or one launch at the file's size when there is none.
     __call__(image, semantic=None, image_ref=None, corr_pts=None, corr_pts_ref=None) -> {"image" (1, 3, h, w) fp32
     [, "image_ref"][, "semantic" (1, h', w') int64][, "corr_pts" / "corr_pts_ref": [(n, 2) fp32]]}; images are (H, W, 3) uint8,
     the label (H, W) uint8, host arrays / tensors (uploaded) or device tensors.  The points are (n, 2) fp32 (x, y) of `image`
@@ -381,7 +407,9 @@ class EvalIngest:
     back as one-element lists, the way the reference's my_collate batches them."""
 
     def __init__(self, dims=None, resize=None, img_only=False, mean=IMNET_MEAN, std=IMNET_STD, only_if_larger=False, device=None,
-                 interpolation="bilinear", dims_interpolation="bilinear", pad=None):
+                 interpolation="bilinear", dims_interpolation="bilinear", pad=None, label_lut=None):
+        self.label_lut = label_lut                                  # 256 uint8 codes (host or device): see label()
+        self._lut_dev = {}
         self.device = torch.device(device) if device is not None else None      # None: the input's device, else the current one
         self.dims = None if dims is None else (int(dims[0]), int(dims[1]))
         self.resize, self.img_only, self.only_if_larger = resize, bool(img_only), bool(only_if_larger)
@@ -427,15 +455,27 @@ class EvalIngest:
         (h, w), filt = chain[-1][:2] if chain else ((x.shape[0], x.shape[1]), "bilinear")
         return resize_crop_flip_normalize(x, (h, w), 0, 0, h, w, False, None, self.mean, self.std, filt, pad_to).unsqueeze(0)
 
+    def _lut(self, device):
+        if self.label_lut is None:
+            return None
+        if device not in self._lut_dev:
+            self._lut_dev[device] = device_lut(self.label_lut, device)
+        return self._lut_dev[device]
+
     def label(self, label_u8):
+        """label_lut: the file's codes are encoded (lut[label]) by the first resize's launch, as the reader does in front of its
+        load-time resize; with no resize to do it is one launch of its own at the file's size"""
         y = self._upload(label_u8)
+        lut = self._lut(y.device)
         steps = (self.dims,) if self.img_only else (self.dims, self.resize)
         for step in steps:
             if step is None:
                 continue
             size = target_size(y.shape[0], y.shape[1], step, self.only_if_larger) if step is self.resize else step
             if tuple(size) != tuple(y.shape):
-                y = resize_nearest_u8(y, size)
+                y, lut = resize_nearest_u8(y, size, lut), None
+        if lut is not None:
+            y = resize_nearest_u8(y, tuple(y.shape), lut)
         return y.to(torch.int64).unsqueeze(0)
 
     def points(self, pts, h, w):

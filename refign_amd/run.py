@@ -16,8 +16,9 @@ Trainer(graph_step=True): the matcher's training step replayed from one hipGraph
              `checkpoints` under the TensorBoard logger's directory, or to ./checkpoints
   validate / test / predict   the split's loaders; predict writes under --save_dir (default: the current directory) at the data
              set's original size (the matcher has no predict: config.OutOfScopeError)
-A data set without a reader here makes the split that names it fail with config.OutOfScopeError; --datasets picks the ones
-to run (`test` of the Dark Zurich configurations: --datasets DarkZurich)."""
+Every segmentation configuration the reference ships runs this way, and every section of each (cityscapes_robotcar: the
+semi-supervised three-loader recipe; `test` of the Dark Zurich configurations: DarkZurich, NighttimeDriving, BDD100kNight);
+--datasets picks sections.  A data set without a reader makes the split that names it fail with config.OutOfScopeError."""
 import argparse
 import os
 import random
@@ -59,7 +60,8 @@ def parse_args(argv):
     p.add_argument("command", choices=("fit", "validate", "test", "predict"))
     p.add_argument("--config", required=True, help="a configuration of the reference (YAML)")
     p.add_argument("--data_dir", default=os.environ.get("DATA_DIR"),
-                   help="holds Cityscapes/, ACDC/, DarkZurich/; for the matcher MegaDepth/, RobotCarMatching/ ($DATA_DIR)")
+                   help="holds Cityscapes/, ACDC/, DarkZurich/, RobotCar/, NighttimeDriving/, BDD100kNight/; for the matcher MegaDepth/, "
+                        "RobotCarMatching/ ($DATA_DIR)")
     p.add_argument("--ckpt_path", default=None, help="a checkpoint of Trainer.save_checkpoint (or Lightning's layout) to start from")
     p.add_argument("--save_dir", default=None)
     p.add_argument("--set", dest="edits", action="append", default=[], metavar="dotted.key=value")
